@@ -1,10 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric: images/sec at 896x640 (W x H), MobileNet-v1 RetinaNet,
-on N MI355X of one node (weak scaling: a fixed shard of images per GPU), plus the p50
-per-image latency of the reference's own batch-1 protocol and, at N = 1, BASELINE config 4
+on N MI355X of one node (weak scaling: a fixed shard of images per GPU); with --full also the
+p50 per-image latency of the reference's own batch-1 protocol and, at N = 1, BASELINE config 4
 (ShuffleNet-v2 + FPN, 640x640, batch 64) as a second object on the same line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the
+per-kernel / roofline figures of those same K steps.  Everything that takes runs of its own (the
+compute / all-gather split, the sustained-rate leg, the other precision mode, the host-fed rate, the
+batch-1 and mixed-size latencies, config 4, the CPU baseline, the live rocprofv3 traffic passes) runs
+only with `--full`.  `--dump-outputs DIR` writes the detections of the last timed step as .npy files.
 
 `--gpus N` with N > 1 starts itself under `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N` (a child process, before anything touches the GPU) unless it already runs
@@ -16,7 +22,7 @@ One step = one pass of the whole hot path (uint8 frames already resident in HBM 
 RCCL all-gather of the detection records) over one batch of synthetic frames per GPU.
 `value` is measured in the reference's arithmetic: every convolution an exact fp32 chain
 (precision mode f32, bit-identical to the CPU oracle).  The opt-in mode f16x3 is reported
-beside it as `other_precision`, never as `value`.  Prints ONE JSON line on rank 0.
+beside it as `other_precision` (--full), never as `value`.  Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -254,7 +260,7 @@ def measure_traffic_live(config, timeout_s=90):
     if not os.path.exists(prof):
         return None, 0, "rocprofv3 not found"
     out = tempfile.mkdtemp(prefix="ssd_traffic_", dir="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-latency", "--no-traffic",
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-latency", "--no-traffic",
              "--sustained-seconds", "0", "--no-other-precision", "--no-shufflenet", "--config", config]
     env = dict(os.environ, TMPDIR="/tmp")
     means = {}
@@ -495,6 +501,26 @@ def sustained_leg(step, images_per_step, device, seconds, window=5.0):
                     "K-step number of the contract"}
 
 
+DUMP_NAMES = ("boxes", "labels", "scores", "num_boxes")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, out):
+    """The four results of the last timed step (the gathered global batch: boxes [N,T,4], labels [N,T], scores [N,T],
+    num_boxes [N]) as DIR/<name>.npy in float32 -- labels and counts are small integers, exact in float32.  Over
+    DUMP_MAX_BYTES in all, a fixed seeded sample of images is written instead and its indices as DIR/sample_index.npy."""
+    arrs = [t.detach().cpu().numpy().astype(np.float32) for t in out]
+    n = arrs[0].shape[0]
+    per_image = sum(a.nbytes for a in arrs) // max(n, 1)
+    os.makedirs(directory, exist_ok=True)
+    if per_image * n > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // per_image, replace=False))
+        arrs = [a[keep] for a in arrs]
+        np.save(os.path.join(directory, "sample_index.npy"), keep.astype(np.float64))
+    for name, a in zip(DUMP_NAMES, arrs):
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def shufflenet_leg(local, timed, steps, warmup, batch):
     """BASELINE config 4: ShuffleNet-v2 + FPN (config_shufflenet.json), 640x640, batch 64, one GPU."""
     Wt = ssd_amd.synthetic_weights(PARAMS_SHUFFLE, seed=0, logits_bias=LOGITS_BIAS["shufflenet"])
@@ -548,7 +574,14 @@ def main(argv=None, engine_factory=None, backend="nccl", script=None):
     ap.add_argument("--config", choices=["mobilenet", "shufflenet"], default="mobilenet",
                     help="mobilenet (default) = BASELINE.json's metric: config_mobilenet.json at 640x896.  shufflenet = BASELINE config 4 "
                          "(config_shufflenet.json, 640x640, default --batch 64) as the line's workload: for profiling that network "
-                         "alone; the default run already carries it as the shufflenet_config4 object")
+                         "alone; a --full run already carries it as the shufflenet_config4 object")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the K timed steps: the compute / all-gather split, the sustained-rate "
+                         "leg, the other precision mode, the host-fed rate, the batch-1 and mixed-size latencies, config 4, the "
+                         "CPU baseline and the live rocprofv3 traffic passes (each still subject to its --no-* switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the detections of the last one (boxes, labels, scores, num_boxes of the "
+                         "global batch) as DIR/<name>.npy in float32; same arguments = same inputs, run to run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-traffic", action="store_true",
                     help="do not re-measure roofline.traffic with two rocprofv3 --pmc child runs at the end (N = 1, mode f32; ~40 s); the "
@@ -650,8 +683,13 @@ def main(argv=None, engine_factory=None, backend="nccl", script=None):
     per_rank_ms = [t / args.steps * 1e3 for t in timed.per_rank_s]
     # where a step goes, per rank: compute up to the engine's last kernel, then the all-gather (with its wait for the slowest rank)
     out = [t.clone() for t in out]
-    comp_ms, coll_ms = timed.breakdown(lambda mark: ssd_amd.detect_sharded(engine, frames, total=total, force=use_dist, on_forward_done=mark),
-                                       min(5, max(2, args.steps)), stub)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    comp_ms = coll_ms = None
+    if args.full:
+        comp_ms, coll_ms = timed.breakdown(lambda mark: ssd_amd.detect_sharded(engine, frames, total=total, force=use_dist, on_forward_done=mark),
+                                           min(5, max(2, args.steps)), stub)
+
     def status_all_ranks():
         """bit 0: an f16x3 activation left the fp16 range on SOME rank since the last call (0 in mode f32)."""
         v = engine.status()
@@ -663,13 +701,13 @@ def main(argv=None, engine_factory=None, backend="nccl", script=None):
 
     status_value = status_all_ranks()
     sustained = None
-    if world == 1 and not use_dist and not stub and args.sustained_seconds > 0:
+    if args.full and world == 1 and not use_dist and not stub and args.sustained_seconds > 0:
         sustained = sustained_leg(step, total, dev, args.sustained_seconds)
 
     # the same workload in the other precision mode, same process, same frames (shorter run)
     other = "f32" if args.precision == "f16x3" else "f16x3"
     other_res = None
-    if not args.no_other_precision and not stub:
+    if args.full and not args.no_other_precision and not stub:
         engine.set_precision(other)
         n_other = max(3, args.steps // 2)
         out = [t.clone() for t in out]       # (collective path: detect_sharded's results are views of its receive buffers)
@@ -693,7 +731,7 @@ def main(argv=None, engine_factory=None, backend="nccl", script=None):
         engine.set_precision(args.precision)
 
     pcie_img_s = None
-    if not stub:
+    if args.full and not stub:
         # the same step with the boundary's host buffers in the loop (pinned host frames -> HBM,
         # detections -> host); reported beside `value`, never as `value`
         host_frames = frames.cpu().numpy()
@@ -726,14 +764,9 @@ def main(argv=None, engine_factory=None, backend="nccl", script=None):
             "data": "synthetic" if not stub else "STAND-IN ENGINE (launcher test, no GPU work)",
             "ranks_seen": ranks_seen, "collective_path": bool(use_dist), "numa_node_bound": numa_node,
             # what a scaling loss would be made of (SCALE_rNN.json is the driver's; this line must explain it): every rank's own
-            # time for the K timed steps (ms_per_step is their MAX), and from a few extra steps with an event between the engine's
-            # forward and the collective: compute and all-gather per rank.  A rank whose compute is short waits in ITS all-gather
-            # for the slowest one: rank skew shows as a spread in per_rank_compute_ms_per_step, the collective's own cost as
-            # min(per_rank_allgather_ms_per_step).
+            # time for the K timed steps (ms_per_step is their MAX), and with --full, from a few extra steps with an event between
+            # the engine's forward and the collective: compute and all-gather per rank (below).
             "per_rank_ms_per_step": per_rank_ms,
-            "per_rank_compute_ms_per_step": comp_ms, "per_rank_allgather_ms_per_step": coll_ms,
-            "compute_ms_per_step": max(comp_ms), "allgather_ms_per_step": max(coll_ms),
-            "allgather_ms_per_step_min_over_ranks": min(coll_ms),
             "allgather_bytes_per_rank": (hi - lo) * (6 * params["num_classes"] * params["max_boxes_per_class"] + 1) * 4,
             "engine_first_forward_before_process_group": first_forward_before_pg,
             "hardware_queue_note": "the engine's internal streams are created by its first forward; run before RCCL creates its streams "
@@ -750,23 +783,30 @@ def main(argv=None, engine_factory=None, backend="nccl", script=None):
                        "library_options": args.option,
                        "detections_per_image": det_per_image},
         }
+        if comp_ms is not None:
+            # a rank whose compute is short waits in ITS all-gather for the slowest one: rank skew shows as a spread in
+            # per_rank_compute_ms_per_step, the collective's own cost as min(per_rank_allgather_ms_per_step)
+            res.update({"per_rank_compute_ms_per_step": comp_ms, "per_rank_allgather_ms_per_step": coll_ms,
+                        "compute_ms_per_step": max(comp_ms), "allgather_ms_per_step": max(coll_ms),
+                        "allgather_ms_per_step_min_over_ranks": min(coll_ms)})
         if not stub:
             ms, rates = kernel_tables(prof, args.steps)
             res["roofline"] = roofline_block(prof, args.precision, args.steps, None if net == "mobilenet" else "shufflenet_" + args.precision)
             res["kernel_ms_per_step"], res["kernel_rates"] = ms, rates
-            res["pcie_inclusive_img_s_per_gpu"] = pcie_img_s
-            res["pcie_inclusive"] = {"img_s_per_gpu": pcie_img_s, "ratio_to_resident": pcie_img_s * world / (total * args.steps / dt),
-                                     "outputs_equal_resident_run": pcie_ok,
-                                     "path": "Detector.detect_stream: host uint8 batches -> pinned staging -> H2D on a copy stream, "
-                                             "forward, packed D2H on a second copy stream, numpy out; copies of batches k+1 / k-1 under "
-                                             "the compute of batch k; rate between interior results of a warmed-up pass"}
+            if pcie_img_s is not None:
+                res["pcie_inclusive_img_s_per_gpu"] = pcie_img_s
+                res["pcie_inclusive"] = {"img_s_per_gpu": pcie_img_s, "ratio_to_resident": pcie_img_s * world / (total * args.steps / dt),
+                                         "outputs_equal_resident_run": pcie_ok,
+                                         "path": "Detector.detect_stream: host uint8 batches -> pinned staging -> H2D on a copy stream, "
+                                                 "forward, packed D2H on a second copy stream, numpy out; copies of batches k+1 / k-1 under "
+                                                 "the compute of batch k; rate between interior results of a warmed-up pass"}
             # 1.113 ms/img at the per-layer roofline of the exact-fp32 arithmetic
             res["whole_net_roofline_frac"] = ROOFLINE_MS[net] * (hi - lo) / ms_step if args.precision == "f32" else None
             if sustained:
                 res["sustained"] = sustained
             if other_res:
                 res["other_precision"] = other_res
-            if not args.no_latency:
+            if args.full and not args.no_latency:
                 lat = {}
                 for mode in ("f32", "f16x3"):
                     engine.set_precision(mode)
@@ -778,12 +818,12 @@ def main(argv=None, engine_factory=None, backend="nccl", script=None):
                 if args.precision == "f32":
                     res["latency_mixed_sizes"] = latency_mixed_sizes(detector)
                     res["throughput_mixed_sizes"] = throughput_mixed_sizes(detector)
-            if world == 1 and not args.no_shufflenet:
+            if args.full and world == 1 and not args.no_shufflenet:
                 engine.close()
                 res["shufflenet_config4"] = shufflenet_leg(local, timed, max(3, args.steps // 2), 2, 64)
-            if not args.no_cpu_baseline:          # (rank 0 at any world size: ~12 s of host time while the other ranks wait at the barrier)
+            if args.full and not args.no_cpu_baseline:          # (rank 0 at any world size: ~12 s of host time while the other ranks wait at the barrier)
                 res["cpu_baseline"] = cpu_baseline()
-            if world == 1 and not use_dist and args.precision == "f32" and not args.no_traffic:
+            if args.full and world == 1 and not use_dist and args.precision == "f32" and not args.no_traffic:
                 # LAST: every timed leg is done; the children profile the same workload while this process sits idle
                 try:
                     engine.close()

@@ -1,7 +1,7 @@
 """Debug aid: bench.py with Engine.detect_stream's host-side blocking points time-stamped for the first batches (stderr).
 Round 6 finding: the first two batches of a batch shape spend ~0.15 s each creating their buffer set (pinning 32 MB of host memory),
 during which finished results wait to be collected -- bench.py's pcie_inclusive leg now warms the stream up and times interior results.
-    python scripts/experiments/bench_pcie_debug.py --no-shufflenet --no-cpu-baseline --no-latency --sustained-seconds 0 > /dev/null"""
+    python scripts/experiments/bench_pcie_debug.py --full --no-shufflenet --no-cpu-baseline --no-latency --sustained-seconds 0 > /dev/null"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)

@@ -234,7 +234,7 @@ def test_bench_collective_path_on_rccl_world_1(cuda):
     with RCCL.  Functional asserts only: no wall-clock ratio is asserted anywhere under tests/ (boxes of the pool differ
     by 1-2 % and a noisy lease must not turn the parity rows behind this file into "untested"); the two throughputs are
     printed side by side by scripts/ab_dist.sh instead."""
-    common = ["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-latency", "--no-shufflenet", "--no-other-precision", "--sustained-seconds", "0"]
+    common = ["--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-latency", "--no-shufflenet", "--no-other-precision", "--sustained-seconds", "0"]
     plain = _bench(common)
     # the form the driver uses for N > 1, at N = 1: torch.distributed.run sets WORLD_SIZE = 1 and the collective path runs
     # (bench.py --force-dist is the same path without the launcher; scripts/ab_dist.sh uses it)
