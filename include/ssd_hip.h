@@ -372,6 +372,59 @@ int ssd_postprocess(const float *logits_dev, const float *codes_dev, const float
                     int32_t *num_boxes_dev, void *workspace_dev, size_t workspace_bytes,
                     void *stream);
 
+/* ---- the EVAL loss: model.py:79-104 in mode EVAL (train.py:61-65), without the regularisation term (host side) ----
+ *
+ * Matching (training_target_creation.py:48-130), targets (:133-176, box_utils.py:80-113) and the focal / smooth-L1 losses
+ * (losses.py, ssd.py:71-133) on the GPU.  Every TF op is one fp32 op (no contraction); exp / log / log1p / sigmoid / pow
+ * are correctly rounded (evaluated in double, rounded once); a reduce_sum is evaluated in double and rounded once, in a
+ * fixed order: two calls give the same bits.
+ *
+ * Tie rule (single-sourced here, like the NMS order): TF's GPU argmax pins no tie order, this library takes the FIRST
+ * index on ties -- per anchor the smallest gt index among those of maximal IoU, per gt the smallest anchor index among
+ * those of maximal IoU (a gt whose IoUs are all 0 picks anchor 0).  The forced match of an anchor is the smallest gt that
+ * picked it, whether or not that gt passes `iou >= 0.1`; it applies when ANY gt that picked it passes, and it overrides
+ * whatever the anchor matched before (the collision of :69 is reproduced, not repaired).  An image with no gt: every
+ * anchor -1.
+ *
+ * Arguments common to both entry points, all device memory of the caller:
+ *   anchors_dev [N,4]     the UNCLIPPED anchors (AnchorGenerator, anchor_generator.py:116-117)
+ *   gt_boxes_dev [B,G,4]  ymin,xmin,ymax,xmax in the frame of the anchors (box_scaler applied, pipeline.py:103-109)
+ *   gt_labels_dev [B,G]   int32 in [0, C); gt_num_dev [B] int32: rows of image b used (clamped to [0, G])
+ *   anchors_dev, gt_boxes_dev, codes_dev and reg_targets_dev 16-byte aligned (SSD_ERR_INVALID otherwise); G <= 4096.
+ * Stream ordering the caller owes: both calls only ENQUEUE work on `stream`.  Tensors copied out of a handle
+ * (ssd_get_tensor_dev) are ordered by that copy's stream.  A caller that points logits_dev / codes_dev straight at a
+ * handle's retained tensors must enqueue on the stream of the NEXT forward of that handle, which starts behind it
+ * (plan.hip enqueue_forward): on another stream the next forward may overwrite the arena while the loss reads it. */
+#define SSD_LOSS_MAX_GT 4096
+#define SSD_LOSS_MAX_LEVELS 8
+typedef struct ssd_loss_config {
+    double alpha;                  /* "alpha" (losses.py:39-43: alpha * x in fp32(alpha), (1 - alpha) formed in double) */
+    float gamma;                   /* "gamma": tf.pow(1 - p_t, gamma)                                                    */
+    float positives_threshold;     /* POSITIVES_THRESHOLD = 0.5 (constants.py:25)                                        */
+    float negatives_threshold;     /* NEGATIVES_THRESHOLD = 0.5 (constants.py:26); < positives: -2 (ignore) in between   */
+    int32_t n_levels;              /* 0 .. SSD_LOSS_MAX_LEVELS: entries of anchors_per_level (sum == N when > 0)          */
+    int64_t anchors_per_level[SSD_LOSS_MAX_LEVELS];    /* num_anchors_per_feature_map (ssd.py:31-35)                    */
+} ssd_loss_config;
+
+size_t ssd_loss_workspace_bytes(int32_t B, int32_t N, int32_t G);
+/* SSD._create_targets (ssd.py:165-199) = get_training_targets per image: reg_targets_dev f32 [B,N,4] (ty,tx,th,tw),
+ * cls_targets_dev i32 [B,N] (label + 1, 0 = background), matches_dev i32 [B,N] (gt index, -1 negative, -2 ignore).
+ * Each output may be NULL.  cfg: the thresholds (gamma, alpha and the levels are not read). */
+int ssd_training_targets(const float *anchors_dev, int32_t N, const float *gt_boxes_dev, const int32_t *gt_labels_dev,
+                         const int32_t *gt_num_dev, int32_t B, int32_t G, const ssd_loss_config *cfg,
+                         float *reg_targets_dev, int32_t *cls_targets_dev, int32_t *matches_dev,
+                         void *workspace_dev, size_t workspace_bytes, void *stream);
+/* SSD.loss (ssd.py:71-133) on logits_dev [B,N,C] and codes_dev [B,N,4] (raw_predictions).
+ *   per_image_dev f32 [B, 3 + n_levels]: localization sum, classification sum, matches, matches per level
+ *                 (the image's own normaliser is max(matches, 1): EVAL runs at batch 1, pipeline.py:22-27)
+ *   losses_dev f32 [2]: localization_loss, classification_loss, each / max(matches over the batch, 1) (ssd.py:120-133)
+ *   cls_losses_dev, loc_losses_dev f32 [B,N] or NULL: the per-anchor losses (focal_loss / localization_loss outputs)
+ * per_image_dev and losses_dev may be NULL too. */
+int ssd_loss(const float *logits_dev, const float *codes_dev, const float *anchors_dev, int32_t B, int32_t N, int32_t C,
+             const float *gt_boxes_dev, const int32_t *gt_labels_dev, const int32_t *gt_num_dev, int32_t G,
+             const ssd_loss_config *cfg, float *per_image_dev, float *losses_dev, float *cls_losses_dev,
+             float *loc_losses_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

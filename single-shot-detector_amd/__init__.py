@@ -7,7 +7,7 @@ C ABI of include/ssd_hip.h (csrc/libssd_hip.so, loaded with ctypes).  PyTorch is
 for device memory, streams and torch.distributed.  There is NO CPU fallback: every op
 raises if the HIP library is missing or no GPU is present.
 """
-from .config import load_config, INFERENCE_KEYS                       # noqa: F401
+from .config import load_config, INFERENCE_KEYS, load_loss_config, LOSS_KEYS   # noqa: F401
 from .variables import (variable_shapes, synthetic_weights, save_weights,   # noqa: F401
                         load_weights)
 from .pb_import import read_frozen_graph, load_pb_weights             # noqa: F401
@@ -15,7 +15,8 @@ from .ckpt_import import (read_checkpoint, read_checkpoint_index, resolve_checkp
                           load_ckpt_weights, crc32c)
 from ._lib import build, lib, lib_path, SsdError, set_option, get_option                       # noqa: F401
 from .ssd import (SSD, AnchorGenerator, RetinaNetFeatureExtractor, RetinaNetBoxPredictor,     # noqa: F401
-                  batch_multiclass_non_max_suppression, network_input_size, Engine)
+                  batch_multiclass_non_max_suppression, network_input_size, Engine,
+                  get_training_targets, ssd_loss)
 from .detector import Detector                                         # noqa: F401
-from . import coco_eval, coco_metric                                   # noqa: F401
+from . import coco_eval, coco_metric, tfrecords                        # noqa: F401  (evaluation: `python -m ssd_amd.evaluation`, imported on use)
 from .distributed import shard_range, all_gather_detections, detect_sharded, bind_to_gpu_numa_node  # noqa: F401

@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
-            "elementwise.hip", "postprocess.hip"]
+            "elementwise.hip", "postprocess.hip", "loss.hip"]
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
 _lib = None
@@ -119,6 +119,13 @@ class SsdConfig(ctypes.Structure):
                 ("min_dimension", ctypes.c_int32), ("device", ctypes.c_int32)]
 
 
+class SsdLossConfig(ctypes.Structure):
+    """ssd_loss_config of include/ssd_hip.h."""
+    _fields_ = [("alpha", ctypes.c_double), ("gamma", ctypes.c_float), ("positives_threshold", ctypes.c_float),
+                ("negatives_threshold", ctypes.c_float), ("n_levels", ctypes.c_int32),
+                ("anchors_per_level", ctypes.c_int64 * 8)]
+
+
 # every symbol include/ssd_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ssd_create": (ctypes.c_int, [ctypes.POINTER(SsdConfig), ctypes.POINTER(_vp)]),
@@ -169,6 +176,11 @@ SIGNATURES = {
     "ssd_postprocess_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i]),
     "ssd_postprocess": (ctypes.c_int, [_vp, _vp, _vp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                                        _i, _f, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_loss_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "ssd_training_targets": (ctypes.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, ctypes.POINTER(SsdLossConfig),
+                                            _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_loss": (ctypes.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, ctypes.POINTER(SsdLossConfig),
+                                _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 

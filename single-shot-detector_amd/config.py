@@ -37,3 +37,20 @@ def load_config(path_or_dict):
     out["max_boxes_per_class"] = int(out["max_boxes_per_class"])
     out["min_dimension"] = int(out["min_dimension"])
     return out
+
+
+LOSS_KEYS = ("gamma", "alpha", "localization_loss_weight", "classification_loss_weight", "weight_decay")
+
+
+def load_loss_config(path_or_dict):
+    """The keys of the reference's JSON config that the EVAL loss reads (model.py:80-104, ssd.py:102-103): a dict with
+    exactly LOSS_KEYS as floats.  load_config / INFERENCE_KEYS are unaffected."""
+    if isinstance(path_or_dict, dict):
+        raw = dict(path_or_dict)
+    else:
+        with open(path_or_dict) as f:
+            raw = json.load(f)
+    missing = [k for k in LOSS_KEYS if k not in raw]
+    if missing:
+        raise KeyError("config is missing the key %r" % missing[0])
+    return {k: float(raw[k]) for k in LOSS_KEYS}

@@ -67,6 +67,9 @@ class Detector:
         device = int(str(visible_device_list).split(",")[0])
         self.engine = Engine(self.params, weights, device=device, precision=precision)
         self.device = device
+        self._config = config
+        from .evaluation import l2_sum
+        self._l2_sum = l2_sum(weights)       # model.py:132-145 over the loaded (with use_ema: averaged) variables
 
     def close(self):
         """Frees the engine's device memory (weights, every cached layer plan, staging buffers) now instead of at garbage
@@ -169,6 +172,29 @@ class Detector:
                 yield self.detect_batch(images)
             return
         yield from self.engine.detect_stream(batches)
+
+    def regularization_loss(self, weight_decay):
+        """model.py:80-81 for the loaded weights: weight_decay * sum of l2_loss over the regularised kernels (float64,
+        rounded to float32 once)."""
+        return np.float32(float(weight_decay) * self._l2_sum)
+
+    def loss(self, image, boxes, labels, config=None):
+        """The EVAL step of train.py for ONE image (model.py:79-104 at batch 1, pipeline.py:22-27): image uint8
+        [height, width, 3]; boxes [n,4] ymin,xmin,ymax,xmax normalised to the image, labels [n] in [0, num_classes)
+        (create_tfrecords.py's groundtruth).  config: the JSON with the loss keys (config.load_loss_config), default
+        the Detector's own.  Returns {'loss' (total_loss), 'localization_loss', 'classification_loss',
+        'regularization_loss'} as float32 numbers."""
+        from .config import load_loss_config
+        from .evaluation import _Run, image_losses
+        lc = load_loss_config(self._config if config is None else config)
+        image = np.asarray(image)
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("image must be a uint8 array of shape [height, width, 3]")
+        reg = self.regularization_loss(lc["weight_decay"])
+        with self.engine.lock:
+            row = _Run(self.engine)([image], [(np.asarray(boxes, np.float32).reshape(-1, 4), np.asarray(labels).reshape(-1))], lc)[0][0]
+        loc, cls, tot = image_losses(row, reg, lc)
+        return {"loss": tot, "localization_loss": loc, "classification_loss": cls, "regularization_loss": reg}
 
     def __call__(self, image, score_threshold=0.1):
         """

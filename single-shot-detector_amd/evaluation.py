@@ -1,0 +1,202 @@
+"""train.py's evaluation (train.py:61-65: EvalSpec over the validation shards, model.py:79-104 in mode EVAL) without
+TensorFlow: the validation loss of a checkpoint and the VOC-style AP of metrics.py.
+
+    python -m ssd_amd.evaluation MODEL_PATH --config config.json [--val_dataset DIR] [--use_ema]
+
+EVAL runs at batch 1 (pipeline.py:22-27), so every image is normalised by its OWN matches; `loss` is the mean over
+images of total_loss = localization_loss_weight * localization + classification_loss_weight * classification +
+regularization (model.py:79-104), what estimator.evaluate reports.  Here the images are grouped by the size the network
+sees and run as mixed-size batches (Engine.forward_mixed), the loss kernels (ssd_loss) give the per-image sums, and the
+predictions come from the same retained tensors through batch_multiclass_non_max_suppression WITHOUT the division by
+box_scaler (model.py divides in PREDICT only): the groundtruth boxes are multiplied by box_scaler instead
+(pipeline.py:103-109), and both meet in the padded frame.
+"""
+import os
+
+import numpy as np
+
+from .coco_eval import Evaluator
+from .config import load_loss_config
+from .ssd import AnchorGenerator, batch_multiclass_non_max_suppression, network_input_size, ssd_loss, _torch
+
+_METRIC_NAMES = ("AP", "precision", "recall", "mean_iou_for_TP", "best_threshold", "total_FP", "total_FN")   # metrics.py:84-100
+
+
+def l2_sum(weights):
+    """The sum of tf.nn.l2_loss(K) (= sum(K^2) / 2) over the variables add_weight_decay regularises (model.py:132-145: the
+    names containing 'weights' or 'kernel' but not 'depthwise_weights'), in float64."""
+    s = 0.0
+    for name in sorted(weights):
+        if ("weights" in name or "kernel" in name) and "depthwise_weights" not in name:
+            k = np.asarray(weights[name], np.float64).reshape(-1)
+            s += float(np.dot(k, k)) / 2.0
+    return s
+
+
+def regularization_loss(weights, weight_decay):
+    """model.py:80-81: weight_decay * l2_sum(weights), evaluated in float64 and rounded to float32 once."""
+    return np.float32(float(weight_decay) * l2_sum(weights))
+
+
+def total_loss(localization, classification, regularization, loss_config):
+    """tf.losses.get_total_loss (model.py:100-104) of one image: each weighted term one fp32 product, their sum in
+    float64 rounded once."""
+    lw = np.float32(loss_config["localization_loss_weight"]) * np.float32(localization)
+    cw = np.float32(loss_config["classification_loss_weight"]) * np.float32(classification)
+    return np.float32(float(lw) + float(cw) + float(regularization))
+
+
+class _Run:
+    """The loss + predictions of one mixed-size batch of decoded frames on one engine."""
+
+    def __init__(self, engine):
+        self.engine = engine
+        self.anchors = {}
+
+    def anchors_for(self, shape):
+        a = self.anchors.get(shape)
+        if a is None:
+            gen = AnchorGenerator()
+            t = _torch().from_numpy(gen(*shape)).to("cuda:%d" % self.engine.device)
+            a = self.anchors[shape] = (t, list(gen.num_anchors_per_feature_map))
+        return a
+
+    def __call__(self, frames, gts, loss_config):
+        """frames: uint8 arrays [H,W,3] of one network shape; gts: (boxes [n,4] normalised to the frame, labels [n]).
+        -> per image (localization, classification, matches) and the predictions (boxes, labels, scores) trimmed to
+        num_boxes, boxes in the padded frame."""
+        torch = _torch()
+        eng, p = self.engine, self.engine.params
+        dev = "cuda:%d" % eng.device
+        shape = eng.network_shape(frames[0].shape[0], frames[0].shape[1])
+        anchors, per_level = self.anchors_for(shape)
+        B, N, C = len(frames), int(anchors.shape[0]), int(p["num_classes"])
+        eng.forward_mixed([torch.from_numpy(np.require(f, np.uint8, ["C", "W"])).to(dev) for f in frames])
+        logits = eng.get_tensor_dev("class_predictions", (B, N, C))
+        codes = eng.get_tensor_dev("encoded_boxes", (B, N, 4))
+        G = max(1, max(len(g[1]) for g in gts))
+        boxes = np.zeros((B, G, 4), np.float32)
+        labels = np.zeros((B, G), np.int32)
+        num = np.zeros((B,), np.int32)
+        scaled = []
+        for b, (f, (gb, gl)) in enumerate(zip(frames, gts)):
+            bs = network_input_size(f.shape[0], f.shape[1], p["min_dimension"])[2]
+            s = np.asarray(gb, np.float32).reshape(-1, 4) * bs                      # pipeline.py:109, float32
+            scaled.append(s)
+            boxes[b, :len(s)] = s
+            labels[b, :len(s)] = gl
+            num[b] = len(s)
+        _losses, per_image = ssd_loss(logits, codes, anchors, {"boxes": boxes, "labels": labels, "num_boxes": num},
+                                      gamma=loss_config["gamma"], alpha=loss_config["alpha"], anchors_per_level=per_level)
+        pb, ps, pc, pn = batch_multiclass_non_max_suppression(codes, anchors, logits, p["score_threshold"], p["iou_threshold"],
+                                                              p["max_boxes_per_class"], box_scaler=None)
+        per_image, pb, ps, pc, pn = (t.cpu().numpy() for t in (per_image, pb, ps, pc, pn))
+        out = []
+        for b in range(B):
+            n = int(pn[b])
+            out.append((per_image[b, :3], scaled[b], (pb[b, :n], pc[b, :n], ps[b, :n])))
+        return out
+
+
+def image_losses(per_image_row, regularization, loss_config):
+    """(localization, classification, total) of one image at batch 1 from its ssd_loss per_image row."""
+    norm = max(np.float32(per_image_row[2]), np.float32(1.0))
+    loc = np.float32(per_image_row[0]) / norm
+    cls = np.float32(per_image_row[1]) / norm
+    return loc, cls, total_loss(loc, cls, regularization, loss_config)
+
+
+def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, decode=None):
+    """estimator.evaluate of train.py:61-65 for `detector` (a Detector) over `val_dataset` (a directory of .tfrecords
+    shards, a shard path, or an iterable of (JPEG bytes | uint8 array, boxes [n,4], labels [n])).  config: the
+    reference's JSON (path or dict).  Returns {'loss', 'localization_loss', 'classification_loss',
+    'regularization_loss'} (means over images) and 'metrics/mAP' -- or the seven 'metrics/*' of metrics.py:84-100 when
+    num_classes == 1.  JPEGs are decoded on `read_workers` threads (default min(16, CPUs))."""
+    from concurrent.futures import ThreadPoolExecutor
+    from . import tfrecords
+    lc = load_loss_config(config)
+    eng = detector.engine
+    max_batch = max(1, min(int(max_batch), eng.MIXED_MAX))
+    reg = detector.regularization_loss(lc["weight_decay"])
+    if decode is None:
+        def decode(x):
+            if isinstance(x, np.ndarray):
+                return x
+            import io
+            from PIL import Image
+            with Image.open(io.BytesIO(x)) as im:
+                return np.asarray(im.convert("RGB"), dtype=np.uint8)
+    data = tfrecords.read_dataset(val_dataset) if isinstance(val_dataset, (str, os.PathLike)) else val_dataset
+    evaluator = Evaluator(int(eng.params["num_classes"]))
+    run = _Run(eng)
+    sums = np.zeros(4, np.float64)
+    count = 0
+    workers = max(1, int(read_workers if read_workers is not None else min(16, os.cpu_count() or 1)))
+    chunk = 256
+
+    def consume(items):
+        nonlocal count, sums
+        groups = {}
+        for i, (frame, _gb, _gl) in enumerate(items):
+            groups.setdefault(eng.network_shape(frame.shape[0], frame.shape[1]), []).append(i)
+        results = [None] * len(items)
+        for part in groups.values():
+            # batches of max_batch and its halvings only, like Detector.detect_many: one layer plan per (shape, batch size)
+            k, b = 0, max_batch
+            while k < len(part):
+                while len(part) - k < b:
+                    b //= 2
+                sub = part[k:k + b]
+                k += b
+                with eng.lock:
+                    res = run([items[i][0] for i in sub], [(items[i][1], items[i][2]) for i in sub], lc)
+                for i, r in zip(sub, res):
+                    results[i] = r
+        for (row, gt_scaled, (bx, lb, sc)), (_f, _gb, gl) in zip(results, items):      # in dataset order
+            loc, cls, tot = image_losses(row, reg, lc)
+            sums = sums + np.array([float(tot), float(loc), float(cls), float(reg)])
+            count += 1
+            evaluator.add_image(gt_scaled, gl, bx, lb, sc)
+
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        pending = []
+        for img, gb, gl in data:
+            pending.append((pool.submit(decode, img), gb, gl))
+            if len(pending) == chunk:
+                consume([(f.result(), gb_, gl_) for f, gb_, gl_ in pending])
+                pending = []
+        if pending:
+            consume([(f.result(), gb_, gl_) for f, gb_, gl_ in pending])
+    if count == 0:
+        raise ValueError("the validation dataset is empty")
+    means = sums / count
+    out = {"loss": float(np.float32(means[0])), "localization_loss": float(np.float32(means[1])),
+           "classification_loss": float(np.float32(means[2])), "regularization_loss": float(np.float32(means[3]))}
+    m = evaluator.evaluate()
+    if evaluator.num_classes == 1:
+        for k in _METRIC_NAMES:
+            out["metrics/" + k] = float(np.float32(m[0][k]))
+    else:
+        out["metrics/mAP"] = float(np.float32(m["mAP"]))
+    out["num_images"] = count
+    return out
+
+
+def main(argv=None):
+    import argparse
+    import json
+    from .detector import Detector
+    ap = argparse.ArgumentParser(description="train.py's evaluation of a checkpoint: validation loss and AP")
+    ap.add_argument("model_path", help="checkpoint prefix / model_dir / frozen graph / .npz")
+    ap.add_argument("--config", required=True, help="the reference's JSON config")
+    ap.add_argument("--val_dataset", default=None, help="directory of .tfrecords shards (default: the config's val_dataset)")
+    ap.add_argument("--use_ema", action="store_true", help="the moving averages, as RestoreMovingAverageHook restores them")
+    ap.add_argument("--max_batch", type=int, default=32)
+    a = ap.parse_args(argv)
+    val = a.val_dataset or json.load(open(a.config))["val_dataset"]
+    with Detector(a.model_path, config=a.config, use_ema=a.use_ema) as det:
+        print(json.dumps(evaluate(det, val, a.config, max_batch=a.max_batch), sort_keys=True))
+
+
+if __name__ == "__main__":
+    main()

@@ -8,7 +8,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from ._lib import SsdConfig, check, lib
+from ._lib import SsdConfig, SsdLossConfig, check, lib
 
 ACT = {None: 0, "none": 0, "relu": 1, "relu6": 2}
 
@@ -282,6 +282,87 @@ def batch_multiclass_non_max_suppression(encoded_boxes, anchors, logits, score_t
                                 int(max_boxes_per_class), bs[1], _ptr(boxes), _ptr(classes),
                                 _ptr(scores), _ptr(num), _ptr(ws), nbytes, _stream(torch)))
     return boxes, scores, classes, num
+
+
+# ----------------------------------------------------------------------------- the EVAL loss (loss.hip)
+POSITIVES_THRESHOLD = 0.5      # detector/constants.py:25-26
+NEGATIVES_THRESHOLD = 0.5
+
+
+def _loss_config(positives_threshold, negatives_threshold, gamma=2.0, alpha=0.25, anchors_per_level=()):
+    lv = [int(n) for n in anchors_per_level]
+    if len(lv) > 8:
+        raise ValueError("at most 8 anchor levels")
+    return SsdLossConfig(float(alpha), float(gamma), float(positives_threshold), float(negatives_threshold), len(lv),
+                         (ctypes.c_int64 * 8)(*lv))
+
+
+def _groundtruth(torch, boxes, labels, num_boxes, B, dev):
+    """groundtruth (numpy or torch: [B,G,4] / [B,G] / [B]) -> contiguous CUDA tensors of the kernels' dtypes."""
+    boxes = torch.as_tensor(boxes, dtype=torch.float32).to(dev).contiguous()
+    labels = torch.as_tensor(labels).to(dev, torch.int32).contiguous()
+    num_boxes = torch.as_tensor(num_boxes).to(dev, torch.int32).contiguous()
+    if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 4:
+        raise ValueError("groundtruth boxes must have shape [batch_size, max_num_boxes, 4]")
+    if tuple(labels.shape) != tuple(boxes.shape[:2]) or tuple(num_boxes.shape) != (B,):
+        raise ValueError("groundtruth labels must be [batch_size, max_num_boxes], num_boxes [batch_size]")
+    return boxes, labels, num_boxes
+
+
+def get_training_targets(anchors, groundtruth_boxes, groundtruth_labels, num_boxes,
+                         positives_threshold=POSITIVES_THRESHOLD, negatives_threshold=NEGATIVES_THRESHOLD):
+    """SSD._create_targets (ssd.py:165-199: get_training_targets of training_target_creation.py:5-45 over the batch) on
+    the GPU (ssd_training_targets).  anchors [N,4] CUDA float32 (unclipped); groundtruth_boxes [B,G,4],
+    groundtruth_labels [B,G], num_boxes [B] (numpy or torch).  The thresholds default to the values ssd.py passes
+    (constants.py:25-26).  Returns reg_targets [B,N,4] f32, cls_targets [B,N] i32, matches [B,N] i32 (CUDA tensors,
+    asynchronous on the current stream)."""
+    torch = _torch()
+    _check_dev(torch, anchors, torch.float32, "anchors")
+    N = int(anchors.shape[0])
+    dev = anchors.device
+    B = int(groundtruth_boxes.shape[0])
+    boxes, labels, num = _groundtruth(torch, groundtruth_boxes, groundtruth_labels, num_boxes, B, dev)
+    G = int(boxes.shape[1])
+    reg = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
+    cls = torch.empty((B, N), dtype=torch.int32, device=dev)
+    matches = torch.empty((B, N), dtype=torch.int32, device=dev)
+    nbytes = lib().ssd_loss_workspace_bytes(B, N, G)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    cfg = _loss_config(positives_threshold, negatives_threshold)
+    check(lib().ssd_training_targets(_ptr(anchors), N, _ptr(boxes), _ptr(labels), _ptr(num), B, G, ctypes.byref(cfg),
+                                     _ptr(reg), _ptr(cls), _ptr(matches), _ptr(ws), nbytes, _stream(torch)))
+    return reg, cls, matches
+
+
+def ssd_loss(logits, encoded_boxes, anchors, groundtruth, gamma=2.0, alpha=0.25, anchors_per_level=(), per_anchor=False,
+             positives_threshold=POSITIVES_THRESHOLD, negatives_threshold=NEGATIVES_THRESHOLD):
+    """The losses of ssd.py:71-133 on the GPU (ssd_loss).  logits [B,N,C], encoded_boxes [B,N,4], anchors [N,4] CUDA
+    float32; groundtruth = {'boxes' [B,G,4], 'labels' [B,G], 'num_boxes' [B]} (numpy or torch).
+    Returns (losses [2] = localization, classification over the batch's normaliser; per_image [B, 3 + levels] =
+    localization sum, classification sum, matches, matches per level) and with per_anchor=True also the per-anchor
+    cls_losses [B,N] and loc_losses [B,N]: CUDA tensors, asynchronous on the current stream."""
+    torch = _torch()
+    for t, n in ((logits, "logits"), (encoded_boxes, "encoded_boxes"), (anchors, "anchors")):
+        _check_dev(torch, t, torch.float32, n)
+    B, N, C = (int(v) for v in logits.shape)
+    if tuple(encoded_boxes.shape) != (B, N, 4) or tuple(anchors.shape) != (N, 4):
+        raise ValueError("shape mismatch between encoded_boxes, anchors and logits")
+    dev = logits.device
+    boxes, labels, num = _groundtruth(torch, groundtruth["boxes"], groundtruth["labels"], groundtruth["num_boxes"], B, dev)
+    G = int(boxes.shape[1])
+    cfg = _loss_config(positives_threshold, negatives_threshold, gamma, alpha, anchors_per_level)
+    losses = torch.empty((2,), dtype=torch.float32, device=dev)
+    per_image = torch.empty((B, 3 + cfg.n_levels), dtype=torch.float32, device=dev)
+    cls_l = torch.empty((B, N), dtype=torch.float32, device=dev) if per_anchor else None
+    loc_l = torch.empty((B, N), dtype=torch.float32, device=dev) if per_anchor else None
+    nbytes = lib().ssd_loss_workspace_bytes(B, N, G)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    check(lib().ssd_loss(_ptr(logits), _ptr(encoded_boxes), _ptr(anchors), B, N, C, _ptr(boxes), _ptr(labels), _ptr(num), G,
+                         ctypes.byref(cfg), _ptr(per_image), _ptr(losses), _ptr(cls_l) if per_anchor else None,
+                         _ptr(loc_l) if per_anchor else None, _ptr(ws), nbytes, _stream(torch)))
+    if per_anchor:
+        return losses, per_image, cls_l, loc_l
+    return losses, per_image
 
 
 # ----------------------------------------------------------------------------- whole graph
@@ -802,3 +883,18 @@ class SSD:
             self.raw_predictions["class_predictions"], score_threshold=score_threshold,
             iou_threshold=iou_threshold, max_boxes_per_class=max_boxes_per_class, box_scaler=self.box_scaler)
         return {"boxes": boxes, "labels": classes, "scores": scores, "num_boxes": num}
+
+    def loss(self, groundtruth, params):
+        """ssd.py:71-133: {'localization_loss', 'classification_loss'} (0-d CUDA tensors) with respect to `groundtruth` =
+        {'boxes' [B,G,4] in the frame of the network (box_scaler applied, pipeline.py:103-109), 'labels' [B,G],
+        'num_boxes' [B]}; params: 'gamma', 'alpha' (config.load_loss_config).  The batch's normaliser is max(matches over
+        the batch, 1).  Also kept, as the summaries of ssd.py:125-129 without the histograms: .localization_losses_per_image,
+        .classification_losses_per_image, .matches_per_image [B] and .matches_per_level [B, levels] (CUDA tensors)."""
+        losses, per_image = ssd_loss(self.raw_predictions["class_predictions"], self.raw_predictions["encoded_boxes"],
+                                     self.anchors, groundtruth, gamma=params["gamma"], alpha=params["alpha"],
+                                     anchors_per_level=self.num_anchors_per_feature_map)
+        self.localization_losses_per_image = per_image[:, 0]
+        self.classification_losses_per_image = per_image[:, 1]
+        self.matches_per_image = per_image[:, 2]
+        self.matches_per_level = per_image[:, 3:]
+        return {"localization_loss": losses[0], "classification_loss": losses[1]}
