@@ -61,7 +61,7 @@ def detection_records_many(detector, images, image_ids, label_to_coco_id, score_
 
 
 def evaluate(detector, annotations_json, images_dir, read_image=None, predictions_json="coco_predictions.json", out=None,
-             score_threshold=0.15, max_batch=32, read_workers=None):
+             score_threshold=0.15, max_batch=32, read_workers=None, group=None, chunk=256):
     """Cells 4-17 end to end: every image of the annotation file through the detector (score_threshold 0.15, cell 10), the
     results written as `predictions_json` (cell 11), then the twelve COCO box statistics (cell 17: COCOeval over all image and
     category ids) -- computed by coco_metric.py, this build's restatement of pycocotools' COCOeval (not installed here, not
@@ -70,7 +70,13 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     same libjpeg, which is the usual case but nothing here can check; pass the notebook's reader to be sure); `out`: a stream for
     the summary table; `read_workers`: threads that read and decode images (default min(16, CPUs): a JPEG decodes in ~5 ms on
     one core, the detector takes ~1.4 ms per image in batches -- the next chunk of files is decoded while this one is detected).
-    Returns the statistics in coco_metric.STAT_NAMES order (AP, AP50, AP75, APs, APm, APl, AR1, ...)."""
+    Returns the statistics in coco_metric.STAT_NAMES order (AP, AP50, AP75, APs, APm, APl, AR1, ...).
+
+    `group`: a torch.distributed process group to shard the images over (None: this process does everything).  The images,
+    sorted by id, go to the ranks in round-robin chunks of `chunk` (distributed.ChunkAssignment); each rank reads, decodes and
+    detects only its own, builds their result rows and runs the per-(image, category, area) matching for them
+    (CocoBoxEval.evaluate(img_ids)); one all-gather of compact arrays (the matching cells, the rows' JSON bytes) follows.  Rank
+    0 writes `predictions_json` (byte for byte the one-process file) and the table; every rank returns the same statistics."""
     import os
     from . import coco_metric
     if read_image is None:
@@ -81,23 +87,70 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     gt = json.load(open(annotations_json)) if isinstance(annotations_json, str) else annotations_json
     mapping = integer_to_coco_id(gt["categories"])
     metas = sorted(gt["images"], key=lambda m: m["id"])
-    results = []
-    chunk = 256           # images read, then detected as batches grouped by network shape (the notebook's loop, one image per sess.run, at batch throughput)
-    from concurrent.futures import ThreadPoolExecutor
     workers = max(1, int(read_workers if read_workers is not None else min(16, os.cpu_count() or 1)))
-    with ThreadPoolExecutor(max_workers=workers) as pool:
-        def start(k):      # (PIL and cv2 release the interpreter lock while they decode)
-            return [pool.submit(read_image, os.path.join(images_dir, m["file_name"])) for m in metas[k:k + chunk]]
-        ahead = start(0)
-        for k in range(0, len(metas), chunk):
-            part = metas[k:k + chunk]
-            images = [f.result() for f in ahead]
-            ahead = start(k + chunk)
-            results += detection_records_many(detector, images, [m["id"] for m in part], mapping, score_threshold, max_batch)
+    if group is not None:
+        return _evaluate_sharded(detector, gt, metas, mapping, images_dir, read_image, predictions_json, out, score_threshold,
+                                 max_batch, workers, group, chunk)
+    results = []
+    for part, images in _read_chunks(metas, images_dir, read_image, workers, chunk):
+        # images read, then detected as batches grouped by network shape (the notebook's loop, one image per sess.run, at batch throughput)
+        results += detection_records_many(detector, images, [m["id"] for m in part], mapping, score_threshold, max_batch)
     if predictions_json:
         with open(predictions_json, "w") as f:
             json.dump(results, f)
     return coco_metric.evaluate_boxes(gt, results, out=out)
+
+
+def _read_chunks(metas, images_dir, read_image, workers, chunk):
+    """(metas of a chunk, its decoded images) for consecutive chunks of `metas`; the next chunk is read while the caller
+    works on this one (PIL and cv2 release the interpreter lock while they decode)."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        def start(k):
+            return [pool.submit(read_image, os.path.join(images_dir, m["file_name"])) for m in metas[k:k + chunk]]
+        ahead = start(0)
+        for k in range(0, len(metas), chunk):
+            images = [f.result() for f in ahead]
+            ahead = start(k + chunk)
+            yield metas[k:k + chunk], images
+
+
+def _evaluate_sharded(detector, gt, metas, mapping, images_dir, read_image, predictions_json, out, score_threshold, max_batch,
+                      workers, group, chunk):
+    import torch.distributed as dist
+    from . import coco_metric
+    from .distributed import ChunkAssignment
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    assign = ChunkAssignment(world, rank, chunk)
+    mine = [m for _i, m in assign.select(metas)]
+    results, frags = [], []
+    many = getattr(detector, "detect_many", None)
+    for part, images in _read_chunks(mine, images_dir, read_image, workers, chunk):
+        dets = many(images, score_threshold=score_threshold, max_batch=max_batch) if many else [None] * len(images)
+        for image, m, d in zip(images, part, dets):
+            rows = detection_records(detector, image, m["id"], mapping, score_threshold, detections=d)
+            results += rows
+            if predictions_json:
+                frags.append(json.dumps(rows)[1:-1].encode())        # json.dump of the whole list joins these with ", "
+    ev = coco_metric.CocoBoxEval(gt, results)
+    ev.evaluate(img_ids=[m["id"] for m in mine])
+    payload = {"cells": ev.cells(), "json": np.frombuffer(b"".join(frags), np.uint8),
+               "lens": np.array([len(f) for f in frags], np.int64)}
+    got = [None] * world
+    dist.all_gather_object(got, payload, group=group)
+    for r, p in enumerate(got):
+        if r != rank:
+            ev.merge(p["cells"])
+    if predictions_json and rank == 0:
+        per_rank = []
+        for p in got:
+            blob, ends = p["json"].tobytes(), np.cumsum(p["lens"]).tolist()
+            per_rank += [blob[a:b] for a, b in zip([0] + ends[:-1], ends)]
+        frags_all = assign.to_input_order(per_rank, [assign.count(len(metas), r) for r in range(world)])
+        with open(predictions_json, "wb") as f:
+            f.write(b"[" + b", ".join(x for x in frags_all if x) + b"]")
+    return ev.accumulate().summarize(out if rank == 0 else None)
 
 
 # ----------------------------------------------------------------------------- VOC-style AP self-check

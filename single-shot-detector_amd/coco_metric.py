@@ -76,12 +76,21 @@ class CocoBoxEval:
         self.precision = self.recall = self.stats = None
 
     # -- cocoeval.py evaluate(): computeIoU + evaluateImg for every (category, area range, image)
-    def evaluate(self):
+    def evaluate(self, img_ids=None):
+        """img_ids: evaluate only these images (a subset of self.img_ids, e.g. one rank's share); the cells of the others come
+        from `merge`.  accumulate() / summarize() always run over all self.img_ids."""
         T = len(IOU_THRS)
         maxdet = MAX_DETS[-1]
         self.eval_imgs = {}
+        if img_ids is None:
+            subset = self.img_ids
+        else:
+            want = set(img_ids)
+            if not want <= set(self.img_ids):
+                raise ValueError("img_ids must be a subset of the evaluated image ids")
+            subset = [i for i in self.img_ids if i in want]
         for cat in self.cat_ids:
-            for img in self.img_ids:
+            for img in subset:
                 gts = self._gts.get((img, cat), [])
                 dts = self._dts.get((img, cat), [])
                 if not gts and not dts:
@@ -133,6 +142,38 @@ class CocoBoxEval:
                     out_of_range = (darea < lo) | (darea > hi)
                     dtig = dtig | (~dtm & out_of_range[None, :])
                     self.eval_imgs[(cat, ai, img)] = (dscore, dtm, dtig, gig_s)
+        return self
+
+    # -- the cells of evaluate() as a few flat arrays (a subset's evaluation travels between processes this way)
+    def cells(self):
+        """self.eval_imgs as numpy arrays: keys [n,3] int64 (category, area index, image), D / G [n] (detections, groundtruth
+        boxes per cell), scores [sum D] float64, matched / ignored [T, sum D] bool, gt_ignore [sum G] bool."""
+        T = len(IOU_THRS)
+        items = list(self.eval_imgs.items()) if self.eval_imgs else []
+        keys = np.array([k for k, _ in items], np.int64).reshape(-1, 3)
+        D = np.array([len(v[0]) for _, v in items], np.int64)
+        G = np.array([len(v[3]) for _, v in items], np.int64)
+        cat = (lambda xs, empty: np.concatenate(xs, axis=-1) if xs else empty)
+        return {"keys": keys, "D": D, "G": G,
+                "scores": cat([np.asarray(v[0], np.float64) for _, v in items], np.zeros(0, np.float64)),
+                "matched": cat([np.asarray(v[1], bool) for _, v in items], np.zeros((T, 0), bool)),
+                "ignored": cat([np.asarray(v[2], bool) for _, v in items], np.zeros((T, 0), bool)),
+                "gt_ignore": cat([np.asarray(v[3], bool) for _, v in items], np.zeros(0, bool))}
+
+    def merge(self, cells):
+        """Adds the cells another subset's evaluate() produced (the dict of `cells()`); the subsets must be disjoint."""
+        if self.eval_imgs is None:
+            self.eval_imgs = {}
+        d0 = np.concatenate([[0], np.cumsum(cells["D"])])
+        g0 = np.concatenate([[0], np.cumsum(cells["G"])])
+        for n, key in enumerate(cells["keys"].tolist()):
+            key = tuple(key)
+            if key in self.eval_imgs:
+                raise ValueError("cell %r evaluated twice" % (key,))
+            a, b = int(d0[n]), int(d0[n + 1])
+            self.eval_imgs[key] = (cells["scores"][a:b], cells["matched"][:, a:b], cells["ignored"][:, a:b],
+                                   cells["gt_ignore"][int(g0[n]):int(g0[n + 1])])
+        self.precision = self.recall = self.stats = None
         return self
 
     # -- cocoeval.py accumulate()

@@ -168,3 +168,224 @@ def detect_sharded(engine, images_local, group=None, total=None, force=False, on
     g3 = got.view(world, per, -1)
     rows = [g3[r, :shard_range(total, r, world)[1] - shard_range(total, r, world)[0]] for r in range(world)]
     return unpack_detections(torch.cat(rows, 0))
+
+
+# ----------------------------------------------------------------------------- mixed sizes: round-robin chunks of a stream
+def node_device_and_backend(device_count=None):
+    """The backend rule of every multi-process entry point: rank r of a node uses device
+    LOCAL_RANK % device_count; the backend is 'nccl' (RCCL, records in device memory, the all-gather in place) only when every
+    rank of the node has a device of its own (LOCAL_WORLD_SIZE <= device_count), else 'gloo' (records in pinned host memory).
+    RCCL never sees two ranks on one device.  Returns (device index, backend)."""
+    import os
+    if device_count is None:
+        device_count = torch.cuda.device_count()
+    if device_count < 1:
+        raise RuntimeError("no GPU: the HIP path has no CPU fallback")
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1")))
+    return local % device_count, ("nccl" if local_world <= device_count else "gloo")
+
+
+def init_node_process_group():
+    """init_process_group for a torch.distributed.run launch (RANK, WORLD_SIZE, MASTER_ADDR / MASTER_PORT in the environment)
+    under node_device_and_backend's rule; makes the rank's device the current one.  Returns (device index, backend)."""
+    import os
+    device, backend = node_device_and_backend()
+    torch.cuda.set_device(device)
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    if backend == "nccl":
+        dist.init_process_group(backend, rank=rank, world_size=world, device_id=torch.device("cuda", device))
+    else:
+        dist.init_process_group(backend, rank=rank, world_size=world)
+    return device, backend
+
+
+def launch_local(nproc, module, argv, env=None):
+    """`python -m MODULE --gpus N ...` typed as is: run MODULE under torch.distributed.run with `nproc` ranks on this node as
+    a CHILD process (never exec: the caller has not touched the GPU and never does) and return its exit code.  The
+    repository root goes in front of PYTHONPATH so that every rank imports this package."""
+    import os
+    import socket
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ if env is None else env)
+    env["PYTHONPATH"] = os.pathsep.join([root] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(int(nproc)),
+           "--master-addr", "127.0.0.1", "--master-port", str(port), "--module", module] + list(argv)
+    return subprocess.call(cmd, env=env)
+
+
+class ChunkAssignment:
+    """Round-robin chunks of an input stream: image i belongs to rank (i // chunk) % world.  A rank decides from the index
+    alone, so no total count is needed up front (a .tfrecords stream has none).  Round k is images [k * world * chunk,
+    (k + 1) * world * chunk): one chunk per rank; the last round may be ragged and a rank may have no image at all.  With
+    world = 1 the chunks are exactly the one-process run's chunks of `chunk` images, so batches are composed the same way.
+
+    The rows the ranks gather are in RANK order (all of rank 0's images, then rank 1's, ...); `input_index(counts)` gives the
+    input index of every such row and `to_input_order` puts the rows back in input order."""
+
+    def __init__(self, world, rank, chunk):
+        if world < 1 or not 0 <= rank < world or chunk < 1:
+            raise ValueError("need world >= 1, 0 <= rank < world, chunk >= 1 (got %r, %r, %r)" % (world, rank, chunk))
+        self.world, self.rank, self.chunk = int(world), int(rank), int(chunk)
+
+    def owner(self, i):
+        return (int(i) // self.chunk) % self.world
+
+    def mine(self, i):
+        return self.owner(i) == self.rank
+
+    def select(self, items):
+        """This rank's (input index, item) pairs of an iterable, in input order (every item is visited, only this rank's are
+        returned)."""
+        for i, x in enumerate(items):
+            if self.mine(i):
+                yield i, x
+
+    def count(self, total, rank=None):
+        """Images of `rank` (default: this one) among `total`."""
+        r = self.rank if rank is None else rank
+        full, rest = divmod(int(total), self.world * self.chunk)
+        return full * self.chunk + min(max(rest - r * self.chunk, 0), self.chunk)
+
+    def input_index(self, counts):
+        """counts[r] = images of rank r -> int64 array: the input index of every gathered row (rank order).  Raises when the
+        counts are not a round-robin split of sum(counts) images."""
+        import numpy as np
+        if len(counts) != self.world:
+            raise ValueError("need one count per rank, got %d for world %d" % (len(counts), self.world))
+        parts = []
+        for r, n in enumerate(counts):
+            j = np.arange(int(n), dtype=np.int64)
+            parts.append(((j // self.chunk) * self.world + r) * self.chunk + j % self.chunk)
+        idx = np.concatenate(parts) if parts else np.zeros(0, np.int64)
+        if not np.array_equal(np.sort(idx), np.arange(len(idx))):
+            raise ValueError("counts %s are not a round-robin split in chunks of %d" % (list(counts), self.chunk))
+        return idx
+
+    def to_input_order(self, rows, counts):
+        """rows: a list in rank order (len = sum(counts)) -> the same rows in input order."""
+        idx = self.input_index(counts)
+        if len(rows) != len(idx):
+            raise ValueError("%d rows for %d counted images" % (len(rows), len(idx)))
+        out = [None] * len(idx)
+        for row, i in zip(rows, idx.tolist()):
+            out[i] = row
+        return out
+
+
+def _all_gather_ints(values, group, device):
+    """A small all-gather of int64 vectors of equal length: [world, len(values)] as numpy."""
+    world = dist.get_world_size(group)
+    mine = torch.tensor(list(values), dtype=torch.int64, device=device)
+    out = torch.empty((world, len(values)), dtype=torch.int64, device=device)
+    dist.all_gather_into_tensor(out.view(-1), mine, group=group)
+    return out.cpu().numpy()
+
+
+def mixed_batches(engine, shapes, max_batch):
+    """detect_many's batching of a list of frame sizes [(H, W)...]: groups by network shape, each group as batches of
+    `max_batch` frames and its halvings only (one layer plan per (shape, batch size)).  Returns lists of list positions."""
+    sizes, b = [], max_batch
+    while b >= 1:
+        sizes.append(b)
+        b //= 2
+    groups = {}
+    for i, (h, w) in enumerate(shapes):
+        groups.setdefault(engine.network_shape(int(h), int(w)), []).append(i)
+    parts = []
+    for idx in groups.values():
+        k = 0
+        for b in sizes:
+            while len(idx) - k >= b:
+                parts.append(idx[k:k + b])
+                k += b
+    return parts
+
+
+_mixed_buffers = {}
+
+
+def detect_many_sharded(detector, images, group=None, score_threshold=0.1, max_batch=32, chunk=256):
+    """Detector.detect_many over the ranks of `group`: every rank passes ITS OWN list of images (any sizes, any count,
+    also none) and gets back every rank's per-image (boxes, labels, scores) in rank order -- each bit for bit what
+    detect_many returns for that image (every image is independent end to end, nms.py:96-101).  Without an initialised
+    process group this is detect_many itself; `group` None with one is the default group (also at world 1: the collective
+    path runs).  Mode f32 only.
+
+    Data flow (detect_sharded's design): one small all-gather of the per-rank counts and one of every rank's processing
+    order; then per round of at most `chunk` images per rank, the engine writes its records (ssd_forward_mixed_host, batches
+    as detect_many forms them) straight into this rank's slice of a receive buffer [world, max_local, 6T+1] and ONE
+    all-gather of that buffer runs.  Records live in device memory with backend 'nccl' (the gather in place) and in pinned
+    host memory otherwise (node_device_and_backend).  At most world x chunk records (48 004 B each at T = 2000) per round."""
+    import numpy as np
+    from .ssd import Engine
+    if not (dist.is_available() and dist.is_initialized()):
+        return detector.detect_many(images, score_threshold=score_threshold, max_batch=max_batch)
+    eng = detector.engine
+    if eng.precision != "f32":
+        raise ValueError("detect_many_sharded runs in mode f32 (the precision of detect_many's batched path)")
+    imgs = [np.asarray(im) for im in images]
+    for im in imgs:
+        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError("every image must be a uint8 array of shape [height, width, 3]")
+    max_batch = max(1, min(int(max_batch), eng.MIXED_MAX))
+    chunk = max(1, int(chunk))
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    on_device = dist.get_backend(group) == "nccl"
+    small = torch.device("cuda", eng.device) if on_device else torch.device("cpu")
+    counts = _all_gather_ints([len(imgs)], group, small)[:, 0]
+    # this rank's processing order: per round of `chunk` images, detect_many's batches back to back
+    order, batches = [], []
+    for k0 in range(0, len(imgs), chunk):
+        parts = mixed_batches(eng, [im.shape[:2] for im in imgs[k0:k0 + chunk]], max_batch)
+        batches.append([[k0 + i for i in p] for p in parts])
+        order += [k0 + i for p in parts for i in p]
+    most = int(counts.max()) if len(counts) else 0
+    padded = order + [-1] * (most - len(order))
+    orders = _all_gather_ints(padded, group, small) if most else np.zeros((world, 0), np.int64)
+    words = eng.record_words
+    rounds = -(-most // chunk)
+    pinned = not on_device and torch.cuda.is_available() and isinstance(eng, Engine)   # (a stand-in engine writes on the CPU)
+    need = world * min(chunk, most) * words
+    key = (id(eng), eng.device, on_device)
+    buf = _mixed_buffers.get(key)
+    if need and (buf is None or buf.numel() < need):           # grow-only, one per engine
+        _mixed_buffers.clear()
+        if on_device:
+            buf = torch.zeros((need,), dtype=torch.int32, device=small)
+        elif pinned:
+            buf = torch.zeros((need,), dtype=torch.int32).pin_memory()
+        else:
+            buf = torch.zeros((need,), dtype=torch.int32)
+        _mixed_buffers[key] = buf
+    results = [[None] * int(c) for c in counts]
+    T = (words - 1) // 6
+    with eng.lock:
+        for k in range(rounds):
+            per = int(min(chunk, max(int(c) - k * chunk for c in counts)))
+            got = buf[:world * per * words].view(world, per, words)
+            row = 0
+            for part in (batches[k] if k < len(batches) else []):
+                eng.forward_mixed_host([imgs[i] for i in part], records=got[rank, row:row + len(part)])
+                row += len(part)
+            if pinned:
+                torch.cuda.current_stream(eng.device).synchronize()      # the kernels' writes into pinned memory, before gloo reads
+            gather_records(got[rank] if on_device else got[rank].clone(), group, out=got.view(world * per, words))
+            host = got.cpu().numpy() if on_device else got.numpy()
+            for r in range(world):
+                n_r = int(min(chunk, max(int(counts[r]) - k * chunk, 0)))
+                rec = host[r, :n_r]
+                boxes = rec[:, :4 * T].view(np.float32).reshape(n_r, T, 4)
+                scores = rec[:, 4 * T:5 * T].view(np.float32)
+                labels, num = rec[:, 5 * T:6 * T], rec[:, 6 * T]
+                for j in range(n_r):
+                    n = int(num[j])
+                    keep = scores[j][:n] > score_threshold           # inference/detector.py:54-58
+                    results[r][int(orders[r, k * chunk + j])] = (boxes[j][:n][keep], labels[j][:n][keep], scores[j][:n][keep])
+    return [x for per_rank in results for x in per_rank]

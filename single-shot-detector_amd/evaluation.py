@@ -106,12 +106,18 @@ def image_losses(per_image_row, regularization, loss_config):
     return loc, cls, total_loss(loc, cls, regularization, loss_config)
 
 
-def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, decode=None):
+def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, decode=None, group=None, chunk=256):
     """estimator.evaluate of train.py:61-65 for `detector` (a Detector) over `val_dataset` (a directory of .tfrecords
     shards, a shard path, or an iterable of (JPEG bytes | uint8 array, boxes [n,4], labels [n])).  config: the
     reference's JSON (path or dict).  Returns {'loss', 'localization_loss', 'classification_loss',
     'regularization_loss'} (means over images) and 'metrics/mAP' -- or the seven 'metrics/*' of metrics.py:84-100 when
-    num_classes == 1.  JPEGs are decoded on `read_workers` threads (default min(16, CPUs))."""
+    num_classes == 1.  JPEGs are decoded on `read_workers` threads (default min(16, CPUs)).
+
+    `group`: a torch.distributed process group to shard the images over (None: this process does everything).  Every rank
+    iterates the whole record stream (bytes only) and decodes and runs only its own round-robin chunks of `chunk` images
+    (distributed.ChunkAssignment); per round one all-gather of one fixed-size row per image (the ssd_loss row, the frame size
+    and the predictions) follows, and the means and the Evaluator are fed in dataset order on every rank: every rank
+    returns the one-process dict, float for float."""
     from concurrent.futures import ThreadPoolExecutor
     from . import tfrecords
     lc = load_loss_config(config)
@@ -132,10 +138,9 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
     sums = np.zeros(4, np.float64)
     count = 0
     workers = max(1, int(read_workers if read_workers is not None else min(16, os.cpu_count() or 1)))
-    chunk = 256
 
-    def consume(items):
-        nonlocal count, sums
+    def run_items(items):
+        """(frame, boxes, labels) triples -> _Run's per-image results, in the order of `items`."""
         groups = {}
         for i, (frame, _gb, _gl) in enumerate(items):
             groups.setdefault(eng.network_shape(frame.shape[0], frame.shape[1]), []).append(i)
@@ -152,21 +157,32 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
                     res = run([items[i][0] for i in sub], [(items[i][1], items[i][2]) for i in sub], lc)
                 for i, r in zip(sub, res):
                     results[i] = r
-        for (row, gt_scaled, (bx, lb, sc)), (_f, _gb, gl) in zip(results, items):      # in dataset order
-            loc, cls, tot = image_losses(row, reg, lc)
-            sums = sums + np.array([float(tot), float(loc), float(cls), float(reg)])
-            count += 1
-            evaluator.add_image(gt_scaled, gl, bx, lb, sc)
+        return results
 
-    with ThreadPoolExecutor(max_workers=workers) as pool:
-        pending = []
-        for img, gb, gl in data:
-            pending.append((pool.submit(decode, img), gb, gl))
-            if len(pending) == chunk:
+    def add(result, gl):
+        nonlocal count, sums
+        row, gt_scaled, (bx, lb, sc) = result
+        loc, cls, tot = image_losses(row, reg, lc)
+        sums = sums + np.array([float(tot), float(loc), float(cls), float(reg)])
+        count += 1
+        evaluator.add_image(gt_scaled, gl, bx, lb, sc)
+
+    def consume(items):
+        for result, (_f, _gb, gl) in zip(run_items(items), items):      # in dataset order
+            add(result, gl)
+
+    if group is None:
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            pending = []
+            for img, gb, gl in data:
+                pending.append((pool.submit(decode, img), gb, gl))
+                if len(pending) == chunk:
+                    consume([(f.result(), gb_, gl_) for f, gb_, gl_ in pending])
+                    pending = []
+            if pending:
                 consume([(f.result(), gb_, gl_) for f, gb_, gl_ in pending])
-                pending = []
-        if pending:
-            consume([(f.result(), gb_, gl_) for f, gb_, gl_ in pending])
+    else:
+        _sharded_rounds(eng, data, decode, workers, run_items, add, group, chunk)
     if count == 0:
         raise ValueError("the validation dataset is empty")
     means = sums / count
@@ -182,9 +198,63 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
     return out
 
 
+def _sharded_rounds(eng, data, decode, workers, run_items, add, group, chunk):
+    """evaluate()'s loop over the ranks of `group`.  Round k is images [k * world * chunk, (k + 1) * world * chunk) of the
+    stream; rank r decodes and runs the r-th chunk of it (the same chunks, so the same batches, as one process), packs one
+    row per image -- int32 words: the ssd_loss row (localization sum, classification sum, matches: 3 x f32), the frame's
+    height and width, the predictions' boxes [T,4] f32, scores [T] f32, labels [T] i32, count -- and one all-gather of
+    [world, chunk, 6T+6] hands every rank the whole round, which is then fed to `add` in dataset order (the groundtruth
+    boxes are scaled by the frame's box_scaler here, as _Run scales them)."""
+    from concurrent.futures import ThreadPoolExecutor
+    import torch.distributed as dist
+    from .distributed import ChunkAssignment, gather_records
+    torch = _torch()
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    assign = ChunkAssignment(world, rank, chunk)
+    p = eng.params
+    T = int(p["num_classes"]) * int(p["max_boxes_per_class"])
+    words = 6 + 6 * T
+    dev = torch.device("cuda", eng.device) if dist.get_backend(group) == "nccl" else torch.device("cpu")
+
+    def flush(items):
+        per = min(chunk, len(items))
+        own = items[rank * chunk:(rank + 1) * chunk]
+        rows = np.zeros((per, words), np.int32)
+        if own:
+            frames = [(f.result(), gb, gl) for f, gb, gl in own]
+            for j, ((frame, _gb, _gl), (row, _s, (bx, lb, sc))) in enumerate(zip(frames, run_items(frames))):
+                n = len(sc)
+                rows[j, 0:3] = np.asarray(row[:3], np.float32).view(np.int32)
+                rows[j, 3:5] = frame.shape[:2]
+                rows[j, 5:5 + 4 * n] = np.asarray(bx, np.float32).reshape(-1).view(np.int32)
+                rows[j, 5 + 4 * T:5 + 4 * T + n] = np.asarray(sc, np.float32).view(np.int32)
+                rows[j, 5 + 5 * T:5 + 5 * T + n] = np.asarray(lb, np.int32)
+                rows[j, 5 + 6 * T] = n
+        got = gather_records(torch.from_numpy(rows).to(dev), group).cpu().numpy().reshape(world, per, words)
+        for q, (_f, gb, gl) in enumerate(items):
+            r, j = divmod(q, chunk)
+            w = got[r, j]
+            n = int(w[5 + 6 * T])
+            bs = network_input_size(int(w[3]), int(w[4]), p["min_dimension"])[2]
+            add((w[0:3].view(np.float32), np.asarray(gb, np.float32).reshape(-1, 4) * bs,
+                 (w[5:5 + 4 * n].view(np.float32).reshape(n, 4), w[5 + 5 * T:5 + 5 * T + n],
+                  w[5 + 4 * T:5 + 4 * T + n].view(np.float32))), gl)
+
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        items = []
+        for i, (img, gb, gl) in enumerate(data):
+            items.append((pool.submit(decode, img) if assign.mine(i) else None, gb, gl))
+            if len(items) == world * chunk:
+                flush(items)
+                items = []
+        if items:
+            flush(items)
+
+
 def main(argv=None):
     import argparse
     import json
+    import sys
     from .detector import Detector
     ap = argparse.ArgumentParser(description="train.py's evaluation of a checkpoint: validation loss and AP")
     ap.add_argument("model_path", help="checkpoint prefix / model_dir / frozen graph / .npz")
@@ -192,10 +262,34 @@ def main(argv=None):
     ap.add_argument("--val_dataset", default=None, help="directory of .tfrecords shards (default: the config's val_dataset)")
     ap.add_argument("--use_ema", action="store_true", help="the moving averages, as RestoreMovingAverageHook restores them")
     ap.add_argument("--max_batch", type=int, default=32)
+    ap.add_argument("--gpus", type=int, default=1,
+                    help="processes to shard the images over: N > 1 starts torch.distributed.run with N ranks as a child process "
+                         "(rank r on device LOCAL_RANK %% device_count; RCCL only when every rank has a device of its own, else "
+                         "gloo); inside such a launch the collective path runs, also at N = 1")
     a = ap.parse_args(argv)
+    if a.gpus < 1:
+        ap.error("--gpus must be >= 1")
+    if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        from .distributed import launch_local
+        # nothing here has touched the GPU yet; the child runs this module again, once per rank
+        sys.exit(launch_local(a.gpus, "ssd_amd.evaluation", sys.argv[1:] if argv is None else list(argv)))
     val = a.val_dataset or json.load(open(a.config))["val_dataset"]
-    with Detector(a.model_path, config=a.config, use_ema=a.use_ema) as det:
-        print(json.dumps(evaluate(det, val, a.config, max_batch=a.max_batch), sort_keys=True))
+    if "WORLD_SIZE" not in os.environ:
+        with Detector(a.model_path, config=a.config, use_ema=a.use_ema) as det:
+            print(json.dumps(evaluate(det, val, a.config, max_batch=a.max_batch), sort_keys=True))
+        return
+    import torch.distributed as dist
+    from .distributed import init_node_process_group
+    if a.gpus != int(os.environ["WORLD_SIZE"]):
+        raise SystemExit("--gpus (%d) != WORLD_SIZE (%s)" % (a.gpus, os.environ["WORLD_SIZE"]))
+    device, _backend = init_node_process_group()
+    try:
+        with Detector(a.model_path, config=a.config, use_ema=a.use_ema, visible_device_list=str(device)) as det:
+            res = evaluate(det, val, a.config, max_batch=a.max_batch, group=dist.group.WORLD)
+        if dist.get_rank() == 0:
+            print(json.dumps(res, sort_keys=True), flush=True)
+    finally:
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

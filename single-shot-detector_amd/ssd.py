@@ -680,6 +680,27 @@ class Engine:
             torch.cuda.current_stream().synchronize()
             return slot["host"]
 
+    def forward_mixed_host(self, images, records):
+        """A list of host uint8 arrays [H_b, W_b, 3] of different sizes that share a network shape, written as B records into
+        `records` (a contiguous int32 tensor [B, 6T+1] in device memory or pinned host memory, e.g. this rank's slice of an
+        all-gather's receive buffer): ONE call of ssd_forward_mixed_host, asynchronous on the current stream (the frames may
+        be reused on return).  Returns the four views of `records`."""
+        torch = _torch()
+        B = len(images)
+        with self.lock:
+            srcs = [np.ascontiguousarray(im) for im in images]
+            for im in srcs:
+                if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                    raise ValueError("every image must be a uint8 array of shape [height, width, 3]")
+            if records.dtype != torch.int32 or tuple(records.shape) != (B, self.record_words) or not records.is_contiguous():
+                raise ValueError("records must be a contiguous int32 tensor [B, %d]" % self.record_words)
+            if not (records.is_cuda or records.is_pinned()):
+                raise ValueError("records must live in device memory or in pinned host memory")
+            ptrs = (ctypes.c_void_p * B)(*[im.ctypes.data for im in srcs])
+            hw_c = (ctypes.c_int32 * (2 * B))(*[int(v) for im in srcs for v in im.shape[:2]])
+            check(lib().ssd_forward_mixed_host(self._h, ptrs, B, hw_c, _ptr(records), _stream(torch)))
+            return self.record_views(records)
+
     def detect_stream(self, batches):
         """Host-fed steady-state serving: an iterable of host uint8 arrays [B,H,W,3] (any mix of sizes) -> a generator of
         (boxes, labels, scores, num_boxes) numpy arrays, in order.  Two sets of buffers and two copy streams: the
