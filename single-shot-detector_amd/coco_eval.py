@@ -79,6 +79,7 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     0 writes `predictions_json` (byte for byte the one-process file) and the table; every rank returns the same statistics."""
     import os
     from . import coco_metric
+    from .distributed import ChunkAssignment
     if read_image is None:
         from PIL import Image
 
@@ -88,17 +89,41 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     mapping = integer_to_coco_id(gt["categories"])
     metas = sorted(gt["images"], key=lambda m: m["id"])
     workers = max(1, int(read_workers if read_workers is not None else min(16, os.cpu_count() or 1)))
-    if group is not None:
-        return _evaluate_sharded(detector, gt, metas, mapping, images_dir, read_image, predictions_json, out, score_threshold,
-                                 max_batch, workers, group, chunk)
-    results = []
-    for part, images in _read_chunks(metas, images_dir, read_image, workers, chunk):
+    if group is None:
+        world, rank = 1, 0
+    else:
+        import torch.distributed as dist
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+    mine = [m for _i, m in ChunkAssignment(world, rank, chunk).select(metas)]
+    results, frags = [], []
+    for part, images in _read_chunks(mine, images_dir, read_image, workers, chunk):
         # images read, then detected as batches grouped by network shape (the notebook's loop, one image per sess.run, at batch throughput)
-        results += detection_records_many(detector, images, [m["id"] for m in part], mapping, score_threshold, max_batch)
-    if predictions_json:
-        with open(predictions_json, "w") as f:
-            json.dump(results, f)
-    return coco_metric.evaluate_boxes(gt, results, out=out)
+        rows = detection_records_many(detector, images, [m["id"] for m in part], mapping, score_threshold, max_batch)
+        results += rows
+        if predictions_json:
+            frags.append(json.dumps(rows)[1:-1].encode())      # json.dump of the whole list joins these with ", "
+    ev = coco_metric.CocoBoxEval(gt, results)
+    ev.evaluate(img_ids=[m["id"] for m in mine])
+    if group is not None:
+        # one all-gather of every rank's matching cells and its chunks' JSON; the chunks go back in input order (chunk c of the
+        # sorted images is rank c % world's: a round-robin split in chunks of one)
+        payload = {"cells": ev.cells(), "json": np.frombuffer(b"".join(frags), np.uint8),
+                   "lens": np.array([len(f) for f in frags], np.int64)}
+        got = [None] * world
+        dist.all_gather_object(got, payload, group=group)
+        per_rank = []
+        for r, p in enumerate(got):
+            if r != rank:
+                ev.merge(p["cells"])
+            blob, ends = p["json"].tobytes(), np.cumsum(p["lens"]).tolist()
+            per_rank += [blob[a:b] for a, b in zip([0] + ends[:-1], ends)]
+        if predictions_json:
+            chunks = ChunkAssignment(world, 0, 1)
+            frags = chunks.to_input_order(per_rank, [chunks.count(-(-len(metas) // chunk), r) for r in range(world)])
+    if predictions_json and rank == 0:
+        with open(predictions_json, "wb") as f:
+            f.write(b"[" + b", ".join(x for x in frags if x) + b"]")
+    return ev.accumulate().summarize(out if rank == 0 else None)
 
 
 def _read_chunks(metas, images_dir, read_image, workers, chunk):
@@ -114,43 +139,6 @@ def _read_chunks(metas, images_dir, read_image, workers, chunk):
             images = [f.result() for f in ahead]
             ahead = start(k + chunk)
             yield metas[k:k + chunk], images
-
-
-def _evaluate_sharded(detector, gt, metas, mapping, images_dir, read_image, predictions_json, out, score_threshold, max_batch,
-                      workers, group, chunk):
-    import torch.distributed as dist
-    from . import coco_metric
-    from .distributed import ChunkAssignment
-    world, rank = dist.get_world_size(group), dist.get_rank(group)
-    assign = ChunkAssignment(world, rank, chunk)
-    mine = [m for _i, m in assign.select(metas)]
-    results, frags = [], []
-    many = getattr(detector, "detect_many", None)
-    for part, images in _read_chunks(mine, images_dir, read_image, workers, chunk):
-        dets = many(images, score_threshold=score_threshold, max_batch=max_batch) if many else [None] * len(images)
-        for image, m, d in zip(images, part, dets):
-            rows = detection_records(detector, image, m["id"], mapping, score_threshold, detections=d)
-            results += rows
-            if predictions_json:
-                frags.append(json.dumps(rows)[1:-1].encode())        # json.dump of the whole list joins these with ", "
-    ev = coco_metric.CocoBoxEval(gt, results)
-    ev.evaluate(img_ids=[m["id"] for m in mine])
-    payload = {"cells": ev.cells(), "json": np.frombuffer(b"".join(frags), np.uint8),
-               "lens": np.array([len(f) for f in frags], np.int64)}
-    got = [None] * world
-    dist.all_gather_object(got, payload, group=group)
-    for r, p in enumerate(got):
-        if r != rank:
-            ev.merge(p["cells"])
-    if predictions_json and rank == 0:
-        per_rank = []
-        for p in got:
-            blob, ends = p["json"].tobytes(), np.cumsum(p["lens"]).tolist()
-            per_rank += [blob[a:b] for a, b in zip([0] + ends[:-1], ends)]
-        frags_all = assign.to_input_order(per_rank, [assign.count(len(metas), r) for r in range(world)])
-        with open(predictions_json, "wb") as f:
-            f.write(b"[" + b", ".join(x for x in frags_all if x) + b"]")
-    return ev.accumulate().summarize(out if rank == 0 else None)
 
 
 # ----------------------------------------------------------------------------- VOC-style AP self-check

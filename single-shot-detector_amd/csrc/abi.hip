@@ -206,9 +206,10 @@ extern "C" int ssd_finalize(ssd_handle *h)
 // last kernel (two host threads sharing a Detector on their own streams, as tf.Session.run allows, inference/detector.py:34,52).
 // (a mixed-size batch: `mx` = its per-frame geometry, the network shape all frames resize to, its largest frame's bytes)
 struct MixedSel { const MixedCall *mx; int netH, netW; long long max_bytes; };
+// Where a forward writes its four outputs: dense tensors (stride 0, ssd_forward) or B records of `stride` words (record_outputs).
+struct Outputs { float *boxes; int32_t *labels; float *scores; int32_t *num_boxes; long long stride; };
 
-static int forward_locked(ssd_handle *h, const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, float *boxes_dev,
-                          int32_t *labels_dev, float *scores_dev, int32_t *num_boxes_dev, long long out_stride, hipStream_t s,
+static int forward_locked(ssd_handle *h, const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, const Outputs &o, hipStream_t s,
                           const MixedSel *ms = nullptr)
 {
     HIPCHK(hipSetDevice(h->cfg.device));
@@ -246,14 +247,13 @@ static int forward_locked(ssd_handle *h, const uint8_t *images_dev, int32_t B, i
     // (hipGraph replay of a repeating forward was measured in rounds 1-2 -- batch 1: replay 2.49 ms against eager 2.33, the forward
     //  is GPU-bound -- and is not part of the library.)
     h->mixed = ms ? ms->mx : nullptr;
-    const int rc = enqueue_forward(h, images_dev, boxes_dev, labels_dev, scores_dev, num_boxes_dev, out_stride, s);
+    const int rc = enqueue_forward(h, images_dev, o.boxes, o.labels, o.scores, o.num_boxes, o.stride, s);
     h->mixed = nullptr;
     return rc;
 }
 
 // (the caller holds h->mu)
-static int forward_checked_locked(ssd_handle *h, const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, float *boxes_dev,
-                                  int32_t *labels_dev, float *scores_dev, int32_t *num_boxes_dev, long long out_stride, void *stream,
+static int forward_checked_locked(ssd_handle *h, const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, const Outputs &o, void *stream,
                                   const MixedSel *ms = nullptr)
 {
     if (!h->finalized) return ssd_fail(SSD_ERR_STATE, "ssd_forward before ssd_finalize");
@@ -265,7 +265,7 @@ static int forward_checked_locked(ssd_handle *h, const uint8_t *images_dev, int3
             return ssd_fail(SSD_ERR_INVALID, "ssd_forward: aspect ratio too extreme (resized image exceeds 64 Mpixel)");
     }
     hipStream_t s = (hipStream_t)stream;
-    const int rc = forward_locked(h, images_dev, B, H, W, boxes_dev, labels_dev, scores_dev, num_boxes_dev, out_stride, s, ms);
+    const int rc = forward_locked(h, images_dev, B, H, W, o, s, ms);
     if (rc == SSD_OK) {
         // (not while a caller captures `s` into a graph of its own: the stream then is not a queue of the device's)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -279,19 +279,18 @@ static int forward_checked_locked(ssd_handle *h, const uint8_t *images_dev, int3
     return rc;
 }
 
-static int forward_checked(ssd_handle *h, const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, float *boxes_dev,
-                           int32_t *labels_dev, float *scores_dev, int32_t *num_boxes_dev, long long out_stride, void *stream)
+static int forward_checked(ssd_handle *h, const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, const Outputs &o, void *stream)
 {
-    if (!h || !images_dev || !boxes_dev || !labels_dev || !scores_dev || !num_boxes_dev)
+    if (!h || !images_dev || !o.boxes || !o.labels || !o.scores || !o.num_boxes)
         return ssd_fail(SSD_ERR_INVALID, "ssd_forward: null argument");
     std::lock_guard<std::mutex> g(h->mu);
-    return forward_checked_locked(h, images_dev, B, H, W, boxes_dev, labels_dev, scores_dev, num_boxes_dev, out_stride, stream);
+    return forward_checked_locked(h, images_dev, B, H, W, o, stream);
 }
 
 extern "C" int ssd_forward(ssd_handle *h, const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, float *boxes_dev,
                            int32_t *labels_dev, float *scores_dev, int32_t *num_boxes_dev, void *stream)
 {
-    return forward_checked(h, images_dev, B, H, W, boxes_dev, labels_dev, scores_dev, num_boxes_dev, 0, stream);
+    return forward_checked(h, images_dev, B, H, W, {boxes_dev, labels_dev, scores_dev, num_boxes_dev, 0}, stream);
 }
 
 // The same graph with its outputs as B fixed RECORDS (what the all-gather of a data-parallel step moves), record b
@@ -304,13 +303,19 @@ extern "C" int32_t ssd_record_words(const ssd_handle *h)
     return h ? 6 * h->cfg.num_classes * h->cfg.max_boxes_per_class + 1 : 0;
 }
 
+// The four arrays of a block of records (the layout above; record b starts `stride` words after record b - 1).
+static Outputs record_outputs(const ssd_handle *h, void *records)
+{
+    const long long T = (long long)h->cfg.num_classes * h->cfg.max_boxes_per_class;
+    int32_t *r = (int32_t *)records;
+    return {(float *)r, r + 5 * T, (float *)(r + 4 * T), r + 6 * T, 6 * T + 1};
+}
+
 extern "C" int ssd_forward_records(ssd_handle *h, const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, void *records_dev, void *stream)
 {
     if (!h || !records_dev) return ssd_fail(SSD_ERR_INVALID, "ssd_forward_records: null argument");
     if ((reinterpret_cast<uintptr_t>(records_dev) & 3) != 0) return ssd_fail(SSD_ERR_INVALID, "ssd_forward_records: records must be 4-byte aligned");
-    const long long T = (long long)h->cfg.num_classes * h->cfg.max_boxes_per_class;
-    int32_t *r = (int32_t *)records_dev;
-    return forward_checked(h, images_dev, B, H, W, (float *)r, r + 5 * T, (float *)(r + 4 * T), r + 6 * T, 6 * T + 1, stream);
+    return forward_checked(h, images_dev, B, H, W, record_outputs(h, records_dev), stream);
 }
 
 // Before the host writes the pinned staging buffer again: the previous call's uploads must have read it.  Only the uploads -- not the
@@ -360,6 +365,18 @@ static int grow_stage(ssd_handle *h, size_t bytes)
     return SSD_OK;
 }
 
+// Before the host writes `bytes` into the staging buffer for an upload on `s`: the previous call's uploads have read it, the
+// stream they ran on is drained when `s` is another one (its uploads into the DEVICE image would not queue behind the forward that
+// still reads it), and the pair is large enough.  (The caller holds h->mu and has set the device.)
+static int stage_begin(ssd_handle *h, hipStream_t s, size_t bytes)
+{
+    SSDCHK(stage_acquire(h));
+    if (h->stage_stream_set && h->stage_stream != s) {
+        if (hipStreamSynchronize(h->stage_stream) != hipSuccess) { (void)hipGetLastError(); HIPCHK(hipDeviceSynchronize()); }
+    }
+    return grow_stage(h, bytes);
+}
+
 // The boundary's own form (inference/detector.py:51-52: a HOST image in on every call): pageable host memory -> the handle's
 // pinned staging buffer -> its device image, in `h2d_chunks` pieces so that piece k crosses the bus under the host copy of
 // piece k + 1 -- one C loop instead of a Python one (two numpy / torch calls per piece cost more than a piece's copy) --
@@ -374,13 +391,7 @@ static int forward_host_impl(ssd_handle *h, const uint8_t *images_host, int32_t 
     HIPCHK(hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     const size_t bytes = (size_t)B * H * W * 3;
-    // the previous call's upload may still be reading the staging buffer when the caller did not wait for it
-    SSDCHK(stage_acquire(h));
-    if (h->stage_stream_set && h->stage_stream != s) {
-        // (another stream than last time: its uploads into the DEVICE image would not queue behind the forward that still reads it)
-        if (hipStreamSynchronize(h->stage_stream) != hipSuccess) { (void)hipGetLastError(); HIPCHK(hipDeviceSynchronize()); }
-    }
-    SSDCHK(grow_stage(h, bytes));
+    SSDCHK(stage_begin(h, s, bytes));
     int nchunk = ssd_opt(h, OPT_H2D_CHUNKS, 2);      // (measured: 1 / 2 / 3 / 4 / 6 / 8 pieces -> Detector p50 1.695 / 1.678 / 1.691 / 1.698 / 1.717 / 1.735 ms: a hipMemcpyAsync costs the host ~10 us)
     if (nchunk < 1) nchunk = 1;
     if (nchunk > 16) nchunk = 16;
@@ -392,9 +403,7 @@ static int forward_host_impl(ssd_handle *h, const uint8_t *images_host, int32_t 
         HIPCHK(hipMemcpyAsync(h->stage_dev + lo, h->stage_pin + lo, n, hipMemcpyHostToDevice, s));
     }
     SSDCHK(stage_release(h, s, stage_event));
-    const long long T = (long long)h->cfg.num_classes * h->cfg.max_boxes_per_class;
-    int32_t *r = (int32_t *)records;
-    return forward_checked_locked(h, h->stage_dev, B, H, W, (float *)r, r + 5 * T, (float *)(r + 4 * T), r + 6 * T, 6 * T + 1, stream);
+    return forward_checked_locked(h, h->stage_dev, B, H, W, record_outputs(h, records), stream);
 }
 
 extern "C" int ssd_forward_host(ssd_handle *h, const uint8_t *images_host, int32_t B, int32_t H, int32_t W, void *records, void *stream)
@@ -461,9 +470,7 @@ extern "C" int ssd_forward_mixed(ssd_handle *h, const uint8_t *images_dev, int32
     std::lock_guard<std::mutex> g(h->mu);
     MixedSel ms;
     SSDCHK(prepare_mixed(h, B, hw_host, offsets_host, &ms, "ssd_forward_mixed"));
-    const long long T = (long long)h->cfg.num_classes * h->cfg.max_boxes_per_class;
-    int32_t *r = (int32_t *)records_dev;
-    return forward_checked_locked(h, images_dev, B, hw_host[0], hw_host[1], (float *)r, r + 5 * T, (float *)(r + 4 * T), r + 6 * T, 6 * T + 1, stream, &ms);
+    return forward_checked_locked(h, images_dev, B, hw_host[0], hw_host[1], record_outputs(h, records_dev), stream, &ms);
 }
 
 // ... fed from host memory: frames_host[b] = frame b, uint8 [hw[b][0], hw[b][1], 3].  The frames are staged back to back (16-byte
@@ -481,20 +488,14 @@ extern "C" int ssd_forward_mixed_host(ssd_handle *h, const uint8_t *const *frame
     hipStream_t s = (hipStream_t)stream;
     const MixedCall &mc = h->mixed_store;
     const size_t bytes = (size_t)mc.geom.f[B - 1].off + (size_t)hw_host[2 * (B - 1)] * hw_host[2 * (B - 1) + 1] * 3;
-    SSDCHK(stage_acquire(h));
-    if (h->stage_stream_set && h->stage_stream != s) {
-        if (hipStreamSynchronize(h->stage_stream) != hipSuccess) { (void)hipGetLastError(); HIPCHK(hipDeviceSynchronize()); }
-    }
-    SSDCHK(grow_stage(h, bytes));
+    SSDCHK(stage_begin(h, s, bytes));
     for (int b = 0; b < B; ++b) {           // frame b crosses the bus under the host copy of frame b + 1
         const size_t n = (size_t)hw_host[2 * b] * hw_host[2 * b + 1] * 3, lo = mc.geom.f[b].off;
         memcpy(h->stage_pin + lo, frames_host[b], n);
         HIPCHK(hipMemcpyAsync(h->stage_dev + lo, h->stage_pin + lo, n, hipMemcpyHostToDevice, s));
     }
     SSDCHK(stage_release(h, s, true));
-    const long long T = (long long)h->cfg.num_classes * h->cfg.max_boxes_per_class;
-    int32_t *r = (int32_t *)records;
-    return forward_checked_locked(h, h->stage_dev, B, hw_host[0], hw_host[1], (float *)r, r + 5 * T, (float *)(r + 4 * T), r + 6 * T, 6 * T + 1, stream, &ms);
+    return forward_checked_locked(h, h->stage_dev, B, hw_host[0], hw_host[1], record_outputs(h, records), stream, &ms);
 }
 
 // inference/detector.py:33-58 as ONE call for one frame: ssd_forward_host, the wait for `stream`, and the score filter
@@ -527,19 +528,17 @@ extern "C" int ssd_detect_host(ssd_handle *h, const uint8_t *image_host, int32_t
     int rc = forward_host_impl(h, image_host, 1, H, W, record, stream, false);       // (this call drains `stream` itself, next line)
     if (rc != SSD_OK) return rc;
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    const long long T = (long long)h->cfg.num_classes * h->cfg.max_boxes_per_class;
-    const int32_t *r = (const int32_t *)record;
-    const float *bx = (const float *)r, *sc = (const float *)(r + 4 * T);
-    const int32_t *lb = r + 5 * T;
-    int32_t n = r[6 * T];
+    const Outputs r = record_outputs(h, record);
+    const long long T = (r.stride - 1) / 6;
+    const int32_t n = *r.num_boxes;
     if (n < 0 || n > T) return ssd_fail(SSD_ERR_STATE, "ssd_detect_host: the record's num_boxes is out of range (is `record` host-visible memory?)");
     int32_t k = 0;
     for (int32_t i = 0; i < n; ++i)
-        if (sc[i] > score_threshold) {
+        if (r.scores[i] > score_threshold) {
             if (k >= capacity) return ssd_fail(SSD_ERR_INVALID, "ssd_detect_host: capacity too small");
-            memcpy(boxes_out + 4 * (size_t)k, bx + 4 * (size_t)i, 16);
-            labels_out[k] = lb[i];
-            scores_out[k] = sc[i];
+            memcpy(boxes_out + 4 * (size_t)k, r.boxes + 4 * (size_t)i, 16);
+            labels_out[k] = r.labels[i];
+            scores_out[k] = r.scores[i];
             ++k;
         }
     *n_out = k;

@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from .config import load_config
-from .ssd import Engine, _torch
+from .ssd import Engine, _torch, host_frame, mixed_batches, score_filter
 from .pb_import import load_pb_weights
 from .ckpt_import import load_ckpt_weights, resolve_checkpoint
 from .variables import load_weights
@@ -83,18 +83,17 @@ class Detector:
         self.close()
         return False
 
-    def _detect_views(self, images):
-        """The graph outputs of one host batch as numpy VIEWS of the engine's pinned result block (valid until the next
-        call); the caller holds self.engine.lock."""
-        out = self.engine.detect_host(images)
+    def _f32_fallback(self, run):
+        """run() -- one forward and its results -- and in mode f16x3 the read-and-clear of the status word: when an activation
+        exceeded +-65504 and was clamped (ssd_hip.h ssd_status) those results are not trustworthy, so this detector continues in
+        the exact mode and run() is repeated.  The caller holds self.engine.lock across this whole call."""
+        out = run()
         if self.engine.precision == "f16x3" and self.engine.status() & 1:
-            # an activation exceeded +-65504 and was clamped (ssd_hip.h ssd_status): these results are not
-            # trustworthy -- this detector continues in the exact mode
             import warnings
             warnings.warn("single-shot-detector_amd: activation outside the fp16 range in precision mode "
                           "f16x3; switching this Detector to f32")
             self.engine.set_precision("f32")
-            out = self.engine.detect_host(images)
+            out = run()
         return out
 
     def detect_batch(self, images):
@@ -107,7 +106,7 @@ class Detector:
             with self.engine.lock:
                 return tuple(t.cpu().numpy() for t in self.engine.forward_cached(images))
         with self.engine.lock:
-            return tuple(np.array(v) for v in self._detect_views(images))
+            return tuple(np.array(v) for v in self._f32_fallback(lambda: self.engine.detect_host(images)))
 
     def detect_many(self, images, score_threshold=0.1, max_batch=32):
         """`__call__` for a LIST of images of any sizes, batched: the images are grouped by the size the network sees for them
@@ -116,30 +115,12 @@ class Detector:
         kernel, per-image box_scaler in the last), and the results come back in the order of `images` as (boxes, labels, scores)
         per image -- each bit for bit what `self(image, score_threshold)` returns.  The reference loops one `sess.run` per image
         (inference/evaluate_on_COCO.ipynb:125-150); this is that loop at batch throughput.  Mode f32.
-        Batch sizes are `max_batch` and its halvings only (a group of 56 at max_batch 32 runs as 32 + 16 + 8): the library keeps
-        one layer plan per (network shape, batch size), and a stream of arbitrary remainders must not build one for every size.
+        The batches are ssd.mixed_batches': `max_batch` and its halvings only (one layer plan per network shape and batch size).
         Two batches are in flight: batch k + 1 is staged and uploaded while batch k computes."""
         if self.engine.precision != "f32":
             return [self(im, score_threshold) for im in images]
-        imgs = [np.asarray(im) for im in images]
-        max_batch = max(1, min(int(max_batch), self.engine.MIXED_MAX))
-        sizes = []
-        b = max_batch
-        while b >= 1:
-            sizes.append(b)
-            b //= 2
-        groups = {}
-        for i, im in enumerate(imgs):
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError("every image must be a uint8 array of shape [height, width, 3]")
-            groups.setdefault(self.engine.network_shape(im.shape[0], im.shape[1]), []).append(i)
-        parts = []
-        for idx in groups.values():
-            k = 0
-            for b in sizes:
-                while len(idx) - k >= b:
-                    parts.append(idx[k:k + b])
-                    k += b
+        imgs = [host_frame(im, "every image") for im in images]
+        parts = mixed_batches(self.engine, [im.shape[:2] for im in imgs], max_batch)
         out = [None] * len(imgs)
 
         def consume(pending):
@@ -147,9 +128,7 @@ class Detector:
             slot["done"].synchronize()
             boxes, labels, scores, num = slot["host"]
             for j, i in enumerate(part):
-                n = int(num[j])
-                keep = scores[j][:n] > score_threshold        # inference/detector.py:54-58
-                out[i] = (boxes[j][:n][keep], labels[j][:n][keep], scores[j][:n][keep])
+                out[i] = score_filter(boxes[j], labels[j], scores[j], num[j], score_threshold)
 
         with self.engine.lock:
             pending = None
@@ -187,9 +166,7 @@ class Detector:
         from .config import load_loss_config
         from .evaluation import _Run, image_losses
         lc = load_loss_config(self._config if config is None else config)
-        image = np.asarray(image)
-        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
-            raise ValueError("image must be a uint8 array of shape [height, width, 3]")
+        image = host_frame(image)
         reg = self.regularization_loss(lc["weight_decay"])
         with self.engine.lock:
             row = _Run(self.engine)([image], [(np.asarray(boxes, np.float32).reshape(-1, 4), np.asarray(labels).reshape(-1))], lc)[0][0]
@@ -212,29 +189,13 @@ class Detector:
             from PIL import Image
             with Image.open(image) as im:
                 image = np.asarray(im.convert("RGB"), dtype=np.uint8)
-        image = np.asarray(image)
-        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
-            raise ValueError("image must be a uint8 array of shape [height, width, 3]")
+        image = host_frame(image)
         if self.engine.one_call_detect:
             # one library call: upload, forward, wait and the filter below in C (ssd_detect_host).  The engine's lock (an RLock)
             # is held across the call AND the read-and-clear of the status word: with two threads on one Detector in mode
             # f16x3, thread A's status() must not consume the overflow bit that thread B's forward raised.
             with self.engine.lock:
-                out = self.engine.detect_one(image, float(score_threshold))
-                if self.engine.precision == "f16x3" and self.engine.status() & 1:
-                    # an activation exceeded +-65504 and was clamped (ssd_hip.h ssd_status): these results are not
-                    # trustworthy -- this detector continues in the exact mode
-                    import warnings
-                    warnings.warn("single-shot-detector_amd: activation outside the fp16 range in precision mode "
-                                  "f16x3; switching this Detector to f32")
-                    self.engine.set_precision("f32")
-                    out = self.engine.detect_one(image, float(score_threshold))
-            return out
+                return self._f32_fallback(lambda: self.engine.detect_one(image, float(score_threshold)))
         with self.engine.lock:      # the views below live in the engine's pinned result block until the next call
-            boxes, labels, scores, n = self._detect_views(image[None])
-            n = n[0]  # inference/detector.py:54-58
-            to_keep = scores[0][:n] > score_threshold
-            boxes = boxes[0][:n][to_keep]         # (boolean indexing copies)
-            labels = labels[0][:n][to_keep]
-            scores = scores[0][:n][to_keep]
-        return boxes, labels, scores
+            boxes, labels, scores, n = self._f32_fallback(lambda: self.engine.detect_host(image[None]))
+            return score_filter(boxes[0], labels[0], scores[0], n[0], score_threshold)

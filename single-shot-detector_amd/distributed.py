@@ -4,11 +4,12 @@ same code runs on gloo/CPU tensors in the tests).  The reference has no multi-GP
 every image is independent end to end (nms.py:96-101 maps over images), so no other
 collective exists on the path.
 
-Record per image, 32-bit words: boxes [T,4] f32 | scores [T] f32 | labels [T] i32 |
-num_boxes i32  = 6T+1 words (48 004 B at T = 2000).
+Record per image: ssd.split_records (6T+1 32-bit words, 48 004 B at T = 2000).
 """
 import torch
 import torch.distributed as dist
+
+from .ssd import host_frame, mixed_batches, pack_records, score_filter, split_records
 
 
 def bind_to_gpu_numa_node(device=0):
@@ -50,24 +51,13 @@ def shard_range(total, rank, world_size):
 
 
 def pack_detections(boxes, labels, scores, num):
-    B, T = scores.shape
-    rec = torch.empty((B, 6 * T + 1), dtype=torch.int32, device=scores.device)
-    rec[:, :4 * T] = boxes.reshape(B, 4 * T).view(torch.int32)
-    rec[:, 4 * T:5 * T] = scores.view(torch.int32)
-    rec[:, 5 * T:6 * T] = labels
-    rec[:, 6 * T] = num
-    return rec
+    """The four outputs of a batch -> a new record block [B, 6T+1] beside them."""
+    return pack_records(boxes, labels, scores, num)
 
 
 def unpack_detections(rec):
     """(boxes, labels, scores, num) as VIEWS of a record block [B, 6T+1]: no copy, no launch."""
-    B, words = rec.shape
-    T = (words - 1) // 6
-    boxes = rec[:, :4 * T].view(torch.float32).unflatten(1, (T, 4))
-    scores = rec[:, 4 * T:5 * T].view(torch.float32)
-    labels = rec[:, 5 * T:6 * T]
-    num = rec[:, 6 * T]
-    return boxes, labels, scores, num
+    return split_records(rec)
 
 
 def gather_records(rec, group=None, out=None):
@@ -98,18 +88,32 @@ def all_gather_detections(boxes, labels, scores, num, group=None, total=None, fo
         return boxes, labels, scores, num
     if dist.get_world_size(group) == 1 and not force:
         return boxes, labels, scores, num
-    world = dist.get_world_size(group)
     rec = pack_detections(boxes, labels, scores, num)
-    if total is None or total % world == 0:
-        return unpack_detections(gather_records(rec, group))
-    per = -(-total // world)
-    if rec.shape[0] > per:
-        raise ValueError("shard of %d images exceeds ceil(%d / %d)" % (rec.shape[0], total, world))
-    pad = torch.zeros((per, rec.shape[1]), dtype=rec.dtype, device=rec.device)
-    pad[:rec.shape[0]] = rec
-    got = gather_records(pad, group).reshape(world, per, rec.shape[1])
-    rows = [got[r, :shard_range(total, r, world)[1] - shard_range(total, r, world)[0]] for r in range(world)]
-    return unpack_detections(torch.cat(rows, 0))
+
+    def gather(per):
+        if per == rec.shape[0]:
+            return gather_records(rec, group)
+        pad = torch.zeros((per, rec.shape[1]), dtype=rec.dtype, device=rec.device)
+        pad[:rec.shape[0]] = rec
+        return gather_records(pad, group)
+    return _gather_shards(rec.shape[0], total, dist.get_world_size(group), gather)
+
+
+def _gather_shards(n, total, world, gather):
+    """The one all-gather of a rank's shard of n images, uneven shards included: `gather(per)` runs it with every rank's part
+    `per` rows high -- n, or the largest shard ceil(total / world) when `total` (shard_range's split) does not divide evenly --
+    and returns the [world * per, 6T+1] records; the pad rows beyond each rank's own shard are dropped here.  Returns the
+    four views of the result."""
+    even = total is None or total % world == 0
+    per = n if even else -(-total // world)
+    if n > per:
+        raise ValueError("shard of %d images exceeds ceil(%d / %d)" % (n, total, world))
+    got = gather(per)
+    if even:
+        return unpack_detections(got)
+    g3 = got.view(world, per, -1)
+    shards = [shard_range(total, r, world) for r in range(world)]
+    return unpack_detections(torch.cat([g3[r, :hi - lo] for r, (lo, hi) in enumerate(shards)], 0))
 
 
 _gather_buffers = {}
@@ -147,27 +151,22 @@ def detect_sharded(engine, images_local, group=None, total=None, force=False, on
         return out
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     n = images_local.shape[0]
-    per = n if (total is None or total % world == 0) else -(-total // world)
-    if n > per:
-        raise ValueError("shard of %d images exceeds ceil(%d / %d)" % (n, total, world))
-    key = (id(engine), world, per, str(images_local.device))
-    slot = _gather_buffers.get(key)
-    if slot is None:
-        _gather_buffers.clear()
-        slot = _gather_buffers[key] = {"bufs": [torch.zeros((world, per, engine.record_words), dtype=torch.int32, device=images_local.device)
-                                                for _ in range(2)], "turn": 0}
-    buf = slot["bufs"][slot["turn"]]
-    slot["turn"] ^= 1
-    engine.forward(images_local, records=buf[rank, :n])
-    if on_forward_done is not None:
-        on_forward_done()
-    inplace = dist.get_backend(group) == "nccl"
-    got = gather_records(buf[rank] if inplace else buf[rank].clone(), group, out=buf.view(world * per, -1))
-    if per == n and (total is None or total % world == 0):
-        return unpack_detections(got)
-    g3 = got.view(world, per, -1)
-    rows = [g3[r, :shard_range(total, r, world)[1] - shard_range(total, r, world)[0]] for r in range(world)]
-    return unpack_detections(torch.cat(rows, 0))
+
+    def gather(per):
+        key = (id(engine), world, per, str(images_local.device))
+        slot = _gather_buffers.get(key)
+        if slot is None:
+            _gather_buffers.clear()
+            slot = _gather_buffers[key] = {"bufs": [torch.zeros((world, per, engine.record_words), dtype=torch.int32,
+                                                                device=images_local.device) for _ in range(2)], "turn": 0}
+        buf = slot["bufs"][slot["turn"]]
+        slot["turn"] ^= 1
+        engine.forward(images_local, records=buf[rank, :n])
+        if on_forward_done is not None:
+            on_forward_done()
+        inplace = dist.get_backend(group) == "nccl"
+        return gather_records(buf[rank] if inplace else buf[rank].clone(), group, out=buf.view(world * per, -1))
+    return _gather_shards(n, total, world, gather)
 
 
 # ----------------------------------------------------------------------------- mixed sizes: round-robin chunks of a stream
@@ -288,26 +287,6 @@ def _all_gather_ints(values, group, device):
     return out.cpu().numpy()
 
 
-def mixed_batches(engine, shapes, max_batch):
-    """detect_many's batching of a list of frame sizes [(H, W)...]: groups by network shape, each group as batches of
-    `max_batch` frames and its halvings only (one layer plan per (shape, batch size)).  Returns lists of list positions."""
-    sizes, b = [], max_batch
-    while b >= 1:
-        sizes.append(b)
-        b //= 2
-    groups = {}
-    for i, (h, w) in enumerate(shapes):
-        groups.setdefault(engine.network_shape(int(h), int(w)), []).append(i)
-    parts = []
-    for idx in groups.values():
-        k = 0
-        for b in sizes:
-            while len(idx) - k >= b:
-                parts.append(idx[k:k + b])
-                k += b
-    return parts
-
-
 _mixed_buffers = {}
 
 
@@ -330,11 +309,7 @@ def detect_many_sharded(detector, images, group=None, score_threshold=0.1, max_b
     eng = detector.engine
     if eng.precision != "f32":
         raise ValueError("detect_many_sharded runs in mode f32 (the precision of detect_many's batched path)")
-    imgs = [np.asarray(im) for im in images]
-    for im in imgs:
-        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-            raise ValueError("every image must be a uint8 array of shape [height, width, 3]")
-    max_batch = max(1, min(int(max_batch), eng.MIXED_MAX))
+    imgs = [host_frame(im, "every image") for im in images]
     chunk = max(1, int(chunk))
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     on_device = dist.get_backend(group) == "nccl"
@@ -365,7 +340,6 @@ def detect_many_sharded(detector, images, group=None, score_threshold=0.1, max_b
             buf = torch.zeros((need,), dtype=torch.int32)
         _mixed_buffers[key] = buf
     results = [[None] * int(c) for c in counts]
-    T = (words - 1) // 6
     with eng.lock:
         for k in range(rounds):
             per = int(min(chunk, max(int(c) - k * chunk for c in counts)))
@@ -380,12 +354,7 @@ def detect_many_sharded(detector, images, group=None, score_threshold=0.1, max_b
             host = got.cpu().numpy() if on_device else got.numpy()
             for r in range(world):
                 n_r = int(min(chunk, max(int(counts[r]) - k * chunk, 0)))
-                rec = host[r, :n_r]
-                boxes = rec[:, :4 * T].view(np.float32).reshape(n_r, T, 4)
-                scores = rec[:, 4 * T:5 * T].view(np.float32)
-                labels, num = rec[:, 5 * T:6 * T], rec[:, 6 * T]
+                boxes, labels, scores, num = split_records(host[r, :n_r])
                 for j in range(n_r):
-                    n = int(num[j])
-                    keep = scores[j][:n] > score_threshold           # inference/detector.py:54-58
-                    results[r][int(orders[r, k * chunk + j])] = (boxes[j][:n][keep], labels[j][:n][keep], scores[j][:n][keep])
+                    results[r][int(orders[r, k * chunk + j])] = score_filter(boxes[j], labels[j], scores[j], num[j], score_threshold)
     return [x for per_rank in results for x in per_rank]

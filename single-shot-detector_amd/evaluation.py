@@ -17,7 +17,8 @@ import numpy as np
 
 from .coco_eval import Evaluator
 from .config import load_loss_config
-from .ssd import AnchorGenerator, batch_multiclass_non_max_suppression, network_input_size, ssd_loss, _torch
+from .ssd import (AnchorGenerator, batch_multiclass_non_max_suppression, mixed_batches, network_input_size, split_records,
+                  ssd_loss, _torch)
 
 _METRIC_NAMES = ("AP", "precision", "recall", "mean_iou_for_TP", "best_threshold", "total_FP", "total_FN")   # metrics.py:84-100
 
@@ -120,9 +121,9 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
     returns the one-process dict, float for float."""
     from concurrent.futures import ThreadPoolExecutor
     from . import tfrecords
+    from .distributed import ChunkAssignment
     lc = load_loss_config(config)
     eng = detector.engine
-    max_batch = max(1, min(int(max_batch), eng.MIXED_MAX))
     reg = detector.regularization_loss(lc["weight_decay"])
     if decode is None:
         def decode(x):
@@ -138,25 +139,21 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
     sums = np.zeros(4, np.float64)
     count = 0
     workers = max(1, int(read_workers if read_workers is not None else min(16, os.cpu_count() or 1)))
+    if group is None:
+        world, rank = 1, 0
+    else:
+        import torch.distributed as dist
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+    assign = ChunkAssignment(world, rank, chunk)
 
     def run_items(items):
         """(frame, boxes, labels) triples -> _Run's per-image results, in the order of `items`."""
-        groups = {}
-        for i, (frame, _gb, _gl) in enumerate(items):
-            groups.setdefault(eng.network_shape(frame.shape[0], frame.shape[1]), []).append(i)
         results = [None] * len(items)
-        for part in groups.values():
-            # batches of max_batch and its halvings only, like Detector.detect_many: one layer plan per (shape, batch size)
-            k, b = 0, max_batch
-            while k < len(part):
-                while len(part) - k < b:
-                    b //= 2
-                sub = part[k:k + b]
-                k += b
-                with eng.lock:
-                    res = run([items[i][0] for i in sub], [(items[i][1], items[i][2]) for i in sub], lc)
-                for i, r in zip(sub, res):
-                    results[i] = r
+        for part in mixed_batches(eng, [frame.shape[:2] for frame, _gb, _gl in items], max_batch):
+            with eng.lock:
+                res = run([items[i][0] for i in part], [(items[i][1], items[i][2]) for i in part], lc)
+            for i, r in zip(part, res):
+                results[i] = r
         return results
 
     def add(result, gl):
@@ -167,22 +164,25 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
         count += 1
         evaluator.add_image(gt_scaled, gl, bx, lb, sc)
 
-    def consume(items):
-        for result, (_f, _gb, gl) in zip(run_items(items), items):      # in dataset order
+    def flush(items):
+        """One round: this rank's chunk of `items` decoded and run, every rank's results exchanged, all fed in dataset order."""
+        own = [(f.result(), gb, gl) for f, gb, gl in items[rank * chunk:(rank + 1) * chunk]]
+        results = run_items(own)
+        if group is not None:
+            results = _exchange(eng, own, results, items, group, chunk)
+        for result, (_f, _gb, gl) in zip(results, items):
             add(result, gl)
 
-    if group is None:
-        with ThreadPoolExecutor(max_workers=workers) as pool:
-            pending = []
-            for img, gb, gl in data:
-                pending.append((pool.submit(decode, img), gb, gl))
-                if len(pending) == chunk:
-                    consume([(f.result(), gb_, gl_) for f, gb_, gl_ in pending])
-                    pending = []
-            if pending:
-                consume([(f.result(), gb_, gl_) for f, gb_, gl_ in pending])
-    else:
-        _sharded_rounds(eng, data, decode, workers, run_items, add, group, chunk)
+    # round k is images [k * world * chunk, (k + 1) * world * chunk) of the stream: a chunk per rank (world 1: the whole round)
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        items = []
+        for i, (img, gb, gl) in enumerate(data):
+            items.append((pool.submit(decode, img) if assign.mine(i) else None, gb, gl))
+            if len(items) == world * chunk:
+                flush(items)
+                items = []
+        if items:
+            flush(items)
     if count == 0:
         raise ValueError("the validation dataset is empty")
     means = sums / count
@@ -198,57 +198,35 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
     return out
 
 
-def _sharded_rounds(eng, data, decode, workers, run_items, add, group, chunk):
-    """evaluate()'s loop over the ranks of `group`.  Round k is images [k * world * chunk, (k + 1) * world * chunk) of the
-    stream; rank r decodes and runs the r-th chunk of it (the same chunks, so the same batches, as one process), packs one
-    row per image -- int32 words: the ssd_loss row (localization sum, classification sum, matches: 3 x f32), the frame's
-    height and width, the predictions' boxes [T,4] f32, scores [T] f32, labels [T] i32, count -- and one all-gather of
-    [world, chunk, 6T+6] hands every rank the whole round, which is then fed to `add` in dataset order (the groundtruth
-    boxes are scaled by the frame's box_scaler here, as _Run scales them)."""
-    from concurrent.futures import ThreadPoolExecutor
+def _exchange(eng, own, results, items, group, chunk):
+    """evaluate()'s all-gather of one round over the ranks of `group`: this rank's `results` (of its decoded frames `own`) ->
+    every rank's, in the order of the round's `items`.  One row per image: 5 prefix words -- the ssd_loss row (localization
+    sum, classification sum, matches: 3 x f32), the frame's height and width -- then the predictions as an ordinary record
+    (split_records); one all-gather of [world * chunk, 5 + 6T+1] int32.  The groundtruth boxes are scaled by the frame's
+    box_scaler here, as _Run scales them."""
     import torch.distributed as dist
-    from .distributed import ChunkAssignment, gather_records
+    from .distributed import gather_records
     torch = _torch()
     world, rank = dist.get_world_size(group), dist.get_rank(group)
-    assign = ChunkAssignment(world, rank, chunk)
-    p = eng.params
-    T = int(p["num_classes"]) * int(p["max_boxes_per_class"])
-    words = 6 + 6 * T
+    per = min(chunk, len(items))
+    rows = np.zeros((per, 5 + eng.record_words), np.int32)
+    boxes, labels, scores, num = split_records(rows[:, 5:])
+    for j, ((frame, _gb, _gl), (row, _s, (bx, lb, sc))) in enumerate(zip(own, results)):
+        n = len(sc)
+        rows[j, 0:3] = np.asarray(row[:3], np.float32).view(np.int32)
+        rows[j, 3:5] = frame.shape[:2]
+        boxes[j, :n], labels[j, :n], scores[j, :n], num[j] = bx, lb, sc, n
     dev = torch.device("cuda", eng.device) if dist.get_backend(group) == "nccl" else torch.device("cpu")
-
-    def flush(items):
-        per = min(chunk, len(items))
-        own = items[rank * chunk:(rank + 1) * chunk]
-        rows = np.zeros((per, words), np.int32)
-        if own:
-            frames = [(f.result(), gb, gl) for f, gb, gl in own]
-            for j, ((frame, _gb, _gl), (row, _s, (bx, lb, sc))) in enumerate(zip(frames, run_items(frames))):
-                n = len(sc)
-                rows[j, 0:3] = np.asarray(row[:3], np.float32).view(np.int32)
-                rows[j, 3:5] = frame.shape[:2]
-                rows[j, 5:5 + 4 * n] = np.asarray(bx, np.float32).reshape(-1).view(np.int32)
-                rows[j, 5 + 4 * T:5 + 4 * T + n] = np.asarray(sc, np.float32).view(np.int32)
-                rows[j, 5 + 5 * T:5 + 5 * T + n] = np.asarray(lb, np.int32)
-                rows[j, 5 + 6 * T] = n
-        got = gather_records(torch.from_numpy(rows).to(dev), group).cpu().numpy().reshape(world, per, words)
-        for q, (_f, gb, gl) in enumerate(items):
-            r, j = divmod(q, chunk)
-            w = got[r, j]
-            n = int(w[5 + 6 * T])
-            bs = network_input_size(int(w[3]), int(w[4]), p["min_dimension"])[2]
-            add((w[0:3].view(np.float32), np.asarray(gb, np.float32).reshape(-1, 4) * bs,
-                 (w[5:5 + 4 * n].view(np.float32).reshape(n, 4), w[5 + 5 * T:5 + 5 * T + n],
-                  w[5 + 4 * T:5 + 4 * T + n].view(np.float32))), gl)
-
-    with ThreadPoolExecutor(max_workers=workers) as pool:
-        items = []
-        for i, (img, gb, gl) in enumerate(data):
-            items.append((pool.submit(decode, img) if assign.mine(i) else None, gb, gl))
-            if len(items) == world * chunk:
-                flush(items)
-                items = []
-        if items:
-            flush(items)
+    got = gather_records(torch.from_numpy(rows).to(dev), group).cpu().numpy()
+    boxes, labels, scores, num = split_records(got[:, 5:])
+    out = []
+    for q, (_f, gb, _gl) in enumerate(items):
+        r, j = divmod(q, chunk)
+        i, n = r * per + j, int(num[r * per + j])
+        bs = network_input_size(int(got[i, 3]), int(got[i, 4]), eng.params["min_dimension"])[2]
+        out.append((got[i, 0:3].view(np.float32), np.asarray(gb, np.float32).reshape(-1, 4) * bs,
+                    (boxes[i, :n], labels[i, :n], scores[i, :n])))
+    return out
 
 
 def main(argv=None):

@@ -365,6 +365,74 @@ def ssd_loss(logits, encoded_boxes, anchors, groundtruth, gamma=2.0, alpha=0.25,
     return losses, per_image
 
 
+# ----------------------------------------------------------------------------- records, frames, batches
+def split_records(rec):
+    """(boxes [B,T,4] f32, labels [B,T] i32, scores [B,T] f32, num_boxes [B] i32) as VIEWS of a record block [B, 6T+1] (torch
+    tensor or numpy array, int32): no copy, no launch.  One image's record, in 32-bit words:
+        boxes [T,4] f32 | scores [T] f32 | labels [T] i32 | num_boxes i32        (include/ssd_hip.h, ssd_record_words)"""
+    B, words = rec.shape
+    T = (words - 1) // 6
+    if isinstance(rec, np.ndarray):
+        return (rec[:, :4 * T].view(np.float32).reshape(B, T, 4), rec[:, 5 * T:6 * T], rec[:, 4 * T:5 * T].view(np.float32),
+                rec[:, 6 * T])
+    import torch
+    return (rec[:, :4 * T].view(torch.float32).unflatten(1, (T, 4)), rec[:, 5 * T:6 * T], rec[:, 4 * T:5 * T].view(torch.float32),
+            rec[:, 6 * T])
+
+
+def pack_records(boxes, labels, scores, num, out=None):
+    """The inverse of split_records: boxes [B,T,4], labels [B,T], scores [B,T], num_boxes [B] -> a record block [B, 6T+1]
+    (`out`, or a new one beside `scores`: torch or numpy like it)."""
+    B, T = scores.shape
+    if out is None:
+        if isinstance(scores, np.ndarray):
+            out = np.empty((B, 6 * T + 1), np.int32)
+        else:
+            import torch
+            out = torch.empty((B, 6 * T + 1), dtype=torch.int32, device=scores.device)
+    for view, part in zip(split_records(out), (boxes, labels, scores, num)):
+        view[...] = part
+    return out
+
+
+def host_frame(image, name="image"):
+    """np.asarray(image), refused unless it is one host frame: uint8 [height, width, 3]."""
+    image = np.asarray(image)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("%s must be a uint8 array of shape [height, width, 3]" % name)
+    return image
+
+
+def score_filter(boxes, labels, scores, num_boxes, score_threshold):
+    """inference/detector.py:54-58 for one image: of its first num_boxes rows, those with score > score_threshold, in order
+    (boolean indexing copies) -> (boxes, labels, scores)."""
+    n = int(num_boxes)
+    keep = scores[:n] > score_threshold
+    return boxes[:n][keep], labels[:n][keep], scores[:n][keep]
+
+
+def mixed_batches(engine, shapes, max_batch):
+    """The batch plan of a list of frame sizes [(H, W)...] on `engine` (anything with network_shape and MIXED_MAX): the frames
+    are grouped by network shape and every group is cut into batches of `max_batch` (clamped to [1, MIXED_MAX]) and its
+    halvings only -- a group of 56 at max_batch 32 runs as 32 + 16 + 8: the library keeps one layer plan per (network shape,
+    batch size), and a stream of arbitrary remainders must not build one for every size.  Returns lists of list positions."""
+    sizes, b = [], max(1, min(int(max_batch), engine.MIXED_MAX))
+    while b >= 1:
+        sizes.append(b)
+        b //= 2
+    groups = {}
+    for i, (h, w) in enumerate(shapes):
+        groups.setdefault(engine.network_shape(int(h), int(w)), []).append(i)
+    parts = []
+    for idx in groups.values():
+        k = 0
+        for b in sizes:
+            while len(idx) - k >= b:
+                parts.append(idx[k:k + b])
+                k += b
+    return parts
+
+
 # ----------------------------------------------------------------------------- whole graph
 class Engine:
     """Owns one ssd_handle: weights + workspace on one GPU.  `forward` is the frozen
@@ -472,11 +540,7 @@ class Engine:
             return boxes, labels, scores, num
         if records is None:
             records = self.new_records(B, images.device)
-        if records.dtype != torch.int32 or tuple(records.shape) != (B, self.record_words) or not records.is_contiguous():
-            raise ValueError("records must be a contiguous int32 tensor [B, %d]" % self.record_words)
-        if not (records.is_cuda or records.is_pinned()):
-            # the GPU writes through this pointer: pageable host memory would fault inside the kernel
-            raise ValueError("records must live in device memory or in pinned host memory")
+        self._check_records(records, B)
         with self.lock:
             check(lib().ssd_forward_records(self._h, _ptr(images), B, H, W, _ptr(records), _stream(torch)))
         return self.record_views(records)
@@ -491,20 +555,17 @@ class Engine:
 
     def record_views(self, rec):
         """(boxes [B,T,4] f32, labels [B,T] i32, scores [B,T] f32, num_boxes [B] i32) as VIEWS of a record block [B, 6T+1]
-        (torch tensor or numpy array): no copy."""
-        T = self.T
-        B = rec.shape[0]
-        if isinstance(rec, np.ndarray):
-            return (rec[:, :4 * T].view(np.float32).reshape(B, T, 4), rec[:, 5 * T:6 * T], rec[:, 4 * T:5 * T].view(np.float32),
-                    rec[:, 6 * T])
-        torch = _torch()
-        return (rec[:, :4 * T].view(torch.float32).unflatten(1, (T, 4)), rec[:, 5 * T:6 * T],
-                rec[:, 4 * T:5 * T].view(torch.float32), rec[:, 6 * T])
+        (torch tensor or numpy array): no copy (split_records)."""
+        return split_records(rec)
 
-    def _new_outputs(self, torch, B, dev):
-        """(record block [B, 6T+1], its four views)."""
-        block = self.new_records(B, dev)
-        return block, self.record_views(block)
+    def _check_records(self, records, B):
+        """The records argument of a forward: the GPU writes B records through its pointer."""
+        torch = _torch()
+        if records.dtype != torch.int32 or tuple(records.shape) != (B, self.record_words) or not records.is_contiguous():
+            raise ValueError("records must be a contiguous int32 tensor [B, %d]" % self.record_words)
+        if not (records.is_cuda or records.is_pinned()):
+            # pageable host memory would fault inside the kernel
+            raise ValueError("records must live in device memory or in pinned host memory")
 
     def _out_slot(self, B, index=0):
         """Persistent result buffers of one BATCH SIZE: the device record block, its pinned host copy and numpy / tensor views
@@ -513,10 +574,9 @@ class Engine:
         torch = _torch()
         slot = self._static.get(("out", B, index))
         if slot is None:
-            dev = "cuda:%d" % self.device
-            block, views = self._new_outputs(torch, B, dev)
+            block = self.new_records(B, "cuda:%d" % self.device)
             pin_out = torch.empty(block.shape, dtype=torch.int32).pin_memory()
-            slot = {"block": block, "views": views, "pin_out": pin_out, "host": self.record_views(pin_out.numpy())}
+            slot = {"block": block, "views": self.record_views(block), "pin_out": pin_out, "host": self.record_views(pin_out.numpy())}
             while sum(1 for k in self._static if k[0] == "out") >= 32:
                 self._static.pop(next(k for k in self._static if k[0] == "out"))
             self._static[("out", B, index)] = slot
@@ -578,18 +638,29 @@ class Engine:
         with self.lock:
             src = np.ascontiguousarray(images)
             B, H, W, _ = src.shape
-            slot = self._out_slot(B)
-            # ssd_forward_host: staging copy + upload in pieces (one C loop) and the forward, on the current stream.  One image:
-            # post_pack_kernel writes its 48 KB record into the pinned block itself (16-byte rows over PCIe) -- no
-            # device-to-host copy behind the forward.  (Records are 48 004 bytes: those of further images are not 16-byte
-            # aligned and would cross the bus in 4-byte writes -- they go through the device block and one copy.)
-            zc = B <= self.zero_copy_max_batch
-            rec = slot["pin_out"] if zc else slot["block"]
-            check(lib().ssd_forward_host(self._h, src.ctypes.data, B, H, W, _ptr(rec), _stream(torch)))
-            if not zc:
-                slot["pin_out"].copy_(slot["block"], non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            return slot["host"]
+            # ssd_forward_host: staging copy + upload in pieces (one C loop) and the forward, on the current stream
+            return self._host_result(self._out_slot(B), B, lambda rec: check(
+                lib().ssd_forward_host(self._h, src.ctypes.data, B, H, W, _ptr(rec), _stream(torch))))
+
+    def _host_result(self, slot, B, enqueue, wait=True):
+        """The way back of a host-fed call into result `slot` (the caller holds the lock).  `enqueue(records)` writes the B
+        records: up to zero_copy_max_batch images straight into the pinned block -- post_pack_kernel writes a 48 KB record over
+        PCIe itself, no device-to-host copy behind the forward (records are 48 004 bytes: those of further images are not
+        16-byte aligned and would cross the bus in 4-byte writes) -- else into the device block and ONE copy to the pinned one.
+        Then one wait and the numpy views of the pinned block, or with wait=False the slot right after enqueuing (slot["done"]:
+        an event behind the copy, slot["host"]: the views it makes valid)."""
+        torch = _torch()
+        zc = B <= self.zero_copy_max_batch
+        enqueue(slot["pin_out"] if zc else slot["block"])
+        if not zc:
+            slot["pin_out"].copy_(slot["block"], non_blocking=True)
+        if not wait:
+            if slot.get("done") is None:
+                slot["done"] = torch.cuda.Event()
+            slot["done"].record()
+            return slot
+        torch.cuda.current_stream().synchronize()
+        return slot["host"]
 
     def detect_one(self, image, score_threshold):
         """inference/detector.py:33-58 for one host frame [H,W,3] as ONE library call (ssd_detect_host): staging copy + upload,
@@ -625,6 +696,8 @@ class Engine:
         current stream."""
         torch = _torch()
         with self.lock:
+            if records is not None:         # (first: a refused call copies and launches nothing)
+                self._check_records(records, len(frames[1]) if isinstance(frames, tuple) else len(frames))
             if isinstance(frames, tuple):
                 flat, hw, offsets = frames
                 _check_dev(torch, flat, torch.uint8, "frames")
@@ -643,8 +716,6 @@ class Engine:
             B = len(hw)
             if records is None:
                 records = self.new_records(B, flat.device)
-            if records.dtype != torch.int32 or tuple(records.shape) != (B, self.record_words) or not records.is_contiguous():
-                raise ValueError("records must be a contiguous int32 tensor [B, %d]" % self.record_words)
             hw_c = (ctypes.c_int32 * (2 * B))(*[v for pair in hw for v in pair])
             off_c = (ctypes.c_int64 * B)(*offsets) if offsets is not None else None
             check(lib().ssd_forward_mixed(self._h, _ptr(flat), B, hw_c, off_c, _ptr(records), _stream(torch)))
@@ -657,49 +728,33 @@ class Engine:
         wait=False: returns the result slot right after enqueuing (slot["done"]: an event behind the copy, slot["host"]: the views
         it makes valid) -- the caller stages the next batch while this one computes (Detector.detect_many; `index` picks one of
         several result slots of this batch size)."""
-        torch = _torch()
-        B = len(images)
         with self.lock:
-            srcs = [np.ascontiguousarray(im) for im in images]
-            for im in srcs:
-                if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                    raise ValueError("every image must be a uint8 array of shape [height, width, 3]")
-            slot = self._out_slot(B, index)
-            zc = B <= self.zero_copy_max_batch
-            rec = slot["pin_out"] if zc else slot["block"]
-            ptrs = (ctypes.c_void_p * B)(*[im.ctypes.data for im in srcs])
-            hw_c = (ctypes.c_int32 * (2 * B))(*[int(v) for im in srcs for v in im.shape[:2]])
-            check(lib().ssd_forward_mixed_host(self._h, ptrs, B, hw_c, _ptr(rec), _stream(torch)))
-            if not zc:
-                slot["pin_out"].copy_(slot["block"], non_blocking=True)
-            if not wait:
-                if slot.get("done") is None:
-                    slot["done"] = torch.cuda.Event()
-                slot["done"].record()
-                return slot
-            torch.cuda.current_stream().synchronize()
-            return slot["host"]
+            enqueue = self._mixed_host_call(images)
+            return self._host_result(self._out_slot(len(images), index), len(images), enqueue, wait)
 
     def forward_mixed_host(self, images, records):
         """A list of host uint8 arrays [H_b, W_b, 3] of different sizes that share a network shape, written as B records into
         `records` (a contiguous int32 tensor [B, 6T+1] in device memory or pinned host memory, e.g. this rank's slice of an
         all-gather's receive buffer): ONE call of ssd_forward_mixed_host, asynchronous on the current stream (the frames may
         be reused on return).  Returns the four views of `records`."""
-        torch = _torch()
-        B = len(images)
         with self.lock:
-            srcs = [np.ascontiguousarray(im) for im in images]
-            for im in srcs:
-                if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                    raise ValueError("every image must be a uint8 array of shape [height, width, 3]")
-            if records.dtype != torch.int32 or tuple(records.shape) != (B, self.record_words) or not records.is_contiguous():
-                raise ValueError("records must be a contiguous int32 tensor [B, %d]" % self.record_words)
-            if not (records.is_cuda or records.is_pinned()):
-                raise ValueError("records must live in device memory or in pinned host memory")
+            enqueue = self._mixed_host_call(images)
+            self._check_records(records, len(images))
+            enqueue(records)
+            return self.record_views(records)
+
+    def _mixed_host_call(self, images):
+        """Checks the host frames and builds their ctypes arguments -> enqueue(records): the ssd_forward_mixed_host call on the
+        current stream (the frames must stay alive until it returns)."""
+        torch = _torch()
+        srcs = [np.ascontiguousarray(host_frame(im, "every image")) for im in images]
+
+        def enqueue(records):
+            B = len(srcs)
             ptrs = (ctypes.c_void_p * B)(*[im.ctypes.data for im in srcs])
             hw_c = (ctypes.c_int32 * (2 * B))(*[int(v) for im in srcs for v in im.shape[:2]])
             check(lib().ssd_forward_mixed_host(self._h, ptrs, B, hw_c, _ptr(records), _stream(torch)))
-            return self.record_views(records)
+        return enqueue
 
     def detect_stream(self, batches):
         """Host-fed steady-state serving: an iterable of host uint8 arrays [B,H,W,3] (any mix of sizes) -> a generator of

@@ -72,6 +72,8 @@ def test_mixed_batch_refusals_and_limits(cuda, ssd):
         eng.detect_host_mixed([_frame(128, 200)] * 65)
     with pytest.raises(ValueError):
         eng.detect_host_mixed([_frame(128, 200).astype(np.float32)])
+    with pytest.raises(ValueError, match="pinned host memory"):     # pageable records: refused before any copy or launch
+        eng.forward_mixed([cuda.from_numpy(_frame(128, 200)).cuda()], records=cuda.zeros((1, eng.record_words), dtype=cuda.int32))
     # the largest batch the argument table holds, with sub-batch plans forced (option nsub): every image equals its own run
     frames = [_frame(*TINY_SIZES[i % len(TINY_SIZES)], seed=i) for i in range(64)]
     ref = {}

@@ -138,6 +138,10 @@ def test_coco_eval_sharded_gloo_equals_one_process(tmp_path):
     one = coco_eval.evaluate(sharding_stub.StubDetector(T=7), gt, "", read_image=store.__getitem__,
                              predictions_json=str(tmp_path / "pred_w1.json"), max_batch=4, read_workers=2)
     assert one[0] > 0
+    det, mapping = sharding_stub.StubDetector(T=7), coco_eval.integer_to_coco_id(gt["categories"])
+    rows = [r for m in sorted(gt["images"], key=lambda m: m["id"])
+            for r in coco_eval.detection_records(det, store[m["file_name"]], m["id"], mapping, 0.15)]
+    assert (tmp_path / "pred_w1.json").read_bytes() == json.dumps(rows).encode()
     for world in (2, 3):
         per_rank = _spawn(world, str(tmp_path))
         for stats in per_rank:
