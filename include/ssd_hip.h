@@ -424,6 +424,30 @@ int ssd_loss(const float *logits_dev, const float *codes_dev, const float *ancho
              const float *gt_boxes_dev, const int32_t *gt_labels_dev, const int32_t *gt_num_dev, int32_t G,
              const ssd_loss_config *cfg, float *per_image_dev, float *losses_dev, float *cls_losses_dev,
              float *loc_losses_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* The gradient of ssd_loss's losses_dev = (localization_loss, classification_loss) with respect to logits_dev [B,N,C] and
+ * codes_dev [B,N,4], given the targets of ssd_training_targets (reg_targets_dev [B,N,4], cls_targets_dev [B,N],
+ * matches_dev [B,N]) and ssd_loss's per_image_dev (row stride per_image_stride = 3 + n_levels floats; only column 2, the
+ * matches, is read).  norm = max(sum over b of per_image[b][2], 1), the fp32 value ssd_loss divides by, is a constant
+ * (as in TF: it depends only on the matching).  g = grad_losses_dev[0..1] (device f32 [2], the upstream gradients of
+ * the two losses) or (1, 1) when NULL.  cfg supplies gamma and alpha only.
+ *   d_logits_dev [b,a,c] = 0 when matches[b,a] == -2 (ignored), otherwise, with x the logit, z = 1 for the target class
+ *     cls_targets - 1 (0 everywhere on background anchors), s = sigmoid(x), q = 1 - p_t = (z ? 1 - s : s),
+ *     alpha_z = (z ? alpha : 1 - alpha) as ssd_loss forms them, nlp = max(x,0) - x*z + log1p(exp(-|x|)):
+ *       alpha_z * (gamma * q^(gamma-1) * dq/dx * nlp + q^gamma * (s - z)) * g[1] / norm,  dq/dx = (z ? -1 : 1) * s(1-s);
+ *     where q == 0 the first term is 0 (its limit for gamma > 1).
+ *   d_codes_dev [b,a,k] = 0 when matches[b,a] < 0, otherwise, with diff = codes - reg_targets (one fp32 op as in
+ *     ssd_loss): (|diff| < 1 ? diff : sign(diff)) * g[0] / norm -- sign(diff) at |diff| == 1 (tf.where / tf.less).
+ * Precision: each element is evaluated in double from its fp32 inputs (s and 1 - s both formed from exp(-|x|) without
+ * cancellation) and rounded to fp32 once.  This is the exact derivative, not TF's autodiff chain op by op (parity with
+ * TF's gradient is unpinned, like the forward's).  No atomics: two calls give the same bits.  Every output element is
+ * written, zeros included: the caller need not clear d_logits_dev / d_codes_dev.  Enqueues only, on `stream`, under the
+ * stream ordering of ssd_loss above.  NULL pointers, B, N or C < 1, C > 4194304, per_image_stride < 3, codes_dev /
+ * reg_targets_dev / d_codes_dev not 16-byte aligned or any other pointer not 4-byte aligned: SSD_ERR_INVALID before any
+ * HIP call. */
+int ssd_loss_backward(const float *logits_dev, const float *codes_dev, int32_t B, int32_t N, int32_t C,
+                      const float *reg_targets_dev, const int32_t *cls_targets_dev, const int32_t *matches_dev,
+                      const float *per_image_dev, int32_t per_image_stride, const ssd_loss_config *cfg,
+                      const float *grad_losses_dev, float *d_logits_dev, float *d_codes_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ from .ckpt_import import (read_checkpoint, read_checkpoint_index, resolve_checkp
 from ._lib import build, lib, lib_path, SsdError, set_option, get_option                       # noqa: F401
 from .ssd import (SSD, AnchorGenerator, RetinaNetFeatureExtractor, RetinaNetBoxPredictor,     # noqa: F401
                   batch_multiclass_non_max_suppression, network_input_size, Engine,
-                  get_training_targets, ssd_loss)
+                  get_training_targets, ssd_loss, ssd_loss_backward, differentiable_loss)
 from .detector import Detector                                         # noqa: F401
 from . import coco_eval, coco_metric, tfrecords                        # noqa: F401  (evaluation: `python -m ssd_amd.evaluation`, imported on use)
 from .distributed import shard_range, all_gather_detections, detect_sharded, bind_to_gpu_numa_node  # noqa: F401

@@ -181,6 +181,8 @@ SIGNATURES = {
                                             _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "ssd_loss": (ctypes.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, ctypes.POINTER(SsdLossConfig),
                                 _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_loss_backward": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(SsdLossConfig),
+                                         _vp, _vp, _vp, _vp]),
 }
 
 

@@ -11,6 +11,12 @@
 //               double partial sums of the focal terms, and lane 0 adds the smooth-L1 term.  Per block: loc / cls sums in
 //               double (fixed shuffle tree over the 64 anchors) and match counts per level into a slab.  No float atomics.
 //   L3 sum      one block: per image the slab entries in a fixed order, per_image, then the batch in image order, losses.
+//   L4 grad     ssd_loss_backward, one block per 256 rows (anchors of the flattened [B*N]): every wave first forms the
+//               batch's normaliser from per_image[:,2] (integer counts, exact in double) and the two upstream gradients;
+//               then the block writes the rows' d_codes (one row per thread) and streams their logits once, 4 per thread
+//               in 16-byte loads / stores when C % 4 == 0 and the rows are 16-byte aligned, one per thread otherwise.
+//               exp(-|x|) is formed once per logit and gives both sigma and log1p; every element is evaluated in double
+//               and rounded once.  Each output element is written exactly once: no atomics, no clearing.
 #include "host.h"
 
 #include <cstring>
@@ -23,6 +29,9 @@ namespace {
 constexpr int L1_THREADS = 256, L1_APT = 4, L1_TILE = 256;
 constexpr int L2_THREADS = 256, L2_ANCHORS = 64, L2_TILE = 256;
 constexpr int L3_THREADS = 256;
+constexpr int L4_THREADS = 256, L4_ROWS = 256;
+constexpr int32_t L4_MAX_C = 1 << 22;        // L4_ROWS * C elements of a block stay below 2^30: 32-bit offsets in a block
+static_assert(L4_ROWS == L4_THREADS, "loss_grad writes one d_codes row per thread");
 
 struct SlabEntry {             // one per (image, L2 block)
     double loc, cls;
@@ -330,6 +339,100 @@ __global__ __launch_bounds__(L3_THREADS) void loss_sum(LossArgs p)
     }
 }
 
+// ----------------------------------------------------------------------------- L4: the gradient (ssd_loss_backward)
+struct GradArgs {
+    const float *logits, *codes, *reg_targets, *per_image, *grad;
+    const int32_t *cls_targets, *matches;
+    float *d_logits, *d_codes;
+    int64_t rows;              // B * N
+    int32_t B, C, stride;
+    double gamma, alpha, one_m_alpha;
+    int32_t vec;               // C % 4 == 0 and logits / d_logits 16-byte aligned
+};
+
+// g / norm for (localization, classification); norm = max(sum of per_image[:,2], 1) in fp32, the value L3 divides by.
+// The counts are integers: the double sum is exact in any order.  Every wave forms it itself (no barrier).
+__device__ __forceinline__ void grad_scales(const GradArgs &p, double &gl, double &gc)
+{
+    const int lane = threadIdx.x & 63;
+    double n = 0.0;
+    for (int b = lane; b < p.B; b += 64) n += (double)p.per_image[(int64_t)b * p.stride + 2];
+    for (int m = 1; m < 64; m <<= 1) n += __shfl_xor(n, m);
+    const double norm = (double)fmaxf((float)n, 1.0f);
+    gl = (p.grad ? (double)p.grad[0] : 1.0) / norm;
+    gc = (p.grad ? (double)p.grad[1] : 1.0) / norm;
+}
+
+// d focal / dx for one (anchor, class), z = 1 for the target class (include/ssd_hip.h, ssd_loss_backward):
+// alpha_z * (gamma * q^(gamma-1) * dq/dx * nlp + q^gamma * (s - z)) * gc, in double, rounded once.  s and 1 - s both come
+// from e = exp(-|x|) without cancellation: s = 1 / (1 + e) for x >= 0, e / (1 + e) otherwise.
+__device__ __forceinline__ float focal_grad(float x, bool z, const GradArgs &p, double gc)
+{
+    const double xd = x;
+    const double e = exp(-fabs(xd));
+    const double r = 1.0 / (1.0 + e);
+    const double s = xd >= 0.0 ? r : e * r, sc = xd >= 0.0 ? e * r : r;           // sigma(x), 1 - sigma(x)
+    const double nlp = ((xd >= 0.0 ? xd : 0.0) - (z ? xd : 0.0)) + log1p(e);
+    const double q = z ? sc : s;
+    const double dq = z ? -(s * sc) : s * sc;
+    const double smz = z ? -sc : s;                                                  // s - z
+    double t1, qg;
+    if (p.gamma == 2.0) {
+        t1 = 2.0 * q * dq * nlp;
+        qg = q * q;
+    } else {
+        t1 = q == 0.0 ? 0.0 : p.gamma * pow(q, p.gamma - 1.0) * dq * nlp;
+        qg = pow(q, p.gamma);
+    }
+    return (float)((z ? p.alpha : p.one_m_alpha) * (t1 + qg * smz) * gc);
+}
+
+__global__ __launch_bounds__(L4_THREADS) void loss_grad(GradArgs p)
+{
+    double gl, gc;
+    grad_scales(p, gl, gc);
+    const int t = threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * L4_ROWS;
+    const int nr = (int)min((int64_t)L4_ROWS, p.rows - r0);
+    if (t < nr) {                                                                    // d_codes: smooth-L1
+        const int64_t r = r0 + t;
+        v4f d = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (p.matches[r] >= 0) {
+            const v4f c = *(const v4f *)(p.codes + 4 * r), g = *(const v4f *)(p.reg_targets + 4 * r);
+            for (int k = 0; k < 4; ++k) {
+                const float df = c[k] - g[k];
+                const float v = fabsf(df) < 1.0f ? df : (df > 0.0f ? 1.0f : -1.0f);
+                d[k] = (float)((double)v * gl);
+            }
+        }
+        *(v4f *)(p.d_codes + 4 * r) = d;
+    }
+    const uint32_t C = (uint32_t)p.C, ne = (uint32_t)nr * C;
+    const float *lg = p.logits + r0 * p.C;
+    float *dl = p.d_logits + r0 * p.C;
+    if (p.vec) {
+        for (uint32_t j = 4 * t; j < ne; j += 4 * L4_THREADS) {
+            const uint32_t rr = j / C;
+            const int64_t r = r0 + rr;
+            v4f d = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (p.matches[r] >= -1) {
+                const int tc = (int)(p.cls_targets[r] - 1) - (int)(j - rr * C);     // the target class, relative to j
+                const v4f x = *(const v4f *)(lg + j);
+                for (int k = 0; k < 4; ++k) d[k] = focal_grad(x[k], k == tc, p, gc);
+            }
+            *(v4f *)(dl + j) = d;
+        }
+    } else {
+        for (uint32_t j = t; j < ne; j += L4_THREADS) {
+            const uint32_t rr = j / C;
+            const int64_t r = r0 + rr;
+            float d = 0.0f;
+            if (p.matches[r] >= -1) d = focal_grad(lg[j], (int)(j - rr * C) == p.cls_targets[r] - 1, p, gc);
+            dl[j] = d;
+        }
+    }
+}
+
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int32_t l2_blocks(int32_t N) { return (N + L2_ANCHORS - 1) / L2_ANCHORS; }
 
@@ -424,5 +527,37 @@ extern "C" int ssd_loss(const float *logits_dev, const float *codes_dev, const f
     p.n_levels = cfg->n_levels;
     p.per_image = per_image_dev; p.losses = losses_dev; p.cls_losses = cls_losses_dev; p.loc_losses = loc_losses_dev;
     HIPCHK(launch(p, true, (hipStream_t)stream));
+    return SSD_OK;
+}
+
+extern "C" int ssd_loss_backward(const float *logits_dev, const float *codes_dev, int32_t B, int32_t N, int32_t C,
+                                 const float *reg_targets_dev, const int32_t *cls_targets_dev, const int32_t *matches_dev,
+                                 const float *per_image_dev, int32_t per_image_stride, const ssd_loss_config *cfg,
+                                 const float *grad_losses_dev, float *d_logits_dev, float *d_codes_dev, void *stream)
+{
+    if (!logits_dev || !codes_dev || !reg_targets_dev || !cls_targets_dev || !matches_dev || !per_image_dev || !cfg ||
+        !d_logits_dev || !d_codes_dev || B < 1 || N < 1 || C < 1 || per_image_stride < 3)
+        return ssd_fail(SSD_ERR_INVALID, "ssd_loss_backward: bad arguments");
+    if (C > L4_MAX_C) return ssd_fail(SSD_ERR_INVALID, "ssd_loss_backward: more than 4194304 classes");
+    if ((int64_t)B * N * 4 >= ((int64_t)1 << 40) || (int64_t)B * N * C >= ((int64_t)1 << 40))
+        return ssd_fail(SSD_ERR_INVALID, "ssd_loss_backward: tensors too large");
+    if (!aligned16(codes_dev) || !aligned16(reg_targets_dev) || !aligned16(d_codes_dev))
+        return ssd_fail(SSD_ERR_INVALID, "ssd_loss_backward: codes, reg_targets and d_codes must be 16-byte aligned");
+    const void *word[] = {logits_dev, d_logits_dev, cls_targets_dev, matches_dev, per_image_dev, grad_losses_dev};
+    for (const void *w : word)
+        if ((uintptr_t)w & 3) return ssd_fail(SSD_ERR_INVALID, "ssd_loss_backward: misaligned pointer");
+    GradArgs p;
+    memset(&p, 0, sizeof(p));
+    p.logits = logits_dev; p.codes = codes_dev; p.reg_targets = reg_targets_dev; p.per_image = per_image_dev;
+    p.grad = grad_losses_dev; p.cls_targets = cls_targets_dev; p.matches = matches_dev;
+    p.d_logits = d_logits_dev; p.d_codes = d_codes_dev;
+    p.rows = (int64_t)B * N; p.B = B; p.C = C; p.stride = per_image_stride;
+    p.gamma = (double)cfg->gamma;                                                    // the constants of L2 (focal_term)
+    p.alpha = (double)(float)cfg->alpha;
+    p.one_m_alpha = (double)(float)(1.0 - cfg->alpha);
+    p.vec = (C & 3) == 0 && aligned16(logits_dev) && aligned16(d_logits_dev);
+    const int64_t blocks = (p.rows + L4_ROWS - 1) / L4_ROWS;
+    hipLaunchKernelGGL(loss_grad, dim3((unsigned)blocks), dim3(L4_THREADS), 0, (hipStream_t)stream, p);
+    HIPCHK(hipGetLastError());
     return SSD_OK;
 }

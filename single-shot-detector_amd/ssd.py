@@ -365,6 +365,86 @@ def ssd_loss(logits, encoded_boxes, anchors, groundtruth, gamma=2.0, alpha=0.25,
     return losses, per_image
 
 
+def ssd_loss_backward(logits, encoded_boxes, reg_targets, cls_targets, matches, per_image, gamma=2.0, alpha=0.25,
+                      grad_losses=None):
+    """The gradient of ssd_loss's losses [2] = (localization, classification) with respect to logits [B,N,C] and
+    encoded_boxes [B,N,4] on the GPU (ssd_loss_backward; semantics in include/ssd_hip.h): reg_targets, cls_targets,
+    matches from get_training_targets and per_image from ssd_loss on the same batch (the normaliser is read from its
+    matches column on the device).  grad_losses: None (= (1, 1)), or the upstream gradients of the two losses as a CUDA
+    float32 tensor of 2 elements (read on the device: no host round trip) or two numbers.  Returns (d_logits [B,N,C],
+    d_codes [B,N,4]): CUDA tensors, asynchronous on the current stream."""
+    torch = _torch()
+    for t, n in ((logits, "logits"), (encoded_boxes, "encoded_boxes"), (reg_targets, "reg_targets"), (per_image, "per_image")):
+        _check_dev(torch, t, torch.float32, n)
+    for t, n in ((cls_targets, "cls_targets"), (matches, "matches")):
+        _check_dev(torch, t, torch.int32, n)
+    B, N, C = (int(v) for v in logits.shape)
+    if (tuple(encoded_boxes.shape) != (B, N, 4) or tuple(reg_targets.shape) != (B, N, 4) or tuple(cls_targets.shape) != (B, N)
+            or tuple(matches.shape) != (B, N) or per_image.dim() != 2 or per_image.shape[0] != B or per_image.shape[1] < 3):
+        raise ValueError("shape mismatch between logits, encoded_boxes, the targets and per_image")
+    dev = logits.device
+    if grad_losses is not None:
+        grad_losses = torch.as_tensor(grad_losses, dtype=torch.float32).to(dev).reshape(2).contiguous()
+    cfg = _loss_config(POSITIVES_THRESHOLD, NEGATIVES_THRESHOLD, gamma, alpha)
+    d_logits = torch.empty((B, N, C), dtype=torch.float32, device=dev)
+    d_codes = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
+    check(lib().ssd_loss_backward(_ptr(logits), _ptr(encoded_boxes), B, N, C, _ptr(reg_targets), _ptr(cls_targets),
+                                  _ptr(matches), _ptr(per_image), int(per_image.shape[1]), ctypes.byref(cfg),
+                                  None if grad_losses is None else _ptr(grad_losses), _ptr(d_logits), _ptr(d_codes),
+                                  _stream(torch)))
+    return d_logits, d_codes
+
+
+_loss_function = None
+
+
+def _differentiable_loss_function(torch):
+    """The torch.autograd.Function behind differentiable_loss (built on first use: torch is imported lazily)."""
+    global _loss_function
+    if _loss_function is None:
+        from torch.autograd.function import once_differentiable
+
+        class SsdLossFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, logits, codes, anchors, groundtruth, gamma, alpha, anchors_per_level):
+                reg, cls, matches = get_training_targets(anchors, groundtruth["boxes"], groundtruth["labels"],
+                                                         groundtruth["num_boxes"])
+                losses, per_image = ssd_loss(logits, codes, anchors, groundtruth, gamma=gamma, alpha=alpha,
+                                             anchors_per_level=anchors_per_level)
+                ctx.save_for_backward(logits, codes, reg, cls, matches, per_image)
+                ctx.gamma, ctx.alpha = gamma, alpha
+                return losses[0], losses[1]
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, g_loc, g_cls):
+                logits, codes, reg, cls, matches, per_image = ctx.saved_tensors
+                g = torch.stack([g_loc.reshape(()), g_cls.reshape(())]).to(torch.float32)
+                d_logits, d_codes = ssd_loss_backward(logits, codes, reg, cls, matches, per_image, ctx.gamma, ctx.alpha, g)
+                return d_logits, d_codes, None, None, None, None, None
+
+        _loss_function = SsdLossFunction
+    return _loss_function
+
+
+def differentiable_loss(class_predictions, encoded_boxes, anchors, groundtruth, params, anchors_per_level=()):
+    """ssd.py:71-133 as a differentiable torch op: {'localization_loss', 'classification_loss'} (0-d CUDA tensors, bit-equal
+    to ssd_loss's) whose backward is ssd_loss_backward.  class_predictions [B,N,C] and encoded_boxes [B,N,4] are CUDA
+    float32 tensors in the reference's anchor order (non-contiguous ones are copied); anchors [N,4] (unclipped),
+    groundtruth = {'boxes', 'labels', 'num_boxes'} and params ('gamma', 'alpha': config.load_loss_config) as for ssd_loss.
+    Gradients flow to class_predictions and encoded_boxes only (anchors and groundtruth get none); the normaliser
+    max(matches over the batch, 1) is a constant, as in TF.  The backward is once-differentiable (no double backward).
+    Gradients stop at the head outputs: the tensors an Engine retains (class_predictions / encoded_boxes of a forward)
+    are plain tensors, not part of any autograd graph -- this trains a torch model that emits logits and box codes, not
+    the HIP network.  The regularisation term of train.py (weight_decay * the sum of squared weights, model.py:132-145)
+    is the caller's to add."""
+    torch = _torch()
+    fn = _differentiable_loss_function(torch)
+    loc, cls = fn.apply(class_predictions.contiguous(), encoded_boxes.contiguous(), anchors.contiguous(), groundtruth,
+                        float(params["gamma"]), float(params["alpha"]), tuple(int(n) for n in anchors_per_level))
+    return {"localization_loss": loc, "classification_loss": cls}
+
+
 # ----------------------------------------------------------------------------- records, frames, batches
 def split_records(rec):
     """(boxes [B,T,4] f32, labels [B,T] i32, scores [B,T] f32, num_boxes [B] i32) as VIEWS of a record block [B, 6T+1] (torch
