@@ -449,6 +449,51 @@ int ssd_loss_backward(const float *logits_dev, const float *codes_dev, int32_t B
                       const float *per_image_dev, int32_t per_image_stride, const ssd_loss_config *cfg,
                       const float *grad_losses_dev, float *d_logits_dev, float *d_codes_dev, void *stream);
 
+/* ---- the TRAIN input pipeline: Pipeline.augmentation after the decode (pipeline.py:117-135) ----
+ *
+ * The host decodes each JPEG and draws the image's random scalars (the crop window included: its rejection sampling reads the
+ * boxes) and does all box arithmetic; this call does every per-pixel step of a batch in ONE launch, on uint8 frames, and
+ * writes the float32 batch.  Per output element (y, x, c) of image b, with p = params[b]:
+ *   1. source pixel    sy = p.crop_y + min(floor(y * (crop_h / out_h)), crop_h - 1), sx likewise with crop_x, crop_w, out_w: the
+ *                      project's nearest-neighbour rule (the expression of front.hip front_src: floorf((float)dst * ((float)in /
+ *                      (float)out)), the division correctly rounded), applied within the crop window
+ *   2. convert         v = u8 * (float)(1.0 / 255.0)                                     (convert_image_dtype)
+ *   3. colour          if SSD_AUG_COLOR: v = clip(v + color_offset[c], 0, 1)             (other_augmentations.py:16-28)
+ *   4. grayscale       if SSD_AUG_GRAY: g = (R * 0.2989f + G * 0.5870f) + B * 0.1140f to all three channels (rgb_to_grayscale's
+ *                      weights; the summation order is this library's choice)
+ *   5. pixel scale     if SSD_AUG_SCALE: Philox4x32-10 with key philox_key (word 0 = the low 32 bits) on the counter
+ *                      (y * out_w + x, 0, 0, 0), (y, x) the output position BEFORE the flip; word c for channel c becomes
+ *                      u = as_float(0x3f800000 | (w & 0x7fffff)) - 1 (TF's Uint32ToFloat), then
+ *                      v = clip(v * (u * scale_range + scale_min), 0, 1)                 (other_augmentations.py:101-106)
+ *   6. flip            if SSD_AUG_FLIP: the element is stored to column out_w - 1 - x    (tf.image.flip_left_right)
+ * Every step is one fp32 op at a time, without contraction (a numpy restatement is bit-exact); clip = min(max(v, 0), 1).  These
+ * choices are single-sourced here and unpinned against TF.  An image's output depends on its own
+ * parameters and frame only: not on its position in the batch, on B, or on the stream.
+ *   images_dev   base pointer of the frames: frame b is uint8 [height, width, 3] (HWC, RGB) at byte offset params[b].offset; any
+ *                size, any byte offset (bytes are gathered as bytes)
+ *   params_host  the B parameter rows, read by this call to refuse bad ones; params_dev: the same rows in device memory (8-byte
+ *                aligned), which the kernel reads -- the caller's upload, ordered before this call on `stream`
+ *   out_dev      float32 [B, out_h, out_w, 3], or [B, 3, out_h, out_w] when channels_first != 0 (DATA_FORMAT); 16-byte aligned;
+ *                every element is written
+ * out_h and out_w: positive multiples of 128 (pipeline.py:32-33), out_h * out_w < 2^31.  Null pointers, B < 1, other sizes, a frame
+ * with height or width < 1 or a negative offset, an empty crop window or one that leaves the frame, unknown flags:
+ * SSD_ERR_INVALID before any HIP call.  Needs no handle; asynchronous on `stream`. */
+#define SSD_AUG_COLOR 1
+#define SSD_AUG_GRAY 2
+#define SSD_AUG_SCALE 4
+#define SSD_AUG_FLIP 8
+typedef struct ssd_augment_params {          /* 64 bytes, no padding */
+    int64_t offset;                          /* byte offset of the frame from images_dev                      */
+    int32_t height, width;                   /* the frame                                                     */
+    int32_t crop_y, crop_x, crop_h, crop_w;  /* the crop window in the frame's pixels                         */
+    int32_t flags;                           /* SSD_AUG_* bits                                                */
+    float color_offset[3];                   /* R, G, B offsets (SSD_AUG_COLOR)                               */
+    float scale_min, scale_range;            /* minval, maxval - minval of random_pixel_value_scale (SSD_AUG_SCALE) */
+    uint64_t philox_key;                     /* the image's Philox key (SSD_AUG_SCALE)                        */
+} ssd_augment_params;
+int ssd_augment(const uint8_t *images_dev, const ssd_augment_params *params_host, const ssd_augment_params *params_dev, int32_t B,
+                int32_t out_h, int32_t out_w, int32_t channels_first, float *out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

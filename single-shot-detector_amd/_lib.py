@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
-            "elementwise.hip", "postprocess.hip", "loss.hip"]
+            "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip"]
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
 _lib = None
@@ -183,6 +183,7 @@ SIGNATURES = {
                                 _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "ssd_loss_backward": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(SsdLossConfig),
                                          _vp, _vp, _vp, _vp]),
+    "ssd_augment": (ctypes.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
 }
 
 

@@ -54,3 +54,25 @@ def load_loss_config(path_or_dict):
     if missing:
         raise KeyError("config is missing the key %r" % missing[0])
     return {k: float(raw[k]) for k in LOSS_KEYS}
+
+
+TRAIN_KEYS = ("batch_size", "image_height", "image_width")
+
+
+def load_train_config(path_or_dict):
+    """The keys of the reference's JSON config that the TRAIN input pipeline reads (pipeline.py:28-33): a dict with exactly
+    TRAIN_KEYS as ints.  image_height and image_width must be positive multiples of 128 (DIVISOR, pipeline.py:32-33)."""
+    if isinstance(path_or_dict, dict):
+        raw = dict(path_or_dict)
+    else:
+        with open(path_or_dict) as f:
+            raw = json.load(f)
+    missing = [k for k in TRAIN_KEYS if k not in raw]
+    if missing:
+        raise KeyError("config is missing the key %r" % missing[0])
+    out = {k: int(raw[k]) for k in TRAIN_KEYS}
+    if out["batch_size"] < 1:
+        raise ValueError("batch_size must be >= 1")
+    if min(out["image_height"], out["image_width"]) < 128 or out["image_height"] % 128 or out["image_width"] % 128:
+        raise ValueError("image_height and image_width must be positive multiples of 128 (pipeline.py:32-33)")
+    return out

@@ -126,13 +126,7 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
     eng = detector.engine
     reg = detector.regularization_loss(lc["weight_decay"])
     if decode is None:
-        def decode(x):
-            if isinstance(x, np.ndarray):
-                return x
-            import io
-            from PIL import Image
-            with Image.open(io.BytesIO(x)) as im:
-                return np.asarray(im.convert("RGB"), dtype=np.uint8)
+        decode = tfrecords.decode_image
     data = tfrecords.read_dataset(val_dataset) if isinstance(val_dataset, (str, os.PathLike)) else val_dataset
     evaluator = Evaluator(int(eng.params["num_classes"]))
     run = _Run(eng)

@@ -116,3 +116,14 @@ def read_dataset(dataset_path, verify=True):
     for path in shard_paths(dataset_path):
         for r in read_records(path, verify=verify):
             yield read_example(r)
+
+
+def decode_image(x):
+    """The decode of the pipelines (tf.image.decode_jpeg(channels=3)): JPEG bytes -> uint8 [H, W, 3] through PIL; an array
+    passes through."""
+    if isinstance(x, np.ndarray):
+        return x
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(x)) as im:
+        return np.asarray(im.convert("RGB"), dtype=np.uint8)
