@@ -168,10 +168,18 @@ struct LevelDesc {
     int stride = 0, pad = -1;       // > 0 / >= 0: this level's own stride / pad_beg (else the launch's)
 };
 
-// in_fmt / out_fmt / res_fmt: 0 fp32 rows, 1 split-fp16 rows (ssd_internal.h); flags: the handle's status word
-Op make_conv_op(const struct ssd_handle *h, const ConvW &cw, const float *in, float *out, float *out2, const float *res, int B,
-                int stride, int pad, int act, const std::vector<LevelDesc> &lv, bool dense, int in_fmt = 0, int out_fmt = 0,
-                int res_fmt = 0, int *flags = nullptr, unsigned *scan_bits = nullptr, float scan_lo = 0.0f,
+// A convolution's operands.  in_fmt / out_fmt / res_fmt: 0 fp32 rows, 1 split-fp16 rows (ssd_internal.h; in_fmt 2: fp32 rows
+// split while they are staged); flags: the handle's status word
+struct ConvIO {
+    const float *in = nullptr;
+    float *out = nullptr;
+    float *out2 = nullptr;          // second output: ReLU of the raw sums (fpn p6 -> p7's input)
+    const float *res = nullptr;     // added to the sums (the FPN's upsampled top-down operand)
+    int in_fmt = 0, out_fmt = 0, res_fmt = 0;
+    int *flags = nullptr;
+};
+Op make_conv_op(const struct ssd_handle *h, const ConvW &cw, const ConvIO &io, int B, int stride, int pad, int act,
+                const std::vector<LevelDesc> &lv, bool dense, unsigned *scan_bits = nullptr, float scan_lo = 0.0f,
                 bool *scan_marked = nullptr);
 Op make_dw_op(const DwW &d, const float *in, int B, int H, int W, int stride, int act, float *out, int Cl, int out16 = 0,
               int *flags = nullptr);
@@ -180,8 +188,6 @@ Op make_dwpws_op(const DwW &d, const ConvW &cw, const float *in, int B, int H, i
                  float *out, int out_rs = 0 /* floats between output rows; 0: cw.CoutP */);
 // sn_pw.hip: 1x1 + batch norm + activation on rows gathered through `src` (device table, CinP entries) from `base`
 Op make_pw_gather_op(const ConvW &cw, const float *base, long long base_bytes, const int *src, int rs, long long M, int act, float *out);
-// front.hip: first convolution + Conv2d_1 in one launch; the frame pointer is the handle's cur_images + img_index frames at run time
-Op make_front_op(struct ssd_handle *h, int img_index, const DwW &f, int act0, const DwW &d, const ConvW &cw, int B, int H, int W, int dact, int act, float *out);
 LevelDesc dense_level(int H, int W, int OH, int OW, int CoutP, long long in_off = 0, long long out_off = 0,
                       int param_off = 0, long long res_off = 0);
 float conservative_logit_bound(float thr);
@@ -252,6 +258,8 @@ struct ssd_handle {
     ConvW tower[2][4], final_[2];       // [box, class]
     int c_ch[3] = {0, 0, 0};            // logical channels of c3, c4, c5
     int c_split[3] = {0, 0, 0};         // > 0: c3 / c4 is a ShuffleNet stage output in two-part rows [x half | y half], this many channels each
+    struct SnStage { int pw = 0, dw = 0, units = 0; };
+    SnStage sn_stage[3];                // ShuffleNet: a stage's first layers in pw / dw (their order: weights.hip) and its number of units
     int precision = SSD_PRECISION_F32;  // ssd_set_precision
     int *flags_dev = nullptr;           // status word (bit 0: an S16 tensor was clamped to the fp16 range)
     // Layer plans: one set per network shape this handle has served, each with an arena of its own, kept until the budget

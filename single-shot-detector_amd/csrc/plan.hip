@@ -11,10 +11,13 @@
 #include <cstdio>
 #include <cstring>
 
-Op make_conv_op(const ssd_handle *h, const ConvW &cw, const float *in, float *out, float *out2, const float *res, int B, int stride,
-                int pad, int act, const std::vector<LevelDesc> &lv, bool dense, int in_fmt, int out_fmt,
-                int res_fmt, int *flags, unsigned *scan_bits, float scan_lo, bool *scan_marked)
+Op make_conv_op(const ssd_handle *h, const ConvW &cw, const ConvIO &io, int B, int stride, int pad, int act,
+                const std::vector<LevelDesc> &lv, bool dense, unsigned *scan_bits, float scan_lo, bool *scan_marked)
 {
+    const float *in = io.in, *res = io.res;
+    float *out = io.out, *out2 = io.out2;
+    const int in_fmt = io.in_fmt, out_fmt = io.out_fmt, res_fmt = io.res_fmt;
+    int *flags = io.flags;
     IgemmArgs a;
     memset(&a, 0, sizeof(a));
     a.in = in; a.wt = in_fmt ? cw.wt16 : cw.wt; a.out = out; a.out2 = out2;
@@ -296,27 +299,28 @@ Op make_pw_gather_op(const ConvW &cw, const float *base, long long base_bytes, c
     return op;
 }
 
-// MobileNet's first convolution + Conv2d_1 as one launch (front.hip): the frames at the network's input size, 32 -> 32 -> 64
-Op make_front_op(ssd_handle *h, int img_index, const DwW &f, int act0, const DwW &d, const ConvW &cw, int B, int H, int W, int dact, int act, float *out)
+// A backbone's first layers as one launch (front.hip) on the frames from img on: at the network's input size, or RESIZED (the
+// gather in its loads) by src = {srcH, srcW, nh, nw} of this call's frames or by every frame's own geometry (mixed, from `first`)
+using FusedFront = std::function<hipError_t(const uint8_t *img, const int *src, const MixedGeom *mixed, int first, hipStream_t s)>;
+
+// MobileNet's first convolution + Conv2d_1, 32 -> 32 -> 64
+static FusedFront mobilenet_front(const ssd_handle *h, int B, int H, int W, float *out)
 {
+    const DwW &f = h->first, &d = h->dw[0];
+    const ConvW &cw = h->pw[0];
     FrontArgs q;
     memset(&q, 0, sizeof(q));
     q.w0 = f.w; q.m0 = f.mean; q.s0 = f.sf; q.b0 = f.beta; q.dwpack = d.pack;
     q.wt = cw.wt; q.mean = cw.mean; q.sf = cw.sf; q.beta = cw.beta; q.out = out;
-    q.B = B; q.H = H; q.W = W; q.act0 = act0; q.dact = dact; q.act = act;
+    q.B = B; q.H = H; q.W = W; q.act0 = h->firstAct; q.dact = SSD_ACT_RELU6; q.act = SSD_ACT_RELU6;
     q.tiles_y = (H / 2 + front_tile_y() - 1) / front_tile_y();
     q.tiles_x = (W / 2 + front_tile_x() - 1) / front_tile_x();
-    Op op;
-    op.cls = 6;
-    const double M = (double)B * (H / 2) * (W / 2);
-    op.flops = (2.0 * 27 * cw.Cin_l + 2.0 * 9 * cw.Cin_l + 2.0 * cw.Cin_l * cw.Cout_l) * M;
-    op.bytes = (double)B * H * W * 3 + M * cw.Cout_l * 4.0;
-    op.run = [q, h, img_index, H, W](hipStream_t s) {
+    return [q](const uint8_t *img, const int *src, const MixedGeom *mixed, int first, hipStream_t s) {
         FrontArgs r = q;
-        r.img = h->cur_images + (size_t)img_index * H * W * 3;       // (a plan with this op runs frames of the network's own size only)
+        r.img = img; r.mixed = mixed; r.mixed_first = first;
+        if (src) { r.resized = 1; r.srcH = src[0]; r.srcW = src[1]; r.nh = src[2]; r.nw = src[3]; }
         return launch_front(r, s);
     };
-    return op;
 }
 
 LevelDesc dense_level(int H, int W, int OH, int OW, int CoutP, long long in_off, long long out_off, int param_off, long long res_off)
@@ -332,446 +336,468 @@ LevelDesc dense_level(int H, int W, int OH, int OW, int CoutP, long long in_off,
     return d;
 }
 
-// H, W: the network's input size (multiples of 128); ident: the source frames already have it (no resize, no pad band)
-static int build_plan(ssd_handle *h, Plan &pl, int B, int H, int W, bool ident, int img0)
-{
-    pl.B = B;
-    pl.img0 = img0;
-    DevPool &ap = pl.pool;
-    auto falloc = [&](float **p, long long nfloats) { return ap.alloc((void **)p, (size_t)nfloats * sizeof(float)); };
-
+// What the builders of one plan share.  An op's `run` closure outlives them: it captures values, the handle and arena pointers,
+// never this context or a builder's local by reference.
+struct Builder {
+    ssd_handle *h;
+    Plan &pl;
+    int B, H, W;            // H, W: the network's input size (multiples of 128)
+    bool ident;             // the source frames already have it (no resize, no pad band)
+    int img0;
     // precision mode f16x3: FPN + heads run on split-fp16 operands (igemm.hip "S16"); the backbone stays exact
     // fp32 and hands over c5 in S16 rows, c3 / c4 (which the next depthwise layer also reads) in fp32.
-    const int X16 = h->precision == SSD_PRECISION_F16X3 ? 1 : 0;
-    int *const FL = h->flags_dev;
-    // ---------------- backbone
-    float *C3 = nullptr, *C4 = nullptr, *C5 = nullptr;
-    unsigned char *scratch = nullptr;           // backbone-only memory that later stages of the same forward may reuse (MobileNet)
-    size_t scratch_bytes = 0;
-    // a tensor's slot inside a shared block: its bytes + the 256 bytes of slack every tensor has behind it (DevPool::alloc), 256-aligned
-    auto scratch_slot = [](size_t bytes) { return (bytes + 256 + 255) & ~(size_t)255; };
-    const int h2 = H / 2, w2 = W / 2;
-    int id_bb_last[4] = {-1, -1, -1, -1};     // last backbone op of each chain (MobileNet split), -1: no such chain
-    int id_c4 = -1;                            // the op that completes c4 when the backbone is ONE chain (then c3 precedes it on the same stream)
-    if (h->cfg.backbone == SSD_BACKBONE_MOBILENET) {
-        // The backbone is a chain of ~30 short, latency-bound kernels (two blocks per CU each waiting for one
-        // round of loads).  From 4 images on it runs as two half-batch chains on the plan's two streams, so that
-        // one chain's memory phases sit under the other's compute; FPN and heads stay full-batch launches.
-        // Measured (f16x3, same box): +2.1 % at 32 images, +3.8 % at 16, +3.2 % at 8, +4.5 % at 4; mode f32 (round 2):
-        // +1.3 % at 4, +1.5 % at 8, +0.8 % at 16, none at 32.
-        // option backbone_split = 1 keeps one chain.
-        int nhalf = B >= 4 ? 2 : 1;
-        { const int v = ssd_opt(h, OPT_BACKBONE_SPLIT, 0); if (v >= 1 && v <= 4 && v <= B) nhalf = v; }
-        // retained outputs c3 / c4 / c5: full-batch tensors, each half writes its images
-        {
-            int hh = h2, ww = w2;
-            for (int i = 0; i < 13; ++i) {
-                hh /= MB_STRIDE[i]; ww /= MB_STRIDE[i];
-                if (i == 4 || i == 10 || i == 12) {
-                    float *t;
-                    SSDCHK(falloc(&t, (long long)B * hh * ww * h->pw[i].CoutP));
-                    if (i == 4) C3 = t; else if (i == 10) C4 = t; else C5 = t;
-                    const char *nm = i == 4 ? "c3" : (i == 10 ? "c4" : "c5");
-                    pl.retained[nm] = Retained{t, B, hh, ww, h->pw[i].Cout_l, h->pw[i].CoutP, true, (i == 12 && X16) ? 1 : 0};
-                }
-            }
-        }
-        // depthwise -> pointwise pairs that run as one launch (bit i = Conv2d_{i+1}); option fuse_dw overrides
-        // (streaming kernel: every pair in mode f32; in mode f16x3 Conv2d_5..13 keep their f16x3 pointwise products)
-        // Measured with the streaming kernel (B = 32, mode f32, one box): masks 0xf / 0x1f / 0x3f / 0x1fff -> 770.7 / 769.4 /
-        // 765.4 / 758.9 img/s: from Conv2d_6 on the pointwise product is MFMA-bound, the exact-fp32 MFMA and the depthwise
-        // VALU work do not overlap on a SIMD, and the two-kernel pair wins.
-        unsigned fuse_mask = SSD_FUSE_DW_DEFAULT;
-        if (ssd_opt(h, OPT_FUSE_DW, -1) >= 0) fuse_mask = (unsigned)ssd_opt(h, OPT_FUSE_DW, -1);
-        std::vector<Op> half_ops[4];
-        // The chains' ping-pong buffers (2 x the largest backbone tensor per chain: 73 MB per 640 x 896 frame, a third of the
-        // arena) as ONE block: nothing reads them once c3 / c4 / c5 exist, so the head towers' buffers -- whose first writer runs
-        // behind the FPN, i.e. behind every backbone launch -- and after them the NMS keys are carved from the same bytes (`scratch`).
-        // The next forward's backbone starts behind this forward's last kernel (one caller stream; another stream waits for
-        // ev_last), and every plan has a block of its own.
-        auto chain_floats = [&](int nb) {
-            long long maxf = (long long)nb * h2 * w2 * h->firstCp;
-            int hh = h2, ww = w2;
-            for (int i = 0; i < 13; ++i) {
-                hh /= MB_STRIDE[i]; ww /= MB_STRIDE[i];
-                maxf = std::max(maxf, std::max((long long)nb * hh * ww * h->dw[i].Cp, (long long)nb * hh * ww * h->pw[i].CoutP));
-            }
-            return maxf;
-        };
-        {
-            size_t total = 0;
-            for (int hf = 0; hf < nhalf; ++hf) {
-                const int nb = (int)((long long)B * (hf + 1) / nhalf) - (int)((long long)B * hf / nhalf);
-                total += 2 * scratch_slot((size_t)chain_floats(nb) * sizeof(float));
-            }
-            SSDCHK(ap.alloc((void **)&scratch, total));
-            scratch_bytes = total;
-        }
-        size_t scratch_used = 0;
-        for (int hf = 0; hf < nhalf; ++hf) {
-            const int b0 = (int)((long long)B * hf / nhalf), nb = (int)((long long)B * (hf + 1) / nhalf) - b0;
-            std::vector<Op> &ops = half_ops[hf];
-            const long long maxf = chain_floats(nb);
-            float *X = (float *)(scratch + scratch_used), *Y = (float *)(scratch + scratch_used + scratch_slot((size_t)maxf * sizeof(float)));
-            scratch_used += 2 * scratch_slot((size_t)maxf * sizeof(float));
-            // first convolution + Conv2d_1 as ONE launch (front.hip) when the frames arrive at the network's input size and
-            // the three layers have MobileNet-1.0's widths; option front_fuse = 0 / 1 pins it
-            bool front = ident && ((fuse_mask >> 0) & 1) && h->first.mean && h->dw[0].pack &&
-                         h->pw[0].taps == 1 && h->pw[0].mean && !h->pw[0].bias && front_supports(nb, H, W, h->firstCp, h->dw[0].Cp, h->pw[0].CoutP) &&
-                         h->pw[0].CinP == 32 && MB_STRIDE[0] == 1;
-            { const int pin = ssd_opt(h, OPT_FRONT_FUSE, -1); if (pin >= 0) front = front && pin != 0; }
-            // RESIZED frames whose width does not shrink (every COCO image at min_dimension 640) take the same fused launch with the
-            // gather in its loads (front.hip, GEN).  Decided per CALL: the source geometry is a launch argument and a plan serves any
-            // source size that lands on its network shape, so such a plan keeps both forms -- the first-convolution op launches the
-            // fused kernel and the Conv2d_1 op does nothing, or (a frame that is reduced in width) the two run as themselves.  A
-            // batch of frames of DIFFERENT sizes takes the fused launch too (per-frame geometry from its arguments) when none of its
-            // frames is reduced in width.  Same conditions as the static form, plus Conv2d_1 being ONE op (the fused depthwise + pointwise).
-            bool front_rt = !ident && ((fuse_mask >> 0) & 1) && h->first.mean && h->dw[0].pack &&
-                            h->pw[0].taps == 1 && h->pw[0].mean && !h->pw[0].bias && front_supports(nb, H, W, h->firstCp, h->dw[0].Cp, h->pw[0].CoutP) &&
-                            h->pw[0].CinP == 32 && MB_STRIDE[0] == 1 && dwpws_eligible(h->dw[0], h->pw[0], nb, h2, w2, MB_STRIDE[0]);
-            { const int pin = ssd_opt(h, OPT_FRONT_FUSE, -1); if (pin >= 0) front_rt = front_rt && pin != 0; }
-            ssd_handle *const hrt = h;
-            const int rt_first = img0 + b0;
-            auto fused_now = [hrt, nb, front_rt, rt_first, H, W]() {
-                if (!front_rt) return false;
-                if (hrt->mixed) return front_mixed_supports(hrt->mixed->geom, rt_first, nb, H, W);      // every frame of this chain's share
-                const SrcGeom &g = hrt->src;
-                return front_gen_supports(nb, g.srcH, g.srcW, g.nh, g.nw);
-            };
-            if (!front) {
-                Op op;
-                op.cls = 3;
-                op.flops = 2.0 * 27 * (double)nb * h2 * w2 * h->pw[0].Cin_l;
-                op.bytes = (double)nb * H * W * 3 + (double)nb * h2 * w2 * h->pw[0].Cin_l * 4.0;
-                ssd_handle *hh = h;
-                const DwW f = h->first;
-                const int act = h->firstAct;
-                const int first_img = img0 + b0;
-                const int variant = ssd_opt(h, OPT_FIRST_CONV_PX, 1) == 0 ? 1 : 0;
-                FrontArgs fq;
-                memset(&fq, 0, sizeof(fq));
-                if (front_rt) {
-                    const ConvW &c0 = h->pw[0];
-                    fq.w0 = f.w; fq.m0 = f.mean; fq.s0 = f.sf; fq.b0 = f.beta; fq.dwpack = h->dw[0].pack;
-                    fq.wt = c0.wt; fq.mean = c0.mean; fq.sf = c0.sf; fq.beta = c0.beta; fq.out = Y;      // (Conv2d_1's output: `dwo` of layer 0 below)
-                    fq.B = nb; fq.H = H; fq.W = W; fq.act0 = act; fq.dact = SSD_ACT_RELU6; fq.act = SSD_ACT_RELU6;
-                    fq.tiles_y = (H / 2 + front_tile_y() - 1) / front_tile_y();
-                    fq.tiles_x = (W / 2 + front_tile_x() - 1) / front_tile_x();
-                }
-                op.run = [=](hipStream_t s) {      // the source's size and the resize's target: this call's (SrcGeom), any that lands on H x W
-                    if (hh->mixed) {               // ... or every frame's own (a batch of frames of different sizes)
-                        if (fused_now()) {
-                            FrontArgs r = fq;
-                            r.img = hh->cur_images;
-                            r.mixed = &hh->mixed->geom;
-                            r.mixed_first = first_img;
-                            return launch_front(r, s);
-                        }
-                        return launch_first_conv_mixed(hh->cur_images, hh->mixed->geom, first_img, nb, H, W, f.w, f.Cp, f.mean, f.sf, f.beta, act, X, s, variant);
-                    }
-                    const SrcGeom &g = hh->src;
-                    if (fused_now()) {
-                        FrontArgs r = fq;
-                        r.img = hh->cur_images + (size_t)first_img * g.srcH * g.srcW * 3;
-                        r.resized = 1; r.srcH = g.srcH; r.srcW = g.srcW; r.nh = g.nh; r.nw = g.nw;
-                        return launch_front(r, s);
-                    }
-                    return launch_first_conv(hh->cur_images + (size_t)first_img * g.srcH * g.srcW * 3, nb, g.srcH, g.srcW, g.nh, g.nw, H, W, f.w, f.Cp,
-                                             f.mean, f.sf, f.beta, act, X, s, variant);
-                };
-                ops.push_back(op);
-            }
-            float *cur = X;
-            int ch = h2, cwid = w2;
-            for (int i = 0; i < 13; ++i) {
-                const int s = MB_STRIDE[i];
-                float *dwo = (cur == X) ? Y : X;
-                const ConvW &cw = h->pw[i];
-                if (i == 0 && front) {
-                    ops.push_back(make_front_op(h, img0 + b0, h->first, h->firstAct, h->dw[0], cw, nb, H, W,
-                                                SSD_ACT_RELU6, SSD_ACT_RELU6, dwo));
-                    cur = dwo;
-                    continue;
-                }
-                const bool fuse = ((fuse_mask >> i) & 1) && dwpws_eligible(h->dw[i], cw, nb, ch, cwid, s);
-                // f16x3: an unfused pair hands the depthwise result (exact fp32, in [0, 6]) to its pointwise
-                // convolution in split-fp16 rows, and the pointwise product runs as 3 x f16 MFMA
-                const int pw16 = X16 && !fuse && (h->dw[i].Cp % 32 == 0) ? 1 : 0;
-                if (!fuse) ops.push_back(make_dw_op(h->dw[i], cur, nb, ch, cwid, s, SSD_ACT_RELU6, dwo, h->pw[i].Cin_l, pw16, FL));
-                const int dh = ch, dwid = cwid;
-                ch /= s; cwid /= s;
-                float *pwo;
-                if (i == 4 || i == 10 || i == 12) {
-                    float *full = i == 4 ? C3 : (i == 10 ? C4 : C5);
-                    pwo = full + (long long)b0 * ch * cwid * cw.CoutP;
-                } else {
-                    pwo = fuse ? dwo : ((dwo == X) ? Y : X);    // fused: input `cur` is live until the launch ends
-                }
-                if (fuse) {
-                    Op o = make_dwpws_op(h->dw[i], cw, cur, nb, dh, dwid, s, SSD_ACT_RELU6, SSD_ACT_RELU6, pwo);
-                    if (i == 0 && front_rt) {        // (its work was done by the fused launch of the op before it when fused_now())
-                        const auto inner = o.run;
-                        o.run = [inner, fused_now](hipStream_t st) { return fused_now() ? hipSuccess : inner(st); };
-                    }
-                    ops.push_back(o);
-                } else   // c5 feeds only the FPN (lateral5, p6): in f16x3 mode it is written in split-fp16 rows
-                    ops.push_back(make_conv_op(h, cw, dwo, pwo, nullptr, nullptr, nb, 1, 0, SSD_ACT_RELU6,
-                                               {dense_level(ch, cwid, ch, cwid, cw.CoutP)}, true, pw16, (i == 12 && X16) ? 1 : 0, 0, h->flags_dev));
-                if (i == 10 && nhalf == 1) id_c4 = (int)ops.size() - 1;          // Conv2d_11_pointwise = c4 (one chain: pl.ops keeps this index)
-                cur = pwo;
-            }
-        }
-        // enqueue order interleaved so that both queues are fed
-        for (size_t i = 0; i < half_ops[0].size(); ++i)
-            for (int hf = 0; hf < nhalf; ++hf)
-                if (i < half_ops[hf].size()) {
-                    Op op = half_ops[hf][i];
-                    op.stream = hf;
-                    pl.ops.push_back(op);
-                    id_bb_last[hf] = (int)pl.ops.size() - 1;
-                }
-    } else {
-        // ---------------- ShuffleNet v2 (shufflenet_v2.py:50-69,79-137)
-        const int units[3] = {4, 8, 4};
-        const int fc = h->firstCp;
-        // depthwise -> 1x1 pairs of the units as one launch each (option fuse_dw = 0 keeps them apart)
-        bool sn_fuse = SSD_FUSE_SHUFFLE_DEFAULT;
-        if (ssd_opt(h, OPT_FUSE_DW, -1) >= 0) sn_fuse = ssd_opt(h, OPT_FUSE_DW, -1) != 0;
-        const int h4 = h2 / 2, w4 = w2 / 2;
-        // first convolution + max pool as ONE launch (front.hip) when the frames arrive at the network's input size; option
-        // front_fuse = 0 / 1 pins it
-        bool sn_front = ident && h->first.mean && front_pool_supports(B, H, W, fc);
-        { const int pin = ssd_opt(h, OPT_FRONT_FUSE, -1); if (pin >= 0) sn_front = sn_front && pin != 0; }
-        // ---- One or two half-batch chains (two from 4 images on, on the plan's two streams, as MobileNet's backbone above: the
-        // backbone is ~45 short kernels far from any bound, one chain's load / store phases sit under the other's arithmetic);
-        // FPN and heads stay full-batch launches.  Option backbone_split = 1 keeps one chain.
-        //
-        // concat_shuffle_split (shufflenet_v2.py:94-115) and the stage concat (:89) run as NO kernel of their own:
-        //   * every producer of a stage -- unit_1's two branches, unit j's conv1x1_after -- stores its D channels DENSE, one
-        //     contiguous run per position, into a tensor of its own (16-byte stores from dwpw_stream.hip's accumulators, every
-        //     line written whole by one launch);
-        //   * unit j's conv1x1_before GATHERS its input row (sn_pw.hip): the host traces input channel k through the interleave-
-        //     and-split of the reference back to (producer tensor, column) and gives the kernel that table; the k order -- and
-        //     with it bit-identity with the oracle -- is untouched;
-        //   * the stage output is kept in two-part rows [x half | y half] (weights.hip packs its consumers for that): the last
-        //     unit stores its channels straight into the x half, the y half (channels no later unit touched) is one row gather.
-        // Each stage is ONE allocation [producer tensors of chain 0 | ... of chain 1 | stage output S of the whole batch] under
-        // one buffer resource (select_plans keeps it below 2 GiB).
-        int nhalf = B >= 4 ? 2 : 1;
-        { const int v = ssd_opt(h, OPT_BACKBONE_SPLIT, 0); if (v >= 1 && v <= 2 && v <= B) nhalf = v; }
-        const int nb_of[2] = {nhalf == 2 ? B / 2 : B, nhalf == 2 ? B - B / 2 : 0};
-        struct StageGeo { int ch, cw, oh, ow, D, Dp, n_units, ipw, idw; long long tbytes[2], toff[2], soff, total; };
-        StageGeo geo[3];
-        {
-            int ch = h4, cw = w4, ipw = 0, idw = 0;
-            for (int st = 0; st < 3; ++st) {
-                StageGeo &g = geo[st];
-                g.ch = ch; g.cw = cw; g.oh = ch / 2; g.ow = cw / 2; g.ipw = ipw; g.idw = idw; g.n_units = units[st];
-                const ConvW &after = h->pw[ipw + 1];
-                g.Dp = after.CoutP; g.D = after.Cout_l;
-                long long off = 0;
-                for (int hf = 0; hf < nhalf; ++hf) {
-                    g.tbytes[hf] = (long long)nb_of[hf] * g.oh * g.ow * g.Dp * 4;       // one producer tensor of this chain
-                    g.toff[hf] = off;
-                    off += g.tbytes[hf] * g.n_units;                                  // x1, y1, o_2 .. o_{n-1}
-                }
-                g.soff = off;
-                g.total = off + (long long)B * g.oh * g.ow * 2 * g.Dp * 4;
-                if (g.total >= (1LL << 31)) return ssd_fail(SSD_ERR_INVALID, "ssd_forward: ShuffleNet stage allocation past 2 GiB (sub-batch split failed)");
-                for (int hf = 0; hf < nhalf; ++hf)
-                    for (int j = 2; j <= g.n_units; ++j) {
-                        const ConvW &b2 = h->pw[ipw + 3 + 2 * (j - 2)];
-                        if (b2.CinP != g.Dp || b2.taps != 1 || !b2.mean || b2.bias ||
-                            !pw_gather_supports(b2.CinP, b2.CoutP, (long long)nb_of[hf] * g.oh * g.ow, g.Dp * 4, g.total, (long long)nb_of[hf] * g.oh * g.ow * b2.CoutP * 4))
-                            return ssd_fail(SSD_ERR_INVALID, "ssd_forward: a ShuffleNet unit's conv1x1_before is not a shape of the gathering kernel (sn_pw.hip)");
-                    }
-                ipw += 3 + 2 * (g.n_units - 1); idw += 2 + (g.n_units - 1);
-                ch = g.oh; cw = g.ow;
-            }
-        }
-        float *stage[3];
-        for (int st = 0; st < 3; ++st) SSDCHK(falloc(&stage[st], geo[st].total / 4));
-        const StageGeo &g2 = geo[2];
-        const ConvW &c5w = h->pw[g2.ipw + 3 + 2 * (g2.n_units - 1)];
-        SSDCHK(falloc(&C5, (long long)B * g2.oh * g2.ow * c5w.CoutP));
-        std::vector<Op> half_ops[2];
-        for (int hf = 0; hf < nhalf; ++hf) {
-            const int b0 = hf == 0 ? 0 : nb_of[0], nb = nb_of[hf];
-            std::vector<Op> &ops = half_ops[hf];
-            float *F = nullptr, *MP, *MID = nullptr;
-            SSDCHK(falloc(&MP, (long long)nb * h4 * w4 * fc));
-            // depthwise -> 1x1 (+ batch norms, ReLU behind the 1x1) into dense rows [M][out_rs]: one launch of the streaming kernel, or
-            // (option fuse_dw = 0, shapes it does not take) the depthwise kernel and the implicit-GEMM kernel with a tensor between them
-            auto pair = [&](const DwW &d, const ConvW &cw, const float *in, int hh, int ww, int stride, float *out, int out_rs) -> int {
-                if (sn_fuse && dwpws_eligible(d, cw, nb, hh, ww, stride)) {
-                    ops.push_back(make_dwpws_op(d, cw, in, nb, hh, ww, stride, SSD_ACT_NONE, SSD_ACT_RELU, out, out_rs));
-                    return SSD_OK;
-                }
-                if (!MID) SSDCHK(falloc(&MID, (long long)nb * h4 * w4 * std::max(fc, 32)));       // (the largest depthwise output: Stage2 unit_1 reads h4 x w4)
-                const int oh = hh / stride, ow = ww / stride;
-                if ((long long)nb * oh * ow * d.Cp > (long long)nb * h4 * w4 * std::max(fc, 32)) return ssd_fail(SSD_ERR_INVALID, "ssd_forward: depthwise scratch too small");
-                ops.push_back(make_dw_op(d, in, nb, hh, ww, stride, SSD_ACT_NONE, MID, cw.Cin_l));
-                LevelDesc lv = dense_level(oh, ow, oh, ow, cw.CoutP);
-                lv.out_rstride = out_rs > 0 ? out_rs : cw.CoutP;
-                lv.out_bstride = (long long)oh * ow * lv.out_rstride;
-                ops.push_back(make_conv_op(h, cw, MID, out, nullptr, nullptr, nb, 1, 0, SSD_ACT_RELU, {lv}, true));
-                return SSD_OK;
-            };
-            {
-                ssd_handle *hh = h;
-                const DwW f = h->first;
-                const int act = h->firstAct;
-                const int first_img = img0 + b0;
-                Op op;
-                op.cls = 3;
-                op.flops = 2.0 * 27 * (double)nb * h2 * w2 * 24;
-                if (sn_front) {
-                    // first convolution + max pool as one launch (front.hip): the half-resolution tensor stays in LDS
-                    op.bytes = (double)nb * H * W * 3 + (double)nb * h4 * w4 * 24 * 4.0;
-                    op.run = [=](hipStream_t s) { return launch_front_pool(hh->cur_images + (size_t)first_img * H * W * 3, nb, H, W, f.w, f.Cp, f.mean, f.sf, f.beta, act, MP, s); };
-                    ops.push_back(op);
-                } else {
-                    SSDCHK(falloc(&F, (long long)nb * h2 * w2 * fc));
-                    op.bytes = (double)nb * H * W * 3 + (double)nb * h2 * w2 * 24 * 4.0;
-                    const int variant = ssd_opt(h, OPT_FIRST_CONV_PX, 1) == 0 ? 1 : 0;
-                    // resized frames whose width does not shrink: the fused launch with the gather in its loads, chosen per call (as
-                    // MobileNet's above): this op then writes the pooled tensor and the max-pool op does nothing
-                    bool front_rt = !ident && h->first.mean && front_pool_supports(nb, H, W, fc);
-                    { const int pin = ssd_opt(h, OPT_FRONT_FUSE, -1); if (pin >= 0) front_rt = front_rt && pin != 0; }
-                    auto fused_now = [hh, nb, front_rt, first_img, H, W]() {
-                        if (!front_rt) return false;
-                        if (hh->mixed) return front_mixed_supports(hh->mixed->geom, first_img, nb, H, W);
-                        const SrcGeom &g = hh->src;
-                        return front_gen_supports(nb, g.srcH, g.srcW, g.nh, g.nw);
-                    };
-                    op.run = [=](hipStream_t s) {
-                        if (hh->mixed) {
-                            if (fused_now())
-                                return launch_front_pool(hh->cur_images, nb, H, W, f.w, f.Cp, f.mean, f.sf, f.beta, act, MP, s, nullptr, &hh->mixed->geom, first_img);
-                            return launch_first_conv_mixed(hh->cur_images, hh->mixed->geom, first_img, nb, H, W, f.w, f.Cp, f.mean, f.sf, f.beta, act, F, s, variant);
-                        }
-                        const SrcGeom &g = hh->src;
-                        if (fused_now()) {
-                            const int src[4] = {g.srcH, g.srcW, g.nh, g.nw};
-                            return launch_front_pool(hh->cur_images + (size_t)first_img * g.srcH * g.srcW * 3, nb, H, W, f.w, f.Cp, f.mean, f.sf, f.beta, act, MP, s, src);
-                        }
-                        return launch_first_conv(hh->cur_images + (size_t)first_img * g.srcH * g.srcW * 3, nb, g.srcH, g.srcW, g.nh, g.nw, H, W, f.w, f.Cp,
-                                                 f.mean, f.sf, f.beta, act, F, s, variant);
-                    };
-                    ops.push_back(op);
-                    Op mp;
-                    mp.cls = 5; mp.flops = 0;
-                    mp.bytes = ((double)nb * h2 * w2 + (double)nb * h4 * w4) * 24 * 4.0;
-                    mp.run = [=](hipStream_t s) { return fused_now() ? hipSuccess : launch_maxpool(F, nb, h2, w2, fc, MP, s); };
-                    ops.push_back(mp);
-                }
-            }
-            const float *cur = MP;
-            for (int st = 0; st < 3; ++st) {
-                const StageGeo &g = geo[st];
-                const ConvW &before = h->pw[g.ipw], &after = h->pw[g.ipw + 1], &after2 = h->pw[g.ipw + 2];
-                const DwW &d1 = h->dw[g.idw], &d2 = h->dw[g.idw + 1];
-                const int D = g.D, Dp = g.Dp, n_units = g.n_units;
-                const long long rows = (long long)nb * g.oh * g.ow;
-                float *t1, *U;
-                SSDCHK(falloc(&t1, (long long)nb * g.ch * g.cw * before.CoutP));
-                SSDCHK(falloc(&U, rows * Dp));
-                float *sb = stage[st];
-                // producer p's tensor of this chain (0: unit_1's second branch = x, 1: its main branch = y, j: unit j's output)
-                auto tensor_off = [&](int p) { return g.toff[hf] + (long long)p * g.tbytes[hf]; };
-                // the chain's rows of S start b0 images into the stage output
-                float *S_chain = sb + g.soff / 4 + (long long)b0 * g.oh * g.ow * 2 * Dp;
-                struct Src { int prod, col; };
-                std::vector<Src> x(D), y(D);
-                for (int d = 0; d < D; ++d) { x[d] = Src{0, d}; y[d] = Src{1, d}; }
-                auto table = [&](const std::vector<Src> &v) {      // physical channel p of a D-channel row -> byte offset of its source
-                    std::vector<int> t(Dp, -1);
-                    for (int d = 0; d < D; ++d) t[ssd_phys_of_logical(d)] = (int)(tensor_off(v[d].prod) + (long long)ssd_phys_of_logical(v[d].col) * 4);
-                    return t;
-                };
-                std::vector<const int *> src_dev(n_units + 1, nullptr);
-                for (int j = 2; j <= n_units; ++j) {
-                    std::vector<Src> z(2 * D);
-                    for (int d = 0; d < D; ++d) { z[2 * d] = x[d]; z[2 * d + 1] = y[d]; }
-                    std::vector<Src> xin(z.begin(), z.begin() + D);
-                    int *dv;
-                    SSDCHK(ap.upload(&dv, table(xin)));
-                    src_dev[j] = dv;
-                    for (int d = 0; d < D; ++d) { x[d] = Src{j, d}; y[d] = z[D + d]; }
-                }
-                int *ysrc;
-                SSDCHK(ap.upload(&ysrc, table(y)));          // the stage output's y half (x = unit n's own channels)
-                ops.push_back(make_conv_op(h, before, cur, t1, nullptr, nullptr, nb, 1, 0, SSD_ACT_RELU,
-                                           {dense_level(g.ch, g.cw, g.ch, g.cw, before.CoutP)}, true));
-                SSDCHK(pair(d1, after, t1, g.ch, g.cw, 2, sb + tensor_off(1) / 4, 0));
-                SSDCHK(pair(d2, after2, cur, g.ch, g.cw, 2, sb + tensor_off(0) / 4, 0));
-                for (int j = 2; j <= n_units; ++j) {
-                    const ConvW &b2 = h->pw[g.ipw + 3 + 2 * (j - 2)], &a2 = h->pw[g.ipw + 3 + 2 * (j - 2) + 1];
-                    const DwW &dd = h->dw[g.idw + j];
-#ifdef SSD_DIAG
-                    // ablation (scripts/experiments/sn_unit_fusion_bound.py): drop conv1x1_before of the stages in the mask -- WRONG
-                    // results, the time of a step whose first 1x1 of every unit is free: what no whole-unit fusion can beat
-                    if (const char *e = getenv("SSD_ABL_SKIP_PWG")) { if ((atoi(e) >> st) & 1) goto skip_before; }
-#endif
-                    ops.push_back(make_pw_gather_op(b2, sb, g.total, src_dev[j], Dp * 4, rows, SSD_ACT_RELU, U));
-#ifdef SSD_DIAG
-                skip_before:
-#endif
-                    if (j < n_units) SSDCHK(pair(dd, a2, U, g.oh, g.ow, 1, sb + tensor_off(j) / 4, 0));
-                    else SSDCHK(pair(dd, a2, U, g.oh, g.ow, 1, S_chain, 2 * Dp));
-                }
-                {
-                    Op gop;
-                    gop.cls = 5; gop.flops = 0; gop.bytes = 2.0 * rows * D * 4.0;
-                    const int rs = Dp * 4, ors = 2 * Dp;
-                    float *ydst = S_chain + Dp;
-                    gop.run = [=](hipStream_t s) { return launch_gather_rows(sb, ysrc, rs, rows, Dp, ydst, ors, s); };
-                    ops.push_back(gop);
-                }
-                cur = S_chain;
-            }
-            ops.push_back(make_conv_op(h, c5w, cur, C5 + (long long)b0 * g2.oh * g2.ow * c5w.CoutP, nullptr, nullptr, nb, 1, 0, SSD_ACT_RELU,
-                                       {dense_level(g2.oh, g2.ow, g2.oh, g2.ow, c5w.CoutP)}, true, 0, X16, 0, FL));
-        }
-        for (int st = 0; st < 2; ++st) {
-            float *S = stage[st] + geo[st].soff / 4;
-            if (st == 0) C3 = S; else C4 = S;
-            pl.retained[st == 0 ? "c3" : "c4"] = Retained{S, B, geo[st].oh, geo[st].ow, 2 * geo[st].D, 2 * geo[st].Dp, true, 0, geo[st].D};
-        }
-        pl.retained["c5"] = Retained{C5, B, g2.oh, g2.ow, c5w.Cout_l, c5w.CoutP, true, X16};
-        for (size_t i = 0; i < std::max(half_ops[0].size(), half_ops[1].size()); ++i)
-            for (int hf = 0; hf < nhalf; ++hf)
-                if (i < half_ops[hf].size()) {
-                    Op op = half_ops[hf][i];
-                    op.stream = hf;
-                    pl.ops.push_back(op);
-                    id_bb_last[hf] = (int)pl.ops.size() - 1;
-                }
-    }
-
-    // ---------------- FPN (feature_extractor.py:40-76)
-    const Pyr py = make_pyr(B, H, W, 256);
-    float *P, *X5, *X4, *X3, *T6;
-    SSDCHK(falloc(&P, py.total));
-    SSDCHK(falloc(&X5, (long long)B * py.h[2] * py.w[2] * 256));
-    SSDCHK(falloc(&X4, (long long)B * py.h[1] * py.w[1] * 256));
-    SSDCHK(falloc(&X3, (long long)B * py.h[0] * py.w[0] * 256));
-    SSDCHK(falloc(&T6, (long long)B * py.h[3] * py.w[3] * 256));
-    auto lvl = [&](int l, int CoutP) { return dense_level(py.h[l], py.w[l], py.h[l], py.w[l], CoutP); };
-    // Three streams, explicit dependencies.  Serving batches: main: lateral5 -> lateral4 (+up) -> lateral3 (+up) -> p3 (the
-    // critical path); second stream: p5 (needs x5) -> p4 (needs x4); third stream: p6 -> p7 (need only c5).
-    // All of them are the same 3x3 kernel, and two such kernels side by side fill each other's tails.
-    auto push = [&](Op op, int stream, std::vector<int> deps = {}) {
+    int X16;
+    int *FL;
+    int falloc(float **p, long long nfloats) { return pl.pool.alloc((void **)p, (size_t)nfloats * sizeof(float)); }
+    // the operands of an FPN or head convolution: split-fp16 rows in mode f16x3
+    ConvIO io16(const float *in, float *out) const { ConvIO io{in, out}; io.in_fmt = io.out_fmt = X16; io.flags = FL; return io; }
+    Op conv(const ConvW &cw, const ConvIO &io, int stride, int pad, int act, const std::vector<LevelDesc> &lv) const     // whole batch, dense rows
+    { return make_conv_op(h, cw, io, B, stride, pad, act, lv, true); }
+    int push(Op op, int stream, std::vector<int> deps = {})
+    {
         op.stream = stream;
         std::sort(deps.begin(), deps.end());                     // (one wait per producer: with p7 inside the grouped launch the towers
         deps.erase(std::unique(deps.begin(), deps.end()), deps.end());      //  name that launch twice)
         op.deps = deps;
         pl.ops.push_back(op);
         return (int)pl.ops.size() - 1;
+    }
+};
+
+// What a backbone hands to the FPN
+struct Backbone {
+    float *C3 = nullptr, *C4 = nullptr, *C5 = nullptr;
+    int last[4] = {-1, -1, -1, -1};     // last op of each chain, -1: no such chain
+    int id_c4 = -1;                     // the op that completes c4 when the backbone is ONE chain (then c3 precedes it on the same stream)
+    unsigned char *scratch = nullptr;   // backbone-only memory that later stages of the same forward may reuse (MobileNet)
+    size_t scratch_bytes = 0;
+};
+
+// a tensor's slot inside a shared block: its bytes + the 256 bytes of slack every tensor has behind it (DevPool::alloc), 256-aligned
+static size_t scratch_slot(size_t bytes) { return (bytes + 256 + 255) & ~(size_t)255; }
+
+// The backbone is a chain of short, latency-bound kernels (MobileNet ~30: two blocks per CU each waiting for one round of loads;
+// ShuffleNet ~45, far from any bound).  From 4 images on it runs as two part-batch chains on the plan's streams, so that one
+// chain's memory phases sit under the other's compute; FPN and heads stay full-batch launches.  Option backbone_split = n pins n
+// chains, up to `cap` (1 keeps one chain).
+static int backbone_chains(const ssd_handle *h, int B, int cap)
+{
+    const int v = ssd_opt(h, OPT_BACKBONE_SPLIT, 0);
+    return v >= 1 && v <= cap && v <= B ? v : (B >= 4 ? 2 : 1);
+}
+
+// enqueue order interleaved so that every chain's queue is fed
+static void interleave_chains(Plan &pl, const std::vector<Op> *chains, int n, Backbone &bb)
+{
+    size_t longest = 0;
+    for (int c = 0; c < n; ++c) longest = std::max(longest, chains[c].size());
+    for (size_t i = 0; i < longest; ++i)
+        for (int c = 0; c < n; ++c)
+            if (i < chains[c].size()) {
+                pl.ops.push_back(chains[c][i]);
+                pl.ops.back().stream = c;
+                bb.last[c] = (int)pl.ops.size() - 1;
+            }
+}
+
+// the backbone's first layers as one launch (front.hip) where they `fit`; option front_fuse = 0 / 1 pins it
+static bool front_fuse(const ssd_handle *h, bool fit)
+{
+    const int pin = ssd_opt(h, OPT_FRONT_FUSE, -1);
+    return pin >= 0 ? fit && pin != 0 : fit;
+}
+
+struct FirstLayer { Op op; std::function<bool()> fused_now; };
+
+// The first convolution (Cl logical channels) of nb frames from frame `first` on into `out`: the source's size and the resize's
+// target are this call's (SrcGeom), any that lands on H x W, or every frame's own (frames of different sizes).  Resized frames
+// whose width does not shrink (every COCO image at min_dimension 640; a mixed batch: all its frames) take the `fused` launch
+// instead, if given -- decided per CALL, so such a plan keeps both forms; fused_now() tells the op behind (MobileNet's Conv2d_1,
+// ShuffleNet's max pool) that the fused launch did its work.
+static FirstLayer first_layer_op(const Builder &b, int first, int nb, int Cl, const FusedFront &fused, float *out)
+{
+    ssd_handle *const hh = b.h;
+    const int H = b.H, W = b.W, h2 = H / 2, w2 = W / 2;
+    const bool can_fuse = (bool)fused;
+    FirstLayer r;
+    r.fused_now = [hh, nb, can_fuse, first, H, W]() {
+        if (!can_fuse) return false;
+        if (hh->mixed) return front_mixed_supports(hh->mixed->geom, first, nb, H, W);      // every frame of this chain's share
+        const SrcGeom &g = hh->src;
+        return front_gen_supports(nb, g.srcH, g.srcW, g.nh, g.nw);
     };
-    // last backbone op on the main stream (produces c5, or its first half); the second half, if any, ends on the
-    // second stream: the main stream's first FPN op waits for it
-    const int id_c5 = id_bb_last[0] >= 0 ? id_bb_last[0] : (int)pl.ops.size() - 1;
+    r.op.cls = 3;
+    r.op.flops = 2.0 * 27 * (double)nb * h2 * w2 * Cl;
+    r.op.bytes = (double)nb * H * W * 3 + (double)nb * h2 * w2 * Cl * 4.0;
+    const DwW f = hh->first;
+    const int act = hh->firstAct, variant = ssd_opt(hh, OPT_FIRST_CONV_PX, 1) == 0 ? 1 : 0;
+    const std::function<bool()> fused_now = r.fused_now;
+    r.op.run = [hh, first, nb, H, W, f, act, variant, out, fused, fused_now](hipStream_t s) {
+        if (hh->mixed) {
+            if (fused_now()) return fused(hh->cur_images, nullptr, &hh->mixed->geom, first, s);
+            return launch_first_conv_mixed(hh->cur_images, hh->mixed->geom, first, nb, H, W, f.w, f.Cp, f.mean, f.sf, f.beta, act, out, s, variant);
+        }
+        const SrcGeom &g = hh->src;
+        const uint8_t *img = hh->cur_images + (size_t)first * g.srcH * g.srcW * 3;
+        if (fused_now()) {
+            const int src[4] = {g.srcH, g.srcW, g.nh, g.nw};
+            return fused(img, src, nullptr, 0, s);
+        }
+        return launch_first_conv(img, nb, g.srcH, g.srcW, g.nh, g.nw, H, W, f.w, f.Cp, f.mean, f.sf, f.beta, act, out, s, variant);
+    };
+    return r;
+}
+
+// ---------------- MobileNet v1 (mobilenet_v1.py)
+// Measured (two chains from 4 images on; f16x3, same box): +2.1 % at 32 images, +3.8 % at 16, +3.2 % at 8, +4.5 % at 4; mode f32
+// (round 2): +1.3 % at 4, +1.5 % at 8, +0.8 % at 16, none at 32.
+static int mobilenet_backbone(Builder &b, Backbone &bb)
+{
+    ssd_handle *h = b.h;
+    const int B = b.B, H = b.H, W = b.W, h2 = H / 2, w2 = W / 2;
+    const int nchain = backbone_chains(h, B, 4);
+    // retained outputs c3 / c4 / c5: full-batch tensors, each chain writes its images
+    {
+        int hh = h2, ww = w2;
+        for (int i = 0; i < 13; ++i) {
+            hh /= MB_STRIDE[i]; ww /= MB_STRIDE[i];
+            if (i == 4 || i == 10 || i == 12) {
+                float *t;
+                SSDCHK(b.falloc(&t, (long long)B * hh * ww * h->pw[i].CoutP));
+                if (i == 4) bb.C3 = t; else if (i == 10) bb.C4 = t; else bb.C5 = t;
+                const char *nm = i == 4 ? "c3" : (i == 10 ? "c4" : "c5");
+                b.pl.retained[nm] = Retained{t, B, hh, ww, h->pw[i].Cout_l, h->pw[i].CoutP, true, (i == 12 && b.X16) ? 1 : 0};
+            }
+        }
+    }
+    // depthwise -> pointwise pairs that run as one launch (bit i = Conv2d_{i+1}); option fuse_dw overrides
+    // (streaming kernel: every pair in mode f32; in mode f16x3 Conv2d_5..13 keep their f16x3 pointwise products)
+    // Measured with the streaming kernel (B = 32, mode f32, one box): masks 0xf / 0x1f / 0x3f / 0x1fff -> 770.7 / 769.4 /
+    // 765.4 / 758.9 img/s: from Conv2d_6 on the pointwise product is MFMA-bound, the exact-fp32 MFMA and the depthwise
+    // VALU work do not overlap on a SIMD, and the two-kernel pair wins.
+    unsigned fuse_mask = SSD_FUSE_DW_DEFAULT;
+    if (ssd_opt(h, OPT_FUSE_DW, -1) >= 0) fuse_mask = (unsigned)ssd_opt(h, OPT_FUSE_DW, -1);
+    // The chains' ping-pong buffers (2 x the largest backbone tensor per chain: 73 MB per 640 x 896 frame, a third of the
+    // arena) as ONE block: nothing reads them once c3 / c4 / c5 exist, so the head towers' buffers -- whose first writer runs
+    // behind the FPN, i.e. behind every backbone launch -- and after them the NMS keys are carved from the same bytes (`scratch`).
+    // The next forward's backbone starts behind this forward's last kernel (one caller stream; another stream waits for
+    // ev_last), and every plan has a block of its own.
+    auto chain_slot = [&](int nb) {
+        long long maxf = (long long)nb * h2 * w2 * h->firstCp;
+        int hh = h2, ww = w2;
+        for (int i = 0; i < 13; ++i) {
+            hh /= MB_STRIDE[i]; ww /= MB_STRIDE[i];
+            maxf = std::max(maxf, std::max((long long)nb * hh * ww * h->dw[i].Cp, (long long)nb * hh * ww * h->pw[i].CoutP));
+        }
+        return scratch_slot((size_t)maxf * sizeof(float));
+    };
+    auto chain_b0 = [&](int c) { return (int)((long long)B * c / nchain); };
+    for (int c = 0; c < nchain; ++c) bb.scratch_bytes += 2 * chain_slot(chain_b0(c + 1) - chain_b0(c));
+    SSDCHK(b.pl.pool.alloc((void **)&bb.scratch, bb.scratch_bytes));
+    std::vector<Op> chain_ops[4];
+    size_t used = 0;
+    for (int c = 0; c < nchain; ++c) {
+        const int b0 = chain_b0(c), nb = chain_b0(c + 1) - b0, first_img = b.img0 + b0;
+        std::vector<Op> &ops = chain_ops[c];
+        const size_t slot = chain_slot(nb);
+        float *X = (float *)(bb.scratch + used), *Y = (float *)(bb.scratch + used + slot);
+        used += 2 * slot;
+        // first convolution + Conv2d_1 as ONE launch (front.hip) when the three layers have MobileNet-1.0's widths: on frames at
+        // the network's input size (`front`), or chosen per call on resized ones (`front_rt`, front.hip GEN) -- then with
+        // Conv2d_1 being ONE op (the fused depthwise + pointwise)
+        const bool fits = ((fuse_mask >> 0) & 1) && h->first.mean && h->dw[0].pack && h->pw[0].taps == 1 && h->pw[0].mean && !h->pw[0].bias &&
+                          front_supports(nb, H, W, h->firstCp, h->dw[0].Cp, h->pw[0].CoutP) && h->pw[0].CinP == 32 && MB_STRIDE[0] == 1;
+        const bool front = front_fuse(h, b.ident && fits);
+        const bool front_rt = front_fuse(h, !b.ident && fits && dwpws_eligible(h->dw[0], h->pw[0], nb, h2, w2, MB_STRIDE[0]));
+        std::function<bool()> fused_now;
+        if (!front) {       // (front_rt: the fused launch writes Conv2d_1's output, `dwo` of layer 0 below)
+            const FirstLayer fl = first_layer_op(b, first_img, nb, h->pw[0].Cin_l, front_rt ? mobilenet_front(h, nb, H, W, Y) : FusedFront(), X);
+            ops.push_back(fl.op);
+            fused_now = fl.fused_now;
+        }
+        float *cur = X;
+        int ch = h2, cwid = w2;
+        for (int i = 0; i < 13; ++i) {
+            const int s = MB_STRIDE[i];
+            float *dwo = (cur == X) ? Y : X;
+            const ConvW &cw = h->pw[i];
+            if (i == 0 && front) {      // (a plan with this op runs frames of the network's own size only)
+                Op op;
+                op.cls = 6;
+                const double M = (double)nb * (H / 2) * (W / 2);
+                op.flops = (2.0 * 27 * cw.Cin_l + 2.0 * 9 * cw.Cin_l + 2.0 * cw.Cin_l * cw.Cout_l) * M;
+                op.bytes = (double)nb * H * W * 3 + M * cw.Cout_l * 4.0;
+                const FusedFront launch = mobilenet_front(h, nb, H, W, dwo);
+                op.run = [launch, h, first_img, H, W](hipStream_t st) { return launch(h->cur_images + (size_t)first_img * H * W * 3, nullptr, nullptr, 0, st); };
+                ops.push_back(op);
+                cur = dwo;
+                continue;
+            }
+            const bool fuse = ((fuse_mask >> i) & 1) && dwpws_eligible(h->dw[i], cw, nb, ch, cwid, s);
+            // f16x3: an unfused pair hands the depthwise result (exact fp32, in [0, 6]) to its pointwise
+            // convolution in split-fp16 rows, and the pointwise product runs as 3 x f16 MFMA
+            const int pw16 = b.X16 && !fuse && (h->dw[i].Cp % 32 == 0) ? 1 : 0;
+            if (!fuse) ops.push_back(make_dw_op(h->dw[i], cur, nb, ch, cwid, s, SSD_ACT_RELU6, dwo, h->pw[i].Cin_l, pw16, b.FL));
+            const int dh = ch, dwid = cwid;
+            ch /= s; cwid /= s;
+            float *pwo;
+            if (i == 4 || i == 10 || i == 12) {
+                float *full = i == 4 ? bb.C3 : (i == 10 ? bb.C4 : bb.C5);
+                pwo = full + (long long)b0 * ch * cwid * cw.CoutP;
+            } else {
+                pwo = fuse ? dwo : ((dwo == X) ? Y : X);    // fused: input `cur` is live until the launch ends
+            }
+            if (fuse) {
+                Op o = make_dwpws_op(h->dw[i], cw, cur, nb, dh, dwid, s, SSD_ACT_RELU6, SSD_ACT_RELU6, pwo);
+                if (i == 0 && front_rt) {        // (its work was done by the fused launch of the op before it when fused_now())
+                    const auto inner = o.run;
+                    o.run = [inner, fused_now](hipStream_t st) { return fused_now() ? hipSuccess : inner(st); };
+                }
+                ops.push_back(o);
+            } else {   // c5 feeds only the FPN (lateral5, p6): in f16x3 mode it is written in split-fp16 rows
+                ConvIO io{dwo, pwo};
+                io.in_fmt = pw16; io.out_fmt = (i == 12 && b.X16) ? 1 : 0; io.flags = b.FL;
+                ops.push_back(make_conv_op(h, cw, io, nb, 1, 0, SSD_ACT_RELU6, {dense_level(ch, cwid, ch, cwid, cw.CoutP)}, true));
+            }
+            if (i == 10 && nchain == 1) bb.id_c4 = (int)ops.size() - 1;          // Conv2d_11_pointwise = c4 (one chain: pl.ops keeps this index)
+            cur = pwo;
+        }
+    }
+    interleave_chains(b.pl, chain_ops, nchain, bb);
+    return SSD_OK;
+}
+
+// ---------------- ShuffleNet v2 (shufflenet_v2.py:50-69,79-137)
+// concat_shuffle_split (shufflenet_v2.py:94-115) and the stage concat (:89) run as NO kernel of their own:
+//   * every producer of a stage -- unit_1's two branches, unit j's conv1x1_after -- stores its D channels DENSE, one
+//     contiguous run per position, into a tensor of its own (16-byte stores from dwpw_stream.hip's accumulators, every
+//     line written whole by one launch);
+//   * unit j's conv1x1_before GATHERS its input row (sn_pw.hip): the host traces input channel k through the interleave-
+//     and-split of the reference back to (producer tensor, column) and gives the kernel that table; the k order -- and
+//     with it bit-identity with the oracle -- is untouched;
+//   * the stage output is kept in two-part rows [x half | y half] (weights.hip packs its consumers for that): the last
+//     unit stores its channels straight into the x half, the y half (channels no later unit touched) is one row gather.
+// Each stage is ONE allocation [producer tensors of chain 0 | ... of chain 1 | stage output S of the whole batch] under
+// one buffer resource (select_plans keeps it below 2 GiB).
+struct StageGeo { int ch, cw, oh, ow, D, Dp, n_units; long long tbytes[2], toff[2], soff, total; };
+
+// the stages at the network's input size H x W, in chains of nb[0] and nb[1] images
+static void sn_stage_geo(const ssd_handle *h, int H, int W, const int nb[2], StageGeo geo[3])
+{
+    int ch = H / 2 / 2, cw = W / 2 / 2;
+    for (int st = 0; st < 3; ++st) {
+        StageGeo &g = geo[st];
+        g.ch = ch; g.cw = cw; g.oh = ch / 2; g.ow = cw / 2; g.n_units = h->sn_stage[st].units;
+        const ConvW &after = h->pw[h->sn_stage[st].pw + 1];        // unit_1's conv1x1_after: the stage's D channels
+        g.Dp = after.CoutP; g.D = after.Cout_l;
+        long long off = 0;
+        for (int c = 0; c < 2; ++c) {
+            g.tbytes[c] = (long long)nb[c] * g.oh * g.ow * g.Dp * 4;       // one producer tensor of this chain
+            g.toff[c] = off;
+            off += g.tbytes[c] * g.n_units;                                  // x1, y1, o_2 .. o_{n-1}
+        }
+        g.soff = off;
+        g.total = off + (long long)(nb[0] + nb[1]) * g.oh * g.ow * 2 * g.Dp * 4;
+        ch = g.oh; cw = g.ow;
+    }
+}
+
+// chain c: images b0 .. b0 + nb - 1 through the three stages (allocations `stage`) into their rows of C5
+static int shufflenet_chain(Builder &b, const StageGeo *geo, float *const *stage, int c, int b0, int nb, float *C5, std::vector<Op> &ops)
+{
+    ssd_handle *const h = b.h;
+    const int H = b.H, W = b.W, h2 = H / 2, w2 = W / 2, h4 = h2 / 2, w4 = w2 / 2, fc = h->firstCp, first_img = b.img0 + b0;
+    // depthwise -> 1x1 pairs of the units as one launch each (option fuse_dw = 0 keeps them apart)
+    bool sn_fuse = SSD_FUSE_SHUFFLE_DEFAULT;
+    if (ssd_opt(h, OPT_FUSE_DW, -1) >= 0) sn_fuse = ssd_opt(h, OPT_FUSE_DW, -1) != 0;
+    float *MP, *MID = nullptr;
+    SSDCHK(b.falloc(&MP, (long long)nb * h4 * w4 * fc));
+    // depthwise -> 1x1 (+ batch norms, ReLU behind the 1x1) into dense rows [M][out_rs]: one launch of the streaming kernel, or
+    // (option fuse_dw = 0, shapes it does not take) the depthwise kernel and the implicit-GEMM kernel with a tensor between them
+    auto pair = [&](const DwW &d, const ConvW &cw, const float *in, int hh, int ww, int stride, float *out, int out_rs) -> int {
+        if (sn_fuse && dwpws_eligible(d, cw, nb, hh, ww, stride)) {
+            ops.push_back(make_dwpws_op(d, cw, in, nb, hh, ww, stride, SSD_ACT_NONE, SSD_ACT_RELU, out, out_rs));
+            return SSD_OK;
+        }
+        if (!MID) SSDCHK(b.falloc(&MID, (long long)nb * h4 * w4 * std::max(fc, 32)));       // (the largest depthwise output: Stage2 unit_1 reads h4 x w4)
+        const int oh = hh / stride, ow = ww / stride;
+        if ((long long)nb * oh * ow * d.Cp > (long long)nb * h4 * w4 * std::max(fc, 32)) return ssd_fail(SSD_ERR_INVALID, "ssd_forward: depthwise scratch too small");
+        ops.push_back(make_dw_op(d, in, nb, hh, ww, stride, SSD_ACT_NONE, MID, cw.Cin_l));
+        LevelDesc lv = dense_level(oh, ow, oh, ow, cw.CoutP);
+        lv.out_rstride = out_rs > 0 ? out_rs : cw.CoutP;
+        lv.out_bstride = (long long)oh * ow * lv.out_rstride;
+        ops.push_back(make_conv_op(h, cw, {MID, out}, nb, 1, 0, SSD_ACT_RELU, {lv}, true));
+        return SSD_OK;
+    };
+    {   // first convolution + max pool as ONE launch (front.hip) when the frames arrive at the network's input size: the
+        // half-resolution tensor stays in LDS.  Resized frames: first_layer_op; its fused launch then writes the pooled tensor
+        // and the max-pool op does nothing.
+        const DwW f = h->first;
+        const int act = h->firstAct;
+        const FusedFront pool = [nb, H, W, f, act, MP](const uint8_t *img, const int *src, const MixedGeom *mixed, int first, hipStream_t s) {
+            return launch_front_pool(img, nb, H, W, f.w, f.Cp, f.mean, f.sf, f.beta, act, MP, s, src, mixed, first);
+        };
+        if (front_fuse(h, b.ident && h->first.mean && front_pool_supports(b.B, H, W, fc))) {
+            Op op;
+            op.cls = 3;
+            op.flops = 2.0 * 27 * (double)nb * h2 * w2 * 24;
+            op.bytes = (double)nb * H * W * 3 + (double)nb * h4 * w4 * 24 * 4.0;
+            op.run = [pool, h, first_img, H, W](hipStream_t s) { return pool(h->cur_images + (size_t)first_img * H * W * 3, nullptr, nullptr, 0, s); };
+            ops.push_back(op);
+        } else {
+            float *F;
+            SSDCHK(b.falloc(&F, (long long)nb * h2 * w2 * fc));
+            const bool rt = front_fuse(h, !b.ident && h->first.mean && front_pool_supports(nb, H, W, fc));
+            const FirstLayer fl = first_layer_op(b, first_img, nb, 24, rt ? pool : FusedFront(), F);
+            ops.push_back(fl.op);
+            Op mp;
+            mp.cls = 5; mp.flops = 0;
+            mp.bytes = ((double)nb * h2 * w2 + (double)nb * h4 * w4) * 24 * 4.0;
+            const std::function<bool()> fused_now = fl.fused_now;
+            mp.run = [fused_now, F, nb, h2, w2, fc, MP](hipStream_t s) { return fused_now() ? hipSuccess : launch_maxpool(F, nb, h2, w2, fc, MP, s); };
+            ops.push_back(mp);
+        }
+    }
+    const float *cur = MP;
+    for (int st = 0; st < 3; ++st) {
+        const StageGeo &g = geo[st];
+        // the stage's layers in their order (weights.hip): unit_1's three 1x1 and two depthwise layers, then each unit's two and one
+        const ConvW *pw = &h->pw[h->sn_stage[st].pw];
+        const DwW *dw = &h->dw[h->sn_stage[st].dw];
+        const ConvW &before = pw[0], &after = pw[1], &after2 = pw[2];
+        const DwW &d1 = dw[0], &d2 = dw[1];
+        pw += 3; dw += 2;
+        const int D = g.D, Dp = g.Dp, n_units = g.n_units;
+        const long long rows = (long long)nb * g.oh * g.ow;
+        float *t1, *U;
+        SSDCHK(b.falloc(&t1, (long long)nb * g.ch * g.cw * before.CoutP));
+        SSDCHK(b.falloc(&U, rows * Dp));
+        float *sb = stage[st];
+        // producer p's tensor of this chain (0: unit_1's second branch = x, 1: its main branch = y, j: unit j's output)
+        auto tensor_off = [&](int p) { return g.toff[c] + (long long)p * g.tbytes[c]; };
+        // the chain's rows of S start b0 images into the stage output
+        float *S_chain = sb + g.soff / 4 + (long long)b0 * g.oh * g.ow * 2 * Dp;
+        struct Src { int prod, col; };
+        std::vector<Src> x(D), y(D);
+        for (int d = 0; d < D; ++d) { x[d] = Src{0, d}; y[d] = Src{1, d}; }
+        auto table = [&](const std::vector<Src> &v) {      // physical channel p of a D-channel row -> byte offset of its source
+            std::vector<int> t(Dp, -1);
+            for (int d = 0; d < D; ++d) t[ssd_phys_of_logical(d)] = (int)(tensor_off(v[d].prod) + (long long)ssd_phys_of_logical(v[d].col) * 4);
+            return t;
+        };
+        std::vector<const int *> src_dev(n_units + 1, nullptr);
+        for (int j = 2; j <= n_units; ++j) {
+            std::vector<Src> z(2 * D);
+            for (int d = 0; d < D; ++d) { z[2 * d] = x[d]; z[2 * d + 1] = y[d]; }
+            std::vector<Src> xin(z.begin(), z.begin() + D);
+            int *dv;
+            SSDCHK(b.pl.pool.upload(&dv, table(xin)));
+            src_dev[j] = dv;
+            for (int d = 0; d < D; ++d) { x[d] = Src{j, d}; y[d] = z[D + d]; }
+        }
+        int *ysrc;
+        SSDCHK(b.pl.pool.upload(&ysrc, table(y)));          // the stage output's y half (x = unit n's own channels)
+        ops.push_back(make_conv_op(h, before, {cur, t1}, nb, 1, 0, SSD_ACT_RELU, {dense_level(g.ch, g.cw, g.ch, g.cw, before.CoutP)}, true));
+        SSDCHK(pair(d1, after, t1, g.ch, g.cw, 2, sb + tensor_off(1) / 4, 0));
+        SSDCHK(pair(d2, after2, cur, g.ch, g.cw, 2, sb + tensor_off(0) / 4, 0));
+        for (int j = 2; j <= n_units; ++j, pw += 2, dw += 1) {
+            const ConvW &b2 = pw[0], &a2 = pw[1];
+            const DwW &dd = dw[0];
+            if (b2.CinP != Dp || b2.taps != 1 || !b2.mean || b2.bias || !pw_gather_supports(b2.CinP, b2.CoutP, rows, Dp * 4, g.total, rows * b2.CoutP * 4))
+                return ssd_fail(SSD_ERR_INVALID, "ssd_forward: a ShuffleNet unit's conv1x1_before is not a shape of the gathering kernel (sn_pw.hip)");
+#ifdef SSD_DIAG
+            // ablation (scripts/experiments/sn_unit_fusion_bound.py): drop conv1x1_before of the stages in the mask -- WRONG
+            // results, the time of a step whose first 1x1 of every unit is free: what no whole-unit fusion can beat
+            if (const char *e = getenv("SSD_ABL_SKIP_PWG")) { if ((atoi(e) >> st) & 1) goto skip_before; }
+#endif
+            ops.push_back(make_pw_gather_op(b2, sb, g.total, src_dev[j], Dp * 4, rows, SSD_ACT_RELU, U));
+#ifdef SSD_DIAG
+        skip_before:
+#endif
+            if (j < n_units) SSDCHK(pair(dd, a2, U, g.oh, g.ow, 1, sb + tensor_off(j) / 4, 0));
+            else SSDCHK(pair(dd, a2, U, g.oh, g.ow, 1, S_chain, 2 * Dp));
+        }
+        {
+            Op gop;
+            gop.cls = 5; gop.flops = 0; gop.bytes = 2.0 * rows * D * 4.0;
+            const int rs = Dp * 4, ors = 2 * Dp;
+            float *ydst = S_chain + Dp;
+            gop.run = [sb, ysrc, rs, rows, Dp, ydst, ors](hipStream_t s) { return launch_gather_rows(sb, ysrc, rs, rows, Dp, ydst, ors, s); };
+            ops.push_back(gop);
+        }
+        cur = S_chain;
+    }
+    const StageGeo &g2 = geo[2];
+    const ConvW &c5w = h->pw.back();            // Conv5, behind the stages
+    ConvIO io{cur, C5 + (long long)b0 * g2.oh * g2.ow * c5w.CoutP};
+    io.out_fmt = b.X16; io.flags = b.FL;
+    ops.push_back(make_conv_op(h, c5w, io, nb, 1, 0, SSD_ACT_RELU, {dense_level(g2.oh, g2.ow, g2.oh, g2.ow, c5w.CoutP)}, true));
+    return SSD_OK;
+}
+
+static int shufflenet_backbone(Builder &b, Backbone &bb)
+{
+    ssd_handle *h = b.h;
+    const int B = b.B;
+    const int nchain = backbone_chains(h, B, 2);
+    const int nb_of[2] = {nchain == 2 ? B / 2 : B, nchain == 2 ? B - B / 2 : 0};
+    StageGeo geo[3];
+    sn_stage_geo(h, b.H, b.W, nb_of, geo);
+    for (const StageGeo &g : geo)
+        if (g.total >= (1LL << 31)) return ssd_fail(SSD_ERR_INVALID, "ssd_forward: ShuffleNet stage allocation past 2 GiB (sub-batch split failed)");
+    float *stage[3];
+    for (int st = 0; st < 3; ++st) SSDCHK(b.falloc(&stage[st], geo[st].total / 4));
+    const StageGeo &g2 = geo[2];
+    const ConvW &c5w = h->pw.back();
+    SSDCHK(b.falloc(&bb.C5, (long long)B * g2.oh * g2.ow * c5w.CoutP));
+    std::vector<Op> chain_ops[2];
+    for (int c = 0; c < nchain; ++c) SSDCHK(shufflenet_chain(b, geo, stage, c, c == 0 ? 0 : nb_of[0], nb_of[c], bb.C5, chain_ops[c]));
+    for (int st = 0; st < 2; ++st) {
+        float *S = stage[st] + geo[st].soff / 4;
+        if (st == 0) bb.C3 = S; else bb.C4 = S;
+        b.pl.retained[st == 0 ? "c3" : "c4"] = Retained{S, B, geo[st].oh, geo[st].ow, 2 * geo[st].D, 2 * geo[st].Dp, true, 0, geo[st].D};
+    }
+    b.pl.retained["c5"] = Retained{bb.C5, B, g2.oh, g2.ow, c5w.Cout_l, c5w.CoutP, true, b.X16};
+    interleave_chains(b.pl, chain_ops, nchain, bb);
+    return SSD_OK;
+}
+
+// What the FPN hands to the heads
+struct Fpn {
+    Pyr py;
+    float *P;                       // p3 .. p7 behind each other (py.off)
+    int id_p3, id_p4, id_p7;        // the ops the towers' first layers wait on
+};
+
+// a pyramid level's launch: the input of level `in`, the output of level `out` into P
+static LevelDesc pyr_level(const Pyr &py, int in, int out)
+{
+    LevelDesc d = dense_level(py.h[in], py.w[in], py.h[out], py.w[out], 256);
+    d.out_off = py.off[out];
+    return d;
+}
+
+// ---------------- FPN (feature_extractor.py:40-76)
+// Three streams, explicit dependencies.  Serving batches: main: lateral5 -> lateral4 (+up) -> lateral3 (+up) -> p3 (the
+// critical path); second stream: p5 (needs x5) -> p4 (needs x4); third stream: p6 -> p7 (need only c5).
+// All of them are the same 3x3 kernel, and two such kernels side by side fill each other's tails.
+static int fpn(Builder &b, const Backbone &bb, Fpn &f)
+{
+    ssd_handle *h = b.h;
+    const int B = b.B, X16 = b.X16;
+    f.py = make_pyr(B, b.H, b.W, 256);
+    const Pyr &py = f.py;
+    float *P, *X5, *X4, *X3, *T6;
+    SSDCHK(b.falloc(&P, py.total));
+    SSDCHK(b.falloc(&X5, (long long)B * py.h[2] * py.w[2] * 256));
+    SSDCHK(b.falloc(&X4, (long long)B * py.h[1] * py.w[1] * 256));
+    SSDCHK(b.falloc(&X3, (long long)B * py.h[0] * py.w[0] * 256));
+    SSDCHK(b.falloc(&T6, (long long)B * py.h[3] * py.w[3] * 256));
+    f.P = P;
+    auto lvl = [&](int l) { return dense_level(py.h[l], py.w[l], py.h[l], py.w[l], 256); };
+    // last backbone op on the main stream (produces c5, or its first part); the other parts, if any, end on other
+    // streams: the main stream's first FPN op waits for them
+    const int id_c5 = bb.last[0] >= 0 ? bb.last[0] : (int)b.pl.ops.size() - 1;
     // Batch 1-2 in exact fp32: p3, p4, p5 (the same 3x3 256 -> 256 + batch norm + ReLU on x3, x4, x5) and p7 as ONE launch
     // behind lateral3, each level with its own kernel (IgemmLevel::wt_off into h->pgroup) and batch norm: 736 tiles -- a
     // tower-sized launch -- instead of three launches that stretch each other.  Option fpn_group = 0 / 1 pins it.
@@ -793,81 +819,68 @@ static int build_plan(ssd_handle *h, Plan &pl, int B, int H, int W, bool ident, 
     // stream as soon as c4 exists (c3 precedes it on the caller's stream), beside the backbone's last four layers; behind c5
     // the third stream then runs lateral5 and ONE elementwise launch for both top-down sums (fpn_merge_kernel) instead of a
     // chain of three convolutions.  Same additions, same bits.  Option fpn_early_lat = 0 / 1 pins it.
-    bool early = swap67 && !X16 && id_c4 >= 0;
+    bool early = swap67 && !X16 && bb.id_c4 >= 0;
     { const int pin = ssd_opt(h, OPT_FPN_EARLY_LAT, -1); if (pin >= 0) early = early && pin != 0; }
     float *L4T = nullptr;
     if (early) {
-        SSDCHK(falloc(&L4T, (long long)B * py.h[1] * py.w[1] * 256));
-        push(make_conv_op(h, h->lat[0], C3, X3, nullptr, nullptr, B, 1, 0, SSD_ACT_NONE, {lvl(0, 256)}, true), s_lat, {id_c4});
-        push(make_conv_op(h, h->lat[1], C4, L4T, nullptr, nullptr, B, 1, 0, SSD_ACT_NONE, {lvl(1, 256)}, true), s_lat);
+        SSDCHK(b.falloc(&L4T, (long long)B * py.h[1] * py.w[1] * 256));
+        b.push(b.conv(h->lat[0], {bb.C3, X3}, 1, 0, SSD_ACT_NONE, {lvl(0)}), s_lat, {bb.id_c4});
+        b.push(b.conv(h->lat[1], {bb.C4, L4T}, 1, 0, SSD_ACT_NONE, {lvl(1)}), s_lat);
     }
     std::vector<int> l5_deps;
-    for (int c = 1; c < 4; ++c) if (id_bb_last[c] >= 0) l5_deps.push_back(id_bb_last[c]);
+    for (int c = 1; c < 4; ++c) if (bb.last[c] >= 0) l5_deps.push_back(bb.last[c]);
     if (swap67) l5_deps.push_back(id_c5);
-    const int id_l5 = push(make_conv_op(h, h->lat[2], C5, X5, nullptr, nullptr, B, 1, 0, SSD_ACT_NONE, {lvl(2, 256)}, true, X16, X16, 0, FL), s_lat, l5_deps);
+    const int id_l5 = b.push(b.conv(h->lat[2], b.io16(bb.C5, X5), 1, 0, SSD_ACT_NONE, {lvl(2)}), s_lat, l5_deps);
     std::vector<int> p6_deps = {id_c5};             // c5 of every backbone chain that is not on p6's own stream
-    for (int c = 1; c < 4; ++c) if (c != 2 && id_bb_last[c] >= 0) p6_deps.push_back(id_bb_last[c]);
-    int id_p7;
+    for (int c = 1; c < 4; ++c) if (c != 2 && bb.last[c] >= 0) p6_deps.push_back(bb.last[c]);
     {   // p6 = conv s2 (c5): BN+ReLU -> P6, ReLU(raw) -> T6 (input of p7, :60)
-        LevelDesc d = dense_level(py.h[2], py.w[2], py.h[3], py.w[3], 256);
-        d.out_off = py.off[3];
-        push(make_conv_op(h, h->pconv[3], C5, P, T6 - py.off[3], nullptr, B, 2, 1, SSD_ACT_RELU, {d}, true, X16, X16, 0, FL), swap67 ? 0 : 2, p6_deps);
-        LevelDesc d7 = dense_level(py.h[3], py.w[3], py.h[4], py.w[4], 256);
-        d7.out_off = py.off[4];
-        if (!p7grouped) id_p7 = push(make_conv_op(h, h->pconv[4], T6, P, nullptr, nullptr, B, 2, 1, SSD_ACT_RELU, {d7}, true, X16, X16, 0, FL), swap67 ? 0 : 2);
-        else id_p7 = -1;
+        ConvIO io = b.io16(bb.C5, P);
+        io.out2 = T6 - py.off[3];
+        b.push(b.conv(h->pconv[3], io, 2, 1, SSD_ACT_RELU, {pyr_level(py, 2, 3)}), swap67 ? 0 : 2, p6_deps);
     }
-    if (!grouped) {   // p5 = conv(x5)
-        LevelDesc d = lvl(2, 256);
-        d.out_off = py.off[2];
-        push(make_conv_op(h, h->pconv[2], X5, P, nullptr, nullptr, B, 1, 1, SSD_ACT_RELU, {d}, true, X16, X16, 0, FL), 1, {id_l5});
-    }
+    f.id_p7 = p7grouped ? -1 : b.push(b.conv(h->pconv[4], b.io16(T6, P), 2, 1, SSD_ACT_RELU, {pyr_level(py, 3, 4)}), swap67 ? 0 : 2);
+    if (!grouped)   // p5 = conv(x5)
+        b.push(b.conv(h->pconv[2], b.io16(X5, P), 1, 1, SSD_ACT_RELU, {pyr_level(py, 2, 2)}), 1, {id_l5});
     // x4 = up(x5) + lateral4(c4); p4;  x3 = up(x4) + lateral3(c3); p3
     // lateral4 / lateral3 read c4 / c3, which stay fp32 rows for the depthwise layer that also consumes them: in
     // f16x3 mode the rows are split into halves while they are staged (in_fmt 2); the upsampled operand and the
     // output follow the mode
     int LF = X16 && h->lat[1].tile == IGEMM_128x128 && h->lat[0].tile == IGEMM_128x128 ? 2 : 0;
     if (!ssd_opt(h, OPT_LATERAL_SPLIT, 1)) LF = 0;       // A/B runs: 0 keeps them on the exact MFMA
+    auto lateral = [&](const ConvW &cw, const float *c, float *x, const float *up, int l) {
+        ConvIO io = b.io16(c, x);
+        io.in_fmt = LF; io.res = up; io.res_fmt = X16;
+        return b.conv(cw, io, 1, 0, SSD_ACT_NONE, {lvl(l)});
+    };
     int id_l4, id_merge = -1;
     if (early) {
         Op m;
         m.cls = 5; m.flops = 0;
         m.bytes = ((double)B * py.h[0] * py.w[0] * 2 + (double)B * py.h[1] * py.w[1] * 2 + (double)B * py.h[2] * py.w[2]) * 256 * 4.0;
         const int mh = py.h[0], mw = py.w[0];
-        float *l4t = L4T;
-        m.run = [=](hipStream_t s) { return launch_fpn_merge(X5, l4t, X4, X3, B, mh, mw, 256, s); };
-        id_l4 = id_merge = push(m, s_lat);
+        m.run = [X5, L4T, X4, X3, B, mh, mw](hipStream_t s) { return launch_fpn_merge(X5, L4T, X4, X3, B, mh, mw, 256, s); };
+        id_l4 = id_merge = b.push(m, s_lat);
     } else {
-        id_l4 = push(make_conv_op(h, h->lat[1], C4, X4, nullptr, X5, B, 1, 0, SSD_ACT_NONE, {lvl(1, 256)}, true, LF, X16, X16, FL), s_lat);
+        id_l4 = b.push(lateral(h->lat[1], bb.C4, X4, X5, 1), s_lat);
     }
-    int id_p4, id_p3;
+    if (!grouped) f.id_p4 = b.push(b.conv(h->pconv[1], b.io16(X4, P), 1, 1, SSD_ACT_RELU, {pyr_level(py, 1, 1)}), 1, {id_l4});
+    const int id_l3 = early ? id_merge : b.push(lateral(h->lat[0], bb.C3, X3, X4, 0), s_lat);
     if (!grouped) {
-        LevelDesc d = lvl(1, 256);
-        d.out_off = py.off[1];
-        id_p4 = push(make_conv_op(h, h->pconv[1], X4, P, nullptr, nullptr, B, 1, 1, SSD_ACT_RELU, {d}, true, X16, X16, 0, FL), 1, {id_l4});
-    }
-    const int id_l3 = early ? id_merge
-                            : push(make_conv_op(h, h->lat[0], C3, X3, nullptr, X4, B, 1, 0, SSD_ACT_NONE, {lvl(0, 256)}, true, LF, X16, X16, FL), s_lat);
-    if (!grouped) {
-        LevelDesc d = lvl(0, 256);
-        d.out_off = py.off[0];
-        id_p3 = push(make_conv_op(h, h->pconv[0], X3, P, nullptr, nullptr, B, 1, 1, SSD_ACT_RELU, {d}, true, X16, X16, 0, FL), 0);
+        f.id_p3 = b.push(b.conv(h->pconv[0], b.io16(X3, P), 1, 1, SSD_ACT_RELU, {pyr_level(py, 0, 0)}), 0);
     } else {
         const ConvW &g = h->pgroup;
         const float *xin[3] = {X3, X4, X5};
         std::vector<LevelDesc> lv3;
         for (int l = 0; l < 3; ++l) {
-            LevelDesc d = lvl(l, 256);
+            LevelDesc d = pyr_level(py, l, l);
             d.in_off = xin[l] - X3;                         // the three inputs are separate allocations: offsets from x3
-            d.out_off = py.off[l];
             d.param_off = l * g.CoutP;
             d.wt_off = (long long)l * g.taps * g.CoutPad * g.CinP;
             lv3.push_back(d);
         }
         if (p7grouped) {
-            LevelDesc d = dense_level(py.h[3], py.w[3], py.h[4], py.w[4], 256);
+            LevelDesc d = pyr_level(py, 3, 4);
             d.in_off = T6 - X3;
-            d.out_off = py.off[4];
             d.param_off = 3 * g.CoutP;
             d.wt_off = (long long)3 * g.taps * g.CoutPad * g.CinP;
             d.stride = 2; d.pad = 1;
@@ -875,29 +888,35 @@ static int build_plan(ssd_handle *h, Plan &pl, int B, int H, int W, bool ident, 
         }
         std::vector<int> gdeps;
         if (swap67) gdeps.push_back(id_l3);
-        id_p3 = id_p4 = push(make_conv_op(h, g, X3, P, nullptr, nullptr, B, 1, 1, SSD_ACT_RELU, lv3, true), 0, gdeps);
-        if (p7grouped) id_p7 = id_p3;
+        f.id_p3 = f.id_p4 = b.push(b.conv(g, {X3, P}, 1, 1, SSD_ACT_RELU, lv3), 0, gdeps);
+        if (p7grouped) f.id_p7 = f.id_p3;
     }
     for (int l = 0; l < 5; ++l) {
         char nm[8];
         snprintf(nm, sizeof nm, "p%d", l + 3);
-        pl.retained[nm] = Retained{P + py.off[l], B, py.h[l], py.w[l], 256, 256, true, X16};
+        b.pl.retained[nm] = Retained{P + py.off[l], B, py.h[l], py.w[l], 256, 256, true, X16};
     }
+    return SSD_OK;
+}
 
-    // ---------------- heads (box_predictor.py:36-155), all levels per launch; box tower on the
-    // main stream, class tower on the second stream (independent chains)
-    const int C = h->cfg.num_classes, A = 6;
+// ---------------- heads (box_predictor.py:36-155), all levels per launch; box tower on the
+// main stream, class tower on the second stream (independent chains); anchors + post-processing
+static int heads(Builder &b, const Backbone &bb, const Fpn &f)
+{
+    ssd_handle *h = b.h;
+    Plan &pl = b.pl;
+    const Pyr &py = f.py;
+    const int B = b.B, C = h->cfg.num_classes, A = 6;
     long long N = 0, aoff[5];
     for (int l = 0; l < 5; ++l) { aoff[l] = N; N += (long long)py.h[l] * py.w[l] * A; }
     pl.N = (int)N;
     float *logits, *codes;
-    SSDCHK(falloc(&logits, (long long)B * N * C));
-    SSDCHK(falloc(&codes, (long long)B * N * 4));
-    // ---------------- anchors + post-processing
+    SSDCHK(b.falloc(&logits, (long long)B * N * C));
+    SSDCHK(b.falloc(&codes, (long long)B * N * 4));
     std::vector<float> anc((size_t)N * 4);
-    SSDCHK(ssd_anchors(H, W, anc.data()));
+    SSDCHK(ssd_anchors(b.H, b.W, anc.data()));
     float *anc_dev;
-    SSDCHK(ap.upload(&anc_dev, anc));
+    SSDCHK(pl.pool.upload(&anc_dev, anc));
     // The head towers' four ping-pong buffers as one block: inside the backbone's block when they fit (MobileNet: they do), else
     // a block of their own (ShuffleNet, whose backbone tensors are stage allocations the FPN still reads).  Either way the block is
     // dead once the two final head convolutions are done -- and the post-processing starts behind both of them (ev_join) -- so the
@@ -907,10 +926,10 @@ static int build_plan(ssd_handle *h, Plan &pl, int B, int H, int W, bool ident, 
     unsigned char *keys_home = nullptr;
     {
         const size_t slot = scratch_slot((size_t)py.total * sizeof(float));
-        unsigned char *tb = scratch;
-        size_t tb_bytes = scratch_bytes;
-        if (!scratch || 4 * slot > scratch_bytes) {
-            SSDCHK(ap.alloc((void **)&tb, 4 * slot));
+        unsigned char *tb = bb.scratch;
+        size_t tb_bytes = bb.scratch_bytes;
+        if (!bb.scratch || 4 * slot > bb.scratch_bytes) {
+            SSDCHK(pl.pool.alloc((void **)&tb, 4 * slot));
             tb_bytes = 4 * slot;
         }
         for (int t = 0; t < 2; ++t)
@@ -919,7 +938,7 @@ static int build_plan(ssd_handle *h, Plan &pl, int B, int H, int W, bool ident, 
     }
     void *ws;
     const size_t wsb = post_workspace_bytes(B, (int)N, C, h->cfg.max_boxes_per_class, keys_home == nullptr);
-    SSDCHK(ap.alloc(&ws, wsb));
+    SSDCHK(pl.pool.alloc(&ws, wsb));
     PostArgs &p = pl.post;
     memset(&p, 0, sizeof(p));
     p.logits = logits; p.codes = codes; p.anchors = anc_dev;
@@ -935,12 +954,12 @@ static int build_plan(ssd_handle *h, Plan &pl, int B, int H, int W, bool ident, 
     std::vector<Op> tower_ops[2];
     bool all_marked = true;
     for (int t = 0; t < 2; ++t) {
-        const float *in = P;
+        const float *in = f.P;
         int cur = 0;
         for (int i = 0; i < 4; ++i) {
             std::vector<LevelDesc> lv;
             for (int l = 0; l < 5; ++l) lv.push_back(dense_level(py.h[l], py.w[l], py.h[l], py.w[l], 256, py.off[l], py.off[l], l * 256));
-            tower_ops[t].push_back(make_conv_op(h, h->tower[t][i], in, TAB[t][cur], nullptr, nullptr, B, 1, 1, SSD_ACT_RELU, lv, true, X16, X16, 0, FL));
+            tower_ops[t].push_back(b.conv(h->tower[t][i], b.io16(in, TAB[t][cur]), 1, 1, SSD_ACT_RELU, lv));
             in = TAB[t][cur];
             cur ^= 1;
         }
@@ -957,9 +976,11 @@ static int build_plan(ssd_handle *h, Plan &pl, int B, int H, int W, bool ident, 
             d.param_off = 0;
             lv.push_back(d);
         }
+        ConvIO io = b.io16(in, t == 0 ? codes : logits);
+        io.out_fmt = 0;             // (fp32 rows: the post-processing reads them)
         bool marked = false;
-        Op fop = make_conv_op(h, h->final_[t], in, t == 0 ? codes : logits, nullptr, nullptr, B, 1, 1, SSD_ACT_NONE, lv, false, X16, 0, 0, FL,
-                              can_mark ? p.scan_bits : nullptr, conservative_logit_bound(h->cfg.score_threshold), &marked);
+        Op fop = make_conv_op(h, h->final_[t], io, B, 1, 1, SSD_ACT_NONE, lv, false, can_mark ? p.scan_bits : nullptr,
+                              conservative_logit_bound(h->cfg.score_threshold), &marked);
         if (t == 1) all_marked = all_marked && marked;
         tower_ops[t].push_back(fop);
     }
@@ -970,23 +991,35 @@ static int build_plan(ssd_handle *h, Plan &pl, int B, int H, int W, bool ident, 
     for (size_t i = 0; i < tower_ops[0].size(); ++i)
         for (int t = 1; t >= 0; --t) {
             std::vector<int> deps;
-            if (i == 0) { deps.push_back(t == 0 ? id_p4 : id_p3); deps.push_back(id_p7); }
-            push(tower_ops[t][i], t, deps);
+            if (i == 0) { deps.push_back(t == 0 ? f.id_p4 : f.id_p3); deps.push_back(f.id_p7); }
+            b.push(tower_ops[t][i], t, deps);
         }
-    {   // does a chain start on an internal stream without a dependency (the second backbone chain from 4 images on)?
-        bool seen[4] = {true, false, false, false};
-        for (const Op &op : pl.ops) {
-            if (!seen[op.stream] && op.deps.empty()) pl.need_begin = true;
-            seen[op.stream] = true;
-        }
+    pl.retained["encoded_boxes"] = Retained{codes, B, 1, (int)N, 4, 4, false};
+    pl.retained["class_predictions"] = Retained{logits, B, 1, (int)N, C, C, false};
+    return SSD_OK;
+}
+
+// H, W: the network's input size (multiples of 128); ident: the source frames already have it (no resize, no pad band)
+static int build_plan(ssd_handle *h, Plan &pl, int B, int H, int W, bool ident, int img0)
+{
+    pl.B = B;
+    pl.img0 = img0;
+    Builder b{h, pl, B, H, W, ident, img0, h->precision == SSD_PRECISION_F16X3 ? 1 : 0, h->flags_dev};
+    Backbone bb;
+    SSDCHK(h->cfg.backbone == SSD_BACKBONE_MOBILENET ? mobilenet_backbone(b, bb) : shufflenet_backbone(b, bb));
+    Fpn f;
+    SSDCHK(fpn(b, bb, f));
+    SSDCHK(heads(b, bb, f));
+    // does a chain start on an internal stream without a dependency (the second backbone chain from 4 images on)?
+    bool seen[4] = {true, false, false, false};
+    for (const Op &op : pl.ops) {
+        if (!seen[op.stream] && op.deps.empty()) pl.need_begin = true;
+        seen[op.stream] = true;
     }
     // events for every op another stream waits on
     for (const Op &op : pl.ops)
         for (int d : op.deps)
             if (!pl.ops[d].done) HIPCHK(hipEventCreateWithFlags(&pl.ops[d].done, ssd_sync_event_flags(h)));
-    pl.retained["encoded_boxes"] = Retained{codes, B, 1, (int)N, 4, 4, false};
-    pl.retained["class_predictions"] = Retained{logits, B, 1, (int)N, C, C, false};
-
     return SSD_OK;
 }
 
@@ -1158,12 +1191,10 @@ int select_plans_net(ssd_handle *h, int B, int netH, int netW, int ident, long l
         per_img = std::max(per_img, (long long)ssd_num_anchors(nH, nW) * std::max(h->cfg.num_classes, 4) * 4);
         per_img = std::max(per_img, max_src_bytes);
         if (h->cfg.backbone == SSD_BACKBONE_SHUFFLENET) {        // a ShuffleNet stage is one allocation: its producers' tensors + its two-part output
-            const int un[3] = {4, 8, 4};
-            int ipw = 0, hh = nH / 8, ww = nW / 8;
-            for (int st = 0; st < 3 && ipw + 1 < (int)h->pw.size(); ++st) {
-                per_img = std::max(per_img, (long long)hh * ww * (un[st] + 2) * h->pw[ipw + 1].CoutP * 4);
-                ipw += 3 + 2 * (un[st] - 1); hh /= 2; ww /= 2;
-            }
+            const int one[2] = {1, 0};
+            StageGeo geo[3];
+            sn_stage_geo(h, nH, nW, one, geo);
+            for (const StageGeo &g : geo) per_img = std::max(per_img, g.total);
         }
         const long long bmax = ((1LL << 31) - 1) / per_img;
         if (bmax < 1) return ssd_fail(SSD_ERR_INVALID, "ssd_forward: image too large for one launch");

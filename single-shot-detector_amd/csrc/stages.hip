@@ -173,8 +173,9 @@ static int conv2d_impl(int x16, const float *in_dev, int32_t B, int32_t H, int32
             SSDCHK(pool.alloc((void **)&tup, (size_t)(rout / 4) * CoutP * 4));
             HIPCHK(launch_permute_channels(up_dev, rout / 4, Cout, CoutP, o16 ? 3 : 1, tup, s));
         }
-        Op op = make_conv_op(nullptr, cw, tin, tout, nullptr, tup, B, stride, pad_beg, act, {dense_level(H, W, OH, OW, CoutP)}, true,
-                             x16, o16, o16, flags);
+        ConvIO io{tin, tout};
+        io.res = tup; io.in_fmt = x16; io.out_fmt = io.res_fmt = o16; io.flags = flags;
+        Op op = make_conv_op(nullptr, cw, io, B, stride, pad_beg, act, {dense_level(H, W, OH, OW, CoutP)}, true);
         HIPCHK(op.run(s));
         HIPCHK(launch_permute_channels(tout, rout, Cout, CoutP, o16 ? 2 : 0, out_dev, s));
         HIPCHK(hipStreamSynchronize(s));
@@ -601,7 +602,9 @@ extern "C" int ssd_bench_conv(int32_t B, int32_t H, int32_t W, int32_t Cin, int3
             HIPCHK(launch_permute_channels(in, in_total / CinP, CinP, CinP, 3, in16, nullptr));
             in = in16;
         }
-        Op op = make_conv_op(nullptr, cw, in, out, nullptr, nullptr, B, stride, pad, SSD_ACT_RELU, lv, true, x16, x16);
+        ConvIO io{in, out};
+        io.in_fmt = io.out_fmt = x16;
+        Op op = make_conv_op(nullptr, cw, io, B, stride, pad, SSD_ACT_RELU, lv, true);
         g_dbg_ts = nullptr;
         g_force_tile = -1;
         hipEvent_t e0, e1;
@@ -678,7 +681,7 @@ extern "C" int ssd_bench_dwpw(int32_t B, int32_t H, int32_t W, int32_t C, int32_
             return ssd_fail(SSD_ERR_INVALID, "ssd_bench_dwpw: fused must be 0 (two kernels) or 1 (dwpw_stream.hip)");
         } else {
             ops.push_back(make_dw_op(d, in, B, H, W, stride, SSD_ACT_RELU6, mid, C));
-            ops.push_back(make_conv_op(nullptr, cw, mid, out, nullptr, nullptr, B, 1, 0, SSD_ACT_RELU6, {dense_level(OH, OW, OH, OW, CoutP)}, true));
+            ops.push_back(make_conv_op(nullptr, cw, {mid, out}, B, 1, 0, SSD_ACT_RELU6, {dense_level(OH, OW, OH, OW, CoutP)}, true));
         }
         const char *dump = getenv("SSD_TS_DUMP");
         hipEvent_t e0, e1;

@@ -277,7 +277,7 @@ static int finalize_mobilenet(ssd_handle *h)
     return SSD_OK;
 }
 
-// ShuffleNet layer order (execution order used by the plan):
+// ShuffleNet layer order (execution order used by the plan, which finds each stage through h->sn_stage):
 //   per stage: unit_1 {before, dw, after, second dw, second after}, units 2..n {before, dw, after}
 //   then Conv5.
 static int finalize_shufflenet(ssd_handle *h)
@@ -295,6 +295,7 @@ static int finalize_shufflenet(ssd_handle *h)
     int cin = 24, out = D0, split = 0;          // split: channels per half of this stage's input rows (0: standard rows)
     for (int st = 0; st < 3; ++st) {
         const int D = out / 2;
+        h->sn_stage[st] = ssd_handle::SnStage{(int)h->pw.size(), (int)h->dw.size(), units[st]};
         char base[64];
         snprintf(base, sizeof base, "ShuffleNetV2/Stage%d", st + 2);
         std::string u1 = std::string(base) + "/unit_1";
