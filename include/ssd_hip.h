@@ -494,6 +494,58 @@ typedef struct ssd_augment_params {          /* 64 bytes, no padding */
 int ssd_augment(const uint8_t *images_dev, const ssd_augment_params *params_host, const ssd_augment_params *params_dev, int32_t B,
                 int32_t out_h, int32_t out_w, int32_t channels_first, float *out_dev, void *stream);
 
+/* ---- the TRAIN update: train_op after the gradients (model.py:106-128) ----
+ *
+ * Cosine-decayed Adam on every trainable variable, the weight-decay term's gradient folded into it, and the exponential moving
+ * average (EMA) of every trainable variable, for a whole model in ONE launch.  TensorFlow's sources are not available to this
+ * project: the formulas restate TF 1.12's ApplyAdam kernel, tf.train.cosine_decay and ExponentialMovingAverage.apply from memory.
+ * What is pinned is the arithmetic below for given inputs, single-sourced here, NOT parity with TensorFlow.
+ *
+ * Let t = 1, 2, ... be the number of this update (global_step is t - 1 before it and t after it).  The host forms, in float64,
+ * each rounded once to float32:
+ *   lr    = initial_learning_rate * 0.5 * (1 + cos(pi * min(t - 1, num_steps) / num_steps))          (model.py:108-113)
+ *   alpha = lr * sqrt(1 - 0.999^t) / (1 - 0.9^t),  lr the float32 value above                         (Adam's step size)
+ *   d     = min(0.993, (1 + t) / (10 + t));  the kernel receives float(1 - d)                        (model.py:126-127:
+ *           num_updates = global_step read AFTER the increment -- one reading of the control dependency)
+ * Per element, float32, contraction off, each operation rounded once, in this order:
+ *   1. g' = g + weight_decay * w  if the tensor decays (add_weight_decay, model.py:132-145: its name contains "weights" or
+ *      "kernel" and does not contain "depthwise_weights"), else g' = g
+ *   2. m += (g' - m) * one_minus_beta1            one_minus_beta1 = float(0.1)
+ *   3. v += (g' * g' - v) * one_minus_beta2       one_minus_beta2 = float(0.001)
+ *   4. w -= (m * alpha) / (sqrt(v) + epsilon)     epsilon = 1e-8f OUTSIDE the bias correction (TF's "epsilon hat"); sqrt and the
+ *      division correctly rounded, denormals kept
+ *   5. ema -= (ema - w) * one_minus_decay         with the new w
+ * A tensor whose grad pointer is NULL (torch: p.grad is None; TF: a None gradient) keeps w, m and v; its ema still takes step 5.
+ * m and v start at 0, ema as a copy of w (the caller's initialisation).  A numpy float32 restatement is bit-exact.
+ *
+ * The table: T rows, one per tensor.  tensors_host is read by this call to refuse bad rows; tensors_dev holds the same rows in
+ * device memory (8-byte aligned), which the kernel reads -- the caller's upload, ordered before this call on `stream`.  A tensor
+ * is cut into blocks of SSD_UPDATE_BLOCK_ELEMS elements counted from the 16-byte boundary at or below w:
+ *   blocks(row) = ceil((count + ((uintptr_t)w / 4) % 4) / SSD_UPDATE_BLOCK_ELEMS),   first_block = sum of blocks(rows before it)
+ * (the caller fills first_block; this call checks it).  w, m, v, ema and grad need 4-byte alignment only: where the five
+ * addresses are congruent modulo 16 the tensor moves as 16-byte loads and stores with a scalar head and tail, otherwise element
+ * by element; the result bits are the same.  The tensors must not overlap.  No LDS, no atomics, no allocation, no host
+ * synchronisation: the call only enqueues one kernel on `stream` and is legal during stream capture.
+ * NULL tables, T < 1 or > SSD_UPDATE_MAX_TENSORS, tensors_dev not 8-byte aligned, a negative count or one above 2^40, a NULL or
+ * misaligned w / m / v / ema, a misaligned grad, a decay flag other than 0 / 1, a wrong first_block, more than 2^31 - 1 blocks,
+ * or a non-finite scalar: SSD_ERR_INVALID before any HIP call.  Needs no handle. */
+#define SSD_UPDATE_BLOCK_ELEMS 4096
+#define SSD_UPDATE_MAX_TENSORS 65536
+typedef struct ssd_update_tensor {           /* 56 bytes, no padding */
+    float *w;                                /* the variable                                                   */
+    const float *grad;                       /* its gradient, or NULL: only ema moves                          */
+    float *m, *v;                            /* Adam's first and second moment                                 */
+    float *ema;                              /* the variable's moving average                                  */
+    int64_t count;                           /* elements                                                       */
+    int32_t decay;                           /* 1: step 1 adds weight_decay * w                                */
+    int32_t first_block;                     /* blocks of the rows before this one (see above)                 */
+} ssd_update_tensor;
+typedef struct ssd_update_scalars {          /* 24 bytes: this step's scalars, all finite                      */
+    float alpha, one_minus_beta1, one_minus_beta2, epsilon, weight_decay, one_minus_decay;
+} ssd_update_scalars;
+int ssd_train_update(const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T,
+                     const ssd_update_scalars *scalars, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ for device memory, streams and torch.distributed.  There is NO CPU fallback: eve
 raises if the HIP library is missing or no GPU is present.
 """
 from .config import load_config, INFERENCE_KEYS, load_loss_config, LOSS_KEYS, load_train_config, TRAIN_KEYS   # noqa: F401
+from .config import load_optimizer_config, OPTIMIZER_KEYS             # noqa: F401
 from .variables import (variable_shapes, synthetic_weights, save_weights,   # noqa: F401
                         load_weights)
 from .pb_import import read_frozen_graph, load_pb_weights             # noqa: F401
@@ -23,3 +24,4 @@ from .distributed import shard_range, all_gather_detections, detect_sharded, bin
 from .distributed import (ChunkAssignment, detect_many_sharded, node_device_and_backend, init_node_process_group,  # noqa: F401
                           launch_local)
 from .augment import augment_batch, sample_augmentation, TrainPipeline   # noqa: F401
+from .train_step import TrainStep                                     # noqa: F401

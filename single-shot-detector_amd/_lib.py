@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
-            "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip"]
+            "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip"]
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
 _lib = None
@@ -126,6 +126,18 @@ class SsdLossConfig(ctypes.Structure):
                 ("anchors_per_level", ctypes.c_int64 * 8)]
 
 
+class SsdUpdateTensor(ctypes.Structure):
+    """ssd_update_tensor of include/ssd_hip.h (56 bytes)."""
+    _fields_ = [("w", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("ema", ctypes.c_void_p), ("count", ctypes.c_int64), ("decay", ctypes.c_int32), ("first_block", ctypes.c_int32)]
+
+
+class SsdUpdateScalars(ctypes.Structure):
+    """ssd_update_scalars of include/ssd_hip.h."""
+    _fields_ = [("alpha", ctypes.c_float), ("one_minus_beta1", ctypes.c_float), ("one_minus_beta2", ctypes.c_float),
+                ("epsilon", ctypes.c_float), ("weight_decay", ctypes.c_float), ("one_minus_decay", ctypes.c_float)]
+
+
 # every symbol include/ssd_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ssd_create": (ctypes.c_int, [ctypes.POINTER(SsdConfig), ctypes.POINTER(_vp)]),
@@ -184,6 +196,7 @@ SIGNATURES = {
     "ssd_loss_backward": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(SsdLossConfig),
                                          _vp, _vp, _vp, _vp]),
     "ssd_augment": (ctypes.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ssd_train_update": (ctypes.c_int, [_vp, _vp, _i, ctypes.POINTER(SsdUpdateScalars), _vp]),
 }
 
 

@@ -5,6 +5,7 @@ create_pb.py:24); training keys are accepted and ignored so the reference's file
 unmodified.
 """
 import json
+import math
 
 INFERENCE_KEYS = ("backbone", "depth_multiplier", "num_classes", "score_threshold",
                   "iou_threshold", "max_boxes_per_class", "min_dimension")
@@ -75,4 +76,27 @@ def load_train_config(path_or_dict):
         raise ValueError("batch_size must be >= 1")
     if min(out["image_height"], out["image_width"]) < 128 or out["image_height"] % 128 or out["image_width"] % 128:
         raise ValueError("image_height and image_width must be positive multiples of 128 (pipeline.py:32-33)")
+    return out
+
+
+OPTIMIZER_KEYS = ("initial_learning_rate", "num_steps", "weight_decay")
+
+
+def load_optimizer_config(path_or_dict):
+    """The keys of the reference's JSON config that the TRAIN update reads (model.py:80-81,108-113): a dict with exactly
+    OPTIMIZER_KEYS, initial_learning_rate and weight_decay as floats, num_steps (the cosine decay's decay_steps) as a positive int."""
+    if isinstance(path_or_dict, dict):
+        raw = dict(path_or_dict)
+    else:
+        with open(path_or_dict) as f:
+            raw = json.load(f)
+    missing = [k for k in OPTIMIZER_KEYS if k not in raw]
+    if missing:
+        raise KeyError("config is missing the key %r" % missing[0])
+    out = {"initial_learning_rate": float(raw["initial_learning_rate"]), "num_steps": int(raw["num_steps"]),
+           "weight_decay": float(raw["weight_decay"])}
+    if out["num_steps"] < 1:
+        raise ValueError("num_steps must be >= 1")
+    if not (math.isfinite(out["initial_learning_rate"]) and math.isfinite(out["weight_decay"])):
+        raise ValueError("initial_learning_rate and weight_decay must be finite")
     return out
