@@ -389,7 +389,8 @@ int ssd_postprocess(const float *logits_dev, const float *codes_dev, const float
  * Arguments common to both entry points, all device memory of the caller:
  *   anchors_dev [N,4]     the UNCLIPPED anchors (AnchorGenerator, anchor_generator.py:116-117)
  *   gt_boxes_dev [B,G,4]  ymin,xmin,ymax,xmax in the frame of the anchors (box_scaler applied, pipeline.py:103-109)
- *   gt_labels_dev [B,G]   int32 in [0, C); gt_num_dev [B] int32: rows of image b used (clamped to [0, G])
+ *   gt_labels_dev [B,G]   int32 in [0, C); gt_num_dev [B] int32: rows of image b used (clamped to [0, G]); with G == 0
+ *                         gt_boxes_dev and gt_labels_dev are not read and may be NULL (every anchor -1)
  *   anchors_dev, gt_boxes_dev, codes_dev and reg_targets_dev 16-byte aligned (SSD_ERR_INVALID otherwise); G <= 4096.
  * Stream ordering the caller owes: both calls only ENQUEUE work on `stream`.  Tensors copied out of a handle
  * (ssd_get_tensor_dev) are ordered by that copy's stream.  A caller that points logits_dev / codes_dev straight at a
@@ -434,7 +435,8 @@ int ssd_loss(const float *logits_dev, const float *codes_dev, const float *ancho
  *     cls_targets - 1 (0 everywhere on background anchors), s = sigmoid(x), q = 1 - p_t = (z ? 1 - s : s),
  *     alpha_z = (z ? alpha : 1 - alpha) as ssd_loss forms them, nlp = max(x,0) - x*z + log1p(exp(-|x|)):
  *       alpha_z * (gamma * q^(gamma-1) * dq/dx * nlp + q^gamma * (s - z)) * g[1] / norm,  dq/dx = (z ? -1 : 1) * s(1-s);
- *     where q == 0 the first term is 0 (its limit for gamma > 1).
+ *     the first term is evaluated as gamma * q^gamma * (z ? -s : 1 - s) * nlp (dq/dx = +-q(1-q) folded in), which is 0
+ *     where q == 0 -- its limit for every gamma > 0 -- and finite where q is denormal, gamma < 1 included.
  *   d_codes_dev [b,a,k] = 0 when matches[b,a] < 0, otherwise, with diff = codes - reg_targets (one fp32 op as in
  *     ssd_loss): (|diff| < 1 ? diff : sign(diff)) * g[0] / norm -- sign(diff) at |diff| == 1 (tf.where / tf.less).
  * Precision: each element is evaluated in double from its fp32 inputs (s and 1 - s both formed from exp(-|x|) without

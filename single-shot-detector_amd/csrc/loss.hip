@@ -381,8 +381,10 @@ __device__ __forceinline__ float focal_grad(float x, bool z, const GradArgs &p, 
         t1 = 2.0 * q * dq * nlp;
         qg = q * q;
     } else {
-        t1 = q == 0.0 ? 0.0 : p.gamma * pow(q, p.gamma - 1.0) * dq * nlp;
+        // gamma * q^(gamma-1) * dq/dx with dq/dx = +-q(1-q) folded in: gamma * q^gamma * (+-(1-q)).  No q^(gamma-1): for
+        // gamma < 1 it overflows on a denormal q (gamma == 0: 0 * inf) and has no value at q == 0; this form is 0 there
         qg = pow(q, p.gamma);
+        t1 = p.gamma * qg * (z ? -s : sc) * nlp;
     }
     return (float)((z ? p.alpha : p.one_m_alpha) * (t1 + qg * smz) * gc);
 }
@@ -447,7 +449,7 @@ int prepare(LossArgs &p, const char *who, const float *anchors, int32_t N, const
             const int32_t *gt_num, int32_t B, int32_t G, const ssd_loss_config *cfg, void *ws, size_t ws_bytes)
 {
     const std::string w(who);
-    if (!anchors || !gt_boxes || !gt_labels || !gt_num || !cfg || !ws || B < 1 || N < 1 || G < 0)
+    if (!anchors || (G > 0 && (!gt_boxes || !gt_labels)) || !gt_num || !cfg || !ws || B < 1 || N < 1 || G < 0)
         return ssd_fail(SSD_ERR_INVALID, w + ": bad arguments");
     if (G > SSD_LOSS_MAX_GT) return ssd_fail(SSD_ERR_INVALID, w + ": more than SSD_LOSS_MAX_GT (4096) groundtruth boxes per image");
     if ((int64_t)B * N * 4 >= ((int64_t)1 << 40)) return ssd_fail(SSD_ERR_INVALID, w + ": tensors too large");

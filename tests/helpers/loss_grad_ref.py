@@ -26,9 +26,8 @@ def focal_grad(x, z, gamma=2.0, alpha=0.25):
         t1 = 2.0 * q * dq * nlp
         qg = q * q
     else:
-        with np.errstate(divide="ignore", invalid="ignore"):
-            t1 = np.where(q == 0.0, 0.0, g * np.power(q, g - 1.0) * dq * nlp)
         qg = np.power(q, g)
+        t1 = g * qg * np.where(z, -s, sc) * nlp            # dq/dx = +-q(1-q) folded into q^(gamma-1): 0 at q == 0
     aw = np.where(z, float(f32(alpha)), float(f32(1.0 - alpha)))
     return aw * (t1 + qg * smz)
 
