@@ -548,6 +548,91 @@ typedef struct ssd_update_scalars {          /* 24 bytes: this step's scalars, a
 int ssd_train_update(const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T,
                      const ssd_update_scalars *scalars, void *stream);
 
+/* ---- the TRAIN head: forward and backward of RetinaNetBoxPredictor in TRAIN mode (box_predictor.py:34-155) ----
+ *
+ * The predictor is ten dense 3x3 stride-1 'same' convolutions (two towers of four 256 -> 256 layers shared by the pyramid
+ * levels, then `logits` and `encoded_boxes` with a bias), each tower layer followed by a per-level training-mode batch norm and
+ * a ReLU (layer_utils.py:5-12).  These calls are those two operations and their gradients.  Conventions as for the loss,
+ * augment and update blocks: device pointers of the caller, logical NHWC fp32 tensors and HWIO kernels, DEVICE weights (they
+ * change every step), scratch from a caller-supplied workspace, every call only enqueues on `stream` (no allocation, no host
+ * round trip, no synchronisation), arguments are refused with SSD_ERR_INVALID before any HIP call, no handle.  No atomics
+ * anywhere: two calls give the same bits.  Not here: strides other than 1, 1x1 and depthwise backward, F16X3, double backward.
+ *
+ * A convolution call takes 1 .. SSD_TRAIN_MAX_LEVELS levels that share B, Cin, Cout and ONE kernel; the weight gradient is the
+ * sum over all of them.  Cin must be a multiple of 8, Cin and Cout at most 4096, every level's tensors (channels padded to 32)
+ * below 2 GiB.  x, dy, out, w_dev, dw_dev and the workspace need 16-byte alignment, bias_dev / dbias_dev 4-byte.
+ * The implicit-GEMM launches follow the PROCESS-wide kernel selectors of ssd_set_option(NULL, ...) ("igemm_96", "igemm_tile",
+ * "igemm_deep64"), like the handle-less stage entry points; none changes a result bit, but "igemm_96" changes the padded width
+ * and with it the workspace size: size the workspace under the options the call will run with (a call re-plans and refuses a
+ * workspace that has become too small).
+ *
+ * ssd_conv3x3_train_forward   out_l = conv3x3_same(x_l, w) (+ bias), raw.  The kernel is packed on the device into ssd_conv2d's
+ *   layout and the launch is ssd_conv2d's exact-fp32 implicit GEMM: per output ONE fmaf chain over taps row-major, ci ascending
+ *   within a tap, then + bias -- bit-identical to ssd_conv2d on the same values.
+ * ssd_conv3x3_train_backward  from x_l, dy_l, w:
+ *   dx_l (levels[l].out; given for every level or for none)  = conv3x3_same(dy_l, w'), w'[kh,kw,co,ci] = w[2-kh,2-kw,ci,co], on the
+ *     same launch: ONE fmaf chain over taps row-major, co ascending within a tap -- bit-identical to the CPU oracle's
+ *     conv2d(dy, w').  Widths that are not multiples of 32 on the reduction side are zero padded.
+ *   dw_dev [3,3,Cin,Cout] = sum over levels, images and positions of x (shifted by the tap, zero outside) * dy, on
+ *     v_mfma_f32_32x32x2_f32.  Order (this implementation's, deterministic, NOT pinned to an oracle chain): the positions of a
+ *     level are cut into slices of rows_per_slice consecutive rows r = (b * H + y) * W + x (rows_per_slice = the total row count
+ *     over max(1, 1536 / tiles) slices, tiles = 9 * ceil(Cin / 128) * ceil(Cout / (Cout <= 32 ? 32 : 128)), at least 256,
+ *     rounded up to 16); within a slice one fp32 chain in ascending r; the slices' partial tiles, kept in the workspace, are
+ *     then added one fp32 addition at a time in ascending slice order, levels in list order.
+ *   dbias_dev [Cout] (nullable) = sum of dy over everything, in double in the two-stage order of the batch norm below over the
+ *     concatenated levels, rounded once.
+ *
+ * The batch norm takes 1 .. SSD_TRAIN_MAX_LEVELS levels x [rows, C] (rows = B*H*W) with their OWN parameters and statistics
+ * (per-level batch norms, box_predictor.py:41-45); C <= 1024; every pointer 16-byte aligned.  Fixed two-stage order of every
+ * column sum: with G = ceil(min(C, 1024) / 4), rpp = 256 / G and slab_rows = max(8 * rpp, ceil(total rows of the call / 1024)) rounded up to
+ * a multiple of rpp, a level's rows are cut into slabs of slab_rows; inside a slab row lane j = (r - slab start) mod rpp adds its
+ * rows in ascending order, the lanes are added in ascending j, the slabs in ascending order; all in double, rounded ONCE.
+ * ssd_bn_relu_train_forward, training != 0:
+ *     mean = fp32(sum x / rows);  var = fp32(sum (x - mean)^2 / rows), difference and square in double (biased)
+ *     invstd = 1 / sqrt(var + epsilon), two correctly rounded fp32 operations
+ *     out = max(((x - mean) * (gamma * invstd)) + beta, 0), one fp32 operation at a time, no contraction
+ *     mean / invstd (required) and var (nullable) receive the batch statistics; where the moving statistics are given
+ *       moving_mean -= (moving_mean - mean) * one_minus_momentum
+ *       moving_variance -= (moving_variance - var * fp32(rows / (rows - 1))) * one_minus_momentum     (rows == 1: var itself)
+ *     (TF's fused batch norm restated from memory: unpinned against TensorFlow, like the update block's formulas.)
+ *   training == 0: out = max(((x - moving_mean) * (gamma * (1 / sqrt(moving_variance + epsilon)))) + beta, 0), the inference form
+ *     ssd_finalize folds into ssd_conv2d's epilogue; nothing else is written and the workspace is not used.
+ * ssd_bn_relu_train_backward, with t = x - mean, xhat = t * invstd, sf = gamma * invstd, y = t * sf + beta RECOMPUTED from x and the
+ *   saved statistics (the forward's output is not read), g = y > 0 ? dy : 0:
+ *     dbeta = fp32(sum g), dgamma = fp32(sum g * xhat) (products and sums in double)
+ *     out = sf * ((g - dbeta / rows) - xhat * (dgamma / rows)), one fp32 operation at a time, rows as fp32 */
+#define SSD_TRAIN_MAX_LEVELS 8
+typedef struct ssd_conv_level {              /* 32 bytes */
+    int32_t H, W;                            /* the level's spatial size (input == output)                      */
+    const float *x;                          /* [B,H,W,Cin]: the layer's input                                   */
+    const float *dy;                         /* backward: [B,H,W,Cout] upstream gradient; forward: not read      */
+    float *out;                              /* forward: [B,H,W,Cout]; backward: dx [B,H,W,Cin] or NULL          */
+} ssd_conv_level;
+typedef struct ssd_bn_level {                /* 104 bytes */
+    int64_t rows;                            /* B*H*W                                                            */
+    const float *x;                          /* [rows, C]: the batch norm's input                                */
+    const float *dy;                         /* backward: [rows, C]                                              */
+    float *out;                              /* forward: y; backward: dx                                         */
+    const float *gamma, *beta;               /* [C]                                                              */
+    float *moving_mean, *moving_variance;    /* [C], nullable as a pair in training (then not updated)           */
+    float *mean, *var, *invstd;              /* [C]: written by the training forward, mean / invstd read by the backward */
+    float *dgamma, *dbeta;                   /* [C]: backward                                                    */
+} ssd_bn_level;
+/* Bytes of workspace either convolution call needs for these sizes (0: the sizes would be refused); pointers are not read. */
+size_t ssd_conv3x3_train_workspace_bytes(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout);
+int ssd_conv3x3_train_forward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
+                              const float *w_dev /* [3,3,Cin,Cout] */, const float *bias_dev /* [Cout] or NULL */,
+                              void *workspace_dev, size_t workspace_bytes, void *stream);
+int ssd_conv3x3_train_backward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
+                               const float *w_dev, float *dw_dev /* [3,3,Cin,Cout] */, float *dbias_dev /* [Cout] or NULL */,
+                               void *workspace_dev, size_t workspace_bytes, void *stream);
+/* Bytes of workspace either batch-norm call needs (0: refused sizes); only `rows` of the levels is read. */
+size_t ssd_bn_relu_train_workspace_bytes(const ssd_bn_level *levels, int32_t n_levels, int32_t C);
+int ssd_bn_relu_train_forward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, int32_t training, float epsilon,
+                              float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream);
+int ssd_bn_relu_train_backward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, void *workspace_dev,
+                               size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

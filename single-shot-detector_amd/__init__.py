@@ -25,3 +25,4 @@ from .distributed import (ChunkAssignment, detect_many_sharded, node_device_and_
                           launch_local)
 from .augment import augment_batch, sample_augmentation, TrainPipeline   # noqa: F401
 from .train_step import TrainStep                                     # noqa: F401
+from .head_train import conv3x3_same, batch_norm_relu, TrainableBoxPredictor, head_variable_shapes   # noqa: F401

@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
-            "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip"]
+            "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip", "train_head.hip", "wgrad.hip"]
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
 _lib = None
@@ -34,6 +34,7 @@ def build(force=False, verbose=False, diag=False):
     include/ssd_hip_diag.h) for scripts/ -- never loaded by the product."""
     srcs = [os.path.join(_CSRC, s) for s in _SOURCES]
     deps = srcs + [os.path.join(_CSRC, "ssd_internal.h"), os.path.join(_CSRC, "host.h"), os.path.join(_CSRC, "igemm_mfma16.h"),
+                   os.path.join(_CSRC, "train_head.h"),
                    os.path.join(_HERE, "..", "include", "ssd_hip.h"),
                    os.path.join(_HERE, "..", "include", "ssd_hip_diag.h"), os.path.join(_CSRC, "exports.map")]
     target = _DIAG_PATH if diag else _LIB_PATH
@@ -138,6 +139,17 @@ class SsdUpdateScalars(ctypes.Structure):
                 ("epsilon", ctypes.c_float), ("weight_decay", ctypes.c_float), ("one_minus_decay", ctypes.c_float)]
 
 
+class SsdConvLevel(ctypes.Structure):
+    """ssd_conv_level of include/ssd_hip.h (32 bytes)."""
+    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("x", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("out", ctypes.c_void_p)]
+
+
+class SsdBnLevel(ctypes.Structure):
+    """ssd_bn_level of include/ssd_hip.h (104 bytes)."""
+    _fields_ = [("rows", ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
+        "x", "dy", "out", "gamma", "beta", "moving_mean", "moving_variance", "mean", "var", "invstd", "dgamma", "dbeta")]
+
+
 # every symbol include/ssd_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ssd_create": (ctypes.c_int, [ctypes.POINTER(SsdConfig), ctypes.POINTER(_vp)]),
@@ -197,6 +209,13 @@ SIGNATURES = {
                                          _vp, _vp, _vp, _vp]),
     "ssd_augment": (ctypes.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ssd_train_update": (ctypes.c_int, [_vp, _vp, _i, ctypes.POINTER(SsdUpdateScalars), _vp]),
+    "ssd_conv3x3_train_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i]),
+    "ssd_conv3x3_train_forward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_conv3x3_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_bn_relu_train_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SsdBnLevel), _i, _i]),
+    "ssd_bn_relu_train_forward": (ctypes.c_int, [ctypes.POINTER(SsdBnLevel), _i, _i, _i, ctypes.c_float, ctypes.c_float, _vp,
+                                                 ctypes.c_size_t, _vp]),
+    "ssd_bn_relu_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdBnLevel), _i, _i, _vp, ctypes.c_size_t, _vp]),
 }
 
 

@@ -144,6 +144,7 @@ static constexpr long long *g_dbg_ts = nullptr;
 // weights.hip: w HWIO [k,k,Cin_l,Cout_l] -> wt [taps][CoutPad][CinP]
 int pack_conv(const struct ssd_handle *h, DevPool &pool, const float *w, int k, int Cin_l, int Cout_l, const std::vector<int> &inmap,
               const std::vector<int> &outmap, ConvW &cw);
+int conv_pick_tile(const struct ssd_handle *h, int CoutP);     // the tile pack_conv gives a kernel of this padded width (train_head.hip packs on the device)
 int upload_bn(DevPool &pool, const BnHost &b, ConvW &cw);
 int pack_dw(DevPool &pool, const std::vector<float> &w9, const std::vector<float> &mean, const std::vector<float> &sf,
             const std::vector<float> &beta, DwW &d);

@@ -59,6 +59,8 @@ static int pick_tile(const ssd_handle *h, int CoutP)
     return IGEMM_128x128;
 }
 
+int conv_pick_tile(const ssd_handle *h, int CoutP) { return pick_tile(h, CoutP); }
+
 // w: HWIO [k,k,Cin_l,Cout_l] -> wt [taps][CoutPad][CinP]
 int pack_conv(const ssd_handle *h, DevPool &pool, const float *w, int k, int Cin_l, int Cout_l, const std::vector<int> &inmap,
                      const std::vector<int> &outmap, ConvW &cw)
