@@ -188,3 +188,177 @@ def torch_loss(class_predictions, encoded_boxes, anchors, boxes, labels, num, ga
     loc_loss = (sl.sum(2) * (m >= 0).to(x.dtype)).sum()
     norm = float(max(f32(int((m >= 0).sum())), f32(1)))
     return loc_loss / norm + cls_loss / norm, int((m >= 0).sum(1).min())
+
+
+# ----------------------------------------------------------------------------- the header's arithmetic, for the edge tests
+def al256(v):
+    return (v + 255) // 256 * 256
+
+
+def slab_plan(rows, C):
+    """include/ssd_hip.h's slab formula for a batch-norm call with these per-level rows -> (rpp, slab_rows, total slabs)."""
+    G = (min(C, 1024) + 3) // 4
+    rpp = 256 // G
+    sr = max(8 * rpp, -(-sum(rows) // 1024))
+    sr = -(-sr // rpp) * rpp
+    return rpp, sr, sum(-(-r // sr) for r in rows)
+
+
+def rows_per_slice(rows, Cin, Cout):
+    """include/ssd_hip.h's K-slice of the weight gradient for these per-level rows."""
+    tiles = 9 * (-(-Cin // 128)) * (-(-Cout // (32 if Cout <= 32 else 128)))
+    want = max(1, 1536 // tiles)
+    return -(-max(256, -(-sum(rows) // want)) // 16) * 16
+
+
+def bn_gate_f32(x, gamma, beta, mean, var, dy, eps=EPS):
+    """The backward's float32 operands as the header forms them: g = (t * sf + beta > 0 ? dy : 0) and xhat = t * invstd, with
+    t = x - mean, sf = gamma * invstd, one float32 operation at a time."""
+    x, gamma, beta, mean = (v.astype(f32) for v in (x, gamma, beta, mean))
+    invstd = invstd_f32(var, eps)
+    t = x - mean
+    ypre = t * (gamma * invstd) + beta
+    return np.where(ypre > 0, dy.astype(f32), f32(0)), t * invstd
+
+
+def double_sum_bound(terms):
+    """terms float64 [rows, C] -> (want, tol): `want` is the EXACT column sum (math.fsum) rounded once to float32, and
+    |got - want| <= tol holds for the float32 rounding `got` of ANY order of double-precision summation of the same terms.
+    Derivation: n terms added in double in any order give S' with |S' - S| <= gamma_(n-1) * sum|t|, gamma_k = k u / (1 - k u),
+    u = 2^-53 (Higham, Accuracy and Stability, eq. 4.4), and gamma_(n-1) <= n u while n < 2^26: E = n * 2^-53 * sum|t|.  Rounding
+    to float32 is monotonic, so got = fl(S') lies between fl(S - E) and fl(S + E): at most E plus half a float32 ulp on either
+    side away from fl(S), the ulps taken at |S| + E (the spacing of the larger neighbour): tol = E + ulp32(|S| + E).  A column
+    that contains a non-finite term gives want = nan, tol = nan: compare it separately."""
+    import math
+    terms = np.asarray(terms, np.float64)
+    n = terms.shape[0]
+    assert n < 2 ** 26
+    finite = np.isfinite(terms).all(0)
+    exact = np.array([math.fsum(terms[:, c].tolist()) if finite[c] else np.nan for c in range(terms.shape[1])])
+    E = n * 2.0 ** -53 * np.abs(terms).sum(0)
+    with np.errstate(invalid="ignore"):
+        tol = E + np.spacing((np.abs(exact) + E).astype(f32)).astype(np.float64)
+    return exact.astype(f32), tol
+
+
+def offset_variance_bound(offset, var):
+    """Relative distance allowed between the header's variance (float64 around the float32 mean m32, rounded once) and the true
+    float64 variance: the sum around m32 is var + (m32 - m)^2 with |m32 - m| <= ulp32(offset) / 2, i.e. (ulp / 2)^2 / var relative,
+    plus 2^-24 for the final rounding; 2 ulp^2 / var covers both wherever ulp^2 / var >= 2^-24 (asserted)."""
+    ulp = float(np.spacing(f32(offset)))
+    assert ulp * ulp / var >= 2.0 ** -24
+    return 2.0 * ulp * ulp / var
+
+
+# ----------------------------------------------------------------------------- the cases of tests/test_gpu_head_train_edges.py
+PYRAMID = [(13, 17), (7, 9), (4, 5), (2, 3), (1, 1)]
+EIGHT = [(9, 11), (8, 7), (6, 5), (5, 5), (4, 3), (3, 2), (2, 1), (1, 1)]
+# name: (B, level sizes, Cin, Cout).  Widths: Cout = 6 * classes for 1, 3 and 20 classes (6 and 18 are no multiples of 4: the
+# 32-wide tile with element-wise dy loads); Cin that is no multiple of 32 / 128, Cin above 256 (three ci tiles, the last with 8
+# channels), Cout just past a tile edge.  Geometry: B = 1 and 3, thin levels, fewer rows than one K-step, eight levels, a level
+# that is a whole number of slices beside one that is one row more (B = 1: 16 * 32 = 512 and 27 * 19 = 513 rows, slices of 256).
+CONV_CASES = {
+    "256-6": (2, PYRAMID, 256, 6), "256-18": (2, PYRAMID, 256, 18), "256-120": (2, PYRAMID, 256, 120),
+    "24-24": (2, PYRAMID, 24, 24), "72-33": (2, PYRAMID, 72, 33), "136-129": (2, PYRAMID, 136, 129),
+    "264-132": (2, PYRAMID, 264, 132), "8-1": (2, PYRAMID, 8, 1),
+    "B1": (1, PYRAMID, 64, 40), "B3": (3, PYRAMID, 256, 18),
+    "thin": (2, [(7, 9), (1, 37), (29, 1), (1, 1)], 64, 40),
+    "six-rows": (1, [(3, 2)], 24, 18),
+    "eight-levels": (2, EIGHT, 64, 40),
+    "slice-edge": (1, [(16, 32), (27, 19)], 64, 40),
+}
+
+
+def conv_case_data(name, integers):
+    """-> (B, sizes, xs, w, bias, dys) of a CONV_CASES entry: small integers (|x|, |dy| <= 3, |w| <= 2) or random normal data."""
+    import zlib
+    B, sizes, Cin, Cout = CONV_CASES[name]
+    rng = np.random.default_rng(zlib.crc32(name.encode()) + (1 if integers else 0))
+    if integers:
+        xs = [rng.integers(-3, 4, (B, h, w, Cin)).astype(f32) for h, w in sizes]
+        dys = [rng.integers(-3, 4, (B, h, w, Cout)).astype(f32) for h, w in sizes]
+        w = rng.integers(-2, 3, (3, 3, Cin, Cout)).astype(f32)
+        bias = rng.integers(-4, 5, Cout).astype(f32)
+    else:
+        xs = [rng.normal(0, 1, (B, h, w, Cin)).astype(f32) for h, w in sizes]
+        dys = [rng.normal(0, 1, (B, h, w, Cout)).astype(f32) for h, w in sizes]
+        w = rng.normal(0, 0.05, (3, 3, Cin, Cout)).astype(f32)
+        bias = rng.normal(0, 0.1, Cout).astype(f32)
+    return B, sizes, xs, w, bias, dys
+
+
+def integer_premise(xs, w, dys):
+    """-> (dw64, dbias64, largest absolute partial sum of dw, of dbias): below 2^24 every partial sum of integers is exact in
+    float32 in ANY order."""
+    _, dw64, db64 = conv3x3_grads(xs, w, dys)
+    _, absum, _ = conv3x3_grads(xs, w, dys, absolute=True)
+    return dw64, db64, float(absum.max()), float(sum(np.abs(d).sum((0, 1, 2)).max() for d in dys))
+
+
+def wgrad_bound(xs, w, dys):
+    """-> (dw64, bound, absum): |dw - dw64| <= gamma_n * sum|x * dy| per element, n its number of products, gamma_n = n u / (1 - n u),
+    u = 2^-24: the bound of ANY order of float32 accumulation of exact products (the matrix instruction's products are exact in
+    its accumulator's sum)."""
+    _, dw64, _ = conv3x3_grads(xs, w, dys)
+    _, absum, _ = conv3x3_grads(xs, w, dys, absolute=True)
+    _, n, _ = conv3x3_grads([np.ones(x.shape) for x in xs], w, [np.ones(d.shape) for d in dys])
+    u = 2.0 ** -24
+    return dw64, n * u / (1 - n * u) * absum, absum
+
+
+# ----------------------------------------------------------------------------- the predictor's whole-graph inputs
+def groundtruth(ssd, batch, seed, height=128, width=128):
+    """Anchors of a height x width image and, per image, one box on a jittered anchor of EVERY pyramid level (unclipped: the
+    anchors of p6 and p7 can be larger than the image), so that both nets receive a gradient at every level."""
+    g = ssd.AnchorGenerator()
+    anchors = g(height, width)
+    per_level = list(g.num_anchors_per_feature_map)
+    rng = np.random.default_rng(seed)
+    boxes = np.zeros((batch, len(per_level), 4), f32)
+    for b in range(batch):
+        at = 0
+        for l, n in enumerate(per_level):
+            a = anchors[at + rng.integers(0, n)]
+            boxes[b, l] = a + rng.normal(0, 0.02, 4) * (a[2] - a[0])
+            at += n
+    return anchors, boxes, rng.integers(0, 80, boxes.shape[:2]).astype(np.int32), np.full(batch, len(per_level), np.int32)
+
+
+LARGE_SIZES = [(40, 56), (20, 28), (10, 14), (5, 7), (3, 4)]          # the pyramid of a 320 x 448 image
+
+
+def large_predictor_input(ssd, params):
+    """The second whole-graph input: B = 3, random normal p3 .. p7 of a 320 x 448 image (256 channels; not from an engine), its
+    anchors, one jittered ground-truth box per level.  -> (W, feats, anchors, boxes, labels, num)."""
+    W = ssd.synthetic_weights(params, seed=21, logits_bias=-4.0)
+    rng = np.random.default_rng(22)
+    feats = [rng.normal(0, 1, (3, h, w, 256)).astype(f32) for h, w in LARGE_SIZES]
+    return (W, feats) + groundtruth(ssd, 3, 23, 320, 448)
+
+
+def predictor_references(W, feats, anchors, boxes, labels, num, num_classes=80):
+    """The reference and the yardstick of the predictor's training-mode test, on the CPU.  Reference: the float64 restatement
+    with the loss's gradient by float64 torch autograd at its float64 outputs.  Yardstick: the same graph, loss included, in
+    float32 CPU torch ops, one backward.  -> (least matches per image, [(name, float32 value, float64 value)]) over the two
+    outputs, the gradient of every variable and of every feature map."""
+    from test_head_train_host import _torch_predictor
+    import torch
+    head = {k: v for k, v in W.items() if k.startswith(("box_net/", "class_net/"))}
+    eb64, cp64 = predictor(head, feats, num_classes)
+    tcp, teb = torch.tensor(cp64, requires_grad=True), torch.tensor(eb64, requires_grad=True)
+    total64, least = torch_loss(tcp, teb, anchors, boxes, labels, num)
+    total64.backward()
+    g64, df64 = predictor(head, feats, num_classes, d_boxes=teb.grad.numpy(), d_classes=tcp.grad.numpy())
+    (tb, tc), T, P = _torch_predictor(head, feats, num_classes, dtype=torch.float32)
+    total32, _ = torch_loss(tc, tb, anchors, boxes, labels, num)
+    assert total32.dtype == torch.float32
+    total32.backward()
+    rows = [("encoded_boxes", tb.detach().numpy(), eb64), ("class_predictions", tc.detach().numpy(), cp64)]
+    rows += [("d " + name, T[name].grad.numpy(), g64[name]) for name in g64]
+    rows += [("d p%d" % (3 + l), P[l].grad.numpy(), df64[l]) for l in range(len(feats))]
+    return least, rows
+
+
+def rel(a, r):
+    """max |a - r| / max |r|: the predictor tests' norm-wise figure."""
+    return float(np.abs(np.asarray(a, np.float64) - r).max() / np.abs(r).max())

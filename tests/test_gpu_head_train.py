@@ -3,12 +3,11 @@ gradient against the CPU oracle bit for bit, the weight gradient exactly on inte
 random data, the batch norm against the float64 / float32 restatements of tests/helpers/head_train_ref.py, the predictor in
 inference mode against the engine bit for bit and in training mode against the float64 restatement, and the closed training loop
 with its checkpoint."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from helpers import head_train_ref as ref
+from helpers.head_train_gpu import bn_raw as _bn_raw, conv_backward as _backward, dev as _dev, predictor_training_check, ulps as _ulps
 from conftest import TINY_PARAMS
 
 pytestmark = pytest.mark.gpu
@@ -20,24 +19,10 @@ B = 2
 LP = {"gamma": 2.0, "alpha": 0.25}
 
 
-def _dev(cuda, a):
-    return cuda.from_numpy(np.ascontiguousarray(a, dtype=f32)).cuda()
-
-
 def _levels(rng, sizes, C, integers=False):
     if integers:
         return [rng.integers(-3, 4, (B, h, w, C)).astype(f32) for h, w in sizes]
     return [rng.normal(0, 1, (B, h, w, C)).astype(f32) for h, w in sizes]
-
-
-def _backward(ssd, cuda, xs, w, dys, bias=True):
-    """conv3x3_same's gradients through autograd: ([dx], dw, dbias) as numpy."""
-    tx = [_dev(cuda, x).requires_grad_() for x in xs]
-    tw = _dev(cuda, w).requires_grad_()
-    tb = cuda.zeros(w.shape[3], device="cuda", requires_grad=True) if bias else None
-    ys = ssd.conv3x3_same(tx, tw, tb)
-    cuda.autograd.backward(ys, [_dev(cuda, d) for d in dys])
-    return [t.grad.cpu().numpy() for t in tx], tw.grad.cpu().numpy(), tb.grad.cpu().numpy() if bias else None
 
 
 @pytest.mark.parametrize("Cin,Cout", SHAPES)
@@ -167,43 +152,6 @@ def test_batch_norm_relu_with_a_channel_count_that_is_no_multiple_of_4(ssd, cuda
     assert mm.abs().max().item() > 0
 
 
-def _ulps(a, b):
-    """Distance in units of the last place between float32 arrays of one sign pattern."""
-    ia, ib = a.astype(f32).view(np.int32).astype(np.int64), b.astype(f32).view(np.int32).astype(np.int64)
-    return np.abs(ia - ib)
-
-
-def _bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, dys=None):
-    """The two entry points straight through the C ABI; returns per level dicts of numpy arrays."""
-    L = ssd.lib()
-    n, C = len(xs), xs[0].shape[-1]
-    t = lambda a: _dev(cuda, a)
-    X, G, Bt, MM, MV = [t(v) for v in xs], [t(v) for v in gammas], [t(v) for v in betas], [t(v) for v in mms], [t(v) for v in mvs]
-    Y = [cuda.full_like(v, float("nan")) for v in X]
-    st = cuda.full((n, 5, C), float("nan"), device="cuda")
-    DX = [cuda.full_like(v, float("nan")) for v in X]
-    DY = [t(v) for v in dys] if dys is not None else [None] * n
-    lv = (ssd._lib.SsdBnLevel * n)()
-    for i in range(n):
-        lv[i].rows = X[i].numel() // C
-        for name, v in (("x", X[i]), ("dy", DY[i]), ("out", Y[i]), ("gamma", G[i]), ("beta", Bt[i]), ("moving_mean", MM[i]),
-                        ("moving_variance", MV[i]), ("mean", st[i, 0]), ("var", st[i, 1]), ("invstd", st[i, 2]), ("dgamma", st[i, 3]),
-                        ("dbeta", st[i, 4])):
-            setattr(lv[i], name, v.data_ptr() if v is not None else None)
-    ws = cuda.empty(L.ssd_bn_relu_train_workspace_bytes(lv, n, C), dtype=cuda.uint8, device="cuda")
-    s = ctypes.c_void_p(cuda.cuda.current_stream().cuda_stream)
-    ssd._lib.check(L.ssd_bn_relu_train_forward(lv, n, C, 1, float(f32(ref.EPS)), float(f32(1.0 - ref.MOMENTUM)), ws.data_ptr(), ws.numel(), s))
-    out = [dict(y=Y[i].cpu().numpy(), mean=st[i, 0].cpu().numpy(), var=st[i, 1].cpu().numpy(), invstd=st[i, 2].cpu().numpy(),
-                mm=MM[i].cpu().numpy(), mv=MV[i].cpu().numpy()) for i in range(n)]
-    if dys is not None:
-        for i in range(n):
-            lv[i].out = DX[i].data_ptr()
-        ssd._lib.check(L.ssd_bn_relu_train_backward(lv, n, C, ws.data_ptr(), ws.numel(), s))
-        for i in range(n):
-            out[i].update(dx=DX[i].cpu().numpy(), dgamma=st[i, 3].cpu().numpy(), dbeta=st[i, 4].cpu().numpy())
-    return out
-
-
 def test_batch_norm_against_the_restatements(ssd, cuda):
     """Mean and biased variance: the float64 value rounded once, 1 ulp allowed (the double sum's order).  invstd and the moving
     statistics: the float32 restatement applied to the kernel's mean and variance, bit for bit.  y, dx, dgamma, dbeta: within
@@ -270,21 +218,7 @@ def test_predictor_in_inference_mode_is_the_engine_bit_for_bit(ssd, cuda):
     assert np.array_equal(cp.cpu().numpy().reshape(classes.shape), classes)
 
 
-def _groundtruth(ssd, batch, seed):
-    """Anchors of 128 x 128 and, per image, one box on a jittered anchor of EVERY pyramid level (unclipped: the anchors of p6 and
-    p7 are larger than the image), so that both nets receive a gradient at every level."""
-    g = ssd.AnchorGenerator()
-    anchors = g(128, 128)
-    per_level = list(g.num_anchors_per_feature_map)
-    rng = np.random.default_rng(seed)
-    boxes = np.zeros((batch, len(per_level), 4), f32)
-    for b in range(batch):
-        at = 0
-        for l, n in enumerate(per_level):
-            a = anchors[at + rng.integers(0, n)]
-            boxes[b, l] = a + rng.normal(0, 0.02, 4) * (a[2] - a[0])
-            at += n
-    return anchors, boxes, rng.integers(0, 80, boxes.shape[:2]).astype(np.int32), np.full(batch, len(per_level), np.int32)
+_groundtruth = ref.groundtruth
 
 
 def test_predictor_in_training_mode_against_the_float64_restatement(ssd, cuda):
@@ -295,45 +229,9 @@ def test_predictor_in_training_mode_against_the_float64_restatement(ssd, cuda):
     in float32 torch ops, one backward; the kernels get FACTOR = 4 x it.  Both figures are printed per tensor and recorded in
     profiles/r14_head_train.log.  Measured on an MI355X: the kernels' figure is at or below the yardstick on most of the 99
     tensors; the worst ratio is 2.2 x (d class_net/batch_norm_3_for_level_7/beta, two rows: 5.26e-7 against 2.38e-7)."""
-    from test_head_train_host import _torch_predictor
-    import torch
     FACTOR = 4.0
     W, feats, _ = _engine_features(ssd, cuda, seed=3)
-    head = {k: v for k, v in W.items() if k.startswith(("box_net/", "class_net/"))}
-    anchors, boxes, labels, num = _groundtruth(ssd, 2, 5)
-    # float64 restatement; the loss gradient at ITS outputs, in float64
-    eb64, cp64 = ref.predictor(head, feats, 80)
-    tcp, teb = torch.tensor(cp64, requires_grad=True), torch.tensor(eb64, requires_grad=True)
-    total64, least = ref.torch_loss(tcp, teb, anchors, boxes, labels, num)
-    assert least >= 1                                               # at least one match per image
-    total64.backward()
-    g64, df64 = ref.predictor(head, feats, 80, d_boxes=teb.grad.numpy(), d_classes=tcp.grad.numpy())
-    # float32 CPU torch, the yardstick: the same graph, loss included, in float32
-    (tb, tc), T, P = _torch_predictor(head, feats, 80, dtype=torch.float32)
-    total32, _ = ref.torch_loss(tc, tb, anchors, boxes, labels, num)
-    assert total32.dtype == torch.float32
-    total32.backward()
-    # the HIP head
-    m = ssd.TrainableBoxPredictor(TINY_PARAMS, W, device="cuda").train()
-    fx = [_dev(cuda, f).requires_grad_() for f in feats]
-    eb, cp = m(fx)
-    gt = {"boxes": boxes, "labels": labels, "num_boxes": num}
-    out = ssd.differentiable_loss(cp, eb, _dev(cuda, anchors), gt, LP)
-    (out["localization_loss"] + out["classification_loss"]).backward()
-    rel = lambda a, r: float(np.abs(np.asarray(a, np.float64) - r).max() / np.abs(r).max())
-    rows = [("encoded_boxes", eb.detach().cpu().numpy(), tb.detach().numpy(), eb64), ("class_predictions", cp.detach().cpu().numpy(), tc.detach().numpy(), cp64)]
-    for name, p in m.named_variables().items():
-        rows.append(("d " + name, p.grad.cpu().numpy(), T[name].grad.numpy(), g64[name]))
-    for l in range(5):
-        rows.append(("d p%d" % (3 + l), fx[l].grad.cpu().numpy(), P[l].grad.numpy(), df64[l]))
-    bad = []
-    for name, got, t32, r64 in rows:
-        assert np.abs(r64).max() > 0, name                            # no vacuous comparison
-        yard, dev = rel(t32, r64), rel(got, r64)
-        print("train mode %-48s float32 torch %.3g  kernels %.3g" % (name, yard, dev))
-        if not dev <= FACTOR * yard:
-            bad.append((name, dev, yard))
-    assert not bad, bad
+    predictor_training_check(ssd, cuda, TINY_PARAMS, LP, W, feats, *_groundtruth(ssd, 2, 5), factor=FACTOR, tag="128x128")
 
 
 def _run_loop(ssd, cuda, W, feats, anchors, gt, steps, tmp=None, resume_from=None):

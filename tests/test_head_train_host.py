@@ -226,3 +226,113 @@ def test_torch_loss_restatement_equals_the_float64_loss_gradient_helper():
     dl, dc = loss_grad_ref.batch_grads(lg, cd, anchors, boxes, labels, num)
     assert least >= 1 and np.abs(dl).max() > 0 and np.abs(dc).max() > 0
     assert _rel(x.grad.numpy(), dl) <= 1e-12 and _rel(c.grad.numpy(), dc) <= 1e-12
+
+
+# ----------------------------------------------------------------------------- the references of tests/test_gpu_head_train_edges.py
+def test_double_sum_bound_holds_for_any_order_of_double_summation_and_not_for_float32():
+    """helpers.head_train_ref.double_sum_bound: a sequential float64 sum in a shuffled order and a long-double sum (math.fsum
+    where long double is no wider), each rounded once to float32, stay inside it -- on ordinary columns, on a column that
+    cancels to 2^-30 against terms that add up to 3e3 in magnitude, on an all-zero column.  A sequential float32 accumulation of the same terms does not:
+    the bound separates the header's "sums in double, rounded ONCE" from a float32 sum."""
+    import math
+    rng = np.random.default_rng(1)
+    n = 5000
+    t = rng.normal(0, 1, (n, 6)).astype(np.float32).astype(np.float64) * rng.normal(0, 1, (n, 6)).astype(np.float32).astype(np.float64)
+    t[n // 2:, 4] = -t[:n // 2, 4][::-1]                                 # cancels exactly ...
+    t[0, 4] += 2.0 ** -30                                                 # ... but for this
+    t[:, 5] = 0.0
+    want, tol = ref.double_sum_bound(t)
+    assert want[5] == 0 and abs(float(want[4]) - 2.0 ** -30) <= tol[4] and tol[4] < 1e-12 * np.abs(t[:, 4]).sum()
+    for seed in range(5):
+        order = np.random.default_rng(seed).permutation(n)
+        seq = np.cumsum(t[order], axis=0)[-1].astype(np.float32)          # one addition at a time, in this order
+        assert np.all(np.abs(seq.astype(np.float64) - want.astype(np.float64)) <= tol), seed
+    if np.finfo(np.longdouble).nmant > 52:
+        wide = t.astype(np.longdouble).sum(0).astype(np.float32)
+    else:
+        wide = np.array([math.fsum(t[:, c]) for c in range(6)], np.float32)
+    assert np.all(np.abs(wide.astype(np.float64) - want.astype(np.float64)) <= tol)
+    low = np.cumsum(t.astype(np.float32), axis=0, dtype=np.float32)[-1]
+    assert np.any(np.abs(low.astype(np.float64) - want.astype(np.float64))[:4] > tol[:4])
+    bad, _ = ref.double_sum_bound(np.where(np.arange(6) == 2, np.inf, t))
+    assert np.isnan(bad[2]) and np.array_equal(np.delete(bad, 2), np.delete(want, 2))
+
+
+def test_gate_and_restatement_agree_and_a_fused_multiply_add_does_not():
+    """bn_gate_f32 forms the gate from the SAME float32 expression as bn_relu_f32's y; on these inputs a fused t * sf + beta (one
+    rounding) differs from the header's two roundings in some elements: the bit-for-bit comparison of y can see a contraction."""
+    rng = np.random.default_rng(2)
+    x, dy = rng.normal(0.3, 1.5, (442, 256)).astype(np.float32), rng.normal(0, 1, (442, 256)).astype(np.float32)
+    gamma, beta = rng.uniform(0.5, 1.5, 256).astype(np.float32), rng.normal(0, 0.3, 256).astype(np.float32)
+    mean, var = x.astype(np.float64).mean(0).astype(np.float32), x.astype(np.float64).var(0).astype(np.float32)
+    y, dx, dg, db = ref.bn_relu_f32(x, gamma, beta, mean, var, dy)
+    g, xh = ref.bn_gate_f32(x, gamma, beta, mean, var, dy)
+    assert np.array_equal(g != 0, (y > 0) & (dy != 0))
+    y2, dx2, _, _ = ref.bn_relu_f32(x, gamma, beta, mean, var, dy, dgamma=dg, dbeta=db)
+    assert np.array_equal(y, y2) and np.array_equal(dx, dx2)
+    sf = gamma * ref.invstd_f32(var)
+    fused = np.maximum(((x - mean).astype(np.float64) * sf.astype(np.float64) + beta.astype(np.float64)).astype(np.float32), 0)
+    assert 0 < np.count_nonzero(fused != y) < y.size // 2
+    # var = 0: the header's two float32 operations give the float32 just below fp32(1 / sqrt(eps)) rounded once
+    two = ref.invstd_f32(np.zeros(1, np.float32))[0]
+    once = np.float32(1.0 / np.sqrt(float(np.float32(ref.EPS))))
+    assert two != once and abs(int(two.view(np.int32)) - int(once.view(np.int32))) == 1
+
+
+def test_offset_channel_two_pass_variance_is_inside_the_bound_and_one_pass_is_not():
+    """mean 1e3, std 1e-2 (the offset channels of the GPU test): the float64 variance around the float32 mean, rounded once, is
+    within offset_variance_bound of the true float64 variance; E[x^2] - mean32^2 (sums in double) and an all-float32 one-pass
+    variance are outside it by orders of magnitude."""
+    rng = np.random.default_rng(5)
+    x = (1e3 + 1e-2 * rng.normal(0, 1, (442, 3))).astype(np.float32)
+    x64 = x.astype(np.float64)
+    true = x64.var(0)
+    m32 = x64.mean(0).astype(np.float32)
+    bound = ref.offset_variance_bound(1e3, true.max())
+    assert 1e-5 < bound < 1e-3
+    two = ((x64 - m32.astype(np.float64)) ** 2).mean(0).astype(np.float32)
+    assert np.all(np.abs(two.astype(np.float64) - true) / true <= bound)
+    assert np.any(m32.astype(np.float64) != x64.mean(0))
+    one = (x64 ** 2).mean(0) - m32.astype(np.float64) ** 2
+    one32 = (x * x).mean(0, dtype=np.float32) - m32 * m32
+    assert np.all(np.abs(one - true) / true > 100 * bound) and np.all(np.abs(one32.astype(np.float64) - true) / true > 100 * bound)
+
+
+def test_slab_and_slice_formulas_give_what_the_cases_intend():
+    assert ref.slab_plan([143360, 35840, 8960, 2240, 560], 256) == (4, 188, 1017)
+    assert ref.slab_plan([442], 256) == (4, 32, 14) and ref.slab_plan([30], 6) == (128, 1024, 1)
+    assert ref.rows_per_slice([17920, 4480, 1026], 256, 40) == 288 and ref.rows_per_slice([17920, 4480, 1026], 64, 40) == 256
+    B, sizes, Cin, Cout = ref.CONV_CASES["slice-edge"]
+    rows = [B * h * w for h, w in sizes]
+    assert rows == [512, 513] and ref.rows_per_slice(rows, Cin, Cout) == 256
+
+
+@pytest.mark.parametrize("case", sorted(ref.CONV_CASES))
+def test_sweep_cases_keep_their_integer_premise(case):
+    """What keeps the GPU sweep's exactness check sound: every absolute partial sum of the integer data is below 2^24 and the
+    expected dw is not zero; the random data's bound is finite and positive."""
+    B, sizes, Cin, Cout = ref.CONV_CASES[case]
+    _, _, xs, w, bias, dys = ref.conv_case_data(case, integers=True)
+    assert Cin % 8 == 0 and all(x.shape == (B, h, ww, Cin) for x, (h, ww) in zip(xs, sizes)) and 1 <= len(sizes) <= 8
+    assert max(np.abs(x).max() for x in xs) <= 3 and max(np.abs(d).max() for d in dys) <= 3 and np.abs(w).max() <= 2
+    dw64, db64, top_w, top_b = ref.integer_premise(xs, w, dys)
+    assert top_w < 2 ** 24 and top_b < 2 ** 24 and np.abs(dw64).max() > 0 and np.abs(db64).max() > 0
+    _, _, xs, w, bias, dys = ref.conv_case_data(case, integers=False)
+    dw64, bound, absum = ref.wgrad_bound(xs, w, dys)
+    assert np.all(bound > 0) and np.all(np.isfinite(bound)) and np.all(np.abs(dw64) <= absum)
+
+
+def test_large_predictor_input_has_a_yardstick_for_every_tensor(ssd):
+    """The 320 x 448 input of the GPU test: at least one match per image, every reference tensor non-zero and every float32
+    yardstick above zero, so that FACTOR x yardstick is a bound and no comparison is vacuous."""
+    from conftest import TINY_PARAMS
+    W, feats, anchors, boxes, labels, num = ref.large_predictor_input(ssd, TINY_PARAMS)
+    assert [f.shape for f in feats] == [(3, h, w, 256) for h, w in ref.LARGE_SIZES]
+    assert anchors.shape[0] == sum(6 * h * w for h, w in ref.LARGE_SIZES)
+    least, rows = ref.predictor_references(W, feats, anchors, boxes, labels, num)
+    assert least >= 1 and len(rows) == 2 + 2 * (4 + 2 + 4 * 5 * 2) + 5
+    for name, t32, r64 in rows:
+        assert np.abs(r64).max() > 0, name
+        yard = ref.rel(t32, r64)
+        print("yardstick 320x448 %-48s %.3g" % (name, yard))
+        assert 0 < yard < 1e-2, name
