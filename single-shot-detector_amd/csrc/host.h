@@ -1,8 +1,9 @@
 // Host-side declarations shared by the translation units behind the C ABI (include/ssd_hip.h):
 //   abi.hip      lifetime, options, ssd_forward, retained tensors, profiling
-//   weights.hip  ssd_finalize: TF variables -> packed device weights (channel order, batch-norm scale factors)
+//   weights.hip  ssd_finalize: TF variables -> packed device weights (batch-norm scale factors), and the packing helpers every
+//                path shares: permute_rows / permute_bn (channel order), conv_geometry, pack_conv, upload_bn, upload_dw, pack_dw
 //   plan.hip     the layer plan of one (B,H,W): ops, streams, dependencies; enqueue
-//   stages.hip   the stage entry points the parity tests call, anchors, resize arithmetic, diagnostics (-DSSD_DIAG)
+//   stages.hip   the stage entry points the parity tests call (StagePool: their scratch), anchors, resize arithmetic, diagnostics (-DSSD_DIAG)
 // Kernels and their launch wrappers: ssd_internal.h.
 #pragma once
 #include "../../include/ssd_hip.h"
@@ -141,13 +142,20 @@ static constexpr int g_force_tile = -1;
 static constexpr long long *g_dbg_ts = nullptr;
 #endif
 
-// weights.hip: w HWIO [k,k,Cin_l,Cout_l] -> wt [taps][CoutPad][CinP]
+// weights.hip.  The physical channel order (ssd_internal.h) reaches weights through permute_rows / permute_bn and pack_conv's own
+// loop, nowhere else; a caller chooses the padded width by the map it passes (phys_map / ident_map / twopart_map above).
+std::vector<float> permute_rows(const float *w, int rows, int C, const std::vector<int> &map);     // [rows][C] -> [rows][map.size()], pads zero
+BnHost permute_bn(const float *mean, const float *sf, const float *beta, const std::vector<int> &map,
+                  BnHost o = BnHost());                  // appended to o; mean == nullptr: nothing
+// taps, padded widths, tile and CoutPad of a packed kernel (pack_conv's; train_head.hip packs the same layout on the device)
+void conv_geometry(const struct ssd_handle *h, int taps, int CinP, int CoutP, int Cin_l, int Cout_l, ConvW &cw);
+// w HWIO [k,k,Cin_l,Cout_l] -> wt [taps][CoutPad][CinP] (+ the lane-order and split-fp16 forms)
 int pack_conv(const struct ssd_handle *h, DevPool &pool, const float *w, int k, int Cin_l, int Cout_l, const std::vector<int> &inmap,
               const std::vector<int> &outmap, ConvW &cw);
-int conv_pick_tile(const struct ssd_handle *h, int CoutP);     // the tile pack_conv gives a kernel of this padded width (train_head.hip packs on the device)
 int upload_bn(DevPool &pool, const BnHost &b, ConvW &cw);
-int pack_dw(DevPool &pool, const std::vector<float> &w9, const std::vector<float> &mean, const std::vector<float> &sf,
-            const std::vector<float> &beta, DwW &d);
+// permuted rows [9 or 27][d.Cp] + batch norm -> d.w / mean / sf / beta (empty vectors skipped), and behind nine taps pack_dw
+int upload_dw(DevPool &pool, const std::vector<float> &w, const BnHost &b, DwW &d);
+int pack_dw(DevPool &pool, const std::vector<float> &w9, const BnHost &b, DwW &d);     // d.pack; nothing unless d.Cp % 32 == 0
 int finalize_weights(struct ssd_handle *h);
 
 // ----------------------------------------------------------------------------- ops

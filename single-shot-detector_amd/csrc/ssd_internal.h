@@ -13,8 +13,8 @@
 // 0,1,2,...,7 -- the order the oracle (and an HWIO kernel) defines.
 // phys -> logical:  p<4 ? 2p : 2(p-4)+1 ;  logical -> phys:  l even ? l/2 : 4+(l-1)/2
 // ---------------------------------------------------------------------------------------
-static inline int ssd_phys_of_logical(int l) { int o = l & ~7, r = l & 7; return o + ((r & 1) ? 4 + (r >> 1) : (r >> 1)); }
-static inline int ssd_logical_of_phys(int p) { int o = p & ~7, r = p & 7; return o + (r < 4 ? 2 * r : 2 * (r - 4) + 1); }
+__host__ __device__ static inline int ssd_phys_of_logical(int l) { int o = l & ~7, r = l & 7; return o + ((r & 1) ? 4 + (r >> 1) : (r >> 1)); }
+__host__ __device__ static inline int ssd_logical_of_phys(int p) { int o = p & ~7, r = p & 7; return o + (r < 4 ? 2 * r : 2 * (r - 4) + 1); }
 
 #define SSD_MAX_LEVELS 10     // 5 pyramid levels; 10 = both head towers' levels in one launch (plan.hip)
 

@@ -115,12 +115,13 @@ ResizeDims resize_dims(int height, int width, int min_dimension, int divisor)
 }
 
 // ----------------------------------------------------------------------------- stage entry points
-static int to_dev(DevPool &pool, const float *host, size_t n, float **out)
-{
-    if (!host) { *out = nullptr; return SSD_OK; }
-    std::vector<float> v(host, host + n);
-    return pool.upload(out, v);
-}
+// The scratch of one stage call: however the call returns, its stream is drained first and the scratch freed after, so every
+// entry point returns with its work complete and nothing of it left on the device.
+struct StagePool : DevPool {
+    hipStream_t s;
+    explicit StagePool(hipStream_t stream) : s(stream) {}
+    ~StagePool() { (void)hipStreamSynchronize(s); free_all(); }
+};
 
 static int conv2d_impl(int x16, const float *in_dev, int32_t B, int32_t H, int32_t W, int32_t Cin, const float *w_host,
                           int32_t k, int32_t Cout, int32_t stride, int32_t pad_beg, int32_t OH, int32_t OW,
@@ -139,57 +140,38 @@ static int conv2d_impl(int x16, const float *in_dev, int32_t B, int32_t H, int32
     if ((bn_mean && (bias_host || up_dev)) || (bias_host && up_dev))
         return ssd_fail(SSD_ERR_INVALID, "ssd_conv2d: batch norm, bias and upsample-add are mutually exclusive");
     hipStream_t s = (hipStream_t)stream;
-    DevPool pool;
-    int rc = SSD_OK;
-    auto body = [&]() -> int {
-        const int CinP = round_up(Cin, 32), CoutP = round_up(Cout, 8);
-        ConvW cw;
-        std::vector<int> inmap = phys_map(Cin, CinP), outmap = phys_map(Cout, CoutP);
-        SSDCHK(pack_conv(nullptr, pool, w_host, k, Cin, Cout, inmap, outmap, cw));
-        if (bn_mean) {
-            BnHost b;
-            for (int p : outmap) {
-                b.mean.push_back(p < 0 ? 0.f : bn_mean[p]);
-                b.sf.push_back(p < 0 ? 0.f : bn_sf[p]);
-                b.beta.push_back(p < 0 ? 0.f : bn_beta[p]);
-            }
-            SSDCHK(upload_bn(pool, b, cw));
-        }
-        if (bias_host) {
-            std::vector<float> b;
-            for (int p : outmap) b.push_back(p < 0 ? 0.f : bias_host[p]);
-            SSDCHK(pool.upload(&cw.bias, b));
-        }
-        float *tin, *tout, *tup = nullptr;
-        const long long rin = (long long)B * H * W, rout = (long long)B * OH * OW;
-        SSDCHK(pool.alloc((void **)&tin, (size_t)rin * CinP * 4));
-        SSDCHK(pool.alloc((void **)&tout, (size_t)rout * CoutP * 4));
-        // f16x3: input, upsampled operand and (unless a bias form / odd width forbids S16 rows) output in split-fp16
-        const int o16 = x16 && !bias_host && CoutP % 8 == 0 ? 1 : 0;
-        int *flags = nullptr;
-        if (x16) { SSDCHK(pool.alloc((void **)&flags, sizeof(int))); HIPCHK(hipMemsetAsync(flags, 0, sizeof(int), s)); }
-        HIPCHK(launch_permute_channels(in_dev, rin, Cin, CinP, x16 ? 3 : 1, tin, s));
-        if (up_dev) {
-            SSDCHK(pool.alloc((void **)&tup, (size_t)(rout / 4) * CoutP * 4));
-            HIPCHK(launch_permute_channels(up_dev, rout / 4, Cout, CoutP, o16 ? 3 : 1, tup, s));
-        }
-        ConvIO io{tin, tout};
-        io.res = tup; io.in_fmt = x16; io.out_fmt = io.res_fmt = o16; io.flags = flags;
-        Op op = make_conv_op(nullptr, cw, io, B, stride, pad_beg, act, {dense_level(H, W, OH, OW, CoutP)}, true);
-        HIPCHK(op.run(s));
-        HIPCHK(launch_permute_channels(tout, rout, Cout, CoutP, o16 ? 2 : 0, out_dev, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (x16) {
-            int f = 0;
-            HIPCHK(hipMemcpy(&f, flags, sizeof(int), hipMemcpyDeviceToHost));
-            if (f) return ssd_fail(SSD_ERR_INVALID, "ssd_conv2d_f16x3: a value left the fp16 range (|x| > 65504)");
-        }
-        return SSD_OK;
-    };
-    rc = body();
-    (void)hipStreamSynchronize(s);
-    pool.free_all();
-    return rc;
+    StagePool pool(s);
+    const int CinP = round_up(Cin, 32), CoutP = round_up(Cout, 8);
+    ConvW cw;
+    std::vector<int> inmap = phys_map(Cin, CinP), outmap = phys_map(Cout, CoutP);
+    SSDCHK(pack_conv(nullptr, pool, w_host, k, Cin, Cout, inmap, outmap, cw));
+    if (bn_mean) SSDCHK(upload_bn(pool, permute_bn(bn_mean, bn_sf, bn_beta, outmap), cw));
+    if (bias_host) SSDCHK(pool.upload(&cw.bias, permute_rows(bias_host, 1, Cout, outmap)));
+    float *tin, *tout, *tup = nullptr;
+    const long long rin = (long long)B * H * W, rout = (long long)B * OH * OW;
+    SSDCHK(pool.alloc((void **)&tin, (size_t)rin * CinP * 4));
+    SSDCHK(pool.alloc((void **)&tout, (size_t)rout * CoutP * 4));
+    // f16x3: input, upsampled operand and (unless a bias form / odd width forbids S16 rows) output in split-fp16
+    const int o16 = x16 && !bias_host && CoutP % 8 == 0 ? 1 : 0;
+    int *flags = nullptr;
+    if (x16) { SSDCHK(pool.alloc((void **)&flags, sizeof(int))); HIPCHK(hipMemsetAsync(flags, 0, sizeof(int), s)); }
+    HIPCHK(launch_permute_channels(in_dev, rin, Cin, CinP, x16 ? 3 : 1, tin, s));
+    if (up_dev) {
+        SSDCHK(pool.alloc((void **)&tup, (size_t)(rout / 4) * CoutP * 4));
+        HIPCHK(launch_permute_channels(up_dev, rout / 4, Cout, CoutP, o16 ? 3 : 1, tup, s));
+    }
+    ConvIO io{tin, tout};
+    io.res = tup; io.in_fmt = x16; io.out_fmt = io.res_fmt = o16; io.flags = flags;
+    Op op = make_conv_op(nullptr, cw, io, B, stride, pad_beg, act, {dense_level(H, W, OH, OW, CoutP)}, true);
+    HIPCHK(op.run(s));
+    HIPCHK(launch_permute_channels(tout, rout, Cout, CoutP, o16 ? 2 : 0, out_dev, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (x16) {
+        int f = 0;
+        HIPCHK(hipMemcpy(&f, flags, sizeof(int), hipMemcpyDeviceToHost));
+        if (f) return ssd_fail(SSD_ERR_INVALID, "ssd_conv2d_f16x3: a value left the fp16 range (|x| > 65504)");
+    }
+    return SSD_OK;
 }
 
 extern "C" int ssd_conv2d(const float *in_dev, int32_t B, int32_t H, int32_t W, int32_t Cin, const float *w_host,
@@ -219,33 +201,21 @@ extern "C" int ssd_depthwise3x3(const float *in_dev, int32_t B, int32_t H, int32
     if ((bn_mean || bn_sf || bn_beta) && !(bn_mean && bn_sf && bn_beta))
         return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise3x3: batch-norm vectors must be given together");
     hipStream_t s = (hipStream_t)stream;
-    DevPool pool;
-    auto body = [&]() -> int {
-        const int Cp = round_up(C, 8);
-        std::vector<int> map = phys_map(C, Cp);
-        std::vector<float> wt((size_t)9 * Cp, 0.f), m, sf, be;
-        for (int t = 0; t < 9; ++t)
-            for (int p = 0; p < Cp; ++p)
-                if (map[p] >= 0) wt[(size_t)t * Cp + p] = w_host[(size_t)t * C + map[p]];
-        float *dw_, *dm = nullptr, *ds = nullptr, *db = nullptr, *tin, *tout;
-        SSDCHK(pool.upload(&dw_, wt));
-        if (bn_mean) {
-            for (int p : map) { m.push_back(p < 0 ? 0.f : bn_mean[p]); sf.push_back(p < 0 ? 0.f : bn_sf[p]); be.push_back(p < 0 ? 0.f : bn_beta[p]); }
-            SSDCHK(pool.upload(&dm, m)); SSDCHK(pool.upload(&ds, sf)); SSDCHK(pool.upload(&db, be));
-        }
-        const long long rin = (long long)B * H * W, rout = (long long)B * OH * OW;
-        SSDCHK(pool.alloc((void **)&tin, (size_t)rin * Cp * 4));
-        SSDCHK(pool.alloc((void **)&tout, (size_t)rout * Cp * 4));
-        HIPCHK(launch_permute_channels(in_dev, rin, C, Cp, 1, tin, s));
-        HIPCHK(launch_depthwise(tin, B, H, W, Cp, dw_, stride, pad_beg, OH, OW, dm, ds, db, act, tout, s));
-        HIPCHK(launch_permute_channels(tout, rout, C, Cp, 0, out_dev, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return SSD_OK;
-    };
-    int rc = body();
-    (void)hipStreamSynchronize(s);
-    pool.free_all();
-    return rc;
+    StagePool pool(s);
+    const int Cp = round_up(C, 8);
+    std::vector<int> map = phys_map(C, Cp);
+    DwW d;
+    d.Cp = Cp;
+    SSDCHK(upload_dw(pool, permute_rows(w_host, 9, C, map), permute_bn(bn_mean, bn_sf, bn_beta, map), d));
+    float *tin, *tout;
+    const long long rin = (long long)B * H * W, rout = (long long)B * OH * OW;
+    SSDCHK(pool.alloc((void **)&tin, (size_t)rin * Cp * 4));
+    SSDCHK(pool.alloc((void **)&tout, (size_t)rout * Cp * 4));
+    HIPCHK(launch_permute_channels(in_dev, rin, C, Cp, 1, tin, s));
+    HIPCHK(launch_depthwise(tin, B, H, W, Cp, d.w, stride, pad_beg, OH, OW, d.mean, d.sf, d.beta, act, tout, s));
+    HIPCHK(launch_permute_channels(tout, rout, C, Cp, 0, out_dev, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SSD_OK;
 }
 
 extern "C" int ssd_dw_pw(const float *in_dev, int32_t B, int32_t H, int32_t W, int32_t C, const float *dw_w_host,
@@ -258,42 +228,28 @@ extern "C" int ssd_dw_pw(const float *in_dev, int32_t B, int32_t H, int32_t W, i
         return ssd_fail(SSD_ERR_INVALID, "ssd_dw_pw: bad arguments");
     if (stride == 2 && ((H & 1) || (W & 1))) return ssd_fail(SSD_ERR_INVALID, "ssd_dw_pw: stride 2 needs even H, W");
     hipStream_t s = (hipStream_t)stream;
-    DevPool pool;
-    auto body = [&]() -> int {
-        const int Cp = round_up(C, 32), CoutP = round_up(Cout, 8);
-        std::vector<int> map = phys_map(C, Cp), outmap = phys_map(Cout, CoutP);
-        DwW d;
-        d.Cp = Cp;
-        std::vector<float> wt((size_t)9 * Cp, 0.f), m, sf, be;
-        for (int t = 0; t < 9; ++t)
-            for (int p = 0; p < Cp; ++p)
-                if (map[p] >= 0) wt[(size_t)t * Cp + p] = dw_w_host[(size_t)t * C + map[p]];
-        for (int p : map) { m.push_back(p < 0 ? 0.f : dw_mean[p]); sf.push_back(p < 0 ? 0.f : dw_sf[p]); be.push_back(p < 0 ? 0.f : dw_beta[p]); }
-        SSDCHK(pool.upload(&d.w, wt)); SSDCHK(pool.upload(&d.mean, m)); SSDCHK(pool.upload(&d.sf, sf)); SSDCHK(pool.upload(&d.beta, be));
-        SSDCHK(pack_dw(pool, wt, m, sf, be, d));
-        ConvW cw;
-        SSDCHK(pack_conv(nullptr, pool, pw_w_host, 1, C, Cout, map, outmap, cw));
-        BnHost b;
-        for (int p : outmap) { b.mean.push_back(p < 0 ? 0.f : pw_mean[p]); b.sf.push_back(p < 0 ? 0.f : pw_sf[p]); b.beta.push_back(p < 0 ? 0.f : pw_beta[p]); }
-        SSDCHK(upload_bn(pool, b, cw));
-        if (!dwpws_eligible(d, cw, B, H, W, stride))
-            return ssd_fail(SSD_ERR_INVALID, "ssd_dw_pw: shape not supported by the fused kernel (every tensor below 2 GiB, stride 2 needs even H and W)");
-        const int OH = H / stride, OW = W / stride;
-        float *tin, *tout;
-        const long long rin = (long long)B * H * W, rout = (long long)B * OH * OW;
-        SSDCHK(pool.alloc((void **)&tin, (size_t)rin * Cp * 4));
-        SSDCHK(pool.alloc((void **)&tout, (size_t)rout * CoutP * 4));
-        HIPCHK(launch_permute_channels(in_dev, rin, C, Cp, 1, tin, s));
-        Op op = make_dwpws_op(d, cw, tin, B, H, W, stride, dw_act, pw_act, tout);
-        HIPCHK(op.run(s));
-        HIPCHK(launch_permute_channels(tout, rout, Cout, CoutP, 0, out_dev, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return SSD_OK;
-    };
-    int rc = body();
-    (void)hipStreamSynchronize(s);
-    pool.free_all();
-    return rc;
+    StagePool pool(s);
+    const int Cp = round_up(C, 32), CoutP = round_up(Cout, 8);
+    std::vector<int> map = phys_map(C, Cp), outmap = phys_map(Cout, CoutP);
+    DwW d;
+    d.Cp = Cp;
+    SSDCHK(upload_dw(pool, permute_rows(dw_w_host, 9, C, map), permute_bn(dw_mean, dw_sf, dw_beta, map), d));
+    ConvW cw;
+    SSDCHK(pack_conv(nullptr, pool, pw_w_host, 1, C, Cout, map, outmap, cw));
+    SSDCHK(upload_bn(pool, permute_bn(pw_mean, pw_sf, pw_beta, outmap), cw));
+    if (!dwpws_eligible(d, cw, B, H, W, stride))
+        return ssd_fail(SSD_ERR_INVALID, "ssd_dw_pw: shape not supported by the fused kernel (every tensor below 2 GiB, stride 2 needs even H and W)");
+    const int OH = H / stride, OW = W / stride;
+    float *tin, *tout;
+    const long long rin = (long long)B * H * W, rout = (long long)B * OH * OW;
+    SSDCHK(pool.alloc((void **)&tin, (size_t)rin * Cp * 4));
+    SSDCHK(pool.alloc((void **)&tout, (size_t)rout * CoutP * 4));
+    HIPCHK(launch_permute_channels(in_dev, rin, C, Cp, 1, tin, s));
+    Op op = make_dwpws_op(d, cw, tin, B, H, W, stride, dw_act, pw_act, tout);
+    HIPCHK(op.run(s));
+    HIPCHK(launch_permute_channels(tout, rout, Cout, CoutP, 0, out_dev, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SSD_OK;
 }
 
 extern "C" int ssd_first_conv(const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, const float *w_host,
@@ -305,31 +261,19 @@ extern "C" int ssd_first_conv(const uint8_t *images_dev, int32_t B, int32_t H, i
     if ((bn_mean || bn_sf || bn_beta) && !(bn_mean && bn_sf && bn_beta))
         return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv: batch-norm vectors must be given together");
     hipStream_t s = (hipStream_t)stream;
-    DevPool pool;
-    auto body = [&]() -> int {
-        const int Cp = round_up(Cout, 8);
-        std::vector<int> map = phys_map(Cout, Cp);
-        std::vector<float> wt((size_t)27 * Cp, 0.f), m, sf, be;
-        for (int t = 0; t < 27; ++t)
-            for (int p = 0; p < Cp; ++p)
-                if (map[p] >= 0) wt[(size_t)t * Cp + p] = w_host[(size_t)t * Cout + map[p]];
-        float *dw_, *dm = nullptr, *ds = nullptr, *db = nullptr, *tout;
-        SSDCHK(pool.upload(&dw_, wt));
-        if (bn_mean) {
-            for (int p : map) { m.push_back(p < 0 ? 0.f : bn_mean[p]); sf.push_back(p < 0 ? 0.f : bn_sf[p]); be.push_back(p < 0 ? 0.f : bn_beta[p]); }
-            SSDCHK(pool.upload(&dm, m)); SSDCHK(pool.upload(&ds, sf)); SSDCHK(pool.upload(&db, be));
-        }
-        const long long rout = (long long)B * (H / 2) * (W / 2);
-        SSDCHK(pool.alloc((void **)&tout, (size_t)rout * Cp * 4));
-        HIPCHK(launch_first_conv(images_dev, B, H, W, H, W, H, W, dw_, Cp, dm, ds, db, act, tout, s));
-        HIPCHK(launch_permute_channels(tout, rout, Cout, Cp, 0, out_dev, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return SSD_OK;
-    };
-    int rc = body();
-    (void)hipStreamSynchronize(s);
-    pool.free_all();
-    return rc;
+    StagePool pool(s);
+    const int Cp = round_up(Cout, 8);
+    std::vector<int> map = phys_map(Cout, Cp);
+    DwW f;
+    f.Cp = Cp;
+    SSDCHK(upload_dw(pool, permute_rows(w_host, 27, Cout, map), permute_bn(bn_mean, bn_sf, bn_beta, map), f));
+    float *tout;
+    const long long rout = (long long)B * (H / 2) * (W / 2);
+    SSDCHK(pool.alloc((void **)&tout, (size_t)rout * Cp * 4));
+    HIPCHK(launch_first_conv(images_dev, B, H, W, H, W, H, W, f.w, Cp, f.mean, f.sf, f.beta, act, tout, s));
+    HIPCHK(launch_permute_channels(tout, rout, Cout, Cp, 0, out_dev, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SSD_OK;
 }
 
 // MobileNet's first three layers as the one launch the layer plan uses for them (front.hip): first convolution 3x3 stride 2
@@ -347,47 +291,30 @@ extern "C" int ssd_front_block(const uint8_t *images_dev, int32_t B, int32_t H, 
     if (!front_supports(B, H, W, C0, C0, Cout))
         return ssd_fail(SSD_ERR_INVALID, "ssd_front_block: shape not supported (32 -> 32 -> 64 channels, every tensor below 2 GiB)");
     hipStream_t s = (hipStream_t)stream;
-    DevPool pool;
-    auto body = [&]() -> int {
-        const int Cp = 32, CoutP = 64;
-        std::vector<int> map = phys_map(C0, Cp), outmap = phys_map(Cout, CoutP);
-        DwW f, d;
-        f.Cp = d.Cp = Cp;
-        std::vector<float> w0((size_t)27 * Cp, 0.f), wd((size_t)9 * Cp, 0.f), m0, s0, b0, m, sf, be;
-        for (int t = 0; t < 27; ++t)
-            for (int p = 0; p < Cp; ++p) w0[(size_t)t * Cp + p] = w0_host[(size_t)t * C0 + map[p]];
-        for (int t = 0; t < 9; ++t)
-            for (int p = 0; p < Cp; ++p) wd[(size_t)t * Cp + p] = dw_w_host[(size_t)t * C0 + map[p]];
-        for (int p : map) {
-            m0.push_back(bn0_mean[p]); s0.push_back(bn0_sf[p]); b0.push_back(bn0_beta[p]);
-            m.push_back(dw_mean[p]); sf.push_back(dw_sf[p]); be.push_back(dw_beta[p]);
-        }
-        SSDCHK(pool.upload(&f.w, w0)); SSDCHK(pool.upload(&f.mean, m0)); SSDCHK(pool.upload(&f.sf, s0)); SSDCHK(pool.upload(&f.beta, b0));
-        SSDCHK(pack_dw(pool, wd, m, sf, be, d));
-        ConvW cw;
-        SSDCHK(pack_conv(nullptr, pool, pw_w_host, 1, C0, Cout, map, outmap, cw));
-        BnHost b;
-        for (int p : outmap) { b.mean.push_back(pw_mean[p]); b.sf.push_back(pw_sf[p]); b.beta.push_back(pw_beta[p]); }
-        SSDCHK(upload_bn(pool, b, cw));
-        float *tout;
-        const long long rout = (long long)B * (H / 2) * (W / 2);
-        SSDCHK(pool.alloc((void **)&tout, (size_t)rout * CoutP * 4));
-        FrontArgs q;
-        memset(&q, 0, sizeof(q));
-        q.img = images_dev; q.w0 = f.w; q.m0 = f.mean; q.s0 = f.sf; q.b0 = f.beta; q.dwpack = d.pack;
-        q.wt = cw.wt; q.mean = cw.mean; q.sf = cw.sf; q.beta = cw.beta; q.out = tout;
-        q.B = B; q.H = H; q.W = W; q.act0 = act0; q.dact = dw_act; q.act = pw_act;
-        q.tiles_y = (H / 2 + front_tile_y() - 1) / front_tile_y();
-        q.tiles_x = (W / 2 + front_tile_x() - 1) / front_tile_x();
-        HIPCHK(launch_front(q, s));
-        HIPCHK(launch_permute_channels(tout, rout, Cout, CoutP, 0, out_dev, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return SSD_OK;
-    };
-    int rc = body();
-    (void)hipStreamSynchronize(s);
-    pool.free_all();
-    return rc;
+    StagePool pool(s);
+    const int Cp = 32, CoutP = 64;
+    std::vector<int> map = phys_map(C0, Cp), outmap = phys_map(Cout, CoutP);
+    DwW f, d;
+    f.Cp = d.Cp = Cp;
+    SSDCHK(upload_dw(pool, permute_rows(w0_host, 27, C0, map), permute_bn(bn0_mean, bn0_sf, bn0_beta, map), f));
+    SSDCHK(pack_dw(pool, permute_rows(dw_w_host, 9, C0, map), permute_bn(dw_mean, dw_sf, dw_beta, map), d));     // (the launch reads the pack only)
+    ConvW cw;
+    SSDCHK(pack_conv(nullptr, pool, pw_w_host, 1, C0, Cout, map, outmap, cw));
+    SSDCHK(upload_bn(pool, permute_bn(pw_mean, pw_sf, pw_beta, outmap), cw));
+    float *tout;
+    const long long rout = (long long)B * (H / 2) * (W / 2);
+    SSDCHK(pool.alloc((void **)&tout, (size_t)rout * CoutP * 4));
+    FrontArgs q;
+    memset(&q, 0, sizeof(q));
+    q.img = images_dev; q.w0 = f.w; q.m0 = f.mean; q.s0 = f.sf; q.b0 = f.beta; q.dwpack = d.pack;
+    q.wt = cw.wt; q.mean = cw.mean; q.sf = cw.sf; q.beta = cw.beta; q.out = tout;
+    q.B = B; q.H = H; q.W = W; q.act0 = act0; q.dact = dw_act; q.act = pw_act;
+    q.tiles_y = (H / 2 + front_tile_y() - 1) / front_tile_y();
+    q.tiles_x = (W / 2 + front_tile_x() - 1) / front_tile_x();
+    HIPCHK(launch_front(q, s));
+    HIPCHK(launch_permute_channels(tout, rout, Cout, CoutP, 0, out_dev, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SSD_OK;
 }
 
 // ShuffleNet's first two layers as the one launch the layer plan uses for them (front.hip): ssd_first_conv (3 -> 24) followed
@@ -401,27 +328,19 @@ extern "C" int ssd_first_conv_maxpool(const uint8_t *images_dev, int32_t B, int3
     if (Cout != 24 || !front_pool_supports(B, H, W, Cout))
         return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_maxpool: shape not supported (24 output channels, H and W multiples of 4, frames below 2 GiB)");
     hipStream_t s = (hipStream_t)stream;
-    DevPool pool;
-    auto body = [&]() -> int {
-        const int Cp = 24;
-        std::vector<int> map = phys_map(Cout, Cp);
-        std::vector<float> wt((size_t)27 * Cp, 0.f), m, sf, be;
-        for (int t = 0; t < 27; ++t)
-            for (int p = 0; p < Cp; ++p) wt[(size_t)t * Cp + p] = w_host[(size_t)t * Cout + map[p]];
-        for (int p : map) { m.push_back(bn_mean[p]); sf.push_back(bn_sf[p]); be.push_back(bn_beta[p]); }
-        float *dw_, *dm, *ds, *db, *tout;
-        SSDCHK(pool.upload(&dw_, wt)); SSDCHK(pool.upload(&dm, m)); SSDCHK(pool.upload(&ds, sf)); SSDCHK(pool.upload(&db, be));
-        const long long rout = (long long)B * (H / 4) * (W / 4);
-        SSDCHK(pool.alloc((void **)&tout, (size_t)rout * Cp * 4));
-        HIPCHK(launch_front_pool(images_dev, B, H, W, dw_, Cp, dm, ds, db, act, tout, s));
-        HIPCHK(launch_permute_channels(tout, rout, Cout, Cp, 0, out_dev, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return SSD_OK;
-    };
-    int rc = body();
-    (void)hipStreamSynchronize(s);
-    pool.free_all();
-    return rc;
+    StagePool pool(s);
+    const int Cp = 24;
+    std::vector<int> map = phys_map(Cout, Cp);
+    DwW f;
+    f.Cp = Cp;
+    SSDCHK(upload_dw(pool, permute_rows(w_host, 27, Cout, map), permute_bn(bn_mean, bn_sf, bn_beta, map), f));
+    float *tout;
+    const long long rout = (long long)B * (H / 4) * (W / 4);
+    SSDCHK(pool.alloc((void **)&tout, (size_t)rout * Cp * 4));
+    HIPCHK(launch_front_pool(images_dev, B, H, W, f.w, Cp, f.mean, f.sf, f.beta, act, tout, s));
+    HIPCHK(launch_permute_channels(tout, rout, Cout, Cp, 0, out_dev, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SSD_OK;
 }
 
 extern "C" int ssd_maxpool3x3s2(const float *in_dev, int32_t B, int32_t H, int32_t W, int32_t C, float *out_dev, void *stream)
@@ -437,25 +356,19 @@ extern "C" int ssd_concat_shuffle_split(const float *x_dev, const float *y_dev, 
 {
     if (!x_dev || !y_dev || !xo_dev || !yo_dev || rows < 1 || D < 1) return ssd_fail(SSD_ERR_INVALID, "ssd_concat_shuffle_split: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    DevPool pool;
-    auto body = [&]() -> int {
-        std::vector<int> tx(2 * D), ty(2 * D);
-        for (int j = 0; j < D; ++j) {
-            const int zx = j, zy = D + j;
-            tx[2 * j] = zx & 1; tx[2 * j + 1] = zx >> 1;
-            ty[2 * j] = zy & 1; ty[2 * j + 1] = zy >> 1;
-        }
-        int *dx, *dy;
-        SSDCHK(pool.upload(&dx, tx)); SSDCHK(pool.upload(&dy, ty));
-        HIPCHK(launch_gather_channels(x_dev, D, y_dev, D, rows, dx, D, xo_dev, s));
-        HIPCHK(launch_gather_channels(x_dev, D, y_dev, D, rows, dy, D, yo_dev, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return SSD_OK;
-    };
-    int rc = body();
-    (void)hipStreamSynchronize(s);
-    pool.free_all();
-    return rc;
+    StagePool pool(s);
+    std::vector<int> tx(2 * D), ty(2 * D);
+    for (int j = 0; j < D; ++j) {
+        const int zx = j, zy = D + j;
+        tx[2 * j] = zx & 1; tx[2 * j + 1] = zx >> 1;
+        ty[2 * j] = zy & 1; ty[2 * j + 1] = zy >> 1;
+    }
+    int *dx, *dy;
+    SSDCHK(pool.upload(&dx, tx)); SSDCHK(pool.upload(&dy, ty));
+    HIPCHK(launch_gather_channels(x_dev, D, y_dev, D, rows, dx, D, xo_dev, s));
+    HIPCHK(launch_gather_channels(x_dev, D, y_dev, D, rows, dy, D, yo_dev, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SSD_OK;
 }
 
 // concat_shuffle_split (shufflenet_v2.py:94-115) followed by the unit's conv1x1_before + batch norm + activation (:119) on the new x
@@ -468,40 +381,32 @@ extern "C" int ssd_shuffle_conv1x1(const float *x_dev, const float *y_dev, int64
     if (!x_dev || !y_dev || !w_host || !bn_mean_host || !bn_sf_host || !bn_beta_host || !out_dev || rows < 1 || D < 2 || (D & 1) || Cout < 1)
         return ssd_fail(SSD_ERR_INVALID, "ssd_shuffle_conv1x1: bad arguments (even D, batch norm required)");
     hipStream_t s = (hipStream_t)stream;
-    DevPool pool;
-    auto body = [&]() -> int {
-        const int Dp = round_up(D, 32), CoutP = round_up(Cout, 32);
-        std::vector<int> inmap = phys_map(D, Dp), outmap = phys_map(Cout, CoutP);
-        ConvW cw;
-        SSDCHK(pack_conv(nullptr, pool, w_host, 1, D, Cout, inmap, outmap, cw));
-        BnHost b;
-        for (int p : outmap) { b.mean.push_back(p < 0 ? 0.f : bn_mean_host[p]); b.sf.push_back(p < 0 ? 0.f : bn_sf_host[p]); b.beta.push_back(p < 0 ? 0.f : bn_beta_host[p]); }
-        SSDCHK(upload_bn(pool, b, cw));
-        // one allocation [x | y], both in physical channel order
-        const long long tbytes = rows * Dp * 4;
-        if (!pw_gather_supports(Dp, CoutP, rows, Dp * 4, 2 * tbytes, rows * CoutP * 4))
-            return ssd_fail(SSD_ERR_INVALID, "ssd_shuffle_conv1x1: shape not supported by the gathering kernel (D <= 512, tensors below 2 GiB)");
-        float *xy, *tout;
-        SSDCHK(pool.alloc((void **)&xy, (size_t)(2 * tbytes)));
-        SSDCHK(pool.alloc((void **)&tout, (size_t)rows * CoutP * 4));
-        HIPCHK(launch_permute_channels(x_dev, rows, D, Dp, 1, xy, s));
-        HIPCHK(launch_permute_channels(y_dev, rows, D, Dp, 1, xy + rows * Dp, s));
-        // new x = z[0 : D] of z[2d] = x[d], z[2d + 1] = y[d]: input channel k comes from (k & 1 ? y : x)[k >> 1]
-        std::vector<int> src(Dp, -1);
-        for (int k = 0; k < D; ++k)
-            src[ssd_phys_of_logical(k)] = (int)((k & 1 ? tbytes : 0) + (long long)ssd_phys_of_logical(k >> 1) * 4);
-        int *src_dev;
-        SSDCHK(pool.upload(&src_dev, src));
-        Op op = make_pw_gather_op(cw, xy, 2 * tbytes, src_dev, Dp * 4, rows, act, tout);
-        HIPCHK(op.run(s));
-        HIPCHK(launch_permute_channels(tout, rows, Cout, CoutP, 0, out_dev, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return SSD_OK;
-    };
-    int rc = body();
-    (void)hipStreamSynchronize(s);
-    pool.free_all();
-    return rc;
+    StagePool pool(s);
+    const int Dp = round_up(D, 32), CoutP = round_up(Cout, 32);
+    std::vector<int> inmap = phys_map(D, Dp), outmap = phys_map(Cout, CoutP);
+    ConvW cw;
+    SSDCHK(pack_conv(nullptr, pool, w_host, 1, D, Cout, inmap, outmap, cw));
+    SSDCHK(upload_bn(pool, permute_bn(bn_mean_host, bn_sf_host, bn_beta_host, outmap), cw));
+    // one allocation [x | y], both in physical channel order
+    const long long tbytes = rows * Dp * 4;
+    if (!pw_gather_supports(Dp, CoutP, rows, Dp * 4, 2 * tbytes, rows * CoutP * 4))
+        return ssd_fail(SSD_ERR_INVALID, "ssd_shuffle_conv1x1: shape not supported by the gathering kernel (D <= 512, tensors below 2 GiB)");
+    float *xy, *tout;
+    SSDCHK(pool.alloc((void **)&xy, (size_t)(2 * tbytes)));
+    SSDCHK(pool.alloc((void **)&tout, (size_t)rows * CoutP * 4));
+    HIPCHK(launch_permute_channels(x_dev, rows, D, Dp, 1, xy, s));
+    HIPCHK(launch_permute_channels(y_dev, rows, D, Dp, 1, xy + rows * Dp, s));
+    // new x = z[0 : D] of z[2d] = x[d], z[2d + 1] = y[d]: input channel k comes from (k & 1 ? y : x)[k >> 1]
+    std::vector<int> src(Dp, -1);
+    for (int k = 0; k < D; ++k)
+        src[ssd_phys_of_logical(k)] = (int)((k & 1 ? tbytes : 0) + (long long)ssd_phys_of_logical(k >> 1) * 4);
+    int *src_dev;
+    SSDCHK(pool.upload(&src_dev, src));
+    Op op = make_pw_gather_op(cw, xy, 2 * tbytes, src_dev, Dp * 4, rows, act, tout);
+    HIPCHK(op.run(s));
+    HIPCHK(launch_permute_channels(tout, rows, Cout, CoutP, 0, out_dev, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SSD_OK;
 }
 
 extern "C" size_t ssd_postprocess_workspace_bytes(int32_t B, int32_t N, int32_t C, int32_t mp)
@@ -545,7 +450,7 @@ extern "C" int ssd_bench_conv(int32_t B, int32_t H, int32_t W, int32_t Cin, int3
 {
     if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (k != 1 && k != 3) || reps < 1 || !avg_ms)
         return ssd_fail(SSD_ERR_INVALID, "ssd_bench_conv: bad arguments");
-    DevPool pool;
+    StagePool pool(nullptr);        // (everything below is enqueued on the null stream, which the pool drains)
     auto body = [&]() -> int {
         const int CinP = round_up(Cin, 32), CoutP = round_up(Cout, 8);
         std::vector<float> w((size_t)k * k * Cin * Cout);
@@ -630,11 +535,9 @@ extern "C" int ssd_bench_conv(int32_t B, int32_t H, int32_t W, int32_t Cin, int3
         (void)hipEventDestroy(e1);
         return SSD_OK;
     };
-    int rc = body();
+    const int rc = body();
     g_force_tile = -1;
     g_dbg_ts = nullptr;
-    (void)hipDeviceSynchronize();
-    pool.free_all();
     return rc;
 }
 
@@ -643,78 +546,72 @@ extern "C" int ssd_bench_dwpw(int32_t B, int32_t H, int32_t W, int32_t C, int32_
 {
     if (B < 1 || H < 1 || W < 1 || C < 1 || Cout < 1 || (stride != 1 && stride != 2) || reps < 1 || !avg_ms)
         return ssd_fail(SSD_ERR_INVALID, "ssd_bench_dwpw: bad arguments");
-    DevPool pool;
-    auto body = [&]() -> int {
-        const int Cp = round_up(C, 32), CoutP = round_up(Cout, 8);
-        unsigned st = 777u;
-        auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xFFFF) / 65536.0f - 0.5f; };
-        std::vector<int> map = phys_map(C, Cp), outmap = phys_map(Cout, CoutP);
-        DwW d;
-        d.Cp = Cp;
-        std::vector<float> wt((size_t)9 * Cp), m(Cp, 0.01f), sf(Cp, 1.01f), be(Cp, 0.02f);
-        for (auto &v : wt) v = rnd();
-        SSDCHK(pool.upload(&d.w, wt)); SSDCHK(pool.upload(&d.mean, m)); SSDCHK(pool.upload(&d.sf, sf)); SSDCHK(pool.upload(&d.beta, be));
-        SSDCHK(pack_dw(pool, wt, m, sf, be, d));
-        std::vector<float> w((size_t)C * Cout);
-        for (auto &v : w) v = rnd() * 0.1f;
-        ConvW cw;
-        SSDCHK(pack_conv(nullptr, pool, w.data(), 1, C, Cout, map, outmap, cw));
-        BnHost b;
-        for (int c = 0; c < CoutP; ++c) { b.mean.push_back(0.01f); b.sf.push_back(1.0f); b.beta.push_back(0.02f); }
-        SSDCHK(upload_bn(pool, b, cw));
-        const int OH = H / stride, OW = W / stride;
-        float *in, *mid, *out;
-        const long long nin = (long long)B * H * W * Cp;
-        SSDCHK(pool.alloc((void **)&in, (size_t)nin * 4));
-        SSDCHK(pool.alloc((void **)&mid, (size_t)B * OH * OW * Cp * 4));
-        SSDCHK(pool.alloc((void **)&out, (size_t)B * OH * OW * CoutP * 4));
-        {
-            std::vector<float> hin((size_t)nin);
-            for (auto &v : hin) v = rnd();
-            HIPCHK(hipMemcpy(in, hin.data(), hin.size() * 4, hipMemcpyHostToDevice));
-        }
-        std::vector<Op> ops;
-        if (fused == 1) {          // the streaming kernel (dwpw_stream.hip)
-            if (!dwpws_eligible(d, cw, B, H, W, stride)) return ssd_fail(SSD_ERR_INVALID, "ssd_bench_dwpw: shape not supported by the streaming kernel");
-            ops.push_back(make_dwpws_op(d, cw, in, B, H, W, stride, SSD_ACT_RELU6, SSD_ACT_RELU6, out));
-        } else if (fused) {
-            return ssd_fail(SSD_ERR_INVALID, "ssd_bench_dwpw: fused must be 0 (two kernels) or 1 (dwpw_stream.hip)");
-        } else {
-            ops.push_back(make_dw_op(d, in, B, H, W, stride, SSD_ACT_RELU6, mid, C));
-            ops.push_back(make_conv_op(nullptr, cw, {mid, out}, B, 1, 0, SSD_ACT_RELU6, {dense_level(OH, OW, OH, OW, CoutP)}, true));
-        }
-        const char *dump = getenv("SSD_TS_DUMP");
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        for (int i = 0; i < 2; ++i) for (auto &op : ops) HIPCHK(op.run(nullptr));
-        HIPCHK(hipEventRecord(e0, nullptr));
-        for (int i = 0; i < reps; ++i) for (auto &op : ops) HIPCHK(op.run(nullptr));
-        HIPCHK(hipEventRecord(e1, nullptr));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        *avg_ms = ms / reps;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (fused == 1 && dump) {   // phase cycle totals of one extra launch of the streaming kernel -> $SSD_TS_DUMP (int64[512][8])
-            long long *t8 = nullptr;
-            SSDCHK(pool.alloc((void **)&t8, 512 * 8 * 8));
-            HIPCHK(hipMemset(t8, 0, 512 * 8 * 8));
-            g_dbg_ts = t8;
-            Op op = make_dwpws_op(d, cw, in, B, H, W, stride, SSD_ACT_RELU6, SSD_ACT_RELU6, out);
-            g_dbg_ts = nullptr;
-            HIPCHK(op.run(nullptr));
-            HIPCHK(hipDeviceSynchronize());
-            std::vector<long long> hts(512 * 8);
-            HIPCHK(hipMemcpy(hts.data(), t8, hts.size() * 8, hipMemcpyDeviceToHost));
-            if (FILE *f = fopen(dump, "wb")) { fwrite(hts.data(), 8, hts.size(), f); fclose(f); }
-        }
-        return SSD_OK;
-    };
-    int rc = body();
-    (void)hipDeviceSynchronize();
-    pool.free_all();
-    return rc;
+    StagePool pool(nullptr);        // (everything below is enqueued on the null stream)
+    const int Cp = round_up(C, 32), CoutP = round_up(Cout, 8);
+    unsigned st = 777u;
+    auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xFFFF) / 65536.0f - 0.5f; };
+    std::vector<int> map = phys_map(C, Cp), outmap = phys_map(Cout, CoutP);
+    DwW d;
+    d.Cp = Cp;
+    std::vector<float> wt((size_t)9 * Cp);
+    const BnHost db{std::vector<float>(Cp, 0.01f), std::vector<float>(Cp, 1.01f), std::vector<float>(Cp, 0.02f)};
+    for (auto &v : wt) v = rnd();
+    SSDCHK(upload_dw(pool, wt, db, d));
+    std::vector<float> w((size_t)C * Cout);
+    for (auto &v : w) v = rnd() * 0.1f;
+    ConvW cw;
+    SSDCHK(pack_conv(nullptr, pool, w.data(), 1, C, Cout, map, outmap, cw));
+    BnHost b;
+    for (int c = 0; c < CoutP; ++c) { b.mean.push_back(0.01f); b.sf.push_back(1.0f); b.beta.push_back(0.02f); }
+    SSDCHK(upload_bn(pool, b, cw));
+    const int OH = H / stride, OW = W / stride;
+    float *in, *mid, *out;
+    const long long nin = (long long)B * H * W * Cp;
+    SSDCHK(pool.alloc((void **)&in, (size_t)nin * 4));
+    SSDCHK(pool.alloc((void **)&mid, (size_t)B * OH * OW * Cp * 4));
+    SSDCHK(pool.alloc((void **)&out, (size_t)B * OH * OW * CoutP * 4));
+    {
+        std::vector<float> hin((size_t)nin);
+        for (auto &v : hin) v = rnd();
+        HIPCHK(hipMemcpy(in, hin.data(), hin.size() * 4, hipMemcpyHostToDevice));
+    }
+    std::vector<Op> ops;
+    if (fused == 1) {          // the streaming kernel (dwpw_stream.hip)
+        if (!dwpws_eligible(d, cw, B, H, W, stride)) return ssd_fail(SSD_ERR_INVALID, "ssd_bench_dwpw: shape not supported by the streaming kernel");
+        ops.push_back(make_dwpws_op(d, cw, in, B, H, W, stride, SSD_ACT_RELU6, SSD_ACT_RELU6, out));
+    } else if (fused) {
+        return ssd_fail(SSD_ERR_INVALID, "ssd_bench_dwpw: fused must be 0 (two kernels) or 1 (dwpw_stream.hip)");
+    } else {
+        ops.push_back(make_dw_op(d, in, B, H, W, stride, SSD_ACT_RELU6, mid, C));
+        ops.push_back(make_conv_op(nullptr, cw, {mid, out}, B, 1, 0, SSD_ACT_RELU6, {dense_level(OH, OW, OH, OW, CoutP)}, true));
+    }
+    const char *dump = getenv("SSD_TS_DUMP");
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    for (int i = 0; i < 2; ++i) for (auto &op : ops) HIPCHK(op.run(nullptr));
+    HIPCHK(hipEventRecord(e0, nullptr));
+    for (int i = 0; i < reps; ++i) for (auto &op : ops) HIPCHK(op.run(nullptr));
+    HIPCHK(hipEventRecord(e1, nullptr));
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    *avg_ms = ms / reps;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (fused == 1 && dump) {   // phase cycle totals of one extra launch of the streaming kernel -> $SSD_TS_DUMP (int64[512][8])
+        long long *t8 = nullptr;
+        SSDCHK(pool.alloc((void **)&t8, 512 * 8 * 8));
+        HIPCHK(hipMemset(t8, 0, 512 * 8 * 8));
+        g_dbg_ts = t8;
+        Op op = make_dwpws_op(d, cw, in, B, H, W, stride, SSD_ACT_RELU6, SSD_ACT_RELU6, out);
+        g_dbg_ts = nullptr;
+        HIPCHK(op.run(nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        std::vector<long long> hts(512 * 8);
+        HIPCHK(hipMemcpy(hts.data(), t8, hts.size() * 8, hipMemcpyDeviceToHost));
+        if (FILE *f = fopen(dump, "wb")) { fwrite(hts.data(), 8, hts.size(), f); fclose(f); }
+    }
+    return SSD_OK;
 }
 #endif  // SSD_DIAG

@@ -16,8 +16,6 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 static inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
 // ----------------------------------------------------------------------------- kernel packing on the device
-static __device__ inline int d_logical_of_phys(int p) { const int o = p & ~7, r = p & 7; return o + (r < 4 ? 2 * r : 2 * (r - 4) + 1); }
-
 // w HWIO [3,3,Cin,Cout] (device) -> wt [9][rows][kp] in physical channel order, zero where a channel is padding.
 //   transpose == 0  the forward's kernel: row = output channel co, k = input channel ci, tap as stored
 //   transpose == 1  the data gradient's kernel w'[kh,kw,co,ci] = w[2-kh,2-kw,ci,co]: row = ci, k = co, tap 8 - tap
@@ -26,7 +24,7 @@ __global__ __launch_bounds__(256) void pack_w_kernel(const float *w, int Cin, in
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= 9LL * rows * kp) return;
     const int p = (int)(idx % kp), n = (int)((idx / kp) % rows), tap = (int)(idx / ((long long)kp * rows));
-    const int lk = d_logical_of_phys(p), ln = d_logical_of_phys(n);
+    const int lk = ssd_logical_of_phys(p), ln = ssd_logical_of_phys(n);
     float v = 0.0f;
     if (!transpose) {
         if (lk < Cin && ln < Cout) v = w[((long long)tap * Cin + lk) * Cout + ln];
@@ -236,18 +234,6 @@ struct ConvTrainPlan {
     size_t off_a, off_b, off_w, off_bias, off_part, off_stat, bytes;
 };
 
-static void conv_geometry(int Cin, int Cout, ConvW &cw)
-{
-    cw = ConvW();
-    cw.taps = 9;
-    cw.CinP = round_up(Cin, 32);
-    cw.CoutP = round_up(Cout, 8);
-    cw.tile = conv_pick_tile(nullptr, cw.CoutP);
-    cw.CoutPad = round_up(cw.CoutP, igemm_tile_bn(cw.tile));
-    cw.Cin_l = Cin;
-    cw.Cout_l = Cout;
-}
-
 static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, int Cout, ConvTrainPlan &p)
 {
     if (!lv) return "null level list";
@@ -255,8 +241,8 @@ static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, in
     if (B < 1 || Cin < 1 || Cout < 1) return "sizes must be positive";
     if (Cin % 8) return "Cin must be a multiple of 8";
     if (Cin > 4096 || Cout > 4096) return "at most 4096 channels";
-    conv_geometry(Cin, Cout, p.f);
-    conv_geometry(Cout, Cin, p.d);
+    conv_geometry(nullptr, 9, round_up(Cin, 32), round_up(Cout, 8), Cin, Cout, p.f);
+    conv_geometry(nullptr, 9, round_up(Cout, 32), round_up(Cin, 8), Cout, Cin, p.d);
     const int widest = std::max(std::max(p.f.CinP, p.f.CoutP), std::max(p.d.CinP, p.d.CoutP));
     p.Rtot = 0;
     for (int l = 0; l < n; ++l) {

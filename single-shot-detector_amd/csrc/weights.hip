@@ -35,18 +35,41 @@ std::vector<int> twopart_map(int D, int Dp)
     return m;
 }
 
-// batch_norm_relu (layer_utils.py:5-12): sf = gamma * rsqrt(var + 1e-3)
-static void bn_pack(const float *gamma, const float *beta, const float *mean, const float *var,
+// rows [rows][C] in logical channel order -> [rows][map.size()] in the order of `map`, pad channels zero: THE place where a
+// weight tensor takes the physical channel order (ssd_internal.h); the width and the map are the caller's
+std::vector<float> permute_rows(const float *w, int rows, int C, const std::vector<int> &map)
+{
+    const size_t Cp = map.size();
+    std::vector<float> t((size_t)rows * Cp, 0.0f);
+    for (int r = 0; r < rows; ++r)
+        for (size_t p = 0; p < Cp; ++p)
+            if (map[p] >= 0) t[r * Cp + p] = w[(size_t)r * C + map[p]];
+    return t;
+}
+
+// ... and a batch norm's three vectors, appended to `o` (mean == nullptr, a layer without batch norm: nothing)
+BnHost permute_bn(const float *mean, const float *sf, const float *beta, const std::vector<int> &map, BnHost o)
+{
+    if (!mean) return o;
+    for (int p : map) {
+        o.mean.push_back(p < 0 ? 0.f : mean[p]);
+        o.sf.push_back(p < 0 ? 0.f : sf[p]);
+        o.beta.push_back(p < 0 ? 0.f : beta[p]);
+    }
+    return o;
+}
+
+// batch_norm_relu (layer_utils.py:5-12): sf = gamma * rsqrt(var + 1e-3); appended to `o` (the head towers: one batch norm per level)
+static void bn_pack(const float *gamma, const float *beta, const float *mean, const float *var, int C,
                     const std::vector<int> &outmap, BnHost &o)
 {
     const float eps = 1e-3f;
-    for (int p : outmap) {
-        if (p < 0) { o.mean.push_back(0.f); o.sf.push_back(0.f); o.beta.push_back(0.f); continue; }
-        o.mean.push_back(mean[p]);
-        float s = 1.0f / sqrtf(var[p] + eps);
-        o.sf.push_back(gamma[p] * s);
-        o.beta.push_back(beta[p]);
+    std::vector<float> sf(C);
+    for (int c = 0; c < C; ++c) {
+        float s = 1.0f / sqrtf(var[c] + eps);
+        sf[c] = gamma[c] * s;
     }
+    o = permute_bn(mean, sf.data(), beta, outmap, std::move(o));
 }
 
 static int pick_tile(const ssd_handle *h, int CoutP)
@@ -59,19 +82,24 @@ static int pick_tile(const ssd_handle *h, int CoutP)
     return IGEMM_128x128;
 }
 
-int conv_pick_tile(const ssd_handle *h, int CoutP) { return pick_tile(h, CoutP); }
+// The geometry of a packed kernel of these padded widths: what pack_conv fills below and what train_head.hip, which packs on the
+// device, must agree with.  (g_force_tile: -1 in the shipped library; in the SSD_DIAG build non-negative only inside ssd_bench_conv.)
+void conv_geometry(const ssd_handle *h, int taps, int CinP, int CoutP, int Cin_l, int Cout_l, ConvW &cw)
+{
+    cw.taps = taps;
+    cw.CinP = CinP;
+    cw.CoutP = CoutP;
+    cw.tile = g_force_tile >= 0 ? g_force_tile : pick_tile(h, cw.CoutP);
+    cw.CoutPad = round_up(cw.CoutP, igemm_tile_bn(cw.tile));
+    cw.Cin_l = Cin_l;
+    cw.Cout_l = Cout_l;
+}
 
 // w: HWIO [k,k,Cin_l,Cout_l] -> wt [taps][CoutPad][CinP]
 int pack_conv(const ssd_handle *h, DevPool &pool, const float *w, int k, int Cin_l, int Cout_l, const std::vector<int> &inmap,
                      const std::vector<int> &outmap, ConvW &cw)
 {
-    cw.taps = k * k;
-    cw.CinP = (int)inmap.size();
-    cw.CoutP = (int)outmap.size();
-    cw.tile = g_force_tile >= 0 ? g_force_tile : pick_tile(h, cw.CoutP);
-    cw.CoutPad = round_up(cw.CoutP, igemm_tile_bn(cw.tile));
-    cw.Cin_l = Cin_l;
-    cw.Cout_l = Cout_l;
+    conv_geometry(h, k * k, (int)inmap.size(), (int)outmap.size(), Cin_l, Cout_l, cw);
     std::vector<float> t((size_t)cw.taps * cw.CoutPad * cw.CinP, 0.0f);
     for (int tap = 0; tap < cw.taps; ++tap)
         for (int n = 0; n < cw.CoutP; ++n) {
@@ -140,21 +168,31 @@ int upload_bn(DevPool &pool, const BnHost &b, ConvW &cw)
     return pool.upload(&cw.beta, b.beta);
 }
 
-// slice-major copy of a depthwise layer's parameters for the streaming fused kernel
-int pack_dw(DevPool &pool, const std::vector<float> &w9, const std::vector<float> &mean, const std::vector<float> &sf,
-                   const std::vector<float> &beta, DwW &d)
+// slice-major copy of a depthwise layer's parameters for the streaming fused kernel (which always has a batch norm)
+int pack_dw(DevPool &pool, const std::vector<float> &w9, const BnHost &b, DwW &d)
 {
-    if (d.Cp % 32) return SSD_OK;
+    if (d.Cp % 32 || b.mean.empty()) return SSD_OK;
     const int KC = d.Cp / 32;
     std::vector<float> p((size_t)KC * 12 * 32);
     for (int s = 0; s < KC; ++s)
         for (int c = 0; c < 32; ++c) {
             for (int t = 0; t < 9; ++t) p[((size_t)s * 12 + t) * 32 + c] = w9[(size_t)t * d.Cp + s * 32 + c];
-            p[((size_t)s * 12 + 9) * 32 + c] = mean[s * 32 + c];
-            p[((size_t)s * 12 + 10) * 32 + c] = sf[s * 32 + c];
-            p[((size_t)s * 12 + 11) * 32 + c] = beta[s * 32 + c];
+            p[((size_t)s * 12 + 9) * 32 + c] = b.mean[s * 32 + c];
+            p[((size_t)s * 12 + 10) * 32 + c] = b.sf[s * 32 + c];
+            p[((size_t)s * 12 + 11) * 32 + c] = b.beta[s * 32 + c];
         }
     return pool.upload(&d.pack, p);
+}
+
+// a depthwise layer's (9 taps) or a first convolution's (27) rows over d.Cp channels and its batch norm: one upload per non-empty
+// vector (a stage call may come without batch norm), and behind nine taps the pack
+int upload_dw(DevPool &pool, const std::vector<float> &w, const BnHost &b, DwW &d)
+{
+    if (!w.empty()) SSDCHK(pool.upload(&d.w, w));
+    if (!b.mean.empty()) SSDCHK(pool.upload(&d.mean, b.mean));
+    if (!b.sf.empty()) SSDCHK(pool.upload(&d.sf, b.sf));
+    if (!b.beta.empty()) SSDCHK(pool.upload(&d.beta, b.beta));
+    return w.size() == (size_t)9 * d.Cp ? pack_dw(pool, w, b, d) : SSD_OK;
 }
 
 static const Tensor *getvar(ssd_handle *h, const std::string &n, std::initializer_list<int64_t> shape)
@@ -179,7 +217,7 @@ static int get_bn(ssd_handle *h, const std::string &scope, int C, const std::vec
     const Tensor *g = getvar(h, scope + "/gamma", {C}), *b = getvar(h, scope + "/beta", {C});
     const Tensor *m = getvar(h, scope + "/moving_mean", {C}), *v = getvar(h, scope + "/moving_variance", {C});
     if (!g || !b || !m || !v) return SSD_ERR_WEIGHT;
-    bn_pack(g->data.data(), b->data.data(), m->data.data(), v->data.data(), outmap, o);
+    bn_pack(g->data.data(), b->data.data(), m->data.data(), v->data.data(), C, outmap, o);
     return SSD_OK;
 }
 
@@ -207,17 +245,9 @@ static int load_dw(ssd_handle *h, const std::string &scope, const std::string &b
     if (!w) return SSD_ERR_WEIGHT;
     d.Cp = in_split > 0 ? 2 * round_up(in_split, 32) : round_up(C, 32);
     std::vector<int> map = in_split > 0 ? twopart_map(in_split, round_up(in_split, 32)) : phys_map(C, d.Cp);
-    std::vector<float> t((size_t)9 * d.Cp, 0.0f);
-    for (int tap = 0; tap < 9; ++tap)
-        for (int p = 0; p < d.Cp; ++p)
-            if (map[p] >= 0) t[(size_t)tap * d.Cp + p] = w->data[(size_t)tap * C + map[p]];
-    SSDCHK(h->wpool.upload(&d.w, t));
     BnHost b;
     SSDCHK(get_bn(h, scope + "/" + bnname, C, map, b));
-    SSDCHK(h->wpool.upload(&d.mean, b.mean));
-    SSDCHK(h->wpool.upload(&d.sf, b.sf));
-    SSDCHK(h->wpool.upload(&d.beta, b.beta));
-    return pack_dw(h->wpool, t, b.mean, b.sf, b.beta, d);
+    return upload_dw(h->wpool, permute_rows(w->data.data(), 9, C, map), b, d);
 }
 
 static int load_first(ssd_handle *h, const std::string &scope, const std::string &bnname, int Cout)
@@ -226,19 +256,10 @@ static int load_first(ssd_handle *h, const std::string &scope, const std::string
     if (!w) return SSD_ERR_WEIGHT;
     const int Cp = round_up(Cout, 32);
     std::vector<int> map = phys_map(Cout, Cp);
-    std::vector<float> t((size_t)27 * Cp, 0.0f);
-    for (int r = 0; r < 27; ++r)
-        for (int p = 0; p < Cp; ++p)
-            if (map[p] >= 0) t[(size_t)r * Cp + p] = w->data[(size_t)r * Cout + map[p]];
-    SSDCHK(h->wpool.upload(&h->first.w, t));
+    h->first.Cp = h->firstCp = Cp;
     BnHost b;
     SSDCHK(get_bn(h, scope + "/" + bnname, Cout, map, b));
-    SSDCHK(h->wpool.upload(&h->first.mean, b.mean));
-    SSDCHK(h->wpool.upload(&h->first.sf, b.sf));
-    SSDCHK(h->wpool.upload(&h->first.beta, b.beta));
-    h->first.Cp = Cp;
-    h->firstCp = Cp;
-    return SSD_OK;
+    return upload_dw(h->wpool, permute_rows(w->data.data(), 27, Cout, map), b, h->first);
 }
 
 // mobilenet_v1.py:52-58

@@ -29,12 +29,24 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _w(w):
+    """host weights -> (contiguous float32 array, its ctypes float pointer); the array keeps the pointer alive."""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    return w, w.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
 def _fp(a):
-    """host float32 array (or None) -> ctypes float pointer (keeps `a` alive via return)."""
-    if a is None:
-        return None, None
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    """_w for an optional array: None -> (None, None)."""
+    return (None, None) if a is None else _w(a)
+
+
+def _bn(bn, optional=False):
+    """bn = (mean, sf, beta) host arrays (None where `optional`: no batch norm) -> their three float pointers and, last, the
+    arrays that keep them alive."""
+    if bn is None and optional:
+        bn = (None, None, None)
+    keep = [_fp(v) for v in bn]
+    return keep[0][1], keep[1][1], keep[2][1], keep
 
 
 def _check_dev(torch, t, dtype, name):
@@ -57,7 +69,7 @@ def conv2d(x, w, stride=1, mode="SAME", bn=None, bias=None, up=None, act=None, p
     x [B,H,W,Cin] cuda f32; w HWIO numpy; bn = (mean, sf, beta) numpy; up = coarser map."""
     torch = _torch()
     _check_dev(torch, x, torch.float32, "x")
-    w = np.ascontiguousarray(w, dtype=np.float32)
+    w, wp = _w(w)
     B, H, W, Cin = x.shape
     k, k2, cin2, Cout = w.shape
     if k != k2 or cin2 != Cin:
@@ -65,15 +77,14 @@ def conv2d(x, w, stride=1, mode="SAME", bn=None, bias=None, up=None, act=None, p
     OH, pb = out_size(H, k, stride, mode)
     OW, _ = out_size(W, k, stride, mode)
     out = torch.empty((B, OH, OW, Cout), dtype=torch.float32, device=x.device)
-    keep = [_fp(v) for v in (bn if bn is not None else (None, None, None))]
+    mean, sf, beta, _keep = _bn(bn, optional=True)
     kb = _fp(bias)
     if up is not None:
         _check_dev(torch, up, torch.float32, "up")
         if tuple(up.shape) != (B, OH // 2, OW // 2, Cout):
             raise ValueError("up must have shape [B, OH/2, OW/2, Cout]")
     fn = {"f32": lib().ssd_conv2d, "f16x3": lib().ssd_conv2d_f16x3}[precision]
-    check(fn(_ptr(x), B, H, W, Cin, w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-             k, Cout, stride, pb, OH, OW, keep[0][1], keep[1][1], keep[2][1], kb[1],
+    check(fn(_ptr(x), B, H, W, Cin, wp, k, Cout, stride, pb, OH, OW, mean, sf, beta, kb[1],
              _ptr(up) if up is not None else None, ACT[act], _ptr(out), _stream(torch)))
     return out
 
@@ -81,16 +92,15 @@ def conv2d(x, w, stride=1, mode="SAME", bn=None, bias=None, up=None, act=None, p
 def depthwise3x3(x, w, stride=1, bn=None, act=None):
     torch = _torch()
     _check_dev(torch, x, torch.float32, "x")
-    w = np.ascontiguousarray(w, dtype=np.float32)
+    w, wp = _w(w)
     B, H, W, C = x.shape
     if w.shape != (3, 3, C, 1):
         raise ValueError("depthwise weights must be [3,3,C,1]")
     OH, pb = out_size(H, 3, stride, "SAME")
     OW, _ = out_size(W, 3, stride, "SAME")
     out = torch.empty((B, OH, OW, C), dtype=torch.float32, device=x.device)
-    keep = [_fp(v) for v in (bn if bn is not None else (None, None, None))]
-    check(lib().ssd_depthwise3x3(_ptr(x), B, H, W, C, w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                 stride, pb, OH, OW, keep[0][1], keep[1][1], keep[2][1], ACT[act],
+    mean, sf, beta, _keep = _bn(bn, optional=True)
+    check(lib().ssd_depthwise3x3(_ptr(x), B, H, W, C, wp, stride, pb, OH, OW, mean, sf, beta, ACT[act],
                                  _ptr(out), _stream(torch)))
     return out
 
@@ -100,8 +110,8 @@ def dw_pw(x, dw_w, stride, dw_bn, dw_act, pw_w, pw_bn, pw_act):
     bn arguments are (mean, scale_factor, beta) as for conv2d; both are required."""
     torch = _torch()
     _check_dev(torch, x, torch.float32, "x")
-    dw_w = np.ascontiguousarray(dw_w, dtype=np.float32)
-    pw_w = np.ascontiguousarray(pw_w, dtype=np.float32)
+    dw_w, dwp = _w(dw_w)
+    pw_w, pwp = _w(pw_w)
     B, H, W, C = x.shape
     if dw_w.shape != (3, 3, C, 1) or pw_w.shape[:3] != (1, 1, C):
         raise ValueError("weights must be [3,3,C,1] and [1,1,C,Cout]")
@@ -109,11 +119,8 @@ def dw_pw(x, dw_w, stride, dw_bn, dw_act, pw_w, pw_bn, pw_act):
     OH, _ = out_size(H, 3, stride, "SAME")
     OW, _ = out_size(W, 3, stride, "SAME")
     out = torch.empty((B, OH, OW, Cout), dtype=torch.float32, device=x.device)
-    kd = [_fp(v) for v in dw_bn]
-    kp = [_fp(v) for v in pw_bn]
-    fp = ctypes.POINTER(ctypes.c_float)
-    check(lib().ssd_dw_pw(_ptr(x), B, H, W, C, dw_w.ctypes.data_as(fp), stride, kd[0][1], kd[1][1], kd[2][1],
-                          ACT[dw_act], pw_w.ctypes.data_as(fp), Cout, kp[0][1], kp[1][1], kp[2][1], ACT[pw_act],
+    kd, kp = _bn(dw_bn), _bn(pw_bn)
+    check(lib().ssd_dw_pw(_ptr(x), B, H, W, C, dwp, stride, *kd[:3], ACT[dw_act], pwp, Cout, *kp[:3], ACT[pw_act],
                           _ptr(out), _stream(torch)))
     return out
 
@@ -121,16 +128,14 @@ def dw_pw(x, dw_w, stride, dw_bn, dw_act, pw_w, pw_bn, pw_act):
 def first_conv(images, w, bn=None, act=None):
     torch = _torch()
     _check_dev(torch, images, torch.uint8, "images")
-    w = np.ascontiguousarray(w, dtype=np.float32)
+    w, wp = _w(w)
     B, H, W, three = images.shape
     if three != 3 or w.shape[:3] != (3, 3, 3):
         raise ValueError("images must be [B,H,W,3] and weights [3,3,3,Cout]")
     Cout = w.shape[3]
     out = torch.empty((B, H // 2, W // 2, Cout), dtype=torch.float32, device=images.device)
-    keep = [_fp(v) for v in (bn if bn is not None else (None, None, None))]
-    check(lib().ssd_first_conv(_ptr(images), B, H, W, w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                               Cout, keep[0][1], keep[1][1], keep[2][1], ACT[act], _ptr(out),
-                               _stream(torch)))
+    mean, sf, beta, _keep = _bn(bn, optional=True)
+    check(lib().ssd_first_conv(_ptr(images), B, H, W, wp, Cout, mean, sf, beta, ACT[act], _ptr(out), _stream(torch)))
     return out
 
 
@@ -139,9 +144,9 @@ def front_block(images, w0, bn0, act0, dw_w, dw_bn, dw_act, pw_w, pw_bn, pw_act)
     stride 1, the 32-channel tensor kept on chip (mobilenet_v1.py:34-67).  Only 3 -> 32 -> 32 -> 64 channels."""
     torch = _torch()
     _check_dev(torch, images, torch.uint8, "images")
-    w0 = np.ascontiguousarray(w0, dtype=np.float32)
-    dw_w = np.ascontiguousarray(dw_w, dtype=np.float32)
-    pw_w = np.ascontiguousarray(pw_w, dtype=np.float32)
+    w0, w0p = _w(w0)
+    dw_w, dwp = _w(dw_w)
+    pw_w, pwp = _w(pw_w)
     B, H, W, three = images.shape
     if three != 3 or w0.shape[:3] != (3, 3, 3):
         raise ValueError("images must be [B,H,W,3] and the first weights [3,3,3,C0]")
@@ -150,14 +155,9 @@ def front_block(images, w0, bn0, act0, dw_w, dw_bn, dw_act, pw_w, pw_bn, pw_act)
         raise ValueError("weights must be [3,3,C0,1] and [1,1,C0,Cout]")
     Cout = pw_w.shape[3]
     out = torch.empty((B, H // 2, W // 2, Cout), dtype=torch.float32, device=images.device)
-    k0 = [_fp(v) for v in bn0]
-    kd = [_fp(v) for v in dw_bn]
-    kp = [_fp(v) for v in pw_bn]
-    fp = ctypes.POINTER(ctypes.c_float)
-    check(lib().ssd_front_block(_ptr(images), B, H, W, w0.ctypes.data_as(fp), C0, k0[0][1], k0[1][1], k0[2][1], ACT[act0],
-                                dw_w.ctypes.data_as(fp), kd[0][1], kd[1][1], kd[2][1], ACT[dw_act],
-                                pw_w.ctypes.data_as(fp), Cout, kp[0][1], kp[1][1], kp[2][1], ACT[pw_act],
-                                _ptr(out), _stream(torch)))
+    k0, kd, kp = _bn(bn0), _bn(dw_bn), _bn(pw_bn)
+    check(lib().ssd_front_block(_ptr(images), B, H, W, w0p, C0, *k0[:3], ACT[act0], dwp, *kd[:3], ACT[dw_act],
+                                pwp, Cout, *kp[:3], ACT[pw_act], _ptr(out), _stream(torch)))
     return out
 
 
@@ -166,15 +166,14 @@ def first_conv_maxpool(images, w, bn, act=None):
     shufflenet_v2.py:50-54).  Only 24 output channels, H and W multiples of 4."""
     torch = _torch()
     _check_dev(torch, images, torch.uint8, "images")
-    w = np.ascontiguousarray(w, dtype=np.float32)
+    w, wp = _w(w)
     B, H, W, three = images.shape
     if three != 3 or w.shape[:3] != (3, 3, 3):
         raise ValueError("images must be [B,H,W,3] and weights [3,3,3,Cout]")
     Cout = w.shape[3]
     out = torch.empty((B, H // 4, W // 4, Cout), dtype=torch.float32, device=images.device)
-    keep = [_fp(v) for v in bn]
-    check(lib().ssd_first_conv_maxpool(_ptr(images), B, H, W, w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                       Cout, keep[0][1], keep[1][1], keep[2][1], ACT[act], _ptr(out), _stream(torch)))
+    mean, sf, beta, _keep = _bn(bn)
+    check(lib().ssd_first_conv_maxpool(_ptr(images), B, H, W, wp, Cout, mean, sf, beta, ACT[act], _ptr(out), _stream(torch)))
     return out
 
 
@@ -208,14 +207,14 @@ def shuffle_conv1x1(x, y, w, bn, act="relu"):
     _check_dev(torch, y, torch.float32, "y")
     if x.shape != y.shape:
         raise ValueError("x and y must have the same shape")
-    w = np.ascontiguousarray(w, dtype=np.float32)
+    w, wp = _w(w)
     D, Cout = x.shape[-1], w.shape[3]
     if w.shape[:3] != (1, 1, D):
         raise ValueError("kernel must be [1,1,D,Cout]")
     out = torch.empty(tuple(x.shape[:-1]) + (Cout,), dtype=torch.float32, device=x.device)
-    keep = [_fp(v) for v in bn]
-    check(lib().ssd_shuffle_conv1x1(_ptr(x), _ptr(y), x.numel() // D, D, w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), Cout,
-                                    keep[0][1], keep[1][1], keep[2][1], ACT[act], _ptr(out), _stream(torch)))
+    mean, sf, beta, _keep = _bn(bn)
+    check(lib().ssd_shuffle_conv1x1(_ptr(x), _ptr(y), x.numel() // D, D, wp, Cout, mean, sf, beta, ACT[act], _ptr(out),
+                                    _stream(torch)))
     return out
 
 

@@ -267,6 +267,70 @@ def test_dw_pw_unsupported_shapes_fail_loudly(cuda, ssd):
         ssd.ssd.dw_pw(x, np.zeros((3, 3, 32, 1), np.float32), 2, bn32, None, np.zeros((1, 1, 32, 32), np.float32), bn32, None)
 
 
+def test_failed_stage_call_leaves_nothing_behind(cuda, ssd, oracle_ops):
+    """A stage call that fails must drain its stream and free its scratch, so that the next call on the same stream is bit-equal
+    to the oracle.  Two failing calls, both argument errors:
+      * dw_pw at stride 2 on an odd height (the shape of test_dw_pw_unsupported_shapes_fail_loudly).  The entry point's own
+        argument check refuses it in front of the first HIP call: dwpws_eligible, whose only further condition is a tensor of
+        2 GiB, cannot be made to refuse a call a test can afford, so this one never reaches the scratch;
+      * shuffle_conv1x1 with D = 576: the gathering kernel takes at most 512 padded input channels, and its shape test runs
+        BEHIND pack_conv and the batch-norm upload -- the failing return leaves through the scratch's destructor with four
+        packed kernels and three vectors allocated."""
+    bn32 = (np.zeros(32, np.float32), np.ones(32, np.float32), np.zeros(32, np.float32))
+    with pytest.raises(ssd.SsdError):
+        ssd.ssd.dw_pw(cuda.zeros((1, 7, 6, 32), dtype=cuda.float32, device="cuda"), np.zeros((3, 3, 32, 1), np.float32), 2, bn32, None,
+                      np.zeros((1, 1, 32, 32), np.float32), bn32, None)
+    B, H, W, C, Cout = 1, 8, 8, 32, 64
+    rng = np.random.default_rng(77)
+    x = rng.standard_normal((B, H, W, C)).astype(np.float32)
+    wd = rng.standard_normal((3, 3, C, 1)).astype(np.float32)
+    wp = (rng.standard_normal((1, 1, C, Cout)) * np.sqrt(2.0 / C)).astype(np.float32)
+    g1, b1, m1, v1 = bn_params(rng, C)
+    g2, b2, m2, v2 = bn_params(rng, Cout)
+    mid = oracle_ops.bn_act(oracle_ops.depthwise3x3(x, wd, 1), g1, b1, m1, v1, "relu6")
+    ref = oracle_ops.bn_act(oracle_ops.conv2d(mid, wp, 1, "SAME"), g2, b2, m2, v2, "relu6")
+    dw_pw = lambda: ssd.ssd.dw_pw(dev(cuda, x), wd, 1, (m1, oracle_ops.bn_scale(g1, v1), b1), "relu6",
+                                  wp, (m2, oracle_ops.bn_scale(g2, v2), b2), "relu6").cpu().numpy()
+    assert close(dw_pw(), ref, "dw_pw after a refused dw_pw") == 1.0
+
+    bn8 = (np.zeros(8, np.float32), np.ones(8, np.float32), np.zeros(8, np.float32))
+    xy = cuda.ones((1, 1, 2, 576), dtype=cuda.float32, device="cuda")
+    cuda.cuda.synchronize()
+    free0 = cuda.cuda.mem_get_info()[0]
+    with pytest.raises(ssd.SsdError, match="not supported by the gathering kernel"):
+        ssd.ssd.shuffle_conv1x1(xy, xy, np.zeros((1, 1, 576, 8), np.float32), bn8)
+    assert cuda.cuda.mem_get_info()[0] >= free0            # the failed call's scratch is back with the device
+    assert close(dw_pw(), ref, "dw_pw after a failed shuffle_conv1x1") == 1.0
+    D = 58
+    xs_, ys_ = (rng.standard_normal((3, 5, 7, D)).astype(np.float32) for _ in range(2))
+    w = (rng.standard_normal((1, 1, D, D)) * np.sqrt(2.0 / D)).astype(np.float32)
+    g, b, m, v = bn_params(rng, D)
+    ref2 = oracle_ops.bn_act(oracle_ops.conv2d(oracle_ops.concat_shuffle_split(xs_, ys_)[0], w, 1, "SAME"), g, b, m, v, "relu")
+    got2 = ssd.ssd.shuffle_conv1x1(dev(cuda, xs_), dev(cuda, ys_), w, (m, oracle_ops.bn_scale(g, v), b), "relu").cpu().numpy()
+    assert close(got2, ref2, "shuffle_conv1x1 after a failed shuffle_conv1x1") == 1.0
+
+
+# no batch norm, no activation: the raw sums (C = 20 leaves pad channels at the padded width 24)
+@pytest.mark.parametrize("B,H,W,C,stride", [(1, 6, 8, 20, 1), (2, 7, 5, 8, 2)])
+def test_depthwise_without_batch_norm(cuda, ssd, oracle_ops, B, H, W, C, stride):
+    rng = np.random.default_rng(C * 11 + stride)
+    x = rng.standard_normal((B, H, W, C)).astype(np.float32)
+    w = rng.standard_normal((3, 3, C, 1)).astype(np.float32)
+    ref = oracle_ops.depthwise3x3(x, w, stride)
+    got = ssd.ssd.depthwise3x3(dev(cuda, x), w, stride, bn=None, act=None).cpu().numpy()
+    assert close(got, ref, "depthwise without batch norm C=%d s=%d" % (C, stride)) == 1.0
+
+
+@pytest.mark.parametrize("B,H,W,Cout", [(1, 8, 12, 12), (2, 4, 4, 32)])
+def test_first_conv_without_batch_norm(cuda, ssd, oracle_ops, B, H, W, Cout):
+    rng = np.random.default_rng(Cout + 100)
+    img = rng.integers(0, 256, (B, H, W, 3), dtype=np.uint8)
+    w = (rng.standard_normal((3, 3, 3, Cout)) * 0.3).astype(np.float32)
+    ref = oracle_ops.conv2d(oracle_ops.preprocess(img), w, 2, "SAME")
+    got = ssd.ssd.first_conv(dev(cuda, img), w, bn=None, act=None).cpu().numpy()
+    assert close(got, ref, "first conv without batch norm") == 1.0
+
+
 @pytest.mark.parametrize("B,H,W,C,stride,act", [(2, 20, 28, 32, 1, "relu6"), (1, 40, 56, 64, 2, "relu6"),
                                                 (2, 16, 16, 24, 2, None), (1, 10, 10, 58, 1, None),
                                                 (1, 6, 8, 1024, 1, "relu6"),
