@@ -556,7 +556,8 @@ int ssd_train_update(const ssd_update_tensor *tensors_host, const ssd_update_ten
  * augment and update blocks: device pointers of the caller, logical NHWC fp32 tensors and HWIO kernels, DEVICE weights (they
  * change every step), scratch from a caller-supplied workspace, every call only enqueues on `stream` (no allocation, no host
  * round trip, no synchronisation), arguments are refused with SSD_ERR_INVALID before any HIP call, no handle.  No atomics
- * anywhere: two calls give the same bits.  Not here: strides other than 1, 1x1 and depthwise backward, F16X3, double backward.
+ * anywhere: two calls give the same bits.  Not here: strides other than 1 and 1x1 kernels (the TRAIN FPN block below), depthwise
+ * backward, F16X3, double backward.
  *
  * A convolution call takes 1 .. SSD_TRAIN_MAX_LEVELS levels that share B, Cin, Cout and ONE kernel; the weight gradient is the
  * sum over all of them.  Cin must be a multiple of 8, Cin and Cout at most 4096, every level's tensors (channels padded to 32)
@@ -603,7 +604,7 @@ int ssd_train_update(const ssd_update_tensor *tensors_host, const ssd_update_ten
  *     out = sf * ((g - dbeta / rows) - xhat * (dgamma / rows)), one fp32 operation at a time, rows as fp32 */
 #define SSD_TRAIN_MAX_LEVELS 8
 typedef struct ssd_conv_level {              /* 32 bytes */
-    int32_t H, W;                            /* the level's spatial size (input == output)                      */
+    int32_t H, W;                            /* the level's INPUT size (TRAIN head: input == output)            */
     const float *x;                          /* [B,H,W,Cin]: the layer's input                                   */
     const float *dy;                         /* backward: [B,H,W,Cout] upstream gradient; forward: not read      */
     float *out;                              /* forward: [B,H,W,Cout]; backward: dx [B,H,W,Cin] or NULL          */
@@ -632,6 +633,69 @@ int ssd_bn_relu_train_forward(const ssd_bn_level *levels, int32_t n_levels, int3
                               float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream);
 int ssd_bn_relu_train_backward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, void *workspace_dev,
                                size_t workspace_bytes, void *stream);
+
+/* ---- the TRAIN FPN: forward and backward of fpn() in TRAIN mode on a frozen backbone (feature_extractor.py:40-76) ----
+ *
+ * fpn() is ten dense convolutions on 256 output channels and five batch norms + ReLU:
+ *     x5 = lateral5(c5) (1x1)                p5 = conv3x3(x5)
+ *     x4 = lateral4(c4) + up2(x5)            p4 = conv3x3(x4)          up2 = nearest-neighbour x2 upsampling
+ *     x3 = lateral3(c3) + up2(x4)            p3 = conv3x3(x3)
+ *     p6 = conv3x3 stride 2 (c5)             p7 = conv3x3 stride 2 (relu(p6)), the RAW p6: the batch norms come last (:71-74)
+ * The batch norms are the TRAIN head's calls above.  The convolutions are the TRAIN head's pair with three more arguments, under
+ * the TRAIN head's conventions (caller's device pointers, logical NHWC fp32, HWIO kernels in device memory, caller's workspace,
+ * SSD_ERR_INVALID before any HIP call, enqueue only, no atomics: two calls give the same bits).  The six ssd_conv3x3_train_* /
+ * ssd_bn_relu_train_* entry points ARE these calls with k = 3, stride = 1, up_dev = NULL: same planner, same launches, same bits.
+ *
+ *   k       1 or 3.  pad_beg = 0 for k = 1, 1 for k = 3.
+ *   stride  1 or 2; 2 only with k = 3.  In ssd_conv_level H, W are the INPUT's size; the output (out of the forward, dy of the
+ *           backward) is H x W for stride 1 and ceil(H/2) x ceil(W/2) for stride 2: conv2d_same's explicit pad of 1 before and
+ *           1 after with a 'valid' convolution (layer_utils.py:25-43).  Backward: out = dx is [B,H,W,Cin].
+ *   up_dev  forward only, nullable: n_levels pointers, up_dev[l] = [B,H/2,W/2,Cout] added to level l's output after nearest x2
+ *           upsampling.  Only with stride 1, even H and W, bias_dev == NULL, every entry non-NULL and 16-byte aligned.
+ * Cin: a multiple of 8 for k = 3, of 4 for k = 1 (ShuffleNet's c3 has 116 channels); Cin, Cout <= 4096; every level's tensors
+ * (channels padded to 32) below 2 GiB.  ssd_conv_train_workspace_bytes sizes the workspace of either call (with_up != 0: a forward
+ * that will pass up_dev); 0 for refused sizes.
+ *
+ * ssd_conv_train_forward    out_l = conv(x_l, w) (+ bias) (+ up2(up_l)) on ssd_conv2d's exact-fp32 implicit GEMM with the kernel
+ *   packed on the device: bit-identical to ssd_conv2d with the same k, stride, pad_beg and up_dev -- per output ONE fmaf chain
+ *   over taps row-major, ci ascending within a tap, then one fp32 addition of the bias or of the upsampled value.
+ * ssd_conv_train_backward
+ *   dw_dev [k,k,Cin,Cout] on v_mfma_f32_32x32x2_f32: tap (kh,kw) of output position (oy,ox) multiplies
+ *     x[oy*stride + kh - pad_beg, ox*stride + kw - pad_beg] (zero outside the input) with dy[oy,ox]; the sum runs over the levels,
+ *     images and OUTPUT positions.  Order: the TRAIN head's slice rule with 9 replaced by k*k and the rows counted at the output --
+ *     rows_per_slice = the total OUTPUT row count over max(1, 1536 / tiles) slices, tiles = k*k * ceil(Cin / 128) *
+ *     ceil(Cout / (Cout <= 32 ? 32 : 128)), at least 256, rounded up to 16; a level's output rows r = (b * OH + oy) * OW + ox are
+ *     cut into such slices, one fp32 chain in ascending r within a slice, the slices added one fp32 addition at a time in
+ *     ascending order, levels in list order.  k = 3, stride 1 is the TRAIN head's order and bits.  This implementation's order,
+ *     deterministic, NOT pinned to an oracle chain.
+ *   dx (levels[l].out, for every level or for none):
+ *     k = 3, stride 1   as the TRAIN head's.
+ *     k = 3, stride 2   dx = conv3x3_same(D, w') on the same launch, D [B,H,W,Cout] with D[b,2oy,2ox,:] = dy[b,oy,ox,:] and zero
+ *                       elsewhere (written into the workspace by the step that permutes dy), w' the TRAIN head's rotated,
+ *                       transposed kernel.  Consequence: ONE fmaf chain per element over taps row-major, co ascending within a
+ *                       tap, the zeros of D included -- on finite data bit-identical to the CPU oracle's conv2d(D, w').
+ *     k = 1             REFUSED with a non-NULL out: nothing trainable lies upstream of a lateral while the backbone is frozen.
+ *   dbias_dev (nullable; the FPN has no bias) as the TRAIN head's, over the output rows.
+ *
+ * ssd_fpn_merge_backward   the backward of the top-down merge and of the ReLU between p6 and p7, one streaming kernel:
+ *     same_size == 0   out[b,y,x,c] = base[b,y,x,c] + g[b,2y,2x,c] + g[b,2y,2x+1,c] + g[b,2y+1,2x,c] + g[b,2y+1,2x+1,c]
+ *                      with g [B,2H,2W,C]: dx4 = dx4' + (the 2x2 sums of dx3)
+ *     same_size != 0   out[b,y,x,c] = base[b,y,x,c] + g[b,y,x,c] with g [B,H,W,C]: d p6 = d p6' + relu'(p6) * dx(p7's input)
+ *   fp32, added left to right as written, no contraction.  base_dev NULL: the sum starts at +0.  gate_dev [B,H,W,C] nullable: where
+ *   gate > 0 is false (zero of either sign, negative, NaN) every g term of that element reads as +0 (the g value is not used: a
+ *   NaN there does not spread).  out, base, gate are [B,H,W,C]; out_dev may be base_dev (in place), no other overlap.  16-byte
+ *   accesses where C % 4 == 0, element-wise otherwise; every pointer 16-byte aligned.  B <= 65536, H, W <= 16384, C <= 4096. */
+size_t ssd_conv_train_workspace_bytes(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
+                                      int32_t k, int32_t stride, int32_t with_up);
+int ssd_conv_train_forward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout, int32_t k,
+                           int32_t stride, const float *w_dev /* [k,k,Cin,Cout] */, const float *bias_dev /* [Cout] or NULL */,
+                           const float *const *up_dev /* NULL or [n_levels] */, void *workspace_dev, size_t workspace_bytes,
+                           void *stream);
+int ssd_conv_train_backward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout, int32_t k,
+                            int32_t stride, const float *w_dev, float *dw_dev /* [k,k,Cin,Cout] */,
+                            float *dbias_dev /* [Cout] or NULL */, void *workspace_dev, size_t workspace_bytes, void *stream);
+int ssd_fpn_merge_backward(const float *base_dev, const float *g_dev, const float *gate_dev, int32_t B, int32_t H, int32_t W,
+                           int32_t C, int32_t same_size, float *out_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ from .pb_import import read_frozen_graph, load_pb_weights             # noqa: F4
 from .ckpt_import import (read_checkpoint, read_checkpoint_index, resolve_checkpoint,   # noqa: F401
                           load_ckpt_weights, crc32c)
 from ._lib import build, lib, lib_path, SsdError, set_option, get_option                       # noqa: F401
-from .ssd import (SSD, AnchorGenerator, RetinaNetFeatureExtractor, RetinaNetBoxPredictor,     # noqa: F401
+from .ssd import (SSD, AnchorGenerator, RetinaNetFeatureExtractor, RetinaNetBoxPredictor, BackboneFeatures,     # noqa: F401
                   batch_multiclass_non_max_suppression, network_input_size, Engine,
                   get_training_targets, ssd_loss, ssd_loss_backward, differentiable_loss)
 from .detector import Detector                                         # noqa: F401
@@ -26,3 +26,4 @@ from .distributed import (ChunkAssignment, detect_many_sharded, node_device_and_
 from .augment import augment_batch, sample_augmentation, TrainPipeline   # noqa: F401
 from .train_step import TrainStep                                     # noqa: F401
 from .head_train import conv3x3_same, batch_norm_relu, TrainableBoxPredictor, head_variable_shapes   # noqa: F401
+from .fpn_train import conv_same, fpn_merge_backward, TrainableFPN, fpn_variable_shapes, variance_scaling_draw   # noqa: F401

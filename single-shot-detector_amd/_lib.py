@@ -216,6 +216,11 @@ SIGNATURES = {
     "ssd_bn_relu_train_forward": (ctypes.c_int, [ctypes.POINTER(SsdBnLevel), _i, _i, _i, ctypes.c_float, ctypes.c_float, _vp,
                                                  ctypes.c_size_t, _vp]),
     "ssd_bn_relu_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdBnLevel), _i, _i, _vp, ctypes.c_size_t, _vp]),
+    "ssd_conv_train_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _i, _i, _i]),
+    "ssd_conv_train_forward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _i, _i, _vp, _vp, ctypes.POINTER(_vp), _vp,
+                                              ctypes.c_size_t, _vp]),
+    "ssd_conv_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_fpn_merge_backward": (ctypes.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 

@@ -7,16 +7,18 @@
 
 // wgrad.hip
 struct WgradLevel {
-    const float *x, *dy;   // logical NHWC [B,H,W,Cin], [B,H,W,Cout]
-    int H, W, R;           // R = B*H*W rows
+    const float *x, *dy;   // logical NHWC [B,H,W,Cin], [B,OH,OW,Cout]
+    int H, W;              // the input's size
+    int OW, P, R;          // output width, P = OH*OW positions per image, R = B*P rows: K runs over OUTPUT positions
     int slice_begin;       // first K-slice of this level
-    UDiv dHW, dW;
+    UDiv dP, dOW;
 };
 struct WgradArgs {
     WgradLevel lv[TH_MAX_LEVELS];
     int nlevels, Cin, Cout;
+    int k, stride, pad;    // tap (kh,kw) of output (oy,ox) reads x[oy*stride + kh - pad, ox*stride + kw - pad], zero outside
     int rows_per_slice, n_slices, tiles_ci;
-    float *partial;        // [n_slices][9][Cin][Cout]
+    float *partial;        // [n_slices][k*k][Cin][Cout]
 };
 int wgrad_tile_n(int Cout);
 hipError_t launch_wgrad(const WgradArgs &a, float *dw, hipStream_t s);

@@ -1,5 +1,6 @@
-// The TRAIN head (include/ssd_hip.h, "the TRAIN head"): forward and backward of the box predictor's 3x3 stride-1 'same'
-// convolutions over a list of pyramid levels, and the training-mode batch norm + ReLU that follows each tower layer.
+// The TRAIN head and the TRAIN FPN (include/ssd_hip.h, "the TRAIN head", "the TRAIN FPN"): forward and backward of the box
+// predictor's 3x3 stride-1 'same' convolutions over a list of pyramid levels, of the FPN's 1x1, 3x3 and 3x3 stride-2 convolutions
+// (one planner, one set of launches), the training-mode batch norm + ReLU that follows them, and the top-down merge's backward.
 //   forward / data gradient  the exact-fp32 implicit-GEMM kernel of the inference path (igemm.hip) on a kernel that is
 //                            packed ON THE DEVICE (pack_w_kernel: weights.hip's pack_conv layout, two index maps)
 //   weight gradient          wgrad.hip
@@ -16,13 +17,13 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 static inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
 // ----------------------------------------------------------------------------- kernel packing on the device
-// w HWIO [3,3,Cin,Cout] (device) -> wt [9][rows][kp] in physical channel order, zero where a channel is padding.
+// w HWIO [k,k,Cin,Cout] (device), taps = k * k = 1 or 9 -> wt [taps][rows][kp] in physical channel order, zero where a channel is padding.
 //   transpose == 0  the forward's kernel: row = output channel co, k = input channel ci, tap as stored
-//   transpose == 1  the data gradient's kernel w'[kh,kw,co,ci] = w[2-kh,2-kw,ci,co]: row = ci, k = co, tap 8 - tap
-__global__ __launch_bounds__(256) void pack_w_kernel(const float *w, int Cin, int Cout, int kp, int rows, int transpose, float *wt)
+//   transpose == 1  the data gradient's kernel w'[kh,kw,co,ci] = w[2-kh,2-kw,ci,co]: row = ci, k = co, tap 8 - tap (taps = 9 only)
+__global__ __launch_bounds__(256) void pack_w_kernel(const float *w, int Cin, int Cout, int kp, int rows, int taps, int transpose, float *wt)
 {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= 9LL * rows * kp) return;
+    if (idx >= (long long)taps * rows * kp) return;
     const int p = (int)(idx % kp), n = (int)((idx / kp) % rows), tap = (int)(idx / ((long long)kp * rows));
     const int lk = ssd_logical_of_phys(p), ln = ssd_logical_of_phys(n);
     float v = 0.0f;
@@ -226,164 +227,218 @@ static void make_slabs(StatArgs &a)
     } while (0)
 
 // ----------------------------------------------------------------------------- the convolutions
+// One planner for the TRAIN head's 3x3 stride-1 calls and the TRAIN FPN's k x k / stride-2 / upsample-add calls: a level's
+// input is [B,H,W,Cin] (Rin rows), its output [B,OH,OW,Cout] (Rout rows; stride 1: the same size).
 struct ConvTrainPlan {
-    long long R[TH_MAX_LEVELS], roff[TH_MAX_LEVELS], Rtot;
+    int k, stride, pad, OH[TH_MAX_LEVELS], OW[TH_MAX_LEVELS];
+    long long Rin[TH_MAX_LEVELS], Rout[TH_MAX_LEVELS], rin_off[TH_MAX_LEVELS], rout_off[TH_MAX_LEVELS], up_off[TH_MAX_LEVELS];
+    long long Rin_tot, Rout_tot, Rup_tot;
     ConvW f, d;                         // geometry of the forward's and the data gradient's packed kernels (no pointers yet)
     int rows_per_slice, n_slices, slice_begin[TH_MAX_LEVELS], tiles_ci;
     StatArgs st;                        // dbias: the slabs of dy
-    size_t off_a, off_b, off_w, off_bias, off_part, off_stat, bytes;
+    size_t off_a, off_b, off_w, off_bias, off_part, off_stat, off_up, bytes;
 };
 
-static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, int Cout, ConvTrainPlan &p)
+static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, int Cout, int k, int stride, int with_up, ConvTrainPlan &p)
 {
     if (!lv) return "null level list";
     if (n < 1 || n > TH_MAX_LEVELS) return "1 .. 8 levels";
     if (B < 1 || Cin < 1 || Cout < 1) return "sizes must be positive";
-    if (Cin % 8) return "Cin must be a multiple of 8";
+    if (k != 1 && k != 3) return "k must be 1 or 3";
+    if (stride != 1 && stride != 2) return "stride must be 1 or 2";
+    if (stride == 2 && k != 3) return "stride 2 only with k = 3";
+    if (with_up && stride != 1) return "the upsample-add only with stride 1";
+    if (k == 3 && Cin % 8) return "Cin must be a multiple of 8";
+    if (Cin % 4) return "Cin must be a multiple of 4";
     if (Cin > 4096 || Cout > 4096) return "at most 4096 channels";
-    conv_geometry(nullptr, 9, round_up(Cin, 32), round_up(Cout, 8), Cin, Cout, p.f);
+    const int taps = k * k;
+    p.k = k; p.stride = stride; p.pad = k == 3 ? 1 : 0;
+    conv_geometry(nullptr, taps, round_up(Cin, 32), round_up(Cout, 8), Cin, Cout, p.f);
     conv_geometry(nullptr, 9, round_up(Cout, 32), round_up(Cin, 8), Cout, Cin, p.d);
     const int widest = std::max(std::max(p.f.CinP, p.f.CoutP), std::max(p.d.CinP, p.d.CoutP));
-    p.Rtot = 0;
+    p.Rin_tot = p.Rout_tot = p.Rup_tot = 0;
     for (int l = 0; l < n; ++l) {
         if (lv[l].H < 1 || lv[l].W < 1) return "sizes must be positive";
+        if (with_up && ((lv[l].H | lv[l].W) & 1)) return "the upsample-add needs even H and W";
         const long long R = (long long)B * lv[l].H * lv[l].W;
         if (lv[l].H > 32768 || lv[l].W > 32768 || R * widest * 4 >= (1LL << 31)) return "every level's tensors must stay below 2 GiB";
-        p.R[l] = R;
-        p.roff[l] = p.Rtot;
-        p.Rtot += R;
+        p.OH[l] = (lv[l].H + stride - 1) / stride;
+        p.OW[l] = (lv[l].W + stride - 1) / stride;
+        p.Rin[l] = R;
+        p.Rout[l] = (long long)B * p.OH[l] * p.OW[l];
+        p.rin_off[l] = p.Rin_tot;
+        p.rout_off[l] = p.Rout_tot;
+        p.up_off[l] = p.Rup_tot;
+        p.Rin_tot += R;
+        p.Rout_tot += p.Rout[l];
+        if (with_up) p.Rup_tot += R / 4;
     }
-    if (p.Rtot >= (1LL << 31)) return "fewer than 2^31 positions in all";
+    if (p.Rin_tot >= (1LL << 31)) return "fewer than 2^31 positions in all";
     // K-slices of the weight gradient: about 1536 blocks in all
     p.tiles_ci = (Cin + 127) / 128;
     const int BN = wgrad_tile_n(Cout);
-    const long long tiles = 9LL * p.tiles_ci * ((Cout + BN - 1) / BN);
+    const long long tiles = (long long)taps * p.tiles_ci * ((Cout + BN - 1) / BN);
     const long long want = std::max(1LL, 1536 / tiles);
-    long long rps = (p.Rtot + want - 1) / want;
+    long long rps = (p.Rout_tot + want - 1) / want;
     if (rps < 256) rps = 256;
     rps = (rps + 15) / 16 * 16;
     p.rows_per_slice = (int)rps;
     p.n_slices = 0;
     for (int l = 0; l < n; ++l) {
         p.slice_begin[l] = p.n_slices;
-        p.n_slices += (int)((p.R[l] + rps - 1) / rps);
+        p.n_slices += (int)((p.Rout[l] + rps - 1) / rps);
     }
     memset(&p.st, 0, sizeof(p.st));
     p.st.nlevels = n;
     p.st.C = Cout;
-    for (int l = 0; l < n; ++l) p.st.lv[l].p.rows = p.R[l];
+    for (int l = 0; l < n; ++l) p.st.lv[l].p.rows = p.Rout[l];
     make_slabs(p.st);
-    // workspace: [a | b | w | bias] of the forward or the data gradient, then the weight gradient's partial tiles and dbias's sums
-    const size_t a_f = (size_t)p.Rtot * p.f.CinP, b_f = (size_t)p.Rtot * p.f.CoutP, w_f = (size_t)9 * p.f.CoutPad * p.f.CinP;
-    const size_t a_d = (size_t)p.Rtot * p.d.CinP, b_d = (size_t)p.Rtot * p.d.CoutP, w_d = (size_t)9 * p.d.CoutPad * p.d.CinP;
+    // workspace: [a | b | w | bias] of the forward or the data gradient (k = 3: its input is dy, or the zero-dilated dy of a
+    // stride-2 layer, at the INPUT's size), then the weight gradient's partial tiles, dbias's sums and the permuted `up` tensors
+    const size_t a_f = (size_t)p.Rin_tot * p.f.CinP, b_f = (size_t)p.Rout_tot * p.f.CoutP, w_f = (size_t)taps * p.f.CoutPad * p.f.CinP;
+    const size_t dg = k == 3 ? 1 : 0;
+    const size_t a_d = dg * p.Rin_tot * p.d.CinP, b_d = dg * p.Rin_tot * p.d.CoutP, w_d = dg * 9 * p.d.CoutPad * p.d.CinP;
     p.off_a = 0;
     p.off_b = al256(std::max(a_f, a_d) * 4 + 256);
     p.off_w = p.off_b + al256(std::max(b_f, b_d) * 4 + 256);
     p.off_bias = p.off_w + al256(std::max(w_f, w_d) * 4 + 256);
     p.off_part = p.off_bias + al256((size_t)p.f.CoutP * 4 + 256);
-    p.off_stat = p.off_part + al256((size_t)p.n_slices * 9 * Cin * Cout * 4);
-    p.bytes = p.off_stat + al256((size_t)p.st.n_slabs * 2 * Cout * 8);
+    p.off_stat = p.off_part + al256((size_t)p.n_slices * taps * Cin * Cout * 4);
+    p.off_up = p.off_stat + al256((size_t)p.st.n_slabs * 2 * Cout * 8);
+    p.bytes = p.off_up + (with_up ? al256((size_t)p.Rup_tot * p.f.CoutP * 4 + 256) : 0);
     return nullptr;
 }
 
 static inline bool mis16(const void *p) { return ((uintptr_t)p & 15) != 0; }
 
-extern "C" size_t ssd_conv3x3_train_workspace_bytes(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout)
+// dy [B,OH,OW,C] logical -> D [B,H,W,Cp] physical, D[b,2oy,2ox,:] = dy[b,oy,ox,:] and zero elsewhere (and in the padding
+// channels): the permute of the data gradient's operand, scattering the gradient of a stride-2 layer over the input's grid
+__global__ __launch_bounds__(256) void dilate_permute_kernel(const float *__restrict__ dy, int H, int W, int OH, int OW, int C, int Cp,
+                                                              long long total, float *__restrict__ out)
 {
-    ConvTrainPlan p;
-    return conv_plan(levels, n_levels, B, Cin, Cout, p) ? 0 : p.bytes;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const int j = (int)(idx % Cp);
+        const long long pos = idx / Cp;
+        const int x = (int)(pos % W);
+        const long long t = pos / W;
+        const int y = (int)(t % H);
+        const long long b = t / H;
+        const int l = ssd_logical_of_phys(j);
+        float v = 0.0f;
+        if (!((x | y) & 1) && l < C) v = dy[((b * OH + (y >> 1)) * OW + (x >> 1)) * C + l];
+        out[idx] = v;
+    }
 }
 
-static int run_igemm(const ConvW &cw, const float *in, float *out, const ssd_conv_level *lv, int n, int B, const ConvTrainPlan &p, hipStream_t s)
+// levels of one implicit-GEMM launch: rows of `in` from in_rows[l] on, rows of `out` from out_rows[l] on
+static int run_igemm(const ConvW &cw, const float *in, float *out, const float *res, const ssd_conv_level *lv, int n, int B, int stride, int pad,
+                     const int *OH, const int *OW, const long long *in_rows, const long long *out_rows, const long long *res_rows, hipStream_t s)
 {
     std::vector<LevelDesc> ld;
     for (int l = 0; l < n; ++l)
-        ld.push_back(dense_level(lv[l].H, lv[l].W, lv[l].H, lv[l].W, cw.CoutP, p.roff[l] * cw.CinP, p.roff[l] * cw.CoutP));
+        ld.push_back(dense_level(lv[l].H, lv[l].W, OH ? OH[l] : lv[l].H, OW ? OW[l] : lv[l].W, cw.CoutP, in_rows[l] * cw.CinP, out_rows[l] * cw.CoutP, 0,
+                                 res ? res_rows[l] * cw.CoutP : 0));
     ConvIO io{in, out};
-    Op op = make_conv_op(nullptr, cw, io, B, 1, 1, SSD_ACT_NONE, ld, true);
+    io.res = res;
+    Op op = make_conv_op(nullptr, cw, io, B, stride, pad, SSD_ACT_NONE, ld, true);
     HIPCHK(op.run(s));
     return SSD_OK;
 }
 
-extern "C" int ssd_conv3x3_train_forward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
-                                         const float *w_dev, const float *bias_dev, void *workspace_dev, size_t workspace_bytes,
-                                         void *stream)
+static int conv_train_forward(const std::string &fn, const ssd_conv_level *levels, int n_levels, int B, int Cin, int Cout, int k, int stride,
+                              const float *w_dev, const float *bias_dev, const float *const *up_dev, void *workspace_dev, size_t workspace_bytes,
+                              void *stream)
 {
     ConvTrainPlan p;
-    if (const char *why = conv_plan(levels, n_levels, B, Cin, Cout, p))
-        return ssd_fail(SSD_ERR_INVALID, std::string("ssd_conv3x3_train_forward: ") + why);
-    if (!w_dev || !workspace_dev) return ssd_fail(SSD_ERR_INVALID, "ssd_conv3x3_train_forward: null pointer");
+    if (const char *why = conv_plan(levels, n_levels, B, Cin, Cout, k, stride, up_dev != nullptr, p))
+        return ssd_fail(SSD_ERR_INVALID, fn + ": " + why);
+    if (!w_dev || !workspace_dev) return ssd_fail(SSD_ERR_INVALID, fn + ": null pointer");
     if (mis16(w_dev) || mis16(workspace_dev) || ((uintptr_t)bias_dev & 3))
-        return ssd_fail(SSD_ERR_INVALID, "ssd_conv3x3_train_forward: w_dev and workspace_dev need 16-byte alignment, bias_dev 4-byte");
+        return ssd_fail(SSD_ERR_INVALID, fn + ": w_dev and workspace_dev need 16-byte alignment, bias_dev 4-byte");
+    if (bias_dev && up_dev) return ssd_fail(SSD_ERR_INVALID, fn + ": bias and upsample-add are mutually exclusive");
     for (int l = 0; l < n_levels; ++l) {
-        if (!levels[l].x || !levels[l].out) return ssd_fail(SSD_ERR_INVALID, "ssd_conv3x3_train_forward: a level's x or out is null");
-        if (mis16(levels[l].x) || mis16(levels[l].out)) return ssd_fail(SSD_ERR_INVALID, "ssd_conv3x3_train_forward: a level's x or out is not 16-byte aligned");
+        if (!levels[l].x || !levels[l].out) return ssd_fail(SSD_ERR_INVALID, fn + ": a level's x or out is null");
+        if (mis16(levels[l].x) || mis16(levels[l].out)) return ssd_fail(SSD_ERR_INVALID, fn + ": a level's x or out is not 16-byte aligned");
+        if (up_dev && (!up_dev[l] || mis16(up_dev[l]))) return ssd_fail(SSD_ERR_INVALID, fn + ": a level's up is null or not 16-byte aligned");
     }
-    if (workspace_bytes < p.bytes) return ssd_fail(SSD_ERR_INVALID, "ssd_conv3x3_train_forward: workspace too small");
+    if (workspace_bytes < p.bytes) return ssd_fail(SSD_ERR_INVALID, fn + ": workspace too small");
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace_dev;
     float *xin = (float *)(ws + p.off_a), *outp = (float *)(ws + p.off_b), *wt = (float *)(ws + p.off_w), *biasp = (float *)(ws + p.off_bias);
+    float *upp = up_dev ? (float *)(ws + p.off_up) : nullptr;
     ConvW cw = p.f;
-    for (int l = 0; l < n_levels; ++l)
-        HIPCHK(launch_permute_channels(levels[l].x, p.R[l], Cin, cw.CinP, 1, xin + p.roff[l] * cw.CinP, s));
-    const long long nw = 9LL * cw.CoutPad * cw.CinP;
-    LAUNCH(pack_w_kernel, dim3((unsigned)((nw + 255) / 256)), s, w_dev, Cin, Cout, cw.CinP, cw.CoutPad, 0, wt);
+    for (int l = 0; l < n_levels; ++l) {
+        HIPCHK(launch_permute_channels(levels[l].x, p.Rin[l], Cin, cw.CinP, 1, xin + p.rin_off[l] * cw.CinP, s));
+        if (up_dev) HIPCHK(launch_permute_channels(up_dev[l], p.Rin[l] / 4, Cout, cw.CoutP, 1, upp + p.up_off[l] * cw.CoutP, s));
+    }
+    const long long nw = (long long)cw.taps * cw.CoutPad * cw.CinP;
+    LAUNCH(pack_w_kernel, dim3((unsigned)((nw + 255) / 256)), s, w_dev, Cin, Cout, cw.CinP, cw.CoutPad, cw.taps, 0, wt);
     cw.wt = wt;
     if (bias_dev) {
         HIPCHK(launch_permute_channels(bias_dev, 1, Cout, cw.CoutP, 1, biasp, s));
         cw.bias = biasp;
     }
-    SSDCHK(run_igemm(cw, xin, outp, levels, n_levels, B, p, s));
+    SSDCHK(run_igemm(cw, xin, outp, upp, levels, n_levels, B, stride, p.pad, p.OH, p.OW, p.rin_off, p.rout_off, p.up_off, s));
     for (int l = 0; l < n_levels; ++l)
-        HIPCHK(launch_permute_channels(outp + p.roff[l] * cw.CoutP, p.R[l], Cout, cw.CoutP, 0, levels[l].out, s));
+        HIPCHK(launch_permute_channels(outp + p.rout_off[l] * cw.CoutP, p.Rout[l], Cout, cw.CoutP, 0, levels[l].out, s));
     return SSD_OK;
 }
 
-extern "C" int ssd_conv3x3_train_backward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
-                                          const float *w_dev, float *dw_dev, float *dbias_dev, void *workspace_dev,
-                                          size_t workspace_bytes, void *stream)
+static int conv_train_backward(const std::string &fn, const ssd_conv_level *levels, int n_levels, int B, int Cin, int Cout, int k, int stride,
+                               const float *w_dev, float *dw_dev, float *dbias_dev, void *workspace_dev, size_t workspace_bytes, void *stream)
 {
     ConvTrainPlan p;
-    if (const char *why = conv_plan(levels, n_levels, B, Cin, Cout, p))
-        return ssd_fail(SSD_ERR_INVALID, std::string("ssd_conv3x3_train_backward: ") + why);
-    if (!w_dev || !dw_dev || !workspace_dev) return ssd_fail(SSD_ERR_INVALID, "ssd_conv3x3_train_backward: null pointer");
+    if (const char *why = conv_plan(levels, n_levels, B, Cin, Cout, k, stride, 0, p))
+        return ssd_fail(SSD_ERR_INVALID, fn + ": " + why);
+    if (!w_dev || !dw_dev || !workspace_dev) return ssd_fail(SSD_ERR_INVALID, fn + ": null pointer");
     if (mis16(w_dev) || mis16(dw_dev) || mis16(workspace_dev) || ((uintptr_t)dbias_dev & 3))
-        return ssd_fail(SSD_ERR_INVALID, "ssd_conv3x3_train_backward: w_dev, dw_dev and workspace_dev need 16-byte alignment, dbias_dev 4-byte");
+        return ssd_fail(SSD_ERR_INVALID, fn + ": w_dev, dw_dev and workspace_dev need 16-byte alignment, dbias_dev 4-byte");
     int with_dx = 0;
     for (int l = 0; l < n_levels; ++l) {
-        if (!levels[l].x || !levels[l].dy) return ssd_fail(SSD_ERR_INVALID, "ssd_conv3x3_train_backward: a level's x or dy is null");
+        if (!levels[l].x || !levels[l].dy) return ssd_fail(SSD_ERR_INVALID, fn + ": a level's x or dy is null");
         if (mis16(levels[l].x) || mis16(levels[l].dy) || mis16(levels[l].out))
-            return ssd_fail(SSD_ERR_INVALID, "ssd_conv3x3_train_backward: a level's x, dy or out is not 16-byte aligned");
+            return ssd_fail(SSD_ERR_INVALID, fn + ": a level's x, dy or out is not 16-byte aligned");
         with_dx += levels[l].out ? 1 : 0;
     }
     if (with_dx != 0 && with_dx != n_levels)
-        return ssd_fail(SSD_ERR_INVALID, "ssd_conv3x3_train_backward: dx (out) must be given for every level or for none");
-    if (workspace_bytes < p.bytes) return ssd_fail(SSD_ERR_INVALID, "ssd_conv3x3_train_backward: workspace too small");
+        return ssd_fail(SSD_ERR_INVALID, fn + ": dx (out) must be given for every level or for none");
+    if (with_dx && k == 1) return ssd_fail(SSD_ERR_INVALID, fn + ": no data gradient of a 1x1 convolution (dx must be NULL)");
+    if (workspace_bytes < p.bytes) return ssd_fail(SSD_ERR_INVALID, fn + ": workspace too small");
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace_dev;
-    if (with_dx) {          // dx = conv3x3_same(dy, w'): the forward's launch on the rotated, transposed kernel
+    if (with_dx) {          // dx = conv3x3_same(dy, w'), stride 2: of the zero-dilated dy: the forward's launch on the rotated, transposed kernel
         float *dyp = (float *)(ws + p.off_a), *dxp = (float *)(ws + p.off_b), *wt = (float *)(ws + p.off_w);
         ConvW cw = p.d;
-        for (int l = 0; l < n_levels; ++l)
-            HIPCHK(launch_permute_channels(levels[l].dy, p.R[l], Cout, cw.CinP, 1, dyp + p.roff[l] * cw.CinP, s));
+        for (int l = 0; l < n_levels; ++l) {
+            float *dst = dyp + p.rin_off[l] * cw.CinP;
+            if (stride == 1) {
+                HIPCHK(launch_permute_channels(levels[l].dy, p.Rin[l], Cout, cw.CinP, 1, dst, s));
+            } else {
+                const long long total = p.Rin[l] * cw.CinP;
+                const long long blocks = std::min<long long>((total + 255) / 256, 256 * 32);
+                LAUNCH(dilate_permute_kernel, dim3((unsigned)blocks), s, levels[l].dy, levels[l].H, levels[l].W, p.OH[l], p.OW[l], Cout, cw.CinP, total, dst);
+            }
+        }
         const long long nw = 9LL * cw.CoutPad * cw.CinP;
-        LAUNCH(pack_w_kernel, dim3((unsigned)((nw + 255) / 256)), s, w_dev, Cin, Cout, cw.CinP, cw.CoutPad, 1, wt);
+        LAUNCH(pack_w_kernel, dim3((unsigned)((nw + 255) / 256)), s, w_dev, Cin, Cout, cw.CinP, cw.CoutPad, 9, 1, wt);
         cw.wt = wt;
-        SSDCHK(run_igemm(cw, dyp, dxp, levels, n_levels, B, p, s));
+        SSDCHK(run_igemm(cw, dyp, dxp, nullptr, levels, n_levels, B, 1, 1, nullptr, nullptr, p.rin_off, p.rin_off, nullptr, s));
         for (int l = 0; l < n_levels; ++l)
-            HIPCHK(launch_permute_channels(dxp + p.roff[l] * cw.CoutP, p.R[l], Cin, cw.CoutP, 0, levels[l].out, s));
+            HIPCHK(launch_permute_channels(dxp + p.rin_off[l] * cw.CoutP, p.Rin[l], Cin, cw.CoutP, 0, levels[l].out, s));
     }
     WgradArgs a;
     memset(&a, 0, sizeof(a));
     a.nlevels = n_levels; a.Cin = Cin; a.Cout = Cout;
+    a.k = k; a.stride = stride; a.pad = p.pad;
     a.rows_per_slice = p.rows_per_slice; a.n_slices = p.n_slices; a.tiles_ci = p.tiles_ci;
     a.partial = (float *)(ws + p.off_part);
     for (int l = 0; l < n_levels; ++l) {
         WgradLevel &L = a.lv[l];
-        L.x = levels[l].x; L.dy = levels[l].dy; L.H = levels[l].H; L.W = levels[l].W; L.R = (int)p.R[l];
+        L.x = levels[l].x; L.dy = levels[l].dy; L.H = levels[l].H; L.W = levels[l].W;
+        L.OW = p.OW[l]; L.P = p.OH[l] * p.OW[l]; L.R = (int)p.Rout[l];
         L.slice_begin = p.slice_begin[l];
-        L.dHW = ssd_udiv_make((unsigned)(L.H * L.W));
-        L.dW = ssd_udiv_make((unsigned)L.W);
+        L.dP = ssd_udiv_make((unsigned)L.P);
+        L.dOW = ssd_udiv_make((unsigned)L.OW);
     }
     HIPCHK(launch_wgrad(a, dw_dev, s));
     if (dbias_dev) {
@@ -394,6 +449,105 @@ extern "C" int ssd_conv3x3_train_backward(const ssd_conv_level *levels, int32_t 
         LAUNCH(stat_partial<0>, dim3((unsigned)st.n_slabs, (unsigned)((Cout + TH_STAT_COLS - 1) / TH_STAT_COLS)), s, st);
         LAUNCH(stat_final<3>, dim3((unsigned)((Cout + 255) / 256), 1), s, st);
     }
+    return SSD_OK;
+}
+
+// the TRAIN head's entry points: k = 3, stride 1, no upsample-add
+extern "C" size_t ssd_conv3x3_train_workspace_bytes(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout)
+{
+    ConvTrainPlan p;
+    return conv_plan(levels, n_levels, B, Cin, Cout, 3, 1, 0, p) ? 0 : p.bytes;
+}
+
+extern "C" int ssd_conv3x3_train_forward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
+                                         const float *w_dev, const float *bias_dev, void *workspace_dev, size_t workspace_bytes,
+                                         void *stream)
+{
+    return conv_train_forward("ssd_conv3x3_train_forward", levels, n_levels, B, Cin, Cout, 3, 1, w_dev, bias_dev, nullptr, workspace_dev,
+                              workspace_bytes, stream);
+}
+
+extern "C" int ssd_conv3x3_train_backward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
+                                          const float *w_dev, float *dw_dev, float *dbias_dev, void *workspace_dev,
+                                          size_t workspace_bytes, void *stream)
+{
+    return conv_train_backward("ssd_conv3x3_train_backward", levels, n_levels, B, Cin, Cout, 3, 1, w_dev, dw_dev, dbias_dev, workspace_dev,
+                               workspace_bytes, stream);
+}
+
+// the TRAIN FPN's entry points
+extern "C" size_t ssd_conv_train_workspace_bytes(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
+                                                 int32_t k, int32_t stride, int32_t with_up)
+{
+    ConvTrainPlan p;
+    return conv_plan(levels, n_levels, B, Cin, Cout, k, stride, with_up != 0, p) ? 0 : p.bytes;
+}
+
+extern "C" int ssd_conv_train_forward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout, int32_t k,
+                                      int32_t stride, const float *w_dev, const float *bias_dev, const float *const *up_dev,
+                                      void *workspace_dev, size_t workspace_bytes, void *stream)
+{
+    return conv_train_forward("ssd_conv_train_forward", levels, n_levels, B, Cin, Cout, k, stride, w_dev, bias_dev, up_dev, workspace_dev,
+                              workspace_bytes, stream);
+}
+
+extern "C" int ssd_conv_train_backward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout, int32_t k,
+                                       int32_t stride, const float *w_dev, float *dw_dev, float *dbias_dev, void *workspace_dev,
+                                       size_t workspace_bytes, void *stream)
+{
+    return conv_train_backward("ssd_conv_train_backward", levels, n_levels, B, Cin, Cout, k, stride, w_dev, dw_dev, dbias_dev, workspace_dev,
+                               workspace_bytes, stream);
+}
+
+// ----------------------------------------------------------------------------- the top-down merge's backward
+// out = base + g[2y,2x] + g[2y,2x+1] + g[2y+1,2x] + g[2y+1,2x+1] (same == 0, g [B,2H,2W,C]) or out = base + g (same != 0), left
+// to right; a NULL base starts at +0, and where gate > 0 is false every g term reads as +0.  One thread per channel quad.
+__global__ __launch_bounds__(256) void fpn_merge_backward_kernel(const float *base, const float *__restrict__ g, const float *__restrict__ gate,
+                                                                  float *out, long long rows, int H, int W, int C, int same)
+{
+    const int CQ = (C + 3) >> 2;
+    const bool vec = (C & 3) == 0;
+    const long long total = rows * CQ;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const int c = (int)(idx % CQ) << 2;
+        const long long r = idx / CQ;
+        v4f acc = {0.f, 0.f, 0.f, 0.f}, open = {1.f, 1.f, 1.f, 1.f};
+        if (base) acc = th_load4(base + r * C, c, C, vec);
+        if (gate) open = th_load4(gate + r * C, c, C, vec);
+        if (same) {
+            const v4f t = th_load4(g + r * C, c, C, vec);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = acc[e] + (open[e] > 0.0f ? t[e] : 0.0f);
+        } else {
+            const int x = (int)(r % W);
+            const long long q = r / W;
+            const int y = (int)(q % H);
+            const long long b = q / H;
+            const long long g0 = ((b * 2 * H + 2 * y) * 2 * W + 2 * x) * C;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const v4f v = th_load4(g + g0 + ((long long)(t >> 1) * 2 * W + (t & 1)) * C, c, C, vec);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] = acc[e] + (open[e] > 0.0f ? v[e] : 0.0f);
+            }
+        }
+        th_store4(out + r * C, c, C, vec, acc);
+    }
+}
+
+extern "C" int ssd_fpn_merge_backward(const float *base_dev, const float *g_dev, const float *gate_dev, int32_t B, int32_t H, int32_t W,
+                                      int32_t C, int32_t same_size, float *out_dev, void *stream)
+{
+    if (!g_dev || !out_dev) return ssd_fail(SSD_ERR_INVALID, "ssd_fpn_merge_backward: g_dev or out_dev is null");
+    if (B < 1 || H < 1 || W < 1 || C < 1 || B > 65536 || H > 16384 || W > 16384 || C > 4096 || (same_size != 0 && same_size != 1))
+        return ssd_fail(SSD_ERR_INVALID, "ssd_fpn_merge_backward: B, H, W, C >= 1, B <= 65536, H and W <= 16384, C <= 4096, same_size 0 or 1");
+    if ((long long)B * H * W * C * (same_size ? 1 : 4) >= (1LL << 40)) return ssd_fail(SSD_ERR_INVALID, "ssd_fpn_merge_backward: tensor too large");
+    if (mis16(base_dev) || mis16(g_dev) || mis16(gate_dev) || mis16(out_dev))
+        return ssd_fail(SSD_ERR_INVALID, "ssd_fpn_merge_backward: every pointer needs 16-byte alignment");
+    if (out_dev == g_dev || (gate_dev && out_dev == gate_dev)) return ssd_fail(SSD_ERR_INVALID, "ssd_fpn_merge_backward: out_dev may alias base_dev only");
+    const long long rows = (long long)B * H * W, total = rows * ((C + 3) / 4);
+    const long long blocks = std::min<long long>((total + 255) / 256, 256 * 32);
+    LAUNCH(fpn_merge_backward_kernel, dim3((unsigned)blocks), (hipStream_t)stream, base_dev, g_dev, gate_dev, out_dev, rows, H, W, C, same_size);
     return SSD_OK;
 }
 

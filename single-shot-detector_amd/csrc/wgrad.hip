@@ -1,8 +1,9 @@
-// The weight gradient of a 3x3 stride-1 'same' convolution on the exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32):
-//     dw[tap][ci][co] = sum over levels, images and output positions r of  x[r shifted by tap][ci] * dy[r][co]
-// a GEMM with M = 9 * Cin, N = Cout and K = every output position of every level.  x and dy are the caller's LOGICAL NHWC
-// tensors (the sum runs over positions, so the channel order of the activations plays no part); the tap shift and the zero
-// border are in the loads of x, as in the forward.  M x N gives few tiles, so K is cut into slices of `rows_per_slice`
+// The weight gradient of a k x k convolution (k = 1 or 3, stride 1 or 2) on the exact-fp32 matrix instruction
+// (v_mfma_f32_32x32x2_f32):
+//     dw[tap][ci][co] = sum over levels, images and output positions r of  x[the tap's input position of r][ci] * dy[r][co]
+// a GEMM with M = k*k * Cin, N = Cout and K = every output position of every level.  x and dy are the caller's LOGICAL NHWC
+// tensors (the sum runs over positions, so the channel order of the activations plays no part); the tap shift, the stride and the
+// zero border are in the loads of x, as in the forward.  M x N gives few tiles, so K is cut into slices of `rows_per_slice`
 // positions (a slice never crosses a level): one block per (slice, tile) writes its partial tile to the workspace, and
 // wgrad_reduce adds the slices of an element in ascending slice order, which is ascending level order.  No atomics: two
 // runs give the same bits.  The order of the sum (include/ssd_hip.h, "the TRAIN head") is this kernel's, not an oracle's.
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a)
     while (l + 1 < a.nlevels && slice >= a.lv[l + 1].slice_begin) ++l;
     const WgradLevel &L = a.lv[l];
     const int tap = blockIdx.z / a.tiles_ci, ci0 = (blockIdx.z % a.tiles_ci) * BM, co0 = blockIdx.y * BN;
-    const int kh = tap / 3, kw = tap % 3;
+    const int kh = tap / a.k - a.pad, kw = tap % a.k - a.pad;      // the tap's offset from the output position's first input
     const int r_begin = (slice - L.slice_begin) * a.rows_per_slice;
     const int r_end = min(L.R, r_begin + a.rows_per_slice);
     const bool vx = (a.Cin & 3) == 0, vy = (a.Cout & 3) == 0;
@@ -47,11 +48,11 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a)
             const int r = r0 + ak + 8 * p;
             v4f v = {0.f, 0.f, 0.f, 0.f};
             if (r < r_end) {
-                const unsigned img = wg_udiv((unsigned)r, L.dHW), rem = (unsigned)r - img * (unsigned)(L.H * L.W);
-                const int oy = (int)wg_udiv(rem, L.dW), ox = (int)rem - oy * L.W;
-                const int sy = oy + kh - 1, sx = ox + kw - 1;
+                const unsigned img = wg_udiv((unsigned)r, L.dP), rem = (unsigned)r - img * (unsigned)L.P;
+                const int oy = (int)wg_udiv(rem, L.dOW), ox = (int)rem - oy * L.OW;
+                const int sy = oy * a.stride + kh, sx = ox * a.stride + kw;
                 if (sy >= 0 && sy < L.H && sx >= 0 && sx < L.W)
-                    v = th_load4(L.x + ((long long)r + (kh - 1) * L.W + (kw - 1)) * a.Cin, ci0 + ac, a.Cin, vx);
+                    v = th_load4(L.x + (((long long)img * L.H + sy) * L.W + sx) * a.Cin, ci0 + ac, a.Cin, vx);
             }
             xa[p] = v;
         }
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a)
         }
     }
     // accumulator element e of a lane: row 8 * (e / 4) + 4 * (lane / 32) + e % 4, column lane % 32
-    float *part = a.partial + (long long)slice * 9 * a.Cin * a.Cout + (long long)tap * a.Cin * a.Cout;
+    float *part = a.partial + ((long long)slice * a.k * a.k + tap) * a.Cin * a.Cout;
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -128,12 +129,12 @@ int wgrad_tile_n(int Cout) { return Cout <= 32 ? 32 : 128; }
 hipError_t launch_wgrad(const WgradArgs &a, float *dw, hipStream_t s)
 {
     const int BN = wgrad_tile_n(a.Cout);
-    const dim3 grid((unsigned)a.n_slices, (unsigned)((a.Cout + BN - 1) / BN), (unsigned)(9 * a.tiles_ci));
+    const dim3 grid((unsigned)a.n_slices, (unsigned)((a.Cout + BN - 1) / BN), (unsigned)(a.k * a.k * a.tiles_ci));
     if (BN == 32) hipLaunchKernelGGL((wgrad_kernel<1, 1, 4, 1>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((wgrad_kernel<2, 2, 2, 2>), grid, dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const long long count = 9LL * a.Cin * a.Cout;
+    const long long count = (long long)a.k * a.k * a.Cin * a.Cout;
     hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, a.partial, a.n_slices, count, dw);
     return hipGetLastError();
 }

@@ -980,6 +980,25 @@ class RetinaNetFeatureExtractor:
         return [self.engine.get_tensor_dev("p%d" % l, (B, -(-nh // s), -(-nw // s), 256)) for l, s in zip(range(3, 8), (8, 16, 32, 64, 128))]
 
 
+class BackboneFeatures:
+    """The frozen backbone of a training step (fpn_train.TrainableFPN's input): callable, images -> [c3, c4, c5], the retained
+    backbone outputs of the engine's forward on `images` (uint8 [B,H,W,3] CUDA), NHWC float32 on the device.  The engine's own
+    FPN and head run too and are ignored."""
+
+    def __init__(self, engine):
+        self.engine = engine
+        from .variables import variable_shapes
+        shapes = variable_shapes(engine.params)
+        self.channels = [shapes["fpn/lateral%d/kernel" % l][2] for l in (3, 4, 5)]
+
+    def __call__(self, images):
+        B, H, W, _ = images.shape
+        self.engine.forward(images)
+        nh, nw, _bs = network_input_size(H, W, self.engine.params["min_dimension"])
+        self.image_size = (nh, nw)
+        return [self.engine.get_tensor_dev("c%d" % l, (B, -(-nh // s), -(-nw // s), c)) for l, s, c in zip((3, 4, 5), (8, 16, 32), self.channels)]
+
+
 class RetinaNetBoxPredictor:
     """Mirror of detector/box_predictor.py:11-64: callable, image_features -> {'encoded_boxes' [B,N,4],
     'class_predictions' [B,N,C]}.  The head towers ran in the same plan as the features: the call returns the retained

@@ -92,6 +92,9 @@ class TrainStep:
                        restore; "tf": parameters already have the variables' shapes
     params             the inference config (backbone, depth_multiplier, num_classes): when given, every name must be one of
                        variable_shapes(params) with that shape (in TF layout)
+    frozen             {reference variable name: float32 array in TF layout} of variables that are NOT trained (a frozen backbone):
+                       never read by step(); save writes them as they are, without averages or slots, so that the checkpoint
+                       holds the whole model; restore leaves them alone
 
     m, v and ema live in three flat allocations of this object (`slots(name)`, `ema(name)` are views in the parameter's shape and
     layout); m and v start at 0, ema as a copy of the parameter.  `step()` is one kernel launch behind one small asynchronous
@@ -99,7 +102,7 @@ class TrainStep:
 
     RING = 4
 
-    def __init__(self, named_parameters, config, statistics=None, layout="torch", params=None):
+    def __init__(self, named_parameters, config, statistics=None, layout="torch", params=None, frozen=None):
         import torch
         if layout not in ("torch", "tf"):
             raise ValueError("layout must be 'torch' or 'tf'")
@@ -144,6 +147,14 @@ class TrainStep:
                 raise KeyError("%r is not a moving_mean / moving_variance name" % name)
             if shapes is not None and (name not in shapes or tuple(s.shape) != tuple(shapes[name])):
                 raise KeyError("statistic %r is not a variable of this architecture with shape %s" % (name, tuple(s.shape)))
+        self.frozen = {}
+        for name, a in (frozen or {}).items():
+            if name in names or name in self.statistics:
+                raise KeyError("frozen variable %r is also a parameter or a statistic" % name)
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if shapes is not None and (name not in shapes or tuple(a.shape) != tuple(shapes[name])):
+                raise KeyError("frozen variable %r is not a variable of this architecture with shape %s" % (name, a.shape))
+            self.frozen[name] = a
         self.names = names
         self.parameters = dict(items)
         self.device = device
@@ -272,6 +283,7 @@ class TrainStep:
             out["optimizer/%s/Adam_1" % name] = self._export(name, v)
         for name, s in self.statistics.items():
             out[name] = np.ascontiguousarray(s.detach().cpu().numpy())
+        out.update(self.frozen)
         # TF's accumulators start at beta and are multiplied once per apply: beta^(global_step + 1)
         out["optimizer/beta1_power"] = np.float32(BETA1 ** (self.global_step + 1))
         out["optimizer/beta2_power"] = np.float32(BETA2 ** (self.global_step + 1))
