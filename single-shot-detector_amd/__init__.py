@@ -25,5 +25,6 @@ from .distributed import (ChunkAssignment, detect_many_sharded, node_device_and_
                           launch_local)
 from .augment import augment_batch, sample_augmentation, TrainPipeline   # noqa: F401
 from .train_step import TrainStep                                     # noqa: F401
-from .head_train import conv3x3_same, batch_norm_relu, TrainableBoxPredictor, head_variable_shapes   # noqa: F401
-from .fpn_train import conv_same, fpn_merge_backward, TrainableFPN, fpn_variable_shapes, variance_scaling_draw   # noqa: F401
+from .train_ops import conv_same, conv3x3_same, batch_norm_relu, fpn_merge_backward   # noqa: F401
+from .head_train import TrainableBoxPredictor, head_variable_shapes   # noqa: F401
+from .fpn_train import TrainableFPN, fpn_variable_shapes, variance_scaling_draw   # noqa: F401

@@ -1,6 +1,6 @@
-"""GPU-side helpers shared by tests/test_gpu_head_train.py and tests/test_gpu_head_train_edges.py: the TRAIN head's entry points
-straight through the C ABI (include/ssd_hip.h, "the TRAIN head"), autograd runs of conv3x3_same, and the body of the predictor's
-training-mode comparison."""
+"""GPU-side helpers shared by tests/test_gpu_head_train.py, tests/test_gpu_head_train_edges.py and tests/test_gpu_fpn_train.py: the
+training entry points straight through the C ABI (include/ssd_hip.h, "the TRAIN head" and "the TRAIN FPN"), autograd runs of
+conv_same, and the body of the predictor's training-mode comparison."""
 import ctypes
 
 import numpy as np
@@ -61,35 +61,55 @@ def bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, dys=None, training=1, fill=fl
     return out
 
 
-def conv_backward(ssd, cuda, xs, w, dys, bias=True):
-    """conv3x3_same's gradients through autograd: ([dx], dw, dbias) as numpy."""
-    tx = [dev(cuda, x).requires_grad_() for x in xs]
+def conv_backward(ssd, cuda, xs, w, dys, stride=1, bias=True, with_dx=True):
+    """conv_same's gradients through autograd (bias: a zero bias is added): ([dx] or None, dw, dbias or None) as numpy."""
+    tx = [dev(cuda, x).requires_grad_(with_dx) for x in xs]
     tw = dev(cuda, w).requires_grad_()
     tb = cuda.zeros(w.shape[3], device="cuda", requires_grad=True) if bias else None
-    ys = ssd.conv3x3_same(tx, tw, tb)
+    ys = ssd.conv_same(tx, tw, stride=stride, bias=tb)
     cuda.autograd.backward(ys, [dev(cuda, d) for d in dys])
-    return [t.grad.cpu().numpy() for t in tx], tw.grad.cpu().numpy(), tb.grad.cpu().numpy() if bias else None
+    return [t.grad.cpu().numpy() for t in tx] if with_dx else None, tw.grad.cpu().numpy(), tb.grad.cpu().numpy() if bias else None
 
 
-def conv_backward_raw(ssd, cuda, xs, w, dys, with_dx, with_dbias, sentinel=-7.5):
-    """ssd_conv3x3_train_backward straight through the C ABI: out = NULL for every level unless with_dx, dbias_dev = NULL unless
-    with_dbias.  -> ([dx] or None, dw, the dbias buffer -- pre-filled with `sentinel`, passed to the call only with_dbias)."""
-    L, Lv = ssd.lib(), ssd._lib.SsdConvLevel
-    n, B, Cin, Cout = len(xs), xs[0].shape[0], w.shape[2], w.shape[3]
+def _conv_raw(ssd, cuda, which, general, X, DY, OUT, Wt, stride, *ptrs):
+    """One call of ssd_conv3x3_train_<which> -- general: of ssd_conv_train_<which> with k from the kernel, `stride` and, for the
+    forward, up = NULL -- with a workspace of exactly the size its planner asks for.  -> that size."""
+    L = ssd.lib()
+    lv = (ssd._lib.SsdConvLevel * len(X))()
+    for i, x in enumerate(X):
+        lv[i].H, lv[i].W, lv[i].x = x.shape[1], x.shape[2], x.data_ptr()
+        lv[i].dy, lv[i].out = DY[i].data_ptr() if DY else None, OUT[i].data_ptr() if OUT else None
+    k, _, Cin, Cout = Wt.shape
+    dims = (lv, len(X), X[0].shape[0], Cin, Cout)
+    need = L.ssd_conv_train_workspace_bytes(*dims, k, stride, 0) if general else L.ssd_conv3x3_train_workspace_bytes(*dims)
+    assert need > 0
+    ws = cuda.empty(need, dtype=cuda.uint8, device="cuda")
+    tail = (ws.data_ptr(), ws.numel(), ctypes.c_void_p(cuda.cuda.current_stream().cuda_stream))
+    if general:
+        up = (None,) if which == "forward" else ()
+        ssd._lib.check(getattr(L, "ssd_conv_train_" + which)(*dims, k, stride, Wt.data_ptr(), *ptrs, *up, *tail))
+    else:
+        ssd._lib.check(getattr(L, "ssd_conv3x3_train_" + which)(*dims, Wt.data_ptr(), *ptrs, *tail))
+    return need
+
+
+def conv_forward_raw(ssd, cuda, xs, w, bias, general=False, stride=1):
+    """The forward straight through the C ABI (general: see _conv_raw); outputs pre-filled with NaN.  -> ([y], workspace bytes)."""
+    X, Wt = [dev(cuda, x) for x in xs], dev(cuda, w)
+    Y = [cuda.full((x.shape[0], -(-x.shape[1] // stride), -(-x.shape[2] // stride), w.shape[3]), float("nan"), device="cuda") for x in xs]
+    tb = dev(cuda, bias) if bias is not None else None
+    need = _conv_raw(ssd, cuda, "forward", general, X, None, Y, Wt, stride, tb.data_ptr() if bias is not None else None)
+    return [y.cpu().numpy() for y in Y], need
+
+
+def conv_backward_raw(ssd, cuda, xs, w, dys, with_dx, with_dbias, sentinel=-7.5, general=False, stride=1):
+    """The backward straight through the C ABI (general: see _conv_raw): out = NULL for every level unless with_dx, dbias_dev = NULL
+    unless with_dbias.  -> ([dx] or None, dw, the dbias buffer -- pre-filled with `sentinel`, passed to the call only with_dbias)."""
     X, DY, Wt = [dev(cuda, x) for x in xs], [dev(cuda, d) for d in dys], dev(cuda, w)
     DX = [cuda.full_like(x, float("nan")) for x in X] if with_dx else None
     dw = cuda.full_like(Wt, float("nan"))
-    db = cuda.full(((Cout + 3) // 4 * 4,), sentinel, device="cuda")
-    lv = (Lv * n)()
-    for i in range(n):
-        lv[i].H, lv[i].W = xs[i].shape[1], xs[i].shape[2]
-        lv[i].x, lv[i].dy, lv[i].out = X[i].data_ptr(), DY[i].data_ptr(), DX[i].data_ptr() if with_dx else None
-    need = L.ssd_conv3x3_train_workspace_bytes(lv, n, B, Cin, Cout)
-    assert need > 0
-    ws = cuda.empty(need, dtype=cuda.uint8, device="cuda")
-    s = ctypes.c_void_p(cuda.cuda.current_stream().cuda_stream)
-    ssd._lib.check(L.ssd_conv3x3_train_backward(lv, n, B, Cin, Cout, Wt.data_ptr(), dw.data_ptr(), db.data_ptr() if with_dbias else None,
-                                                ws.data_ptr(), ws.numel(), s))
+    db = cuda.full(((w.shape[3] + 3) // 4 * 4,), sentinel, device="cuda")
+    _conv_raw(ssd, cuda, "backward", general, X, DY, DX, Wt, stride, dw.data_ptr(), db.data_ptr() if with_dbias else None)
     return [d.cpu().numpy() for d in DX] if with_dx else None, dw.cpu().numpy(), db.cpu().numpy()
 
 

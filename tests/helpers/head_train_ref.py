@@ -1,55 +1,14 @@
-"""Float64 numpy restatement of the TRAIN head (include/ssd_hip.h, "the TRAIN head"): the 3x3 'same' convolution and the
-training-mode batch norm + ReLU with their gradients, and the whole RetinaNetBoxPredictor (box_predictor.py:34-155) forward and
-backward; plus the float32 restatement of the batch norm in the header's operation order."""
+"""Float64 numpy restatement of the TRAIN head (include/ssd_hip.h, "the TRAIN head"): the training-mode batch norm + ReLU with its
+gradients and the whole RetinaNetBoxPredictor (box_predictor.py:34-155) forward and backward over helpers.train_ops_ref's
+convolution (re-exported here: the head is its k = 3, stride 1 case); plus the float32 restatement of the batch norm in the
+header's operation order."""
 import numpy as np
+
+from helpers.train_ops_ref import conv, conv_grads, integer_premise, rotated_transposed, rows_per_slice, wgrad_bound   # noqa: F401
 
 EPS = 1e-3
 MOMENTUM = 0.993
 f32 = np.float32
-
-
-def _shifted(x, kh, kw):
-    """x [B,H,W,C] -> the tensor a 'same' 3x3 tap (kh, kw) reads: x[b, y+kh-1, x+kw-1], zero outside."""
-    B, H, W, C = x.shape
-    p = np.zeros((B, H + 2, W + 2, C), x.dtype)
-    p[:, 1:H + 1, 1:W + 1] = x
-    return p[:, kh:kh + H, kw:kw + W]
-
-
-def conv3x3(x, w, bias=None):
-    y = np.zeros(x.shape[:3] + (w.shape[3],), np.float64)
-    for kh in range(3):
-        for kw in range(3):
-            y += _shifted(x.astype(np.float64), kh, kw) @ w[kh, kw].astype(np.float64)
-    return y if bias is None else y + bias.astype(np.float64)
-
-
-def conv3x3_grads(xs, w, dys, absolute=False):
-    """Levels xs, dys -> ([dx per level], dw, dbias).  absolute=True: the sums of |x * dy| per dw element instead of dw."""
-    w = w.astype(np.float64)
-    dw = np.zeros(w.shape, np.float64)
-    db = np.zeros(w.shape[3], np.float64)
-    dxs = []
-    for x, dy in zip(xs, dys):
-        x, dy = x.astype(np.float64), dy.astype(np.float64)
-        dx = np.zeros(x.shape, np.float64)
-        B, H, W, _ = x.shape
-        pad = np.zeros((B, H + 2, W + 2, x.shape[3]), np.float64)
-        for kh in range(3):
-            for kw in range(3):
-                xs_ = _shifted(x, kh, kw)
-                a2, d2 = xs_.reshape(-1, xs_.shape[3]), dy.reshape(-1, dy.shape[3])
-                dw[kh, kw] += np.abs(a2).T @ np.abs(d2) if absolute else a2.T @ d2
-                pad[:, kh:kh + H, kw:kw + W] += dy @ w[kh, kw].T
-        dx = pad[:, 1:H + 1, 1:W + 1]
-        db += dy.sum((0, 1, 2))
-        dxs.append(dx)
-    return dxs, dw, db
-
-
-def rotated_transposed(w):
-    """w'[kh,kw,co,ci] = w[2-kh,2-kw,ci,co]: the data gradient is conv3x3_same(dy, w')."""
-    return np.ascontiguousarray(w[::-1, ::-1].transpose(0, 1, 3, 2))
 
 
 def bn_relu_forward(x, gamma, beta, eps=EPS):
@@ -122,7 +81,7 @@ def predictor(W, feats, num_classes, training=True, d_boxes=None, d_classes=None
         tape = []
         for i in range(4):
             k = W["%s/conv3x3_%d/kernel" % (net, i)]
-            c = [conv3x3(v, k) for v in x]
+            c = [conv(v, k) for v in x]
             y = []
             for l in range(n):
                 s = "%s/batch_norm_%d_for_level_%d" % (net, i, 3 + l)
@@ -133,7 +92,7 @@ def predictor(W, feats, num_classes, training=True, d_boxes=None, d_classes=None
                     y.append(np.maximum((c[l] - W[s + "/moving_mean"]) * sf + W[s + "/beta"], 0.0))
             tape.append((x, c))
             x = y
-        o = [conv3x3(v, W["%s/%s/kernel" % (net, last)], W["%s/%s/bias" % (net, last)]) for v in x]
+        o = [conv(v, W["%s/%s/kernel" % (net, last)], bias=W["%s/%s/bias" % (net, last)]) for v in x]
         tapes[net] = (tape, x, [v.shape for v in o])
         outs[net] = np.concatenate([v.reshape(B, -1, width) for v in o], axis=1)
     if d_boxes is None:
@@ -147,7 +106,7 @@ def predictor(W, feats, num_classes, training=True, d_boxes=None, d_classes=None
             cnt = s[1] * s[2] * s[3] // d.shape[2]
             dys.append(d[:, at:at + cnt].reshape(s))
             at += cnt
-        dxs, dw, db = conv3x3_grads(xlast, W["%s/%s/kernel" % (net, last)], dys)
+        dxs, dw, db = conv_grads(xlast, W["%s/%s/kernel" % (net, last)], dys)
         grads["%s/%s/kernel" % (net, last)], grads["%s/%s/bias" % (net, last)] = dw, db
         for i in range(3, -1, -1):
             x, c = tape[i]
@@ -157,7 +116,7 @@ def predictor(W, feats, num_classes, training=True, d_boxes=None, d_classes=None
                 dx, dg, dbt = bn_relu_backward(c[l], W[s + "/gamma"], W[s + "/beta"], dxs[l])
                 grads[s + "/gamma"], grads[s + "/beta"] = dg, dbt
                 dc.append(dx)
-            dxs, dw, _ = conv3x3_grads(x, W["%s/conv3x3_%d/kernel" % (net, i)], dc)
+            dxs, dw, _ = conv_grads(x, W["%s/conv3x3_%d/kernel" % (net, i)], dc)
             grads["%s/conv3x3_%d/kernel" % (net, i)] = dw
         for l in range(n):
             dfeats[l] += dxs[l]
@@ -202,13 +161,6 @@ def slab_plan(rows, C):
     sr = max(8 * rpp, -(-sum(rows) // 1024))
     sr = -(-sr // rpp) * rpp
     return rpp, sr, sum(-(-r // sr) for r in rows)
-
-
-def rows_per_slice(rows, Cin, Cout):
-    """include/ssd_hip.h's K-slice of the weight gradient for these per-level rows."""
-    tiles = 9 * (-(-Cin // 128)) * (-(-Cout // (32 if Cout <= 32 else 128)))
-    want = max(1, 1536 // tiles)
-    return -(-max(256, -(-sum(rows) // want)) // 16) * 16
 
 
 def bn_gate_f32(x, gamma, beta, mean, var, dy, eps=EPS):
@@ -285,25 +237,6 @@ def conv_case_data(name, integers):
         w = rng.normal(0, 0.05, (3, 3, Cin, Cout)).astype(f32)
         bias = rng.normal(0, 0.1, Cout).astype(f32)
     return B, sizes, xs, w, bias, dys
-
-
-def integer_premise(xs, w, dys):
-    """-> (dw64, dbias64, largest absolute partial sum of dw, of dbias): below 2^24 every partial sum of integers is exact in
-    float32 in ANY order."""
-    _, dw64, db64 = conv3x3_grads(xs, w, dys)
-    _, absum, _ = conv3x3_grads(xs, w, dys, absolute=True)
-    return dw64, db64, float(absum.max()), float(sum(np.abs(d).sum((0, 1, 2)).max() for d in dys))
-
-
-def wgrad_bound(xs, w, dys):
-    """-> (dw64, bound, absum): |dw - dw64| <= gamma_n * sum|x * dy| per element, n its number of products, gamma_n = n u / (1 - n u),
-    u = 2^-24: the bound of ANY order of float32 accumulation of exact products (the matrix instruction's products are exact in
-    its accumulator's sum)."""
-    _, dw64, _ = conv3x3_grads(xs, w, dys)
-    _, absum, _ = conv3x3_grads(xs, w, dys, absolute=True)
-    _, n, _ = conv3x3_grads([np.ones(x.shape) for x in xs], w, [np.ones(d.shape) for d in dys])
-    u = 2.0 ** -24
-    return dw64, n * u / (1 - n * u) * absum, absum
 
 
 # ----------------------------------------------------------------------------- the predictor's whole-graph inputs

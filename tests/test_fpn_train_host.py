@@ -18,7 +18,7 @@ def test_reference_gradients_agree_with_finite_differences(k, stride, with_up):
     OH, OW = ref.out_hw(H, W, stride)
     dy = rng.normal(0, 1, (B, OH, OW, Cout))
     assert ref.conv(x, w, stride).shape == dy.shape
-    (dx,), dw = ref.conv_grads([x], w, [dy], stride)
+    (dx,), dw, _ = ref.conv_grads([x], w, [dy], stride)
     loss = lambda x_, w_: float((ref.conv(x_, w_, stride) * dy).sum())
     h = 1e-3
     for arr, grad, which in ((x, dx, 0), (w, dw, 1)):
@@ -54,7 +54,7 @@ def test_dilation_identity_holds_exactly_on_integers(H, W):
     w = rng.integers(-2, 3, (3, 3, Cin, Cout)).astype(f32)
     OH, OW = ref.out_hw(H, W, 2)
     dy = rng.integers(-3, 4, (B, OH, OW, Cout)).astype(f32)
-    (dx,), _ = ref.conv_grads([x], w, [dy], 2)
+    (dx,), _, _ = ref.conv_grads([x], w, [dy], 2)
     D = ref.dilate(dy, H, W)
     assert D.sum() == dy.sum() and np.array_equal(D[:, ::2, ::2], dy)
     assert np.array_equal(ref.conv(D, href.rotated_transposed(w), 1), dx) and np.abs(dx).max() > 0

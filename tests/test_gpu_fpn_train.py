@@ -9,7 +9,7 @@ import pytest
 
 from helpers import fpn_train_ref as ref
 from helpers import head_train_ref as href
-from helpers.head_train_gpu import dev as _dev, same_bits
+from helpers.head_train_gpu import conv_backward, conv_backward_raw, conv_forward_raw, dev as _dev, same_bits
 from conftest import TINY_PARAMS
 
 pytestmark = pytest.mark.gpu
@@ -27,15 +27,6 @@ def _data(rng, shape, integers=False, scale=1.0):
 
 def _kernel(rng, k, Cin, Cout, integers=False):
     return rng.integers(-2, 3, (k, k, Cin, Cout)).astype(f32) if integers else rng.normal(0, 0.05, (k, k, Cin, Cout)).astype(f32)
-
-
-def _grads(ssd, cuda, xs, w, dys, stride, with_dx):
-    """conv_same's gradients through autograd: ([dx] or None, dw) as numpy."""
-    tx = [_dev(cuda, x).requires_grad_(with_dx) for x in xs]
-    tw = _dev(cuda, w).requires_grad_()
-    ys = ssd.conv_same(tx, tw, stride=stride)
-    cuda.autograd.backward(ys, [_dev(cuda, d) for d in dys])
-    return ([t.grad.cpu().numpy() for t in tx] if with_dx else None), tw.grad.cpu().numpy()
 
 
 # ----------------------------------------------------------------------------- 1. the forward
@@ -85,7 +76,7 @@ def test_stride_2_data_gradient_is_the_oracles_convolution_of_the_dilated_gradie
     xs = [_data(rng, (B, h, w, Cin)) for h, w in sizes]
     dys = [_data(rng, (B,) + ref.out_hw(h, w, 2) + (Cout,)) for h, w in sizes]
     w = _kernel(rng, 3, Cin, Cout)
-    dxs, _ = _grads(ssd, cuda, xs, w, dys, 2, True)
+    dxs, _, _ = conv_backward(ssd, cuda, xs, w, dys, stride=2, bias=False)
     wr = href.rotated_transposed(w)
     for (h, ww), dy, dx in zip(sizes, dys, dxs):
         want = oracle_ops.conv2d(ref.dilate(dy, h, ww), wr)
@@ -99,9 +90,9 @@ def _exact_case(ssd, cuda, sizes, k, stride, Cin, Cout, seed):
     xs = [_data(rng, (B, h, w, Cin), True) for h, w in sizes]
     dys = [_data(rng, (B,) + ref.out_hw(h, w, stride) + (Cout,), True) for h, w in sizes]
     w = _kernel(rng, k, Cin, Cout, True)
-    dw64, absmax = ref.integer_premise(xs, w, dys, stride)
+    dw64, _, absmax, _ = ref.integer_premise(xs, w, dys, stride)
     assert absmax < 2 ** 24 and np.abs(dw64).max() > 0                # the premise, checked
-    _, dw = _grads(ssd, cuda, xs, w, dys, stride, False)
+    _, dw, _ = conv_backward(ssd, cuda, xs, w, dys, stride=stride, bias=False, with_dx=False)
     assert dw.shape == w.shape and np.array_equal(dw.astype(np.float64), dw64)
 
 
@@ -127,20 +118,59 @@ def test_weight_gradient_is_exact_over_several_slices_and_two_levels(ssd, cuda):
 
 
 def test_3x3_stride_1_through_the_new_entry_point_is_the_old_one_bit_for_bit(ssd, cuda):
+    """ssd_conv3x3_train_* and ssd_conv_train_* with k = 3, stride = 1, up = NULL, both straight through the C ABI: the same
+    workspace size and the same bits in the outputs, dx, dw and dbias; conv3x3_same through autograd gives those bits too."""
     rng = np.random.default_rng(9)
     sizes, Cin, Cout = [(13, 17), (4, 5)], 64, 40
     xs = [_data(rng, (B, h, w, Cin)) for h, w in sizes]
     dys = [_data(rng, (B, h, w, Cout)) for h, w in sizes]
-    w = _kernel(rng, 3, Cin, Cout)
-    dxs, dw = _grads(ssd, cuda, xs, w, dys, 1, True)
+    w, bias = _kernel(rng, 3, Cin, Cout), _data(rng, (Cout,), scale=0.1)
+    ys_old, need_old = conv_forward_raw(ssd, cuda, xs, w, bias)
+    ys_new, need_new = conv_forward_raw(ssd, cuda, xs, w, bias, general=True)
+    dxs_old, dw_old, db_old = conv_backward_raw(ssd, cuda, xs, w, dys, True, True)
+    dxs_new, dw_new, db_new = conv_backward_raw(ssd, cuda, xs, w, dys, True, True, general=True)
+    assert need_old == need_new
     tx = [_dev(cuda, x).requires_grad_() for x in xs]
-    tw = _dev(cuda, w).requires_grad_()
-    ys_old = ssd.conv3x3_same(tx, tw)
-    cuda.autograd.backward(ys_old, [_dev(cuda, d) for d in dys])
-    ys_new = ssd.conv_same([_dev(cuda, x) for x in xs], _dev(cuda, w))
-    for a, b_, c, d in zip(ys_old, ys_new, tx, dxs):
-        assert cuda.equal(a.detach(), b_) and same_bits(c.grad.cpu().numpy(), d)
-    assert same_bits(tw.grad.cpu().numpy(), dw)
+    tw, tb = _dev(cuda, w).requires_grad_(), _dev(cuda, bias).requires_grad_()
+    ys = ssd.conv3x3_same(tx, tw, tb)
+    cuda.autograd.backward(ys, [_dev(cuda, d) for d in dys])
+    for old, new, got in zip(ys_old + dxs_old, ys_new + dxs_new, [y.detach() for y in ys] + [t.grad for t in tx]):
+        assert np.isfinite(old).all() and same_bits(old, new) and same_bits(old, got.cpu().numpy())
+    assert same_bits(dw_old, dw_new) and same_bits(dw_old, tw.grad.cpu().numpy()) and np.abs(dw_old).max() > 0
+    assert same_bits(db_old, db_new) and same_bits(db_old[:Cout], tb.grad.cpu().numpy()) and np.abs(db_old).max() > 0
+
+
+def test_partial_needs_give_the_bits_of_a_zero_gradient(ssd, cuda):
+    """Only level 0's output is differentiated and only x0 requires a gradient: x1 gets none, and x0.grad and dw have the bits of a
+    run where both outputs are used and level 1's dy is all zeros."""
+    rng = np.random.default_rng(21)
+    sizes, Cin, Cout = [(4, 6), (2, 2)], 8, 16
+    xs = [_data(rng, (B, h, w, Cin)) for h, w in sizes]
+    w, dy0 = _kernel(rng, 3, Cin, Cout), _data(rng, (B, 4, 6, Cout))
+    x0, x1, tw = _dev(cuda, xs[0]).requires_grad_(), _dev(cuda, xs[1]), _dev(cuda, w).requires_grad_()
+    ys = ssd.conv_same([x0, x1], tw)
+    (ys[0] * _dev(cuda, dy0)).sum().backward()
+    assert x1.grad is None
+    dxs, dw, _ = conv_backward(ssd, cuda, xs, w, [dy0, np.zeros((B, 2, 2, Cout), f32)], bias=False)
+    assert same_bits(x0.grad.cpu().numpy(), dxs[0]) and same_bits(tw.grad.cpu().numpy(), dw) and np.abs(dw).max() > 0
+
+
+def test_up_with_a_gradient_and_features_without(ssd, cuda):
+    """1x1 with `up`, two levels, only up[0] requiring a gradient: it is fpn_merge_backward(dy0), up[1] gets none and nothing
+    raises; once a feature requires a gradient the backward raises the 1x1 RuntimeError."""
+    rng = np.random.default_rng(46)
+    Cin, Cout = 116, 256
+    xs = [_dev(cuda, _data(rng, (B, 4, 6, Cin))), _dev(cuda, _data(rng, (B, 2, 2, Cin)))]
+    ups = [_dev(cuda, _data(rng, (B, 2, 3, Cout))).requires_grad_(), _dev(cuda, _data(rng, (B, 1, 1, Cout)))]
+    w = _dev(cuda, _kernel(rng, 1, Cin, Cout))
+    dys = [_dev(cuda, _data(rng, (B, 4, 6, Cout))), _dev(cuda, _data(rng, (B, 2, 2, Cout)))]
+    cuda.autograd.backward(ssd.conv_same(xs, w, up=ups), dys)
+    assert ups[1].grad is None and float(ups[0].grad.abs().max()) > 0
+    assert same_bits(ups[0].grad.cpu().numpy(), ssd.fpn_merge_backward(dys[0]).cpu().numpy())
+    xs[0].requires_grad_()
+    ys = ssd.conv_same(xs, w, up=ups)
+    with pytest.raises(RuntimeError, match="1x1"):
+        cuda.autograd.backward(ys, dys)
 
 
 # ----------------------------------------------------------------------------- 4. the weight gradient on random data
@@ -154,11 +184,11 @@ def test_weight_gradient_obeys_the_order_free_fp32_bound(ssd, cuda, k, stride, C
     dys = [_data(rng, (B,) + ref.out_hw(h, w, stride) + (Cout,)) for h, w in sizes]
     w = _kernel(rng, k, Cin, Cout)
     dw64, bound, absum = ref.wgrad_bound(xs, w, dys, stride)
-    _, dw = _grads(ssd, cuda, xs, w, dys, stride, False)
+    _, dw, _ = conv_backward(ssd, cuda, xs, w, dys, stride=stride, bias=False, with_dx=False)
     err = np.abs(dw.astype(np.float64) - dw64)
     print("fpn wgrad k=%d s=%d %d->%d: max |dw - dw64| / sum|x dy| = %.3g" % (k, stride, Cin, Cout, (err / absum).max()))
     assert np.isfinite(dw).all() and np.all(err <= bound) and np.abs(dw64).max() > 0
-    _, dw2 = _grads(ssd, cuda, xs, w, dys, stride, False)
+    _, dw2, _ = conv_backward(ssd, cuda, xs, w, dys, stride=stride, bias=False, with_dx=False)
     assert same_bits(dw, dw2)
 
 

@@ -40,6 +40,17 @@ def test_forward_is_ssd_conv2d_bit_for_bit(ssd, cuda, Cin, Cout):
     assert cuda.equal(one, ssd.ssd.conv2d(_dev(cuda, xs[1]), w))
 
 
+def test_conv3x3_same_refuses_what_it_refused(ssd, cuda):
+    """A kernel that is not 3x3 and a level of another width are ValueErrors; a single tensor in gives a single tensor out."""
+    x = cuda.zeros((B, 4, 6, 8), device="cuda")
+    with pytest.raises(ValueError):
+        ssd.conv3x3_same(x, cuda.zeros((1, 1, 8, 16), device="cuda"))
+    with pytest.raises(ValueError):
+        ssd.conv3x3_same([x, cuda.zeros((B, 4, 6, 12), device="cuda")], cuda.zeros((3, 3, 8, 16), device="cuda"))
+    y = ssd.conv3x3_same(x, cuda.zeros((3, 3, 8, 16), device="cuda"))
+    assert isinstance(y, cuda.Tensor) and tuple(y.shape) == (B, 4, 6, 16)
+
+
 @pytest.mark.parametrize("Cin,Cout", SHAPES)
 def test_data_gradient_is_the_oracles_convolution_bit_for_bit(ssd, cuda, oracle_ops, Cin, Cout):
     rng = np.random.default_rng(Cin * 3 + Cout)
@@ -61,8 +72,8 @@ def test_weight_gradient_is_exact_on_small_integers(ssd, cuda, Cin, Cout, nlev):
     sizes = PYRAMID[:nlev]
     xs, dys = _levels(rng, sizes, Cin, True), _levels(rng, sizes, Cout, True)
     w = rng.integers(-2, 3, (3, 3, Cin, Cout)).astype(f32)
-    _, dw64, db64 = ref.conv3x3_grads(xs, w, dys)
-    _, absum, _ = ref.conv3x3_grads(xs, w, dys, absolute=True)
+    _, dw64, db64 = ref.conv_grads(xs, w, dys)
+    _, absum, _ = ref.conv_grads(xs, w, dys, absolute=True)
     assert absum.max() < 2 ** 24 and sum(np.abs(d).sum((0, 1, 2)).max() for d in dys) < 2 ** 24       # the premise, checked
     assert np.abs(dw64).max() > 0
     _, dw, db = _backward(ssd, cuda, xs, w, dys)
@@ -77,10 +88,10 @@ def test_weight_gradient_obeys_the_order_free_fp32_bound(ssd, cuda, Cin, Cout):
     rng = np.random.default_rng(Cin * 7 + Cout)
     xs, dys = _levels(rng, PYRAMID, Cin), _levels(rng, PYRAMID, Cout)
     w = rng.normal(0, 0.05, (3, 3, Cin, Cout)).astype(f32)
-    _, dw64, db64 = ref.conv3x3_grads(xs, w, dys)
-    _, absum, _ = ref.conv3x3_grads(xs, w, dys, absolute=True)
+    _, dw64, db64 = ref.conv_grads(xs, w, dys)
+    _, absum, _ = ref.conv_grads(xs, w, dys, absolute=True)
     ones = lambda c: [np.ones((B, h, ww, c)) for h, ww in PYRAMID]
-    _, n, _ = ref.conv3x3_grads(ones(Cin), w, ones(Cout))
+    _, n, _ = ref.conv_grads(ones(Cin), w, ones(Cout))
     u = 2.0 ** -24
     bound = n * u / (1 - n * u) * absum
     _, dw, db = _backward(ssd, cuda, xs, w, dys)
@@ -105,8 +116,8 @@ def test_weight_gradient_is_exact_with_many_slices_per_level(ssd, cuda, Cin, Cou
     L, Lv = ssd.lib(), ssd._lib.SsdConvLevel
     lv = (Lv * 3)(*[Lv(h, ww, None, None, None) for h, ww in sizes])
     assert L.ssd_conv3x3_train_workspace_bytes(lv, 3, B, Cin, Cout) > 0
-    _, dw64, db64 = ref.conv3x3_grads(xs, w, dys)
-    _, absum, _ = ref.conv3x3_grads(xs, w, dys, absolute=True)
+    _, dw64, db64 = ref.conv_grads(xs, w, dys)
+    _, absum, _ = ref.conv_grads(xs, w, dys, absolute=True)
     assert absum.max() < 2 ** 24 and sum(np.abs(d).sum((0, 1, 2)).max() for d in dys) < 2 ** 24
     _, dw, db = _backward(ssd, cuda, xs, w, dys)
     assert np.array_equal(dw.astype(np.float64), dw64) and np.array_equal(db.astype(np.float64), db64)
@@ -123,8 +134,8 @@ def test_layers_wider_than_1024_channels(ssd, cuda, Cout):
     bias = rng.integers(-4, 5, Cout).astype(f32)
     ys = ssd.conv3x3_same([_dev(cuda, x) for x in xs], _dev(cuda, w), _dev(cuda, bias))
     for x, y in zip(xs, ys):
-        assert np.array_equal(y.cpu().numpy().astype(np.float64), ref.conv3x3(x, w, bias))
-    dx64, dw64, db64 = ref.conv3x3_grads(xs, w, dys)
+        assert np.array_equal(y.cpu().numpy().astype(np.float64), ref.conv(x, w, bias=bias))
+    dx64, dw64, db64 = ref.conv_grads(xs, w, dys)
     assert max(np.abs(d).max() for d in dx64) < 2 ** 24 and np.abs(dw64).max() < 2 ** 24
     dxs, dw, db = _backward(ssd, cuda, xs, w, dys)
     for got, want in zip(dxs, dx64):

@@ -91,8 +91,8 @@ def test_helper_equals_torch_autograd(B, sizes, nc):
 def test_data_gradient_is_the_convolution_with_the_rotated_transposed_kernel():
     rng = np.random.default_rng(3)
     x, w, dy = rng.normal(0, 1, (2, 5, 7, 8)), rng.normal(0, 1, (3, 3, 8, 6)), rng.normal(0, 1, (2, 5, 7, 6))
-    dxs, _, _ = ref.conv3x3_grads([x], w, [dy])
-    assert _rel(ref.conv3x3(dy, ref.rotated_transposed(w)), dxs[0]) <= 1e-13
+    dxs, _, _ = ref.conv_grads([x], w, [dy])
+    assert _rel(ref.conv(dy, ref.rotated_transposed(w)), dxs[0]) <= 1e-13
 
 
 def _conv_call(L, which, a):
