@@ -557,7 +557,7 @@ int ssd_train_update(const ssd_update_tensor *tensors_host, const ssd_update_ten
  * change every step), scratch from a caller-supplied workspace, every call only enqueues on `stream` (no allocation, no host
  * round trip, no synchronisation), arguments are refused with SSD_ERR_INVALID before any HIP call, no handle.  No atomics
  * anywhere: two calls give the same bits.  Not here: strides other than 1 and 1x1 kernels (the TRAIN FPN block below), depthwise
- * backward, F16X3, double backward.
+ * backward (the TRAIN backbone block below), F16X3, double backward.
  *
  * A convolution call takes 1 .. SSD_TRAIN_MAX_LEVELS levels that share B, Cin, Cout and ONE kernel; the weight gradient is the
  * sum over all of them.  Cin must be a multiple of 8, Cin and Cout at most 4096, every level's tensors (channels padded to 32)
@@ -696,6 +696,69 @@ int ssd_conv_train_backward(const ssd_conv_level *levels, int32_t n_levels, int3
                             float *dbias_dev /* [Cout] or NULL */, void *workspace_dev, size_t workspace_bytes, void *stream);
 int ssd_fpn_merge_backward(const float *base_dev, const float *g_dev, const float *gate_dev, int32_t B, int32_t H, int32_t W,
                            int32_t C, int32_t same_size, float *out_dev, void *stream);
+
+/* ---- the TRAIN backbone: forward and backward of MobileNet-v1's Conv2d_1 .. Conv2d_13 in TRAIN mode (mobilenet_v1.py:52-67) ----
+ *
+ * Each of the 13 blocks is a 3x3 depthwise convolution ('SAME', stride 1 or 2) and a 1x1 convolution, each followed by a
+ * training-mode batch norm and ReLU6.  These calls are the operations the TRAIN head and the TRAIN FPN lack for it: the raw
+ * depthwise convolution with its two gradients, the data gradient of a 1x1 convolution, and the batch norm with ReLU6.  Conv2d_0
+ * (3 -> 32, stride 2) stays FROZEN: it runs through ssd_first_conv on its moving statistics and has no gradient here.
+ * Conventions as for the TRAIN head: the caller's device pointers, logical NHWC fp32, TF-layout kernels in DEVICE memory, the
+ * caller's workspace, SSD_ERR_INVALID before any HIP call, enqueue only, no atomics: two calls give the same bits.  Every existing
+ * entry point keeps its arguments, its refusals and its bits (ssd_conv_train_backward still refuses dx with k = 1).  Not here:
+ * ShuffleNet's split and shuffle, Conv2d_0's weight gradient, F16X3, double backward.
+ *
+ * The depthwise calls: x [B,H,W,C], w_dev [3,3,C,1] (= [9][C]), out / dy [B,OH,OW,C] with OH = ceil(H / stride), OW likewise, and
+ * pad_beg = p = max((OH - 1) * stride + 3 - H, 0) / 2 (TF 'SAME': 1 for stride 1; for stride 2, 0 on even and 1 on odd sizes).
+ * C a multiple of 4; stride 1 or 2; stride 2 with H and W of different parity is refused (one pad_beg serves both axes); B <= 65536,
+ * H, W <= 32768, B*H*W < 2^31, fewer than 2^40 elements; every pointer 16-byte aligned.
+ *
+ * ssd_depthwise_train_forward   raw tf.nn.depthwise_conv2d: ssd_depthwise3x3's kernel on the caller's device weights without batch
+ *   norm and activation -- per output ONE fmaf chain from +0 over the taps row-major, a tap outside the input contributing
+ *   fmaf(0, w, acc): bit-identical to ssd_depthwise3x3 (no batch norm, no activation) and to the CPU oracle's depthwise3x3.
+ * ssd_depthwise_train_backward  (C <= 1024) from x, dy, w:
+ *   dx_dev [B,H,W,C] (nullable)   dx[b,iy,ix,c] = sum of dy[b,(iy+p-ky)/s,(ix+p-kx)/s,c] * w[ky,kx,c] over the taps whose source
+ *     index is an integer inside the output.  Order: ONE fmaf chain per element from +0 over the taps of the flipped kernel
+ *     row-major, i.e. ky = 2, 1, 0 and within each kx = 2, 1, 0; taps without a source are SKIPPED.  On finite data that is
+ *     bit-identical to the CPU oracle's depthwise3x3(E, flip(w), stride 1), E [B,H,W,C] zero except E[b,s*oy+1-p,s*ox+1-p,:] =
+ *     dy[b,oy,ox,:] (stride 1: E = dy): a chain that starts at +0 never holds -0, so the oracle's fmaf(0, w, acc) is acc.  E is
+ *     never materialised.
+ *   dw_dev [3,3,C,1]   dw[ky,kx,c] = sum over b, oy, ox of x[b,oy*s+ky-p,ox*s+kx-p,c] * dy[b,oy,ox,c] (positions outside the input
+ *     contribute nothing): 9 * C column sums over the OUTPUT rows r = (b * OH + oy) * OW + ox, products and sums in double, rounded
+ *     ONCE.  Fixed two-stage order, the batch norm's: with G = C / 4, rpp = 256 / G and slab_rows = max(8 * rpp,
+ *     ceil(B*OH*OW / 1024)) rounded up to a multiple of rpp, the rows are cut into slabs of slab_rows; inside a slab row lane
+ *     j = (r - slab start) mod rpp adds its rows in ascending order, the lanes are added in ascending j, the slabs in ascending
+ *     order.  The partial sums ([slabs][9][C] doubles) live in the workspace.
+ *
+ * ssd_pointwise_train_backward  ssd_conv_train_backward with k = 1 that also gives the data gradient: levels, B, Cin, Cout, w_dev
+ *   [1,1,Cin,Cout] and dw_dev as there (Cin a multiple of 4; dw_dev: the same launches and bits); dx goes to levels[l].out, for
+ *   every level or for none: dx_l = conv1x1(dy_l, w'), w'[0,0,co,ci] = w[0,0,ci,co] packed on the device, on the forward's exact-fp32
+ *   implicit GEMM: ONE fmaf chain per element, co ascending -- bit-identical to the CPU oracle's conv2d(dy, w').  The reduction
+ *   side (Cout) is zero padded to a multiple of 32.  ssd_pointwise_train_workspace_bytes sizes its workspace (0: refused sizes).
+ *
+ * ssd_bn_act_train_forward / _backward are ssd_bn_relu_train_forward / _backward with one more argument, act = SSD_ACT_RELU or
+ * SSD_ACT_RELU6 (anything else is refused); the old pair IS these calls with SSD_ACT_RELU: same planner, same launches, same bits,
+ * and ssd_bn_relu_train_workspace_bytes sizes both.  With SSD_ACT_RELU6:
+ *     forward    out = min(max(y, 0), 6) as v = y > 0 ? y : 0; v = v < 6 ? v : 6 (the inference path's activation), y as above;
+ *                training == 0 is the epilogue ssd_finalize folds into the engine's layers, bit for bit
+ *     backward   g = (y > 0 && y < 6) ? dy : 0 with y recomputed from x and the saved statistics; the rest as above
+ *   A NaN y gives out = 0 and a closed gate; y == 6 closes the gate as y == 0 does (TF's Relu6Grad restated from memory: unpinned
+ *   against TensorFlow, like the batch norm's formulas above). */
+int ssd_depthwise_train_forward(const float *x_dev, int32_t B, int32_t H, int32_t W, int32_t C, const float *w_dev /* [3,3,C,1] */,
+                                int32_t stride, float *out_dev, void *stream);
+/* Bytes of workspace ssd_depthwise_train_backward needs (0: the sizes would be refused). */
+size_t ssd_depthwise_train_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride);
+int ssd_depthwise_train_backward(const float *x_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t C,
+                                 const float *w_dev, int32_t stride, float *dx_dev /* nullable */, float *dw_dev /* [3,3,C,1] */,
+                                 void *workspace_dev, size_t workspace_bytes, void *stream);
+size_t ssd_pointwise_train_workspace_bytes(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout);
+int ssd_pointwise_train_backward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
+                                 const float *w_dev /* [1,1,Cin,Cout] */, float *dw_dev, void *workspace_dev, size_t workspace_bytes,
+                                 void *stream);
+int ssd_bn_act_train_forward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, int32_t act, int32_t training, float epsilon,
+                             float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream);
+int ssd_bn_act_train_backward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, int32_t act, void *workspace_dev,
+                              size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
-            "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip", "train_head.hip", "wgrad.hip"]
+            "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip", "train_head.hip", "wgrad.hip", "train_backbone.hip"]
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
 _lib = None
@@ -221,6 +221,14 @@ SIGNATURES = {
                                               ctypes.c_size_t, _vp]),
     "ssd_conv_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "ssd_fpn_merge_backward": (ctypes.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ssd_depthwise_train_forward": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "ssd_depthwise_train_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
+    "ssd_depthwise_train_backward": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_pointwise_train_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i]),
+    "ssd_pointwise_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_bn_act_train_forward": (ctypes.c_int, [ctypes.POINTER(SsdBnLevel), _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _vp,
+                                                ctypes.c_size_t, _vp]),
+    "ssd_bn_act_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdBnLevel), _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
 }
 
 

@@ -1,0 +1,108 @@
+"""The trainable MobileNet-v1 backbone: detector/backbones/mobilenet_v1.py in TRAIN mode on this project's own kernels
+(include/ssd_hip.h, "the TRAIN backbone").
+
+    TrainPipeline -> TrainableMobileNet -> TrainableFPN -> TrainableBoxPredictor -> differentiable_loss -> backward (HIP)
+                  -> TrainStep over the three modules' variables (frozen = Conv2d_0) -> checkpoint -> Detector / evaluation
+
+train.py:44-50 warm-starts the backbone and then trains it with everything else; this module is that, with one difference that is
+a MODE of this project and not parity with the reference: Conv2d_0 stays FROZEN.  It runs in the engine's
+inference form (ssd.first_conv on its moving statistics); Conv2d_1 .. Conv2d_13 -- 13 depthwise and 13 pointwise layers, each
+followed by a batch norm and ReLU6 -- run on batch statistics and all their variables train.  The ops (depthwise_conv,
+pointwise_conv, batch_norm_act) and the variable loading (ReferenceVariables) are train_ops.py's; this file keeps the layer table
+and the graph.
+"""
+import numpy as np
+import torch
+
+from .train_ops import BATCH_NORM_EPSILON, ReferenceVariables, depthwise_conv, pointwise_conv
+from .variables import MOBILENET_LAYERS
+
+FIRST = "MobilenetV1/Conv2d_0"
+OUTPUTS = {5: "c3", 11: "c4", 13: "c5"}             # mobilenet_v1.py:69-73
+
+
+def mobilenet_variable_shapes(params):
+    """The backbone's subset of variables.variable_shapes(params): MobilenetV1/*, Conv2d_0 and statistics included."""
+    from .variables import variable_shapes
+    if params.get("backbone") != "mobilenet":
+        raise ValueError("mobilenet_variable_shapes: the config's backbone is %r" % (params.get("backbone"),))
+    return {k: v for k, v in variable_shapes(params).items() if k.startswith("MobilenetV1/")}
+
+
+class TrainableMobileNet(ReferenceVariables):
+    """mobilenet_v1(images, is_training, depth_multiplier) (mobilenet_v1.py:7-73) as a torch.nn.Module on the HIP kernels, with
+    Conv2d_0 frozen.
+
+    params   the model config (backbone "mobilenet", depth_multiplier <= 1.0: the batch norm takes at most 1024 channels)
+    weights  {reference variable name: float32 array in TF layout}; every MobilenetV1/* variable must be there (the reference never
+             initialises a backbone from scratch: a missing one is a KeyError, not a draw)
+    forward(images uint8 [B,H,W,3] on the GPU, at the network's size: H and W even) -> [c3, c4, c5] NHWC float32, the outputs of
+    Conv2d_5, Conv2d_11 and Conv2d_13's pointwise layers.  .train(): batch statistics through batch_norm_act, the moving statistics
+    of Conv2d_1 .. 13 move; .eval(): the engine's c3, c4, c5 bit for bit (raw depthwise, the inference batch norm + ReLU6, the raw
+    1x1, the inference batch norm + ReLU6).  named_variables() / statistics() hold Conv2d_1 .. 13 only; frozen_variables() returns
+    the Conv2d_0 arrays for TrainStep(..., frozen=backbone.frozen_variables()).  keep_features=True keeps the 26 post-activation
+    tensors of the last forward in .features under the reference's features[layer_name] names (detached)."""
+
+    def __init__(self, params, weights, device=None, seed=0, keep_features=False):
+        if params.get("backbone") != "mobilenet":
+            raise ValueError("TrainableMobileNet: the config's backbone is %r (ShuffleNet's split and shuffle have no backward here)"
+                             % (params.get("backbone"),))
+        if float(params["depth_multiplier"]) > 1.0:
+            raise ValueError("TrainableMobileNet: depth_multiplier above 1.0 is not supported (the batch norm takes at most 1024 channels)")
+        shapes = mobilenet_variable_shapes(params)
+        frozen = {}
+        for name, shape in shapes.items():
+            if name.startswith(FIRST + "/"):
+                a = weights.get(name)
+                if a is None:
+                    raise KeyError("weights has no variable %r" % name)
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if tuple(a.shape) != tuple(shape):
+                    raise ValueError("variable %r has shape %s, expected %s" % (name, a.shape, tuple(shape)))
+                frozen[name] = a.copy()
+        trained = {k: v for k, v in shapes.items() if not k.startswith(FIRST + "/")}
+        super().__init__(trained, weights, lambda name, shape, rng: None, device, seed)
+        self._frozen = frozen
+        self.params = dict(params)
+        self.keep_features = bool(keep_features)
+        self.features = {}
+        f = self._frozen
+        one = np.float32(1.0)
+        sf = f[FIRST + "/BatchNorm/gamma"] * (one / np.sqrt(f[FIRST + "/BatchNorm/moving_variance"] + np.float32(BATCH_NORM_EPSILON)))
+        self._first_bn = (f[FIRST + "/BatchNorm/moving_mean"], sf.astype(np.float32), f[FIRST + "/BatchNorm/beta"])
+
+    def frozen_variables(self):
+        """{reference name: float32 array} of Conv2d_0: its kernel, gamma, beta and moving statistics, untouched by training."""
+        return {k: v.copy() for k, v in self._frozen.items()}
+
+    def first_conv(self, images):
+        """Conv2d_0 in the engine's inference form: uint8 frames -> 2x/255 - 1 -> 3x3 stride 2 -> batch norm (moving) -> ReLU6."""
+        from . import ssd
+        if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4
+                and images.shape[3] == 3):
+            raise TypeError("images must be a uint8 [B,H,W,3] tensor on a GPU")
+        if (images.shape[1] | images.shape[2]) & 1:
+            raise ValueError("images: even height and width (the network's size)")
+        with torch.cuda.device(images.device):
+            return ssd.first_conv(images.contiguous(), self._frozen[FIRST + "/weights"], self._first_bn, "relu6")
+
+    def _bn(self, x, scope):
+        return self.batch_norm_relu([x], [scope + "/BatchNorm"], act="relu6")[0]
+
+    def body(self, x):
+        """Conv2d_1 .. Conv2d_13 on Conv2d_0's output [B,H,W,C0] -> [c3, c4, c5]."""
+        feats, outs = {}, []
+        for i, (stride, _f) in enumerate(MOBILENET_LAYERS, 1):
+            s = "MobilenetV1/Conv2d_%d_depthwise" % i
+            x = self._bn(depthwise_conv(x, self.variable(s + "/depthwise_weights"), stride), s)
+            feats["Conv2d_%d_depthwise" % i] = x
+            s = "MobilenetV1/Conv2d_%d_pointwise" % i
+            x = self._bn(pointwise_conv(x, self.variable(s + "/weights")), s)
+            feats["Conv2d_%d_pointwise" % i] = x
+            if i in OUTPUTS:
+                outs.append(x)
+        self.features = {k: v.detach() for k, v in feats.items()} if self.keep_features else {}
+        return outs
+
+    def forward(self, images):
+        return self.body(self.first_conv(images))

@@ -65,4 +65,5 @@ struct StatArgs {
     double *partial;       // [n_slabs][2][C]
     float eps, one_minus_momentum;
     int training;
+    int act;               // SSD_ACT_RELU | SSD_ACT_RELU6: the gate of the batch norm's activation
 };

@@ -19,7 +19,8 @@ static inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 // ----------------------------------------------------------------------------- kernel packing on the device
 // w HWIO [k,k,Cin,Cout] (device), taps = k * k = 1 or 9 -> wt [taps][rows][kp] in physical channel order, zero where a channel is padding.
 //   transpose == 0  the forward's kernel: row = output channel co, k = input channel ci, tap as stored
-//   transpose == 1  the data gradient's kernel w'[kh,kw,co,ci] = w[2-kh,2-kw,ci,co]: row = ci, k = co, tap 8 - tap (taps = 9 only)
+//   transpose == 1  the data gradient's kernel w'[kh,kw,co,ci] = w[2-kh,2-kw,ci,co]: row = ci, k = co, tap taps - 1 - tap (taps = 1, the
+//                   1x1 data gradient: w'[0,0,co,ci] = w[0,0,ci,co])
 __global__ __launch_bounds__(256) void pack_w_kernel(const float *w, int Cin, int Cout, int kp, int rows, int taps, int transpose, float *wt)
 {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -30,7 +31,7 @@ __global__ __launch_bounds__(256) void pack_w_kernel(const float *w, int Cin, in
     if (!transpose) {
         if (lk < Cin && ln < Cout) v = w[((long long)tap * Cin + lk) * Cout + ln];
     } else {
-        if (lk < Cout && ln < Cin) v = w[((long long)(8 - tap) * Cin + ln) * Cout + lk];
+        if (lk < Cout && ln < Cin) v = w[((long long)(taps - 1 - tap) * Cin + ln) * Cout + lk];
     }
     wt[idx] = v;
 }
@@ -46,6 +47,9 @@ static __device__ inline int th_level(const StatArgs &a, int slab)
     while (l + 1 < a.nlevels && slab >= a.lv[l + 1].slab_begin) ++l;
     return l;
 }
+
+// the activation's gate on the recomputed y: open where y > 0 (ReLU) and, for ReLU6, y < 6; a NaN closes it
+static __device__ inline bool th_gate(float y, int act) { return y > 0.0f && (act != SSD_ACT_RELU6 || y < 6.0f); }
 
 // MODE 0: sum x | 1: sum (x - mean)^2, the difference and the square in double | 2: sum g and sum g * xhat (batch-norm backward)
 template <int MODE>
@@ -78,7 +82,7 @@ __global__ __launch_bounds__(256) void stat_partial(const StatArgs a)
                 for (int e = 0; e < 4; ++e) {
                     const float t = x[e] - mean[e], xh = t * invstd[e], sf = gamma[e] * invstd[e];
                     const float y = t * sf + beta[e];
-                    const float gg = y > 0.0f ? dy[e] : 0.0f;
+                    const float gg = th_gate(y, a.act) ? dy[e] : 0.0f;
                     acc[0][e] += (double)gg;
                     acc[1][e] += (double)gg * (double)xh;
                 }
@@ -131,7 +135,7 @@ __global__ __launch_bounds__(256) void stat_final(const StatArgs a)
     if (MODE == 3) L.p.out[c] = (float)s;
 }
 
-// y = relu((x - mean) * sf + beta): training -- the batch's mean, sf = gamma * invstd; inference -- the moving mean,
+// y = act((x - mean) * sf + beta), act = ReLU or ReLU6 (elementwise.hip act_apply): training -- the batch's mean, sf = gamma * invstd; inference -- the moving mean,
 // sf = gamma * (1 / sqrt(moving_variance + eps)) as ssd_finalize forms it
 __global__ __launch_bounds__(256) void bn_apply_forward(const StatArgs a)
 {
@@ -162,13 +166,15 @@ __global__ __launch_bounds__(256) void bn_apply_forward(const StatArgs a)
         for (int e = 0; e < 4; ++e) {
             const float t = (x[e] - mean[e]) * sf[e];
             const float y = t + beta[e];
-            x[e] = y > 0.0f ? y : 0.0f;
+            float v = y > 0.0f ? y : 0.0f;
+            if (a.act == SSD_ACT_RELU6) v = v < 6.0f ? v : 6.0f;
+            x[e] = v;
         }
         th_store4(L.p.out + r * C, c, C, vec, x);
     }
 }
 
-// dx = (gamma * invstd) * ((g - dbeta / R) - xhat * (dgamma / R)), g = dy where the recomputed y > 0
+// dx = (gamma * invstd) * ((g - dbeta / R) - xhat * (dgamma / R)), g = dy where the gate of the recomputed y is open
 __global__ __launch_bounds__(256) void bn_apply_backward(const StatArgs a)
 {
     const int tid = threadIdx.x, slab = blockIdx.x;
@@ -192,7 +198,7 @@ __global__ __launch_bounds__(256) void bn_apply_backward(const StatArgs a)
         for (int e = 0; e < 4; ++e) {
             const float t = x[e] - mean[e], xh = t * invstd[e];
             const float y = t * sf[e] + beta[e];
-            const float gg = y > 0.0f ? dy[e] : 0.0f;
+            const float gg = th_gate(y, a.act) ? dy[e] : 0.0f;
             const float u = gg - c1[e], v = xh * c2[e];
             d[e] = sf[e] * (u - v);
         }
@@ -239,7 +245,7 @@ struct ConvTrainPlan {
     size_t off_a, off_b, off_w, off_bias, off_part, off_stat, off_up, bytes;
 };
 
-static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, int Cout, int k, int stride, int with_up, ConvTrainPlan &p)
+static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, int Cout, int k, int stride, int with_up, ConvTrainPlan &p, bool pw_dx = false)
 {
     if (!lv) return "null level list";
     if (n < 1 || n > TH_MAX_LEVELS) return "1 .. 8 levels";
@@ -254,7 +260,8 @@ static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, in
     const int taps = k * k;
     p.k = k; p.stride = stride; p.pad = k == 3 ? 1 : 0;
     conv_geometry(nullptr, taps, round_up(Cin, 32), round_up(Cout, 8), Cin, Cout, p.f);
-    conv_geometry(nullptr, 9, round_up(Cout, 32), round_up(Cin, 8), Cout, Cin, p.d);
+    const int taps_d = k == 3 ? 9 : 1;                                  // k = 1: only ssd_pointwise_train_backward (pw_dx) runs a data gradient
+    conv_geometry(nullptr, taps_d, round_up(Cout, 32), round_up(Cin, 8), Cout, Cin, p.d);
     const int widest = std::max(std::max(p.f.CinP, p.f.CoutP), std::max(p.d.CinP, p.d.CoutP));
     p.Rin_tot = p.Rout_tot = p.Rup_tot = 0;
     for (int l = 0; l < n; ++l) {
@@ -296,8 +303,8 @@ static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, in
     // workspace: [a | b | w | bias] of the forward or the data gradient (k = 3: its input is dy, or the zero-dilated dy of a
     // stride-2 layer, at the INPUT's size), then the weight gradient's partial tiles, dbias's sums and the permuted `up` tensors
     const size_t a_f = (size_t)p.Rin_tot * p.f.CinP, b_f = (size_t)p.Rout_tot * p.f.CoutP, w_f = (size_t)taps * p.f.CoutPad * p.f.CinP;
-    const size_t dg = k == 3 ? 1 : 0;
-    const size_t a_d = dg * p.Rin_tot * p.d.CinP, b_d = dg * p.Rin_tot * p.d.CoutP, w_d = dg * 9 * p.d.CoutPad * p.d.CinP;
+    const size_t dg = k == 3 || pw_dx ? 1 : 0;
+    const size_t a_d = dg * p.Rin_tot * p.d.CinP, b_d = dg * p.Rin_tot * p.d.CoutP, w_d = dg * taps_d * p.d.CoutPad * p.d.CinP;
     p.off_a = 0;
     p.off_b = al256(std::max(a_f, a_d) * 4 + 256);
     p.off_w = p.off_b + al256(std::max(b_f, b_d) * 4 + 256);
@@ -385,10 +392,11 @@ static int conv_train_forward(const std::string &fn, const ssd_conv_level *level
 }
 
 static int conv_train_backward(const std::string &fn, const ssd_conv_level *levels, int n_levels, int B, int Cin, int Cout, int k, int stride,
-                               const float *w_dev, float *dw_dev, float *dbias_dev, void *workspace_dev, size_t workspace_bytes, void *stream)
+                               const float *w_dev, float *dw_dev, float *dbias_dev, void *workspace_dev, size_t workspace_bytes, void *stream,
+                               bool pw_dx = false)
 {
     ConvTrainPlan p;
-    if (const char *why = conv_plan(levels, n_levels, B, Cin, Cout, k, stride, 0, p))
+    if (const char *why = conv_plan(levels, n_levels, B, Cin, Cout, k, stride, 0, p, pw_dx))
         return ssd_fail(SSD_ERR_INVALID, fn + ": " + why);
     if (!w_dev || !dw_dev || !workspace_dev) return ssd_fail(SSD_ERR_INVALID, fn + ": null pointer");
     if (mis16(w_dev) || mis16(dw_dev) || mis16(workspace_dev) || ((uintptr_t)dbias_dev & 3))
@@ -402,11 +410,11 @@ static int conv_train_backward(const std::string &fn, const ssd_conv_level *leve
     }
     if (with_dx != 0 && with_dx != n_levels)
         return ssd_fail(SSD_ERR_INVALID, fn + ": dx (out) must be given for every level or for none");
-    if (with_dx && k == 1) return ssd_fail(SSD_ERR_INVALID, fn + ": no data gradient of a 1x1 convolution (dx must be NULL)");
+    if (with_dx && k == 1 && !pw_dx) return ssd_fail(SSD_ERR_INVALID, fn + ": no data gradient of a 1x1 convolution (dx must be NULL)");
     if (workspace_bytes < p.bytes) return ssd_fail(SSD_ERR_INVALID, fn + ": workspace too small");
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace_dev;
-    if (with_dx) {          // dx = conv3x3_same(dy, w'), stride 2: of the zero-dilated dy: the forward's launch on the rotated, transposed kernel
+    if (with_dx) {          // dx = conv_same(dy, w'), stride 2: of the zero-dilated dy: the forward's launch on the rotated, transposed kernel
         float *dyp = (float *)(ws + p.off_a), *dxp = (float *)(ws + p.off_b), *wt = (float *)(ws + p.off_w);
         ConvW cw = p.d;
         for (int l = 0; l < n_levels; ++l) {
@@ -419,10 +427,10 @@ static int conv_train_backward(const std::string &fn, const ssd_conv_level *leve
                 LAUNCH(dilate_permute_kernel, dim3((unsigned)blocks), s, levels[l].dy, levels[l].H, levels[l].W, p.OH[l], p.OW[l], Cout, cw.CinP, total, dst);
             }
         }
-        const long long nw = 9LL * cw.CoutPad * cw.CinP;
-        LAUNCH(pack_w_kernel, dim3((unsigned)((nw + 255) / 256)), s, w_dev, Cin, Cout, cw.CinP, cw.CoutPad, 9, 1, wt);
+        const long long nw = (long long)cw.taps * cw.CoutPad * cw.CinP;
+        LAUNCH(pack_w_kernel, dim3((unsigned)((nw + 255) / 256)), s, w_dev, Cin, Cout, cw.CinP, cw.CoutPad, cw.taps, 1, wt);
         cw.wt = wt;
-        SSDCHK(run_igemm(cw, dyp, dxp, nullptr, levels, n_levels, B, 1, 1, nullptr, nullptr, p.rin_off, p.rin_off, nullptr, s));
+        SSDCHK(run_igemm(cw, dyp, dxp, nullptr, levels, n_levels, B, 1, p.pad, nullptr, nullptr, p.rin_off, p.rin_off, nullptr, s));
         for (int l = 0; l < n_levels; ++l)
             HIPCHK(launch_permute_channels(dxp + p.rin_off[l] * cw.CoutP, p.Rin[l], Cin, cw.CoutP, 0, levels[l].out, s));
     }
@@ -497,6 +505,20 @@ extern "C" int ssd_conv_train_backward(const ssd_conv_level *levels, int32_t n_l
 {
     return conv_train_backward("ssd_conv_train_backward", levels, n_levels, B, Cin, Cout, k, stride, w_dev, dw_dev, dbias_dev, workspace_dev,
                                workspace_bytes, stream);
+}
+
+// the TRAIN backbone's 1x1 backward: ssd_conv_train_backward with k = 1 and, where the levels carry `out`, the data gradient
+extern "C" size_t ssd_pointwise_train_workspace_bytes(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout)
+{
+    ConvTrainPlan p;
+    return conv_plan(levels, n_levels, B, Cin, Cout, 1, 1, 0, p, true) ? 0 : p.bytes;
+}
+
+extern "C" int ssd_pointwise_train_backward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
+                                            const float *w_dev, float *dw_dev, void *workspace_dev, size_t workspace_bytes, void *stream)
+{
+    return conv_train_backward("ssd_pointwise_train_backward", levels, n_levels, B, Cin, Cout, 1, 1, w_dev, dw_dev, nullptr, workspace_dev,
+                               workspace_bytes, stream, true);
 }
 
 // ----------------------------------------------------------------------------- the top-down merge's backward
@@ -583,29 +605,30 @@ static void bn_fill(StatArgs &a, const ssd_bn_level *lv)
     }
 }
 
-extern "C" int ssd_bn_relu_train_forward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, int32_t training, float epsilon,
-                                         float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream)
+static int bn_train_forward(const std::string &fn, const ssd_bn_level *levels, int n_levels, int C, int act, int training, float epsilon,
+                            float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream)
 {
     StatArgs a;
-    if (const char *why = bn_plan(levels, n_levels, C, a)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_bn_relu_train_forward: ") + why);
+    if (const char *why = bn_plan(levels, n_levels, C, a)) return ssd_fail(SSD_ERR_INVALID, fn + ": " + why);
+    if (act != SSD_ACT_RELU && act != SSD_ACT_RELU6) return ssd_fail(SSD_ERR_INVALID, fn + ": act must be SSD_ACT_RELU or SSD_ACT_RELU6");
     if (!(epsilon > 0.0f) || !(epsilon < 1e30f) || !(one_minus_momentum >= 0.0f) || !(one_minus_momentum <= 1.0f) || (training != 0 && training != 1))
-        return ssd_fail(SSD_ERR_INVALID, "ssd_bn_relu_train_forward: epsilon > 0, 0 <= one_minus_momentum <= 1, training 0 or 1");
+        return ssd_fail(SSD_ERR_INVALID, fn + ": epsilon > 0, 0 <= one_minus_momentum <= 1, training 0 or 1");
     for (int l = 0; l < n_levels; ++l) {
         const ssd_bn_level &L = levels[l];
-        if (!L.x || !L.out || !L.gamma || !L.beta) return ssd_fail(SSD_ERR_INVALID, "ssd_bn_relu_train_forward: a level's x, out, gamma or beta is null");
+        if (!L.x || !L.out || !L.gamma || !L.beta) return ssd_fail(SSD_ERR_INVALID, fn + ": a level's x, out, gamma or beta is null");
         if (training ? (!L.mean || !L.invstd) : (!L.moving_mean || !L.moving_variance))
-            return ssd_fail(SSD_ERR_INVALID, "ssd_bn_relu_train_forward: training needs mean and invstd, inference the moving statistics");
+            return ssd_fail(SSD_ERR_INVALID, fn + ": training needs mean and invstd, inference the moving statistics");
         if ((L.moving_mean == nullptr) != (L.moving_variance == nullptr))
-            return ssd_fail(SSD_ERR_INVALID, "ssd_bn_relu_train_forward: the moving statistics must be given together");
+            return ssd_fail(SSD_ERR_INVALID, fn + ": the moving statistics must be given together");
         if (mis16(L.x) || mis16(L.out) || mis16(L.gamma) || mis16(L.beta) || mis16(L.moving_mean) || mis16(L.moving_variance) || mis16(L.mean) ||
             mis16(L.var) || mis16(L.invstd))
-            return ssd_fail(SSD_ERR_INVALID, "ssd_bn_relu_train_forward: every pointer needs 16-byte alignment");
+            return ssd_fail(SSD_ERR_INVALID, fn + ": every pointer needs 16-byte alignment");
     }
-    if (training && (!workspace_dev || mis16(workspace_dev))) return ssd_fail(SSD_ERR_INVALID, "ssd_bn_relu_train_forward: workspace_dev null or misaligned");
-    if (training && workspace_bytes < al256((size_t)a.n_slabs * 2 * C * 8)) return ssd_fail(SSD_ERR_INVALID, "ssd_bn_relu_train_forward: workspace too small");
+    if (training && (!workspace_dev || mis16(workspace_dev))) return ssd_fail(SSD_ERR_INVALID, fn + ": workspace_dev null or misaligned");
+    if (training && workspace_bytes < al256((size_t)a.n_slabs * 2 * C * 8)) return ssd_fail(SSD_ERR_INVALID, fn + ": workspace too small");
     bn_fill(a, levels);
     a.partial = (double *)workspace_dev;
-    a.eps = epsilon; a.one_minus_momentum = one_minus_momentum; a.training = training;
+    a.eps = epsilon; a.one_minus_momentum = one_minus_momentum; a.training = training; a.act = act;
     hipStream_t s = (hipStream_t)stream;
     const dim3 gf((unsigned)((C + 255) / 256), (unsigned)n_levels);
     if (training) {
@@ -618,26 +641,55 @@ extern "C" int ssd_bn_relu_train_forward(const ssd_bn_level *levels, int32_t n_l
     return SSD_OK;
 }
 
-extern "C" int ssd_bn_relu_train_backward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, void *workspace_dev,
-                                          size_t workspace_bytes, void *stream)
+static int bn_train_backward(const std::string &fn, const ssd_bn_level *levels, int n_levels, int C, int act, void *workspace_dev,
+                             size_t workspace_bytes, void *stream)
 {
     StatArgs a;
-    if (const char *why = bn_plan(levels, n_levels, C, a)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_bn_relu_train_backward: ") + why);
+    if (const char *why = bn_plan(levels, n_levels, C, a)) return ssd_fail(SSD_ERR_INVALID, fn + ": " + why);
+    if (act != SSD_ACT_RELU && act != SSD_ACT_RELU6) return ssd_fail(SSD_ERR_INVALID, fn + ": act must be SSD_ACT_RELU or SSD_ACT_RELU6");
     for (int l = 0; l < n_levels; ++l) {
         const ssd_bn_level &L = levels[l];
         if (!L.x || !L.dy || !L.out || !L.gamma || !L.beta || !L.mean || !L.invstd || !L.dgamma || !L.dbeta)
-            return ssd_fail(SSD_ERR_INVALID, "ssd_bn_relu_train_backward: a level's x, dy, out, gamma, beta, mean, invstd, dgamma or dbeta is null");
+            return ssd_fail(SSD_ERR_INVALID, fn + ": a level's x, dy, out, gamma, beta, mean, invstd, dgamma or dbeta is null");
         if (mis16(L.x) || mis16(L.dy) || mis16(L.out) || mis16(L.gamma) || mis16(L.beta) || mis16(L.mean) || mis16(L.invstd) || mis16(L.dgamma) ||
             mis16(L.dbeta))
-            return ssd_fail(SSD_ERR_INVALID, "ssd_bn_relu_train_backward: every pointer needs 16-byte alignment");
+            return ssd_fail(SSD_ERR_INVALID, fn + ": every pointer needs 16-byte alignment");
     }
-    if (!workspace_dev || mis16(workspace_dev)) return ssd_fail(SSD_ERR_INVALID, "ssd_bn_relu_train_backward: workspace_dev null or misaligned");
-    if (workspace_bytes < al256((size_t)a.n_slabs * 2 * C * 8)) return ssd_fail(SSD_ERR_INVALID, "ssd_bn_relu_train_backward: workspace too small");
+    if (!workspace_dev || mis16(workspace_dev)) return ssd_fail(SSD_ERR_INVALID, fn + ": workspace_dev null or misaligned");
+    if (workspace_bytes < al256((size_t)a.n_slabs * 2 * C * 8)) return ssd_fail(SSD_ERR_INVALID, fn + ": workspace too small");
     bn_fill(a, levels);
     a.partial = (double *)workspace_dev;
+    a.act = act;
     hipStream_t s = (hipStream_t)stream;
     LAUNCH(stat_partial<2>, dim3((unsigned)a.n_slabs), s, a);
     LAUNCH(stat_final<2>, dim3((unsigned)((C + 255) / 256), (unsigned)n_levels), s, a);
     LAUNCH(bn_apply_backward, dim3((unsigned)a.n_slabs), s, a);
     return SSD_OK;
+}
+
+// the TRAIN head's pair is the ReLU case of the TRAIN backbone's
+extern "C" int ssd_bn_relu_train_forward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, int32_t training, float epsilon,
+                                         float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream)
+{
+    return bn_train_forward("ssd_bn_relu_train_forward", levels, n_levels, C, SSD_ACT_RELU, training, epsilon, one_minus_momentum, workspace_dev,
+                            workspace_bytes, stream);
+}
+
+extern "C" int ssd_bn_relu_train_backward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, void *workspace_dev,
+                                          size_t workspace_bytes, void *stream)
+{
+    return bn_train_backward("ssd_bn_relu_train_backward", levels, n_levels, C, SSD_ACT_RELU, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int ssd_bn_act_train_forward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, int32_t act, int32_t training, float epsilon,
+                                        float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream)
+{
+    return bn_train_forward("ssd_bn_act_train_forward", levels, n_levels, C, act, training, epsilon, one_minus_momentum, workspace_dev,
+                            workspace_bytes, stream);
+}
+
+extern "C" int ssd_bn_act_train_backward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, int32_t act, void *workspace_dev,
+                                         size_t workspace_bytes, void *stream)
+{
+    return bn_train_backward("ssd_bn_act_train_backward", levels, n_levels, C, act, workspace_dev, workspace_bytes, stream);
 }

@@ -1,12 +1,13 @@
-"""The trainable FPN on a frozen backbone: detector/feature_extractor.py's fpn() in TRAIN mode on this project's own kernels
-(include/ssd_hip.h, "the TRAIN FPN").
+"""The trainable FPN: detector/feature_extractor.py's fpn() in TRAIN mode on this project's own kernels (include/ssd_hip.h, "the
+TRAIN FPN").
 
     TrainPipeline -> Engine (frozen backbone, retained c3, c4, c5) -> TrainableFPN -> TrainableBoxPredictor -> differentiable_loss
                   -> backward (HIP) -> TrainStep over both modules' variables -> checkpoint -> Detector / evaluation
 
 This is the reference's own recipe (train.py:44-50 warm-starts only the backbone; fpn/*, box_net/* and class_net/* start from
-their initialisers and are trained), except that the backbone stays frozen: no gradient flows into c3, c4, c5.
-The FPN's graph is ONE torch.autograd.Function over train_ops.py's calls of ssd_conv_train_forward / _backward; its backward runs
+their initialisers and are trained).  On features that do not require a gradient (an Engine's: a frozen backbone) no gradient
+flows into c3, c4, c5; on features that do (TrainableMobileNet's, backbone_train.py) the backward also returns
+d c3, d c4, d c5.  The FPN's graph is ONE torch.autograd.Function over train_ops.py's calls of ssd_conv_train_forward / _backward; its backward runs
 the gradients in a fixed order with ssd_fpn_merge_backward doing every sum, so torch provides memory, streams and the autograd
 graph only.  The ops (conv_same, batch_norm_relu, fpn_merge_backward) and the variable loading (ReferenceVariables) are
 train_ops.py's; this file keeps the FPN's initialisers and its graph.
@@ -17,7 +18,7 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from .train_ops import ReferenceVariables, _conv_backward, _conv_forward, _need, fpn_merge_backward
+from .train_ops import ReferenceVariables, _conv_backward, _conv_forward, _need, _pointwise_backward, fpn_merge_backward
 
 FPN_DEPTH = 256                 # detector/feature_extractor.py:7
 LEVELS = (3, 4, 5, 6, 7)
@@ -25,7 +26,10 @@ LEVELS = (3, 4, 5, 6, 7)
 
 class _FpnGraph(torch.autograd.Function):
     """fpn() before its batch norms (feature_extractor.py:57-69) as one node: (c3, c4, c5, the ten kernels) -> raw p3 .. p7.  The
-    backward is the fixed sequence of DESIGN.md 4.12; c3, c4, c5 receive no gradient (the backbone is frozen)."""
+    backward is the fixed sequence of DESIGN.md 4.12.  When none of c3, c4, c5 requires a gradient that is all of it; when one
+    does, the three laterals' weight-gradient calls become ssd_pointwise_train_backward with the data gradient and p6's gives its
+    stride-2 data gradient too: d c3 = lateral3^T(d x3), d c4 = lateral4^T(d x4), d c5 = lateral5^T(d x5) +
+    dx_p6(d p6), the sum by ssd_fpn_merge_backward."""
 
     @staticmethod
     def forward(ctx, c3, c4, c5, l3, l4, l5, k3, k4, k5, k6, k7):
@@ -54,16 +58,26 @@ class _FpnGraph(torch.autograd.Function):
         d7 = torch.zeros(ctx.shape7, dtype=torch.float32, device=r6.device) if d7 is None else d7.contiguous()
         g7, _, (dr6,) = _conv_backward((r6,), k7, (d7,), 2, True)
         dp6 = fpn_merge_backward(dr6, base=d6, gate=p6, same_size=True)  # d p6 (raw) = d p6 from its batch norm + relu'(p6) * d relu(p6)
-        g6, _, _ = _conv_backward((c5,), k6, (dp6,), 2, False)
+        bridge = any(ctx.needs_input_grad[:3])                           # a trainable backbone: also d c3, d c4, d c5
+
+        def lateral(c, l, dx):
+            if not bridge:
+                return _conv_backward((c,), l, (dx,), 1, False)[0], None
+            gl, (dc,) = _pointwise_backward((c,), l, (dx,), True)
+            return gl, dc
+        g6, _, dc5_p6 = _conv_backward((c5,), k6, (dp6,), 2, bridge)
         g3, _, (dx3,) = _conv_backward((x3,), k3, (d3,), 1, True)
-        gl3, _, _ = _conv_backward((c3,), l3, (dx3,), 1, False)
+        gl3, dc3 = lateral(c3, l3, dx3)
         g4, _, (dx4,) = _conv_backward((x4,), k4, (d4,), 1, True)
         fpn_merge_backward(dx3, base=dx4, out=dx4)                      # d x4 = d x4 from p4 + the 2x2 sums of d x3
-        gl4, _, _ = _conv_backward((c4,), l4, (dx4,), 1, False)
+        gl4, dc4 = lateral(c4, l4, dx4)
         g5, _, (dx5,) = _conv_backward((x5,), k5, (d5,), 1, True)
         fpn_merge_backward(dx4, base=dx5, out=dx5)                      # d x5 = d x5 from p5 + the 2x2 sums of d x4
-        gl5, _, _ = _conv_backward((c5,), l5, (dx5,), 1, False)
-        return None, None, None, gl3, gl4, gl5, g3, g4, g5, g6, g7
+        gl5, dc5 = lateral(c5, l5, dx5)
+        if bridge:
+            fpn_merge_backward(dc5_p6[0], base=dc5, same_size=True, out=dc5)    # d c5 = lateral5^T(d x5) + dx_p6(d p6)
+            dc3, dc4, dc5 = [d if need else None for d, need in zip((dc3, dc4, dc5), ctx.needs_input_grad[:3])]
+        return dc3, dc4, dc5, gl3, gl4, gl5, g3, g4, g5, g6, g7
 
 
 def fpn_variable_shapes(params):
@@ -89,7 +103,7 @@ def variance_scaling_draw(rng, shape):
 
 
 class TrainableFPN(ReferenceVariables):
-    """fpn(features, is_training) (feature_extractor.py:40-76) as a torch.nn.Module on the HIP kernels, for a FROZEN backbone.
+    """fpn(features, is_training) (feature_extractor.py:40-76) as a torch.nn.Module on the HIP kernels.
 
     params   the model config (backbone, depth_multiplier: config.load_config)
     weights  {reference variable name: float32 array in TF layout}; only fpn/* is read.  A variable that is missing -- train.py's
@@ -97,7 +111,9 @@ class TrainableFPN(ReferenceVariables):
              variance_scaling_draw(numpy default_rng(seed), shape) in variables.variable_shapes order, gamma 1, beta 0,
              moving_mean 0, moving_variance 1.
     forward([c3, c4, c5], NHWC, e.g. from ssd.BackboneFeatures) -> [p3, p4, p5, p6, p7]; p7 = conv(relu(RAW p6)), the batch norms
-    come last (:71-74).  No gradient flows into c3, c4, c5.  .train(): batch statistics, the moving statistics move; .eval(): the
+    come last (:71-74).  A feature that requires a gradient (TrainableMobileNet's outputs) receives one; a feature that does not (an
+    Engine's: a frozen backbone) is detached, and with three such features the backward is the frozen-backbone sequence, launch for
+    launch.  .train(): batch statistics, the moving statistics move; .eval(): the
     engine's inference form, bit for bit.  named_variables() / statistics() are what TrainStep takes, e.g. together with the head's:
     TrainStep({**fpn.named_variables(), **head.named_variables()}, config, {**fpn.statistics(), **head.statistics()}, layout="tf",
     params=params)."""
@@ -119,5 +135,5 @@ class TrainableFPN(ReferenceVariables):
         for f in feats:
             _need(f, "features")
         kernels = [self.variable("fpn/lateral%d/kernel" % i) for i in (3, 4, 5)] + [self.variable("fpn/p%d/kernel" % i) for i in LEVELS]
-        raw = _FpnGraph.apply(*[f.detach() for f in feats], *kernels)
+        raw = _FpnGraph.apply(*[f if f.requires_grad else f.detach() for f in feats], *kernels)
         return self.batch_norm_relu(list(raw), ["fpn/p%d_batch_norm" % i for i in LEVELS])

@@ -1,8 +1,9 @@
-"""The differentiable ops under the trainable modules (include/ssd_hip.h, "the TRAIN head" and "the TRAIN FPN"), and nothing about
-any model: conv_same / conv3x3_same and batch_norm_relu are torch.autograd.Functions over the C entry points (once differentiable),
-fpn_merge_backward is ssd_fpn_merge_backward, and ReferenceVariables is the torch.nn.Module base that holds a block's variables
-under their reference names.  torch provides memory, streams and the autograd graph only.  head_train.py and fpn_train.py build
-RetinaNetBoxPredictor and fpn() from these.
+"""The differentiable ops under the trainable modules (include/ssd_hip.h, "the TRAIN head", "the TRAIN FPN" and "the TRAIN
+backbone"), and nothing about any model: conv_same / conv3x3_same, depthwise_conv, pointwise_conv and batch_norm_act (batch_norm_relu
+is its act="relu" case) are torch.autograd.Functions over the C entry points (once differentiable), fpn_merge_backward is
+ssd_fpn_merge_backward, and ReferenceVariables is the torch.nn.Module base that holds a block's variables under their reference
+names.  torch provides memory, streams and the autograd graph only.  head_train.py, fpn_train.py and backbone_train.py build
+RetinaNetBoxPredictor, fpn() and mobilenet_v1() from these.
 """
 import ctypes
 
@@ -81,6 +82,21 @@ def _conv_backward(xs, kernel, dys, stride, want_dx, want_dbias=False):
         check(L.ssd_conv_train_backward(lv, len(xs), B, Cin, Cout, k, stride, kernel.data_ptr(), dw.data_ptr(),
                                         dbias.data_ptr() if dbias is not None else None, ws.data_ptr(), ws.numel(), _stream(dev)))
     return dw, dbias, dxs
+
+
+def _pointwise_backward(xs, kernel, dys, want_dx):
+    """ssd_pointwise_train_backward -> (dw, dxs or None): _conv_backward's k = 1 call with the data gradient."""
+    Cin, Cout = kernel.shape[2], kernel.shape[3]
+    B, dev = xs[0].shape[0], kernel.device
+    dxs = tuple(torch.empty_like(x) for x in xs) if want_dx else None
+    dw = torch.empty_like(kernel)
+    lv = _conv_levels(xs, dys, dxs)
+    L = lib()
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, L.ssd_pointwise_train_workspace_bytes(lv, len(xs), B, Cin, Cout))
+        check(L.ssd_pointwise_train_backward(lv, len(xs), B, Cin, Cout, kernel.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             _stream(dev)))
+    return dw, dxs
 
 
 def fpn_merge_backward(g, base=None, gate=None, same_size=False, out=None):
@@ -184,7 +200,94 @@ def conv3x3_same(features, kernel, bias=None):
     return conv_same(features, kernel, bias=bias)
 
 
+# ----------------------------------------------------------------------------- the backbone's convolutions
+class _Pointwise(torch.autograd.Function):
+    """(kernel, the n levels) -> the n outputs of the 1x1 convolution; the backward is ssd_pointwise_train_backward."""
+
+    @staticmethod
+    def forward(ctx, kernel, *xs):
+        xs = tuple(x.contiguous() for x in xs)
+        kernel = kernel.contiguous()
+        outs = _conv_forward(xs, kernel, None, 1, None)
+        ctx.save_for_backward(kernel, *xs)
+        return outs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *dys):
+        kernel, xs = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        dys = tuple(torch.zeros(_out_shape(x, kernel.shape[3], 1), dtype=torch.float32, device=x.device) if d is None else d.contiguous()
+                    for x, d in zip(xs, dys))
+        want_dx = any(ctx.needs_input_grad[1:])
+        dw, dxs = _pointwise_backward(xs, kernel, dys, want_dx)
+        return (dw,) + (dxs if want_dx else (None,) * len(xs))
+
+
+def pointwise_conv(features, kernel):
+    """slim.conv2d 1x1, stride 1, raw (mobilenet_v1.py:66 before its batch norm): features a tensor [B,H,W,Cin] or a list of them that
+    share ONE kernel HWIO [1,1,Cin,Cout], Cin a multiple of 4.  The forward is conv_same's (bit-identical to ssd_amd.ssd.conv2d);
+    gradients flow to the kernel AND to the features (dx = conv1x1(dy, kernel transposed), one fmaf chain per element)."""
+    single = isinstance(features, torch.Tensor)
+    xs = [features] if single else list(features)
+    if not xs or len(xs) > 8:
+        raise ValueError("pointwise_conv takes 1 .. 8 levels")
+    _need(kernel, "kernel")
+    if kernel.dim() != 4 or tuple(kernel.shape[:2]) != (1, 1):
+        raise ValueError("kernel must be HWIO [1,1,Cin,Cout]")
+    for x in xs:
+        _need(x, "features")
+        if x.dim() != 4 or x.shape[3] != kernel.shape[2] or x.shape[0] != xs[0].shape[0]:
+            raise ValueError("every level must be [B,H,W,Cin] with the kernel's Cin and one batch size")
+    outs = _Pointwise.apply(kernel, *xs)
+    return outs[0] if single else list(outs)
+
+
+class _Depthwise(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kernel, stride):
+        x, kernel = x.contiguous(), kernel.contiguous()
+        B, H, W, C = x.shape
+        out = torch.empty((B, -(-H // stride), -(-W // stride), C), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            check(lib().ssd_depthwise_train_forward(x.data_ptr(), B, H, W, C, kernel.data_ptr(), stride, out.data_ptr(), _stream(x.device)))
+        ctx.save_for_backward(x, kernel)
+        ctx.stride = stride
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, kernel = ctx.saved_tensors
+        B, H, W, C = x.shape
+        dy = dy.contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(kernel)
+        L = lib()
+        with torch.cuda.device(x.device):
+            ws = _workspace(x.device, L.ssd_depthwise_train_workspace_bytes(B, H, W, C, ctx.stride))
+            check(L.ssd_depthwise_train_backward(x.data_ptr(), dy.data_ptr(), B, H, W, C, kernel.data_ptr(), ctx.stride,
+                                                 dx.data_ptr() if dx is not None else None, dw.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 _stream(x.device)))
+        return dx, dw, None
+
+
+def depthwise_conv(x, kernel, stride=1):
+    """tf.nn.depthwise_conv2d, 3x3, 'SAME', raw (depthwise_conv.py:5-26 before its batch norm): x [B,H,W,C], kernel [3,3,C,1], C a
+    multiple of 4 (at most 1024 for the backward), stride 1 or 2 (2: H and W of one parity).  The forward is bit-identical to
+    ssd_amd.ssd.depthwise3x3 without batch norm and activation; gradients flow to x and the kernel."""
+    _need(x, "x")
+    _need(kernel, "kernel")
+    if x.dim() != 4 or tuple(kernel.shape) != (3, 3, x.shape[3], 1):
+        raise ValueError("x must be [B,H,W,C] and kernel [3,3,C,1]")
+    if stride not in (1, 2):
+        raise ValueError("stride must be 1 or 2")
+    return _Depthwise.apply(x, kernel, stride)
+
+
 # ----------------------------------------------------------------------------- the batch norm
+_ACTS = {"relu": 1, "relu6": 2}                                                # SSD_ACT_RELU, SSD_ACT_RELU6
+
+
 def _bn_levels(xs, dys, outs, gammas, betas, mms, mvs, means, vars_, invstds, dgammas, dbetas):
     lv = (SsdBnLevel * len(xs))()
     cols = (("x", xs), ("dy", dys), ("out", outs), ("gamma", gammas), ("beta", betas), ("moving_mean", mms), ("moving_variance", mvs),
@@ -203,9 +306,9 @@ def _bn_call(fn, lv, n, C, device, *args):
         check(fn(lv, n, C, *args, ws.data_ptr(), ws.numel(), _stream(device)))
 
 
-class _BnRelu(torch.autograd.Function):
+class _BnAct(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, n, epsilon, one_minus_momentum, *t):
+    def forward(ctx, n, epsilon, one_minus_momentum, act, *t):
         xs = tuple(x.contiguous() for x in t[:n])
         gammas, betas, mms, mvs = t[n:2 * n], t[2 * n:3 * n], t[3 * n:4 * n], t[4 * n:5 * n]
         C, dev = xs[0].shape[-1], xs[0].device
@@ -214,9 +317,9 @@ class _BnRelu(torch.autograd.Function):
         stats = torch.empty((n, 3, Cp), dtype=torch.float32, device=dev)      # mean, var, invstd per level
         means, vars_, invstds = [stats[i, 0, :C] for i in range(n)], [stats[i, 1, :C] for i in range(n)], [stats[i, 2, :C] for i in range(n)]
         lv = _bn_levels(xs, None, outs, gammas, betas, mms, mvs, means, vars_, invstds, None, None)
-        _bn_call(lib().ssd_bn_relu_train_forward, lv, n, C, dev, 1, epsilon, one_minus_momentum)
+        _bn_call(lib().ssd_bn_act_train_forward, lv, n, C, dev, act, 1, epsilon, one_minus_momentum)
         ctx.save_for_backward(stats, *(xs + tuple(gammas) + tuple(betas)))
-        ctx.n = n
+        ctx.n, ctx.act = n, act
         return outs
 
     @staticmethod
@@ -232,12 +335,18 @@ class _BnRelu(torch.autograd.Function):
         dgammas, dbetas = [grads[i, 0, :C] for i in range(n)], [grads[i, 1, :C] for i in range(n)]
         means, invstds = [stats[i, 0, :C] for i in range(n)], [stats[i, 2, :C] for i in range(n)]
         lv = _bn_levels(xs, dys, dxs, gammas, betas, None, None, means, None, invstds, dgammas, dbetas)
-        _bn_call(lib().ssd_bn_relu_train_backward, lv, n, C, dev)
-        return (None, None, None) + dxs + tuple(dgammas) + tuple(dbetas) + (None,) * (2 * n)
+        _bn_call(lib().ssd_bn_act_train_backward, lv, n, C, dev, ctx.act)
+        return (None, None, None, None) + dxs + tuple(dgammas) + tuple(dbetas) + (None,) * (2 * n)
 
 
 def batch_norm_relu(x, gamma, beta, moving_mean, moving_variance, training, momentum=BATCH_NORM_MOMENTUM, epsilon=BATCH_NORM_EPSILON):
-    """layer_utils.py:5-12: batch norm + ReLU of x [..., C] with its own gamma, beta and moving statistics [C] -- or of a LIST of
+    """batch_norm_act with act="relu" (layer_utils.py:5-12)."""
+    return batch_norm_act(x, gamma, beta, moving_mean, moving_variance, training, momentum, epsilon, act="relu")
+
+
+def batch_norm_act(x, gamma, beta, moving_mean, moving_variance, training, momentum=BATCH_NORM_MOMENTUM, epsilon=BATCH_NORM_EPSILON,
+                   act="relu6"):
+    """Batch norm + ReLU (act="relu", layer_utils.py:5-12) or ReLU6 (act="relu6", mobilenet_v1.py:22-41) of x [..., C] with its own gamma, beta and moving statistics [C] -- or of a LIST of
     levels, each argument then a list (one launch sequence for all of them).  training=True: the batch's statistics (biased
     variance), the moving statistics are updated in place (moving -= (moving - batch) * (1 - momentum), unbiased variance);
     gradients flow to x, gamma and beta.  training=False: the inference form (x - moving_mean) * sf + beta that the engine
@@ -245,8 +354,10 @@ def batch_norm_relu(x, gamma, beta, moving_mean, moving_variance, training, mome
     single = isinstance(x, torch.Tensor)
     cols = [[v] if single else list(v) for v in (x, gamma, beta, moving_mean, moving_variance)]
     n = len(cols[0])
+    if act not in _ACTS:
+        raise ValueError("act must be 'relu' or 'relu6'")
     if n < 1 or n > 8 or any(len(c) != n for c in cols):
-        raise ValueError("batch_norm_relu takes 1 .. 8 levels, every argument one entry per level")
+        raise ValueError("batch_norm_act takes 1 .. 8 levels, every argument one entry per level")
     C = cols[0][0].shape[-1]
     for i in range(n):
         for c, name in zip(cols, ("x", "gamma", "beta", "moving_mean", "moving_variance")):
@@ -256,12 +367,12 @@ def batch_norm_relu(x, gamma, beta, moving_mean, moving_variance, training, mome
     eps = float(np.float32(epsilon))
     if training:
         omm = float(np.float32(1.0 - momentum))
-        outs = _BnRelu.apply(n, eps, omm, *(cols[0] + cols[1] + cols[2] + cols[3] + cols[4]))
+        outs = _BnAct.apply(n, eps, omm, _ACTS[act], *(cols[0] + cols[1] + cols[2] + cols[3] + cols[4]))
     else:
         xs = [v.detach().contiguous() for v in cols[0]]
         outs = [torch.empty_like(v) for v in xs]
         lv = _bn_levels(xs, None, outs, cols[1], cols[2], cols[3], cols[4], None, None, None, None, None)
-        _bn_call(lib().ssd_bn_relu_train_forward, lv, n, C, xs[0].device, 0, eps, 0.0)
+        _bn_call(lib().ssd_bn_act_train_forward, lv, n, C, xs[0].device, _ACTS[act], 0, eps, 0.0)
     return outs[0] if single else list(outs)
 
 
@@ -309,7 +420,7 @@ class ReferenceVariables(torch.nn.Module):
         """{reference name: moving_mean / moving_variance buffer}."""
         return {n: self.variable(n) for n in self._stat_names}
 
-    def batch_norm_relu(self, xs, scopes):
-        """batch_norm_relu of the levels xs, level i with the variables of the batch-norm scope scopes[i], in the module's mode."""
-        return batch_norm_relu(xs, *[[self.variable("%s/%s" % (s, leaf)) for s in scopes]
-                                     for leaf in ("gamma", "beta", "moving_mean", "moving_variance")], training=self.training)
+    def batch_norm_relu(self, xs, scopes, act="relu"):
+        """batch_norm_act of the levels xs, level i with the variables of the batch-norm scope scopes[i], in the module's mode."""
+        return batch_norm_act(xs, *[[self.variable("%s/%s" % (s, leaf)) for s in scopes]
+                                    for leaf in ("gamma", "beta", "moving_mean", "moving_variance")], training=self.training, act=act)
