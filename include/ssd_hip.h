@@ -702,11 +702,12 @@ int ssd_fpn_merge_backward(const float *base_dev, const float *g_dev, const floa
  * Each of the 13 blocks is a 3x3 depthwise convolution ('SAME', stride 1 or 2) and a 1x1 convolution, each followed by a
  * training-mode batch norm and ReLU6.  These calls are the operations the TRAIN head and the TRAIN FPN lack for it: the raw
  * depthwise convolution with its two gradients, the data gradient of a 1x1 convolution, and the batch norm with ReLU6.  Conv2d_0
- * (3 -> 32, stride 2) stays FROZEN: it runs through ssd_first_conv on its moving statistics and has no gradient here.
+ * (3 -> 32, stride 2) stays FROZEN BY DEFAULT: it then runs through ssd_first_conv on its moving statistics; its own forward and
+ * weight gradient are the block "the TRAIN first convolution" below.
  * Conventions as for the TRAIN head: the caller's device pointers, logical NHWC fp32, TF-layout kernels in DEVICE memory, the
  * caller's workspace, SSD_ERR_INVALID before any HIP call, enqueue only, no atomics: two calls give the same bits.  Every existing
  * entry point keeps its arguments, its refusals and its bits (ssd_conv_train_backward still refuses dx with k = 1).  Not here:
- * ShuffleNet's split and shuffle, Conv2d_0's weight gradient, F16X3, double backward.
+ * ShuffleNet's split and shuffle, F16X3, double backward.
  *
  * The depthwise calls: x [B,H,W,C], w_dev [3,3,C,1] (= [9][C]), out / dy [B,OH,OW,C] with OH = ceil(H / stride), OW likewise, and
  * pad_beg = p = max((OH - 1) * stride + 3 - H, 0) / 2 (TF 'SAME': 1 for stride 1; for stride 2, 0 on even and 1 on odd sizes).
@@ -759,6 +760,40 @@ int ssd_bn_act_train_forward(const ssd_bn_level *levels, int32_t n_levels, int32
                              float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream);
 int ssd_bn_act_train_backward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, int32_t act, void *workspace_dev,
                               size_t workspace_bytes, void *stream);
+
+/* ---- the TRAIN first convolution: forward and weight gradient of Conv2d_0 (3 -> Cout, 3x3, stride 2) from uint8 frames ----------
+ *
+ * The layer the TRAIN backbone leaves frozen BY DEFAULT (mobilenet_v1.py:34-50: slim.conv2d on the normalised frames, 'SAME', then
+ * batch norm and ReLU6; ShuffleNet's Conv1 is the same convolution with 24 channels).  These calls are its raw convolution and its
+ * weight gradient; its batch norm + ReLU6 are ssd_bn_act_train_forward / _backward above.  There is no data gradient: the input is
+ * the image.  Conventions are the TRAIN backbone's: the caller's device pointers, the TF-layout kernel [3,3,3,Cout] (= [27][Cout],
+ * row t = (ky * 3 + kx) * 3 + ci) in DEVICE memory, the caller's workspace, SSD_ERR_INVALID with the argument named in
+ * ssd_last_error() before any HIP call, enqueue only, no synchronisation, no atomics: two calls give the same bits.
+ *
+ * images_dev [B,H,W,3] uint8 at the network's own size (no resize), H and W even; out / dy [B,H/2,W/2,Cout]; Cout a multiple of 4,
+ * at most 64; B*H*W*3 < 2^31 (so R = B * (H/2) * (W/2) < 2^31); float pointers and the workspace 16-byte aligned, images_dev 4-byte
+ * aligned.  The pixel value is the inference path's: with inv255 = (float)(1.0 / 255.0), p(u) = fp32(2 * fp32(u * inv255) - 1), no
+ * contraction (the oracle's preprocess).  TF 'SAME' on even sizes has pad_beg = 0: output (oy,ox) reads rows 2oy .. 2oy+2 and
+ * columns 2ox .. 2ox+2; row H (ky = 2 on the last output row) and column W (kx = 2 on the last output column) are outside the input.
+ *
+ * ssd_first_conv_train_forward   raw, no batch norm, no activation: ssd_first_conv's kernels on the caller's device weights -- per
+ *   output ONE fmaf chain from +0 over the taps row-major, ci ascending within a tap, a tap outside the input contributing
+ *   fmaf(0, w, acc): bit-identical to ssd_first_conv without batch norm and activation and to the CPU oracle's
+ *   conv2d(preprocess(images), w, stride 2).
+ * ssd_first_conv_train_backward  from the images and dy:
+ *   dw_dev [3,3,3,Cout]   dw[ky,kx,ci,co] = sum over b, oy, ox of p(images[b,2oy+ky,2ox+kx,ci]) * dy[b,oy,ox,co] (positions outside the
+ *     input contribute nothing): 27 * Cout column sums over the OUTPUT rows r = (b * OH + oy) * OW + ox, OH = H/2, OW = W/2, products
+ *     and sums in double (the product of two floats is exact in double), rounded ONCE.  Fixed two-stage order, the batch norm's with
+ *     C = Cout: with G = Cout / 4, rpp = 256 / G and slab_rows = max(8 * rpp, ceil(R / 1024)) rounded up to a multiple of rpp, the
+ *     rows are cut into slabs of slab_rows; inside a slab row lane j = (r - slab start) mod rpp adds its rows in ascending order,
+ *     the lanes are added in ascending j, the slabs in ascending order.  The partial sums ([slabs][27][Cout] doubles) live in the
+ *     workspace, which ssd_first_conv_train_workspace_bytes sizes (0: the sizes would be refused).
+ * Not here: a resize in front of the convolution (TRAIN batches arrive at the network's size), ShuffleNet's max pool. */
+int ssd_first_conv_train_forward(const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, const float *w_dev /* [3,3,3,Cout] */,
+                                 int32_t Cout, float *out_dev, void *stream);
+size_t ssd_first_conv_train_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t Cout);
+int ssd_first_conv_train_backward(const uint8_t *images_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t Cout,
+                                  float *dw_dev /* [3,3,3,Cout] */, void *workspace_dev, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

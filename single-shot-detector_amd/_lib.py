@@ -229,6 +229,9 @@ SIGNATURES = {
     "ssd_bn_act_train_forward": (ctypes.c_int, [ctypes.POINTER(SsdBnLevel), _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _vp,
                                                 ctypes.c_size_t, _vp]),
     "ssd_bn_act_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdBnLevel), _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
+    "ssd_first_conv_train_forward": (ctypes.c_int, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "ssd_first_conv_train_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i]),
+    "ssd_first_conv_train_backward": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 

@@ -5,16 +5,17 @@
                   -> TrainStep over the three modules' variables (frozen = Conv2d_0) -> checkpoint -> Detector / evaluation
 
 train.py:44-50 warm-starts the backbone and then trains it with everything else; this module is that, with one difference that is
-a MODE of this project and not parity with the reference: Conv2d_0 stays FROZEN.  It runs in the engine's
-inference form (ssd.first_conv on its moving statistics); Conv2d_1 .. Conv2d_13 -- 13 depthwise and 13 pointwise layers, each
-followed by a batch norm and ReLU6 -- run on batch statistics and all their variables train.  The ops (depthwise_conv,
-pointwise_conv, batch_norm_act) and the variable loading (ReferenceVariables) are train_ops.py's; this file keeps the layer table
-and the graph.
+a MODE of this project and not parity with the reference: BY DEFAULT Conv2d_0 stays FROZEN.  It runs in the
+engine's inference form (ssd.first_conv on its moving statistics); Conv2d_1 .. Conv2d_13 -- 13 depthwise and 13 pointwise layers,
+each followed by a batch norm and ReLU6 -- run on batch statistics and all their variables train.  train_first=True (DESIGN.md
+4.14) trains Conv2d_0 as well, the reference's recipe: first_conv_train on the uint8 frames, then the batch norm on batch
+statistics.  The ops (first_conv_train, depthwise_conv, pointwise_conv, batch_norm_act) and the variable loading
+(ReferenceVariables) are train_ops.py's; this file keeps the layer table and the graph.
 """
 import numpy as np
 import torch
 
-from .train_ops import BATCH_NORM_EPSILON, ReferenceVariables, depthwise_conv, pointwise_conv
+from .train_ops import BATCH_NORM_EPSILON, ReferenceVariables, depthwise_conv, first_conv_train, pointwise_conv
 from .variables import MOBILENET_LAYERS
 
 FIRST = "MobilenetV1/Conv2d_0"
@@ -31,7 +32,7 @@ def mobilenet_variable_shapes(params):
 
 class TrainableMobileNet(ReferenceVariables):
     """mobilenet_v1(images, is_training, depth_multiplier) (mobilenet_v1.py:7-73) as a torch.nn.Module on the HIP kernels, with
-    Conv2d_0 frozen.
+    Conv2d_0 frozen by default.
 
     params   the model config (backbone "mobilenet", depth_multiplier <= 1.0: the batch norm takes at most 1024 channels)
     weights  {reference variable name: float32 array in TF layout}; every MobilenetV1/* variable must be there (the reference never
@@ -41,18 +42,23 @@ class TrainableMobileNet(ReferenceVariables):
     of Conv2d_1 .. 13 move; .eval(): the engine's c3, c4, c5 bit for bit (raw depthwise, the inference batch norm + ReLU6, the raw
     1x1, the inference batch norm + ReLU6).  named_variables() / statistics() hold Conv2d_1 .. 13 only; frozen_variables() returns
     the Conv2d_0 arrays for TrainStep(..., frozen=backbone.frozen_variables()).  keep_features=True keeps the 26 post-activation
-    tensors of the last forward in .features under the reference's features[layer_name] names (detached)."""
+    tensors of the last forward in .features under the reference's features[layer_name] names (detached).
+    train_first=True trains Conv2d_0 too: its kernel, gamma and beta join named_variables() (81 variables) and its moving statistics
+    statistics() (54), frozen_variables() returns {}; .train() runs first_conv_train and batch_norm_act on batch statistics (Conv2d_0's
+    moving statistics move), .eval() the same raw convolution and the inference batch norm + ReLU6 -- still the engine's c3, c4, c5
+    bit for bit; keep_features=True also keeps features["Conv2d_0"]."""
 
-    def __init__(self, params, weights, device=None, seed=0, keep_features=False):
+    def __init__(self, params, weights, device=None, seed=0, keep_features=False, train_first=False):
         if params.get("backbone") != "mobilenet":
             raise ValueError("TrainableMobileNet: the config's backbone is %r (ShuffleNet's split and shuffle have no backward here)"
                              % (params.get("backbone"),))
         if float(params["depth_multiplier"]) > 1.0:
             raise ValueError("TrainableMobileNet: depth_multiplier above 1.0 is not supported (the batch norm takes at most 1024 channels)")
         shapes = mobilenet_variable_shapes(params)
+        self.train_first = bool(train_first)
         frozen = {}
         for name, shape in shapes.items():
-            if name.startswith(FIRST + "/"):
+            if name.startswith(FIRST + "/") and not self.train_first:
                 a = weights.get(name)
                 if a is None:
                     raise KeyError("weights has no variable %r" % name)
@@ -60,29 +66,35 @@ class TrainableMobileNet(ReferenceVariables):
                 if tuple(a.shape) != tuple(shape):
                     raise ValueError("variable %r has shape %s, expected %s" % (name, a.shape, tuple(shape)))
                 frozen[name] = a.copy()
-        trained = {k: v for k, v in shapes.items() if not k.startswith(FIRST + "/")}
+        trained = {k: v for k, v in shapes.items() if self.train_first or not k.startswith(FIRST + "/")}
         super().__init__(trained, weights, lambda name, shape, rng: None, device, seed)
         self._frozen = frozen
         self.params = dict(params)
         self.keep_features = bool(keep_features)
         self.features = {}
+        if self.train_first:
+            return
         f = self._frozen
         one = np.float32(1.0)
         sf = f[FIRST + "/BatchNorm/gamma"] * (one / np.sqrt(f[FIRST + "/BatchNorm/moving_variance"] + np.float32(BATCH_NORM_EPSILON)))
         self._first_bn = (f[FIRST + "/BatchNorm/moving_mean"], sf.astype(np.float32), f[FIRST + "/BatchNorm/beta"])
 
     def frozen_variables(self):
-        """{reference name: float32 array} of Conv2d_0: its kernel, gamma, beta and moving statistics, untouched by training."""
+        """{reference name: float32 array} of Conv2d_0: its kernel, gamma, beta and moving statistics, untouched by training
+        ({} with train_first)."""
         return {k: v.copy() for k, v in self._frozen.items()}
 
     def first_conv(self, images):
-        """Conv2d_0 in the engine's inference form: uint8 frames -> 2x/255 - 1 -> 3x3 stride 2 -> batch norm (moving) -> ReLU6."""
+        """Conv2d_0: uint8 frames -> 2x/255 - 1 -> 3x3 stride 2 -> batch norm -> ReLU6.  Frozen: the engine's inference form on the
+        moving statistics.  train_first: the raw convolution with a weight gradient, then the batch norm in the module's mode."""
         from . import ssd
         if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4
                 and images.shape[3] == 3):
             raise TypeError("images must be a uint8 [B,H,W,3] tensor on a GPU")
         if (images.shape[1] | images.shape[2]) & 1:
             raise ValueError("images: even height and width (the network's size)")
+        if self.train_first:
+            return self._bn(first_conv_train(images, self.variable(FIRST + "/weights")), FIRST)
         with torch.cuda.device(images.device):
             return ssd.first_conv(images.contiguous(), self._frozen[FIRST + "/weights"], self._first_bn, "relu6")
 
@@ -105,4 +117,8 @@ class TrainableMobileNet(ReferenceVariables):
         return outs
 
     def forward(self, images):
-        return self.body(self.first_conv(images))
+        x = self.first_conv(images)
+        outs = self.body(x)
+        if self.keep_features and self.train_first:
+            self.features["Conv2d_0"] = x.detach()
+        return outs

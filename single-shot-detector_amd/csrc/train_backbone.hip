@@ -2,6 +2,8 @@
 // caller's device weights (the inference kernel, elementwise.hip), its data gradient (one streaming kernel) and its weight gradient
 // (9 * C column sums in double, the two-stage slab order of the batch norm's column statistics).  The 1x1 data gradient and the
 // batch norm + ReLU6 of the same header block live in train_head.hip beside the calls they extend.
+// The TRAIN first convolution (the header block of that name) follows: Conv2d_0's raw forward (the inference kernels on the caller's
+// device weights) and its weight gradient from the uint8 frames (27 * Cout column sums in double, the same slab order).
 // Every call checks its arguments before the first HIP call, then only enqueues on `stream`; scratch is the caller's workspace.
 #include "host.h"
 
@@ -22,6 +24,18 @@ struct DwPlan {
 // TF 'SAME' for a 3x3 window: out = ceil(n / stride), pad_beg = max((out - 1) * stride + 3 - n, 0) / 2
 static inline int same_pad(int n, int stride) { return std::max(((n + stride - 1) / stride - 1) * stride + 3 - n, 0) / 2; }
 
+// The batch norm's slab rule (train_head.hip make_slabs) for R rows of C channels: slab_rows = max(8 * rpp, ceil(R / 1024)) rounded
+// up to a multiple of rpp = 256 / (C / 4).
+static void slab_rule(long long R, int C, int &slab_rows, int &n_slabs)
+{
+    const int G = C / 4, rpp = 256 / (G < 1 ? 1 : (G > 256 ? 256 : G));
+    long long sr = (R + 1023) / 1024;
+    if (sr < 8LL * rpp) sr = 8LL * rpp;
+    sr = (sr + rpp - 1) / rpp * rpp;
+    slab_rows = (int)sr;
+    n_slabs = (int)((R + sr - 1) / sr);
+}
+
 static const char *dw_plan(int B, int H, int W, int C, int stride, bool backward, DwPlan &p)
 {
     if (B < 1 || H < 1 || W < 1 || C < 1) return "sizes must be positive";
@@ -35,13 +49,7 @@ static const char *dw_plan(int B, int H, int W, int C, int stride, bool backward
     p.OW = (W + stride - 1) / stride;
     p.pad = same_pad(H, stride);
     p.R = (long long)B * p.OH * p.OW;
-    // the batch norm's slab rule (train_head.hip make_slabs) over the OUTPUT rows
-    const int G = C / 4, rpp = 256 / (G < 1 ? 1 : (G > 256 ? 256 : G));
-    long long sr = (p.R + 1023) / 1024;
-    if (sr < 8LL * rpp) sr = 8LL * rpp;
-    sr = (sr + rpp - 1) / rpp * rpp;
-    p.slab_rows = (int)sr;
-    p.n_slabs = (int)((p.R + sr - 1) / sr);
+    slab_rule(p.R, C, p.slab_rows, p.n_slabs);                          // over the OUTPUT rows
     p.bytes = al256((size_t)p.n_slabs * 9 * C * 8);
     return nullptr;
 }
@@ -249,6 +257,175 @@ extern "C" int ssd_depthwise_train_backward(const float *x_dev, const float *dy_
     hipLaunchKernelGGL(dw_wgrad_partial, dim3((unsigned)p.n_slabs), dim3(256), 0, s, a);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(dw_wgrad_final, dim3((unsigned)((9 * C + 255) / 256)), dim3(256), 0, s, a, dw_dev);
+    HIPCHK(hipGetLastError());
+    return SSD_OK;
+}
+
+// ============================================================================= the TRAIN first convolution
+struct FcPlan {
+    int OH, OW;
+    long long R;                     // output rows B * OH * OW
+    int slab_rows, n_slabs;
+    size_t bytes;
+};
+
+static const char *fc_plan(int B, int H, int W, int Cout, FcPlan &p)
+{
+    if (B < 1 || H < 1 || W < 1) return "B, H and W must be positive";
+    if ((H & 1) || (W & 1)) return "H and W must be even (the network's own size)";
+    if (Cout < 4 || Cout > 64 || Cout % 4) return "Cout must be a multiple of 4 and at most 64";
+    if ((long long)B * H * W * 3 >= (1LL << 31)) return "B * H * W * 3 must stay below 2^31";
+    p.OH = H / 2;
+    p.OW = W / 2;
+    p.R = (long long)B * p.OH * p.OW;
+    slab_rule(p.R, Cout, p.slab_rows, p.n_slabs);                       // over the OUTPUT rows, C = Cout
+    p.bytes = al256((size_t)p.n_slabs * 27 * Cout * 8);
+    return nullptr;
+}
+
+struct FcGradArgs {
+    const uint8_t *img;
+    const float *dy;
+    int B, H, W, C, OH, OW;          // C = Cout
+    long long R;
+    int slab_rows, n_slabs;
+    double *partial;                 // [n_slabs][27][C]
+};
+
+// dw_wgrad_partial's sibling.  Block = slab of output rows x the three filter rows: thread (ky = threadIdx.y, rl = tid / G,
+// g = tid % G), G = C / 4, rpp = 256 / G, walks the rows r0 + rl, r0 + rl + rpp, ... of its slab for the channel quad g and keeps
+// the sums of p * dy of filter row ky -- 3 pixels x 3 channels x 4 output channels, 36 doubles -- so that the 27 x 4 accumulators
+// of a channel quad are spread over three threads of one block, which read the same dy rows at about the same time, instead of
+// filling one thread's register file.  The nine bytes under a filter row are contiguous, 0 or 2 bytes past a dword
+// boundary (W is even; which of the two depends on the row when W % 4 == 2): three aligned dword loads through a range-checked
+// buffer resource and a byte alignment, as in first_conv_px_kernel (elementwise.hip).  Only row 2oy+2 and column 2ox+2 can lie
+// outside the image: such taps are skipped.  The product of two floats is exact in double, so fma(p, dy, acc) has the bits of
+// acc + p * dy.  The block then adds its rpp row lanes in ascending order, one tap at a time
+// through LDS.
+__global__ __launch_bounds__(768) void fc_wgrad_partial(const FcGradArgs a)
+{
+    __shared__ double sm[3][1024];
+    const int tid = threadIdx.x, ky = threadIdx.y, slab = blockIdx.x;
+    const int C = a.C, G = C >> 2, rpp = 256 / G;
+    const int rl = tid / G, g = tid - rl * G, c = g << 2;
+    const long long r0 = (long long)slab * a.slab_rows;
+    const long long r1 = r0 + a.slab_rows < a.R ? r0 + a.slab_rows : a.R;
+    const float inv255 = (float)(1.0 / 255.0);
+    const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.img, 0, (int)((long long)a.B * a.H * a.W * 3), 0x00020000);
+    double acc[9][4];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[t][e] = 0.0;
+    if (rl < rpp) {
+        // r -> (row = b * OH + oy, ox) once; a step of rpp rows then moves ox by rpp % OW and row by rpp / OW (+ 1 on a carry), and
+        // oy = row % OH follows with one conditional subtraction: no division inside the loop.  H = 2 * OH, so the image row of
+        // tap ky is b * H + 2 * oy + ky = 2 * row + ky.
+        const int OW = a.OW, OH = a.OH;
+        const int step_x = rpp % OW, step_row = rpp / OW, step_y = step_row % OH;
+        const unsigned first = (unsigned)(r0 + rl);
+        int ox = (int)(first % (unsigned)OW), row = (int)(first / (unsigned)OW), oy = row % OH;
+        for (long long r = r0 + rl; r < r1; r += rpp) {
+            const int cx = ox, crow = row, cy = oy;
+            ox += step_x; row += step_row; oy += step_y;
+            if (ox >= OW) { ox -= OW; ++row; ++oy; }
+            if (oy >= OH) oy -= OH;
+            if (ky == 2 && cy == OH - 1) continue;           // row H: outside
+            const v4f d = *(const v4f *)(a.dy + r * C + c);
+            const double dd[4] = {(double)d[0], (double)d[1], (double)d[2], (double)d[3]};
+            const int ad = ((2 * crow + ky) * a.W + 2 * cx) * 3;
+            const int a0 = ad & ~3, sh = ad & 3;         // sh: byte offset of the row's first pixel inside its dword (0 or 2)
+            const unsigned w0 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 0, 0);
+            const unsigned w1 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0 + 4, 0, 0);
+            const unsigned w2 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0 + 8, 0, 0);
+            const unsigned d0 = __builtin_amdgcn_alignbyte(w1, w0, sh);
+            const unsigned d1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
+            const unsigned d2 = w2 >> (8 * sh);
+            const unsigned char px[9] = {(unsigned char)d0, (unsigned char)(d0 >> 8), (unsigned char)(d0 >> 16), (unsigned char)(d0 >> 24),
+                                         (unsigned char)d1, (unsigned char)(d1 >> 8), (unsigned char)(d1 >> 16), (unsigned char)(d1 >> 24),
+                                         (unsigned char)d2};
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                float v = (float)px[k] * inv255;
+                v = 2.0f * v - 1.0f;
+                const double pv = (double)v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[k][e] = fma(pv, dd[e], acc[k][e]);
+            }
+            if (cx < OW - 1) {                               // else column W: outside
+#pragma unroll
+                for (int k = 6; k < 9; ++k) {
+                    float v = (float)px[k] * inv255;
+                    v = 2.0f * v - 1.0f;
+                    const double pv = (double)v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[k][e] = fma(pv, dd[e], acc[k][e]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sm[ky][tid * 4 + e] = acc[t][e];
+        __syncthreads();
+        if (rl < 4) {                                        // rpp >= 16: row lanes 0 .. 3 exist; lane rl adds element e = rl of the quad
+            double s = 0.0;
+            for (int j = 0; j < rpp; ++j) s += sm[ky][(j * G + g) * 4 + rl];
+            a.partial[((long long)slab * 27 + ky * 9 + t) * C + c + rl] = s;
+        }
+        __syncthreads();
+    }
+}
+
+// dw[t][c] = fp32(the slabs' sums added in ascending order)
+__global__ __launch_bounds__(256) void fc_wgrad_final(const FcGradArgs a, float *dw)
+{
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= 27 * a.C) return;
+    double s = 0.0;
+    for (int k = 0; k < a.n_slabs; ++k) s += a.partial[(long long)k * 27 * a.C + idx];
+    dw[idx] = (float)s;
+}
+
+extern "C" int ssd_first_conv_train_forward(const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, const float *w_dev, int32_t Cout,
+                                            float *out_dev, void *stream)
+{
+    FcPlan p;
+    if (const char *why = fc_plan(B, H, W, Cout, p)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_first_conv_train_forward: ") + why);
+    if (!images_dev || !w_dev || !out_dev) return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_forward: null pointer (images_dev, w_dev, out_dev)");
+    if (mis16(w_dev) || mis16(out_dev)) return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_forward: w_dev and out_dev need 16-byte alignment");
+    if ((uintptr_t)images_dev & 3) return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_forward: images_dev needs 4-byte alignment");
+    HIPCHK(launch_first_conv(images_dev, B, H, W, H, W, H, W, w_dev, Cout, nullptr, nullptr, nullptr, SSD_ACT_NONE, out_dev, (hipStream_t)stream));
+    return SSD_OK;
+}
+
+extern "C" size_t ssd_first_conv_train_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t Cout)
+{
+    FcPlan p;
+    return fc_plan(B, H, W, Cout, p) ? 0 : p.bytes;
+}
+
+extern "C" int ssd_first_conv_train_backward(const uint8_t *images_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t Cout,
+                                             float *dw_dev, void *workspace_dev, size_t workspace_bytes, void *stream)
+{
+    FcPlan p;
+    if (const char *why = fc_plan(B, H, W, Cout, p)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_first_conv_train_backward: ") + why);
+    if (!images_dev || !dy_dev || !dw_dev || !workspace_dev)
+        return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_backward: null pointer (images_dev, dy_dev, dw_dev, workspace_dev)");
+    if (mis16(dy_dev) || mis16(dw_dev) || mis16(workspace_dev))
+        return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_backward: dy_dev, dw_dev and workspace_dev need 16-byte alignment");
+    if ((uintptr_t)images_dev & 3) return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_backward: images_dev needs 4-byte alignment");
+    if (workspace_bytes < p.bytes) return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_backward: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    FcGradArgs a;
+    a.img = images_dev; a.dy = dy_dev;
+    a.B = B; a.H = H; a.W = W; a.C = Cout; a.OH = p.OH; a.OW = p.OW;
+    a.R = p.R; a.slab_rows = p.slab_rows; a.n_slabs = p.n_slabs;
+    a.partial = (double *)workspace_dev;
+    hipLaunchKernelGGL(fc_wgrad_partial, dim3((unsigned)p.n_slabs), dim3(256, 3), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(fc_wgrad_final, dim3((unsigned)((27 * Cout + 255) / 256)), dim3(256), 0, s, a, dw_dev);
     HIPCHK(hipGetLastError());
     return SSD_OK;
 }

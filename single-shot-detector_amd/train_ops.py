@@ -1,6 +1,6 @@
 """The differentiable ops under the trainable modules (include/ssd_hip.h, "the TRAIN head", "the TRAIN FPN" and "the TRAIN
-backbone"), and nothing about any model: conv_same / conv3x3_same, depthwise_conv, pointwise_conv and batch_norm_act (batch_norm_relu
-is its act="relu" case) are torch.autograd.Functions over the C entry points (once differentiable), fpn_merge_backward is
+backbone" and "the TRAIN first convolution"), and nothing about any model: conv_same / conv3x3_same, depthwise_conv, pointwise_conv,
+first_conv_train and batch_norm_act (batch_norm_relu is its act="relu" case) are torch.autograd.Functions over the C entry points (once differentiable), fpn_merge_backward is
 ssd_fpn_merge_backward, and ReferenceVariables is the torch.nn.Module base that holds a block's variables under their reference
 names.  torch provides memory, streams and the autograd graph only.  head_train.py, fpn_train.py and backbone_train.py build
 RetinaNetBoxPredictor, fpn() and mobilenet_v1() from these.
@@ -282,6 +282,54 @@ def depthwise_conv(x, kernel, stride=1):
     if stride not in (1, 2):
         raise ValueError("stride must be 1 or 2")
     return _Depthwise.apply(x, kernel, stride)
+
+
+class _FirstConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, images, kernel):
+        images, kernel = images.contiguous(), kernel.contiguous()
+        B, H, W, _ = images.shape
+        Cout = kernel.shape[3]
+        out = torch.empty((B, H // 2, W // 2, Cout), dtype=torch.float32, device=images.device)
+        with torch.cuda.device(images.device):
+            check(lib().ssd_first_conv_train_forward(images.data_ptr(), B, H, W, kernel.data_ptr(), Cout, out.data_ptr(), _stream(images.device)))
+        ctx.save_for_backward(images)
+        ctx.Cout = Cout
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        images, = ctx.saved_tensors
+        B, H, W, _ = images.shape
+        dy = dy.contiguous()
+        dw = torch.empty((3, 3, 3, ctx.Cout), dtype=torch.float32, device=images.device)
+        L = lib()
+        with torch.cuda.device(images.device):
+            ws = _workspace(images.device, L.ssd_first_conv_train_workspace_bytes(B, H, W, ctx.Cout))
+            check(L.ssd_first_conv_train_backward(images.data_ptr(), dy.data_ptr(), B, H, W, ctx.Cout, dw.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                  _stream(images.device)))
+        return None, dw
+
+
+def first_conv_train(images, kernel):
+    """slim.conv2d 3x3, stride 2, 'SAME', raw, on the normalised frames (mobilenet_v1.py:34-50 before its batch norm): images uint8
+    [B,H,W,3] on the GPU at the network's own size (H and W even), kernel [3,3,3,Cout], Cout a multiple of 4 and at most 64.  The
+    pixel value is the inference path's 2 * (u / 255) - 1.  The forward is bit-identical to ssd_amd.ssd.first_conv without batch norm
+    and activation; the gradient flows to the kernel only (the input is the image)."""
+    if not (isinstance(images, torch.Tensor) and images.dtype == torch.uint8):
+        raise TypeError("images must be a uint8 tensor on a GPU (there is no CPU path)")
+    if not (isinstance(kernel, torch.Tensor) and kernel.dtype == torch.float32):
+        raise TypeError("kernel must be a float32 tensor on a GPU (there is no CPU path)")
+    if images.dim() != 4 or images.shape[3] != 3 or kernel.dim() != 4 or tuple(kernel.shape[:3]) != (3, 3, 3):
+        raise ValueError("images must be [B,H,W,3] and kernel [3,3,3,Cout]")
+    if (images.shape[1] | images.shape[2]) & 1:
+        raise ValueError("images: even height and width (the network's size)")
+    if kernel.shape[3] % 4 or not 4 <= kernel.shape[3] <= 64:
+        raise ValueError("kernel: Cout must be a multiple of 4 and at most 64")
+    if not (images.is_cuda and kernel.is_cuda):
+        raise TypeError("images and kernel must be on a GPU (there is no CPU path)")
+    return _FirstConv.apply(images, kernel)
 
 
 # ----------------------------------------------------------------------------- the batch norm
