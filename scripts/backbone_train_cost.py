@@ -73,7 +73,8 @@ def pointwise_lines(B, H, W, Cin, Cout, reps):
     print("    data gradient (permutes + pack + igemm) %6.3f ms  %6.1f TFLOP/s  %4.1f %% of peak" % (t_x, tf(t_x), 100 * tf(t_x) / PEAK))
 
 
-def bn_lines(B, H, W, C, reps):
+def bn_lines(B, H, W, C, reps, inline=False):
+    """inline: two lines under another layer's heading, each naming the batch norm, instead of a heading of its own"""
     L, s = lib(), stream()
     g = torch.Generator(device="cuda").manual_seed(3)
     x = torch.randn((B * H * W, C), device="cuda", generator=g) * 2
@@ -86,15 +87,20 @@ def bn_lines(B, H, W, C, reps):
     lv[0].out = dx.data_ptr()
     t_b = timed(lambda: check(L.ssd_bn_act_train_backward(lv, 1, C, 2, ws.data_ptr(), ws.numel(), s)), reps)
     nb = x.numel() * 4.0
-    print("  batch norm + ReLU6, %d channels at %dx%d (%.1f MB)" % (C, H, W, nb / 1e6))
-    print("    forward  (3 reads + 1 write)          %8.3f ms  %7.1f GB/s" % (t_f, 4 * nb / t_f / 1e6))
-    print("    backward (4 reads + 1 write)          %8.3f ms  %7.1f GB/s" % (t_b, 5 * nb / t_b / 1e6))
+    if inline:
+        fmt = "    batch norm + ReLU6 %s %6.3f ms  %7.1f GB/s"
+    else:
+        print("  batch norm + ReLU6, %d channels at %dx%d (%.1f MB)" % (C, H, W, nb / 1e6))
+        fmt = "    %s          %8.3f ms  %7.1f GB/s"
+    print(fmt % ("forward  (3 reads + 1 write)", t_f, 4 * nb / t_f / 1e6))
+    print(fmt % ("backward (4 reads + 1 write)", t_b, 5 * nb / t_b / 1e6))
 
 
-def step_lines(B, reps):
+def step_lines(B, reps, train_first=None):
+    """The backbone alone and one whole step.  train_first None: the default backbone (Conv2d_0 frozen), after the FPN alone with and
+    without the bridge; a tuple of train_first values: those backbones IN THE SAME RUN under one FPN and head, then on minus off."""
     params = {"backbone": "mobilenet", "depth_multiplier": 1.0, "num_classes": 80}
     W = ssd_amd.synthetic_weights(params, seed=1)
-    backbone = ssd_amd.TrainableMobileNet(params, W, device="cuda").train()
     fpn = ssd_amd.TrainableFPN(params, W, device="cuda").train()
     head = ssd_amd.TrainableBoxPredictor(params, W, device="cuda").train()
     g = torch.Generator(device="cuda").manual_seed(4)
@@ -102,12 +108,21 @@ def step_lines(B, reps):
     anchors = torch.from_numpy(ssd_amd.AnchorGenerator()(640, 896)).cuda()
     boxes = np.tile(np.array([[[0.2, 0.2, 0.6, 0.7], [0.5, 0.1, 0.9, 0.4]]], np.float32), (B, 1, 1))
     gt = {"boxes": boxes, "labels": np.ones((B, 2), np.int32), "num_boxes": np.full(B, 2, np.int32)}
-    modules = (backbone, fpn, head)
+    BACKBONE, STEP = "the backbone alone, forward + backward", "one backbone + FPN + head step (forward + loss + backward)"
 
-    def clear():
-        for m in modules:
+    def clear(*more):
+        for m in (fpn, head) + more:
             for p in m.parameters():
                 p.grad = None
+
+    def timed_line(label, fn):
+        """One line: label, time, peak memory.  -> ms"""
+        clear()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        t = timed(fn, reps)
+        print("%s %8.2f ms  peak memory %.2f GB" % (label, t, torch.cuda.max_memory_allocated() / 1e9))
+        return t
 
     def fpn_only(grad):
         clear()
@@ -115,27 +130,31 @@ def step_lines(B, reps):
         ps = fpn(cs)
         torch.autograd.backward(ps, [torch.ones_like(p) for p in ps])
 
-    def backbone_only():
-        clear()
+    def backbone_only(backbone):
+        clear(backbone)
         cs = backbone(images)
         torch.autograd.backward(cs, [torch.ones_like(c) for c in cs])
 
-    def step():
-        clear()
+    def step(backbone):
+        clear(backbone)
         eb, cp = head(fpn(backbone(images)))
         out = ssd_amd.differentiable_loss(cp, eb, anchors, gt, {"gamma": 2.0, "alpha": 0.25})
         (out["localization_loss"] + out["classification_loss"]).backward()
-    t0, t1 = timed(lambda: fpn_only(False), reps), timed(lambda: fpn_only(True), reps)
-    print("  the FPN alone, forward + backward: frozen features %8.2f ms, with the bridge to c3, c4, c5 %8.2f ms (+ %.2f ms)" % (t0, t1, t1 - t0))
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    tb = timed(backbone_only, reps)
-    print("  the backbone alone (Conv2d_0 frozen; forward + backward of 26 convolutions and 26 batch norms)  %8.2f ms  peak memory %.2f GB"
-          % (tb, torch.cuda.max_memory_allocated() / 1e9))
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    t = timed(step, reps)
-    print("  one backbone + FPN + head step (forward + loss + backward)  %8.2f ms  peak memory %.2f GB" % (t, torch.cuda.max_memory_allocated() / 1e9))
+    if train_first is None:
+        t0, t1 = timed(lambda: fpn_only(False), reps), timed(lambda: fpn_only(True), reps)
+        print("  the FPN alone, forward + backward: frozen features %8.2f ms, with the bridge to c3, c4, c5 %8.2f ms (+ %.2f ms)" % (t0, t1, t1 - t0))
+        backbone = ssd_amd.TrainableMobileNet(params, W, device="cuda").train()
+        timed_line("  the backbone alone (Conv2d_0 frozen; forward + backward of 26 convolutions and 26 batch norms) ", lambda: backbone_only(backbone))
+        timed_line("  %s " % STEP, lambda: step(backbone))
+        return
+    res = {}
+    for first in train_first:
+        backbone = ssd_amd.TrainableMobileNet(params, W, device="cuda", train_first=first).train()
+        for what, fn in ((BACKBONE, backbone_only), (STEP, step)):
+            res[(what, first)] = timed_line("  train_first=%-5s  %-58s" % (first, what), lambda: fn(backbone))
+        del backbone
+    for what in sorted((STEP, BACKBONE)):
+        print("  train_first on - off: %-58s %+8.2f ms" % (what, res[(what, True)] - res[(what, False)]))
 
 
 def main():

@@ -1,42 +1,27 @@
 // The TRAIN backbone's depthwise convolution (include/ssd_hip.h, "the TRAIN backbone"): the raw 3x3 depthwise forward on the
 // caller's device weights (the inference kernel, elementwise.hip), its data gradient (one streaming kernel) and its weight gradient
-// (9 * C column sums in double, the two-stage slab order of the batch norm's column statistics).  The 1x1 data gradient and the
+// (9 * C column sums in double on the column-sum core of train_head.h, the batch norm's slab order).  The 1x1 data gradient and the
 // batch norm + ReLU6 of the same header block live in train_head.hip beside the calls they extend.
 // The TRAIN first convolution (the header block of that name) follows: Conv2d_0's raw forward (the inference kernels on the caller's
 // device weights) and its weight gradient from the uint8 frames (27 * Cout column sums in double, the same slab order).
 // Every call checks its arguments before the first HIP call, then only enqueues on `stream`; scratch is the caller's workspace.
 #include "host.h"
+#include "train_head.h"
 
 #include <algorithm>
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-static inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-static inline bool mis16(const void *p) { return ((uintptr_t)p & 15) != 0; }
-
-struct DwPlan {
-    int OH, OW, pad;
-    long long R;                     // output rows B * OH * OW
-    int slab_rows, n_slabs;
-    size_t bytes;
+// the plan of a depthwise call (dw_plan) and, with the pointers, the weight gradient's launch arguments
+struct DwArgs {
+    const float *x, *dy;
+    int H, W, C, OH, OW, stride, pad;
+    Slabs sl;                        // of the OUTPUT rows B * OH * OW
+    double *partial;                 // [n_slabs][9][C]
 };
 
 // TF 'SAME' for a 3x3 window: out = ceil(n / stride), pad_beg = max((out - 1) * stride + 3 - n, 0) / 2
 static inline int same_pad(int n, int stride) { return std::max(((n + stride - 1) / stride - 1) * stride + 3 - n, 0) / 2; }
 
-// The batch norm's slab rule (train_head.hip make_slabs) for R rows of C channels: slab_rows = max(8 * rpp, ceil(R / 1024)) rounded
-// up to a multiple of rpp = 256 / (C / 4).
-static void slab_rule(long long R, int C, int &slab_rows, int &n_slabs)
-{
-    const int G = C / 4, rpp = 256 / (G < 1 ? 1 : (G > 256 ? 256 : G));
-    long long sr = (R + 1023) / 1024;
-    if (sr < 8LL * rpp) sr = 8LL * rpp;
-    sr = (sr + rpp - 1) / rpp * rpp;
-    slab_rows = (int)sr;
-    n_slabs = (int)((R + sr - 1) / sr);
-}
-
-static const char *dw_plan(int B, int H, int W, int C, int stride, bool backward, DwPlan &p)
+static const char *dw_plan(int B, int H, int W, int C, int stride, bool backward, DwArgs &p)
 {
     if (B < 1 || H < 1 || W < 1 || C < 1) return "sizes must be positive";
     if (C % 4) return "C must be a multiple of 4";
@@ -45,14 +30,15 @@ static const char *dw_plan(int B, int H, int W, int C, int stride, bool backward
     if (B > 65536 || H > 32768 || W > 32768 || (long long)B * H * W >= (1LL << 31) || (long long)B * H * W * C >= (1LL << 40))
         return "B <= 65536, H and W <= 32768, fewer than 2^31 positions and 2^40 elements";
     if (backward && C > 1024) return "the backward takes at most 1024 channels";
+    p.H = H; p.W = W; p.C = C; p.stride = stride;
     p.OH = (H + stride - 1) / stride;
     p.OW = (W + stride - 1) / stride;
     p.pad = same_pad(H, stride);
-    p.R = (long long)B * p.OH * p.OW;
-    slab_rule(p.R, C, p.slab_rows, p.n_slabs);                          // over the OUTPUT rows
-    p.bytes = al256((size_t)p.n_slabs * 9 * C * 8);
+    p.sl = slab_rule((long long)B * p.OH * p.OW, std::min(C, TH_STAT_COLS) / 4);   // (the forward takes wider tensors; it has no slabs)
     return nullptr;
 }
+
+static size_t dw_bytes(const DwArgs &p) { return al256((size_t)p.sl.n_slabs * 9 * p.C * 8); }
 
 // ----------------------------------------------------------------------------- the data gradient
 // dx[b,iy,ix,c] = sum over the taps (ky,kx) of dy[b,(iy+P-ky)/S,(ix+P-kx)/S,c] * w[ky,kx,c] whose source index is an integer inside
@@ -134,32 +120,22 @@ __global__ __launch_bounds__(256) void dw_dx_kernel(const float *__restrict__ dy
 }
 
 // ----------------------------------------------------------------------------- the weight gradient
-struct DwGradArgs {
-    const float *x, *dy;
-    int H, W, C, OH, OW, stride, pad;
-    long long R;
-    int slab_rows, n_slabs;
-    double *partial;                 // [n_slabs][9][C]
-};
-
-// Block = slab of output rows; thread (rl = tid / G, g = tid % G), G = C / 4, rpp = 256 / G, walks the rows r0 + rl, r0 + rl + rpp, ...
-// of its slab for the channel quad g and keeps the nine taps' sums of x * dy in double (the product of two floats is exact in
-// double); the block then adds its rpp row lanes in ascending order, one tap at a time through LDS.
-__global__ __launch_bounds__(256) void dw_wgrad_partial(const DwGradArgs a)
+// The column-sum core of train_head.h over the output rows, G = C / 4: a thread keeps the nine taps' sums of x * dy of its channel
+// quad in double (the product of two floats is exact in double); the block then adds its row lanes one tap at a time.
+__global__ __launch_bounds__(256) void dw_wgrad_partial(const DwArgs a)
 {
     __shared__ double sm[1024];
     const int tid = threadIdx.x, slab = blockIdx.x;
-    const int C = a.C, G = C >> 2, rpp = 256 / G;
-    const int rl = tid / G, g = tid - rl * G, c = g << 2;
-    const long long r0 = (long long)slab * a.slab_rows;
-    const long long r1 = r0 + a.slab_rows < a.R ? r0 + a.slab_rows : a.R;
+    const int C = a.C, G = C >> 2;
+    const SlabLane ln = slab_lane(tid, G, slab, a.sl.slab_rows, a.sl.R);
+    const int c = ln.c;
     double acc[9][4];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[t][e] = 0.0;
-    if (rl < rpp) {
-        for (long long r = r0 + rl; r < r1; r += rpp) {
+    if (ln.on) {
+        for (long long r = ln.r0 + ln.rl; r < ln.r1; r += ln.rpp) {
             const unsigned ur = (unsigned)r;
             const int ox = (int)(ur % (unsigned)a.OW);
             const unsigned qq = ur / (unsigned)a.OW;
@@ -184,36 +160,16 @@ __global__ __launch_bounds__(256) void dw_wgrad_partial(const DwGradArgs a)
     }
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sm[tid * 4 + e] = acc[t][e];
-        __syncthreads();
-        if (rl == 0) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                double s = 0.0;
-                for (int j = 0; j < rpp; ++j) s += sm[(j * G + g) * 4 + e];
-                a.partial[((long long)slab * 9 + t) * C + c + e] = s;
-            }
-        }
-        __syncthreads();
+        slab_reduce4(sm, acc[t], tid, G, a.partial + ((long long)slab * 9 + t) * C, 0, C);
+        __syncthreads();                                     // sm goes round again
     }
-}
-
-// dw[t][c] = fp32(the slabs' sums added in ascending order)
-__global__ __launch_bounds__(256) void dw_wgrad_final(const DwGradArgs a, float *dw)
-{
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= 9 * a.C) return;
-    double s = 0.0;
-    for (int k = 0; k < a.n_slabs; ++k) s += a.partial[(long long)k * 9 * a.C + idx];
-    dw[idx] = (float)s;
 }
 
 // ----------------------------------------------------------------------------- entry points
 extern "C" int ssd_depthwise_train_forward(const float *x_dev, int32_t B, int32_t H, int32_t W, int32_t C, const float *w_dev,
                                            int32_t stride, float *out_dev, void *stream)
 {
-    DwPlan p;
+    DwArgs p;
     if (const char *why = dw_plan(B, H, W, C, stride, false, p)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_depthwise_train_forward: ") + why);
     if (!x_dev || !w_dev || !out_dev) return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise_train_forward: null pointer");
     if (mis16(x_dev) || mis16(w_dev) || mis16(out_dev)) return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise_train_forward: every pointer needs 16-byte alignment");
@@ -223,93 +179,80 @@ extern "C" int ssd_depthwise_train_forward(const float *x_dev, int32_t B, int32_
 
 extern "C" size_t ssd_depthwise_train_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride)
 {
-    DwPlan p;
-    return dw_plan(B, H, W, C, stride, true, p) ? 0 : p.bytes;
+    DwArgs p;
+    return dw_plan(B, H, W, C, stride, true, p) ? 0 : dw_bytes(p);
 }
 
 extern "C" int ssd_depthwise_train_backward(const float *x_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t C,
                                             const float *w_dev, int32_t stride, float *dx_dev, float *dw_dev, void *workspace_dev,
                                             size_t workspace_bytes, void *stream)
 {
-    DwPlan p;
-    if (const char *why = dw_plan(B, H, W, C, stride, true, p)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_depthwise_train_backward: ") + why);
+    DwArgs a;
+    if (const char *why = dw_plan(B, H, W, C, stride, true, a)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_depthwise_train_backward: ") + why);
     if (!x_dev || !dy_dev || !w_dev || !dw_dev || !workspace_dev) return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise_train_backward: null pointer");
     if (mis16(x_dev) || mis16(dy_dev) || mis16(w_dev) || mis16(dx_dev) || mis16(dw_dev) || mis16(workspace_dev))
         return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise_train_backward: every pointer needs 16-byte alignment");
-    if (workspace_bytes < p.bytes) return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise_train_backward: workspace too small");
+    if (workspace_bytes < dw_bytes(a)) return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise_train_backward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     if (dx_dev) {
         const long long total = (long long)B * ((H + 1) / 2) * ((W + 3) / 4) * (C / 4);
         const unsigned blocks = (unsigned)std::max(1LL, std::min<long long>((total + 255) / 256, 256 * 64));
         if (stride == 1)
-            hipLaunchKernelGGL((dw_dx_kernel<1, 1>), dim3(blocks), dim3(256), 0, s, dy_dev, B, H, W, C, w_dev, p.OH, p.OW, dx_dev);
-        else if (p.pad == 0)
-            hipLaunchKernelGGL((dw_dx_kernel<2, 0>), dim3(blocks), dim3(256), 0, s, dy_dev, B, H, W, C, w_dev, p.OH, p.OW, dx_dev);
+            LAUNCH((dw_dx_kernel<1, 1>), dim3(blocks), s, dy_dev, B, H, W, C, w_dev, a.OH, a.OW, dx_dev);
+        else if (a.pad == 0)
+            LAUNCH((dw_dx_kernel<2, 0>), dim3(blocks), s, dy_dev, B, H, W, C, w_dev, a.OH, a.OW, dx_dev);
         else
-            hipLaunchKernelGGL((dw_dx_kernel<2, 1>), dim3(blocks), dim3(256), 0, s, dy_dev, B, H, W, C, w_dev, p.OH, p.OW, dx_dev);
-        HIPCHK(hipGetLastError());
+            LAUNCH((dw_dx_kernel<2, 1>), dim3(blocks), s, dy_dev, B, H, W, C, w_dev, a.OH, a.OW, dx_dev);
     }
-    DwGradArgs a;
     a.x = x_dev; a.dy = dy_dev;
-    a.H = H; a.W = W; a.C = C; a.OH = p.OH; a.OW = p.OW; a.stride = stride; a.pad = p.pad;
-    a.R = p.R; a.slab_rows = p.slab_rows; a.n_slabs = p.n_slabs;
     a.partial = (double *)workspace_dev;
-    hipLaunchKernelGGL(dw_wgrad_partial, dim3((unsigned)p.n_slabs), dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(dw_wgrad_final, dim3((unsigned)((9 * C + 255) / 256)), dim3(256), 0, s, a, dw_dev);
-    HIPCHK(hipGetLastError());
+    LAUNCH(dw_wgrad_partial, dim3((unsigned)a.sl.n_slabs), s, a);
+    HIPCHK(launch_slab_sum(a.partial, a.sl.n_slabs, 9LL * C, 9 * C, dw_dev, s));
     return SSD_OK;
 }
 
 // ============================================================================= the TRAIN first convolution
-struct FcPlan {
-    int OH, OW;
-    long long R;                     // output rows B * OH * OW
-    int slab_rows, n_slabs;
-    size_t bytes;
+// the plan of a first-convolution call (fc_plan) and, with the pointers, the weight gradient's launch arguments
+struct FcArgs {
+    const uint8_t *img;
+    const float *dy;
+    int B, H, W, C, OH, OW;          // C = Cout
+    Slabs sl;                        // of the OUTPUT rows B * OH * OW
+    double *partial;                 // [n_slabs][27][C]
 };
 
-static const char *fc_plan(int B, int H, int W, int Cout, FcPlan &p)
+static const char *fc_plan(int B, int H, int W, int Cout, FcArgs &p)
 {
     if (B < 1 || H < 1 || W < 1) return "B, H and W must be positive";
     if ((H & 1) || (W & 1)) return "H and W must be even (the network's own size)";
     if (Cout < 4 || Cout > 64 || Cout % 4) return "Cout must be a multiple of 4 and at most 64";
     if ((long long)B * H * W * 3 >= (1LL << 31)) return "B * H * W * 3 must stay below 2^31";
+    p.B = B; p.H = H; p.W = W; p.C = Cout;
     p.OH = H / 2;
     p.OW = W / 2;
-    p.R = (long long)B * p.OH * p.OW;
-    slab_rule(p.R, Cout, p.slab_rows, p.n_slabs);                       // over the OUTPUT rows, C = Cout
-    p.bytes = al256((size_t)p.n_slabs * 27 * Cout * 8);
+    p.sl = slab_rule((long long)B * p.OH * p.OW, Cout / 4);
     return nullptr;
 }
 
-struct FcGradArgs {
-    const uint8_t *img;
-    const float *dy;
-    int B, H, W, C, OH, OW;          // C = Cout
-    long long R;
-    int slab_rows, n_slabs;
-    double *partial;                 // [n_slabs][27][C]
-};
+static size_t fc_bytes(const FcArgs &p) { return al256((size_t)p.sl.n_slabs * 27 * p.C * 8); }
 
-// dw_wgrad_partial's sibling.  Block = slab of output rows x the three filter rows: thread (ky = threadIdx.y, rl = tid / G,
-// g = tid % G), G = C / 4, rpp = 256 / G, walks the rows r0 + rl, r0 + rl + rpp, ... of its slab for the channel quad g and keeps
-// the sums of p * dy of filter row ky -- 3 pixels x 3 channels x 4 output channels, 36 doubles -- so that the 27 x 4 accumulators
-// of a channel quad are spread over three threads of one block, which read the same dy rows at about the same time, instead of
-// filling one thread's register file.  The nine bytes under a filter row are contiguous, 0 or 2 bytes past a dword
-// boundary (W is even; which of the two depends on the row when W % 4 == 2): three aligned dword loads through a range-checked
-// buffer resource and a byte alignment, as in first_conv_px_kernel (elementwise.hip).  Only row 2oy+2 and column 2ox+2 can lie
-// outside the image: such taps are skipped.  The product of two floats is exact in double, so fma(p, dy, acc) has the bits of
-// acc + p * dy.  The block then adds its rpp row lanes in ascending order, one tap at a time
-// through LDS.
-__global__ __launch_bounds__(768) void fc_wgrad_partial(const FcGradArgs a)
+// dw_wgrad_partial's sibling.  Block = slab of output rows x the three filter rows: thread (ky = threadIdx.y, tid = threadIdx.x)
+// is lane tid of the column-sum core, G = C / 4, for filter row ky: it keeps the sums of p * dy of that row -- 3 pixels x 3
+// channels x 4 output channels, 36 doubles -- so that the 27 x 4 accumulators of a channel quad are spread over three threads of
+// one block, which read the same dy rows at about the same time, instead of filling one thread's register file.  The nine bytes
+// under a filter row are contiguous, 0 or 2 bytes past a dword boundary (W is even; which of the two depends on the row when
+// W % 4 == 2): three aligned dword loads through a range-checked buffer resource and a byte alignment, as in first_conv_px_kernel
+// (elementwise.hip).  Only row 2oy+2 and column 2ox+2 can lie outside the image: such taps are skipped.  The product of two
+// floats is exact in double, so fma(p, dy, acc) has the bits of acc + p * dy.  The block then adds its row lanes one tap at a
+// time, each filter row in its own third of the LDS.
+__global__ __launch_bounds__(768) void fc_wgrad_partial(const FcArgs a)
 {
     __shared__ double sm[3][1024];
     const int tid = threadIdx.x, ky = threadIdx.y, slab = blockIdx.x;
-    const int C = a.C, G = C >> 2, rpp = 256 / G;
-    const int rl = tid / G, g = tid - rl * G, c = g << 2;
-    const long long r0 = (long long)slab * a.slab_rows;
-    const long long r1 = r0 + a.slab_rows < a.R ? r0 + a.slab_rows : a.R;
+    const int C = a.C, G = C >> 2;
+    const SlabLane ln = slab_lane(tid, G, slab, a.sl.slab_rows, a.sl.R);
+    const int c = ln.c, rpp = ln.rpp;
+    const long long r0 = ln.r0, r1 = ln.r1;
     const float inv255 = (float)(1.0 / 255.0);
     const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.img, 0, (int)((long long)a.B * a.H * a.W * 3), 0x00020000);
     double acc[9][4];
@@ -317,15 +260,15 @@ __global__ __launch_bounds__(768) void fc_wgrad_partial(const FcGradArgs a)
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[t][e] = 0.0;
-    if (rl < rpp) {
+    if (ln.on) {
         // r -> (row = b * OH + oy, ox) once; a step of rpp rows then moves ox by rpp % OW and row by rpp / OW (+ 1 on a carry), and
         // oy = row % OH follows with one conditional subtraction: no division inside the loop.  H = 2 * OH, so the image row of
         // tap ky is b * H + 2 * oy + ky = 2 * row + ky.
         const int OW = a.OW, OH = a.OH;
         const int step_x = rpp % OW, step_row = rpp / OW, step_y = step_row % OH;
-        const unsigned first = (unsigned)(r0 + rl);
+        const unsigned first = (unsigned)(r0 + ln.rl);
         int ox = (int)(first % (unsigned)OW), row = (int)(first / (unsigned)OW), oy = row % OH;
-        for (long long r = r0 + rl; r < r1; r += rpp) {
+        for (long long r = r0 + ln.rl; r < r1; r += rpp) {
             const int cx = ox, crow = row, cy = oy;
             ox += step_x; row += step_row; oy += step_y;
             if (ox >= OW) { ox -= OW; ++row; ++oy; }
@@ -366,32 +309,15 @@ __global__ __launch_bounds__(768) void fc_wgrad_partial(const FcGradArgs a)
     }
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sm[ky][tid * 4 + e] = acc[t][e];
-        __syncthreads();
-        if (rl < 4) {                                        // rpp >= 16: row lanes 0 .. 3 exist; lane rl adds element e = rl of the quad
-            double s = 0.0;
-            for (int j = 0; j < rpp; ++j) s += sm[ky][(j * G + g) * 4 + rl];
-            a.partial[((long long)slab * 27 + ky * 9 + t) * C + c + rl] = s;
-        }
-        __syncthreads();
+        slab_reduce4(sm[ky], acc[t], tid, G, a.partial + ((long long)slab * 27 + ky * 9 + t) * C, 0, C);
+        __syncthreads();                                     // sm goes round again
     }
-}
-
-// dw[t][c] = fp32(the slabs' sums added in ascending order)
-__global__ __launch_bounds__(256) void fc_wgrad_final(const FcGradArgs a, float *dw)
-{
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= 27 * a.C) return;
-    double s = 0.0;
-    for (int k = 0; k < a.n_slabs; ++k) s += a.partial[(long long)k * 27 * a.C + idx];
-    dw[idx] = (float)s;
 }
 
 extern "C" int ssd_first_conv_train_forward(const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, const float *w_dev, int32_t Cout,
                                             float *out_dev, void *stream)
 {
-    FcPlan p;
+    FcArgs p;
     if (const char *why = fc_plan(B, H, W, Cout, p)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_first_conv_train_forward: ") + why);
     if (!images_dev || !w_dev || !out_dev) return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_forward: null pointer (images_dev, w_dev, out_dev)");
     if (mis16(w_dev) || mis16(out_dev)) return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_forward: w_dev and out_dev need 16-byte alignment");
@@ -402,30 +328,26 @@ extern "C" int ssd_first_conv_train_forward(const uint8_t *images_dev, int32_t B
 
 extern "C" size_t ssd_first_conv_train_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t Cout)
 {
-    FcPlan p;
-    return fc_plan(B, H, W, Cout, p) ? 0 : p.bytes;
+    FcArgs p;
+    return fc_plan(B, H, W, Cout, p) ? 0 : fc_bytes(p);
 }
 
 extern "C" int ssd_first_conv_train_backward(const uint8_t *images_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t Cout,
                                              float *dw_dev, void *workspace_dev, size_t workspace_bytes, void *stream)
 {
-    FcPlan p;
-    if (const char *why = fc_plan(B, H, W, Cout, p)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_first_conv_train_backward: ") + why);
+    FcArgs a;
+    if (const char *why = fc_plan(B, H, W, Cout, a)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_first_conv_train_backward: ") + why);
     if (!images_dev || !dy_dev || !dw_dev || !workspace_dev)
         return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_backward: null pointer (images_dev, dy_dev, dw_dev, workspace_dev)");
     if (mis16(dy_dev) || mis16(dw_dev) || mis16(workspace_dev))
         return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_backward: dy_dev, dw_dev and workspace_dev need 16-byte alignment");
     if ((uintptr_t)images_dev & 3) return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_backward: images_dev needs 4-byte alignment");
-    if (workspace_bytes < p.bytes) return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_backward: workspace too small");
+    if (workspace_bytes < fc_bytes(a)) return ssd_fail(SSD_ERR_INVALID, "ssd_first_conv_train_backward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    FcGradArgs a;
     a.img = images_dev; a.dy = dy_dev;
-    a.B = B; a.H = H; a.W = W; a.C = Cout; a.OH = p.OH; a.OW = p.OW;
-    a.R = p.R; a.slab_rows = p.slab_rows; a.n_slabs = p.n_slabs;
     a.partial = (double *)workspace_dev;
-    hipLaunchKernelGGL(fc_wgrad_partial, dim3((unsigned)p.n_slabs), dim3(256, 3), 0, s, a);
+    hipLaunchKernelGGL(fc_wgrad_partial, dim3((unsigned)a.sl.n_slabs), dim3(256, 3), 0, s, a);     // 256 x 3: not LAUNCH's block
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(fc_wgrad_final, dim3((unsigned)((27 * Cout + 255) / 256)), dim3(256), 0, s, a, dw_dev);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_slab_sum(a.partial, a.sl.n_slabs, 27LL * Cout, 27 * Cout, dw_dev, s));
     return SSD_OK;
 }

@@ -1,4 +1,5 @@
-// Launch arguments of the TRAIN head's own kernels (train_head.hip, wgrad.hip); the C ABI is in include/ssd_hip.h.
+// Launch arguments of the TRAIN head's own kernels (train_head.hip, wgrad.hip) and the column-sum core they share with
+// train_backbone.hip; the C ABI is in include/ssd_hip.h.
 #pragma once
 #include "../../include/ssd_hip.h"
 #include "ssd_internal.h"
@@ -23,15 +24,55 @@ struct WgradArgs {
 int wgrad_tile_n(int Cout);
 hipError_t launch_wgrad(const WgradArgs &a, float *dw, hipStream_t s);
 
+static inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
+static inline bool mis16(const void *p) { return ((uintptr_t)p & 15) != 0; }
+
+// a 256-thread launch inside an entry point (host.h's HIPCHK returns on an error)
+#define LAUNCH(kernel, grid, s, ...)                                  \
+    do {                                                              \
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, __VA_ARGS__); \
+        HIPCHK(hipGetLastError());                                    \
+    } while (0)
+
+// ----------------------------------------------------------------------------- the column-sum core
+// Sums over the rows of a [rows][C] tensor, per column, in double and in an order fixed by the shapes alone (include/ssd_hip.h:
+// the batch norm's slab order): the batch norm's statistics and dbias (train_head.hip), the depthwise and the first convolution's
+// weight gradients (train_backbone.hip).  The rows are cut into slabs of `slab_rows`; block = slab.  Thread (rl = tid / G,
+// g = tid % G) of a block's 256 walks the rows r0 + rl, r0 + rl + rpp, ... of its slab for the channel quad g (G quads, rpp = 256 / G
+// rows per pass), adding in double; the block then adds its rpp row lanes in ascending order (slab_reduce4) and writes one double per
+// column and slab; the second stage (launch_slab_sum, or stat_final where it does more than sum) adds the slabs in ascending order.
+#define TH_STAT_COLS 1024  // channels one block covers (256 threads x 4)
+
+// The slab rule for a tensor of R rows of G channel quads (1 <= G <= 256): about 1024 blocks in all, a slab a whole number of passes
+// and at least 8 of them: slab_rows = max(8 * rpp, ceil(R / 1024)) rounded up to a multiple of rpp.  The result is what the
+// tensor's kernels take; a level list (train_head.hip make_slabs) applies the rule to the rows of all its levels together.
+struct Slabs {
+    long long R;
+    int slab_rows, n_slabs;
+};
+static inline Slabs slab_rule(long long R, int G)
+{
+    const int rpp = 256 / G;
+    long long sr = (R + 1023) / 1024;
+    if (sr < 8LL * rpp) sr = 8LL * rpp;
+    sr = (sr + rpp - 1) / rpp * rpp;
+    return {R, (int)sr, (int)((R + sr - 1) / sr)};
+}
+
+// out[i] = fp32(partial[i] + partial[stride + i] + ... + partial[(n_slabs - 1) * stride + i]), i < n: added in double in ascending
+// slab order, rounded once (train_head.hip)
+hipError_t launch_slab_sum(const double *partial, int n_slabs, long long stride, int n, float *out, hipStream_t s);
+
+#ifdef __HIPCC__
+typedef float v4f __attribute__((ext_vector_type(4)));
+
 // 4 consecutive channels of a row from channel c on: one 16-byte access where C % 4 == 0 (c % 4 == 0, so the quad is inside or
 // outside as a whole), else element by element; channels beyond C read 0 / are not written
-#ifdef __HIPCC__
-typedef float th_v4f __attribute__((ext_vector_type(4)));
-static __device__ inline th_v4f th_load4(const float *row, int c, int C, bool vec)
+static __device__ inline v4f th_load4(const float *row, int c, int C, bool vec)
 {
-    th_v4f v = {0.f, 0.f, 0.f, 0.f};
+    v4f v = {0.f, 0.f, 0.f, 0.f};
     if (vec) {
-        if (c < C) v = *(const th_v4f *)(row + c);
+        if (c < C) v = *(const v4f *)(row + c);
     } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -39,22 +80,59 @@ static __device__ inline th_v4f th_load4(const float *row, int c, int C, bool ve
     }
     return v;
 }
-static __device__ inline void th_store4(float *row, int c, int C, bool vec, th_v4f v)
+static __device__ inline void th_store4(float *row, int c, int C, bool vec, v4f v)
 {
     if (vec) {
-        if (c < C) *(th_v4f *)(row + c) = v;
+        if (c < C) *(v4f *)(row + c) = v;
     } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (c + e < C) row[c + e] = v[e];
     }
 }
+
+// a thread's place in its block's slab (slab: counted within its tensor): the row lane rl, the first channel c of its quad
+// g = tid % G within the block's columns, the rows [r0, r1) of the slab, and whether the lane walks rows at all (256 % G lanes of
+// a block idle)
+struct SlabLane {
+    int rl, c, rpp;
+    long long r0, r1;
+    bool on;
+};
+static __device__ inline SlabLane slab_lane(int tid, int G, int slab, int slab_rows, long long rows)
+{
+    SlabLane t;
+    t.rpp = 256 / G;
+    t.rl = tid / G;
+    t.c = (tid - t.rl * G) << 2;
+    t.r0 = (long long)slab * slab_rows;
+    t.r1 = t.r0 + slab_rows < rows ? t.r0 + slab_rows : rows;
+    t.on = t.rl < t.rpp;
+    return t;
+}
+
+// The in-block reduction of one quantity: every thread of the block hands in its quad's four sums (idle lanes: zeros, never read),
+// sm holds 1024 doubles.  Column i of the block's 4 * G is then the sum over j of lane (j, i / 4)'s element i % 4, j = 0 .. rpp - 1
+// ASCENDING from +0, by thread i, i + 256, ...: sm is read and dst written at consecutive addresses, for any rpp >= 1.  Column
+// c0 + i of the tensor goes to dst[c0 + i] where it is below C (the batch norm takes C % 4 != 0).  There is no barrier behind the
+// reads: a caller that hands in the same sm again puts a __syncthreads() between the two calls.
+static __device__ inline void slab_reduce4(double *sm, const double (&acc)[4], int tid, int G, double *dst, int c0, int C)
+{
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sm[tid * 4 + e] = acc[e];
+    __syncthreads();
+    const int n = G << 2, rpp = 256 / G;
+    for (int i = tid; i < n; i += 256) {
+        double s = 0.0;
+        for (int j = 0; j < rpp; ++j) s += sm[j * n + i];
+        if (c0 + i < C) dst[c0 + i] = s;
+    }
+}
 #endif
 
-#define TH_STAT_COLS 1024  // channels one block of the column statistics covers (256 threads x 4)
-// train_head.hip: column statistics and the batch norm.  A level's rows are cut into slabs of `slab_rows`; block = slab.
+// train_head.hip: the column statistics of a level list and the batch norm.  A slab never crosses a level.
 struct StatLevel {
-    ssd_bn_level p;        // the caller's level (dbias: x = a level's dy, lv[0].out = dbias)
+    ssd_bn_level p;        // the caller's level (dbias: x = a level's dy)
     int slab_begin, n_slabs;
     float unbias;          // (float)(rows / (rows - 1)), 1 when rows == 1
 };

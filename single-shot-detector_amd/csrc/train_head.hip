@@ -12,10 +12,6 @@
 #include <algorithm>
 #include <cstring>
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-static inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-
 // ----------------------------------------------------------------------------- kernel packing on the device
 // w HWIO [k,k,Cin,Cout] (device), taps = k * k = 1 or 9 -> wt [taps][rows][kp] in physical channel order, zero where a channel is padding.
 //   transpose == 0  the forward's kernel: row = output channel co, k = input channel ci, tap as stored
@@ -37,10 +33,9 @@ __global__ __launch_bounds__(256) void pack_w_kernel(const float *w, int Cin, in
 }
 
 // ----------------------------------------------------------------------------- column statistics
-// Thread (rl = tid / G, g = tid % G) of a block walks the rows r0 + rl, r0 + rl + rpp, ... of its slab for the channel quad g
-// (G = ceil(min(C, 1024) / 4) quads, rpp = 256 / G rows per pass; a tensor wider than 1024 channels -- dbias only -- takes one
-// block per 1024 channels and slab), adding in double; the block then adds its rpp row lanes in ascending
-// order.  The second stage (stat_final) adds a level's slabs in ascending order.  Both orders are fixed by the shapes alone.
+// The column-sum core of train_head.h over a level list: G = ceil(min(C, 1024) / 4) quads; a tensor wider than 1024 channels -- dbias
+// only -- takes one block per 1024 channels and slab.  The second stage (stat_final; dbias: launch_slab_sum) adds a level's slabs in
+// ascending order.  Both orders are fixed by the shapes alone.
 static __device__ inline int th_level(const StatArgs &a, int slab)
 {
     int l = 0;
@@ -58,17 +53,16 @@ __global__ __launch_bounds__(256) void stat_partial(const StatArgs a)
     __shared__ double sm[MODE == 2 ? 2 : 1][1024];
     const int tid = threadIdx.x, slab = blockIdx.x;
     const StatLevel &L = a.lv[th_level(a, slab)];
-    const int C = a.C, G = (a.CW + 3) >> 2, rpp = 256 / G;
-    const int rl = tid / G, g = tid - rl * G, c = blockIdx.y * TH_STAT_COLS + (g << 2);     // (blockIdx.y > 0: dbias of a layer wider than one block)
+    const int C = a.C, G = (a.CW + 3) >> 2;
+    const SlabLane ln = slab_lane(tid, G, slab - L.slab_begin, a.slab_rows, L.p.rows);
+    const int c0 = blockIdx.y * TH_STAT_COLS, c = c0 + ln.c;               // (blockIdx.y > 0: dbias of a layer wider than one block)
     const bool vec = (C & 3) == 0;
-    const long long r0 = (long long)(slab - L.slab_begin) * a.slab_rows;
-    const long long r1 = r0 + a.slab_rows < L.p.rows ? r0 + a.slab_rows : L.p.rows;
     double acc[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-    if (rl < rpp) {
+    if (ln.on) {
         v4f mean = {0, 0, 0, 0}, invstd = mean, gamma = mean, beta = mean;
         if (MODE >= 1) mean = th_load4(L.p.mean, c, C, vec);
         if (MODE == 2) { invstd = th_load4(L.p.invstd, c, C, vec); gamma = th_load4(L.p.gamma, c, C, vec); beta = th_load4(L.p.beta, c, C, vec); }
-        for (long long r = r0 + rl; r < r1; r += rpp) {
+        for (long long r = ln.r0 + ln.rl; r < ln.r1; r += ln.rpp) {
             const v4f x = th_load4(L.p.x + r * C, c, C, vec);
             if (MODE == 0) {
 #pragma unroll
@@ -89,34 +83,19 @@ __global__ __launch_bounds__(256) void stat_partial(const StatArgs a)
             }
         }
     }
-    constexpr int NQ = MODE == 2 ? 2 : 1;
 #pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sm[q][tid * 4 + e] = acc[q][e];
-    __syncthreads();
-    if (rl == 0) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                double s = 0.0;
-                for (int j = 0; j < rpp; ++j) s += sm[q][(j * G + g) * 4 + e];
-                if (c + e < C) a.partial[((long long)slab * 2 + q) * C + c + e] = s;
-            }
-    }
+    for (int q = 0; q < (MODE == 2 ? 2 : 1); ++q) slab_reduce4(sm[q], acc[q], tid, G, a.partial + ((long long)slab * 2 + q) * C, c0, C);
 }
 
-// MODE 0: mean | 1: var, invstd, moving statistics | 2: dgamma, dbeta | 3: the sum over every slab of every level -> lv[0].out (dbias)
+// MODE 0: mean | 1: var, invstd, moving statistics | 2: dgamma, dbeta
 template <int MODE>
 __global__ __launch_bounds__(256) void stat_final(const StatArgs a)
 {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= a.C) return;
     const StatLevel &L = a.lv[blockIdx.y];
-    const int s0 = MODE == 3 ? 0 : L.slab_begin, s1 = MODE == 3 ? a.n_slabs : L.slab_begin + L.n_slabs;
     double s = 0.0, t = 0.0;
-    for (int k = s0; k < s1; ++k) {
+    for (int k = L.slab_begin; k < L.slab_begin + L.n_slabs; ++k) {
         s += a.partial[((long long)k * 2) * a.C + c];
         if (MODE == 2) t += a.partial[((long long)k * 2 + 1) * a.C + c];
     }
@@ -132,7 +111,23 @@ __global__ __launch_bounds__(256) void stat_final(const StatArgs a)
         }
     }
     if (MODE == 2) { L.p.dbeta[c] = (float)s; L.p.dgamma[c] = (float)t; }
-    if (MODE == 3) L.p.out[c] = (float)s;
+}
+
+// the second stage where it only sums (train_head.h): dbias over every slab of every level, the weight gradients of train_backbone.hip
+__global__ __launch_bounds__(256) void slab_sum_kernel(const double *__restrict__ partial, int n_slabs, long long stride, int n,
+                                                       float *__restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int k = 0; k < n_slabs; ++k) s += partial[k * stride + i];
+    out[i] = (float)s;
+}
+
+hipError_t launch_slab_sum(const double *partial, int n_slabs, long long stride, int n, float *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, partial, n_slabs, stride, n, out);
+    return hipGetLastError();
 }
 
 // y = act((x - mean) * sf + beta), act = ReLU or ReLU6 (elementwise.hip act_apply): training -- the batch's mean, sf = gamma * invstd; inference -- the moving mean,
@@ -141,12 +136,10 @@ __global__ __launch_bounds__(256) void bn_apply_forward(const StatArgs a)
 {
     const int tid = threadIdx.x, slab = blockIdx.x;
     const StatLevel &L = a.lv[th_level(a, slab)];
-    const int C = a.C, G = (a.CW + 3) >> 2, rpp = 256 / G;
-    const int rl = tid / G, g = tid - rl * G, c = g << 2;
-    if (rl >= rpp) return;
+    const SlabLane ln = slab_lane(tid, (a.CW + 3) >> 2, slab - L.slab_begin, a.slab_rows, L.p.rows);
+    const int C = a.C, c = ln.c;
+    if (!ln.on) return;
     const bool vec = (C & 3) == 0;
-    const long long r0 = (long long)(slab - L.slab_begin) * a.slab_rows;
-    const long long r1 = r0 + a.slab_rows < L.p.rows ? r0 + a.slab_rows : L.p.rows;
     const v4f gamma = th_load4(L.p.gamma, c, C, vec), beta = th_load4(L.p.beta, c, C, vec);
     v4f mean, sf;
     if (a.training) {
@@ -160,7 +153,7 @@ __global__ __launch_bounds__(256) void bn_apply_forward(const StatArgs a)
 #pragma unroll
         for (int e = 0; e < 4; ++e) sf[e] = gamma[e] * __fdiv_rn(1.0f, sqrtf(mv[e] + a.eps));
     }
-    for (long long r = r0 + rl; r < r1; r += rpp) {
+    for (long long r = ln.r0 + ln.rl; r < ln.r1; r += ln.rpp) {
         v4f x = th_load4(L.p.x + r * C, c, C, vec);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -179,19 +172,17 @@ __global__ __launch_bounds__(256) void bn_apply_backward(const StatArgs a)
 {
     const int tid = threadIdx.x, slab = blockIdx.x;
     const StatLevel &L = a.lv[th_level(a, slab)];
-    const int C = a.C, G = (a.CW + 3) >> 2, rpp = 256 / G;
-    const int rl = tid / G, g = tid - rl * G, c = g << 2;
-    if (rl >= rpp) return;
+    const SlabLane ln = slab_lane(tid, (a.CW + 3) >> 2, slab - L.slab_begin, a.slab_rows, L.p.rows);
+    const int C = a.C, c = ln.c;
+    if (!ln.on) return;
     const bool vec = (C & 3) == 0;
-    const long long r0 = (long long)(slab - L.slab_begin) * a.slab_rows;
-    const long long r1 = r0 + a.slab_rows < L.p.rows ? r0 + a.slab_rows : L.p.rows;
     const v4f gamma = th_load4(L.p.gamma, c, C, vec), beta = th_load4(L.p.beta, c, C, vec), mean = th_load4(L.p.mean, c, C, vec);
     const v4f invstd = th_load4(L.p.invstd, c, C, vec), dgamma = th_load4(L.p.dgamma, c, C, vec), dbeta = th_load4(L.p.dbeta, c, C, vec);
     const float Rf = (float)L.p.rows;
     v4f sf, c1, c2;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { sf[e] = gamma[e] * invstd[e]; c1[e] = __fdiv_rn(dbeta[e], Rf); c2[e] = __fdiv_rn(dgamma[e], Rf); }
-    for (long long r = r0 + rl; r < r1; r += rpp) {
+    for (long long r = ln.r0 + ln.rl; r < ln.r1; r += ln.rpp) {
         const v4f x = th_load4(L.p.x + r * C, c, C, vec), dy = th_load4(L.p.dy + r * C, c, C, vec);
         v4f d;
 #pragma unroll
@@ -206,31 +197,20 @@ __global__ __launch_bounds__(256) void bn_apply_backward(const StatArgs a)
     }
 }
 
-// slabs of a level list: about 1024 blocks in all, a slab a whole number of passes
+// slabs of a level list: the slab rule on the rows of every level together, each level its own run of slabs
 static void make_slabs(StatArgs &a)
 {
     a.CW = a.C < TH_STAT_COLS ? a.C : TH_STAT_COLS;
-    const int G = (a.CW + 3) / 4, rpp = 256 / G;
     long long tot = 0;
     for (int l = 0; l < a.nlevels; ++l) tot += a.lv[l].p.rows;
-    long long sr = (tot + 1023) / 1024;
-    if (sr < 8LL * rpp) sr = 8LL * rpp;
-    sr = (sr + rpp - 1) / rpp * rpp;
-    a.slab_rows = (int)sr;
-    int n = 0;
+    a.slab_rows = slab_rule(tot, (a.CW + 3) / 4).slab_rows;
+    a.n_slabs = 0;
     for (int l = 0; l < a.nlevels; ++l) {
-        a.lv[l].slab_begin = n;
-        a.lv[l].n_slabs = (int)((a.lv[l].p.rows + sr - 1) / sr);
-        n += a.lv[l].n_slabs;
+        a.lv[l].slab_begin = a.n_slabs;
+        a.lv[l].n_slabs = (int)((a.lv[l].p.rows + a.slab_rows - 1) / a.slab_rows);
+        a.n_slabs += a.lv[l].n_slabs;
     }
-    a.n_slabs = n;
 }
-
-#define LAUNCH(kernel, grid, s, ...)                                  \
-    do {                                                              \
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, __VA_ARGS__); \
-        HIPCHK(hipGetLastError());                                    \
-    } while (0)
 
 // ----------------------------------------------------------------------------- the convolutions
 // One planner for the TRAIN head's 3x3 stride-1 calls and the TRAIN FPN's k x k / stride-2 / upsample-add calls: a level's
@@ -315,8 +295,6 @@ static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, in
     p.bytes = p.off_up + (with_up ? al256((size_t)p.Rup_tot * p.f.CoutP * 4 + 256) : 0);
     return nullptr;
 }
-
-static inline bool mis16(const void *p) { return ((uintptr_t)p & 15) != 0; }
 
 // dy [B,OH,OW,C] logical -> D [B,H,W,Cp] physical, D[b,2oy,2ox,:] = dy[b,oy,ox,:] and zero elsewhere (and in the padding
 // channels): the permute of the data gradient's operand, scattering the gradient of a stride-2 layer over the input's grid
@@ -453,9 +431,8 @@ static int conv_train_backward(const std::string &fn, const ssd_conv_level *leve
         StatArgs st = p.st;
         st.partial = (double *)(ws + p.off_stat);
         for (int l = 0; l < n_levels; ++l) st.lv[l].p.x = levels[l].dy;
-        st.lv[0].p.out = dbias_dev;
         LAUNCH(stat_partial<0>, dim3((unsigned)st.n_slabs, (unsigned)((Cout + TH_STAT_COLS - 1) / TH_STAT_COLS)), s, st);
-        LAUNCH(stat_final<3>, dim3((unsigned)((Cout + 255) / 256), 1), s, st);
+        HIPCHK(launch_slab_sum(st.partial, st.n_slabs, 2LL * Cout, Cout, dbias_dev, s));
     }
     return SSD_OK;
 }

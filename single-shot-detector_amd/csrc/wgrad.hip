@@ -10,7 +10,6 @@
 #include "train_head.h"
 
 typedef float v16f __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 static __device__ inline unsigned wg_udiv(unsigned n, UDiv d) { return d.sh < 0 ? n : (__umulhi(n, d.mag) >> d.sh); }
 

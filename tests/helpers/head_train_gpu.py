@@ -26,8 +26,16 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
 
 
-def bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, dys=None, training=1, fill=float("nan"), workspace=True):
-    """ssd_bn_relu_train_forward (and, with dys, _backward) straight through the C ABI; returns per level dicts of numpy arrays.
+ACT = {"relu": 1, "relu6": 2}
+
+
+def stream(cuda):
+    return ctypes.c_void_p(cuda.cuda.current_stream().cuda_stream)
+
+
+def bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, dys=None, training=1, fill=float("nan"), workspace=True, act=None):
+    """ssd_bn_relu_train_forward (and, with dys, _backward) straight through the C ABI -- act "relu" or "relu6": ssd_bn_act_train_*
+    with that act; returns per level dicts of numpy arrays.
     Every output is pre-filled with `fill`; the statistics sit in rows padded to a multiple of 4 channels, so that every pointer
     is 16-byte aligned for any C.  workspace=False passes NULL (inference mode does not use it)."""
     L = ssd.lib()
@@ -48,14 +56,15 @@ def bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, dys=None, training=1, fill=fl
             setattr(lv[i], name, v.data_ptr() if v is not None else None)
     ws = cuda.empty(max(L.ssd_bn_relu_train_workspace_bytes(lv, n, C), 256), dtype=cuda.uint8, device="cuda")
     wsp, wsb = (ws.data_ptr(), ws.numel()) if workspace else (None, 0)
-    s = ctypes.c_void_p(cuda.cuda.current_stream().cuda_stream)
-    ssd._lib.check(L.ssd_bn_relu_train_forward(lv, n, C, training, float(f32(ref.EPS)), float(f32(1.0 - ref.MOMENTUM)), wsp, wsb, s))
+    family, acts = ("ssd_bn_relu_train_", ()) if act is None else ("ssd_bn_act_train_", (ACT[act],))
+    s = stream(cuda)
+    ssd._lib.check(getattr(L, family + "forward")(lv, n, C, *acts, training, float(f32(ref.EPS)), float(f32(1.0 - ref.MOMENTUM)), wsp, wsb, s))
     out = [dict(y=Y[i].cpu().numpy(), mean=st[i, 0, :C].cpu().numpy(), var=st[i, 1, :C].cpu().numpy(), invstd=st[i, 2, :C].cpu().numpy(),
                 mm=MM[i].cpu().numpy(), mv=MV[i].cpu().numpy()) for i in range(n)]
     if dys is not None:
         for i in range(n):
             lv[i].out = DX[i].data_ptr()
-        ssd._lib.check(L.ssd_bn_relu_train_backward(lv, n, C, wsp, wsb, s))
+        ssd._lib.check(getattr(L, family + "backward")(lv, n, C, *acts, wsp, wsb, s))
         for i in range(n):
             out[i].update(dx=DX[i].cpu().numpy(), dgamma=st[i, 3, :C].cpu().numpy(), dbeta=st[i, 4, :C].cpu().numpy())
     return out
@@ -84,7 +93,7 @@ def _conv_raw(ssd, cuda, which, general, X, DY, OUT, Wt, stride, *ptrs):
     need = L.ssd_conv_train_workspace_bytes(*dims, k, stride, 0) if general else L.ssd_conv3x3_train_workspace_bytes(*dims)
     assert need > 0
     ws = cuda.empty(need, dtype=cuda.uint8, device="cuda")
-    tail = (ws.data_ptr(), ws.numel(), ctypes.c_void_p(cuda.cuda.current_stream().cuda_stream))
+    tail = (ws.data_ptr(), ws.numel(), stream(cuda))
     if general:
         up = (None,) if which == "forward" else ()
         ssd._lib.check(getattr(L, "ssd_conv_train_" + which)(*dims, k, stride, Wt.data_ptr(), *ptrs, *up, *tail))

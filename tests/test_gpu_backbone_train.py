@@ -3,14 +3,12 @@ its data gradient against the CPU oracle bit for bit, its weight gradient exactl
 rounded once on random data, the 1x1 data gradient against the oracle bit for bit, the batch norm with ReLU6 against the header's
 float32 sequence, the refusals, TrainableMobileNet in inference mode against the engine bit for bit and in training mode against a
 float64 restatement with forced gates, the FPN's bridge to c3, c4, c5, and the closed loop through a checkpoint."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from helpers import backbone_train_ref as ref
 from helpers import head_train_ref as href
-from helpers.head_train_gpu import bn_raw, conv_backward, dev as _dev, same_bits
+from helpers.head_train_gpu import bn_raw, conv_backward, dev as _dev, same_bits, stream as _stream
 from conftest import TINY_PARAMS
 
 pytestmark = pytest.mark.gpu
@@ -21,10 +19,6 @@ B = 2
 LP = {"gamma": 2.0, "alpha": 0.25}
 SIZES = [(6, 8), (5, 7), (13, 17), (1, 1), (2, 2)]                    # 13 x 17 leaves remainders in every thread's 2 x 4 patch
 WIDTHS = [4, 36, 1024]
-
-
-def _stream(cuda):
-    return ctypes.c_void_p(cuda.cuda.current_stream().cuda_stream)
 
 
 def _dw_data(rng, h, w, C, stride, integers=False, batch=B):
@@ -165,43 +159,6 @@ def test_pointwise_data_gradient_is_the_oracles_convolution_bit_for_bit(ssd, cud
 
 
 # ----------------------------------------------------------------------------- 5. the batch norm with ReLU6
-ACT = {"relu": 1, "relu6": 2}
-
-
-def _bn_act_raw(ssd, cuda, act, xs, gammas, betas, mms, mvs, dys=None, training=1):
-    """ssd_bn_act_train_forward (and, with dys, _backward) straight through the C ABI, laid out as head_train_gpu.bn_raw lays out
-    the old pair; every output pre-filled with NaN."""
-    L = ssd.lib()
-    n, C = len(xs), xs[0].shape[-1]
-    Cp = (C + 3) // 4 * 4
-    t = lambda a: _dev(cuda, a)
-    X, G, Bt, MM, MV = [t(v) for v in xs], [t(v) for v in gammas], [t(v) for v in betas], [t(v) for v in mms], [t(v) for v in mvs]
-    Y = [cuda.full_like(v, float("nan")) for v in X]
-    st = cuda.full((n, 5, Cp), float("nan"), device="cuda")
-    DX = [cuda.full_like(v, float("nan")) for v in X]
-    DY = [t(v) for v in dys] if dys is not None else [None] * n
-    lv = (ssd._lib.SsdBnLevel * n)()
-    for i in range(n):
-        lv[i].rows = X[i].numel() // C
-        for name, v in (("x", X[i]), ("dy", DY[i]), ("out", Y[i]), ("gamma", G[i]), ("beta", Bt[i]), ("moving_mean", MM[i]),
-                        ("moving_variance", MV[i]), ("mean", st[i, 0]), ("var", st[i, 1]), ("invstd", st[i, 2]), ("dgamma", st[i, 3]),
-                        ("dbeta", st[i, 4])):
-            setattr(lv[i], name, v.data_ptr() if v is not None else None)
-    ws = cuda.empty(max(L.ssd_bn_relu_train_workspace_bytes(lv, n, C), 256), dtype=cuda.uint8, device="cuda")
-    s = _stream(cuda)
-    ssd._lib.check(L.ssd_bn_act_train_forward(lv, n, C, ACT[act], training, float(f32(ref.EPS)), float(f32(1.0 - ref.MOMENTUM)),
-                                              ws.data_ptr(), ws.numel(), s))
-    out = [dict(y=Y[i].cpu().numpy(), mean=st[i, 0, :C].cpu().numpy(), var=st[i, 1, :C].cpu().numpy(), invstd=st[i, 2, :C].cpu().numpy(),
-                mm=MM[i].cpu().numpy(), mv=MV[i].cpu().numpy()) for i in range(n)]
-    if dys is not None:
-        for i in range(n):
-            lv[i].out = DX[i].data_ptr()
-        ssd._lib.check(L.ssd_bn_act_train_backward(lv, n, C, ACT[act], ws.data_ptr(), ws.numel(), s))
-        for i in range(n):
-            out[i].update(dx=DX[i].cpu().numpy(), dgamma=st[i, 3, :C].cpu().numpy(), dbeta=st[i, 4, :C].cpu().numpy())
-    return out
-
-
 def _same_bits_or_nan(a, b):
     """Bit equality where either is a number; a NaN only has to meet a NaN (its payload is not pinned)."""
     na, nb = np.isnan(a), np.isnan(b)
@@ -228,7 +185,7 @@ def test_batch_norm_relu6_is_the_headers_float32_sequence_bit_for_bit(ssd, cuda,
     xs, gammas, betas, mms, mvs, dys = _bn_inputs(np.random.default_rng(C), rows, C)
     for x in xs:
         x[3, 2] = np.nan
-    first = _bn_act_raw(ssd, cuda, "relu6", xs, gammas, betas, mms, mvs)
+    first = bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, act="relu6")
     for i, g in enumerate(first):
         assert same_bits(g["invstd"][[0, 1]], href.invstd_f32(g["var"])[[0, 1]])
         t = ((xs[i] - g["mean"]) * (gammas[i] * g["invstd"])).astype(f32)
@@ -237,8 +194,8 @@ def test_batch_norm_relu6_is_the_headers_float32_sequence_bit_for_bit(ssd, cuda,
         hit = np.nonzero((t[:, 1] + cand).astype(f32) == f32(6))[0]
         assert hit.size
         betas[i][1] = cand[hit[0]]
-    got = _bn_act_raw(ssd, cuda, "relu6", xs, gammas, betas, mms, mvs, dys)
-    again = _bn_act_raw(ssd, cuda, "relu6", xs, gammas, betas, mms, mvs, dys)
+    got = bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, dys, act="relu6")
+    again = bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, dys, act="relu6")
     for i, g in enumerate(got):
         for name in ("mean", "var", "invstd"):
             assert same_bits(np.delete(g[name], 2), np.delete(first[i][name], 2)) and np.isnan(g[name][2])
@@ -268,8 +225,8 @@ def test_batch_norm_relu_through_the_new_entry_points_is_the_old_pair_bit_for_bi
     rows = [442, 35, 1]
     xs, gammas, betas, mms, mvs, dys = _bn_inputs(np.random.default_rng(C + 2), rows, C)
     old = bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, dys)
-    new = _bn_act_raw(ssd, cuda, "relu", xs, gammas, betas, mms, mvs, dys)
-    six = _bn_act_raw(ssd, cuda, "relu6", xs, gammas, betas, mms, mvs, dys)
+    new = bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, dys, act="relu")
+    six = bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, dys, act="relu6")
     for i in range(len(rows)):
         for name in old[i]:
             assert same_bits(old[i][name], new[i][name]), (i, name)
@@ -281,7 +238,7 @@ def test_batch_norm_relu_through_the_new_entry_points_is_the_old_pair_bit_for_bi
 def test_batch_norm_relu6_inference_form_is_the_oracles_epilogue(ssd, cuda, oracle_ops, C):
     rows = [442, 35, 1]
     xs, gammas, betas, mms, mvs, _ = _bn_inputs(np.random.default_rng(C + 3), rows, C)
-    got = _bn_act_raw(ssd, cuda, "relu6", xs, gammas, betas, mms, mvs, training=0)
+    got = bn_raw(ssd, cuda, xs, gammas, betas, mms, mvs, training=0, act="relu6")
     for i, g in enumerate(got):
         want = oracle_ops.bn_act(xs[i], gammas[i], betas[i], mms[i], mvs[i], "relu6")
         assert same_bits(g["y"], want)

@@ -3,15 +3,13 @@ and the CPU oracle bit for bit, the weight gradient exactly on integer dy and wi
 dy, its determinism, the last row and column, the refusals, TrainableMobileNet(train_first=True) in inference mode against the engine
 bit for bit and in training mode against a float64 restatement with forced gates, the closed loop through a checkpoint with no frozen
 variable, and the untouched default module."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from helpers import backbone_train_ref as bref
 from helpers import first_conv_train_ref as ref
 from helpers import head_train_ref as href
-from helpers.head_train_gpu import dev as _dev, same_bits
+from helpers.head_train_gpu import dev as _dev, same_bits, stream as _stream
 from conftest import TINY_PARAMS
 
 pytestmark = pytest.mark.gpu
@@ -23,10 +21,6 @@ WIDTHS = [8, 24, 32]
 BATCHES = [1, 3]
 LP = {"gamma": 2.0, "alpha": 0.25}
 FIRST = "MobilenetV1/Conv2d_0"
-
-
-def _stream(cuda):
-    return ctypes.c_void_p(cuda.cuda.current_stream().cuda_stream)
 
 
 def _images(rng, B, H, W):
