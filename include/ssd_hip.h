@@ -457,7 +457,7 @@ int ssd_loss_backward(const float *logits_dev, const float *codes_dev, int32_t B
  * boxes) and does all box arithmetic; this call does every per-pixel step of a batch in ONE launch, on uint8 frames, and
  * writes the float32 batch.  Per output element (y, x, c) of image b, with p = params[b]:
  *   1. source pixel    sy = p.crop_y + min(floor(y * (crop_h / out_h)), crop_h - 1), sx likewise with crop_x, crop_w, out_w: the
- *                      project's nearest-neighbour rule (the expression of front.hip front_src: floorf((float)dst * ((float)in /
+ *                      project's nearest-neighbour rule (the expression of first_pixels.h fc_src: floorf((float)dst * ((float)in /
  *                      (float)out)), the division correctly rounded), applied within the crop window
  *   2. convert         v = u8 * (float)(1.0 / 255.0)                                     (convert_image_dtype)
  *   3. colour          if SSD_AUG_COLOR: v = clip(v + color_offset[c], 0, 1)             (other_augmentations.py:16-28)

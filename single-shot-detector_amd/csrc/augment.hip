@@ -45,7 +45,7 @@ __device__ __forceinline__ float uint_to_unit(uint32_t w) { return __uint_as_flo
 
 __device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
 
-// the project's nearest-neighbour index (front.hip front_src): min(floor(dst * (in / out)), in - 1)
+// the project's nearest-neighbour index (first_pixels.h fc_src): min(floor(dst * (in / out)), in - 1)
 __device__ __forceinline__ int nn_src(int dst, float scale, int n)
 {
     const int v = (int)floorf((float)dst * scale);

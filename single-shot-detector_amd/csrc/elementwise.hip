@@ -5,15 +5,7 @@
 // wave touches whole 128-B lines.  All fused multiply-adds are explicit fmaf chains in
 // (ky,kx[,ci]) order; everything else is separately rounded (-ffp-contract=off).
 #include "ssd_internal.h"
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float act_apply(float v, int act)
-{
-    if (act >= 1) v = v > 0.0f ? v : 0.0f;
-    if (act == 2) v = v < 6.0f ? v : 6.0f;
-    return v;
-}
+#include "first_pixels.h"
 
 __device__ __forceinline__ v4f bn_act4(v4f v, const float *mean, const float *sf, const float *beta, int c, int act)
 {
@@ -31,27 +23,32 @@ __device__ __forceinline__ v4f bn_act4(v4f v, const float *mean, const float *sf
 }
 
 // ---------------------------------------------------------------------------------------
-// K1: images uint8 [B,srcH,srcW,3] -> float -> nearest-neighbour resize to [nh,nw] + zero pad to
+// The first convolution: images uint8 [B,srcH,srcW,3] -> float -> nearest-neighbour resize to [nh,nw] + zero pad to
 // [H,W] (resize_keeping_aspect_ratio, pipeline.py:138-194; TF r1.12 ResizeNearestNeighbor:
 // src = min(floorf(dst * in/out), in-1)) -> /255 -> 2x-1 -> conv 3x3 stride 2 'SAME' (even H,W:
 // taps at rows 2oy..2oy+2, zero beyond the bottom/right edge) -> BN -> act, all fused: the
 // resized / padded / normalised image never exists in memory.  Pixels of the pad band are
-// 0 before normalisation, i.e. 2*0-1 = -1 after it; taps beyond [H,W] contribute 0.
-// One thread = one output pixel x 4 output channels; weights [27][Cout] staged in LDS.
-// IDENT: the resize is the identity (srcH == nh == H, srcW == nw == W): no index arithmetic.
-template <bool IDENT>
-__global__ __launch_bounds__(256, IDENT ? 4 : 2) void first_conv_kernel(const uint8_t *__restrict__ img, int B, int srcH, int srcW,
-                                                          int nh, int nw, int H, int W, float hs, float ws,
-                                                          const float *__restrict__ w, int Cout,
-                                                          const float *mean, const float *sf, const float *beta,
-                                                          int act, float *__restrict__ out)
+// 0 before normalisation, i.e. 2*0-1 = -1 after it; taps beyond [H,W] contribute 0.  What a pixel is and where it comes from
+// is first_pixels.h for every kernel below (and for front.hip's fused launches); the kernels differ in who computes what:
+//   first_conv_ident_kernel   frames of the network's size, a thread = one output pixel x 4 channels (Cout % 8 != 0)
+//   K1b first_conv_px_kernel  frames of the network's size, a lane = one output pixel, all channels (Cout % 8 == 0)
+//   K1  first_conv_kernel / K1c first_conv_mixed_kernel     resized frames of one size / one size per frame, thread = pixel x 4 channels
+//   K1d first_conv_gen_kernel / first_conv_gen_mixed_kernel the same in K1b's form
+// A launch's frames (GeomOf): frame b -> its FrameGeom (byte offset, source size, resize target, scales), from one geometry for
+// equally sized frames (fc_frame_of) or from entries first .. of the table in the kernel's arguments
+
+// One thread = one output pixel x 4 output channels; weights [27][Cout] staged in LDS.  The resize is the identity (srcH == nh
+// == H, srcW == nw == W): a filter row is fc_row_fetch's three dword loads instead of nine byte loads (the kernel was bound by
+// the rate of its 27 byte-load instructions per thread, not by HBM).
+__global__ __launch_bounds__(256, 4) void first_conv_ident_kernel(const uint8_t *__restrict__ img, int B, int H, int W, const float *__restrict__ w, int Cout,
+                                                                  const float *mean, const float *sf, const float *beta, int act, float *__restrict__ out)
 {
     extern __shared__ float wl[];   // 27*Cout
     for (int i = threadIdx.x; i < 27 * Cout; i += blockDim.x) wl[i] = w[i];
     __syncthreads();
     const int OH = H >> 1, OW = W >> 1, C4 = Cout >> 2;
     const long long total = (long long)B * OH * OW * C4;
-    const float inv255 = (float)(1.0 / 255.0);
+    const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)img, 0, (int)((long long)B * H * W * 3), 0x00020000);
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
         const int c4 = (int)(idx % C4);
@@ -61,110 +58,113 @@ __global__ __launch_bounds__(256, IDENT ? 4 : 2) void first_conv_kernel(const ui
         const int oy = (int)(pix % OH);
         const int b = (int)(pix / OH);
         v4f acc = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (IDENT) {
-            // The 3 pixels x 3 channels under one filter row are 9 contiguous bytes at byte (..*W + 2*ox)*3, i.e.
-            // 0 or 2 bytes past a dword boundary (W is even; which of the two depends on the row when W % 4 == 2): three aligned dword loads through a range-checked
-            // buffer resource and a byte alignment replace nine byte loads (the kernel was bound by the rate of
-            // its 27 byte-load instructions per thread, not by HBM).  Bytes past the image edge are masked below.
-            const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)img, 0, (int)((long long)B * H * W * 3), 0x00020000);
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                const int iy = 2 * oy + ky;
-                const bool yok = iy < H;
-                const int ad = ((b * H + (yok ? iy : 0)) * W + 2 * ox) * 3;
-                const int a0 = ad & ~3, sh = ad & 3;           // sh: byte offset of the row's first pixel inside its dword (0 or 2)
-                const unsigned w0 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 0, 0);
-                const unsigned w1 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0 + 4, 0, 0);
-                const unsigned w2 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0 + 8, 0, 0);
-                const unsigned d0 = __builtin_amdgcn_alignbyte(w1, w0, sh);
-                const unsigned d1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
-                const unsigned d2 = w2 >> (8 * sh);
-                const unsigned char px[9] = {(unsigned char)d0, (unsigned char)(d0 >> 8), (unsigned char)(d0 >> 16), (unsigned char)(d0 >> 24),
-                                             (unsigned char)d1, (unsigned char)(d1 >> 8), (unsigned char)(d1 >> 16), (unsigned char)(d1 >> 24),
-                                             (unsigned char)d2};
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const bool ok = yok && 2 * ox + kx < W;
-#pragma unroll
-                    for (int ci = 0; ci < 3; ++ci) {
-                        float x = (float)px[kx * 3 + ci] * inv255;
-                        x = 2.0f * x - 1.0f;
-                        if (!ok) x = 0.0f;
-                        const v4f wv = *(const v4f *)(wl + ((ky * 3 + kx) * 3 + ci) * Cout + c4 * 4);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[i] = fmaf(x, wv[i], acc[i]);
-                    }
-                }
-            }
-        } else {
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
-            const int iy = 2 * oy + ky;
-            int sy = iy;
-            if constexpr (!IDENT) {
-                sy = (int)floorf((float)iy * hs);
-                sy = sy < srcH - 1 ? sy : srcH - 1;
-            }
+            const bool yok = 2 * oy + ky < H;
+            const int ad = frame_row_ad<false>(b, H, W, oy, ox, ky);
+            unsigned w0, w1, w2;
+            unsigned char px[9];
+            fc_row_fetch<true>(irsrc, true, ad, w0, w1, w2);
+            fc_row_bytes(w0, w1, w2, ad & 3, px);
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
-                const int ix = 2 * ox + kx;
-                if constexpr (IDENT) {
-                    const bool ok = iy < H && ix < W;
-                    const uint8_t *p = img + (((long long)b * H + (ok ? iy : 0)) * W + (ok ? ix : 0)) * 3;
+                const bool ok = yok && 2 * ox + kx < W;        // else: beyond the image edge
 #pragma unroll
-                    for (int ci = 0; ci < 3; ++ci) {
-                        float x = (float)p[ci] * inv255;
-                        x = 2.0f * x - 1.0f;
-                        if (!ok) x = 0.0f;
-                        const v4f wv = *(const v4f *)(wl + ((ky * 3 + kx) * 3 + ci) * Cout + c4 * 4);
+                for (int ci = 0; ci < 3; ++ci) {
+                    float x = fc_pixel(px[kx * 3 + ci]);
+                    if (!ok) x = 0.0f;
+                    const v4f wv = *(const v4f *)(wl + ((ky * 3 + kx) * 3 + ci) * Cout + c4 * 4);
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[i] = fmaf(x, wv[i], acc[i]);
-                    }
-                } else {
-                    int sx = (int)floorf((float)ix * ws);
-                    sx = sx < srcW - 1 ? sx : srcW - 1;
-                    const bool inside = iy < H && ix < W;      // else: zero padding of the convolution
-                    const bool inimg = iy < nh && ix < nw;     // else (but inside): the resize's zero pad band
-                    const uint8_t *p = img + (((long long)b * srcH + (inimg ? sy : 0)) * srcW + (inimg ? sx : 0)) * 3;
-#pragma unroll
-                    for (int ci = 0; ci < 3; ++ci) {
-                        float x = inimg ? (float)p[ci] : 0.0f;
-                        x = x * inv255;
-                        x = 2.0f * x - 1.0f;
-                        if (!inside) x = 0.0f;
-                        const v4f wv = *(const v4f *)(wl + ((ky * 3 + kx) * 3 + ci) * Cout + c4 * 4);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[i] = fmaf(x, wv[i], acc[i]);
-                    }
+                    for (int i = 0; i < 4; ++i) acc[i] = fmaf(x, wv[i], acc[i]);
                 }
             }
-        }
         }
         acc = bn_act4(acc, mean, sf, beta, c4 * 4, act);
         *(v4f *)(out + idx * 4) = acc;
     }
 }
 
-// K1b: the identity-resize case (the image is already H x W: every frame of the benchmark workload) with Cout % 8 == 0.
-// K1 is bound by LDS reads -- 27 x 16 B of weights per 16 B of output, 1.5 TB/s alone -- and by its ~500 instructions
-// per 16 B.  Here one LANE = one output pixel, all channels: the 27 input values are unpacked and normalised once per
-// pixel, the weights are wave-uniform (scalar loads, an SGPR operand of the packed fmaf), channels go in chunks of 8
-// accumulators, and the finished rows leave through a per-wave LDS transpose so that a store instruction writes 1 KB of
-// consecutive bytes (the wave's 64 pixels are 64 * Cout * 4 consecutive bytes of the output).  Same (ky,kx,ci)-ordered
-// fmaf chain per output.
+// K1 / K1c: resized frames, one thread = one output pixel x 4 output channels, nine byte-wise pixel loads per thread; weights
+// [27][Cout] staged in LDS (wl).  The reference form that the option first_conv_px = 0 pins.
+template <class GeomOf>
+__device__ __forceinline__ void first_conv_body(const uint8_t *__restrict__ img, GeomOf geom_of, int B, int H, int W, const float *__restrict__ w, int Cout,
+                                                const float *mean, const float *sf, const float *beta, int act, float *__restrict__ out, float *wl)
+{
+    for (int i = threadIdx.x; i < 27 * Cout; i += blockDim.x) wl[i] = w[i];
+    __syncthreads();
+    const int OH = H >> 1, OW = W >> 1, C4 = Cout >> 2;
+    const long long total = (long long)B * OH * OW * C4;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(idx % C4);
+        long long pix = idx / C4;
+        const int ox = (int)(pix % OW);
+        pix /= OW;
+        const int oy = (int)(pix % OH);
+        const int b = (int)(pix / OH);
+        const FrameGeom g = geom_of(b);
+        const uint8_t *src = img + g.off;
+        v4f acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            const int iy = 2 * oy + ky;
+            const int sy = fc_src(iy, g.hs, g.srcH);
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int ix = 2 * ox + kx;
+                const int sx = fc_src(ix, g.ws, g.srcW);
+                const bool inside = iy < H && ix < W;          // else: zero padding of the convolution
+                const bool inimg = iy < g.nh && ix < g.nw;     // else (but inside): the resize's zero pad band
+                const uint8_t *p = src + ((long long)(inimg ? sy : 0) * g.srcW + (inimg ? sx : 0)) * 3;
+#pragma unroll
+                for (int ci = 0; ci < 3; ++ci) {
+                    float x = fc_pixel(inimg ? p[ci] : 0u);
+                    if (!inside) x = 0.0f;
+                    const v4f wv = *(const v4f *)(wl + ((ky * 3 + kx) * 3 + ci) * Cout + c4 * 4);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) acc[i] = fmaf(x, wv[i], acc[i]);
+                }
+            }
+        }
+        acc = bn_act4(acc, mean, sf, beta, c4 * 4, act);
+        *(v4f *)(out + idx * 4) = acc;
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void first_conv_kernel(const uint8_t *__restrict__ img, const FrameGeom g1, int B, int H, int W, const float *__restrict__ w,
+                                                            int Cout, const float *mean, const float *sf, const float *beta, int act, float *__restrict__ out)
+{
+    extern __shared__ float wl[];   // 27*Cout
+    first_conv_body(img, [&](int b) { return fc_frame_of(g1, b); }, B, H, W, w, Cout, mean, sf, beta, act, out, wl);
+}
+
+// (the table -- 64 x 28 bytes -- travels in the kernel's arguments: no upload, nothing to keep alive)
+__global__ __launch_bounds__(256, 2) void first_conv_mixed_kernel(const uint8_t *__restrict__ img, const MixedGeom mg, int first, int B, int H, int W,
+                                                                  const float *__restrict__ w, int Cout, const float *mean, const float *sf,
+                                                                  const float *beta, int act, float *__restrict__ out)
+{
+    extern __shared__ float wl[];   // 27*Cout
+    first_conv_body(img, [&](int b) { return mg.f[first + b]; }, B, H, W, w, Cout, mean, sf, beta, act, out, wl);
+}
+
+// K1b / K1d: one LANE = one output pixel, all channels.  The thread-per-4-channels kernels above are bound by LDS reads -- 27 x 16 B
+// of weights per 16 B of output, 1.5 TB/s alone -- and by their ~500 instructions per 16 B, and K1's 8 (6) threads of a pixel each
+// repeat the nine index computations and the 27 byte loads.  Here the 27 input values are gathered and normalised once per pixel
+// (`gather`: frame b, output row, output column -> x[27], first_pixels.h), the weights are wave-uniform (scalar loads, an SGPR operand
+// of the packed fmaf), channels go in chunks of 8 or 16 accumulators, and the finished rows leave through a per-wave LDS transpose
+// so that a store instruction writes 1 KB of consecutive bytes (the wave's 64 pixels are 64 * Cout * 4 consecutive bytes of the
+// output).  Same (ky,kx,ci)-ordered fmaf chain per output: the chain, batch norm and activation are fc_taps' text (first_pixels.h)
+// -- its text and not a call, because with the accumulators passed to a helper by reference the compiler vectorises the helper's
+// batch-norm loads on its own before inlining it, which costs these kernels 8 VGPRs and one wave per SIMD of occupancy.
 #define FC_ROWPAD 4     // floats of padding per LDS row: 16-B aligned rows whose 16-B writes of 16 consecutive lanes miss each other's banks
 // COUT: the width as a compile-time constant (scalar-load offsets become immediates), 0 = read the argument.
-template <int COUT>
-__global__ __launch_bounds__(256) void first_conv_px_kernel(const uint8_t *__restrict__ img, int B, int H, int W,
-                                                             const float *__restrict__ w, int Cout_arg,
-                                                             const float *__restrict__ mean, const float *__restrict__ sf,
-                                                             const float *__restrict__ beta, int act, float *__restrict__ out)
+template <int COUT, class Gather>
+__device__ __forceinline__ void first_conv_lane_body(Gather gather, int B, int H, int W, const float *__restrict__ w, int Cout_arg,
+                                                     const float *__restrict__ mean, const float *__restrict__ sf, const float *__restrict__ beta, int act,
+                                                     float *__restrict__ out, float *fc_tr /* [4 waves][64 pixels][Cout + FC_ROWPAD] */)
 {
-    extern __shared__ __attribute__((aligned(16))) float fc_tr[];     // [4 waves][64 pixels][Cout + FC_ROWPAD]
     const int Cout = COUT ? COUT : Cout_arg;
     const int OH = H >> 1, OW = W >> 1;
     const long long total = (long long)B * OH * OW;
-    const float inv255 = (float)(1.0 / 255.0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // 32 channels (MobileNet): rows of exactly 128 B with the 16-byte chunk c of pixel p at slot c ^ (p & 7) -- both the
     // writes (8 consecutive lanes = 8 pixels, same chunk) and the reads (a 16-lane group = chunk halves of 4 pixels) are
@@ -173,45 +173,16 @@ __global__ __launch_bounds__(256) void first_conv_px_kernel(const uint8_t *__res
     constexpr bool SWZ = COUT == 32;
     const int rowf = SWZ ? 32 : Cout + FC_ROWPAD;
     float *reg = fc_tr + (size_t)wave * 64 * rowf;
-    const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)img, 0, (int)((long long)B * H * W * 3), 0x00020000);
     const long long nwave = (long long)gridDim.x * 4;
     for (long long wbase = ((long long)blockIdx.x * 4 + wave) * 64; wbase < total; wbase += nwave * 64) {
         const long long pix = wbase + lane;
-        const bool live = pix < total;
-        const long long pp = live ? pix : total - 1;
+        const long long pp = pix < total ? pix : total - 1;
         const int ox = (int)(pp % OW);
         const long long rowi = pp / OW;
         const int oy = (int)(rowi % OH);
         const int b = (int)(rowi / OH);
-        // 3 pixels x 3 channels under one filter row = 9 contiguous bytes at byte (..*W + 2*ox)*3, 0 or 2 bytes past a dword
-        // boundary (W even): three aligned dword loads and a byte alignment.  Only the taps of column 2ox+2 and of row
-        // 2oy+2 can fall outside the image (even H, W): they are masked, the others never are.
         float x[27];
-        const bool xok = 2 * ox + 2 < W;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int iy = 2 * oy + ky;
-            const bool yok = ky < 2 || iy < H;
-            const int ad = ((b * H + (yok ? iy : 0)) * W + 2 * ox) * 3;
-            const int a0 = ad & ~3, sh = ad & 3;
-            const unsigned w0 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 0, 0);
-            const unsigned w1 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0 + 4, 0, 0);
-            const unsigned w2 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0 + 8, 0, 0);
-            const unsigned d0 = __builtin_amdgcn_alignbyte(w1, w0, sh);
-            const unsigned d1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
-            const unsigned d2 = w2 >> (8 * sh);
-            const unsigned char px[9] = {(unsigned char)d0, (unsigned char)(d0 >> 8), (unsigned char)(d0 >> 16), (unsigned char)(d0 >> 24),
-                                         (unsigned char)d1, (unsigned char)(d1 >> 8), (unsigned char)(d1 >> 16), (unsigned char)(d1 >> 24),
-                                         (unsigned char)d2};
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                float v = (float)px[k] * inv255;
-                v = 2.0f * v - 1.0f;
-                if (ky == 2 && !yok) v = 0.0f;
-                if (k >= 6 && !xok) v = 0.0f;
-                x[ky * 9 + k] = v;
-            }
-        }
+        gather(b, oy, ox, x);
         constexpr int CH = (COUT && COUT % 16 == 0) ? 16 : 8;       // accumulators per pass over the 27 taps
 #pragma unroll 1
         for (int ch = 0; ch < Cout; ch += CH) {         // wave-uniform (not unrolled: 864 weights do not fit the SGPRs)
@@ -251,122 +222,33 @@ __global__ __launch_bounds__(256) void first_conv_px_kernel(const uint8_t *__res
     }
 }
 
-// K1d (round 6): K1 / K1c -- the resize fused into the first convolution, frames of ANY size, one size per batch or one per
-// frame -- in K1b's form.  K1 gives 4 output channels of one pixel to a thread: the 8 (6) threads of a pixel each repeat the nine
-// index computations and the 27 byte loads, and the weights come from LDS per 16 B of output -- 0.99 ms per 32 frames of 480 x 640
-// against 0.17 ms for K1b on frames that need no resize, i.e. every COCO image paid 2.6 % of a 32-frame step for not being
-// 640 x 896 already.  Here one LANE = one output pixel, all channels: three source rows and three source columns per lane (the
-// index rule of K1, value for value: floorf((float)dst * scale), clamped to the last row / column), each of the nine source
-// pixels as two aligned dwords through a range-checked buffer resource + a byte alignment (a pixel's 3 bytes start at any byte),
-// then K1b's wave-uniform weights, chunks of accumulators and LDS transpose.  The same (ky,kx,ci)-ordered fmaf chain per output,
-// the same separately rounded normalisation: bit-identical to K1 / K1c (tests/test_gpu_multishape.py pins both kernels on every size).
-// GeomOf: frame b of the launch -> its FrameGeom (byte offset, source size, resize target, scales).
-template <int COUT, class GeomOf>
-__device__ __forceinline__ void first_conv_gen_body(const uint8_t *__restrict__ img, unsigned img_bytes4, GeomOf geom_of, int B, int H, int W,
-                                                    const float *__restrict__ w, int Cout_arg, const float *__restrict__ mean,
-                                                    const float *__restrict__ sf, const float *__restrict__ beta, int act, float *__restrict__ out,
-                                                    float *fc_tr)
+// K1b: the identity-resize case (the image is already H x W: every frame of the benchmark workload) with Cout % 8 == 0
+template <int COUT>
+__global__ __launch_bounds__(256) void first_conv_px_kernel(const uint8_t *__restrict__ img, int B, int H, int W,
+                                                             const float *__restrict__ w, int Cout_arg,
+                                                             const float *__restrict__ mean, const float *__restrict__ sf,
+                                                             const float *__restrict__ beta, int act, float *__restrict__ out)
 {
-    const int Cout = COUT ? COUT : Cout_arg;
-    const int OH = H >> 1, OW = W >> 1;
-    const long long total = (long long)B * OH * OW;
-    const float inv255 = (float)(1.0 / 255.0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr bool SWZ = COUT == 32;
-    const int rowf = SWZ ? 32 : Cout + FC_ROWPAD;
-    float *reg = fc_tr + (size_t)wave * 64 * rowf;
-    const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)img, 0, (int)img_bytes4, 0x00020000);
-    const long long nwave = (long long)gridDim.x * 4;
-    for (long long wbase = ((long long)blockIdx.x * 4 + wave) * 64; wbase < total; wbase += nwave * 64) {
-        const long long pix = wbase + lane;
-        const long long pp = pix < total ? pix : total - 1;
-        const int ox = (int)(pp % OW);
-        const long long rowi = pp / OW;
-        const int oy = (int)(rowi % OH);
-        const int b = (int)(rowi / OH);
-        const FrameGeom g = geom_of(b);
-        int roff[3], coff[3];
-        bool yin[3], xin[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int iy = 2 * oy + k, ix = 2 * ox + k;
-            int sy = (int)floorf((float)iy * g.hs), sx = (int)floorf((float)ix * g.ws);
-            sy = sy < g.srcH - 1 ? sy : g.srcH - 1;
-            sx = sx < g.srcW - 1 ? sx : g.srcW - 1;
-            yin[k] = iy < g.nh;                          // else: the resize's zero pad band (or beyond the padded frame)
-            xin[k] = ix < g.nw;
-            roff[k] = (yin[k] ? sy : 0) * g.srcW;
-            coff[k] = xin[k] ? sx : 0;
-        }
-        float x[27];
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const bool yok = ky < 2 || 2 * oy + 2 < H;  // else: the convolution's zero padding ('SAME' on even sizes pads bottom / right only)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const bool xok = kx < 2 || 2 * ox + 2 < W;
-                const unsigned p = g.off + (unsigned)(roff[ky] + coff[kx]) * 3u;
-                const int a0 = (int)(p & ~3u), sh = (int)(p & 3u);
-                const unsigned w0 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 0, 0);
-                const unsigned w1 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 4, 0);
-                const unsigned d = __builtin_amdgcn_alignbyte(w1, w0, sh);
-                const bool inimg = yin[ky] && xin[kx];
-#pragma unroll
-                for (int ci = 0; ci < 3; ++ci) {
-                    float v = inimg ? (float)((d >> (8 * ci)) & 0xffu) : 0.0f;
-                    v = v * inv255;
-                    v = 2.0f * v - 1.0f;
-                    if (!(yok && xok)) v = 0.0f;
-                    x[(ky * 3 + kx) * 3 + ci] = v;
-                }
-            }
-        }
-        constexpr int CH = (COUT && COUT % 16 == 0) ? 16 : 8;
-#pragma unroll 1
-        for (int ch = 0; ch < Cout; ch += CH) {
-            float acc[CH];
-#pragma unroll
-            for (int i = 0; i < CH; ++i) acc[i] = 0.0f;
-#pragma unroll
-            for (int t = 0; t < 27; ++t) {
-                const float *wr = w + t * Cout + ch;
-#pragma unroll
-                for (int i = 0; i < CH; ++i) acc[i] = fmaf(x[t], wr[i], acc[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                if (mean) {
-                    const float tq = (acc[i] - mean[ch + i]) * sf[ch + i];
-                    acc[i] = tq + beta[ch + i];
-                }
-                acc[i] = act_apply(acc[i], act);
-            }
-#pragma unroll
-            for (int i = 0; i < CH; i += 4) {
-                const int c = SWZ ? ((((ch + i) >> 2) ^ (lane & 7)) << 2) : ch + i;
-                *(v4f *)(reg + lane * rowf + c) = (v4f){acc[i], acc[i + 1], acc[i + 2], acc[i + 3]};
-            }
-        }
-        const int LP = Cout >> 2;
-        const long long nlive = (total - wbase < 64 ? total - wbase : 64) * LP;
-        float *obase = out + wbase * Cout;
-        for (int q = lane; q < 64 * LP; q += 64) {
-            const int p = q / LP, c4 = q - p * LP;
-            const v4f v = *(const v4f *)(reg + p * rowf + (SWZ ? ((c4 ^ (p & 7)) << 2) : c4 * 4));
-            if (q < nlive) *(v4f *)(obase + (long long)q * 4) = v;
-        }
-    }
+    extern __shared__ __attribute__((aligned(16))) float fc_tr[];
+    const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)img, 0, (int)((long long)B * H * W * 3), 0x00020000);
+    first_conv_lane_body<COUT>([&](int b, int oy, int ox, float (&x)[27]) { frame_gather(irsrc, b, H, W, oy, ox, x); }, B, H, W, w, Cout_arg, mean, sf, beta,
+                               act, out, fc_tr);
 }
 
+// K1d (round 6): K1 / K1c -- the resize fused into the first convolution, frames of ANY size, one size per batch or one per
+// frame -- in K1b's form: 0.99 ms per 32 frames of 480 x 640 for K1 against 0.17 ms for K1b on frames that need no resize, i.e.
+// every COCO image paid 2.6 % of a 32-frame step for not being 640 x 896 already.  frame_gather_any's three source rows and three
+// source columns per lane, on fc_src, the index rule K1 uses: bit-identical to K1 / K1c (tests/test_gpu_multishape.py pins both
+// kernels on every size).
 template <int COUT>
 __global__ __launch_bounds__(256) void first_conv_gen_kernel(const uint8_t *__restrict__ img, unsigned img_bytes4, const FrameGeom g1, int B, int H, int W,
                                                               const float *__restrict__ w, int Cout_arg, const float *__restrict__ mean,
                                                               const float *__restrict__ sf, const float *__restrict__ beta, int act, float *__restrict__ out)
 {
     extern __shared__ __attribute__((aligned(16))) float fc_tr[];
-    const unsigned frame = (unsigned)g1.srcH * (unsigned)g1.srcW * 3u;
-    first_conv_gen_body<COUT>(img, img_bytes4, [&](int b) { FrameGeom g = g1; g.off = g1.off + (unsigned)b * frame; return g; }, B, H, W, w, Cout_arg,
-                              mean, sf, beta, act, out, fc_tr);
+    const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)img, 0, (int)img_bytes4, 0x00020000);
+    first_conv_lane_body<COUT>([&](int b, int oy, int ox, float (&x)[27]) { frame_gather_any(irsrc, fc_frame_of(g1, b), H, W, oy, ox, x); }, B, H, W, w,
+                               Cout_arg, mean, sf, beta, act, out, fc_tr);
 }
 
 template <int COUT>
@@ -376,7 +258,16 @@ __global__ __launch_bounds__(256) void first_conv_gen_mixed_kernel(const uint8_t
                                                                     const float *__restrict__ beta, int act, float *__restrict__ out)
 {
     extern __shared__ __attribute__((aligned(16))) float fc_tr[];
-    first_conv_gen_body<COUT>(img, img_bytes4, [&](int b) { return mg.f[first + b]; }, B, H, W, w, Cout_arg, mean, sf, beta, act, out, fc_tr);
+    const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)img, 0, (int)img_bytes4, 0x00020000);
+    first_conv_lane_body<COUT>([&](int b, int oy, int ox, float (&x)[27]) { frame_gather_any(irsrc, mg.f[first + b], H, W, oy, ox, x); }, B, H, W, w,
+                               Cout_arg, mean, sf, beta, act, out, fc_tr);
+}
+
+// one thread per item in blocks of 256, grid-stride beyond 8192 blocks
+static unsigned grid256(long long n)
+{
+    const long long blocks = (n + 255) / 256;
+    return (unsigned)(blocks < 256 * 32 ? blocks : 256 * 32);
 }
 
 // K1d's launch: false when this width has no instantiation (then K1 / K1c run).  The first layer's physical width is the logical
@@ -386,80 +277,18 @@ static bool launch_first_conv_gen(const uint8_t *img, unsigned long long img_byt
                                   const float *w, int Cout, const float *mean, const float *sf, const float *beta, int act, float *out, hipStream_t s)
 {
     if (Cout != 32 || img_bytes + 6 >= (1ull << 31)) return false;
-    // The kernel's dword loads are aligned RELATIVE TO ITS BASE: a base that is not a multiple of 4 itself (the second chain's or
-    // sub-batch's first frame when a frame's byte size is odd, a caller's slice) is rounded down and the remainder added to every
-    // frame's byte offset, so that no load depends on the device's unaligned-access mode.
-    const unsigned adj = (unsigned)((uintptr_t)img & 3u);
-    img -= adj;
     const size_t lds = (size_t)256 * 32 * sizeof(float);
-    const unsigned bytes4 = (unsigned)((img_bytes + adj + 3) & ~3ull);      // (a pixel's second dword may reach <= 3 bytes past a size that is no multiple of 4: the same word)
-    const long long px = (long long)B * (H / 2) * (W / 2);
-    long long blocks = (px + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    const dim3 grid((unsigned)blocks), blk(256);
+    const dim3 grid(grid256((long long)B * (H / 2) * (W / 2))), blk(256);
     if (one) {
         FrameGeom g = *one;
-        g.off += adj;
+        const unsigned bytes4 = frame_base_align(img, img_bytes, g);
         hipLaunchKernelGGL(first_conv_gen_kernel<32>, grid, blk, lds, s, img, bytes4, g, B, H, W, w, Cout, mean, sf, beta, act, out);
     } else {
         MixedGeom t = *mg;
-        for (int b = first; b < first + B; ++b) t.f[b].off += adj;
+        const unsigned bytes4 = frame_base_align(img, img_bytes, t, first, B);
         hipLaunchKernelGGL(first_conv_gen_mixed_kernel<32>, grid, blk, lds, s, img, bytes4, t, first, B, H, W, w, Cout, mean, sf, beta, act, out);
     }
     return true;
-}
-
-// K1c: K1 (the general, non-identity form) for a batch whose frames have DIFFERENT source sizes and resize to the same [H,W]:
-// frame b reads its geometry from the argument table.  The arithmetic per output is K1's, value for value: the same index rule
-// (floorf((float)dst * scale), clamped), the same (ky,kx,ci)-ordered fmaf chain.
-__global__ __launch_bounds__(256, 2) void first_conv_mixed_kernel(const uint8_t *__restrict__ img, const MixedGeom mg, int first, int B, int H, int W,
-                                                                  const float *__restrict__ w, int Cout, const float *mean, const float *sf,
-                                                                  const float *beta, int act, float *__restrict__ out)
-{
-    extern __shared__ float wl[];   // 27*Cout
-    for (int i = threadIdx.x; i < 27 * Cout; i += blockDim.x) wl[i] = w[i];
-    __syncthreads();
-    const int OH = H >> 1, OW = W >> 1, C4 = Cout >> 2;
-    const long long total = (long long)B * OH * OW * C4;
-    const float inv255 = (float)(1.0 / 255.0);
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(idx % C4);
-        long long pix = idx / C4;
-        const int ox = (int)(pix % OW);
-        pix /= OW;
-        const int oy = (int)(pix % OH);
-        const int b = (int)(pix / OH);
-        const FrameGeom g = mg.f[first + b];
-        const uint8_t *src = img + g.off;
-        v4f acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int iy = 2 * oy + ky;
-            int sy = (int)floorf((float)iy * g.hs);
-            sy = sy < g.srcH - 1 ? sy : g.srcH - 1;
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int ix = 2 * ox + kx;
-                int sx = (int)floorf((float)ix * g.ws);
-                sx = sx < g.srcW - 1 ? sx : g.srcW - 1;
-                const bool inside = iy < H && ix < W;          // else: zero padding of the convolution
-                const bool inimg = iy < g.nh && ix < g.nw;     // else (but inside): the resize's zero pad band
-                const uint8_t *p = src + ((long long)(inimg ? sy : 0) * g.srcW + (inimg ? sx : 0)) * 3;
-#pragma unroll
-                for (int ci = 0; ci < 3; ++ci) {
-                    float x = inimg ? (float)p[ci] : 0.0f;
-                    x = x * inv255;
-                    x = 2.0f * x - 1.0f;
-                    if (!inside) x = 0.0f;
-                    const v4f wv = *(const v4f *)(wl + ((ky * 3 + kx) * 3 + ci) * Cout + c4 * 4);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[i] = fmaf(x, wv[i], acc[i]);
-                }
-            }
-        }
-        acc = bn_act4(acc, mean, sf, beta, c4 * 4, act);
-        *(v4f *)(out + idx * 4) = acc;
-    }
 }
 
 hipError_t launch_first_conv_mixed(const uint8_t *img, const MixedGeom &mg, int first, int B, int H, int W, const float *w, int Cout,
@@ -474,11 +303,8 @@ hipError_t launch_first_conv_mixed(const uint8_t *img, const MixedGeom &mg, int 
         end = std::max(end, (unsigned long long)g.off + (unsigned long long)g.srcH * g.srcW * 3);
     }
     if (variant != 1 && launch_first_conv_gen(img, end, nullptr, &mg, first, B, H, W, w, Cout, mean, sf, beta, act, out, s)) return hipGetLastError();
-    const long long total = (long long)B * (H / 2) * (W / 2) * (Cout / 4);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(first_conv_mixed_kernel, dim3((unsigned)blocks), dim3(256), 27 * Cout * sizeof(float), s, img, mg, first, B, H, W, w, Cout,
-                       mean, sf, beta, act, out);
+    hipLaunchKernelGGL(first_conv_mixed_kernel, dim3(grid256((long long)B * (H / 2) * (W / 2) * (Cout / 4))), dim3(256), 27 * Cout * sizeof(float), s, img, mg,
+                       first, B, H, W, w, Cout, mean, sf, beta, act, out);
     return hipGetLastError();
 }
 
@@ -489,19 +315,16 @@ hipError_t launch_first_conv(const uint8_t *img, int B, int srcH, int srcW, int 
     if ((long long)B * srcH * srcW * 3 >= (1LL << 31)) return hipErrorInvalidValue;      // 32-bit byte offsets into the image
     if (Cout % 4 || (H & 1) || (W & 1) || 27 * Cout * 4 > 65536 || nh < 1 || nw < 1 || nh > H || nw > W || srcH < 1 || srcW < 1)
         return hipErrorInvalidValue;
-    const float hs = (float)srcH / (float)nh, ws = (float)srcW / (float)nw;
-    const long long total = (long long)B * (H / 2) * (W / 2) * (Cout / 4);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (srcH == nh && nh == H && srcW == nw && nw == W && Cout % 8 == 0 && Cout <= 128) {
-        const long long px = (long long)B * (H / 2) * (W / 2);
-        blocks = (px + 255) / 256;
-        if (blocks > 256 * 32) blocks = 256 * 32;
+    const long long px = (long long)B * (H / 2) * (W / 2);
+    const dim3 grid4(grid256(px * (Cout / 4))), blk(256);         // a thread = a pixel x 4 channels
+    const bool ident = srcH == nh && nh == H && srcW == nw && nw == W;
+    if (ident && Cout % 8 == 0 && Cout <= 128) {
+        const dim3 grid(grid256(px));
         const size_t lds = (size_t)256 * (Cout == 32 ? 32 : Cout + FC_ROWPAD) * sizeof(float);
         if (Cout == 32)        // MobileNet-v1 at depth multiplier 1
-            hipLaunchKernelGGL(first_conv_px_kernel<32>, dim3((unsigned)blocks), dim3(256), lds, s, img, B, H, W, w, Cout, mean, sf, beta, act, out);
+            hipLaunchKernelGGL(first_conv_px_kernel<32>, grid, blk, lds, s, img, B, H, W, w, Cout, mean, sf, beta, act, out);
         else if (Cout == 24)   // ShuffleNet-v2
-            hipLaunchKernelGGL(first_conv_px_kernel<24>, dim3((unsigned)blocks), dim3(256), lds, s, img, B, H, W, w, Cout, mean, sf, beta, act, out);
+            hipLaunchKernelGGL(first_conv_px_kernel<24>, grid, blk, lds, s, img, B, H, W, w, Cout, mean, sf, beta, act, out);
         else {
             // wider first layers (depth multiplier 2: 64 channels = 68 KB, up to 128 = 135 KB): above the 64 KB a kernel gets
             // without asking, so ask -- per device
@@ -510,17 +333,15 @@ hipError_t launch_first_conv(const uint8_t *img, int B, int srcH, int srcW, int 
                 hipError_t e = ssd_allow_lds((const void *)first_conv_px_kernel<0>, (int)lds, attr_done);
                 if (e != hipSuccess) return e;
             }
-            hipLaunchKernelGGL(first_conv_px_kernel<0>, dim3((unsigned)blocks), dim3(256), lds, s, img, B, H, W, w, Cout, mean, sf, beta, act, out);
+            hipLaunchKernelGGL(first_conv_px_kernel<0>, grid, blk, lds, s, img, B, H, W, w, Cout, mean, sf, beta, act, out);
         }
-    } else if (srcH == nh && nh == H && srcW == nw && nw == W)
-        hipLaunchKernelGGL(first_conv_kernel<true>, dim3((unsigned)blocks), dim3(256), 27 * Cout * sizeof(float), s, img, B,
-                           srcH, srcW, nh, nw, H, W, hs, ws, w, Cout, mean, sf, beta, act, out);
+    } else if (ident)
+        hipLaunchKernelGGL(first_conv_ident_kernel, grid4, blk, 27 * Cout * sizeof(float), s, img, B, H, W, w, Cout, mean, sf, beta, act, out);
     else {
-        const FrameGeom g1 = {0u, srcH, srcW, nh, nw, hs, ws};
+        const FrameGeom g1 = frame_geom(srcH, srcW, nh, nw);
         // K1d (one lane per output pixel) where the width has an instantiation; variant 1 pins K1 (tests, A/B)
         if (variant == 1 || !launch_first_conv_gen(img, (unsigned long long)B * srcH * srcW * 3, &g1, nullptr, 0, B, H, W, w, Cout, mean, sf, beta, act, out, s))
-            hipLaunchKernelGGL(first_conv_kernel<false>, dim3((unsigned)blocks), dim3(256), 27 * Cout * sizeof(float), s, img, B,
-                               srcH, srcW, nh, nw, H, W, hs, ws, w, Cout, mean, sf, beta, act, out);
+            hipLaunchKernelGGL(first_conv_kernel, grid4, blk, 27 * Cout * sizeof(float), s, img, g1, B, H, W, w, Cout, mean, sf, beta, act, out);
     }
     return hipGetLastError();
 }
@@ -687,9 +508,8 @@ hipError_t launch_maxpool(const float *in, int B, int H, int W, int C, float *ou
 {
     if (C % 4 || (H & 1) || (W & 1)) return hipErrorInvalidValue;
     const long long total = (long long)B * (H / 2) * (W / 2) * (C / 4);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, B, H, W, C, out);
+    const unsigned blocks = grid256(total);
+    hipLaunchKernelGGL(maxpool_kernel, dim3(blocks), dim3(256), 0, s, in, B, H, W, C, out);
     return hipGetLastError();
 }
 
@@ -729,9 +549,8 @@ hipError_t launch_fpn_merge(const float *x5, const float *l4, float *x4, float *
 {
     if (C % 4 || (H3 & 3) || (W3 & 3) || B < 1) return hipErrorInvalidValue;
     const long long total = (long long)B * H3 * W3 * (C / 4);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(fpn_merge_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x5, l4, x4, x3, B, H3, W3, C);
+    const unsigned blocks = grid256(total);
+    hipLaunchKernelGGL(fpn_merge_kernel, dim3(blocks), dim3(256), 0, s, x5, l4, x4, x3, B, H3, W3, C);
     return hipGetLastError();
 }
 
@@ -763,10 +582,8 @@ hipError_t launch_gather_channels(const float *x, int xs, const float *y, int ys
                                   int Cout, float *out, hipStream_t s)
 {
     const long long total = rows * Cout;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, xs, y, ys, rows, tab, Cout, out);
+    const unsigned blocks = std::max(grid256(total), 1u);
+    hipLaunchKernelGGL(gather_kernel, dim3(blocks), dim3(256), 0, s, x, xs, y, ys, rows, tab, Cout, out);
     return hipGetLastError();
 }
 
@@ -844,9 +661,7 @@ hipError_t launch_permute_channels(const float *in, long long rows, int C, int C
 {
     if (split && to_phys != 0) return hipErrorInvalidValue;
     const long long total = rows * ((to_phys & 1) ? Cpad : C);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(permute_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, rows, C, Cpad, to_phys, out, split);
+    const unsigned blocks = std::max(grid256(total), 1u);
+    hipLaunchKernelGGL(permute_kernel, dim3(blocks), dim3(256), 0, s, in, rows, C, Cpad, to_phys, out, split);
     return hipGetLastError();
 }

@@ -7,9 +7,9 @@
 // it in LDS.  One launch less per forward, 36.6 MB less traffic per frame.
 //
 //   tile        12 x 16 output positions of one image x all 64 output channels; a block walks tiles b, b + G, ...
-//   phase 1     first convolution: one LANE = one patch position, all 32 channels (the arithmetic of first_conv_px_kernel,
-//               elementwise.hip: 27 inputs unpacked and normalised once, wave-uniform weights from scalar loads, the
-//               (ky,kx,ci)-ordered fmaf chain, batch norm in three separately rounded steps, activation); positions outside
+//   phase 1     first convolution: one LANE = one patch position, all 32 channels (first_pixels.h, as K1b of elementwise.hip:
+//               frame_unpack's 27 inputs unpacked and normalised once, fc_taps' wave-uniform weights from scalar loads,
+//               (ky,kx,ci)-ordered fmaf chain, batch norm in three separately rounded steps and activation); positions outside
 //               the layer's output are the depthwise layer's zero padding.  The frame bytes of the NEXT tile are fetched
 //               here and used one tile later.
 //   phase 2     depthwise 3x3: a thread = 4 channels x one column x 6 rows (8 patch rows x 3 columns read once); the
@@ -21,9 +21,9 @@
 //               of one position), as dwpw_stream.hip's dense epilogue
 // Bit-identical to first_conv_px_kernel -> dwpw_stream_kernel (and so to the three-kernel chain and the oracle).
 #include "ssd_internal.h"
+#include "first_pixels.h"
 
 typedef float v16f __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -32,140 +32,19 @@ constexpr int OFF_A = NSLOT * 128, OFF_P = OFF_A + TY * TX * 128, LDS_BYTES = OF
 static_assert(NSLOT <= 256 && LDS_BYTES <= 64 * 1024, "one lane per patch position, two blocks per CU");
 }
 
-// The frame bytes under the 3x3 stride-2 window of first-convolution output (cy, cx) of image b (coordinates inside the layer's
-// output): three filter rows of 9 contiguous bytes at byte ((b H + 2 cy + ky) W + 2 cx) 3, each fetched as three aligned
-// dwords -- the addressing of first_conv_px_kernel (elementwise.hip).  Row 2 cy + 2 may lie below the frame (even H): it is
-// fetched from row 0 and masked in frame_unpack.
-static __device__ __forceinline__ void frame_fetch(const __amdgpu_buffer_rsrc_t irsrc, bool live, int b, int H, int W, int cy, int cx,
-                                                   unsigned (&raw)[9])
-{
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-        const int iy = 2 * cy + ky;
-        const int ad = ((b * H + (iy < H ? iy : 0)) * W + 2 * cx) * 3;
-        const int a0 = live ? (ad & ~3) : (int)0x80000000u;
-        raw[ky * 3 + 0] = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 0, 0);
-        raw[ky * 3 + 1] = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 4, 0);
-        raw[ky * 3 + 2] = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 8, 0);
-    }
-}
-
-// ... -> the 27 normalised inputs x / 255 -> 2 x - 1 in (ky, kx, ci) order; taps below / right of the frame ('SAME' on even
-// sizes pads there only) are 0.  The arithmetic of first_conv_px_kernel, value for value.
-static __device__ __forceinline__ void frame_unpack(const unsigned (&raw)[9], int b, int H, int W, int cy, int cx, float (&x)[27])
-{
-    const float inv255 = (float)(1.0 / 255.0);
-    const bool xok = 2 * cx + 2 < W;
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-        const int iy = 2 * cy + ky;
-        const bool yok = ky < 2 || iy < H;
-        const int ad = ((b * H + (iy < H ? iy : 0)) * W + 2 * cx) * 3;
-        const int sh = ad & 3;
-        const unsigned w0 = raw[ky * 3], w1 = raw[ky * 3 + 1], w2 = raw[ky * 3 + 2];
-        const unsigned d0 = __builtin_amdgcn_alignbyte(w1, w0, sh);
-        const unsigned d1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
-        const unsigned d2 = w2 >> (8 * sh);
-        const unsigned char px[9] = {(unsigned char)d0, (unsigned char)(d0 >> 8), (unsigned char)(d0 >> 16), (unsigned char)(d0 >> 24),
-                                     (unsigned char)d1, (unsigned char)(d1 >> 8), (unsigned char)(d1 >> 16), (unsigned char)(d1 >> 24),
-                                     (unsigned char)d2};
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            float v = (float)px[k] * inv255;
-            v = 2.0f * v - 1.0f;
-            if (ky == 2 && !yok) v = 0.0f;
-            if (k >= 6 && !xok) v = 0.0f;
-            x[ky * 9 + k] = v;
-        }
-    }
-}
-
-// Round 6: the same for a RESIZED frame (resize_keeping_aspect_ratio fused, pipeline.py:138-194 -- the index rule of
-// elementwise.hip K1 / K1d, value for value) whose width is not reduced (srcW <= nw, i.e. every COCO image at min_dimension 640):
-// the three taps of a filter row then read source columns sx(2 cx), sx(2 cx + 1), sx(2 cx + 2) that lie at most two pixels apart,
-// so a filter row is still 9 contiguous source bytes from the first tap's pixel -- three aligned dwords, like the frame of the
-// network's own size -- and tap kx takes the pixel sx(2 cx + kx) - sx(2 cx) in {0, 1, 2} of them.  Rows are three independent
-// source rows (any vertical scale).  Beyond the resize's target (the zero pad band) a tap is 0 before the normalisation, beyond
-// the padded frame 0 after it.
-struct FrontGeom { int srcH, srcW, nh, nw; float hs, ws; unsigned off0; };      // off0: byte offset of frame 0 from the (4-byte aligned) base
-// MODE of the two kernels below: 0 = frames of the network's size, 1 = resized frames of ONE size (FrontGeom; frame b starts at byte
-// b * srcH * srcW * 3), 2 = a batch of frames of DIFFERENT sizes (ssd_forward_mixed): frame b's geometry and byte offset are entry
-// first + b of the table in the kernel's arguments -- a tile belongs to one frame, so the entry is read with scalar loads
+// MODE of the two kernels below: 0 = frames of the network's size (first_pixels.h frame_fetch / frame_unpack), else resized frames
+// whose width does not shrink (frame_fetch_gen / frame_unpack_gen): 1 = of ONE size (the FrameGeom of frame 0; frame b starts
+// srcH * srcW * 3 bytes further, fc_frame_of), 2 = a batch of frames of DIFFERENT sizes (ssd_forward_mixed): frame b's geometry and
+// byte offset are entry first + b of the table in the kernel's arguments -- a tile belongs to one frame, so the entry is read with
+// scalar loads
 struct FrontMixed { MixedGeom mg; int first; unsigned bytes4; };
-template <int MODE> struct FrontGeomArg { typedef FrontGeom type; };
+template <int MODE> struct FrontGeomArg { typedef FrameGeom type; };
 template <> struct FrontGeomArg<2> { typedef FrontMixed type; };
 template <int MODE>
-static __device__ __forceinline__ void front_geom_of(const typename FrontGeomArg<MODE>::type &ga, int b, FrontGeom &g, unsigned &base)
+static __device__ __forceinline__ FrameGeom front_geom_of(const typename FrontGeomArg<MODE>::type &ga, int b)
 {
-    if constexpr (MODE == 2) {
-        const FrameGeom f = ga.mg.f[ga.first + b];
-        g.srcH = f.srcH; g.srcW = f.srcW; g.nh = f.nh; g.nw = f.nw; g.hs = f.hs; g.ws = f.ws;
-        base = f.off;
-    } else {
-        g = ga;
-        base = ga.off0 + (unsigned)b * (unsigned)ga.srcH * (unsigned)ga.srcW * 3u;
-    }
-}
-
-static __device__ __forceinline__ int front_src(int dst, float scale, int n)
-{
-    const int v = (int)floorf((float)dst * scale);
-    return v < n - 1 ? v : n - 1;
-}
-
-static __device__ __forceinline__ void frame_fetch_gen(const __amdgpu_buffer_rsrc_t irsrc, bool live, unsigned base, const FrontGeom &g, int cy, int cx,
-                                                       unsigned (&raw)[9])
-{
-    const int sx0 = front_src(2 * cx, g.ws, g.srcW);
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-        const int sy = front_src(2 * cy + ky, g.hs, g.srcH);
-        const int ad = (int)(base + (unsigned)(sy * g.srcW + sx0) * 3u);
-        const int a0 = live ? (ad & ~3) : (int)0x80000000u;
-        raw[ky * 3 + 0] = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 0, 0);
-        raw[ky * 3 + 1] = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 4, 0);
-        raw[ky * 3 + 2] = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 8, 0);
-    }
-}
-
-static __device__ __forceinline__ void frame_unpack_gen(const unsigned (&raw)[9], unsigned base, int H, int W, const FrontGeom &g, int cy, int cx, float (&x)[27])
-{
-    const float inv255 = (float)(1.0 / 255.0);
-    const int sx0 = front_src(2 * cx, g.ws, g.srcW);
-    int off[3];
-    bool xin[3];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-        off[kx] = 3 * (front_src(2 * cx + kx, g.ws, g.srcW) - sx0);      // 0, 3 or 6
-        xin[kx] = 2 * cx + kx < g.nw;
-    }
-    const bool xok = 2 * cx + 2 < W;
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-        const int iy = 2 * cy + ky;
-        const bool yok = ky < 2 || iy < H;
-        const bool yin = iy < g.nh;
-        const int sy = front_src(iy, g.hs, g.srcH);
-        const int sh = (int)((base + (unsigned)(sy * g.srcW + sx0) * 3u) & 3u);
-        const unsigned w0 = raw[ky * 3], w1 = raw[ky * 3 + 1], w2 = raw[ky * 3 + 2];
-        const unsigned d0 = __builtin_amdgcn_alignbyte(w1, w0, sh);      // source bytes 0..3 of the row's span
-        const unsigned d1 = __builtin_amdgcn_alignbyte(w2, w1, sh);      // 4..7
-        const unsigned d2 = w2 >> (8 * sh);                              // 8..
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const unsigned lo = off[kx] < 4 ? d0 : d1, hi = off[kx] < 4 ? d1 : d2;
-            const unsigned px = __builtin_amdgcn_alignbyte(hi, lo, off[kx] & 3);
-            const bool inimg = yin && xin[kx];
-#pragma unroll
-            for (int ci = 0; ci < 3; ++ci) {
-                float v = inimg ? (float)((px >> (8 * ci)) & 0xffu) : 0.0f;
-                v = v * inv255;
-                v = 2.0f * v - 1.0f;
-                if (!yok || (kx == 2 && !xok)) v = 0.0f;
-                x[ky * 9 + kx * 3 + ci] = v;
-            }
-        }
-    }
+    if constexpr (MODE == 2) return ga.mg.f[ga.first + b];
+    else return fc_frame_of(ga, b);
 }
 
 // (the read-only operands as `const __restrict__` kernel parameters: with them inside the by-value struct the compiler cannot
@@ -188,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void front_kernel(const uint8_t *__restrict
     // (GEN: the size rounded up to whole dwords -- a row's third dword may reach <= 3 bytes past a size that is no multiple of 4)
     int ibytes;
     if constexpr (MODE == 2) ibytes = (int)gg.bytes4;
-    else if constexpr (MODE == 1) ibytes = (int)((((long long)a.B * gg.srcH * gg.srcW * 3) + gg.off0 + 3) & ~3LL);
+    else if constexpr (MODE == 1) ibytes = (int)((((long long)a.B * gg.srcH * gg.srcW * 3) + gg.off + 3) & ~3LL);
     else ibytes = (int)((long long)a.B * H * W * 3);
     const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a_img, 0, ibytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a_out, 0, (int)((long long)a.B * OH * OW * 64 * 4), 0x00020000);
@@ -224,21 +103,16 @@ __global__ __launch_bounds__(256, 2) void front_kernel(const uint8_t *__restrict
     const bool dact_on = a.dact >= 1, pact_on = a.act >= 1;
     const float dact_hi = a.dact == 2 ? 6.0f : __builtin_inff(), pact_hi = a.act == 2 ? 6.0f : __builtin_inff();
 
-    // the frame bytes under this lane's patch position of tile `t`: three filter rows of 9 contiguous bytes, each as three
-    // aligned dwords (the arithmetic of first_conv_px_kernel); positions outside the layer's output are fetched clamped
-    // and zeroed after the activation
+    // the frame bytes under this lane's patch position of tile `t` (frame_fetch / frame_fetch_gen); positions outside the layer's
+    // output are fetched clamped and zeroed after the activation
     unsigned raw[9];
     auto fetch = [&](int t) {
         const int b = t / tiles_img, r = t - b * tiles_img, ty = r / a.tiles_x, tx = r - ty * a.tiles_x;
         int fy = ty * TY - 1 + ppy, fx = tx * TX - 1 + ppx;
         fy = fy < 0 ? 0 : (fy >= OH ? OH - 1 : fy);
         fx = fx < 0 ? 0 : (fx >= OW ? OW - 1 : fx);
-        if constexpr (GEN) {
-            FrontGeom g;
-            unsigned base;
-            front_geom_of<MODE>(gg, b, g, base);
-            frame_fetch_gen(irsrc, tid < NSLOT, base, g, fy, fx, raw);
-        } else frame_fetch(irsrc, tid < NSLOT, b, H, W, fy, fx, raw);
+        if constexpr (GEN) frame_fetch_gen(irsrc, tid < NSLOT, front_geom_of<MODE>(gg, b), fy, fx, raw);
+        else frame_fetch(irsrc, tid < NSLOT, b, H, W, fy, fx, raw);
     };
     int t = blockIdx.x;
     if (t < total) fetch(t);
@@ -252,33 +126,16 @@ __global__ __launch_bounds__(256, 2) void front_kernel(const uint8_t *__restrict
             const bool inside = tid < NSLOT && (unsigned)fy < (unsigned)OH && (unsigned)fx < (unsigned)OW;
             const int cy = fy < 0 ? 0 : (fy >= OH ? OH - 1 : fy), cx = fx < 0 ? 0 : (fx >= OW ? OW - 1 : fx);
             float x[27];
-            if constexpr (GEN) {
-                FrontGeom g;
-                unsigned base;
-                front_geom_of<MODE>(gg, b, g, base);
-                frame_unpack_gen(raw, base, H, W, g, cy, cx, x);
-            } else frame_unpack(raw, b, H, W, cy, cx, x);
+            if constexpr (GEN) frame_unpack_gen(raw, H, W, front_geom_of<MODE>(gg, b), cy, cx, x);
+            else frame_unpack(raw, b, H, W, cy, cx, x);
             // the next tile's bytes: in flight until the next iteration's phase 1
             if (t + (int)gridDim.x < total) fetch(t + (int)gridDim.x);
             unsigned char *prow = lds + tid * 128;
             {                                                // all 32 accumulators in one pass over the 27 taps
                 float acc[32];
+                fc_taps(x, a_w0, 32, a_m0, a_s0, a_b0, a.act0, acc);
 #pragma unroll
-                for (int i = 0; i < 32; ++i) acc[i] = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 27; ++k) {
-                    const float *wr = a_w0 + k * 32;
-#pragma unroll
-                    for (int i = 0; i < 32; ++i) acc[i] = fmaf(x[k], wr[i], acc[i]);
-                }
-#pragma unroll
-                for (int i = 0; i < 32; ++i) {
-                    const float tq = (acc[i] - a_m0[i]) * a_s0[i];
-                    float v = tq + a_b0[i];
-                    if (a.act0 >= 1) v = v > 0.0f ? v : 0.0f;
-                    if (a.act0 == 2) v = v < 6.0f ? v : 6.0f;
-                    acc[i] = inside ? v : 0.0f;
-                }
+                for (int i = 0; i < 32; ++i) acc[i] = inside ? acc[i] : 0.0f;
                 if (tid < NSLOT) {
 #pragma unroll
                     for (int i = 0; i < 32; i += 4)
@@ -406,7 +263,7 @@ __global__ __launch_bounds__(256, 2) void front_pool_kernel(const uint8_t *__res
     const int tiles_img = a.tiles_y * a.tiles_x, total = a.B * tiles_img;
     int ibytes;
     if constexpr (MODE == 2) ibytes = (int)gg.bytes4;
-    else if constexpr (MODE == 1) ibytes = (int)((((long long)a.B * gg.srcH * gg.srcW * 3) + gg.off0 + 3) & ~3LL);
+    else if constexpr (MODE == 1) ibytes = (int)((((long long)a.B * gg.srcH * gg.srcW * 3) + gg.off + 3) & ~3LL);
     else ibytes = (int)((long long)a.B * H * W * 3);
     const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a_img, 0, ibytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a_out, 0, (int)((long long)a.B * PH2 * PW2 * CS * 4), 0x00020000);
@@ -417,12 +274,8 @@ __global__ __launch_bounds__(256, 2) void front_pool_kernel(const uint8_t *__res
         int fy = 2 * QY * ty + ppy, fx = 2 * QX * tx + ppx;
         fy = fy >= OH ? OH - 1 : fy;
         fx = fx >= OW ? OW - 1 : fx;
-        if constexpr (GEN) {
-            FrontGeom g;
-            unsigned base;
-            front_geom_of<MODE>(gg, b, g, base);
-            frame_fetch_gen(irsrc, tid < QSLOT, base, g, fy, fx, raw);
-        } else frame_fetch(irsrc, tid < QSLOT, b, H, W, fy, fx, raw);
+        if constexpr (GEN) frame_fetch_gen(irsrc, tid < QSLOT, front_geom_of<MODE>(gg, b), fy, fx, raw);
+        else frame_fetch(irsrc, tid < QSLOT, b, H, W, fy, fx, raw);
     };
     int t = blockIdx.x;
     if (t < total) fetch(t);
@@ -433,32 +286,15 @@ __global__ __launch_bounds__(256, 2) void front_pool_kernel(const uint8_t *__res
             const bool inside = tid < QSLOT && fy < OH && fx < OW;
             const int cy = fy >= OH ? OH - 1 : fy, cx = fx >= OW ? OW - 1 : fx;
             float x[27];
-            if constexpr (GEN) {
-                FrontGeom g;
-                unsigned base;
-                front_geom_of<MODE>(gg, b, g, base);
-                frame_unpack_gen(raw, base, H, W, g, cy, cx, x);
-            } else frame_unpack(raw, b, H, W, cy, cx, x);
+            if constexpr (GEN) frame_unpack_gen(raw, H, W, front_geom_of<MODE>(gg, b), cy, cx, x);
+            else frame_unpack(raw, b, H, W, cy, cx, x);
             if (t + (int)gridDim.x < total) fetch(t + (int)gridDim.x);
             unsigned char *prow = lds + tid * 128;
             {                                                // all COUT accumulators in one pass over the 27 taps
                 float acc[COUT];
+                fc_taps(x, a_w0, CS, a_m0, a_s0, a_b0, a.act0, acc);      // (weights [27][CS])
 #pragma unroll
-                for (int i = 0; i < COUT; ++i) acc[i] = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 27; ++k) {
-                    const float *wr = a_w0 + k * CS;             // (weights [27][CS])
-#pragma unroll
-                    for (int i = 0; i < COUT; ++i) acc[i] = fmaf(x[k], wr[i], acc[i]);
-                }
-#pragma unroll
-                for (int i = 0; i < COUT; ++i) {
-                    const float tq = (acc[i] - a_m0[i]) * a_s0[i];
-                    float v = tq + a_b0[i];
-                    if (a.act0 >= 1) v = v > 0.0f ? v : 0.0f;
-                    if (a.act0 == 2) v = v < 6.0f ? v : 6.0f;
-                    acc[i] = inside ? v : -__builtin_inff();
-                }
+                for (int i = 0; i < COUT; ++i) acc[i] = inside ? acc[i] : -__builtin_inff();
                 if (tid < QSLOT) {
 #pragma unroll
                     for (int i = 0; i < COUT; i += 4)
@@ -535,27 +371,21 @@ hipError_t launch_front_pool(const uint8_t *img, int B, int H, int W, const floa
     const long long total = (long long)B * d.tiles_y * d.tiles_x;
     if (total > 0x7fffffffLL) return hipErrorInvalidValue;
     const int grid = (int)(total < 4096 ? total : 4096);
-    // (resized / mixed: the kernel's dword loads are aligned relative to its base -- a base that is no multiple of 4 is rounded down
-    //  and the remainder added to the frames' byte offsets, elementwise.hip launch_first_conv_gen)
-    const unsigned adj = (src || mixed) ? (unsigned)((uintptr_t)img & 3u) : 0u;
-    img -= adj;
     if (mixed) {
         FrontMixed fm;
         if (!front_mixed_supports(*mixed, first, B, H, W, &fm.bytes4)) return hipErrorInvalidValue;
         fm.mg = *mixed;
-        for (int b = first; b < first + B; ++b) fm.mg.f[b].off += adj;
-        fm.bytes4 = (fm.bytes4 + adj + 3u) & ~3u;
+        fm.bytes4 = frame_base_align(img, fm.bytes4, fm.mg, first, B);
         fm.first = first;
         if (C0 == 24) hipLaunchKernelGGL((front_pool_kernel<24, 24, 2>), dim3((unsigned)grid), dim3(256), 0, s, img, w0, m0, s0, b0, out, d, fm);
         else hipLaunchKernelGGL((front_pool_kernel<24, 32, 2>), dim3((unsigned)grid), dim3(256), 0, s, img, w0, m0, s0, b0, out, d, fm);
-        return hipGetLastError();
-    }
-    const FrontGeom g = src ? FrontGeom{src[0], src[1], src[2], src[3], (float)src[0] / (float)src[2], (float)src[1] / (float)src[3], adj}
-                            : FrontGeom{H, W, H, W, 1.0f, 1.0f, 0u};
-    if (src) {
+    } else if (src) {
+        FrameGeom g = frame_geom(src[0], src[1], src[2], src[3]);
+        frame_base_align(img, (unsigned long long)B * src[0] * src[1] * 3, g);       // (the kernel forms the same dword-rounded range from g)
         if (C0 == 24) hipLaunchKernelGGL((front_pool_kernel<24, 24, 1>), dim3((unsigned)grid), dim3(256), 0, s, img, w0, m0, s0, b0, out, d, g);
         else hipLaunchKernelGGL((front_pool_kernel<24, 32, 1>), dim3((unsigned)grid), dim3(256), 0, s, img, w0, m0, s0, b0, out, d, g);
     } else {
+        const FrameGeom g = frame_geom(H, W, H, W);
         if (C0 == 24) hipLaunchKernelGGL((front_pool_kernel<24, 24, 0>), dim3((unsigned)grid), dim3(256), 0, s, img, w0, m0, s0, b0, out, d, g);
         else hipLaunchKernelGGL((front_pool_kernel<24, 32, 0>), dim3((unsigned)grid), dim3(256), 0, s, img, w0, m0, s0, b0, out, d, g);
     }
@@ -581,26 +411,23 @@ hipError_t launch_front(const FrontArgs &q, hipStream_t s)
     // 512 / 756 blocks -> 34.2 / 32.8 / 28.8 / 32.1 us; 32 frames: 512 / 1024 / 2048 the same step time)
     const int grid = (int)(total < 512 ? total : 512);
     const FrontDims d = {q.B, q.H, q.W, q.act0, q.dact, q.act, q.tiles_y, q.tiles_x};
-    // (resized / mixed: loads aligned relative to a base that is itself a multiple of 4, as in launch_front_pool)
-    const unsigned adj = (q.mixed || q.resized) ? (unsigned)((uintptr_t)q.img & 3u) : 0u;
-    const uint8_t *img = q.img - adj;
+    const uint8_t *img = q.img;
     if (q.mixed) {
         FrontMixed fm;
         if (!front_mixed_supports(*q.mixed, q.mixed_first, q.B, q.H, q.W, &fm.bytes4)) return hipErrorInvalidValue;
         fm.mg = *q.mixed;
-        for (int b = q.mixed_first; b < q.mixed_first + q.B; ++b) fm.mg.f[b].off += adj;
-        fm.bytes4 = (fm.bytes4 + adj + 3u) & ~3u;
+        fm.bytes4 = frame_base_align(img, fm.bytes4, fm.mg, q.mixed_first, q.B);
         fm.first = q.mixed_first;
         hipLaunchKernelGGL(front_kernel<2>, dim3((unsigned)grid), dim3(256), LDS_BYTES, s, img, q.w0, q.m0, q.s0, q.b0, q.dwpack, q.wt, q.mean,
                            q.sf, q.beta, q.out, d, fm);
     } else if (q.resized) {
-        // (the scale factors as launch_first_conv forms them: the same float expressions as elementwise.hip K1 / K1d)
-        const FrontGeom g = {q.srcH, q.srcW, q.nh, q.nw, (float)q.srcH / (float)q.nh, (float)q.srcW / (float)q.nw, adj};
+        FrameGeom g = frame_geom(q.srcH, q.srcW, q.nh, q.nw);
+        frame_base_align(img, (unsigned long long)q.B * q.srcH * q.srcW * 3, g);     // (the kernel forms the same dword-rounded range from g)
         hipLaunchKernelGGL(front_kernel<1>, dim3((unsigned)grid), dim3(256), LDS_BYTES, s, img, q.w0, q.m0, q.s0, q.b0, q.dwpack, q.wt, q.mean,
                            q.sf, q.beta, q.out, d, g);
     } else {
-        const FrontGeom g = {q.H, q.W, q.H, q.W, 1.0f, 1.0f, 0u};
-        hipLaunchKernelGGL(front_kernel<0>, dim3((unsigned)grid), dim3(256), LDS_BYTES, s, q.img, q.w0, q.m0, q.s0, q.b0, q.dwpack, q.wt, q.mean,
+        const FrameGeom g = frame_geom(q.H, q.W, q.H, q.W);
+        hipLaunchKernelGGL(front_kernel<0>, dim3((unsigned)grid), dim3(256), LDS_BYTES, s, img, q.w0, q.m0, q.s0, q.b0, q.dwpack, q.wt, q.mean,
                            q.sf, q.beta, q.out, d, g);
     }
     return hipGetLastError();

@@ -177,6 +177,33 @@ hipError_t launch_pw_gather(const PwGArgs &a, hipStream_t s);
 #define SSD_MIXED_MAX 64
 struct FrameGeom { unsigned off; int srcH, srcW, nh, nw; float hs, ws; };
 struct MixedGeom { FrameGeom f[SSD_MIXED_MAX]; };
+// frames [.,srcH,srcW,3] resized to [nh,nw], the first at byte 0: the scale factors are these float expressions everywhere
+inline FrameGeom frame_geom(int srcH, int srcW, int nh, int nw) { return {0u, srcH, srcW, nh, nw, (float)srcH / (float)nh, (float)srcW / (float)nw}; }
+// The gathers of resized frames (first_pixels.h) load dwords that are aligned RELATIVE TO THEIR BASE: a base that is not a multiple
+// of 4 itself (the second chain's or sub-batch's first frame when a frame's byte size is odd, a caller's slice) is rounded down and
+// the remainder added to the frames' byte offsets, so that no load depends on the device's unaligned-access mode.  Returns the byte
+// range `bytes` from the new base, rounded up to whole dwords (a row's or pixel's last dword may reach <= 3 bytes past a size
+// that is no multiple of 4: the same word).
+inline unsigned frame_base_round(const uint8_t *&img, unsigned long long &bytes)
+{
+    const unsigned adj = (unsigned)((uintptr_t)img & 3u);
+    img -= adj;
+    bytes = (bytes + adj + 3) & ~3ull;
+    return adj;
+}
+// ... equally sized frames, g the first
+inline unsigned frame_base_align(const uint8_t *&img, unsigned long long bytes, FrameGeom &g)
+{
+    g.off += frame_base_round(img, bytes);
+    return (unsigned)bytes;
+}
+// ... entries first .. first + B - 1 of a table
+inline unsigned frame_base_align(const uint8_t *&img, unsigned long long bytes, MixedGeom &mg, int first, int B)
+{
+    const unsigned adj = frame_base_round(img, bytes);
+    for (int b = first; b < first + B; ++b) mg.f[b].off += adj;
+    return (unsigned)bytes;
+}
 struct FrontArgs {
     const uint8_t *img;                    // [B,H,W,3] uint8 frames at the network's input size (identity resize), H and W even
     const float *w0, *m0, *s0, *b0;        // first convolution: [27][32] weights (physical output order), batch norm [32]

@@ -7,6 +7,7 @@
 // Every call checks its arguments before the first HIP call, then only enqueues on `stream`; scratch is the caller's workspace.
 #include "host.h"
 #include "train_head.h"
+#include "first_pixels.h"
 
 #include <algorithm>
 
@@ -240,9 +241,8 @@ static size_t fc_bytes(const FcArgs &p) { return al256((size_t)p.sl.n_slabs * 27
 // is lane tid of the column-sum core, G = C / 4, for filter row ky: it keeps the sums of p * dy of that row -- 3 pixels x 3
 // channels x 4 output channels, 36 doubles -- so that the 27 x 4 accumulators of a channel quad are spread over three threads of
 // one block, which read the same dy rows at about the same time, instead of filling one thread's register file.  The nine bytes
-// under a filter row are contiguous, 0 or 2 bytes past a dword boundary (W is even; which of the two depends on the row when
-// W % 4 == 2): three aligned dword loads through a range-checked buffer resource and a byte alignment, as in first_conv_px_kernel
-// (elementwise.hip).  Only row 2oy+2 and column 2ox+2 can lie outside the image: such taps are skipped.  The product of two
+// under a filter row come from fc_row_fetch / fc_row_bytes and their values from fc_pixel (first_pixels.h), as in the forward
+// kernels.  Only row 2oy+2 and column 2ox+2 can lie outside the image: such taps are skipped.  The product of two
 // floats is exact in double, so fma(p, dy, acc) has the bits of acc + p * dy.  The block then adds its row lanes one tap at a
 // time, each filter row in its own third of the LDS.
 __global__ __launch_bounds__(768) void fc_wgrad_partial(const FcArgs a)
@@ -253,7 +253,6 @@ __global__ __launch_bounds__(768) void fc_wgrad_partial(const FcArgs a)
     const SlabLane ln = slab_lane(tid, G, slab, a.sl.slab_rows, a.sl.R);
     const int c = ln.c, rpp = ln.rpp;
     const long long r0 = ln.r0, r1 = ln.r1;
-    const float inv255 = (float)(1.0 / 255.0);
     const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.img, 0, (int)((long long)a.B * a.H * a.W * 3), 0x00020000);
     double acc[9][4];
 #pragma unroll
@@ -277,30 +276,20 @@ __global__ __launch_bounds__(768) void fc_wgrad_partial(const FcArgs a)
             const v4f d = *(const v4f *)(a.dy + r * C + c);
             const double dd[4] = {(double)d[0], (double)d[1], (double)d[2], (double)d[3]};
             const int ad = ((2 * crow + ky) * a.W + 2 * cx) * 3;
-            const int a0 = ad & ~3, sh = ad & 3;         // sh: byte offset of the row's first pixel inside its dword (0 or 2)
-            const unsigned w0 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0, 0, 0);
-            const unsigned w1 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0 + 4, 0, 0);
-            const unsigned w2 = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a0 + 8, 0, 0);
-            const unsigned d0 = __builtin_amdgcn_alignbyte(w1, w0, sh);
-            const unsigned d1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
-            const unsigned d2 = w2 >> (8 * sh);
-            const unsigned char px[9] = {(unsigned char)d0, (unsigned char)(d0 >> 8), (unsigned char)(d0 >> 16), (unsigned char)(d0 >> 24),
-                                         (unsigned char)d1, (unsigned char)(d1 >> 8), (unsigned char)(d1 >> 16), (unsigned char)(d1 >> 24),
-                                         (unsigned char)d2};
+            unsigned w0, w1, w2;
+            unsigned char px[9];
+            fc_row_fetch<true>(irsrc, true, ad, w0, w1, w2);
+            fc_row_bytes(w0, w1, w2, ad & 3, px);
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
-                float v = (float)px[k] * inv255;
-                v = 2.0f * v - 1.0f;
-                const double pv = (double)v;
+                const double pv = (double)fc_pixel(px[k]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[k][e] = fma(pv, dd[e], acc[k][e]);
             }
             if (cx < OW - 1) {                               // else column W: outside
 #pragma unroll
                 for (int k = 6; k < 9; ++k) {
-                    float v = (float)px[k] * inv255;
-                    v = 2.0f * v - 1.0f;
-                    const double pv = (double)v;
+                    const double pv = (double)fc_pixel(px[k]);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[k][e] = fma(pv, dd[e], acc[k][e]);
                 }
