@@ -80,9 +80,10 @@ def conv_backward(ssd, cuda, xs, w, dys, stride=1, bias=True, with_dx=True):
     return [t.grad.cpu().numpy() for t in tx] if with_dx else None, tw.grad.cpu().numpy(), tb.grad.cpu().numpy() if bias else None
 
 
-def _conv_raw(ssd, cuda, which, general, X, DY, OUT, Wt, stride, *ptrs):
+def _conv_raw(ssd, cuda, which, general, X, DY, OUT, Wt, stride, *ptrs, fill_ws=None):
     """One call of ssd_conv3x3_train_<which> -- general: of ssd_conv_train_<which> with k from the kernel, `stride` and, for the
-    forward, up = NULL -- with a workspace of exactly the size its planner asks for.  -> that size."""
+    forward, up = NULL -- with a workspace of exactly the size its planner asks for, pre-filled with the byte `fill_ws` when given.
+    -> that size."""
     L = ssd.lib()
     lv = (ssd._lib.SsdConvLevel * len(X))()
     for i, x in enumerate(X):
@@ -92,7 +93,7 @@ def _conv_raw(ssd, cuda, which, general, X, DY, OUT, Wt, stride, *ptrs):
     dims = (lv, len(X), X[0].shape[0], Cin, Cout)
     need = L.ssd_conv_train_workspace_bytes(*dims, k, stride, 0) if general else L.ssd_conv3x3_train_workspace_bytes(*dims)
     assert need > 0
-    ws = cuda.empty(need, dtype=cuda.uint8, device="cuda")
+    ws = cuda.empty(need, dtype=cuda.uint8, device="cuda") if fill_ws is None else cuda.full((need,), fill_ws, dtype=cuda.uint8, device="cuda")
     tail = (ws.data_ptr(), ws.numel(), stream(cuda))
     if general:
         up = (None,) if which == "forward" else ()
@@ -111,14 +112,14 @@ def conv_forward_raw(ssd, cuda, xs, w, bias, general=False, stride=1):
     return [y.cpu().numpy() for y in Y], need
 
 
-def conv_backward_raw(ssd, cuda, xs, w, dys, with_dx, with_dbias, sentinel=-7.5, general=False, stride=1):
-    """The backward straight through the C ABI (general: see _conv_raw): out = NULL for every level unless with_dx, dbias_dev = NULL
-    unless with_dbias.  -> ([dx] or None, dw, the dbias buffer -- pre-filled with `sentinel`, passed to the call only with_dbias)."""
+def conv_backward_raw(ssd, cuda, xs, w, dys, with_dx, with_dbias, sentinel=-7.5, general=False, stride=1, fill_ws=None):
+    """The backward straight through the C ABI (general, fill_ws: see _conv_raw): out = NULL for every level unless with_dx, dbias_dev
+    = NULL unless with_dbias.  -> ([dx] or None, dw, the dbias buffer -- pre-filled with `sentinel`, passed to the call only with_dbias)."""
     X, DY, Wt = [dev(cuda, x) for x in xs], [dev(cuda, d) for d in dys], dev(cuda, w)
     DX = [cuda.full_like(x, float("nan")) for x in X] if with_dx else None
     dw = cuda.full_like(Wt, float("nan"))
     db = cuda.full(((w.shape[3] + 3) // 4 * 4,), sentinel, device="cuda")
-    _conv_raw(ssd, cuda, "backward", general, X, DY, DX, Wt, stride, dw.data_ptr(), db.data_ptr() if with_dbias else None)
+    _conv_raw(ssd, cuda, "backward", general, X, DY, DX, Wt, stride, dw.data_ptr(), db.data_ptr() if with_dbias else None, fill_ws=fill_ws)
     return [d.cpu().numpy() for d in DX] if with_dx else None, dw.cpu().numpy(), db.cpu().numpy()
 
 

@@ -8,6 +8,7 @@ import pytest
 
 from helpers import backbone_train_ref as ref
 from helpers import head_train_ref as href
+from helpers.backbone_train_gpu import dw_backward_raw as _dw_backward_raw
 from helpers.head_train_gpu import bn_raw, conv_backward, dev as _dev, same_bits, stream as _stream
 from conftest import TINY_PARAMS
 
@@ -28,22 +29,6 @@ def _dw_data(rng, h, w, C, stride, integers=False, batch=B):
                 rng.integers(-3, 4, (batch, oh, ow, C)).astype(f32))
     return (rng.normal(0, 1, (batch, h, w, C)).astype(f32), rng.normal(0, 0.5, (3, 3, C, 1)).astype(f32),
             rng.normal(0, 1, (batch, oh, ow, C)).astype(f32))
-
-
-def _dw_backward_raw(ssd, cuda, x, w, dy, stride, with_dx=True):
-    """ssd_depthwise_train_backward straight through the C ABI with a workspace of exactly the size its planner asks for; the
-    outputs are pre-filled with NaN.  -> (dx or None, dw)."""
-    L = ssd.lib()
-    X, Wt, DY = _dev(cuda, x), _dev(cuda, w), _dev(cuda, dy)
-    DX = cuda.full_like(X, float("nan")) if with_dx else None
-    DW = cuda.full_like(Wt, float("nan"))
-    b, h, ww, C = x.shape
-    need = L.ssd_depthwise_train_workspace_bytes(b, h, ww, C, stride)
-    assert need > 0
-    ws = cuda.empty(need, dtype=cuda.uint8, device="cuda")
-    ssd._lib.check(L.ssd_depthwise_train_backward(X.data_ptr(), DY.data_ptr(), b, h, ww, C, Wt.data_ptr(), stride,
-                                                  DX.data_ptr() if with_dx else None, DW.data_ptr(), ws.data_ptr(), ws.numel(), _stream(cuda)))
-    return DX.cpu().numpy() if with_dx else None, DW.cpu().numpy()
 
 
 # ----------------------------------------------------------------------------- 1. the depthwise forward
