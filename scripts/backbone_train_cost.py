@@ -11,7 +11,6 @@ kernel's own rate, 3.7 TB/s at stride 1 and 4.7 TB/s at stride 2 (profiles/r02_d
 of it), the batch norm with ReLU6 in GB/s, the FPN with and without the bridge to c3, c4, c5, and one whole
 backbone + FPN + head step (forward, loss, backward) with its peak memory."""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -20,17 +19,12 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch                                                      # noqa: E402
 import ssd_amd                                                    # noqa: E402
-from ssd_amd._lib import SsdBnLevel, SsdConvLevel, check, lib    # noqa: E402
+from ssd_amd import train_calls as calls                          # noqa: E402
 from head_train_cost import PEAK, timed                           # noqa: E402
 from fpn_train_cost import C_SIZES, C_WIDTHS                      # noqa: E402
 
 
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def depthwise_lines(name, B, H, W, C, stride, reps):
-    L, s = lib(), stream()
     g = torch.Generator(device="cuda").manual_seed(1)
     OH, OW = -(-H // stride), -(-W // stride)
     x = torch.randn((B, H, W, C), device="cuda", generator=g)
@@ -38,12 +32,11 @@ def depthwise_lines(name, B, H, W, C, stride, reps):
     y, dx = torch.empty_like(dy), torch.empty_like(x)
     w = torch.randn((3, 3, C, 1), device="cuda", generator=g)
     dw = torch.empty_like(w)
-    ws = torch.empty(L.ssd_depthwise_train_workspace_bytes(B, H, W, C, stride), dtype=torch.uint8, device="cuda")
-    bwd = lambda d: check(L.ssd_depthwise_train_backward(x.data_ptr(), dy.data_ptr(), B, H, W, C, w.data_ptr(), stride, d, dw.data_ptr(),
-                                                         ws.data_ptr(), ws.numel(), s))
-    t_f = timed(lambda: check(L.ssd_depthwise_train_forward(x.data_ptr(), B, H, W, C, w.data_ptr(), stride, y.data_ptr(), s)), reps)
+    ws = torch.empty(calls.depthwise_workspace_bytes(x, stride), dtype=torch.uint8, device="cuda")
+    bwd = lambda d: calls.depthwise_backward(x, w, dy, dw, stride, d, workspace=ws)
+    t_f = timed(lambda: calls.depthwise_forward(x, w, y, stride), reps)
     t_w = timed(lambda: bwd(None), reps)
-    t_x = timed(lambda: bwd(dx.data_ptr()), reps) - t_w
+    t_x = timed(lambda: bwd(dx), reps) - t_w
     nb = (x.numel() + dy.numel()) * 4.0
     gbs = lambda t: nb / t / 1e6
     print("  %-9s depthwise s%d %4d channels at %dx%d  %.1f MB in + out  workspace %.1f MB" % (name, stride, C, H, W, nb / 1e6, ws.numel() / 1e6))
@@ -53,19 +46,16 @@ def depthwise_lines(name, B, H, W, C, stride, reps):
 
 
 def pointwise_lines(B, H, W, Cin, Cout, reps):
-    L, s = lib(), stream()
     g = torch.Generator(device="cuda").manual_seed(2)
     x = torch.randn((B, H, W, Cin), device="cuda", generator=g)
     dy = torch.randn((B, H, W, Cout), device="cuda", generator=g)
     dx = torch.empty_like(x)
     w = torch.randn((1, 1, Cin, Cout), device="cuda", generator=g) * 0.05
     dw = torch.empty_like(w)
-    level = lambda out: (SsdConvLevel * 1)(SsdConvLevel(H, W, x.data_ptr(), dy.data_ptr(), out.data_ptr() if out is not None else None))
-    lw, lb = level(None), level(dx)
-    ws = torch.empty(L.ssd_pointwise_train_workspace_bytes(lb, 1, B, Cin, Cout), dtype=torch.uint8, device="cuda")
-    call = lambda lv: check(L.ssd_pointwise_train_backward(lv, 1, B, Cin, Cout, w.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), s))
-    t_w = timed(lambda: call(lw), reps)
-    t_x = timed(lambda: call(lb), reps) - t_w
+    ws = torch.empty(calls.conv_workspace_bytes([x], B, Cin, Cout, 1, entry="pointwise"), dtype=torch.uint8, device="cuda")
+    call = lambda dxs: calls.conv_backward([x], w, [dy], dw, dxs=dxs, workspace=ws, entry="pointwise")
+    t_w = timed(lambda: call(None), reps)
+    t_x = timed(lambda: call([dx]), reps) - t_w
     fl = 2.0 * Cin * Cout * B * H * W
     tf = lambda t: fl / t / 1e9
     print("  1x1 %4d -> %4d at %dx%d  workspace %.1f MB" % (Cin, Cout, H, W, ws.numel() / 1e6))
@@ -75,17 +65,14 @@ def pointwise_lines(B, H, W, Cin, Cout, reps):
 
 def bn_lines(B, H, W, C, reps, inline=False):
     """inline: two lines under another layer's heading, each naming the batch norm, instead of a heading of its own"""
-    L, s = lib(), stream()
     g = torch.Generator(device="cuda").manual_seed(3)
     x = torch.randn((B * H * W, C), device="cuda", generator=g) * 2
     dy = torch.randn_like(x)
     y, dx = torch.empty_like(x), torch.empty_like(x)
-    v = [torch.ones(C, device="cuda") for _ in range(9)]
-    lv = (SsdBnLevel * 1)(SsdBnLevel(x.shape[0], x.data_ptr(), dy.data_ptr(), y.data_ptr(), *[t.data_ptr() for t in v]))
-    ws = torch.empty(max(L.ssd_bn_relu_train_workspace_bytes(lv, 1, C), 256), dtype=torch.uint8, device="cuda")
-    t_f = timed(lambda: check(L.ssd_bn_act_train_forward(lv, 1, C, 2, 1, 1e-3, 0.007, ws.data_ptr(), ws.numel(), s)), reps)
-    lv[0].out = dx.data_ptr()
-    t_b = timed(lambda: check(L.ssd_bn_act_train_backward(lv, 1, C, 2, ws.data_ptr(), ws.numel(), s)), reps)
+    gamma, beta, mm, mv, mean, var, invstd, dgamma, dbeta = [[torch.ones(C, device="cuda")] for _ in range(9)]
+    ws = torch.empty(max(calls.bn_workspace_bytes([x], C), 256), dtype=torch.uint8, device="cuda")
+    t_f = timed(lambda: calls.bn_forward([x], [y], gamma, beta, True, 1e-3, 0.007, mm, mv, mean, var, invstd, act="relu6", workspace=ws), reps)
+    t_b = timed(lambda: calls.bn_backward([x], [dy], [dx], gamma, beta, mean, invstd, dgamma, dbeta, act="relu6", workspace=ws), reps)
     nb = x.numel() * 4.0
     if inline:
         fmt = "    batch norm + ReLU6 %s %6.3f ms  %7.1f GB/s"

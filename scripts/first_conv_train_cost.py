@@ -14,23 +14,21 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch                                                      # noqa: E402
-from ssd_amd._lib import check, lib                               # noqa: E402
+from ssd_amd import train_calls as calls                          # noqa: E402
 from head_train_cost import timed                                 # noqa: E402
-from backbone_train_cost import bn_lines, step_lines, stream      # noqa: E402
+from backbone_train_cost import bn_lines, step_lines              # noqa: E402
 
 
 def first_conv_lines(B, H, W, Cout, reps):
-    L, s = lib(), stream()
     g = torch.Generator(device="cuda").manual_seed(1)
     OH, OW = H // 2, W // 2
     images = torch.randint(0, 256, (B, H, W, 3), device="cuda", generator=g, dtype=torch.uint8)
     w = torch.randn((3, 3, 3, Cout), device="cuda", generator=g)
     dy = torch.randn((B, OH, OW, Cout), device="cuda", generator=g)
     y, dw = torch.empty_like(dy), torch.empty_like(w)
-    ws = torch.empty(L.ssd_first_conv_train_workspace_bytes(B, H, W, Cout), dtype=torch.uint8, device="cuda")
-    t_f = timed(lambda: check(L.ssd_first_conv_train_forward(images.data_ptr(), B, H, W, w.data_ptr(), Cout, y.data_ptr(), s)), reps)
-    t_w = timed(lambda: check(L.ssd_first_conv_train_backward(images.data_ptr(), dy.data_ptr(), B, H, W, Cout, dw.data_ptr(), ws.data_ptr(),
-                                                              ws.numel(), s)), reps)
+    ws = torch.empty(calls.first_conv_workspace_bytes(images, Cout), dtype=torch.uint8, device="cuda")
+    t_f = timed(lambda: calls.first_conv_forward(images, w, y), reps)
+    t_w = timed(lambda: calls.first_conv_backward(images, dy, dw, workspace=ws), reps)
     nb = images.numel() + dy.numel() * 4.0
     fma = 27.0 * Cout * B * OH * OW
     print("  Conv2d_0  3 -> %d channels, stride 2, %dx%d  images %.1f MB, output / dy %.1f MB  workspace %.2f MB"

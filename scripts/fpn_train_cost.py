@@ -8,7 +8,6 @@ Reports the forward, data-gradient and weight-gradient time and TFLOP/s of later
 yardstick is the head's 256 -> 256 weight gradient at 0.52 of it --, the two forms of ssd_fpn_merge_backward in
 GB/s, and one whole FPN + head step (forward, loss, backward) through TrainableFPN and TrainableBoxPredictor."""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -17,7 +16,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch                                                      # noqa: E402
 import ssd_amd                                                    # noqa: E402
-from ssd_amd._lib import SsdConvLevel, check, lib                # noqa: E402
+from ssd_amd import train_calls as calls                          # noqa: E402
 from head_train_cost import PEAK, SIZES, timed                    # noqa: E402
 
 C_SIZES = [(80, 112), (40, 56), (20, 28)]
@@ -25,8 +24,6 @@ C_WIDTHS = [256, 512, 1024]
 
 
 def conv_lines(name, B, H, W, Cin, Cout, k, stride, with_dx, reps):
-    L = lib()
-    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     g = torch.Generator(device="cuda").manual_seed(1)
     OH, OW = -(-H // stride), -(-W // stride)
     x = torch.randn((B, H, W, Cin), device="cuda", generator=g)
@@ -34,18 +31,17 @@ def conv_lines(name, B, H, W, Cin, Cout, k, stride, with_dx, reps):
     y, dx = torch.empty_like(dy), torch.empty_like(x)
     w = torch.randn((k, k, Cin, Cout), device="cuda", generator=g) * 0.05
     dw = torch.empty_like(w)
-    level = lambda out: (SsdConvLevel * 1)(SsdConvLevel(H, W, x.data_ptr(), dy.data_ptr(), out.data_ptr() if out is not None else None))
-    lf, lw, lb = level(y), level(None), level(dx)
-    ws = torch.empty(L.ssd_conv_train_workspace_bytes(lf, 1, B, Cin, Cout, k, stride, 0), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(calls.conv_workspace_bytes([x], B, Cin, Cout, k, stride), dtype=torch.uint8, device="cuda")
+    bwd = lambda dxs: calls.conv_backward([x], w, [dy], dw, stride, dxs, workspace=ws)
     fl = 2.0 * k * k * Cin * Cout * B * OH * OW
     tf = lambda t: fl / t / 1e9
-    t_f = timed(lambda: check(L.ssd_conv_train_forward(lf, 1, B, Cin, Cout, k, stride, w.data_ptr(), None, None, ws.data_ptr(), ws.numel(), s)), reps)
-    t_w = timed(lambda: check(L.ssd_conv_train_backward(lw, 1, B, Cin, Cout, k, stride, w.data_ptr(), dw.data_ptr(), None, ws.data_ptr(), ws.numel(), s)), reps)
+    t_f = timed(lambda: calls.conv_forward([x], w, [y], stride, workspace=ws), reps)
+    t_w = timed(lambda: bwd(None), reps)
     print("  %-9s %dx%d s%d %4d -> %3d at %dx%d  output rows %7d  workspace %6.1f MB" % (name, k, k, stride, Cin, Cout, H, W, B * OH * OW, ws.numel() / 1e6))
     print("    forward (permutes + pack + igemm)     %8.3f ms  %6.1f TFLOP/s  %4.1f %% of peak" % (t_f, tf(t_f), 100 * tf(t_f) / PEAK))
     print("    weight gradient (wgrad + reduce)      %8.3f ms  %6.1f TFLOP/s  %4.1f %% of peak" % (t_w, tf(t_w), 100 * tf(t_w) / PEAK))
     if with_dx:
-        t_x = timed(lambda: check(L.ssd_conv_train_backward(lb, 1, B, Cin, Cout, k, stride, w.data_ptr(), dw.data_ptr(), None, ws.data_ptr(), ws.numel(), s)), reps)
+        t_x = timed(lambda: bwd([dx]), reps)
         t_d = t_x - t_w
         # a stride-2 data gradient runs the launch over the zero-dilated gradient: stride^2 times the useful multiply-adds
         print("    data gradient (permutes + pack + igemm) %6.3f ms  %6.1f TFLOP/s useful  %4.1f %% of peak  (backward with dx %.3f ms minus the weight gradient)"

@@ -9,7 +9,6 @@ head step (forward, loss, backward) through TrainableBoxPredictor, and -- when t
 -- F.conv2d forward + backward on the same shapes as a second reference line.  For the per-kernel view run it once under
 `rocprofv3 --kernel-trace --stats -- python scripts/head_train_cost.py --frames 8 --reps 1 --no-torch`."""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -18,7 +17,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch                                                      # noqa: E402
 import ssd_amd                                                    # noqa: E402
-from ssd_amd._lib import SsdBnLevel, SsdConvLevel, check, lib    # noqa: E402
+from ssd_amd import train_calls as calls                          # noqa: E402
 
 PEAK = 157.3
 SIZES = [(80, 112), (40, 56), (20, 28), (10, 14), (5, 7)]
@@ -37,8 +36,6 @@ def timed(fn, reps):
 
 
 def conv_lines(B, Cin, Cout, reps):
-    L = lib()
-    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     g = torch.Generator(device="cuda").manual_seed(1)
     xs = [torch.randn((B, h, w, Cin), device="cuda", generator=g) for h, w in SIZES]
     dys = [torch.randn((B, h, w, Cout), device="cuda", generator=g) for h, w in SIZES]
@@ -46,21 +43,14 @@ def conv_lines(B, Cin, Cout, reps):
     dxs = [torch.empty_like(x) for x in xs]
     w = torch.randn((3, 3, Cin, Cout), device="cuda", generator=g) * 0.05
     dw, db = torch.empty_like(w), torch.empty(Cout, device="cuda")
-
-    def levels(outs):
-        lv = (SsdConvLevel * 5)()
-        for i, (h, ww) in enumerate(SIZES):
-            lv[i].H, lv[i].W, lv[i].x, lv[i].dy = h, ww, xs[i].data_ptr(), dys[i].data_ptr()
-            lv[i].out = outs[i].data_ptr() if outs else None
-        return lv
-    lf, lw, lb = levels(ys), levels(None), levels(dxs)
-    ws = torch.empty(L.ssd_conv3x3_train_workspace_bytes(lf, 5, B, Cin, Cout), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(calls.conv_workspace_bytes(SIZES, B, Cin, Cout, entry="conv3x3"), dtype=torch.uint8, device="cuda")
+    bwd = lambda dxs_, db_: calls.conv_backward(xs, w, dys, dw, dxs=dxs_, dbias=db_, workspace=ws, entry="conv3x3")
     R = B * sum(h * w for h, w in SIZES)
     fl = 2.0 * 9 * Cin * Cout * R
-    t_f = timed(lambda: check(L.ssd_conv3x3_train_forward(lf, 5, B, Cin, Cout, w.data_ptr(), None, ws.data_ptr(), ws.numel(), s)), reps)
-    t_w = timed(lambda: check(L.ssd_conv3x3_train_backward(lw, 5, B, Cin, Cout, w.data_ptr(), dw.data_ptr(), None, ws.data_ptr(), ws.numel(), s)), reps)
-    t_x = timed(lambda: check(L.ssd_conv3x3_train_backward(lb, 5, B, Cin, Cout, w.data_ptr(), dw.data_ptr(), None, ws.data_ptr(), ws.numel(), s)), reps)
-    t_b = timed(lambda: check(L.ssd_conv3x3_train_backward(lb, 5, B, Cin, Cout, w.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), s)), reps)
+    t_f = timed(lambda: calls.conv_forward(xs, w, ys, workspace=ws, entry="conv3x3"), reps)
+    t_w = timed(lambda: bwd(None, None), reps)
+    t_x = timed(lambda: bwd(dxs, None), reps)
+    t_b = timed(lambda: bwd(dxs, db), reps)
     tf = lambda t: fl / t / 1e9
     print("  conv %3d -> %3d  rows %7d  workspace %6.1f MB" % (Cin, Cout, R, ws.numel() / 1e6))
     print("    forward (permutes + pack + igemm)     %8.3f ms  %6.1f TFLOP/s  %4.1f %% of peak" % (t_f, tf(t_f), 100 * tf(t_f) / PEAK))
@@ -72,22 +62,15 @@ def conv_lines(B, Cin, Cout, reps):
 
 
 def bn_lines(B, reps, C=256):
-    L = lib()
-    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     g = torch.Generator(device="cuda").manual_seed(2)
     xs = [torch.randn((B, h, w, C), device="cuda", generator=g) for h, w in SIZES]
     dys = [torch.randn_like(x) for x in xs]
     outs = [torch.empty_like(x) for x in xs]
     par = torch.ones((5, 9, C), device="cuda")
-    lv = (SsdBnLevel * 5)()
-    for i, x in enumerate(xs):
-        lv[i].rows = x.numel() // C
-        for k, name in enumerate(("gamma", "beta", "moving_mean", "moving_variance", "mean", "var", "invstd", "dgamma", "dbeta")):
-            setattr(lv[i], name, par[i, k].data_ptr())
-        lv[i].x, lv[i].dy, lv[i].out = x.data_ptr(), dys[i].data_ptr(), outs[i].data_ptr()
-    ws = torch.empty(L.ssd_bn_relu_train_workspace_bytes(lv, 5, C), dtype=torch.uint8, device="cuda")
-    t_f = timed(lambda: check(L.ssd_bn_relu_train_forward(lv, 5, C, 1, 1e-3, 0.007, ws.data_ptr(), ws.numel(), s)), reps)
-    t_b = timed(lambda: check(L.ssd_bn_relu_train_backward(lv, 5, C, ws.data_ptr(), ws.numel(), s)), reps)
+    gamma, beta, mm, mv, mean, var, invstd, dgamma, dbeta = [[par[i, k] for i in range(5)] for k in range(9)]
+    ws = torch.empty(calls.bn_workspace_bytes(xs, C), dtype=torch.uint8, device="cuda")
+    t_f = timed(lambda: calls.bn_forward(xs, outs, gamma, beta, True, 1e-3, 0.007, mm, mv, mean, var, invstd, workspace=ws, entry="bn_relu"), reps)
+    t_b = timed(lambda: calls.bn_backward(xs, dys, outs, gamma, beta, mean, invstd, dgamma, dbeta, workspace=ws, entry="bn_relu"), reps)
     nbytes = sum(x.numel() for x in xs) * 4.0
     print("  batch norm + relu, 5 levels, C = %d, tensor %.1f MB" % (C, nbytes / 1e6))
     print("    forward  (5 launches, 4 passes)       %8.3f ms  %7.1f GB/s moved" % (t_f, 4 * nbytes / t_f / 1e6))

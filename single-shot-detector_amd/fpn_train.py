@@ -7,7 +7,7 @@ TRAIN FPN").
 This is the reference's own recipe (train.py:44-50 warm-starts only the backbone; fpn/*, box_net/* and class_net/* start from
 their initialisers and are trained).  On features that do not require a gradient (an Engine's: a frozen backbone) no gradient
 flows into c3, c4, c5; on features that do (TrainableMobileNet's, backbone_train.py) the backward also returns
-d c3, d c4, d c5.  The FPN's graph is ONE torch.autograd.Function over train_ops.py's calls of ssd_conv_train_forward / _backward; its backward runs
+d c3, d c4, d c5.  The FPN's graph is ONE torch.autograd.Function over train_ops.py's allocating helpers around train_calls.py's conv_forward / conv_backward (ssd_conv_train_forward / _backward); its backward runs
 the gradients in a fixed order with ssd_fpn_merge_backward doing every sum, so torch provides memory, streams and the autograd
 graph only.  The ops (conv_same, batch_norm_relu, fpn_merge_backward) and the variable loading (ReferenceVariables) are
 train_ops.py's; this file keeps the FPN's initialisers and its graph.
@@ -18,7 +18,7 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from .train_ops import ReferenceVariables, _conv_backward, _conv_forward, _need, _pointwise_backward, fpn_merge_backward
+from .train_ops import ReferenceVariables, _conv_backward, _conv_forward, _need, fpn_merge_backward
 
 FPN_DEPTH = 256                 # detector/feature_extractor.py:7
 LEVELS = (3, 4, 5, 6, 7)
@@ -61,10 +61,8 @@ class _FpnGraph(torch.autograd.Function):
         bridge = any(ctx.needs_input_grad[:3])                           # a trainable backbone: also d c3, d c4, d c5
 
         def lateral(c, l, dx):
-            if not bridge:
-                return _conv_backward((c,), l, (dx,), 1, False)[0], None
-            gl, (dc,) = _pointwise_backward((c,), l, (dx,), True)
-            return gl, dc
+            gl, _, dcs = _conv_backward((c,), l, (dx,), 1, bridge, entry="pointwise" if bridge else "conv")
+            return gl, dcs[0] if bridge else None
         g6, _, dc5_p6 = _conv_backward((c5,), k6, (dp6,), 2, bridge)
         g3, _, (dx3,) = _conv_backward((x3,), k3, (d3,), 1, True)
         gl3, dc3 = lateral(c3, l3, dx3)

@@ -1,0 +1,314 @@
+"""How a TRAIN entry point of include/ssd_hip.h is called ("the TRAIN head", "the TRAIN FPN", "the TRAIN backbone", "the TRAIN first
+convolution"): the only module that fills ssd_conv_level / ssd_bn_level, orders the arguments, sizes the workspace and passes the
+stream.  One function per entry point family, no autograd, no model.  Arguments are torch tensors, None exactly where the header
+allows NULL; every result is the CALLER's tensor.  Before the library is called every tensor is checked against the shape the
+geometry implies (ValueError naming the argument: shape, dtype, contiguity, level counts) and then for lying on one GPU
+(TypeError: there is no CPU path); alignment and size limits stay the C side's refusals (SsdError).
+workspace=None: the grow-only buffer per (device, stream), sized by the call's own planner; workspace=<uint8 tensor>: exactly that
+buffer (data_ptr(), numel()), which the family's *_workspace_bytes sizes."""
+import ctypes
+
+import torch
+
+from ._lib import SsdBnLevel, SsdConvLevel, check, lib
+
+ACTS = {"relu": 1, "relu6": 2}                                                 # SSD_ACT_RELU, SSD_ACT_RELU6
+_workspaces = {}
+
+
+def stream(device):
+    """The current torch stream of `device` as the entry points' `void *stream`."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _workspace(device, nbytes):
+    """A grow-only scratch buffer per (device, stream): every call is ordered on the stream that owns it."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _workspaces.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+        _workspaces[key] = ws
+    return ws
+
+
+def _need(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+        raise TypeError("%s must be a float32 tensor on a GPU (there is no CPU path)" % name)
+
+
+# ----------------------------------------------------------------------------- the checks
+def _dense(t, name, shape, dtype=torch.float32):
+    """t is a contiguous `dtype` tensor of `shape` (None: any size along that axis) -> its shape."""
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and t.dim() == len(shape)
+            and all(want in (None, have) for want, have in zip(shape, t.shape))):
+        raise ValueError("%s must be a contiguous %s tensor of shape %s" % (name, str(dtype)[6:], list(shape)))
+    return t.shape
+
+
+def _vector(t, name, C):
+    """t is None or a per-channel vector, 1-D float32 contiguous with AT LEAST C elements (a padded row, a sentinel behind it)
+    -> its address."""
+    if t is None:
+        return None
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 1 and t.numel() >= C and t.is_contiguous()):
+        raise ValueError("%s must be a contiguous 1-D float32 tensor of at least %d elements" % (name, C))
+    return t.data_ptr()
+
+
+def _levels(xs):
+    xs = list(xs)
+    if not 1 <= len(xs) <= 8:                                                  # SSD_TRAIN_MAX_LEVELS
+        raise ValueError("xs: 1 .. 8 levels")
+    return xs
+
+
+def _column(col, name, shapes):
+    """col is None or holds one dense tensor per level of `shapes` -> the list."""
+    if col is None:
+        return None
+    col = list(col)
+    if len(col) != len(shapes):
+        raise ValueError("%s: one tensor for every one of the %d levels (or None for all of them)" % (name, len(shapes)))
+    for i, (t, shape) in enumerate(zip(col, shapes)):
+        _dense(t, "%s[%d]" % (name, i), shape)
+    return col
+
+
+def conv_out_shape(shape, Cout, stride):
+    """The output shape of a 'same' convolution of an input of `shape` [B,H,W,C] at `stride`: [B,ceil(H/stride),ceil(W/stride),Cout]."""
+    if not (isinstance(stride, int) and stride >= 1):
+        raise ValueError("stride must be a positive integer")
+    return (shape[0], -(-shape[1] // stride), -(-shape[2] // stride), Cout)
+
+
+def _one_gpu(workspace, **tensors):
+    """LAST of the checks, so that the others can be exercised on CPU tensors: every tensor (lists flattened, None skipped) and the
+    caller's workspace, a 1-D uint8 tensor, on ONE GPU -> that device."""
+    if workspace is not None:
+        _dense(workspace, "workspace", (None,), torch.uint8)
+    dev = None
+    for name, v in dict(tensors, workspace=workspace).items():
+        for t in (v if isinstance(v, (list, tuple)) else (v,)):
+            if t is not None:
+                if not t.is_cuda:
+                    raise TypeError("%s must be on a GPU (there is no CPU path)" % name)
+                if dev not in (None, t.device):
+                    raise ValueError("%s is on %s, another argument on %s: one device per call" % (name, t.device, dev))
+                dev = t.device
+    return dev
+
+
+def _run(dev, workspace, need, call):
+    """call(workspace_dev, workspace_bytes, stream) on `dev`; need() -> the planner's bytes, asked only for the cached workspace."""
+    with torch.cuda.device(dev):
+        ws = workspace if workspace is not None else _workspace(dev, need())
+        check(call(ws.data_ptr(), ws.numel(), stream(dev)))
+
+
+# ----------------------------------------------------------------------------- the convolution
+_CONV = {"conv": "ssd_conv_train_", "conv3x3": "ssd_conv3x3_train_", "pointwise": "ssd_pointwise_train_"}
+
+
+def _conv_extra(entry, k, stride, with_up=False):
+    """The arguments that only the general family takes; the other two fix them."""
+    if entry == "conv":
+        return (k, stride)
+    if entry not in _CONV or (k, stride) != ((3, 1) if entry == "conv3x3" else (1, 1)) or with_up:
+        raise ValueError("entry must be 'conv', 'conv3x3' (k = 3, stride 1, no ups) or 'pointwise' (k = 1, stride 1, no ups)")
+    return ()
+
+
+def _conv_need(entry, dims, k, stride, with_up):
+    return getattr(lib(), _CONV[entry] + "workspace_bytes")(*dims, *((k, stride, 1 if with_up else 0) if entry == "conv" else ()))
+
+
+def conv_workspace_bytes(levels, B, Cin, Cout, k=3, stride=1, with_up=False, entry="conv"):
+    """ssd_conv_train_workspace_bytes (entry "conv3x3", "pointwise": that family's planner): levels are (H, W) pairs or [B,H,W,C]
+    tensors of which only H and W are read."""
+    _conv_extra(entry, k, stride, with_up)
+    sizes = [l.shape[1:3] if isinstance(l, torch.Tensor) else l for l in levels]
+    return _conv_need(entry, ((SsdConvLevel * len(sizes))(*[SsdConvLevel(h, w) for h, w in sizes]), len(sizes), B, Cin, Cout), k, stride, with_up)
+
+
+def _conv_args(xs, kernel, stride, entry, with_up=False):
+    """The checks both convolution calls share -> (xs, B, Cin, Cout, k, the family's extra arguments, every level's output shape)."""
+    xs = _levels(xs)
+    k, _, Cin, Cout = _dense(kernel, "kernel", (None,) * 4)
+    if kernel.shape[1] != k:
+        raise ValueError("kernel must be HWIO [k,k,Cin,Cout]")
+    extra = _conv_extra(entry, k, stride, with_up)
+    B = _dense(xs[0], "xs[0]", (None, None, None, Cin))[0]
+    return xs, B, Cin, Cout, k, extra, [conv_out_shape(_dense(x, "xs[%d]" % i, (B, None, None, Cin)), Cout, stride) for i, x in enumerate(xs)]
+
+
+def _conv_levels(xs, dys, outs):
+    lv = (SsdConvLevel * len(xs))()
+    for i, x in enumerate(xs):
+        lv[i].H, lv[i].W = x.shape[1], x.shape[2]
+        lv[i].x = x.data_ptr()
+        lv[i].dy = dys[i].data_ptr() if dys is not None else None
+        lv[i].out = outs[i].data_ptr() if outs is not None else None
+    return lv
+
+
+def conv_forward(xs, kernel, outs, stride=1, bias=None, ups=None, workspace=None, entry="conv"):
+    """ssd_conv_train_forward (entry "conv3x3": ssd_conv3x3_train_forward) of the levels xs [B,H,W,Cin] with ONE kernel HWIO
+    [k,k,Cin,Cout] into outs [B,ceil(H/stride),ceil(W/stride),Cout]; bias [Cout] and ups (one [B,H/2,W/2,Cout] per level) nullable."""
+    if entry == "pointwise":
+        raise ValueError("entry: the pointwise family has no forward of its own ('conv' runs a 1x1 kernel)")
+    xs, B, Cin, Cout, k, extra, shapes = _conv_args(xs, kernel, stride, entry, ups is not None)
+    outs = _column(outs, "outs", shapes)
+    ups = _column(ups, "ups", [(B, x.shape[1] // 2, x.shape[2] // 2, Cout) for x in xs])
+    middle = (_vector(bias, "bias", Cout),)
+    dev = _one_gpu(workspace, xs=xs, kernel=kernel, outs=outs, bias=bias, ups=ups)
+    if entry == "conv":
+        middle += ((ctypes.c_void_p * len(xs))(*[u.data_ptr() for u in ups]) if ups is not None else None,)
+    dims, fn = (_conv_levels(xs, None, outs), len(xs), B, Cin, Cout), getattr(lib(), _CONV[entry] + "forward")
+    _run(dev, workspace, lambda: _conv_need(entry, dims, k, stride, ups is not None), lambda *tail: fn(*dims, *extra, kernel.data_ptr(), *middle, *tail))
+
+
+def conv_backward(xs, kernel, dys, dw, stride=1, dxs=None, dbias=None, workspace=None, entry="conv"):
+    """ssd_conv_train_backward (entry "conv3x3": ssd_conv3x3_train_backward; "pointwise": ssd_pointwise_train_backward, k = 1 with
+    the data gradient and no dbias) from xs, the kernel and dys (the forward's output shapes): dw of the kernel's shape, dxs (for
+    every level or None) of the levels' shapes, dbias [Cout] nullable."""
+    xs, B, Cin, Cout, k, extra, shapes = _conv_args(xs, kernel, stride, entry)
+    dys = _column(dys, "dys", shapes)
+    _dense(dw, "dw", kernel.shape)
+    dxs = _column(dxs, "dxs", [x.shape for x in xs])
+    if entry == "pointwise" and dbias is not None:
+        raise ValueError("dbias: the pointwise family has none")
+    middle = (dw.data_ptr(),) + ((_vector(dbias, "dbias", Cout),) if entry != "pointwise" else ())
+    dev = _one_gpu(workspace, xs=xs, kernel=kernel, dys=dys, dw=dw, dxs=dxs, dbias=dbias)
+    dims, fn = (_conv_levels(xs, dys, dxs), len(xs), B, Cin, Cout), getattr(lib(), _CONV[entry] + "backward")
+    _run(dev, workspace, lambda: _conv_need(entry, dims, k, stride, False), lambda *tail: fn(*dims, *extra, kernel.data_ptr(), *middle, *tail))
+
+
+def fpn_merge_backward(g, base=None, gate=None, same_size=False, out=None):
+    """ssd_fpn_merge_backward: out = base + the 2x2 sums of g [B,2H,2W,C] (same_size: + g [B,H,W,C]), the g terms read as +0 where
+    gate > 0 is false; base None starts at +0.  out may be base (in place).  No autograd."""
+    _need(g, "g")
+    g = g.contiguous()
+    B, H, W, C = g.shape
+    if not same_size:
+        if (H | W) & 1:
+            raise ValueError("g must have even height and width")
+        H, W = H // 2, W // 2
+    for t, name in ((base, "base"), (gate, "gate"), (out, "out")):
+        if t is not None:
+            _need(t, name)
+            if tuple(t.shape) != (B, H, W, C) or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous [B,H,W,C] tensor of the output's shape" % name)
+    if out is None:
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        check(lib().ssd_fpn_merge_backward(base.data_ptr() if base is not None else None, g.data_ptr(),
+                                           gate.data_ptr() if gate is not None else None, B, H, W, C, 1 if same_size else 0,
+                                           out.data_ptr(), stream(g.device)))
+    return out
+
+
+# ----------------------------------------------------------------------------- the depthwise and the first convolution
+def depthwise_forward(x, kernel, out, stride=1):
+    """ssd_depthwise_train_forward: x [B,H,W,C], kernel [3,3,C,1] -> out [B,ceil(H/stride),ceil(W/stride),C]."""
+    B, H, W, C = _dense(x, "x", (None,) * 4)
+    _dense(kernel, "kernel", (3, 3, C, 1))
+    _dense(out, "out", conv_out_shape(x.shape, C, stride))
+    dev = _one_gpu(None, x=x, kernel=kernel, out=out)
+    with torch.cuda.device(dev):
+        check(lib().ssd_depthwise_train_forward(x.data_ptr(), B, H, W, C, kernel.data_ptr(), stride, out.data_ptr(), stream(dev)))
+
+
+def depthwise_workspace_bytes(x, stride):
+    """ssd_depthwise_train_workspace_bytes: x is the input or its shape (B, H, W, C)."""
+    return lib().ssd_depthwise_train_workspace_bytes(*getattr(x, "shape", x), stride)
+
+
+def depthwise_backward(x, kernel, dy, dw, stride=1, dx=None, workspace=None):
+    """ssd_depthwise_train_backward from x, the kernel and dy (the forward's output shape): dw of the kernel's shape, dx of x's
+    shape or None."""
+    B, H, W, C = _dense(x, "x", (None,) * 4)
+    _dense(kernel, "kernel", (3, 3, C, 1))
+    _dense(dy, "dy", conv_out_shape(x.shape, C, stride))
+    _dense(dw, "dw", (3, 3, C, 1))
+    if dx is not None:
+        _dense(dx, "dx", x.shape)
+    dev = _one_gpu(workspace, x=x, kernel=kernel, dy=dy, dw=dw, dx=dx)
+    L, dxp = lib(), dx.data_ptr() if dx is not None else None
+    _run(dev, workspace, lambda: L.ssd_depthwise_train_workspace_bytes(B, H, W, C, stride),
+         lambda *tail: L.ssd_depthwise_train_backward(x.data_ptr(), dy.data_ptr(), B, H, W, C, kernel.data_ptr(), stride, dxp, dw.data_ptr(), *tail))
+
+
+def first_conv_forward(images, kernel, out):
+    """ssd_first_conv_train_forward: images uint8 [B,H,W,3], kernel [3,3,3,Cout] -> out [B,H/2,W/2,Cout]."""
+    B, H, W, _ = _dense(images, "images", (None, None, None, 3), torch.uint8)
+    Cout = _dense(kernel, "kernel", (3, 3, 3, None))[3]
+    _dense(out, "out", (B, H // 2, W // 2, Cout))
+    dev = _one_gpu(None, images=images, kernel=kernel, out=out)
+    with torch.cuda.device(dev):
+        check(lib().ssd_first_conv_train_forward(images.data_ptr(), B, H, W, kernel.data_ptr(), Cout, out.data_ptr(), stream(dev)))
+
+
+def first_conv_workspace_bytes(images, Cout):
+    """ssd_first_conv_train_workspace_bytes: images is the batch or its (B, H, W)."""
+    return lib().ssd_first_conv_train_workspace_bytes(*tuple(getattr(images, "shape", images))[:3], Cout)
+
+
+def first_conv_backward(images, dy, dw, workspace=None):
+    """ssd_first_conv_train_backward from the images uint8 [B,H,W,3] and dy [B,H/2,W/2,Cout]: dw [3,3,3,Cout]."""
+    B, H, W, _ = _dense(images, "images", (None, None, None, 3), torch.uint8)
+    Cout = _dense(dy, "dy", (B, H // 2, W // 2, None))[3]
+    _dense(dw, "dw", (3, 3, 3, Cout))
+    dev = _one_gpu(workspace, images=images, dy=dy, dw=dw)
+    L = lib()
+    _run(dev, workspace, lambda: L.ssd_first_conv_train_workspace_bytes(B, H, W, Cout),
+         lambda *tail: L.ssd_first_conv_train_backward(images.data_ptr(), dy.data_ptr(), B, H, W, Cout, dw.data_ptr(), *tail))
+
+
+# ----------------------------------------------------------------------------- the batch norm
+def bn_workspace_bytes(rows, C):
+    """ssd_bn_relu_train_workspace_bytes (it sizes both families): rows are row counts or [..., C] tensors."""
+    rows = [r.numel() // C if isinstance(r, torch.Tensor) else r for r in rows]
+    return lib().ssd_bn_relu_train_workspace_bytes((SsdBnLevel * len(rows))(*[SsdBnLevel(r) for r in rows]), len(rows), C)
+
+
+def _bn_call(which, entry, act, scalars, workspace, xs, dys, outs, out_name, **vectors):
+    """Both batch-norm calls: xs, dys, outs [..., C] of equal shape per level, every column of `vectors` (named after ssd_bn_level's
+    fields) None or one per-channel vector per level; <family><which>(levels, n, C[, act], *scalars, workspace, stream)."""
+    if entry not in ("bn_act", "bn_relu") or act not in ACTS or (entry == "bn_relu" and act != "relu"):
+        raise ValueError("entry must be 'bn_act' or 'bn_relu' (act 'relu' only), act 'relu' or 'relu6'")
+    xs = _levels(xs)
+    n, C, shapes = len(xs), xs[0].shape[-1] if isinstance(xs[0], torch.Tensor) and xs[0].dim() else 0, []
+    for i, x in enumerate(xs):
+        if not (C and isinstance(x, torch.Tensor)):
+            raise ValueError("xs[%d] must be a tensor [..., C]" % i)
+        shapes.append(_dense(x, "xs[%d]" % i, (None,) * (x.dim() - 1) + (C,)))
+    dys, outs = _column(dys, "dys", shapes), _column(outs, out_name, shapes)
+    lv = (SsdBnLevel * n)()
+    for i, x in enumerate(xs):
+        lv[i].rows = x.numel() // C
+        lv[i].x, lv[i].dy, lv[i].out = x.data_ptr(), dys[i].data_ptr() if dys is not None else None, outs[i].data_ptr()
+    for name, col in vectors.items():
+        if col is not None:
+            if len(col) != n:
+                raise ValueError("%ss: one vector for every one of the %d levels" % (name, n))
+            for i, t in enumerate(col):
+                setattr(lv[i], name, _vector(t, "%ss[%d]" % (name, i), C))
+    dev = _one_gpu(workspace, xs=xs, dys=dys, **{out_name: outs}, **vectors)
+    fn, acts = getattr(lib(), "ssd_%s_train_%s" % (entry, which)), (ACTS[act],) if entry == "bn_act" else ()
+    _run(dev, workspace, lambda: lib().ssd_bn_relu_train_workspace_bytes(lv, n, C), lambda *tail: fn(lv, n, C, *acts, *scalars, *tail))
+
+
+def bn_forward(xs, outs, gammas, betas, training, epsilon, one_minus_momentum, moving_means=None, moving_variances=None, means=None,
+               vars_=None, invstds=None, act="relu", workspace=None, entry="bn_act"):
+    """ssd_bn_act_train_forward (entry "bn_relu": ssd_bn_relu_train_forward, act "relu") of the levels xs [..., C] into outs; every
+    other argument a list of [C] vectors per level.  training: the batch statistics go to means, vars_ (nullable), invstds and move
+    the moving statistics (nullable as a pair); not training: the inference form on the moving statistics, nothing else written."""
+    _bn_call("forward", entry, act, (1 if training else 0, epsilon, one_minus_momentum), workspace, xs, None, outs, "outs", gamma=gammas, beta=betas,
+             moving_mean=moving_means, moving_variance=moving_variances, mean=means, var=vars_, invstd=invstds)
+
+
+def bn_backward(xs, dys, dxs, gammas, betas, means, invstds, dgammas, dbetas, act="relu", workspace=None, entry="bn_act"):
+    """ssd_bn_act_train_backward (entry "bn_relu": ssd_bn_relu_train_backward, act "relu") from xs, dys and the forward's means and
+    invstds: dxs of the levels' shapes, dgammas and dbetas [C] per level."""
+    _bn_call("backward", entry, act, (), workspace, xs, dys, dxs, "dxs", gamma=gammas, beta=betas, mean=means, invstd=invstds, dgamma=dgammas,
+             dbeta=dbetas)

@@ -1,21 +1,16 @@
 """GPU-side helpers shared by tests/test_gpu_backbone_train.py and tests/test_gpu_train_scale.py: the depthwise and the first
-convolution's backward straight through the C ABI (include/ssd_hip.h, "the TRAIN backbone", "the TRAIN first convolution") on
+convolution's backward (include/ssd_hip.h, "the TRAIN backbone", "the TRAIN first convolution") through ssd.train_calls on
 device tensors, and bit equality on the device."""
-from helpers.head_train_gpu import dev, stream
+from helpers.head_train_gpu import dev, exact_workspace
 
 
 def dw_backward_dev(ssd, cuda, X, Wt, DY, stride, with_dx=True):
     """ssd_depthwise_train_backward on device tensors with a workspace of exactly the size its planner asks for; the outputs are
     pre-filled with NaN.  -> (dx or None, dw) on the device."""
-    L = ssd.lib()
     DX = cuda.full_like(X, float("nan")) if with_dx else None
     DW = cuda.full_like(Wt, float("nan"))
-    b, h, ww, C = X.shape
-    need = L.ssd_depthwise_train_workspace_bytes(b, h, ww, C, stride)
-    assert need > 0
-    ws = cuda.empty(need, dtype=cuda.uint8, device="cuda")
-    ssd._lib.check(L.ssd_depthwise_train_backward(X.data_ptr(), DY.data_ptr(), b, h, ww, C, Wt.data_ptr(), stride,
-                                                  DX.data_ptr() if with_dx else None, DW.data_ptr(), ws.data_ptr(), ws.numel(), stream(cuda)))
+    ws = exact_workspace(cuda, ssd.train_calls.depthwise_workspace_bytes(X, stride))
+    ssd.train_calls.depthwise_backward(X, Wt, DY, DW, stride, DX, workspace=ws)
     return DX, DW
 
 
@@ -25,18 +20,12 @@ def dw_backward_raw(ssd, cuda, x, w, dy, stride, with_dx=True):
     return DX.cpu().numpy() if with_dx else None, DW.cpu().numpy()
 
 
-def fc_backward_dev(ssd, cuda, IMG, DY):
+def fc_backward_dev(ssd, cuda, IMG, DY, fill_ws=None):
     """ssd_first_conv_train_backward on device tensors (IMG uint8 [B,H,W,3], DY [B,H/2,W/2,Cout]) with a workspace of exactly the
-    planner's size; dw is pre-filled with NaN.  -> dw on the device."""
-    L = ssd.lib()
-    B, H, W, _ = IMG.shape
-    Cout = DY.shape[3]
-    DW = cuda.full((3, 3, 3, Cout), float("nan"), device="cuda")
-    need = L.ssd_first_conv_train_workspace_bytes(B, H, W, Cout)
-    assert need > 0
-    ws = cuda.empty(need, dtype=cuda.uint8, device="cuda")
-    ssd._lib.check(L.ssd_first_conv_train_backward(IMG.data_ptr(), DY.data_ptr(), B, H, W, Cout, DW.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                   stream(cuda)))
+    planner's size, pre-filled with `fill_ws` (a byte) when given; dw is pre-filled with NaN.  -> dw on the device."""
+    DW = cuda.full((3, 3, 3, DY.shape[3]), float("nan"), device="cuda")
+    ws = exact_workspace(cuda, ssd.train_calls.first_conv_workspace_bytes(IMG, DY.shape[3]), fill_ws)
+    ssd.train_calls.first_conv_backward(IMG, DY, DW, workspace=ws)
     return DW
 
 

@@ -9,7 +9,7 @@ import pytest
 from helpers import backbone_train_ref as ref
 from helpers import head_train_ref as href
 from helpers.backbone_train_gpu import dw_backward_raw as _dw_backward_raw
-from helpers.head_train_gpu import bn_raw, conv_backward, dev as _dev, same_bits, stream as _stream
+from helpers.head_train_gpu import bn_raw, conv_backward, dev as _dev, same_bits
 from conftest import TINY_PARAMS
 
 pytestmark = pytest.mark.gpu
@@ -242,7 +242,7 @@ def test_refusals_come_before_any_launch(ssd, cuda):
     x, w = cuda.zeros((B, H, W, C), device="cuda"), cuda.zeros((3, 3, C, 1), device="cuda")
     dy1, out, dx, dw = cuda.zeros((B, H, W, C), device="cuda"), full((B, H, W, C)), full((B, H, W, C)), full((3, 3, C, 1))
     ws = cuda.empty(1 << 20, dtype=cuda.uint8, device="cuda")
-    s = _stream(cuda)
+    s = ssd.train_calls.stream(x.device)
 
     def fwd(c=C, stride=1, h=H, ww=W, xp=x.data_ptr()):
         return L.ssd_depthwise_train_forward(xp, B, h, ww, c, w.data_ptr(), stride, out.data_ptr(), s)
@@ -414,17 +414,12 @@ def test_fpn_on_features_without_a_gradient_runs_the_frozen_backbone_sequence(ss
     ds = [_dev(cuda, rng.normal(0, 1, (B, h, w, 256)).astype(f32)) for h, w in [(16, 16), (8, 8), (4, 4), (2, 2), (1, 1)]]
     fpn_train = ssd.fpn_train
     calls = []
-    real_conv, real_pw = fpn_train._conv_backward, fpn_train._pointwise_backward
+    real_conv = fpn_train._conv_backward
 
-    def conv(xs, kernel, dys, stride, want_dx, want_dbias=False):
-        calls.append((kernel.shape[0], stride, bool(want_dx)))
-        return real_conv(xs, kernel, dys, stride, want_dx, want_dbias)
-
-    def pw(*a):
-        calls.append("pointwise")
-        return real_pw(*a)
+    def conv(xs, kernel, dys, stride, want_dx, want_dbias=False, entry="conv"):
+        calls.append("pointwise" if entry == "pointwise" else (kernel.shape[0], stride, bool(want_dx)))
+        return real_conv(xs, kernel, dys, stride, want_dx, want_dbias, entry)
     monkeypatch.setattr(fpn_train, "_conv_backward", conv)
-    monkeypatch.setattr(fpn_train, "_pointwise_backward", pw)
     runs = []
     for grad in (False, False, True):
         del calls[:]

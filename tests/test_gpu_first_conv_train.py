@@ -9,7 +9,8 @@ import pytest
 from helpers import backbone_train_ref as bref
 from helpers import first_conv_train_ref as ref
 from helpers import head_train_ref as href
-from helpers.head_train_gpu import dev as _dev, same_bits, stream as _stream
+from helpers.backbone_train_gpu import fc_backward_dev
+from helpers.head_train_gpu import dev as _dev, same_bits
 from conftest import TINY_PARAMS
 
 pytestmark = pytest.mark.gpu
@@ -33,19 +34,8 @@ def _images(rng, B, H, W):
 
 
 def _dw_raw(ssd, cuda, images, dy, fill_ws=None):
-    """ssd_first_conv_train_backward straight through the C ABI with a workspace of exactly the size its planner asks for; dw is
-    pre-filled with NaN, the workspace with `fill_ws` (a byte) when given."""
-    L = ssd.lib()
-    B, H, W, _ = images.shape
-    Cout = dy.shape[3]
-    IMG, DY = cuda.from_numpy(images).cuda(), _dev(cuda, dy)
-    DW = cuda.full((3, 3, 3, Cout), float("nan"), device="cuda")
-    need = L.ssd_first_conv_train_workspace_bytes(B, H, W, Cout)
-    assert need > 0
-    ws = cuda.empty(need, dtype=cuda.uint8, device="cuda") if fill_ws is None else cuda.full((need,), fill_ws, dtype=cuda.uint8, device="cuda")
-    ssd._lib.check(L.ssd_first_conv_train_backward(IMG.data_ptr(), DY.data_ptr(), B, H, W, Cout, DW.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                   _stream(cuda)))
-    return DW.cpu().numpy()
+    """helpers.backbone_train_gpu.fc_backward_dev (a workspace of exactly the planner's size, dw pre-filled with NaN) on numpy arrays."""
+    return fc_backward_dev(ssd, cuda, cuda.from_numpy(images).cuda(), _dev(cuda, dy), fill_ws).cpu().numpy()
 
 
 # ----------------------------------------------------------------------------- 1. the forward
@@ -95,8 +85,7 @@ def test_weight_gradient_is_exact_on_integer_dy(ssd, cuda, Cout, B):
 def test_weight_gradient_is_exact_over_two_slabs(ssd, cuda):
     """B = 2 on 32 x 32 with 32 channels: R = 512 output rows, rpp = 32 row lanes, two slabs of 256 rows."""
     assert ref.slab_plan(512, 32) == (32, 256, 2)
-    L = ssd.lib()
-    assert L.ssd_first_conv_train_workspace_bytes(2, 32, 32, 32) == 2 * 27 * 32 * 8
+    assert ssd.train_calls.first_conv_workspace_bytes((2, 32, 32), 32) == 2 * 27 * 32 * 8
     assert np.abs(_exact_case(ssd, cuda, 2, 32, 32, 32, 5)).max() > 0
 
 
@@ -169,7 +158,7 @@ def test_refusals_come_before_any_launch(ssd, cuda):
     dy = cuda.zeros((B, H // 2, W // 2, C), device="cuda")
     out, dw = cuda.full((B, H // 2, W // 2, C), 7.0, device="cuda"), cuda.full((3, 3, 3, C), 7.0, device="cuda")
     ws = cuda.empty(1 << 20, dtype=cuda.uint8, device="cuda")
-    s = _stream(cuda)
+    s = ssd.train_calls.stream(img.device)
     need = L.ssd_first_conv_train_workspace_bytes(B, H, W, C)
     assert 0 < need <= ws.numel()
 

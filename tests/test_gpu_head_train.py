@@ -113,9 +113,7 @@ def test_weight_gradient_is_exact_with_many_slices_per_level(ssd, cuda, Cin, Cou
     sizes = [(80, 112), (40, 56), (19, 27)]
     xs, dys = _levels(rng, sizes, Cin, True), _levels(rng, sizes, Cout, True)
     w = rng.integers(-2, 3, (3, 3, Cin, Cout)).astype(f32)
-    L, Lv = ssd.lib(), ssd._lib.SsdConvLevel
-    lv = (Lv * 3)(*[Lv(h, ww, None, None, None) for h, ww in sizes])
-    assert L.ssd_conv3x3_train_workspace_bytes(lv, 3, B, Cin, Cout) > 0
+    assert ssd.train_calls.conv_workspace_bytes(sizes, B, Cin, Cout, entry="conv3x3") > 0
     _, dw64, db64 = ref.conv_grads(xs, w, dys)
     _, absum, _ = ref.conv_grads(xs, w, dys, absolute=True)
     assert absum.max() < 2 ** 24 and sum(np.abs(d).sum((0, 1, 2)).max() for d in dys) < 2 ** 24

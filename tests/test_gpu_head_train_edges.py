@@ -79,9 +79,7 @@ def test_batch_norm_at_production_row_counts(ssd, cuda):
     rows, C = [143360, 35840, 8960, 2240, 560], 256
     rpp, slab_rows, n_slabs = ref.slab_plan(rows, C)
     assert (rpp, slab_rows, n_slabs) == (4, 188, 1017) and all(r % slab_rows for r in rows)
-    Lv = ssd._lib.SsdBnLevel
-    lv = (Lv * 5)(*[Lv(r, *([None] * 12)) for r in rows])
-    assert ssd.lib().ssd_bn_relu_train_workspace_bytes(lv, 5, C) == ref.al256(1017 * 2 * 256 * 8)
+    assert ssd.train_calls.bn_workspace_bytes(rows, C) == ref.al256(1017 * 2 * 256 * 8)
     _check_bn(ssd, cuda, "production", *_bn_inputs(np.random.default_rng(1), rows, C))
 
 

@@ -20,7 +20,7 @@ from helpers import fpn_train_ref as fref
 from helpers import head_train_ref as href
 from helpers import train_scale_cases as cases
 from helpers.backbone_train_gpu import dw_backward_dev, dw_backward_raw, fc_backward_dev, frames_same_bits, same_bits_dev
-from helpers.head_train_gpu import bn_raw, conv_backward, conv_backward_raw, dev, same_bits, stream, ulps
+from helpers.head_train_gpu import bn_raw, conv_backward, conv_backward_raw, dev, same_bits, ulps
 
 pytestmark = pytest.mark.gpu
 
@@ -248,7 +248,7 @@ def test_depthwise_forward_and_backward_past_4_gib(ssd, cuda, oracle_ops, case):
     X = xs[idv]
     assert X.numel() * 4 > 2 ** 32
     OUT = cuda.full((B, oh, ow, C), NAN, device="cuda")
-    ssd._lib.check(ssd.lib().ssd_depthwise_train_forward(X.data_ptr(), B, H, W, C, ks.data_ptr(), stride, OUT.data_ptr(), stream(cuda)))
+    ssd.train_calls.depthwise_forward(X, ks, OUT, stride)
     bad = frames_same_bits(cuda, OUT, sy, idv)
     assert bad is None, "out differs from its small frame in frames %d .. (of %d)" % (bad, B)
     del OUT
