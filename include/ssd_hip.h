@@ -143,6 +143,11 @@ int ssd_get_precision(ssd_handle *h);
  *   "first_conv_px"   1 | 0: the first convolution of RESIZED frames (any size that is not the network's own) on the
  *                     lane-per-pixel kernel / on the thread-per-4-channels kernel of rounds 1-5                (1)
  *   "debug_sync"      0 | 1: announce every op on stderr, run it alone, wait for it, print its time           (0)
+ *   "logits_screen"   -1 auto | 0: the class logits as one dense launch | 1: screen + fill (an upper bound of every logit on the
+ *                     f16 matrix pipe marks the octets the score filter cannot exclude, those are computed exactly; F32 only,
+ *                     auto: from 32 768 rows on).  Detections are bit-identical; "class_predictions" is made whole by the dense
+ *                     launch at its first read behind a screened forward (a caller that reads it every time sets 0) | 2: as 1
+ *                     with the tensor pre-filled with 0xff bytes, for tests that read "class_logits_filled"     (-1)
  * (Rounds 1-4 carried more switches -- schedule experiments that measured equal or slower: tower_group, head_serial,
  *  side_priority, level_split, fpn_p6_first, lat_one, dwpw_lat, graph, staggered sub-batch plans.  They are out of the library;
  *  scripts/experiments/README.md has what each measured and the commit that holds its source.)

@@ -18,7 +18,7 @@ static Options g_opts;                 // process-wide values (ssd_set_option wi
 static std::mutex g_opts_mu;
 static const char *const OPT_NAMES[OPT_COUNT] = {"streams", "h2d_chunks", "front_fuse", "fuse_dw", "backbone_split", "event_fence", "plan_cache_mb",
                                                  "igemm_tile", "igemm16", "igemm_96", "igemm_lat", "igemm_deep64", "lateral_split", "fpn_group", "fpn_p7_group",
-                                                 "fpn_early_lat", "nsub", "nms_fast_max", "first_conv_px", "debug_sync"};
+                                                 "fpn_early_lat", "nsub", "nms_fast_max", "first_conv_px", "debug_sync", "logits_screen"};
 int ssd_opt_index(const char *key)
 {
     for (int i = 0; i < OPT_COUNT; ++i)
@@ -560,6 +560,10 @@ extern "C" int ssd_get_tensor(ssd_handle *h, const char *name, float *dst, int64
         const Retained &r = it->second;
         const long long rows = (long long)r.B * r.H * r.W;
         if (cap < done + rows * r.C) return ssd_fail(SSD_ERR_INVALID, "ssd_get_tensor: destination too small");
+        if (pl->screened && !pl->logits_whole && !strcmp(name, "class_predictions")) {
+            SSDCHK(materialize_logits(h, *pl, nullptr));          // (the device is idle: any stream will do)
+            HIPCHK(hipDeviceSynchronize());
+        }
         std::vector<float> tmp((size_t)rows * r.Cp);
         HIPCHK(hipMemcpy(tmp.data(), r.dev, tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (long long q = 0; q < rows; ++q)
@@ -596,6 +600,9 @@ extern "C" int ssd_get_tensor_dev(ssd_handle *h, const char *name, float *dst_de
         const Retained &r = it->second;
         const long long rows = (long long)r.B * r.H * r.W;
         if (cap < done + rows * r.C) return ssd_fail(SSD_ERR_INVALID, "ssd_get_tensor_dev: destination too small");
+        // a screened forward left exact logits at the marked octets only: the dense launch of the same plan, on `stream`
+        // like the copy below (ordered behind the forward as that copy is: by the caller's stream)
+        if (!strcmp(name, "class_predictions")) SSDCHK(materialize_logits(h, *pl, (hipStream_t)stream));
         if (r.permuted) HIPCHK(launch_permute_channels(r.dev, rows, r.C, r.Cp, r.fmt ? 2 : 0, dst_dev + done, (hipStream_t)stream, r.fmt ? 0 : r.split));
         else HIPCHK(hipMemcpyAsync(dst_dev + done, r.dev, (size_t)rows * r.C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
         done += rows * r.C;

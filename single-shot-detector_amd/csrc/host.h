@@ -59,6 +59,8 @@ enum SsdOpt {
     OPT_NMS_FAST_MAX,       // -1 default | n >= 0: candidate lists up to n run in one wave's registers
     OPT_FIRST_CONV_PX,      // 1 (default) | 0: resized frames' first convolution on the lane-per-pixel kernel (elementwise.hip K1d) / on K1, K1c
     OPT_DEBUG_SYNC,         // 0 | 1: announce every op, run it alone, wait for it (fault localisation)
+    OPT_LOGITS_SCREEN,      // -1 auto | 0: the class logits as one dense launch | 1: screen + fill (logit_screen.hip; exact fp32 mode only)
+                            // | 2: as 1, and the logits tensor is filled with 0xff bytes first (tests read what the fill wrote)
     OPT_COUNT
 };
 #define SSD_OPT_UNSET INT_MIN
@@ -119,6 +121,9 @@ struct ConvW {
     float *wt16w = nullptr;    // wide outputs whose width 256 does not divide (480 class logits): the S16 rows again,
     int CoutPad16 = 0;         //   padded to CoutPad16 = a multiple of 256 rows per tap for the 256x256-tile kernel
     float scale16 = 1.0f;      // 2^-s
+    unsigned short *wscr = nullptr;   // the class logits' screen (logit_screen.hip): [taps][ceil(CoutP / 128) * 256][CinP] f16, per 256-row tile
+                                      //   128 rows max(w, 0) rounded up, 128 rows max(-w, 0) rounded down; scst [CoutP]: the bound's constant term
+    float *scst = nullptr;
     int CinP = 0, CoutP = 0, CoutPad = 0, taps = 1, tile = IGEMM_128x128;
     int Cin_l = 0, Cout_l = 0;
 };
@@ -133,6 +138,8 @@ struct DwW {
 // Conv2d_1..4 as one depthwise+pointwise launch: 751.9 -> 760.6 img/s at B=32 (masks 0x3 / 0x5 / 0x7 / 0xf:
 // 754.6 / 757.2 / 760.2 / 760.6); from Conv2d_5 on (K >= 256) the two-kernel pair is faster.
 #define SSD_FUSE_DW_DEFAULT 0xfu
+// screen + fill of the class logits from this many rows (positions x images over the five levels) on; below, the dense launch
+#define SSD_SCREEN_MIN_ROWS 32768
 #define SSD_FUSE_SHUFFLE_DEFAULT true    // ShuffleNet B=64 640x640: depthwise + pointwise 4.19 -> 3.76 ms per step
 #ifdef SSD_DIAG                      // libssd_hip_diag.so (scripts/): tile override and phase-stamp buffer of ssd_bench_conv
 extern int g_force_tile;
@@ -151,7 +158,7 @@ BnHost permute_bn(const float *mean, const float *sf, const float *beta, const s
 void conv_geometry(const struct ssd_handle *h, int taps, int CinP, int CoutP, int Cin_l, int Cout_l, ConvW &cw);
 // w HWIO [k,k,Cin_l,Cout_l] -> wt [taps][CoutPad][CinP] (+ the lane-order and split-fp16 forms)
 int pack_conv(const struct ssd_handle *h, DevPool &pool, const float *w, int k, int Cin_l, int Cout_l, const std::vector<int> &inmap,
-              const std::vector<int> &outmap, ConvW &cw);
+              const std::vector<int> &outmap, ConvW &cw, const float *screen_bias = nullptr /* [Cout_l] in outmap order: also pack wscr / scst */);
 int upload_bn(DevPool &pool, const BnHost &b, ConvW &cw);
 // permuted rows [9 or 27][d.Cp] + batch norm -> d.w / mean / sf / beta (empty vectors skipped), and behind nine taps pack_dw
 int upload_dw(DevPool &pool, const std::vector<float> &w, const BnHost &b, DwW &d);
@@ -227,6 +234,11 @@ struct Plan {
     hipStream_t s_bb[2] = {nullptr, nullptr};   // Op::stream 2, 3 (fpn p6 -> p7; the batch-1 lateral chain); process-wide, not owned
     hipEvent_t ev_join = nullptr, ev_begin = nullptr;
     bool need_begin = false;            // some chain starts on an internal stream without a dependency: it waits for ev_begin
+    // A plan whose class logits are screened + filled holds exact logits at the marked octets only.  The first read of
+    // "class_predictions" behind such a forward runs `logits_dense` (the dense launch of the same plan, on the class tower's
+    // still-resident last output -- nothing of the plan reuses that buffer) and the tensor is whole and bit-identical.
+    bool screened = false, logits_whole = true;
+    Op logits_dense;
 };
 
 // What a forward takes from the SOURCE frames (resize_keeping_aspect_ratio, pipeline.py:138-194; model.py:67-68): launch arguments
@@ -314,5 +326,6 @@ int select_plans(ssd_handle *h, int B, int H, int W);   // h->cur = the set of t
 int select_plans_net(ssd_handle *h, int B, int netH, int netW, int ident, long long max_src_bytes);
 int trim_plan_cache(ssd_handle *h, const PlanSet *keep);
 size_t plan_cache_limit_bytes(const ssd_handle *h);
+int materialize_logits(ssd_handle *h, Plan &pl, hipStream_t s);      // no-op unless pl.screened && !pl.logits_whole
 int enqueue_forward(ssd_handle *h, const uint8_t *images_dev, float *boxes_dev, int32_t *labels_dev, float *scores_dev,
                     int32_t *num_boxes_dev, long long out_stride, hipStream_t s);

@@ -922,6 +922,16 @@ static int heads(Builder &b, const Backbone &bb, const Fpn &f)
     // dead once the two final head convolutions are done -- and the post-processing starts behind both of them (ev_join) -- so the
     // NMS candidate keys [B][C][N] u64, 46 of the workspace's 50 MB per frame and the one part of it with no state between
     // forwards, take their place (when they fit: up to 85 classes).
+    // The class logits as screen + fill (logit_screen.hip) instead of the dense launch: exact fp32 mode, a bitmap the
+    // post-processing can read (whole octets), and enough rows that three more launches cost less than the dense one saves --
+    // option logits_screen = 0 / 1 pins it.  Such a plan keeps the class tower's last output until the next forward (the dense
+    // launch may still be asked for: materialize_logits), so the NMS keys do not move into the towers' block.
+    long long rows_total = 0;
+    for (int l = 0; l < 5; ++l) rows_total += (long long)B * py.h[l] * py.w[l];
+    const int scr_opt = ssd_opt(h, OPT_LOGITS_SCREEN, -1);
+    const bool screen = !b.X16 && scr_opt != 0 && ((long long)N * C) % 8 == 0 && (A * C) % 8 == 0 && A * C <= 8 * SCREEN_MAX_OCT &&
+                        h->final_[1].wscr && h->final_[1].scst && h->final_[1].CinP == 256 && h->final_[1].CoutP == A * C &&
+                        (scr_opt > 0 || rows_total >= SSD_SCREEN_MIN_ROWS);
     float *TAB[2][2];
     unsigned char *keys_home = nullptr;
     {
@@ -934,7 +944,7 @@ static int heads(Builder &b, const Backbone &bb, const Fpn &f)
         }
         for (int t = 0; t < 2; ++t)
             for (int k = 0; k < 2; ++k) TAB[t][k] = (float *)(tb + (size_t)(2 * t + k) * slot);
-        if (post_keys_bytes(B, (int)N, C) <= tb_bytes) keys_home = tb;
+        if (post_keys_bytes(B, (int)N, C) <= tb_bytes && !screen) keys_home = tb;
     }
     void *ws;
     const size_t wsb = post_workspace_bytes(B, (int)N, C, h->cfg.max_boxes_per_class, keys_home == nullptr);
@@ -981,6 +991,56 @@ static int heads(Builder &b, const Backbone &bb, const Fpn &f)
         bool marked = false;
         Op fop = make_conv_op(h, h->final_[t], io, B, 1, 1, SSD_ACT_NONE, lv, false, can_mark ? p.scan_bits : nullptr,
                               conservative_logit_bound(h->cfg.score_threshold), &marked);
+        if (t == 1 && screen) {
+            // the dense launch without the bitmap: what a read of "class_predictions" behind a screened forward runs
+            pl.logits_dense = make_conv_op(h, h->final_[t], io, B, 1, 1, SSD_ACT_NONE, lv, false);
+            pl.screened = true;
+            ScreenArgs sa;
+            memset(&sa, 0, sizeof(sa));
+            const ConvW &fc = h->final_[t];
+            sa.x = in;
+            sa.x16 = (unsigned short *)TAB[1][cur];         // the tower's other buffer: free behind its last layer
+            sa.w16 = fc.wscr; sa.wt = fc.wt; sa.bias = fc.bias; sa.cst = fc.scst;
+            sa.logits = logits; sa.bits = p.scan_bits;
+            SSDCHK(pl.pool.alloc((void **)&sa.counts, SCREEN_MAX_OCT * sizeof(int)));
+            SSDCHK(pl.pool.alloc((void **)&sa.lists, (size_t)(A * C / 8) * (size_t)rows_total * sizeof(int)));
+            HIPCHK(hipMemset(sa.counts, 0, SCREEN_MAX_OCT * sizeof(int)));
+            sa.lo = conservative_logit_bound(h->cfg.score_threshold);
+            sa.B = B; sa.Cin = fc.CinP; sa.Cout = fc.CoutP; sa.CoutPad = fc.CoutPad; sa.NT = (fc.CoutP + 127) / 128;
+            sa.nlevels = 5;
+            sa.out_rstride = A * C; sa.out_bstride = N * C;
+            sa.x_elems = py.total;
+            int rows = 0, tiles = 0;
+            for (int l = 0; l < 5; ++l) {
+                ScreenLevel &L = sa.lv[l];
+                L.H = py.h[l]; L.W = py.w[l]; L.P = L.H * L.W; L.M = B * L.P;
+                L.row_begin = rows; L.tile_begin = tiles;
+                L.in_off = py.off[l]; L.out_off = aoff[l] * C;
+                rows += L.M;
+                tiles += (L.M + 255) / 256;
+            }
+            sa.rows_total = rows; sa.tiles_m = tiles;
+            // booked under `postprocess` (the screen is the first half of the score filter): no kernel selector of bench.py or of
+            // the tests depends on that class
+            Op o;
+            o.cls = 4; o.flops = 0;
+            if (scr_opt == 2) {
+                const size_t lbytes = (size_t)B * N * C * sizeof(float);
+                o.bytes = (double)lbytes;
+                o.run = [logits, lbytes](hipStream_t s) { return hipMemsetAsync(logits, 0xff, lbytes, s); };
+                tower_ops[t].push_back(o);
+            }
+            o.bytes = (double)py.total * 6.0;
+            o.run = [sa](hipStream_t s) { return launch_logit_convert(sa, s); };
+            tower_ops[t].push_back(o);
+            o.bytes = (double)py.total * 2.0 + (double)fc.taps * sa.NT * 256 * fc.CinP * 2.0;
+            o.run = [sa](hipStream_t s) { return launch_logit_screen(sa, s); };
+            tower_ops[t].push_back(o);
+            o.bytes = (double)B * N * C / 64.0;
+            o.run = [sa](hipStream_t s) { return launch_logit_fill(sa, s); };
+            tower_ops[t].push_back(o);
+            continue;
+        }
         if (t == 1) all_marked = all_marked && marked;
         tower_ops[t].push_back(fop);
     }
@@ -988,14 +1048,16 @@ static int heads(Builder &b, const Backbone &bb, const Fpn &f)
     // enqueue order interleaved so the hardware queues stay fed.  The first box-tower layer (main) needs p4, p5 from the
     // second stream and p6, p7 from the third; the first class-tower layer (second stream) needs p3 from the main stream
     // (and p6, p7).  The box head (24 of 32 columns) runs beside the class logits.
-    for (size_t i = 0; i < tower_ops[0].size(); ++i)
+    for (size_t i = 0; i < std::max(tower_ops[0].size(), tower_ops[1].size()); ++i)
         for (int t = 1; t >= 0; --t) {
+            if (i >= tower_ops[t].size()) continue;
             std::vector<int> deps;
             if (i == 0) { deps.push_back(t == 0 ? f.id_p4 : f.id_p3); deps.push_back(f.id_p7); }
             b.push(tower_ops[t][i], t, deps);
         }
     pl.retained["encoded_boxes"] = Retained{codes, B, 1, (int)N, 4, 4, false};
     pl.retained["class_predictions"] = Retained{logits, B, 1, (int)N, C, C, false};
+    pl.retained["class_logits_filled"] = Retained{logits, B, 1, (int)N, C, C, false};       // the same memory, never made whole (tests)
     return SSD_OK;
 }
 
@@ -1020,6 +1082,15 @@ static int build_plan(ssd_handle *h, Plan &pl, int B, int H, int W, bool ident, 
     for (const Op &op : pl.ops)
         for (int d : op.deps)
             if (!pl.ops[d].done) HIPCHK(hipEventCreateWithFlags(&pl.ops[d].done, ssd_sync_event_flags(h)));
+    return SSD_OK;
+}
+
+int materialize_logits(ssd_handle *h, Plan &pl, hipStream_t s)
+{
+    (void)h;
+    if (!pl.screened || pl.logits_whole) return SSD_OK;
+    HIPCHK(pl.logits_dense.run(s));
+    pl.logits_whole = true;
     return SSD_OK;
 }
 
@@ -1264,6 +1335,7 @@ int enqueue_forward(ssd_handle *h, const uint8_t *images_dev, float *boxes_dev, 
         // (k > 0: the previous plan's side streams were joined into `s` before its post-processing, and this plan's chains on
         //  them start behind ev_begin or behind an op of this plan: the shared streams need no further ordering)
         if (pl.need_begin) HIPCHK(hipEventRecord(pl.ev_begin, s));
+        if (pl.screened) pl.logits_whole = false;
         // option streams = 1: every op on the caller's stream, in plan order (a valid order: an op's dependencies precede it) --
         // a measurement aid that shows what the kernels cost without each other beside them
         const bool single = ssd_opt(h, OPT_STREAMS, 0) == 1;

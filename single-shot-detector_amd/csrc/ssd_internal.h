@@ -131,6 +131,40 @@ hipError_t launch_igemm_lat(int tile, const IgemmArgs &a, int total_tiles_m, hip
 #define IGEMM16_TILE 100
 hipError_t launch_igemm16(const IgemmArgs &a, int total_tiles_m, hipStream_t s);
 
+// logit_screen.hip: the class logits as screen (an upper bound of every logit on the f16 matrix pipe, marking PostArgs::scan_bits)
+// + fill (the marked octets exactly), instead of the dense bias-form launch -------------------------------------------------
+#define SCREEN_MAX_LEVELS 5
+#define SCREEN_MAX_OCT 128             // column octets: 6 * num_classes / 8
+struct ScreenLevel {
+    int H, W, P, M;        // spatial size (3x3, stride 1, pad 1: input = output), P = H*W, M = B*P rows
+    int row_begin;         // first row of this level in the launch's row numbering (levels concatenated)
+    int tile_begin;        // first 256-row tile of this level
+    long long in_off;      // element offset of the level's [B,H,W,Cin] tensor in x and in x16
+    long long out_off;     // float offset of (image 0, position 0) in the logits [B][N][C]
+};
+struct ScreenArgs {
+    const float *x;                // the class tower's last output, fp32 rows in physical channel order
+    unsigned short *x16;           // the same elements as f16 rounded up (written by the convert launch)
+    const unsigned short *w16;     // [9][NT * 256][Cin] f16: per 256-row tile 128 rows Wp, 128 rows Wn (ConvW::wscr)
+    const float *wt;               // [9][CoutPad][Cin] the exact kernel
+    const float *bias;             // [Cout]
+    const float *cst;              // [Cout] the bound's constant term (ConvW::scst)
+    float *logits;                 // [B][N][C]
+    unsigned *bits;                // PostArgs::scan_bits
+    int *counts;                   // [Cout / 8] marked rows per column octet
+    int *lists;                    // [Cout / 8][rows_total] their row numbers
+    float lo;                      // conservative logit bound
+    int B, Cin, Cout, CoutPad, NT; // NT = ceil(Cout / 128) column tiles
+    int nlevels, tiles_m, rows_total;
+    int out_rstride;               // floats between positions of the logits = Cout
+    long long out_bstride;         // floats between images = N * C
+    long long x_elems;             // elements of x over all levels
+    ScreenLevel lv[SCREEN_MAX_LEVELS];
+};
+hipError_t launch_logit_convert(const ScreenArgs &a, hipStream_t s);
+hipError_t launch_logit_screen(const ScreenArgs &a, hipStream_t s);
+hipError_t launch_logit_fill(const ScreenArgs &a, hipStream_t s);       // compaction + fill
+
 // depthwise -> pointwise, K streamed in 32-channel slices, LDS-DMA staged input patches (dwpw_stream.hip) ----------
 struct DwPwSArgs {
     const float *in;                       // [B,H,W,K] depthwise input, physical channel order, K % 32 == 0

@@ -96,8 +96,56 @@ void conv_geometry(const ssd_handle *h, int taps, int CinP, int CoutP, int Cin_l
 }
 
 // w: HWIO [k,k,Cin_l,Cout_l] -> wt [taps][CoutPad][CinP]
+// The screen's operands (logit_screen.hip) from the packed kernel t [taps][CoutPad][CinP]: Wp = max(w, 0) rounded UP to
+// f16, Wn = max(-w, 0) rounded DOWN, neither ever subnormal (a positive value below 2^-14 becomes 2^-14 in Wp and 0 in Wn: the
+// bound then holds whether or not the matrix pipe flushes subnormal inputs); a NaN weight goes to Wp, where it marks.
+// cst[n] >= bias + 2^-14 * sum Wn + 2^-20 |bias| (the input plane's round-up to a normal half, the epilogue's one rounding).
+static int pack_screen(DevPool &pool, const std::vector<float> &t, const float *bias, ConvW &cw)
+{
+    const int NT = (cw.CoutP + 127) / 128, rows = NT * 256;
+    std::vector<uint16_t> s((size_t)cw.taps * rows * cw.CinP, 0);
+    std::vector<double> wn_sum(cw.CoutP, 0.0);
+    auto bits_of = [](_Float16 v) { uint16_t b; memcpy(&b, &v, 2); return b; };
+    for (int tap = 0; tap < cw.taps; ++tap)
+        for (int n = 0; n < cw.CoutP; ++n) {
+            const float *src = &t[((size_t)tap * cw.CoutPad + n) * cw.CinP];
+            uint16_t *dp = &s[((size_t)tap * rows + (n / 128) * 256 + n % 128) * cw.CinP], *dn = dp + (size_t)128 * cw.CinP;
+            for (int p = 0; p < cw.CinP; ++p) {
+                const float v = src[p];
+                if (v != v) { dp[p] = 0x7e00; continue; }
+                if (v > 0.0f) {
+                    const _Float16 hh = (_Float16)v;
+                    uint16_t b = bits_of(hh);
+                    if ((float)hh < v) b += 1;
+                    dp[p] = b < 0x0400 ? 0x0400 : b;
+                } else if (v < 0.0f) {
+                    const float m = -v;
+                    const _Float16 hh = (_Float16)m;
+                    uint16_t b = bits_of(hh);
+                    if ((float)hh > m) b -= 1;
+                    if (b >= 0x7c00) b = 0x7bff;
+                    if (b < 0x0400) b = 0;
+                    dn[p] = b;
+                    _Float16 back;
+                    memcpy(&back, &b, 2);
+                    wn_sum[n] += (double)(float)back;
+                }
+            }
+        }
+    std::vector<float> cst(cw.CoutP);
+    for (int n = 0; n < cw.CoutP; ++n) {
+        const double b = bias[n];
+        const double c = b + ldexp(wn_sum[n] * (1.0 + 1e-9), -14) + ldexp(fabs(b), -20) + 1e-30;
+        float f = (float)c;
+        if ((double)f < c) f = nextafterf(f, INFINITY);
+        cst[n] = f;
+    }
+    SSDCHK(pool.upload(&cw.wscr, s));
+    return pool.upload(&cw.scst, cst);
+}
+
 int pack_conv(const ssd_handle *h, DevPool &pool, const float *w, int k, int Cin_l, int Cout_l, const std::vector<int> &inmap,
-                     const std::vector<int> &outmap, ConvW &cw)
+                     const std::vector<int> &outmap, ConvW &cw, const float *screen_bias)
 {
     conv_geometry(h, k * k, (int)inmap.size(), (int)outmap.size(), Cin_l, Cout_l, cw);
     std::vector<float> t((size_t)cw.taps * cw.CoutPad * cw.CinP, 0.0f);
@@ -109,6 +157,7 @@ int pack_conv(const ssd_handle *h, DevPool &pool, const float *w, int k, int Cin
                 if (inmap[p] >= 0) dst[p] = w[((size_t)tap * Cin_l + inmap[p]) * Cout_l + outmap[n]];
         }
     SSDCHK(pool.upload(&cw.wt, t));
+    if (screen_bias && cw.taps == 9 && cw.CinP % 64 == 0 && cw.CoutP % 8 == 0 && cw.CoutP == Cout_l) SSDCHK(pack_screen(pool, t, screen_bias, cw));
     {   // igemm_lat.hip: per (tap, 16-channel tile, K-step of 32 channels) two 1-KB pieces in MFMA lane order -- lane
         // (i = l & 15, kk = l >> 4) holds the weights of channel row i for k = 4 t + kk, t = 4 hf .. 4 hf + 3
         const int KC = cw.CinP / 32, NT = cw.CoutPad / 16;
@@ -224,13 +273,13 @@ static int get_bn(ssd_handle *h, const std::string &scope, int C, const std::vec
 // dense conv + optional BN, standard physical maps on both sides
 // (in_split > 0: the input is a ShuffleNet stage output in two-part rows, in_split channels per half)
 static int load_conv(ssd_handle *h, const std::string &wname, const std::string &bnscope, int k, int Cin, int Cout,
-                     ConvW &cw, bool out_identity = false, int in_split = 0)
+                     ConvW &cw, bool out_identity = false, int in_split = 0, const float *screen_bias = nullptr)
 {
     const Tensor *w = getvar(h, wname, {k, k, Cin, Cout});
     if (!w) return SSD_ERR_WEIGHT;
     std::vector<int> inmap = in_split > 0 ? twopart_map(in_split, round_up(in_split, 32)) : phys_map(Cin, round_up(Cin, 32));
     std::vector<int> outmap = out_identity ? ident_map(Cout, Cout) : phys_map(Cout, round_up(Cout, 32));
-    SSDCHK(pack_conv(h, h->wpool, w->data.data(), k, Cin, Cout, inmap, outmap, cw));
+    SSDCHK(pack_conv(h, h->wpool, w->data.data(), k, Cin, Cout, inmap, outmap, cw, out_identity ? screen_bias : nullptr));
     if (!bnscope.empty()) {
         BnHost b;
         SSDCHK(get_bn(h, bnscope, Cout, outmap, b));
@@ -422,9 +471,9 @@ static int finalize_fpn_heads(ssd_handle *h)
         const int Cout = t == 0 ? 4 * A : C * A;
         const std::string scope = std::string(nets[t]) + (t == 0 ? "/encoded_boxes" : "/logits");
         ConvW &cw = h->final_[t];
-        SSDCHK(load_conv(h, scope + "/kernel", "", 3, 256, Cout, cw, /*out_identity=*/true));
         const Tensor *bias = getvar(h, scope + "/bias", {Cout});
         if (!bias) return SSD_ERR_WEIGHT;
+        SSDCHK(load_conv(h, scope + "/kernel", "", 3, 256, Cout, cw, /*out_identity=*/true, 0, t == 1 ? bias->data.data() : nullptr));
         std::vector<float> bpad(bias->data);
         bpad.resize((size_t)round_up(Cout, 4), 0.0f);     // the epilogue reads parameters 4 at a time
         SSDCHK(h->wpool.upload(&cw.bias, bpad));

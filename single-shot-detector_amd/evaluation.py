@@ -53,6 +53,7 @@ class _Run:
     def __init__(self, engine):
         self.engine = engine
         self.anchors = {}
+        engine.set_option("logits_screen", 0)       # the loss reads every logit: the dense launch, not screen + fill + dense on demand
 
     def anchors_for(self, shape):
         a = self.anchors.get(shape)

@@ -1009,6 +1009,7 @@ class RetinaNetBoxPredictor:
         self.num_classes = engine.params["num_classes"] if num_classes is None else num_classes
         if self.num_classes != engine.params["num_classes"]:
             raise ValueError("num_classes differs from the engine's configuration")
+        engine.set_option("logits_screen", 0)       # every call hands out all logits: the dense launch, not screen + fill
 
     def __call__(self, image_features):
         B = image_features[0].shape[0]
