@@ -712,7 +712,7 @@ int ssd_fpn_merge_backward(const float *base_dev, const float *g_dev, const floa
  * Conventions as for the TRAIN head: the caller's device pointers, logical NHWC fp32, TF-layout kernels in DEVICE memory, the
  * caller's workspace, SSD_ERR_INVALID before any HIP call, enqueue only, no atomics: two calls give the same bits.  Every existing
  * entry point keeps its arguments, its refusals and its bits (ssd_conv_train_backward still refuses dx with k = 1).  Not here:
- * ShuffleNet's split and shuffle, F16X3, double backward.
+ * F16X3, double backward; ShuffleNet's split and shuffle are the block "the TRAIN ShuffleNet" below.
  *
  * The depthwise calls: x [B,H,W,C], w_dev [3,3,C,1] (= [9][C]), out / dy [B,OH,OW,C] with OH = ceil(H / stride), OW likewise, and
  * pad_beg = p = max((OH - 1) * stride + 3 - H, 0) / 2 (TF 'SAME': 1 for stride 1; for stride 2, 0 on even and 1 on odd sizes).
@@ -793,12 +793,93 @@ int ssd_bn_act_train_backward(const ssd_bn_level *levels, int32_t n_levels, int3
  *     rows are cut into slabs of slab_rows; inside a slab row lane j = (r - slab start) mod rpp adds its rows in ascending order,
  *     the lanes are added in ascending j, the slabs in ascending order.  The partial sums ([slabs][27][Cout] doubles) live in the
  *     workspace, which ssd_first_conv_train_workspace_bytes sizes (0: the sizes would be refused).
- * Not here: a resize in front of the convolution (TRAIN batches arrive at the network's size), ShuffleNet's max pool. */
+ * Not here: a resize in front of the convolution (TRAIN batches arrive at the network's size); ShuffleNet's max pool has its gradient in
+ * the block "the TRAIN ShuffleNet" below. */
 int ssd_first_conv_train_forward(const uint8_t *images_dev, int32_t B, int32_t H, int32_t W, const float *w_dev /* [3,3,3,Cout] */,
                                  int32_t Cout, float *out_dev, void *stream);
 size_t ssd_first_conv_train_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t Cout);
 int ssd_first_conv_train_backward(const uint8_t *images_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t Cout,
                                   float *dw_dev /* [3,3,3,Cout] */, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* ---- the TRAIN ShuffleNet: what ShuffleNet-v2 in TRAIN mode needs beyond the TRAIN backbone (shufflenet_v2.py:9-135) --------------
+ *
+ * ShuffleNet-v2 is Conv1 (the first convolution with 24 channels, batch norm + ReLU), a 3x3 stride-2 max pool, three stages of
+ * units and Conv5.  A unit works on channel halves: 1x1 convolution + batch norm + ReLU, 3x3 depthwise + batch norm WITHOUT an
+ * activation, 1x1 + batch norm + ReLU; between units concat_shuffle_split interleaves the two halves and splits them again, and a
+ * stage closes with a concat.  At depth_multiplier 1.0 the Stage2 halves have 58 channels.  These calls are what the TRAIN blocks
+ * above refuse or lack for it: channel counts that are even but no multiple of 4, the batch norm without an activation, the
+ * shuffle and the concat with their gradients, and the gradient of the max pool (the forward stays ssd_maxpool3x3s2, which only
+ * enqueues).  Conventions are the TRAIN backbone's: the caller's device pointers, logical NHWC fp32, TF-layout kernels in DEVICE
+ * memory, the caller's workspace, SSD_ERR_INVALID with the argument named in ssd_last_error() before any HIP call, enqueue only
+ * (no allocation, no synchronisation, no host round trip, no index table), no atomics: two calls give the same bits.  Every
+ * pointer 16-byte aligned.  The entry points above keep their arguments, their refusals and their bits; these share their
+ * planners and kernels.  ONE thing changes for the older calls too: the batch-norm kernels (ssd_bn_relu_train_*, ssd_bn_act_train_*,
+ * dbias) and the weight gradient of ssd_conv*_train_backward / ssd_pointwise_train_backward now read and write rows whose width is
+ * 2 mod 4 (C = 6, a Cout of 58) 8 bytes at a time where they went element by element -- the same values in the same order, so no
+ * result bit moves, and the 16-byte alignment they already require covers it.  Not here: depth_multiplier 2.0 (Conv5's 2048 channels: the batch norm takes 1024), F16X3, the fusion of a
+ * shuffle or concat into its neighbouring convolutions.
+ *
+ * ssd_sn_depthwise_train_forward / _workspace_bytes / _backward   ssd_depthwise_train_* with C any EVEN number (C <= 1024 for the
+ *   backward; odd C is refused): the same fmaf chains (forward: taps row-major from +0, a tap outside contributing fmaf(0, w, acc);
+ *   dx: the flipped kernel's taps, those without a source skipped) and the same double column sums of dw, the slab rule written for
+ *   G = ceil(C / 4) quads (rpp = 256 / G; C = 58: G = 15, rpp = 17, slab_rows >= 136; the last quad's second pair lies outside the
+ *   tensor).  C % 4 == 0: the old entry points' launches and bits.  C % 4 == 2: the same kernels instantiated for 2 channels per
+ *   lane -- every access is 8 bytes (a row of 58 floats is 232 bytes, so every row start and every channel pair is 8-byte aligned);
+ *   no access falls to 4 bytes.
+ * ssd_sn_pointwise_train_forward / _workspace_bytes / _backward   a 1x1 stride-1 convolution with Cin and Cout any EVEN numbers up
+ *   to 4096, levels as in ssd_conv_train_*.  forward: ssd_conv_train_forward with k = 1 (no bias, no upsample-add), bit-identical
+ *   to ssd_conv2d with k = 1 on the same values.  backward: ssd_pointwise_train_backward -- dx (levels[l].out, for every level or
+ *   for none) ONE fmaf chain per element, co ascending, bit-identical to the CPU oracle's conv2d(dy, w'); dw by the k = 1 slice
+ *   rule of the TRAIN FPN.  Both reduction sides are zero padded to a multiple of 32 by the steps that permute x / dy and pack the
+ *   kernel (element-wise, any width); the weight gradient loads x and dy rows 16 bytes at a time where the width is a multiple of
+ *   4, 8 bytes where it is even.  Cin % 4 == 0: the old calls' launches and bits.
+ * ssd_sn_bn_train_forward / _backward   ssd_bn_act_train_forward / _backward that also take act = SSD_ACT_NONE: forward out = y,
+ *   backward g = dy; the rest of the float32 sequence of the TRAIN head's batch norm is unchanged, and training == 0 is the
+ *   inference form (x - moving_mean) * sf + beta, bit for bit what ssd_finalize folds behind the engine's depthwise layers.
+ *   SSD_ACT_RELU / SSD_ACT_RELU6: the old pair's planner, launches and bits.  ssd_bn_relu_train_workspace_bytes sizes all of them.
+ *   Rows of C % 4 == 2 channels are read and written 8 bytes at a time.
+ *
+ * ssd_sn_shuffle_train   on [rows, D] tensors, rows >= 1, 1 <= D <= 2^20, rows * D < 2^39 (the limits of all four copies).
+ *   transpose == 0   concat_shuffle_split (shufflenet_v2.py:94-115): z[2i] = x[i], z[2i+1] = y[i] (i < D); xo = z[:D], yo = z[D:].
+ *   transpose != 0   its backward: x_dev, y_dev hold the gradients of xo and yo, dz = [x | y], and xo_dev, yo_dev receive those of x
+ *                    and y: xo[i] = dz[2i], yo[i] = dz[2i+1].
+ * ssd_sn_concat_train   out [rows, 2D] = [x | y], the stage's closing tf.concat (shufflenet_v2.py:89);  ssd_sn_split_train its
+ *   backward: dx = g[:, :D], dy = g[:, D:].
+ *   All four are pure copies of 32-bit words: every bit pattern arrives unchanged, NaN payloads and -0 included.  Indices are
+ *   computed arithmetically.  Accesses are 16-byte where D % 4 == 0, 8-byte where D % 2 == 0, else element-wise.  No tensor read
+ *   may overlap a tensor written, nor two written ones each other (refused).
+ *
+ * ssd_sn_maxpool_train_backward   the gradient of ssd_maxpool3x3s2 (3x3, stride 2, 'SAME' on even H and W: pad_beg = 0, window
+ *   (oy,ox) covers rows 2oy .. 2oy+2 and columns 2ox .. 2ox+2, cells beyond the edge take no part): x [B,H,W,C], dy [B,H/2,W/2,C],
+ *   dx [B,H,W,C]; C a multiple of 4 (at least 4), H and W even (at least 2), as the forward; B <= 65536, H, W <= 32768, B*H*W < 2^31,
+ *   fewer than 2^40 elements; dx_dev may alias neither x_dev nor dy_dev.  A gather, no atomics: an input position lies in at most four
+ *   windows, and dx[b,iy,ix,c] is the sum of dy over those windows in which this position is the WINNER, one fp32 addition at a time
+ *   from +0 over the won windows in ascending (oy, ox).  The winner of a window is the FIRST tap in row-major order whose value
+ *   equals the window's forward output, m = a > m ? a : m from -inf over the taps row-major (NaN taps never replace m); a window
+ *   whose output equals none of its taps (all NaN) gives its gradient to nobody.  (TF's MaxPoolGrad tie rule restated from memory:
+ *   unpinned against TensorFlow, like the batch norm's formulas above.) */
+int ssd_sn_depthwise_train_forward(const float *x_dev, int32_t B, int32_t H, int32_t W, int32_t C, const float *w_dev /* [3,3,C,1] */,
+                                   int32_t stride, float *out_dev, void *stream);
+size_t ssd_sn_depthwise_train_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride);
+int ssd_sn_depthwise_train_backward(const float *x_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t C,
+                                    const float *w_dev, int32_t stride, float *dx_dev /* nullable */, float *dw_dev /* [3,3,C,1] */,
+                                    void *workspace_dev, size_t workspace_bytes, void *stream);
+/* Bytes of workspace either pointwise call needs (0: the sizes would be refused). */
+size_t ssd_sn_pointwise_train_workspace_bytes(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout);
+int ssd_sn_pointwise_train_forward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
+                                   const float *w_dev /* [1,1,Cin,Cout] */, void *workspace_dev, size_t workspace_bytes, void *stream);
+int ssd_sn_pointwise_train_backward(const ssd_conv_level *levels, int32_t n_levels, int32_t B, int32_t Cin, int32_t Cout,
+                                    const float *w_dev, float *dw_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int ssd_sn_bn_train_forward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, int32_t act, int32_t training, float epsilon,
+                            float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream);
+int ssd_sn_bn_train_backward(const ssd_bn_level *levels, int32_t n_levels, int32_t C, int32_t act, void *workspace_dev,
+                             size_t workspace_bytes, void *stream);
+int ssd_sn_shuffle_train(const float *x_dev, const float *y_dev, int64_t rows, int32_t D, int32_t transpose, float *xo_dev,
+                         float *yo_dev, void *stream);
+int ssd_sn_concat_train(const float *x_dev, const float *y_dev, int64_t rows, int32_t D, float *out_dev, void *stream);
+int ssd_sn_split_train(const float *g_dev, int64_t rows, int32_t D, float *dx_dev, float *dy_dev, void *stream);
+int ssd_sn_maxpool_train_backward(const float *x_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t C, float *dx_dev,
+                                  void *stream);
 
 #ifdef __cplusplus
 }

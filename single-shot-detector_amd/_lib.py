@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "logit_screen.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
-            "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip", "train_head.hip", "wgrad.hip", "train_backbone.hip"]
+            "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip", "train_head.hip", "wgrad.hip", "train_backbone.hip", "train_shufflenet.hip"]
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
 _lib = None
@@ -232,6 +232,19 @@ SIGNATURES = {
     "ssd_first_conv_train_forward": (ctypes.c_int, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "ssd_first_conv_train_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i]),
     "ssd_first_conv_train_backward": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_sn_depthwise_train_forward": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "ssd_sn_depthwise_train_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
+    "ssd_sn_depthwise_train_backward": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_sn_pointwise_train_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i]),
+    "ssd_sn_pointwise_train_forward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_sn_pointwise_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_sn_bn_train_forward": (ctypes.c_int, [ctypes.POINTER(SsdBnLevel), _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _vp,
+                                               ctypes.c_size_t, _vp]),
+    "ssd_sn_bn_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdBnLevel), _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
+    "ssd_sn_shuffle_train": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _i, _i, _vp, _vp, _vp]),
+    "ssd_sn_concat_train": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _i, _vp, _vp]),
+    "ssd_sn_split_train": (ctypes.c_int, [_vp, ctypes.c_int64, _i, _vp, _vp, _vp]),
+    "ssd_sn_maxpool_train_backward": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
 }
 
 

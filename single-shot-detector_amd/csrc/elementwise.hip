@@ -357,45 +357,49 @@ hipError_t launch_first_conv(const uint8_t *img, int B, int srcH, int srcW, int 
 // profiles/r02_depthwise_probe.log, scripts/experiments/dw_probe.hip.
 // OUT16: the result rows are written in split-fp16 form (h | l per octet, igemm.hip) for a pointwise
 // convolution that runs in precision mode f16x3; the values are exact fp32 results, rounded to h + l.
-template <int STRIDE, int OUT16 = 0, int R = (STRIDE == 1 ? 2 : 1), int PX = (STRIDE == 1 ? 4 : 2)>
+// V: channels per lane, 4 (16 B) or -- the TRAIN ShuffleNet's C % 4 == 2 (train_shufflenet.hip), raw only -- 2 (8 B: a row of 58 floats
+// is 232 bytes, so every row start and every channel pair is 8-byte aligned).
+template <int STRIDE, int OUT16 = 0, int R = (STRIDE == 1 ? 2 : 1), int PX = (STRIDE == 1 ? 4 : 2), int V = 4>
 __global__ __launch_bounds__(256) void depthwise_kernel(const float *__restrict__ in, int B, int H, int W, int C,
                                                          const float *__restrict__ w, int pad, int OH, int OW,
                                                          const float *mean, const float *sf, const float *beta,
                                                          int act, float *__restrict__ out, int *flags)
 {
     constexpr int NCOL = (PX - 1) * STRIDE + 3, NROW = (R - 1) * STRIDE + 3;
+    static_assert(V == 4 || (V == 2 && !OUT16), "4 channels per lane, or 2 without the split-fp16 rows");
+    typedef float vf __attribute__((ext_vector_type(V)));
     bool ovf = false;
-    const int C4 = C >> 2, XG = (OW + PX - 1) / PX, YG = (OH + R - 1) / R;
+    const int C4 = C >> (V == 4 ? 2 : 1), XG = (OW + PX - 1) / PX, YG = (OH + R - 1) / R;
     const long long total = (long long)B * YG * XG * C4;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % C4) * 4;
+        const int c = (int)(idx % C4) * V;
         long long q = idx / C4;
         const int ox0 = (int)(q % XG) * PX;
         q /= XG;
         const int oy0 = (int)(q % YG) * R;
         const int b = (int)(q / YG);
-        v4f wv[9];
+        vf wv[9];
 #pragma unroll
-        for (int t = 0; t < 9; ++t) wv[t] = *(const v4f *)(w + t * C + c);
-        v4f acc[R][PX];
+        for (int t = 0; t < 9; ++t) wv[t] = *(const vf *)(w + t * C + c);
+        vf acc[R][PX];
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
-            for (int p = 0; p < PX; ++p) acc[r][p] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+            for (int p = 0; p < PX; ++p) acc[r][p] = (vf)(0.0f);
         const int ix0 = ox0 * STRIDE - pad, iy0 = oy0 * STRIDE - pad;
 #pragma unroll
         for (int j = 0; j < NROW; ++j) {
             const int iy = iy0 + j;
             const bool rowok = (unsigned)iy < (unsigned)H;
             const float *rowp = in + (((long long)b * H + (rowok ? iy : 0)) * W) * C + c;
-            v4f x[NCOL];
+            vf x[NCOL];
 #pragma unroll
             for (int k = 0; k < NCOL; ++k) {
                 const int ix = ix0 + k;
                 const bool ok = rowok && (unsigned)ix < (unsigned)W;
-                x[k] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
-                if (ok) x[k] = *(const v4f *)(rowp + (long long)ix * C);
+                x[k] = (vf)(0.0f);
+                if (ok) x[k] = *(const vf *)(rowp + (long long)ix * C);
             }
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -406,7 +410,7 @@ __global__ __launch_bounds__(256) void depthwise_kernel(const float *__restrict_
 #pragma unroll
                         for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
-                            for (int i = 0; i < 4; ++i)
+                            for (int i = 0; i < V; ++i)
                                 acc[r][p][i] = fmaf(x[p * STRIDE + kx][i], wv[ky * 3 + kx][i], acc[r][p][i]);
                 }
             }
@@ -414,7 +418,7 @@ __global__ __launch_bounds__(256) void depthwise_kernel(const float *__restrict_
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             if (oy0 + r >= OH) continue;
-            if constexpr (OUT16) {
+            if constexpr (OUT16 && V == 4) {
                 typedef _Float16 v4h __attribute__((ext_vector_type(4)));
                 typedef unsigned v2u __attribute__((ext_vector_type(2)));
                 // 4 channels = half an octet: h at (octet * 8 + half * 2) floats, l 4 floats further
@@ -438,7 +442,10 @@ __global__ __launch_bounds__(256) void depthwise_kernel(const float *__restrict_
                 float *o = out + (((long long)b * OH + oy0 + r) * OW + ox0) * C + c;
 #pragma unroll
                 for (int p = 0; p < PX; ++p)
-                    if (ox0 + p < OW) *(v4f *)(o + (long long)p * C) = bn_act4(acc[r][p], mean, sf, beta, c, act);
+                    if (ox0 + p < OW) {
+                        if constexpr (V == 4) *(v4f *)(o + (long long)p * C) = bn_act4(acc[r][p], mean, sf, beta, c, act);
+                        else *(vf *)(o + (long long)p * C) = acc[r][p];         // raw: launch_depthwise refuses a batch norm or an activation here
+                    }
             }
         }
     }
@@ -447,15 +454,22 @@ __global__ __launch_bounds__(256) void depthwise_kernel(const float *__restrict_
 
 hipError_t launch_depthwise(const float *in, int B, int H, int W, int C, const float *w, int stride, int pad, int OH,
                             int OW, const float *mean, const float *sf, const float *beta, int act, float *out,
-                            hipStream_t s, int out16, int *flags)
+                            hipStream_t s, int out16, int *flags, int pairs)
 {
-    if (C % 4 || (stride != 1 && stride != 2) || (out16 && C % 8)) return hipErrorInvalidValue;
+    if (pairs ? (C % 4 != 2 || mean || act != 0 /* SSD_ACT_NONE */ || out16) : C % 4 != 0) return hipErrorInvalidValue;
+    if ((stride != 1 && stride != 2) || (out16 && C % 8)) return hipErrorInvalidValue;
     const int R = stride == 1 ? 2 : 1, PX = stride == 1 ? 4 : 2;      // as in the kernel
-    const long long total = (long long)B * ((OH + R - 1) / R) * ((OW + PX - 1) / PX) * (C / 4);
+    const long long total = (long long)B * ((OH + R - 1) / R) * ((OW + PX - 1) / PX) * (C / (pairs ? 2 : 4));
     long long blocks = (total + 255) / 256;
     if (blocks > 256 * 64) blocks = 256 * 64;
     if (blocks < 1) blocks = 1;
-    if (stride == 1 && !out16)
+    if (pairs && stride == 1)
+        hipLaunchKernelGGL((depthwise_kernel<1, 0, 2, 4, 2>), dim3((unsigned)blocks), dim3(256), 0, s, in, B, H, W, C, w, pad, OH, OW,
+                           mean, sf, beta, act, out, flags);
+    else if (pairs)
+        hipLaunchKernelGGL((depthwise_kernel<2, 0, 1, 2, 2>), dim3((unsigned)blocks), dim3(256), 0, s, in, B, H, W, C, w, pad, OH, OW,
+                           mean, sf, beta, act, out, flags);
+    else if (stride == 1 && !out16)
         hipLaunchKernelGGL(depthwise_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, in, B, H, W, C, w, pad, OH, OW,
                            mean, sf, beta, act, out, flags);
     else if (!out16)

@@ -22,10 +22,11 @@ struct DwArgs {
 // TF 'SAME' for a 3x3 window: out = ceil(n / stride), pad_beg = max((out - 1) * stride + 3 - n, 0) / 2
 static inline int same_pad(int n, int stride) { return std::max(((n + stride - 1) / stride - 1) * stride + 3 - n, 0) / 2; }
 
-static const char *dw_plan(int B, int H, int W, int C, int stride, bool backward, DwArgs &p)
+// even_c (the TRAIN ShuffleNet's entry points): any even C, C % 4 == 2 on 8-byte accesses
+static const char *dw_plan(int B, int H, int W, int C, int stride, bool backward, DwArgs &p, bool even_c = false)
 {
     if (B < 1 || H < 1 || W < 1 || C < 1) return "sizes must be positive";
-    if (C % 4) return "C must be a multiple of 4";
+    if (C % (even_c ? 2 : 4)) return even_c ? "C must be even" : "C must be a multiple of 4";
     if (stride != 1 && stride != 2) return "stride must be 1 or 2";
     if (stride == 2 && ((H ^ W) & 1)) return "stride 2 needs H and W of the same parity (one pad_beg for both axes)";
     if (B > 65536 || H > 32768 || W > 32768 || (long long)B * H * W >= (1LL << 31) || (long long)B * H * W * C >= (1LL << 40))
@@ -35,7 +36,7 @@ static const char *dw_plan(int B, int H, int W, int C, int stride, bool backward
     p.OH = (H + stride - 1) / stride;
     p.OW = (W + stride - 1) / stride;
     p.pad = same_pad(H, stride);
-    p.sl = slab_rule((long long)B * p.OH * p.OW, std::min(C, TH_STAT_COLS) / 4);   // (the forward takes wider tensors; it has no slabs)
+    p.sl = slab_rule((long long)B * p.OH * p.OW, (std::min(C, TH_STAT_COLS) + 3) / 4);   // (the forward takes wider tensors; it has no slabs)
     return nullptr;
 }
 
@@ -44,48 +45,49 @@ static size_t dw_bytes(const DwArgs &p) { return al256((size_t)p.sl.n_slabs * 9 
 // ----------------------------------------------------------------------------- the data gradient
 // dx[b,iy,ix,c] = sum over the taps (ky,kx) of dy[b,(iy+P-ky)/S,(ix+P-kx)/S,c] * w[ky,kx,c] whose source index is an integer inside
 // the output: ONE fmaf chain per element from +0 over ky = 2, 1, 0 and within each kx = 2, 1, 0, taps without a source skipped.
-// One thread = 2 rows x 4 pixels of dx x 4 channels.  The dy rows it needs (4 rows x 6 pixels at stride 1, 2 x 3 at stride 2, where
+// One thread = 2 rows x 4 pixels of dx x V channels (V = 4, or 2 where C % 4 == 2: 8-byte accesses).  The dy rows it needs (4 rows x 6 pixels at stride 1, 2 x 3 at stride 2, where
 // every dy value serves up to four dx pixels) are streamed top to bottom, each loaded once; a dy row further down is a tap row
 // further up (ky smaller), so every element still sees its taps in the pinned order.  S and P (pad_beg) are template arguments and
 // a tile starts on even coordinates, so which tap meets which window cell is decided at compile time.
-template <int S, int P>
+template <int S, int P, int V = 4>
 __global__ __launch_bounds__(256) void dw_dx_kernel(const float *__restrict__ dy, int B, int H, int W, int C, const float *__restrict__ w,
                                                      int OH, int OW, float *__restrict__ dx)
 {
     constexpr int TR = 2, TC = 4;
     constexpr int NWR = S == 1 ? TR + 2 : TR / 2 + 1, NWC = S == 1 ? TC + 2 : TC / 2 + 1;
     constexpr int OFF = S == 1 ? P - 2 : (P == 0 ? -1 : 0);             // first source index of a tile at i0: i0 / S + OFF
-    const int C4 = C >> 2, XG = (W + TC - 1) / TC, YG = (H + TR - 1) / TR;
+    typedef float vf __attribute__((ext_vector_type(V)));
+    const int C4 = C >> (V == 4 ? 2 : 1), XG = (W + TC - 1) / TC, YG = (H + TR - 1) / TR;
     const long long total = (long long)B * YG * XG * C4;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % C4) * 4;
+        const int c = (int)(idx % C4) * V;
         long long q = idx / C4;
         const int ix0 = (int)(q % XG) * TC;
         q /= XG;
         const int iy0 = (int)(q % YG) * TR;
         const int b = (int)(q / YG);
         const int oy0 = iy0 / S + OFF, ox0 = ix0 / S + OFF;
-        v4f wv[9];
+        vf wv[9];
 #pragma unroll
-        for (int t = 0; t < 9; ++t) wv[t] = *(const v4f *)(w + t * C + c);
-        v4f acc[TR][TC];
+        for (int t = 0; t < 9; ++t) wv[t] = *(const vf *)(w + t * C + c);
+        vf acc[TR][TC];
 #pragma unroll
         for (int r = 0; r < TR; ++r)
 #pragma unroll
-            for (int p = 0; p < TC; ++p) acc[r][p] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+            for (int p = 0; p < TC; ++p) acc[r][p] = (vf)(0.0f);
 #pragma unroll
         for (int j = 0; j < NWR; ++j) {
             const int oy = oy0 + j;
             const bool rowok = (unsigned)oy < (unsigned)OH;
             const float *rowp = dy + (((long long)b * OH + (rowok ? oy : 0)) * OW) * C + c;
-            v4f d[NWC];
+            vf d[NWC];
             bool ok[NWC];
 #pragma unroll
             for (int k = 0; k < NWC; ++k) {
                 const int ox = ox0 + k;
                 ok[k] = rowok && (unsigned)ox < (unsigned)OW;
-                d[k] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
-                if (ok[k]) d[k] = *(const v4f *)(rowp + (long long)ox * C);
+                d[k] = (vf)(0.0f);
+                if (ok[k]) d[k] = *(const vf *)(rowp + (long long)ox * C);
             }
 #pragma unroll
             for (int r = 0; r < TR; ++r) {
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(256) void dw_dx_kernel(const float *__restrict__ dy
                             const int k = (S == 1 ? vx : vx / 2) - OFF;
                             if (ok[k]) {
 #pragma unroll
-                                for (int i = 0; i < 4; ++i) acc[r][p][i] = fmaf(d[k][i], wv[(2 - jy) * 3 + (2 - jx)][i], acc[r][p][i]);
+                                for (int i = 0; i < V; ++i) acc[r][p][i] = fmaf(d[k][i], wv[(2 - jy) * 3 + (2 - jx)][i], acc[r][p][i]);
                             }
                         }
                     }
@@ -115,19 +117,21 @@ __global__ __launch_bounds__(256) void dw_dx_kernel(const float *__restrict__ dy
             float *o = dx + (((long long)b * H + iy0 + r) * W + ix0) * C + c;
 #pragma unroll
             for (int p = 0; p < TC; ++p)
-                if (ix0 + p < W) *(v4f *)(o + (long long)p * C) = acc[r][p];
+                if (ix0 + p < W) *(vf *)(o + (long long)p * C) = acc[r][p];
         }
     }
 }
 
 // ----------------------------------------------------------------------------- the weight gradient
-// The column-sum core of train_head.h over the output rows, G = C / 4: a thread keeps the nine taps' sums of x * dy of its channel
+// The column-sum core of train_head.h over the output rows, G = ceil(C / 4) (VW: th_load4's access width, 4 or -- C % 4 == 2 -- 2,
+// the second pair of the last quad then lies outside and stays +0): a thread keeps the nine taps' sums of x * dy of its channel
 // quad in double (the product of two floats is exact in double); the block then adds its row lanes one tap at a time.
+template <int VW>
 __global__ __launch_bounds__(256) void dw_wgrad_partial(const DwArgs a)
 {
     __shared__ double sm[1024];
     const int tid = threadIdx.x, slab = blockIdx.x;
-    const int C = a.C, G = C >> 2;
+    const int C = a.C, G = (C + 3) >> 2;
     const SlabLane ln = slab_lane(tid, G, slab, a.sl.slab_rows, a.sl.R);
     const int c = ln.c;
     double acc[9][4];
@@ -141,7 +145,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_partial(const DwArgs a)
             const int ox = (int)(ur % (unsigned)a.OW);
             const unsigned qq = ur / (unsigned)a.OW;
             const int oy = (int)(qq % (unsigned)a.OH), b = (int)(qq / (unsigned)a.OH);
-            const v4f d = *(const v4f *)(a.dy + r * C + c);
+            const v4f d = th_load4(a.dy + r * C, c, C, VW);
             const int iy0 = oy * a.stride - a.pad, ix0 = ox * a.stride - a.pad;
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_partial(const DwArgs a)
                 for (int kx = 0; kx < 3; ++kx) {
                     const int ix = ix0 + kx;
                     if ((unsigned)ix >= (unsigned)a.W) continue;
-                    const v4f xv = *(const v4f *)(rowp + (long long)ix * C);
+                    const v4f xv = th_load4(rowp + (long long)ix * C - c, c, C, VW);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[ky * 3 + kx][e] += (double)xv[e] * (double)d[e];
                 }
@@ -167,49 +171,77 @@ __global__ __launch_bounds__(256) void dw_wgrad_partial(const DwArgs a)
 }
 
 // ----------------------------------------------------------------------------- entry points
+// the bodies (train_head.h): even_c is the TRAIN ShuffleNet's flag; without it the arguments, refusals, launches and bits of before
+int dw_train_forward(const std::string &fn, const float *x_dev, int B, int H, int W, int C, const float *w_dev, int stride, float *out_dev,
+                     void *stream, bool even_c)
+{
+    DwArgs p;
+    if (const char *why = dw_plan(B, H, W, C, stride, false, p, even_c)) return ssd_fail(SSD_ERR_INVALID, fn + ": " + why);
+    if (!x_dev || !w_dev || !out_dev) return ssd_fail(SSD_ERR_INVALID, fn + ": null pointer");
+    if (mis16(x_dev) || mis16(w_dev) || mis16(out_dev)) return ssd_fail(SSD_ERR_INVALID, fn + ": every pointer needs 16-byte alignment");
+    HIPCHK(launch_depthwise(x_dev, B, H, W, C, w_dev, stride, p.pad, p.OH, p.OW, nullptr, nullptr, nullptr, SSD_ACT_NONE, out_dev, (hipStream_t)stream, 0,
+                            nullptr, C % 4 ? 1 : 0));
+    return SSD_OK;
+}
+
+size_t dw_train_workspace(int B, int H, int W, int C, int stride, bool even_c)
+{
+    DwArgs p;
+    return dw_plan(B, H, W, C, stride, true, p, even_c) ? 0 : dw_bytes(p);
+}
+
+template <int V>
+static hipError_t launch_dw_backward(const DwArgs &a, int B, const float *w_dev, float *dx_dev, hipStream_t s)
+{
+    if (dx_dev) {
+        const long long total = (long long)B * ((a.H + 1) / 2) * ((a.W + 3) / 4) * (a.C / V);
+        const unsigned blocks = (unsigned)std::max(1LL, std::min<long long>((total + 255) / 256, 256 * 64));
+        if (a.stride == 1)
+            hipLaunchKernelGGL((dw_dx_kernel<1, 1, V>), dim3(blocks), dim3(256), 0, s, a.dy, B, a.H, a.W, a.C, w_dev, a.OH, a.OW, dx_dev);
+        else if (a.pad == 0)
+            hipLaunchKernelGGL((dw_dx_kernel<2, 0, V>), dim3(blocks), dim3(256), 0, s, a.dy, B, a.H, a.W, a.C, w_dev, a.OH, a.OW, dx_dev);
+        else
+            hipLaunchKernelGGL((dw_dx_kernel<2, 1, V>), dim3(blocks), dim3(256), 0, s, a.dy, B, a.H, a.W, a.C, w_dev, a.OH, a.OW, dx_dev);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    hipLaunchKernelGGL(dw_wgrad_partial<V>, dim3((unsigned)a.sl.n_slabs), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+int dw_train_backward(const std::string &fn, const float *x_dev, const float *dy_dev, int B, int H, int W, int C, const float *w_dev, int stride,
+                      float *dx_dev, float *dw_dev, void *workspace_dev, size_t workspace_bytes, void *stream, bool even_c)
+{
+    DwArgs a;
+    if (const char *why = dw_plan(B, H, W, C, stride, true, a, even_c)) return ssd_fail(SSD_ERR_INVALID, fn + ": " + why);
+    if (!x_dev || !dy_dev || !w_dev || !dw_dev || !workspace_dev) return ssd_fail(SSD_ERR_INVALID, fn + ": null pointer");
+    if (mis16(x_dev) || mis16(dy_dev) || mis16(w_dev) || mis16(dx_dev) || mis16(dw_dev) || mis16(workspace_dev))
+        return ssd_fail(SSD_ERR_INVALID, fn + ": every pointer needs 16-byte alignment");
+    if (workspace_bytes < dw_bytes(a)) return ssd_fail(SSD_ERR_INVALID, fn + ": workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    a.x = x_dev; a.dy = dy_dev;
+    a.partial = (double *)workspace_dev;
+    HIPCHK(C % 4 ? launch_dw_backward<2>(a, B, w_dev, dx_dev, s) : launch_dw_backward<4>(a, B, w_dev, dx_dev, s));
+    HIPCHK(launch_slab_sum(a.partial, a.sl.n_slabs, 9LL * C, 9 * C, dw_dev, s));
+    return SSD_OK;
+}
+
 extern "C" int ssd_depthwise_train_forward(const float *x_dev, int32_t B, int32_t H, int32_t W, int32_t C, const float *w_dev,
                                            int32_t stride, float *out_dev, void *stream)
 {
-    DwArgs p;
-    if (const char *why = dw_plan(B, H, W, C, stride, false, p)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_depthwise_train_forward: ") + why);
-    if (!x_dev || !w_dev || !out_dev) return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise_train_forward: null pointer");
-    if (mis16(x_dev) || mis16(w_dev) || mis16(out_dev)) return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise_train_forward: every pointer needs 16-byte alignment");
-    HIPCHK(launch_depthwise(x_dev, B, H, W, C, w_dev, stride, p.pad, p.OH, p.OW, nullptr, nullptr, nullptr, SSD_ACT_NONE, out_dev, (hipStream_t)stream));
-    return SSD_OK;
+    return dw_train_forward("ssd_depthwise_train_forward", x_dev, B, H, W, C, w_dev, stride, out_dev, stream, false);
 }
 
 extern "C" size_t ssd_depthwise_train_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride)
 {
-    DwArgs p;
-    return dw_plan(B, H, W, C, stride, true, p) ? 0 : dw_bytes(p);
+    return dw_train_workspace(B, H, W, C, stride, false);
 }
 
 extern "C" int ssd_depthwise_train_backward(const float *x_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t C,
                                             const float *w_dev, int32_t stride, float *dx_dev, float *dw_dev, void *workspace_dev,
                                             size_t workspace_bytes, void *stream)
 {
-    DwArgs a;
-    if (const char *why = dw_plan(B, H, W, C, stride, true, a)) return ssd_fail(SSD_ERR_INVALID, std::string("ssd_depthwise_train_backward: ") + why);
-    if (!x_dev || !dy_dev || !w_dev || !dw_dev || !workspace_dev) return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise_train_backward: null pointer");
-    if (mis16(x_dev) || mis16(dy_dev) || mis16(w_dev) || mis16(dx_dev) || mis16(dw_dev) || mis16(workspace_dev))
-        return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise_train_backward: every pointer needs 16-byte alignment");
-    if (workspace_bytes < dw_bytes(a)) return ssd_fail(SSD_ERR_INVALID, "ssd_depthwise_train_backward: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    if (dx_dev) {
-        const long long total = (long long)B * ((H + 1) / 2) * ((W + 3) / 4) * (C / 4);
-        const unsigned blocks = (unsigned)std::max(1LL, std::min<long long>((total + 255) / 256, 256 * 64));
-        if (stride == 1)
-            LAUNCH((dw_dx_kernel<1, 1>), dim3(blocks), s, dy_dev, B, H, W, C, w_dev, a.OH, a.OW, dx_dev);
-        else if (a.pad == 0)
-            LAUNCH((dw_dx_kernel<2, 0>), dim3(blocks), s, dy_dev, B, H, W, C, w_dev, a.OH, a.OW, dx_dev);
-        else
-            LAUNCH((dw_dx_kernel<2, 1>), dim3(blocks), s, dy_dev, B, H, W, C, w_dev, a.OH, a.OW, dx_dev);
-    }
-    a.x = x_dev; a.dy = dy_dev;
-    a.partial = (double *)workspace_dev;
-    LAUNCH(dw_wgrad_partial, dim3((unsigned)a.sl.n_slabs), s, a);
-    HIPCHK(launch_slab_sum(a.partial, a.sl.n_slabs, 9LL * C, 9 * C, dw_dev, s));
-    return SSD_OK;
+    return dw_train_backward("ssd_depthwise_train_backward", x_dev, dy_dev, B, H, W, C, w_dev, stride, dx_dev, dw_dev, workspace_dev, workspace_bytes,
+                             stream, false);
 }
 
 // ============================================================================= the TRAIN first convolution

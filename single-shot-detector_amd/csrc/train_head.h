@@ -66,13 +66,21 @@ hipError_t launch_slab_sum(const double *partial, int n_slabs, long long stride,
 #ifdef __HIPCC__
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-// 4 consecutive channels of a row from channel c on: one 16-byte access where C % 4 == 0 (c % 4 == 0, so the quad is inside or
-// outside as a whole), else element by element; channels beyond C read 0 / are not written
-static __device__ inline v4f th_load4(const float *row, int c, int C, bool vec)
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+// 4 consecutive channels of a row from channel c on (c % 4 == 0), by the widest access the row width allows (th_width): one 16-byte
+// access where C % 4 == 0 (the quad is inside or outside as a whole), two 8-byte accesses where C % 4 == 2 (every row start and
+// every channel pair is 8-byte aligned; the second pair of the last quad is outside), else element by element; channels beyond C
+// read 0 / are not written
+static __device__ inline int th_width(int C) { return (C & 3) == 0 ? 4 : (C & 1) == 0 ? 2 : 1; }
+static __device__ inline v4f th_load4(const float *row, int c, int C, int vec)
 {
     v4f v = {0.f, 0.f, 0.f, 0.f};
-    if (vec) {
+    if (vec == 4) {
         if (c < C) v = *(const v4f *)(row + c);
+    } else if (vec == 2) {
+        if (c < C) { const v2f t = *(const v2f *)(row + c); v[0] = t[0]; v[1] = t[1]; }
+        if (c + 2 < C) { const v2f t = *(const v2f *)(row + c + 2); v[2] = t[0]; v[3] = t[1]; }
     } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -80,10 +88,13 @@ static __device__ inline v4f th_load4(const float *row, int c, int C, bool vec)
     }
     return v;
 }
-static __device__ inline void th_store4(float *row, int c, int C, bool vec, v4f v)
+static __device__ inline void th_store4(float *row, int c, int C, int vec, v4f v)
 {
-    if (vec) {
+    if (vec == 4) {
         if (c < C) *(v4f *)(row + c) = v;
+    } else if (vec == 2) {
+        if (c < C) *(v2f *)(row + c) = (v2f){v[0], v[1]};
+        if (c + 2 < C) *(v2f *)(row + c + 2) = (v2f){v[2], v[3]};
     } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -130,6 +141,28 @@ static __device__ inline void slab_reduce4(double *sm, const double (&acc)[4], i
 }
 #endif
 
+// The bodies of the convolution, batch-norm (train_head.hip) and depthwise (train_backbone.hip) entry points; `fn` names the entry
+// point in ssd_last_error().  The last flag of each is set by the TRAIN ShuffleNet's entry points (train_shufflenet.hip) alone and
+// lifts one refusal: even_cin -- k = 1 takes any even Cin; pw_dx -- k = 1 gives the data gradient; none_ok -- the batch norm takes
+// SSD_ACT_NONE; even_c -- the depthwise calls take any even C.  Without the flag: the arguments, refusals and bits of before.
+#include <string>
+size_t conv_train_workspace(const ssd_conv_level *levels, int n_levels, int B, int Cin, int Cout, int k, int stride, bool pw_dx, bool even_cin);
+int conv_train_forward(const std::string &fn, const ssd_conv_level *levels, int n_levels, int B, int Cin, int Cout, int k, int stride,
+                       const float *w_dev, const float *bias_dev, const float *const *up_dev, void *workspace_dev, size_t workspace_bytes,
+                       void *stream, bool even_cin = false);
+int conv_train_backward(const std::string &fn, const ssd_conv_level *levels, int n_levels, int B, int Cin, int Cout, int k, int stride,
+                        const float *w_dev, float *dw_dev, float *dbias_dev, void *workspace_dev, size_t workspace_bytes, void *stream,
+                        bool pw_dx = false, bool even_cin = false);
+int bn_train_forward(const std::string &fn, const ssd_bn_level *levels, int n_levels, int C, int act, int training, float epsilon,
+                     float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream, bool none_ok = false);
+int bn_train_backward(const std::string &fn, const ssd_bn_level *levels, int n_levels, int C, int act, void *workspace_dev,
+                      size_t workspace_bytes, void *stream, bool none_ok = false);
+int dw_train_forward(const std::string &fn, const float *x_dev, int B, int H, int W, int C, const float *w_dev, int stride, float *out_dev,
+                     void *stream, bool even_c);
+size_t dw_train_workspace(int B, int H, int W, int C, int stride, bool even_c);
+int dw_train_backward(const std::string &fn, const float *x_dev, const float *dy_dev, int B, int H, int W, int C, const float *w_dev, int stride,
+                      float *dx_dev, float *dw_dev, void *workspace_dev, size_t workspace_bytes, void *stream, bool even_c);
+
 // train_head.hip: the column statistics of a level list and the batch norm.  A slab never crosses a level.
 struct StatLevel {
     ssd_bn_level p;        // the caller's level (dbias: x = a level's dy)
@@ -143,5 +176,5 @@ struct StatArgs {
     double *partial;       // [n_slabs][2][C]
     float eps, one_minus_momentum;
     int training;
-    int act;               // SSD_ACT_RELU | SSD_ACT_RELU6: the gate of the batch norm's activation
+    int act;               // SSD_ACT_RELU | SSD_ACT_RELU6: the gate of the batch norm's activation; SSD_ACT_NONE (the TRAIN ShuffleNet): none
 };

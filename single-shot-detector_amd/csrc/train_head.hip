@@ -43,8 +43,9 @@ static __device__ inline int th_level(const StatArgs &a, int slab)
     return l;
 }
 
-// the activation's gate on the recomputed y: open where y > 0 (ReLU) and, for ReLU6, y < 6; a NaN closes it
-static __device__ inline bool th_gate(float y, int act) { return y > 0.0f && (act != SSD_ACT_RELU6 || y < 6.0f); }
+// the activation's gate on the recomputed y: open where y > 0 (ReLU) and, for ReLU6, y < 6; a NaN closes it.  SSD_ACT_NONE (the
+// TRAIN ShuffleNet's batch norm): there is no activation and the gate is open everywhere
+static __device__ inline bool th_gate(float y, int act) { return act == SSD_ACT_NONE || (y > 0.0f && (act != SSD_ACT_RELU6 || y < 6.0f)); }
 
 // MODE 0: sum x | 1: sum (x - mean)^2, the difference and the square in double | 2: sum g and sum g * xhat (batch-norm backward)
 template <int MODE>
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void stat_partial(const StatArgs a)
     const int C = a.C, G = (a.CW + 3) >> 2;
     const SlabLane ln = slab_lane(tid, G, slab - L.slab_begin, a.slab_rows, L.p.rows);
     const int c0 = blockIdx.y * TH_STAT_COLS, c = c0 + ln.c;               // (blockIdx.y > 0: dbias of a layer wider than one block)
-    const bool vec = (C & 3) == 0;
+    const int vec = th_width(C);
     double acc[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
     if (ln.on) {
         v4f mean = {0, 0, 0, 0}, invstd = mean, gamma = mean, beta = mean;
@@ -130,7 +131,7 @@ hipError_t launch_slab_sum(const double *partial, int n_slabs, long long stride,
     return hipGetLastError();
 }
 
-// y = act((x - mean) * sf + beta), act = ReLU or ReLU6 (elementwise.hip act_apply): training -- the batch's mean, sf = gamma * invstd; inference -- the moving mean,
+// y = act((x - mean) * sf + beta), act = ReLU, ReLU6 (elementwise.hip act_apply) or none: training -- the batch's mean, sf = gamma * invstd; inference -- the moving mean,
 // sf = gamma * (1 / sqrt(moving_variance + eps)) as ssd_finalize forms it
 __global__ __launch_bounds__(256) void bn_apply_forward(const StatArgs a)
 {
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(256) void bn_apply_forward(const StatArgs a)
     const SlabLane ln = slab_lane(tid, (a.CW + 3) >> 2, slab - L.slab_begin, a.slab_rows, L.p.rows);
     const int C = a.C, c = ln.c;
     if (!ln.on) return;
-    const bool vec = (C & 3) == 0;
+    const int vec = th_width(C);
     const v4f gamma = th_load4(L.p.gamma, c, C, vec), beta = th_load4(L.p.beta, c, C, vec);
     v4f mean, sf;
     if (a.training) {
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(256) void bn_apply_forward(const StatArgs a)
             const float y = t + beta[e];
             float v = y > 0.0f ? y : 0.0f;
             if (a.act == SSD_ACT_RELU6) v = v < 6.0f ? v : 6.0f;
-            x[e] = v;
+            x[e] = a.act == SSD_ACT_NONE ? y : v;
         }
         th_store4(L.p.out + r * C, c, C, vec, x);
     }
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(256) void bn_apply_backward(const StatArgs a)
     const SlabLane ln = slab_lane(tid, (a.CW + 3) >> 2, slab - L.slab_begin, a.slab_rows, L.p.rows);
     const int C = a.C, c = ln.c;
     if (!ln.on) return;
-    const bool vec = (C & 3) == 0;
+    const int vec = th_width(C);
     const v4f gamma = th_load4(L.p.gamma, c, C, vec), beta = th_load4(L.p.beta, c, C, vec), mean = th_load4(L.p.mean, c, C, vec);
     const v4f invstd = th_load4(L.p.invstd, c, C, vec), dgamma = th_load4(L.p.dgamma, c, C, vec), dbeta = th_load4(L.p.dbeta, c, C, vec);
     const float Rf = (float)L.p.rows;
@@ -225,7 +226,8 @@ struct ConvTrainPlan {
     size_t off_a, off_b, off_w, off_bias, off_part, off_stat, off_up, bytes;
 };
 
-static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, int Cout, int k, int stride, int with_up, ConvTrainPlan &p, bool pw_dx = false)
+static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, int Cout, int k, int stride, int with_up, ConvTrainPlan &p, bool pw_dx = false,
+                             bool even_cin = false)
 {
     if (!lv) return "null level list";
     if (n < 1 || n > TH_MAX_LEVELS) return "1 .. 8 levels";
@@ -235,7 +237,7 @@ static const char *conv_plan(const ssd_conv_level *lv, int n, int B, int Cin, in
     if (stride == 2 && k != 3) return "stride 2 only with k = 3";
     if (with_up && stride != 1) return "the upsample-add only with stride 1";
     if (k == 3 && Cin % 8) return "Cin must be a multiple of 8";
-    if (Cin % 4) return "Cin must be a multiple of 4";
+    if (even_cin ? (Cin % 2 || k != 1) : Cin % 4) return even_cin ? "Cin must be even (k = 1)" : "Cin must be a multiple of 4";
     if (Cin > 4096 || Cout > 4096) return "at most 4096 channels";
     const int taps = k * k;
     p.k = k; p.stride = stride; p.pad = k == 3 ? 1 : 0;
@@ -330,12 +332,19 @@ static int run_igemm(const ConvW &cw, const float *in, float *out, const float *
     return SSD_OK;
 }
 
-static int conv_train_forward(const std::string &fn, const ssd_conv_level *levels, int n_levels, int B, int Cin, int Cout, int k, int stride,
-                              const float *w_dev, const float *bias_dev, const float *const *up_dev, void *workspace_dev, size_t workspace_bytes,
-                              void *stream)
+size_t conv_train_workspace(const ssd_conv_level *levels, int n_levels, int B, int Cin, int Cout, int k, int stride, bool pw_dx, bool even_cin)
 {
     ConvTrainPlan p;
-    if (const char *why = conv_plan(levels, n_levels, B, Cin, Cout, k, stride, up_dev != nullptr, p))
+    return conv_plan(levels, n_levels, B, Cin, Cout, k, stride, 0, p, pw_dx, even_cin) ? 0 : p.bytes;
+}
+
+int conv_train_forward(const std::string &fn, const ssd_conv_level *levels, int n_levels, int B, int Cin, int Cout, int k, int stride,
+                       const float *w_dev, const float *bias_dev, const float *const *up_dev, void *workspace_dev, size_t workspace_bytes,
+                       void *stream, bool even_cin)
+{
+    ConvTrainPlan p;
+    // (even_cin: the TRAIN ShuffleNet's family has ONE workspace size for both calls, the backward's with its data gradient)
+    if (const char *why = conv_plan(levels, n_levels, B, Cin, Cout, k, stride, up_dev != nullptr, p, even_cin, even_cin))
         return ssd_fail(SSD_ERR_INVALID, fn + ": " + why);
     if (!w_dev || !workspace_dev) return ssd_fail(SSD_ERR_INVALID, fn + ": null pointer");
     if (mis16(w_dev) || mis16(workspace_dev) || ((uintptr_t)bias_dev & 3))
@@ -369,12 +378,12 @@ static int conv_train_forward(const std::string &fn, const ssd_conv_level *level
     return SSD_OK;
 }
 
-static int conv_train_backward(const std::string &fn, const ssd_conv_level *levels, int n_levels, int B, int Cin, int Cout, int k, int stride,
-                               const float *w_dev, float *dw_dev, float *dbias_dev, void *workspace_dev, size_t workspace_bytes, void *stream,
-                               bool pw_dx = false)
+int conv_train_backward(const std::string &fn, const ssd_conv_level *levels, int n_levels, int B, int Cin, int Cout, int k, int stride,
+                        const float *w_dev, float *dw_dev, float *dbias_dev, void *workspace_dev, size_t workspace_bytes, void *stream,
+                        bool pw_dx, bool even_cin)
 {
     ConvTrainPlan p;
-    if (const char *why = conv_plan(levels, n_levels, B, Cin, Cout, k, stride, 0, p, pw_dx))
+    if (const char *why = conv_plan(levels, n_levels, B, Cin, Cout, k, stride, 0, p, pw_dx, even_cin))
         return ssd_fail(SSD_ERR_INVALID, fn + ": " + why);
     if (!w_dev || !dw_dev || !workspace_dev) return ssd_fail(SSD_ERR_INVALID, fn + ": null pointer");
     if (mis16(w_dev) || mis16(dw_dev) || mis16(workspace_dev) || ((uintptr_t)dbias_dev & 3))
@@ -505,7 +514,7 @@ __global__ __launch_bounds__(256) void fpn_merge_backward_kernel(const float *ba
                                                                   float *out, long long rows, int H, int W, int C, int same)
 {
     const int CQ = (C + 3) >> 2;
-    const bool vec = (C & 3) == 0;
+    const int vec = (C & 3) == 0 ? 4 : 1;
     const long long total = rows * CQ;
     for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
         const int c = (int)(idx % CQ) << 2;
@@ -582,12 +591,13 @@ static void bn_fill(StatArgs &a, const ssd_bn_level *lv)
     }
 }
 
-static int bn_train_forward(const std::string &fn, const ssd_bn_level *levels, int n_levels, int C, int act, int training, float epsilon,
-                            float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream)
+int bn_train_forward(const std::string &fn, const ssd_bn_level *levels, int n_levels, int C, int act, int training, float epsilon,
+                     float one_minus_momentum, void *workspace_dev, size_t workspace_bytes, void *stream, bool none_ok)
 {
     StatArgs a;
     if (const char *why = bn_plan(levels, n_levels, C, a)) return ssd_fail(SSD_ERR_INVALID, fn + ": " + why);
-    if (act != SSD_ACT_RELU && act != SSD_ACT_RELU6) return ssd_fail(SSD_ERR_INVALID, fn + ": act must be SSD_ACT_RELU or SSD_ACT_RELU6");
+    if (act != SSD_ACT_RELU && act != SSD_ACT_RELU6 && !(none_ok && act == SSD_ACT_NONE))
+        return ssd_fail(SSD_ERR_INVALID, fn + (none_ok ? ": act must be SSD_ACT_NONE, SSD_ACT_RELU or SSD_ACT_RELU6" : ": act must be SSD_ACT_RELU or SSD_ACT_RELU6"));
     if (!(epsilon > 0.0f) || !(epsilon < 1e30f) || !(one_minus_momentum >= 0.0f) || !(one_minus_momentum <= 1.0f) || (training != 0 && training != 1))
         return ssd_fail(SSD_ERR_INVALID, fn + ": epsilon > 0, 0 <= one_minus_momentum <= 1, training 0 or 1");
     for (int l = 0; l < n_levels; ++l) {
@@ -618,12 +628,13 @@ static int bn_train_forward(const std::string &fn, const ssd_bn_level *levels, i
     return SSD_OK;
 }
 
-static int bn_train_backward(const std::string &fn, const ssd_bn_level *levels, int n_levels, int C, int act, void *workspace_dev,
-                             size_t workspace_bytes, void *stream)
+int bn_train_backward(const std::string &fn, const ssd_bn_level *levels, int n_levels, int C, int act, void *workspace_dev,
+                      size_t workspace_bytes, void *stream, bool none_ok)
 {
     StatArgs a;
     if (const char *why = bn_plan(levels, n_levels, C, a)) return ssd_fail(SSD_ERR_INVALID, fn + ": " + why);
-    if (act != SSD_ACT_RELU && act != SSD_ACT_RELU6) return ssd_fail(SSD_ERR_INVALID, fn + ": act must be SSD_ACT_RELU or SSD_ACT_RELU6");
+    if (act != SSD_ACT_RELU && act != SSD_ACT_RELU6 && !(none_ok && act == SSD_ACT_NONE))
+        return ssd_fail(SSD_ERR_INVALID, fn + (none_ok ? ": act must be SSD_ACT_NONE, SSD_ACT_RELU or SSD_ACT_RELU6" : ": act must be SSD_ACT_RELU or SSD_ACT_RELU6"));
     for (int l = 0; l < n_levels; ++l) {
         const ssd_bn_level &L = levels[l];
         if (!L.x || !L.dy || !L.out || !L.gamma || !L.beta || !L.mean || !L.invstd || !L.dgamma || !L.dbeta)

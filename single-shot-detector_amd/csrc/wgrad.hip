@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a)
     const int kh = tap / a.k - a.pad, kw = tap % a.k - a.pad;      // the tap's offset from the output position's first input
     const int r_begin = (slice - L.slice_begin) * a.rows_per_slice;
     const int r_end = min(L.R, r_begin + a.rows_per_slice);
-    const bool vx = (a.Cin & 3) == 0, vy = (a.Cout & 3) == 0;
+    const int vx = th_width(a.Cin), vy = th_width(a.Cout);      // C % 4 == 2 (ShuffleNet's 58): 8-byte loads
 
     // staging: thread -> (row k = tid / 32 (+ 8), channel quad tid % 32) of the x tile; the dy tile likewise over BN / 4 quads
     const int ak = tid >> 5, ac = (tid & 31) << 2;

@@ -1,0 +1,154 @@
+"""The trainable ShuffleNet-v2 backbone: detector/backbones/shufflenet_v2.py in TRAIN mode on this project's own kernels
+(include/ssd_hip.h, "the TRAIN ShuffleNet").
+
+    TrainPipeline -> TrainableShuffleNet -> TrainableFPN -> TrainableBoxPredictor -> differentiable_loss -> backward (HIP)
+                  -> TrainStep over the three modules' variables (frozen = Conv1) -> checkpoint -> Detector / evaluation
+
+It mirrors backbone_train.TrainableMobileNet point for point, with the same MODE of this project that is not parity with the
+reference: BY DEFAULT Conv1 stays FROZEN and runs in the engine's inference form (ssd.first_conv on its
+moving statistics, then ssd.maxpool3x3s2); the three stages and Conv5 -- 55 convolutions, each followed by a batch norm, the
+depthwise ones without an activation -- run on batch statistics and all their variables train.  train_first=True trains Conv1 as
+well, the reference's recipe: first_conv_train on the uint8 frames, the batch norm + ReLU on batch statistics, maxpool3x3s2_train.
+The ops (first_conv_train, depthwise_conv, pointwise_conv, batch_norm_act, concat_shuffle_split, concat_channels,
+maxpool3x3s2_train) and the variable loading (ReferenceVariables) are train_ops.py's; this file keeps the unit table and the graph.
+"""
+import numpy as np
+import torch
+
+from .train_ops import (BATCH_NORM_EPSILON, ReferenceVariables, concat_channels, concat_shuffle_split, depthwise_conv, first_conv_train,
+                        maxpool3x3s2_train, pointwise_conv)
+from .variables import SHUFFLENET_DEPTHS
+
+FIRST = "ShuffleNetV2/Conv1"
+STAGES = ((2, 4), (3, 8), (4, 4))                   # (stage, units): shufflenet_v2.py:56-66
+
+
+def shufflenet_variable_shapes(params):
+    """The backbone's subset of variables.variable_shapes(params): ShuffleNetV2/*, Conv1 and statistics included."""
+    from .variables import variable_shapes
+    if params.get("backbone") != "shufflenet":
+        raise ValueError("shufflenet_variable_shapes: the config's backbone is %r" % (params.get("backbone"),))
+    if float(params["depth_multiplier"]) not in SHUFFLENET_DEPTHS:
+        raise ValueError("shufflenet_variable_shapes: depth_multiplier must be one of %s" % sorted(SHUFFLENET_DEPTHS))
+    return {k: v for k, v in variable_shapes(params).items() if k.startswith("ShuffleNetV2/")}
+
+
+class TrainableShuffleNet(ReferenceVariables):
+    """shufflenet_v2(images, is_training, depth_multiplier) (shufflenet_v2.py:7-137) as a torch.nn.Module on the HIP kernels, with
+    Conv1 frozen by default.
+
+    params   the model config (backbone "shufflenet", depth_multiplier 0.5, 1.0 or 1.5; 2.0 is refused: Conv5 has 2048 channels and
+             the batch norm takes at most 1024)
+    weights  {reference variable name: float32 array in TF layout}; every ShuffleNetV2/* variable must be there (a missing one is a
+             KeyError, not a draw)
+    forward(images uint8 [B,H,W,3] on the GPU, H and W multiples of 32) -> [c3, c4, c5] NHWC float32: Stage2, Stage3 and Conv5.
+    .train(): all 56 batch norms (55 with Conv1 frozen) on batch statistics, their moving statistics move; .eval(): the engine's c3,
+    c4, c5 bit for bit.  named_variables() / statistics() hold 165 + 110 variables and frozen_variables() the 5 Conv1 arrays for
+    TrainStep(..., frozen=backbone.frozen_variables()); with train_first=True 168 + 112 and {}.  keep_features=True keeps the
+    post-batch-norm tensor of every layer of the last forward in .features under its scope name (without the "ShuffleNetV2/" prefix
+    and the "/batch_norm" suffix; "Conv1" with train_first only), plus "MaxPool", "Stage2" .. "Stage4" and "Conv5" (detached)."""
+
+    def __init__(self, params, weights, device=None, seed=0, keep_features=False, train_first=False):
+        if params.get("backbone") != "shufflenet":
+            raise ValueError("TrainableShuffleNet: the config's backbone is %r" % (params.get("backbone"),))
+        if float(params["depth_multiplier"]) not in (0.5, 1.0, 1.5):
+            raise ValueError("TrainableShuffleNet: depth_multiplier must be 0.5, 1.0 or 1.5 (2.0: Conv5 has 2048 channels, the batch norm "
+                             "takes at most 1024)")
+        shapes = shufflenet_variable_shapes(params)
+        self.train_first = bool(train_first)
+        frozen = {}
+        for name, shape in shapes.items():
+            if name.startswith(FIRST + "/") and not self.train_first:
+                a = weights.get(name)
+                if a is None:
+                    raise KeyError("weights has no variable %r" % name)
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if tuple(a.shape) != tuple(shape):
+                    raise ValueError("variable %r has shape %s, expected %s" % (name, a.shape, tuple(shape)))
+                frozen[name] = a.copy()
+        trained = {k: v for k, v in shapes.items() if self.train_first or not k.startswith(FIRST + "/")}
+        super().__init__(trained, weights, lambda name, shape, rng: None, device, seed)
+        self._frozen = frozen
+        self.params = dict(params)
+        self.keep_features = bool(keep_features)
+        self.features, self._feats = {}, {}
+        if self.train_first:
+            return
+        f = self._frozen
+        one = np.float32(1.0)
+        sf = f[FIRST + "/batch_norm/gamma"] * (one / np.sqrt(f[FIRST + "/batch_norm/moving_variance"] + np.float32(BATCH_NORM_EPSILON)))
+        self._first_bn = (f[FIRST + "/batch_norm/moving_mean"], sf.astype(np.float32), f[FIRST + "/batch_norm/beta"])
+
+    def frozen_variables(self):
+        """{reference name: float32 array} of Conv1: its kernel, gamma, beta and moving statistics, untouched by training ({} with
+        train_first)."""
+        return {k: v.copy() for k, v in self._frozen.items()}
+
+    def first_conv(self, images):
+        """Conv1 and MaxPool: uint8 frames -> 2x/255 - 1 -> 3x3 stride 2 -> batch norm -> ReLU -> 3x3 stride-2 max pool.  Frozen: the
+        engine's inference form on the moving statistics.  train_first: the raw convolution with a weight gradient, the batch norm
+        in the module's mode and the max pool with its gradient."""
+        from . import ssd
+        if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4
+                and images.shape[3] == 3):
+            raise TypeError("images must be a uint8 [B,H,W,3] tensor on a GPU")
+        if images.shape[1] % 32 or images.shape[2] % 32:
+            raise ValueError("images: height and width must be multiples of 32 (the network's stride)")
+        self._feats = {}
+        if self.train_first:
+            x = self._bn(first_conv_train(images, self.variable(FIRST + "/weights")), FIRST)
+            self._keep("Conv1", x)
+            x = maxpool3x3s2_train(x)
+        else:
+            with torch.cuda.device(images.device):
+                x = ssd.maxpool3x3s2(ssd.first_conv(images.contiguous(), self._frozen[FIRST + "/weights"], self._first_bn, "relu"))
+        self._keep("MaxPool", x)
+        return x
+
+    def _keep(self, name, x):
+        if self.keep_features:
+            self._feats[name] = x.detach()
+
+    def _bn(self, x, scope, act="relu"):
+        return self.batch_norm_relu([x], [scope + "/batch_norm"], act=act)[0]
+
+    def _conv(self, x, scope):
+        x = self._bn(pointwise_conv(x, self.variable("ShuffleNetV2/" + scope + "/weights")), "ShuffleNetV2/" + scope)
+        self._keep(scope, x)
+        return x
+
+    def _dw(self, x, scope, stride):
+        # depthwise_conv(..., activation_fn=None): a batch norm and nothing after it (shufflenet_v2.py:121,131,135)
+        x = self._bn(depthwise_conv(x, self.variable("ShuffleNetV2/" + scope + "/depthwise_weights"), stride), "ShuffleNetV2/" + scope, act="none")
+        self._keep(scope, x)
+        return x
+
+    def _stage(self, x, stage, units):
+        u = "Stage%d/unit_1" % stage                             # basic_unit_with_downsampling (:126-137)
+        y = self._conv(x, u + "/conv1x1_before")
+        y = self._dw(y, u + "/depthwise", 2)
+        y = self._conv(y, u + "/conv1x1_after")
+        x = self._dw(x, u + "/second_branch/depthwise", 2)
+        x = self._conv(x, u + "/second_branch/conv1x1_after")
+        for j in range(2, units + 1):                            # concat_shuffle_split + basic_unit (:79-91, :118-123)
+            x, y = concat_shuffle_split(x, y)
+            u = "Stage%d/unit_%d" % (stage, j)
+            x = self._conv(x, u + "/conv1x1_before")
+            x = self._dw(x, u + "/depthwise", 1)
+            x = self._conv(x, u + "/conv1x1_after")
+        x = concat_channels(x, y)
+        self._keep("Stage%d" % stage, x)
+        return x
+
+    def body(self, x):
+        """Stage2 .. Stage4 and Conv5 on MaxPool's output [B,H/4,W/4,24] -> [c3, c4, c5]."""
+        outs = []
+        for stage, units in STAGES:
+            x = self._stage(x, stage, units)
+            outs.append(x)
+        outs[2] = self._conv(x, "Conv5")
+        self.features = self._feats
+        return outs
+
+    def forward(self, images):
+        return self.body(self.first_conv(images))

@@ -1,5 +1,5 @@
 """How a TRAIN entry point of include/ssd_hip.h is called ("the TRAIN head", "the TRAIN FPN", "the TRAIN backbone", "the TRAIN first
-convolution"): the only module that fills ssd_conv_level / ssd_bn_level, orders the arguments, sizes the workspace and passes the
+convolution", "the TRAIN ShuffleNet"): the only module that fills ssd_conv_level / ssd_bn_level, orders the arguments, sizes the workspace and passes the
 stream.  One function per entry point family, no autograd, no model.  Arguments are torch tensors, None exactly where the header
 allows NULL; every result is the CALLER's tensor.  Before the library is called every tensor is checked against the shape the
 geometry implies (ValueError naming the argument: shape, dtype, contiguity, level counts) and then for lying on one GPU
@@ -13,6 +13,7 @@ import torch
 from ._lib import SsdBnLevel, SsdConvLevel, check, lib
 
 ACTS = {"relu": 1, "relu6": 2}                                                 # SSD_ACT_RELU, SSD_ACT_RELU6
+SN_ACTS = dict(ACTS, none=0)                                                   # entry "sn_bn" alone: SSD_ACT_NONE too
 _workspaces = {}
 
 
@@ -106,7 +107,8 @@ def _run(dev, workspace, need, call):
 
 
 # ----------------------------------------------------------------------------- the convolution
-_CONV = {"conv": "ssd_conv_train_", "conv3x3": "ssd_conv3x3_train_", "pointwise": "ssd_pointwise_train_"}
+_CONV = {"conv": "ssd_conv_train_", "conv3x3": "ssd_conv3x3_train_", "pointwise": "ssd_pointwise_train_",
+         "sn_pointwise": "ssd_sn_pointwise_train_"}                            # the TRAIN ShuffleNet's: any even Cin, Cout; forward too
 
 
 def _conv_extra(entry, k, stride, with_up=False):
@@ -114,7 +116,7 @@ def _conv_extra(entry, k, stride, with_up=False):
     if entry == "conv":
         return (k, stride)
     if entry not in _CONV or (k, stride) != ((3, 1) if entry == "conv3x3" else (1, 1)) or with_up:
-        raise ValueError("entry must be 'conv', 'conv3x3' (k = 3, stride 1, no ups) or 'pointwise' (k = 1, stride 1, no ups)")
+        raise ValueError("entry must be 'conv', 'conv3x3' (k = 3, stride 1, no ups) or 'pointwise' / 'sn_pointwise' (k = 1, stride 1, no ups)")
     return ()
 
 
@@ -152,14 +154,17 @@ def _conv_levels(xs, dys, outs):
 
 
 def conv_forward(xs, kernel, outs, stride=1, bias=None, ups=None, workspace=None, entry="conv"):
-    """ssd_conv_train_forward (entry "conv3x3": ssd_conv3x3_train_forward) of the levels xs [B,H,W,Cin] with ONE kernel HWIO
+    """ssd_conv_train_forward (entry "conv3x3": ssd_conv3x3_train_forward; "sn_pointwise": ssd_sn_pointwise_train_forward, k = 1, no
+    bias, no ups) of the levels xs [B,H,W,Cin] with ONE kernel HWIO
     [k,k,Cin,Cout] into outs [B,ceil(H/stride),ceil(W/stride),Cout]; bias [Cout] and ups (one [B,H/2,W/2,Cout] per level) nullable."""
     if entry == "pointwise":
         raise ValueError("entry: the pointwise family has no forward of its own ('conv' runs a 1x1 kernel)")
     xs, B, Cin, Cout, k, extra, shapes = _conv_args(xs, kernel, stride, entry, ups is not None)
     outs = _column(outs, "outs", shapes)
     ups = _column(ups, "ups", [(B, x.shape[1] // 2, x.shape[2] // 2, Cout) for x in xs])
-    middle = (_vector(bias, "bias", Cout),)
+    if entry == "sn_pointwise" and bias is not None:
+        raise ValueError("bias: the sn_pointwise family has none")
+    middle = (_vector(bias, "bias", Cout),) if entry != "sn_pointwise" else ()
     dev = _one_gpu(workspace, xs=xs, kernel=kernel, outs=outs, bias=bias, ups=ups)
     if entry == "conv":
         middle += ((ctypes.c_void_p * len(xs))(*[u.data_ptr() for u in ups]) if ups is not None else None,)
@@ -168,16 +173,16 @@ def conv_forward(xs, kernel, outs, stride=1, bias=None, ups=None, workspace=None
 
 
 def conv_backward(xs, kernel, dys, dw, stride=1, dxs=None, dbias=None, workspace=None, entry="conv"):
-    """ssd_conv_train_backward (entry "conv3x3": ssd_conv3x3_train_backward; "pointwise": ssd_pointwise_train_backward, k = 1 with
-    the data gradient and no dbias) from xs, the kernel and dys (the forward's output shapes): dw of the kernel's shape, dxs (for
+    """ssd_conv_train_backward (entry "conv3x3": ssd_conv3x3_train_backward; "pointwise" / "sn_pointwise": ssd_pointwise_train_backward
+    / ssd_sn_pointwise_train_backward, k = 1 with the data gradient and no dbias) from xs, the kernel and dys (the forward's output shapes): dw of the kernel's shape, dxs (for
     every level or None) of the levels' shapes, dbias [Cout] nullable."""
     xs, B, Cin, Cout, k, extra, shapes = _conv_args(xs, kernel, stride, entry)
     dys = _column(dys, "dys", shapes)
     _dense(dw, "dw", kernel.shape)
     dxs = _column(dxs, "dxs", [x.shape for x in xs])
-    if entry == "pointwise" and dbias is not None:
-        raise ValueError("dbias: the pointwise family has none")
-    middle = (dw.data_ptr(),) + ((_vector(dbias, "dbias", Cout),) if entry != "pointwise" else ())
+    if entry in ("pointwise", "sn_pointwise") and dbias is not None:
+        raise ValueError("dbias: the pointwise families have none")
+    middle = (dw.data_ptr(),) + ((_vector(dbias, "dbias", Cout),) if entry not in ("pointwise", "sn_pointwise") else ())
     dev = _one_gpu(workspace, xs=xs, kernel=kernel, dys=dys, dw=dw, dxs=dxs, dbias=dbias)
     dims, fn = (_conv_levels(xs, dys, dxs), len(xs), B, Cin, Cout), getattr(lib(), _CONV[entry] + "backward")
     _run(dev, workspace, lambda: _conv_need(entry, dims, k, stride, False), lambda *tail: fn(*dims, *extra, kernel.data_ptr(), *middle, *tail))
@@ -208,24 +213,37 @@ def fpn_merge_backward(g, base=None, gate=None, same_size=False, out=None):
 
 
 # ----------------------------------------------------------------------------- the depthwise and the first convolution
-def depthwise_forward(x, kernel, out, stride=1):
-    """ssd_depthwise_train_forward: x [B,H,W,C], kernel [3,3,C,1] -> out [B,ceil(H/stride),ceil(W/stride),C]."""
+_DW = {"depthwise": "ssd_depthwise_train_", "sn_depthwise": "ssd_sn_depthwise_train_"}    # the TRAIN ShuffleNet's: any even C
+
+
+def _dw_entry(entry, which):
+    if entry not in _DW:
+        raise ValueError("entry must be 'depthwise' or 'sn_depthwise'")
+    return getattr(lib(), _DW[entry] + which)
+
+
+def depthwise_forward(x, kernel, out, stride=1, entry="depthwise"):
+    """ssd_depthwise_train_forward (entry "sn_depthwise": ssd_sn_depthwise_train_forward): x [B,H,W,C], kernel [3,3,C,1] -> out
+    [B,ceil(H/stride),ceil(W/stride),C]."""
+    fn = _dw_entry(entry, "forward")
     B, H, W, C = _dense(x, "x", (None,) * 4)
     _dense(kernel, "kernel", (3, 3, C, 1))
     _dense(out, "out", conv_out_shape(x.shape, C, stride))
     dev = _one_gpu(None, x=x, kernel=kernel, out=out)
     with torch.cuda.device(dev):
-        check(lib().ssd_depthwise_train_forward(x.data_ptr(), B, H, W, C, kernel.data_ptr(), stride, out.data_ptr(), stream(dev)))
+        check(fn(x.data_ptr(), B, H, W, C, kernel.data_ptr(), stride, out.data_ptr(), stream(dev)))
 
 
-def depthwise_workspace_bytes(x, stride):
-    """ssd_depthwise_train_workspace_bytes: x is the input or its shape (B, H, W, C)."""
-    return lib().ssd_depthwise_train_workspace_bytes(*getattr(x, "shape", x), stride)
+def depthwise_workspace_bytes(x, stride, entry="depthwise"):
+    """ssd_depthwise_train_workspace_bytes (entry "sn_depthwise": ssd_sn_depthwise_train_workspace_bytes): x is the input or its shape
+    (B, H, W, C)."""
+    return _dw_entry(entry, "workspace_bytes")(*getattr(x, "shape", x), stride)
 
 
-def depthwise_backward(x, kernel, dy, dw, stride=1, dx=None, workspace=None):
-    """ssd_depthwise_train_backward from x, the kernel and dy (the forward's output shape): dw of the kernel's shape, dx of x's
-    shape or None."""
+def depthwise_backward(x, kernel, dy, dw, stride=1, dx=None, workspace=None, entry="depthwise"):
+    """ssd_depthwise_train_backward (entry "sn_depthwise": ssd_sn_depthwise_train_backward) from x, the kernel and dy (the forward's
+    output shape): dw of the kernel's shape, dx of x's shape or None."""
+    need, fn = _dw_entry(entry, "workspace_bytes"), _dw_entry(entry, "backward")
     B, H, W, C = _dense(x, "x", (None,) * 4)
     _dense(kernel, "kernel", (3, 3, C, 1))
     _dense(dy, "dy", conv_out_shape(x.shape, C, stride))
@@ -233,9 +251,9 @@ def depthwise_backward(x, kernel, dy, dw, stride=1, dx=None, workspace=None):
     if dx is not None:
         _dense(dx, "dx", x.shape)
     dev = _one_gpu(workspace, x=x, kernel=kernel, dy=dy, dw=dw, dx=dx)
-    L, dxp = lib(), dx.data_ptr() if dx is not None else None
-    _run(dev, workspace, lambda: L.ssd_depthwise_train_workspace_bytes(B, H, W, C, stride),
-         lambda *tail: L.ssd_depthwise_train_backward(x.data_ptr(), dy.data_ptr(), B, H, W, C, kernel.data_ptr(), stride, dxp, dw.data_ptr(), *tail))
+    dxp = dx.data_ptr() if dx is not None else None
+    _run(dev, workspace, lambda: need(B, H, W, C, stride),
+         lambda *tail: fn(x.data_ptr(), dy.data_ptr(), B, H, W, C, kernel.data_ptr(), stride, dxp, dw.data_ptr(), *tail))
 
 
 def first_conv_forward(images, kernel, out):
@@ -274,8 +292,8 @@ def bn_workspace_bytes(rows, C):
 def _bn_call(which, entry, act, scalars, workspace, xs, dys, outs, out_name, **vectors):
     """Both batch-norm calls: xs, dys, outs [..., C] of equal shape per level, every column of `vectors` (named after ssd_bn_level's
     fields) None or one per-channel vector per level; <family><which>(levels, n, C[, act], *scalars, workspace, stream)."""
-    if entry not in ("bn_act", "bn_relu") or act not in ACTS or (entry == "bn_relu" and act != "relu"):
-        raise ValueError("entry must be 'bn_act' or 'bn_relu' (act 'relu' only), act 'relu' or 'relu6'")
+    if entry not in ("bn_act", "bn_relu", "sn_bn") or act not in (SN_ACTS if entry == "sn_bn" else ACTS) or (entry == "bn_relu" and act != "relu"):
+        raise ValueError("entry must be 'bn_act', 'bn_relu' (act 'relu' only) or 'sn_bn' (act 'none' too), act 'relu' or 'relu6'")
     xs = _levels(xs)
     n, C, shapes = len(xs), xs[0].shape[-1] if isinstance(xs[0], torch.Tensor) and xs[0].dim() else 0, []
     for i, x in enumerate(xs):
@@ -294,13 +312,14 @@ def _bn_call(which, entry, act, scalars, workspace, xs, dys, outs, out_name, **v
             for i, t in enumerate(col):
                 setattr(lv[i], name, _vector(t, "%ss[%d]" % (name, i), C))
     dev = _one_gpu(workspace, xs=xs, dys=dys, **{out_name: outs}, **vectors)
-    fn, acts = getattr(lib(), "ssd_%s_train_%s" % (entry, which)), (ACTS[act],) if entry == "bn_act" else ()
+    fn, acts = getattr(lib(), "ssd_%s_train_%s" % (entry, which)), (SN_ACTS[act],) if entry != "bn_relu" else ()
     _run(dev, workspace, lambda: lib().ssd_bn_relu_train_workspace_bytes(lv, n, C), lambda *tail: fn(lv, n, C, *acts, *scalars, *tail))
 
 
 def bn_forward(xs, outs, gammas, betas, training, epsilon, one_minus_momentum, moving_means=None, moving_variances=None, means=None,
                vars_=None, invstds=None, act="relu", workspace=None, entry="bn_act"):
-    """ssd_bn_act_train_forward (entry "bn_relu": ssd_bn_relu_train_forward, act "relu") of the levels xs [..., C] into outs; every
+    """ssd_bn_act_train_forward (entry "bn_relu": ssd_bn_relu_train_forward, act "relu"; "sn_bn": ssd_sn_bn_train_forward, act "none"
+    too) of the levels xs [..., C] into outs; every
     other argument a list of [C] vectors per level.  training: the batch statistics go to means, vars_ (nullable), invstds and move
     the moving statistics (nullable as a pair); not training: the inference form on the moving statistics, nothing else written."""
     _bn_call("forward", entry, act, (1 if training else 0, epsilon, one_minus_momentum), workspace, xs, None, outs, "outs", gamma=gammas, beta=betas,
@@ -308,7 +327,57 @@ def bn_forward(xs, outs, gammas, betas, training, epsilon, one_minus_momentum, m
 
 
 def bn_backward(xs, dys, dxs, gammas, betas, means, invstds, dgammas, dbetas, act="relu", workspace=None, entry="bn_act"):
-    """ssd_bn_act_train_backward (entry "bn_relu": ssd_bn_relu_train_backward, act "relu") from xs, dys and the forward's means and
+    """ssd_bn_act_train_backward (entry "bn_relu": ssd_bn_relu_train_backward, act "relu"; "sn_bn": ssd_sn_bn_train_backward, act "none"
+    too) from xs, dys and the forward's means and
     invstds: dxs of the levels' shapes, dgammas and dbetas [C] per level."""
     _bn_call("backward", entry, act, (), workspace, xs, dys, dxs, "dxs", gamma=gammas, beta=betas, mean=means, invstd=invstds, dgamma=dgammas,
              dbeta=dbetas)
+
+
+# ----------------------------------------------------------------------------- the TRAIN ShuffleNet's copies and its max pool
+def _halves(x, y, xname, yname):
+    """x and y [..., D] of one shape -> (rows, D)."""
+    if not (isinstance(x, torch.Tensor) and x.dim() >= 1 and x.shape[-1] >= 1):
+        raise ValueError("%s must be a tensor [..., D]" % xname)
+    shape = _dense(x, xname, (None,) * x.dim())
+    _dense(y, yname, tuple(shape))
+    return x.numel() // shape[-1], shape[-1]
+
+
+def shuffle(x, y, xo, yo, transpose=False):
+    """ssd_sn_shuffle_train on four tensors [..., D] of one shape: concat_shuffle_split(x, y) -> (xo, yo); transpose: x, y are the
+    gradients of the two outputs and xo, yo receive those of the two inputs."""
+    rows, D = _halves(x, y, "x", "y")
+    _dense(xo, "xo", tuple(x.shape))
+    _dense(yo, "yo", tuple(x.shape))
+    dev = _one_gpu(None, x=x, y=y, xo=xo, yo=yo)
+    with torch.cuda.device(dev):
+        check(lib().ssd_sn_shuffle_train(x.data_ptr(), y.data_ptr(), rows, D, 1 if transpose else 0, xo.data_ptr(), yo.data_ptr(), stream(dev)))
+
+
+def concat(x, y, out):
+    """ssd_sn_concat_train: x, y [..., D] -> out [..., 2D] = [x | y]."""
+    rows, D = _halves(x, y, "x", "y")
+    _dense(out, "out", tuple(x.shape[:-1]) + (2 * D,))
+    dev = _one_gpu(None, x=x, y=y, out=out)
+    with torch.cuda.device(dev):
+        check(lib().ssd_sn_concat_train(x.data_ptr(), y.data_ptr(), rows, D, out.data_ptr(), stream(dev)))
+
+
+def split(g, dx, dy):
+    """ssd_sn_split_train: g [..., 2D] -> dx = g[..., :D], dy = g[..., D:]."""
+    rows, D = _halves(dx, dy, "dx", "dy")
+    _dense(g, "g", tuple(dx.shape[:-1]) + (2 * D,))
+    dev = _one_gpu(None, g=g, dx=dx, dy=dy)
+    with torch.cuda.device(dev):
+        check(lib().ssd_sn_split_train(g.data_ptr(), rows, D, dx.data_ptr(), dy.data_ptr(), stream(dev)))
+
+
+def maxpool_backward(x, dy, dx):
+    """ssd_sn_maxpool_train_backward: x [B,H,W,C] (the pool's input), dy [B,H/2,W/2,C] -> dx of x's shape."""
+    B, H, W, C = _dense(x, "x", (None,) * 4)
+    _dense(dy, "dy", (B, H // 2, W // 2, C))
+    _dense(dx, "dx", (B, H, W, C))
+    dev = _one_gpu(None, x=x, dy=dy, dx=dx)
+    with torch.cuda.device(dev):
+        check(lib().ssd_sn_maxpool_train_backward(x.data_ptr(), dy.data_ptr(), B, H, W, C, dx.data_ptr(), stream(dev)))

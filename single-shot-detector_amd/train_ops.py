@@ -1,11 +1,14 @@
 """The differentiable ops under the trainable modules (include/ssd_hip.h, "the TRAIN head", "the TRAIN FPN" and "the TRAIN
-backbone" and "the TRAIN first convolution"), and nothing about any model: conv_same / conv3x3_same, depthwise_conv, pointwise_conv,
-first_conv_train and batch_norm_act (batch_norm_relu is its act="relu" case) are torch.autograd.Functions over the C entry points (once differentiable), fpn_merge_backward is
+backbone", "the TRAIN first convolution" and "the TRAIN ShuffleNet"), and nothing about any model: conv_same / conv3x3_same,
+depthwise_conv, pointwise_conv, first_conv_train, batch_norm_act (batch_norm_relu is its act="relu" case), concat_shuffle_split,
+concat_channels and maxpool3x3s2_train are torch.autograd.Functions over the C entry points (once differentiable), fpn_merge_backward is
 ssd_fpn_merge_backward, and ReferenceVariables is the torch.nn.Module base that holds a block's variables under their reference
 names.  The Functions allocate the results and keep what the backward needs; how an entry point is called (the level structs, the
 argument order, the workspace, the stream, the shape checks) is train_calls.py's, where fpn_merge_backward lives too.  torch
-provides memory, streams and the autograd graph only.  head_train.py, fpn_train.py and backbone_train.py build
-RetinaNetBoxPredictor, fpn() and mobilenet_v1() from these.
+provides memory, streams and the autograd graph only.  head_train.py, fpn_train.py, backbone_train.py and shufflenet_train.py build
+RetinaNetBoxPredictor, fpn(), mobilenet_v1() and shufflenet_v2() from these.
+depthwise_conv, pointwise_conv and batch_norm_act go to the TRAIN ShuffleNet's entry points exactly where the older ones refuse -- a
+channel count that is 2 mod 4, act="none" -- so every shape they took before keeps its launches and bits.
 """
 import numpy as np
 import torch
@@ -19,10 +22,10 @@ BATCH_NORM_EPSILON = 1e-3
 
 
 # ----------------------------------------------------------------------------- the convolution
-def _conv_forward(xs, kernel, bias, stride, ups):
+def _conv_forward(xs, kernel, bias, stride, ups, entry="conv"):
     """train_calls.conv_forward on contiguous levels -> the outputs."""
     outs = tuple(torch.empty(calls.conv_out_shape(x.shape, kernel.shape[3], stride), dtype=torch.float32, device=kernel.device) for x in xs)
-    calls.conv_forward(xs, kernel, outs, stride, bias, ups)
+    calls.conv_forward(xs, kernel, outs, stride, bias, ups, entry=entry)
     return outs
 
 
@@ -37,14 +40,15 @@ def _conv_backward(xs, kernel, dys, stride, want_dx, want_dbias=False, entry="co
 
 class _Conv(torch.autograd.Function):
     """(kernel, bias, stride, pointwise, n, the n levels, then one `up` per level or none) -> the n outputs.  pointwise: the backward
-    is ssd_pointwise_train_backward, which gives a 1x1 convolution's data gradient."""
+    is ssd_pointwise_train_backward, which gives a 1x1 convolution's data gradient; pointwise == "sn_pointwise" (Cin = 2 mod 4): the
+    TRAIN ShuffleNet's pair, forward and backward."""
 
     @staticmethod
     def forward(ctx, kernel, bias, stride, pointwise, n, *t):
         xs = tuple(x.contiguous() for x in t[:n])
         ups = tuple(u.contiguous() for u in t[n:]) if len(t) > n else None
         kernel = kernel.contiguous()
-        outs = _conv_forward(xs, kernel, bias, stride, ups)
+        outs = _conv_forward(xs, kernel, bias, stride, ups, "sn_pointwise" if pointwise == "sn_pointwise" else "conv")
         ctx.save_for_backward(kernel, *xs)
         ctx.stride, ctx.pointwise, ctx.n, ctx.has_bias, ctx.has_up = stride, pointwise, n, bias is not None, ups is not None
         return outs
@@ -60,7 +64,8 @@ class _Conv(torch.autograd.Function):
         if want_dx and kernel.shape[0] == 1 and not ctx.pointwise:
             raise RuntimeError("conv_same: a 1x1 convolution has no data gradient here (nothing trainable lies upstream of a lateral "
                                "while the backbone is frozen); detach its input")
-        dw, dbias, dxs = _conv_backward(xs, kernel, dys, ctx.stride, want_dx, ctx.has_bias, "pointwise" if ctx.pointwise else "conv")
+        entry = ctx.pointwise if ctx.pointwise == "sn_pointwise" else "pointwise" if ctx.pointwise else "conv"
+        dw, dbias, dxs = _conv_backward(xs, kernel, dys, ctx.stride, want_dx, ctx.has_bias, entry)
         dups = ()
         if ctx.has_up:                                                  # the gradient of `up`: the 2x2 sums of dy
             dups = tuple(fpn_merge_backward(d) if need else None for d, need in zip(dys, ctx.needs_input_grad[5 + n:]))
@@ -122,10 +127,11 @@ def conv3x3_same(features, kernel, bias=None):
 # ----------------------------------------------------------------------------- the backbone's convolutions
 def pointwise_conv(features, kernel):
     """slim.conv2d 1x1, stride 1, raw (mobilenet_v1.py:66 before its batch norm): features a tensor [B,H,W,Cin] or a list of them that
-    share ONE kernel HWIO [1,1,Cin,Cout], Cin a multiple of 4.  The forward is conv_same's (bit-identical to ssd_amd.ssd.conv2d);
+    share ONE kernel HWIO [1,1,Cin,Cout], Cin a multiple of 4 -- or 2 mod 4 with an even Cout (ShuffleNet's 58), which takes the TRAIN
+    ShuffleNet's entry points.  The forward is conv_same's (bit-identical to ssd_amd.ssd.conv2d);
     gradients flow to the kernel AND to the features (dx = conv1x1(dy, kernel transposed), one fmaf chain per element)."""
     single, xs = _level_list(features, kernel, "pointwise_conv", lambda s: s[:2] == (1, 1), "[1,1,Cin,Cout]")
-    outs = _Conv.apply(kernel, None, 1, True, len(xs), *xs)
+    outs = _Conv.apply(kernel, None, 1, "sn_pointwise" if kernel.shape[2] % 4 == 2 else True, len(xs), *xs)
     return outs[0] if single else list(outs)
 
 
@@ -134,7 +140,8 @@ class _Depthwise(torch.autograd.Function):
     def forward(ctx, x, kernel, stride):
         x, kernel = x.contiguous(), kernel.contiguous()
         out = torch.empty(calls.conv_out_shape(x.shape, x.shape[3], stride), dtype=torch.float32, device=x.device)
-        calls.depthwise_forward(x, kernel, out, stride)
+        ctx.entry = "sn_depthwise" if x.shape[3] % 4 == 2 else "depthwise"
+        calls.depthwise_forward(x, kernel, out, stride, entry=ctx.entry)
         ctx.save_for_backward(x, kernel)
         ctx.stride = stride
         return out
@@ -145,13 +152,13 @@ class _Depthwise(torch.autograd.Function):
         x, kernel = ctx.saved_tensors
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(kernel)
-        calls.depthwise_backward(x, kernel, dy.contiguous(), dw, ctx.stride, dx)
+        calls.depthwise_backward(x, kernel, dy.contiguous(), dw, ctx.stride, dx, entry=ctx.entry)
         return dx, dw, None
 
 
 def depthwise_conv(x, kernel, stride=1):
     """tf.nn.depthwise_conv2d, 3x3, 'SAME', raw (depthwise_conv.py:5-26 before its batch norm): x [B,H,W,C], kernel [3,3,C,1], C a
-    multiple of 4 (at most 1024 for the backward), stride 1 or 2 (2: H and W of one parity).  The forward is bit-identical to
+    multiple of 4 -- or 2 mod 4, on the TRAIN ShuffleNet's entry points -- (at most 1024 for the backward), stride 1 or 2 (2: H and W of one parity).  The forward is bit-identical to
     ssd_amd.ssd.depthwise3x3 without batch norm and activation; gradients flow to x and the kernel."""
     _need(x, "x")
     _need(kernel, "kernel")
@@ -208,6 +215,11 @@ def _rows(buf, C):
     return [[buf[i, j, :C] for i in range(buf.shape[0])] for j in range(buf.shape[1])]
 
 
+def _bn_entry(act):
+    """act "none" (ShuffleNet's depthwise layers) is the TRAIN ShuffleNet's pair; the others keep theirs."""
+    return "sn_bn" if act == "none" else "bn_act"
+
+
 class _BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, n, epsilon, one_minus_momentum, act, *t):
@@ -216,7 +228,7 @@ class _BnAct(torch.autograd.Function):
         C = xs[0].shape[-1]
         outs = tuple(torch.empty_like(x) for x in xs)
         stats = torch.empty((n, 3, (C + 3) // 4 * 4), dtype=torch.float32, device=xs[0].device)      # mean, var, invstd per level
-        calls.bn_forward(xs, outs, gammas, betas, True, epsilon, one_minus_momentum, mms, mvs, *_rows(stats, C), act=act)
+        calls.bn_forward(xs, outs, gammas, betas, True, epsilon, one_minus_momentum, mms, mvs, *_rows(stats, C), act=act, entry=_bn_entry(act))
         ctx.save_for_backward(stats, *(xs + tuple(gammas) + tuple(betas)))
         ctx.n, ctx.act = n, act
         return outs
@@ -233,7 +245,7 @@ class _BnAct(torch.autograd.Function):
         grads = torch.empty((n, 2, (C + 3) // 4 * 4), dtype=torch.float32, device=xs[0].device)
         dgammas, dbetas = _rows(grads, C)
         means, _, invstds = _rows(stats, C)
-        calls.bn_backward(xs, dys, dxs, gammas, betas, means, invstds, dgammas, dbetas, act=ctx.act)
+        calls.bn_backward(xs, dys, dxs, gammas, betas, means, invstds, dgammas, dbetas, act=ctx.act, entry=_bn_entry(ctx.act))
         return (None, None, None, None) + dxs + tuple(dgammas) + tuple(dbetas) + (None,) * (2 * n)
 
 
@@ -244,7 +256,8 @@ def batch_norm_relu(x, gamma, beta, moving_mean, moving_variance, training, mome
 
 def batch_norm_act(x, gamma, beta, moving_mean, moving_variance, training, momentum=BATCH_NORM_MOMENTUM, epsilon=BATCH_NORM_EPSILON,
                    act="relu6"):
-    """Batch norm + ReLU (act="relu", layer_utils.py:5-12) or ReLU6 (act="relu6", mobilenet_v1.py:22-41) of x [..., C] with its own gamma, beta and moving statistics [C] -- or of a LIST of
+    """Batch norm + ReLU (act="relu", layer_utils.py:5-12), ReLU6 (act="relu6", mobilenet_v1.py:22-41) or no activation (act="none",
+    shufflenet_v2.py:121,131,135) of x [..., C] with its own gamma, beta and moving statistics [C] -- or of a LIST of
     levels, each argument then a list (one launch sequence for all of them).  training=True: the batch's statistics (biased
     variance), the moving statistics are updated in place (moving -= (moving - batch) * (1 - momentum), unbiased variance);
     gradients flow to x, gamma and beta.  training=False: the inference form (x - moving_mean) * sf + beta that the engine
@@ -252,8 +265,8 @@ def batch_norm_act(x, gamma, beta, moving_mean, moving_variance, training, momen
     single = isinstance(x, torch.Tensor)
     cols = [[v] if single else list(v) for v in (x, gamma, beta, moving_mean, moving_variance)]
     n = len(cols[0])
-    if act not in calls.ACTS:
-        raise ValueError("act must be 'relu' or 'relu6'")
+    if act not in calls.SN_ACTS:
+        raise ValueError("act must be 'relu', 'relu6' or 'none'")
     if n < 1 or n > 8 or any(len(c) != n for c in cols):
         raise ValueError("batch_norm_act takes 1 .. 8 levels, every argument one entry per level")
     C = cols[0][0].shape[-1]
@@ -269,8 +282,92 @@ def batch_norm_act(x, gamma, beta, moving_mean, moving_variance, training, momen
     else:
         xs = [v.detach().contiguous() for v in cols[0]]
         outs = [torch.empty_like(v) for v in xs]
-        calls.bn_forward(xs, outs, cols[1], cols[2], False, eps, 0.0, cols[3], cols[4], act=act)
+        calls.bn_forward(xs, outs, cols[1], cols[2], False, eps, 0.0, cols[3], cols[4], act=act, entry=_bn_entry(act))
     return outs[0] if single else list(outs)
+
+
+# ----------------------------------------------------------------------------- ShuffleNet's copies and its max pool
+def _pair(x, y, who):
+    _need(x, "x")
+    _need(y, "y")
+    if x.dim() < 1 or x.shape != y.shape:
+        raise ValueError("%s: x and y must be [..., D] tensors of one shape" % who)
+
+
+class _Shuffle(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y):
+        x, y = x.contiguous(), y.contiguous()
+        xo, yo = torch.empty_like(x), torch.empty_like(y)
+        calls.shuffle(x, y, xo, yo)
+        return xo, yo
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dxo, dyo):
+        dxo, dyo = dxo.contiguous(), dyo.contiguous()
+        dx, dy = torch.empty_like(dxo), torch.empty_like(dyo)
+        calls.shuffle(dxo, dyo, dx, dy, transpose=True)
+        return dx, dy
+
+
+def concat_shuffle_split(x, y):
+    """concat_shuffle_split (shufflenet_v2.py:94-115) of x, y [..., D]: z[2i] = x[i], z[2i+1] = y[i] -> (z[:D], z[D:]), a copy of bit
+    patterns; the gradients of x and y are the transpose of that copy."""
+    _pair(x, y, "concat_shuffle_split")
+    return _Shuffle.apply(x, y)
+
+
+class _Concat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y):
+        x, y = x.contiguous(), y.contiguous()
+        out = torch.empty(x.shape[:-1] + (2 * x.shape[-1],), dtype=torch.float32, device=x.device)
+        calls.concat(x, y, out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        g = g.contiguous()
+        dx = torch.empty(g.shape[:-1] + (g.shape[-1] // 2,), dtype=torch.float32, device=g.device)
+        dy = torch.empty_like(dx)
+        calls.split(g, dx, dy)
+        return dx, dy
+
+
+def concat_channels(x, y):
+    """tf.concat([x, y], axis=3) of two halves [..., D] (shufflenet_v2.py:89) -> [..., 2D]; the gradient splits again."""
+    _pair(x, y, "concat_channels")
+    return _Concat.apply(x, y)
+
+
+class _MaxPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        from . import ssd
+        x = x.contiguous()
+        with torch.cuda.device(x.device):
+            out = ssd.maxpool3x3s2(x)
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        calls.maxpool_backward(x, dy.contiguous(), dx)
+        return dx
+
+
+def maxpool3x3s2_train(x):
+    """slim.max_pool2d 3x3, stride 2, 'SAME' (shufflenet_v2.py:51-54) of x [B,H,W,C], H and W even, C a multiple of 4: the forward is
+    ssd_amd.ssd.maxpool3x3s2; the gradient of a window goes to its first maximal tap in row-major order."""
+    _need(x, "x")
+    if x.dim() != 4 or (x.shape[1] | x.shape[2]) & 1 or x.shape[3] % 4:
+        raise ValueError("x must be [B,H,W,C] with even H and W and C a multiple of 4")
+    return _MaxPool.apply(x)
 
 
 # ----------------------------------------------------------------------------- a block's variables
