@@ -13,30 +13,7 @@ sum is covered by the chain's own error term many times over).  This pins 2^-9, 
 the GPU."""
 import numpy as np
 
-K = 2304
-U_PIPE = 2.0 ** -22
-
-
-def f16_up(v):
-    """float64 array >= 0 -> smallest normal f16 value (or inf) >= v; 0 -> 0."""
-    v = np.asarray(v, np.float64)
-    with np.errstate(over="ignore"):
-        h = v.astype(np.float16)
-        low = h.astype(np.float64) < v
-        h = np.where(low, np.nextafter(h, np.float16(np.inf)), h)
-    out = h.astype(np.float64)
-    return np.where(v > 0, np.maximum(out, 2.0 ** -14), 0.0)
-
-
-def f16_down(v):
-    """float64 array >= 0 -> largest normal f16 value <= v (a subnormal result: 0; inf: 65504)."""
-    v = np.asarray(v, np.float64)
-    with np.errstate(over="ignore"):
-        h = v.astype(np.float16)
-        high = h.astype(np.float64) > v
-        h = np.where(high, np.nextafter(h, np.float16(-np.inf)), h)
-    out = np.minimum(h.astype(np.float64), 65504.0)
-    return np.where(out < 2.0 ** -14, 0.0, out)
+from helpers.logit_screen_ref import E_PIPE, K, U_PIPE, envelope, f16_down, f16_up, screen_constant
 
 
 def fmaf_chain(x, w, bias):
@@ -65,8 +42,8 @@ def perturbed_sum(terms, rng):
     return outs          # random, low, high
 
 
-def bound(x, w, bias, rng):
-    """The smallest U over the perturbations tried (fp32), per row."""
+def bounds(x, w, bias, rng):
+    """U per perturbation tried (fp32, per row): [random errors, P as low and N as high as the pipe may make them]."""
     xu = f16_up(x.astype(np.float64))
     wp = f16_up(np.maximum(w, 0).astype(np.float64))
     wn = f16_down(np.maximum(-w, 0).astype(np.float64))
@@ -77,14 +54,22 @@ def bound(x, w, bias, rng):
         c = b + np.ldexp(wn.sum(axis=1) * (1.0 + 1e-9), -14) + np.ldexp(np.abs(b), -20) + 1e-30
         cst = c.astype(np.float32)
         cst = np.where(cst.astype(np.float64) < c, np.nextafter(cst, np.float32(np.inf)), cst).astype(np.float32)
-        worst = None
-        for Ph, Nh in ((P[0], N[0]), (P[1], N[2])):          # random errors; P as low and N as high as the pipe may make them
+        out = []
+        for Ph, Nh in ((P[0], N[0]), (P[1], N[2]), (P[2], N[1])):       # the third: P high, N low -- the largest U the pipe may give
             Pf, Nf = Ph.astype(np.float32), Nh.astype(np.float32)
             t1 = (Pf * np.float32(1.001953125)).astype(np.float32)
             t2 = (Nf * np.float32(0.998046875)).astype(np.float32)
             u = ((t1 - t2).astype(np.float32) + cst).astype(np.float32)
             u = (u + (np.float32(2.0 ** -18) * ((Pf + Nf).astype(np.float32) + np.abs(cst)).astype(np.float32)).astype(np.float32)).astype(np.float32)
-            worst = u if worst is None else np.where(np.isnan(u) | np.isnan(worst), np.float32(np.nan), np.minimum(u, worst))
+            out.append(u)
+    return out
+
+
+def bound(x, w, bias, rng):
+    """The smallest U over the first two perturbations (fp32), per row."""
+    worst = None
+    for u in bounds(x, w, bias, rng)[:2]:
+        worst = u if worst is None else np.where(np.isnan(u) | np.isnan(worst), np.float32(np.nan), np.minimum(u, worst))
     return worst
 
 
@@ -145,3 +130,30 @@ def test_directed_roundings_bracket_their_operand():
     norm = (v >= 2.0 ** -14) & (v <= 65504)
     assert (up[norm] <= v[norm] * (1 + 2.0 ** -10)).all() and (dn[norm] >= v[norm] * (1 - 2.0 ** -10)).all()
     assert f16_up(np.array([0.0]))[0] == 0.0 and np.isinf(f16_up(np.array([65505.0]))[0])
+
+
+def test_envelope_is_never_below_the_screen_bound_and_not_vacuous():
+    """helpers/logit_screen_ref.py: U_hi, from the exact sums alone, is at or above U for every perturbed summation order
+    (the pipe's errors random, against the bound, and for it), and it still leaves octets unmarked."""
+    rng = np.random.default_rng(950)
+    lo = np.float32(np.log(0.15 / 0.85) - 1e-3 * (1.0 + abs(np.log(0.15 / 0.85))))      # conservative_logit_bound(0.15) of csrc/plan.hip
+    kinds = ["plain", "overflow", "subnormal", "zero", "negative", "positive", "tiny_w", "mixed_scale", "cancel"]
+    marked = {}
+    for kind, n, k in [(kd, 400, K) for kd in kinds] + [(kd, 4000, 72) for kd in kinds]:
+        x, w, bias = draws(rng, n, kind, k)
+        xu = f16_up(x.astype(np.float64))
+        wp = f16_up(np.maximum(w, 0).astype(np.float64))
+        wn = f16_down(np.maximum(-w, 0).astype(np.float64))
+        with np.errstate(over="ignore", invalid="ignore"):
+            hi = envelope((xu * wp).sum(axis=1), (xu * wn).sum(axis=1), screen_constant(wn.sum(axis=1), bias))
+            for which, U in enumerate(bounds(x, w, bias, rng)):
+                bad = hi < U
+                assert not bad.any(), (kind, k, which, int(bad.sum()), float((U - hi)[bad].max()))
+            may = ~(hi < lo)
+        octs = may.reshape(-1, 8).any(axis=1)           # 8 consecutive draws as the 8 columns of an octet
+        marked[(kind, k)] = (int(octs.sum()), octs.size)
+        print("%-12s K=%-4d envelope marks %d of %d octets" % ((kind, k) + marked[(kind, k)]))
+    assert E_PIPE == K * U_PIPE
+    for key in (("plain", K), ("plain", 72)):
+        assert 0 < marked[key][0] < marked[key][1], (key, marked[key])
+    assert sum(m for m, _ in marked.values()) < sum(t for _, t in marked.values())
