@@ -1,22 +1,23 @@
-"""GPU-side helpers shared by tests/test_gpu_backbone_train.py and tests/test_gpu_train_scale.py: the depthwise and the first
-convolution's backward (include/ssd_hip.h, "the TRAIN backbone", "the TRAIN first convolution") through ssd.train_calls on
-device tensors, and bit equality on the device."""
+"""GPU-side helpers shared by tests/test_gpu_backbone_train.py, tests/test_gpu_train_scale.py and tests/
+test_gpu_shufflenet_train_scale.py: the depthwise and the first convolution's backward (include/ssd_hip.h, "the TRAIN backbone",
+"the TRAIN first convolution"; entry "sn_depthwise": "the TRAIN ShuffleNet") through ssd.train_calls on device tensors, and bit
+equality on the device."""
 from helpers.head_train_gpu import dev, exact_workspace
 
 
-def dw_backward_dev(ssd, cuda, X, Wt, DY, stride, with_dx=True):
-    """ssd_depthwise_train_backward on device tensors with a workspace of exactly the size its planner asks for; the outputs are
-    pre-filled with NaN.  -> (dx or None, dw) on the device."""
+def dw_backward_dev(ssd, cuda, X, Wt, DY, stride, with_dx=True, entry="depthwise"):
+    """ssd_depthwise_train_backward (entry "sn_depthwise": ssd_sn_depthwise_train_backward) on device tensors with a workspace of
+    exactly the size its planner asks for; the outputs are pre-filled with NaN.  -> (dx or None, dw) on the device."""
     DX = cuda.full_like(X, float("nan")) if with_dx else None
     DW = cuda.full_like(Wt, float("nan"))
-    ws = exact_workspace(cuda, ssd.train_calls.depthwise_workspace_bytes(X, stride))
-    ssd.train_calls.depthwise_backward(X, Wt, DY, DW, stride, DX, workspace=ws)
+    ws = exact_workspace(cuda, ssd.train_calls.depthwise_workspace_bytes(X, stride, entry=entry))
+    ssd.train_calls.depthwise_backward(X, Wt, DY, DW, stride, DX, workspace=ws, entry=entry)
     return DX, DW
 
 
-def dw_backward_raw(ssd, cuda, x, w, dy, stride, with_dx=True):
+def dw_backward_raw(ssd, cuda, x, w, dy, stride, with_dx=True, entry="depthwise"):
     """dw_backward_dev on numpy arrays.  -> (dx or None, dw) as numpy."""
-    DX, DW = dw_backward_dev(ssd, cuda, dev(cuda, x), dev(cuda, w), dev(cuda, dy), stride, with_dx)
+    DX, DW = dw_backward_dev(ssd, cuda, dev(cuda, x), dev(cuda, w), dev(cuda, dy), stride, with_dx, entry)
     return DX.cpu().numpy() if with_dx else None, DW.cpu().numpy()
 
 

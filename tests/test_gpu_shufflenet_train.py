@@ -10,6 +10,7 @@ from helpers import backbone_train_ref as bref
 from helpers import head_train_ref as href
 from helpers import shufflenet_train_ref as ref
 from helpers.head_train_gpu import dev as _dev, exact_workspace, same_bits
+from helpers.shufflenet_train_gpu import bn_raw as _bn_raw, dw_forward as _dw_forward, pw as _pw
 from conftest import TINY_PARAMS
 
 pytestmark = pytest.mark.gpu
@@ -23,13 +24,6 @@ DW_CASES = [(5, 7, 1), (6, 8, 2), (7, 9, 2)]                          # stride 1
 
 
 # ----------------------------------------------------------------------------- the raw calls
-def _dw_forward(ssd, cuda, x, k, stride, entry):
-    X = _dev(cuda, x)
-    out = cuda.full((x.shape[0],) + bref.dw_out_hw(x.shape[1], x.shape[2], stride) + (x.shape[3],), float("nan"), device="cuda")
-    ssd.train_calls.depthwise_forward(X, _dev(cuda, k), out, stride, entry=entry)
-    return out.cpu().numpy()
-
-
 def _dw_backward(ssd, cuda, x, k, dy, stride, entry, with_dx=True):
     X, K, DY = _dev(cuda, x), _dev(cuda, k), _dev(cuda, dy)
     DX = cuda.full_like(X, float("nan")) if with_dx else None
@@ -103,18 +97,6 @@ def test_depthwise_at_8_channels_is_the_old_entry_point_bit_for_bit(ssd, cuda):
 
 
 # ----------------------------------------------------------------------------- 2. pointwise
-def _pw(ssd, cuda, x, k, dy, entry):
-    calls = ssd.train_calls
-    X, K, DY = _dev(cuda, x), _dev(cuda, k), _dev(cuda, dy)
-    need = calls.conv_workspace_bytes([X], X.shape[0], k.shape[2], k.shape[3], 1, entry=entry)
-    ws = exact_workspace(cuda, need)
-    Y = cuda.full_like(DY, float("nan"))
-    calls.conv_forward([X], K, [Y], workspace=None if entry == "pointwise" else ws, entry="conv" if entry == "pointwise" else entry)
-    DX, DW = cuda.full_like(X, float("nan")), cuda.full_like(K, float("nan"))
-    calls.conv_backward([X], K, [DY], DW, dxs=[DX], workspace=ws, entry=entry)
-    return Y.cpu().numpy(), DX.cpu().numpy(), DW.cpu().numpy()
-
-
 @pytest.mark.parametrize("Cin,Cout", [(6, 10), (58, 58), (24, 58), (8, 16)])
 def test_pointwise_forward_and_gradients(ssd, cuda, oracle_ops, Cin, Cout):
     """forward = ssd.conv2d, dx = the oracle's conv2d(dy, w') bit for bit; dw exact on small integers; through autograd the same."""
@@ -140,26 +122,6 @@ def test_pointwise_forward_and_gradients(ssd, cuda, oracle_ops, Cin, Cout):
 
 
 # ----------------------------------------------------------------------------- 3. the batch norm without an activation
-def _bn_raw(ssd, cuda, x, gamma, beta, mm, mv, dy=None, training=1, act="none", entry="sn_bn"):
-    calls = ssd.train_calls
-    C = x.shape[-1]
-    Cp = (C + 3) // 4 * 4
-    X, G, Bt, MM, MV = (_dev(cuda, v) for v in (x, gamma, beta, mm, mv))
-    Y = cuda.full_like(X, float("nan"))
-    st = cuda.full((5, Cp), float("nan"), device="cuda")
-    mean, var, invstd, dgamma, dbeta = [[st[j, :C]] for j in range(5)]
-    ws = exact_workspace(cuda, max(calls.bn_workspace_bytes([X], C), 256))
-    calls.bn_forward([X], [Y], [G], [Bt], training, float(f32(href.EPS)), float(f32(1.0 - href.MOMENTUM)), [MM], [MV], mean, var, invstd,
-                     act=act, workspace=ws, entry=entry)
-    out = dict(y=Y, mm=MM, mv=MV)
-    if dy is not None:
-        DX = cuda.full_like(X, float("nan"))
-        calls.bn_backward([X], [_dev(cuda, dy)], [DX], [G], [Bt], mean, invstd, dgamma, dbeta, act=act, workspace=ws, entry=entry)
-        out["dx"] = DX
-    out.update(mean=st[0, :C], var=st[1, :C], invstd=st[2, :C], dgamma=st[3, :C], dbeta=st[4, :C])
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
 def _bn_inputs(rng, rows, C):
     # gamma 2 .. 4: y = gamma * xhat + beta goes a few percent beyond 6
     return (rng.normal(0.3, 1.5, (rows, C)).astype(f32), rng.uniform(2.0, 4.0, C).astype(f32), rng.normal(0, 0.3, C).astype(f32),
@@ -287,8 +249,9 @@ def test_shuffle_concat_and_split_are_copies_of_bit_patterns(ssd, cuda, oracle_o
     assert same_bits(tx2.grad.cpu().numpy(), dc[:, :D]) and same_bits(ty2.grad.cpu().numpy(), dc[:, D:])
 
 
-@pytest.mark.parametrize("D", [58, 24])
+@pytest.mark.parametrize("D", [58, 24, 1, 122])
 def test_the_copies_go_round_their_grid_more_than_once(ssd, cuda, oracle_ops, D):
+    """58 and 122: two words per access, 24: four, 1: one -- every instance of sn_copy_kernel past one pass of its capped grid."""
     rows = ref.copy_rows_past_one_grid_pass(D)
     rng = np.random.default_rng(D + 1)
     x = rng.integers(0, 2 ** 32, (rows, D), dtype=np.uint64).astype(np.uint32).view(f32)
