@@ -801,6 +801,39 @@ size_t ssd_first_conv_train_workspace_bytes(int32_t B, int32_t H, int32_t W, int
 int ssd_first_conv_train_backward(const uint8_t *images_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t Cout,
                                   float *dw_dev /* [3,3,3,Cout] */, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- the TRAIN first convolution from float frames: the same layer on float32 [B,H,W,3] images in [0, 1] -------------------------
+ *
+ * What Pipeline(is_training=True) / ssd_augment yield and the reference's backbones take (mobilenet_v1.py:10-11,34 and
+ * shufflenet_v2.py: x = 2.0 * images - 1.0): frames after crop, resize, colour offsets, grayscale and the random scale, which are
+ * NOT on the byte grid.  Conventions are those of the block above: the caller's device pointers, the TF-layout kernel [3,3,3,Cout]
+ * in DEVICE memory, the caller's workspace, SSD_ERR_INVALID with the argument named in ssd_last_error() before any HIP call,
+ * enqueue only, no synchronisation, no atomics: two calls give the same bits.
+ *
+ * images_dev [B,H,W,3] float32 NHWC at the network's own size, H and W even; out / dy [B,H/2,W/2,Cout]; Cout a multiple of 4, at
+ * most 64; every float pointer and the workspace 16-byte aligned.  The kernels address the frames through a buffer resource with
+ * 32-bit byte offsets: B*H*W*12 < 2^31 bytes (312 frames of 640 x 896); a larger batch is refused and the workspace call returns
+ * 0 for it.
+ *
+ * The pixel value is q(x) = fp32(2 * x - 1): 2 * x is exact, so ONE rounding; no contraction, no clamp, no special case -- what
+ * the pipeline clipped to [0, 1] stays there, anything else goes through as IEEE arithmetic takes it.  Consequence: for
+ * x = fp32(u * inv255), the first step of ssd_augment, q(x) is the block above's p(u) bit for bit, so frames on the byte grid
+ * give the uint8 calls' results, forward and dw.
+ *
+ * ssd_first_conv_f32_train_forward   raw, no batch norm, no activation: per output ONE fmaf chain from +0 over the taps
+ *   row-major, ci ascending within a tap, a tap outside the input (row H, column W) contributing fmaf(0, w, acc): bit-identical
+ *   to the CPU oracle's conv2d(q(images), w, stride 2) with q computed in fp32.
+ * ssd_first_conv_f32_train_backward  from the images and dy:
+ *   dw_dev [3,3,3,Cout]   dw[ky,kx,ci,co] = sum over b, oy, ox of q(images[b,2oy+ky,2ox+kx,ci]) * dy[b,oy,ox,co], positions outside
+ *     the input contributing nothing: products and sums in double, rounded ONCE, in the two-stage slab order of
+ *     ssd_first_conv_train_backward with C = Cout (the same slab_rows, lanes and slabs), partial sums [slabs][27][Cout] doubles
+ *     in the workspace, which ssd_first_conv_f32_train_workspace_bytes sizes by the same formula (0: the sizes would be refused).
+ * There is no data gradient.  Not here: a resize, NCHW frames, quantising the floats back to bytes. */
+int ssd_first_conv_f32_train_forward(const float *images_dev, int32_t B, int32_t H, int32_t W, const float *w_dev /* [3,3,3,Cout] */,
+                                     int32_t Cout, float *out_dev, void *stream);
+size_t ssd_first_conv_f32_train_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t Cout);
+int ssd_first_conv_f32_train_backward(const float *images_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t Cout,
+                                      float *dw_dev /* [3,3,3,Cout] */, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---- the TRAIN ShuffleNet: what ShuffleNet-v2 in TRAIN mode needs beyond the TRAIN backbone (shufflenet_v2.py:9-135) --------------
  *
  * ShuffleNet-v2 is Conv1 (the first convolution with 24 channels, batch norm + ReLU), a 3x3 stride-2 max pool, three stages of

@@ -8,14 +8,16 @@ train.py:44-50 warm-starts the backbone and then trains it with everything else;
 a MODE of this project and not parity with the reference: BY DEFAULT Conv2d_0 stays FROZEN.  It runs in the
 engine's inference form (ssd.first_conv on its moving statistics); Conv2d_1 .. Conv2d_13 -- 13 depthwise and 13 pointwise layers,
 each followed by a batch norm and ReLU6 -- run on batch statistics and all their variables train.  train_first=True (DESIGN.md
-4.14) trains Conv2d_0 as well, the reference's recipe: first_conv_train on the uint8 frames, then the batch norm on batch
-statistics.  The ops (first_conv_train, depthwise_conv, pointwise_conv, batch_norm_act) and the variable loading
+4.14) trains Conv2d_0 as well, the reference's recipe: first_conv_train on uint8 frames or first_conv_train_float on the float32
+batches TrainPipeline yields, then the batch norm on batch statistics.  The ops (first_conv_train,
+first_conv_train_float, depthwise_conv, pointwise_conv, batch_norm_act) and the variable loading
 (ReferenceVariables) are train_ops.py's; this file keeps the layer table and the graph.
 """
 import numpy as np
 import torch
 
-from .train_ops import BATCH_NORM_EPSILON, ReferenceVariables, depthwise_conv, first_conv_train, pointwise_conv
+from .train_ops import (BATCH_NORM_EPSILON, ReferenceVariables, batch_norm_act, depthwise_conv, first_conv_train, first_conv_train_float,
+                        pointwise_conv)
 from .variables import MOBILENET_LAYERS
 
 FIRST = "MobilenetV1/Conv2d_0"
@@ -37,7 +39,7 @@ class TrainableMobileNet(ReferenceVariables):
     params   the model config (backbone "mobilenet", depth_multiplier <= 1.0: the batch norm takes at most 1024 channels)
     weights  {reference variable name: float32 array in TF layout}; every MobilenetV1/* variable must be there (the reference never
              initialises a backbone from scratch: a missing one is a KeyError, not a draw)
-    forward(images uint8 [B,H,W,3] on the GPU, at the network's size: H and W even) -> [c3, c4, c5] NHWC float32, the outputs of
+    forward(images uint8 or float32 [B,H,W,3] on the GPU, at the network's size: H and W even) -> [c3, c4, c5] NHWC float32, the outputs of
     Conv2d_5, Conv2d_11 and Conv2d_13's pointwise layers.  .train(): batch statistics through batch_norm_act, the moving statistics
     of Conv2d_1 .. 13 move; .eval(): the engine's c3, c4, c5 bit for bit (raw depthwise, the inference batch norm + ReLU6, the raw
     1x1, the inference batch norm + ReLU6).  named_variables() / statistics() hold Conv2d_1 .. 13 only; frozen_variables() returns
@@ -46,7 +48,10 @@ class TrainableMobileNet(ReferenceVariables):
     train_first=True trains Conv2d_0 too: its kernel, gamma and beta join named_variables() (81 variables) and its moving statistics
     statistics() (54), frozen_variables() returns {}; .train() runs first_conv_train and batch_norm_act on batch statistics (Conv2d_0's
     moving statistics move), .eval() the same raw convolution and the inference batch norm + ReLU6 -- still the engine's c3, c4, c5
-    bit for bit; keep_features=True also keeps features["Conv2d_0"]."""
+    bit for bit; keep_features=True also keeps features["Conv2d_0"].
+    float32 frames are the batches TrainPipeline yields, in [0, 1] (pixel value 2x - 1): first_conv_train_float in
+    place of first_conv_train, the same batch norm; with Conv2d_0 frozen the raw float convolution on the frozen kernel and the
+    inference batch norm + ReLU6.  On frames u * (1 / 255) every result has the bits of the uint8 frames u."""
 
     def __init__(self, params, weights, device=None, seed=0, keep_features=False, train_first=False):
         if params.get("backbone") != "mobilenet":
@@ -69,6 +74,7 @@ class TrainableMobileNet(ReferenceVariables):
         trained = {k: v for k, v in shapes.items() if self.train_first or not k.startswith(FIRST + "/")}
         super().__init__(trained, weights, lambda name, shape, rng: None, device, seed)
         self._frozen = frozen
+        self._frozen_dev = {}
         self.params = dict(params)
         self.keep_features = bool(keep_features)
         self.features = {}
@@ -84,15 +90,34 @@ class TrainableMobileNet(ReferenceVariables):
         ({} with train_first)."""
         return {k: v.copy() for k, v in self._frozen.items()}
 
+    def _frozen_on(self, device):
+        """Conv2d_0's frozen arrays on `device` for the float route: plain tensors, no variables (no gradient, not in
+        named_variables() / statistics()), copied once per device from the arrays frozen_variables() returns."""
+        dev = self._frozen_dev.get(device)
+        if dev is None:
+            dev = self._frozen_dev[device] = {k: torch.from_numpy(v.copy()).to(device) for k, v in self._frozen.items()}
+        return dev
+
     def first_conv(self, images):
-        """Conv2d_0: uint8 frames -> 2x/255 - 1 -> 3x3 stride 2 -> batch norm -> ReLU6.  Frozen: the engine's inference form on the
-        moving statistics.  train_first: the raw convolution with a weight gradient, then the batch norm in the module's mode."""
+        """Conv2d_0: frames -> pixel values in [-1, 1] -> 3x3 stride 2 -> batch norm -> ReLU6, from uint8 frames (2u/255 - 1) or from
+        float32 frames in [0, 1] (2x - 1: TrainPipeline's batches; on u * (1 / 255) the bits of the uint8 route).  Frozen: the
+        engine's inference form on the moving statistics -- uint8: ssd.first_conv; float32: the raw float convolution on a device
+        copy of the frozen kernel, then the inference batch norm + ReLU6, without a gradient.  train_first: the raw convolution with
+        a weight gradient, then the batch norm in the module's mode."""
         from . import ssd
-        if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4
+        if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype in (torch.uint8, torch.float32) and images.dim() == 4
                 and images.shape[3] == 3):
-            raise TypeError("images must be a uint8 [B,H,W,3] tensor on a GPU")
+            raise TypeError("images must be a uint8 or float32 [B,H,W,3] tensor on a GPU")
         if (images.shape[1] | images.shape[2]) & 1:
             raise ValueError("images: even height and width (the network's size)")
+        if images.dtype == torch.float32:
+            if self.train_first:
+                return self._bn(first_conv_train_float(images, self.variable(FIRST + "/weights")), FIRST)
+            f = self._frozen_on(images.device)
+            with torch.no_grad():
+                raw = first_conv_train_float(images, f[FIRST + "/weights"])
+                return batch_norm_act(raw, *[f["%s/BatchNorm/%s" % (FIRST, leaf)] for leaf in ("gamma", "beta", "moving_mean", "moving_variance")],
+                                      training=False, act="relu6")
         if self.train_first:
             return self._bn(first_conv_train(images, self.variable(FIRST + "/weights")), FIRST)
         with torch.cuda.device(images.device):

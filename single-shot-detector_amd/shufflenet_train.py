@@ -8,15 +8,16 @@ It mirrors backbone_train.TrainableMobileNet point for point, with the same MODE
 reference: BY DEFAULT Conv1 stays FROZEN and runs in the engine's inference form (ssd.first_conv on its
 moving statistics, then ssd.maxpool3x3s2); the three stages and Conv5 -- 55 convolutions, each followed by a batch norm, the
 depthwise ones without an activation -- run on batch statistics and all their variables train.  train_first=True trains Conv1 as
-well, the reference's recipe: first_conv_train on the uint8 frames, the batch norm + ReLU on batch statistics, maxpool3x3s2_train.
-The ops (first_conv_train, depthwise_conv, pointwise_conv, batch_norm_act, concat_shuffle_split, concat_channels,
+well, the reference's recipe: first_conv_train on uint8 frames or first_conv_train_float on the float32 batches TrainPipeline
+yields, the batch norm + ReLU on batch statistics, maxpool3x3s2_train.
+The ops (first_conv_train, first_conv_train_float, depthwise_conv, pointwise_conv, batch_norm_act, concat_shuffle_split, concat_channels,
 maxpool3x3s2_train) and the variable loading (ReferenceVariables) are train_ops.py's; this file keeps the unit table and the graph.
 """
 import numpy as np
 import torch
 
-from .train_ops import (BATCH_NORM_EPSILON, ReferenceVariables, concat_channels, concat_shuffle_split, depthwise_conv, first_conv_train,
-                        maxpool3x3s2_train, pointwise_conv)
+from .train_ops import (BATCH_NORM_EPSILON, ReferenceVariables, batch_norm_act, concat_channels, concat_shuffle_split, depthwise_conv,
+                        first_conv_train, first_conv_train_float, maxpool3x3s2_train, pointwise_conv)
 from .variables import SHUFFLENET_DEPTHS
 
 FIRST = "ShuffleNetV2/Conv1"
@@ -41,12 +42,15 @@ class TrainableShuffleNet(ReferenceVariables):
              the batch norm takes at most 1024)
     weights  {reference variable name: float32 array in TF layout}; every ShuffleNetV2/* variable must be there (a missing one is a
              KeyError, not a draw)
-    forward(images uint8 [B,H,W,3] on the GPU, H and W multiples of 32) -> [c3, c4, c5] NHWC float32: Stage2, Stage3 and Conv5.
+    forward(images uint8 or float32 [B,H,W,3] on the GPU, H and W multiples of 32) -> [c3, c4, c5] NHWC float32: Stage2, Stage3 and Conv5.
     .train(): all 56 batch norms (55 with Conv1 frozen) on batch statistics, their moving statistics move; .eval(): the engine's c3,
     c4, c5 bit for bit.  named_variables() / statistics() hold 165 + 110 variables and frozen_variables() the 5 Conv1 arrays for
     TrainStep(..., frozen=backbone.frozen_variables()); with train_first=True 168 + 112 and {}.  keep_features=True keeps the
     post-batch-norm tensor of every layer of the last forward in .features under its scope name (without the "ShuffleNetV2/" prefix
-    and the "/batch_norm" suffix; "Conv1" with train_first only), plus "MaxPool", "Stage2" .. "Stage4" and "Conv5" (detached)."""
+    and the "/batch_norm" suffix; "Conv1" with train_first only), plus "MaxPool", "Stage2" .. "Stage4" and "Conv5" (detached).
+    float32 frames are the batches TrainPipeline yields, in [0, 1] (pixel value 2x - 1): first_conv_train_float in
+    place of first_conv_train; with Conv1 frozen the raw float convolution on the frozen kernel, the inference batch norm + ReLU and
+    the inference max pool.  On frames u * (1 / 255) every result has the bits of the uint8 frames u."""
 
     def __init__(self, params, weights, device=None, seed=0, keep_features=False, train_first=False):
         if params.get("backbone") != "shufflenet":
@@ -69,6 +73,7 @@ class TrainableShuffleNet(ReferenceVariables):
         trained = {k: v for k, v in shapes.items() if self.train_first or not k.startswith(FIRST + "/")}
         super().__init__(trained, weights, lambda name, shape, rng: None, device, seed)
         self._frozen = frozen
+        self._frozen_dev = {}
         self.params = dict(params)
         self.keep_features = bool(keep_features)
         self.features, self._feats = {}, {}
@@ -84,21 +89,41 @@ class TrainableShuffleNet(ReferenceVariables):
         train_first)."""
         return {k: v.copy() for k, v in self._frozen.items()}
 
+    def _frozen_on(self, device):
+        """Conv1's frozen arrays on `device` for the float route: plain tensors, no variables (no gradient, not in named_variables() /
+        statistics()), copied once per device from the arrays frozen_variables() returns."""
+        dev = self._frozen_dev.get(device)
+        if dev is None:
+            dev = self._frozen_dev[device] = {k: torch.from_numpy(v.copy()).to(device) for k, v in self._frozen.items()}
+        return dev
+
     def first_conv(self, images):
-        """Conv1 and MaxPool: uint8 frames -> 2x/255 - 1 -> 3x3 stride 2 -> batch norm -> ReLU -> 3x3 stride-2 max pool.  Frozen: the
-        engine's inference form on the moving statistics.  train_first: the raw convolution with a weight gradient, the batch norm
-        in the module's mode and the max pool with its gradient."""
+        """Conv1 and MaxPool: frames -> pixel values in [-1, 1] -> 3x3 stride 2 -> batch norm -> ReLU -> 3x3 stride-2 max pool, from uint8
+        frames (2u/255 - 1) or from float32 frames in [0, 1] (2x - 1: TrainPipeline's batches; on u * (1 / 255) the bits of the uint8
+        route).  Frozen: the engine's inference form on the moving statistics -- uint8: ssd.first_conv; float32: the raw float
+        convolution on a device copy of the frozen kernel, then the inference batch norm + ReLU, without a gradient -- and the
+        inference max pool.  train_first: the raw convolution with a weight gradient, the batch norm in the module's mode and the max
+        pool with its gradient."""
         from . import ssd
-        if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4
+        if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype in (torch.uint8, torch.float32) and images.dim() == 4
                 and images.shape[3] == 3):
-            raise TypeError("images must be a uint8 [B,H,W,3] tensor on a GPU")
+            raise TypeError("images must be a uint8 or float32 [B,H,W,3] tensor on a GPU")
         if images.shape[1] % 32 or images.shape[2] % 32:
             raise ValueError("images: height and width must be multiples of 32 (the network's stride)")
         self._feats = {}
+        first = first_conv_train_float if images.dtype == torch.float32 else first_conv_train
         if self.train_first:
-            x = self._bn(first_conv_train(images, self.variable(FIRST + "/weights")), FIRST)
+            x = self._bn(first(images, self.variable(FIRST + "/weights")), FIRST)
             self._keep("Conv1", x)
             x = maxpool3x3s2_train(x)
+        elif images.dtype == torch.float32:
+            f = self._frozen_on(images.device)
+            with torch.no_grad():
+                x = batch_norm_act(first(images, f[FIRST + "/weights"]),
+                                   *[f["%s/batch_norm/%s" % (FIRST, leaf)] for leaf in ("gamma", "beta", "moving_mean", "moving_variance")],
+                                   training=False, act="relu")
+            with torch.cuda.device(images.device):
+                x = ssd.maxpool3x3s2(x)
         else:
             with torch.cuda.device(images.device):
                 x = ssd.maxpool3x3s2(ssd.first_conv(images.contiguous(), self._frozen[FIRST + "/weights"], self._first_bn, "relu"))

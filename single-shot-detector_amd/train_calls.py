@@ -1,5 +1,5 @@
 """How a TRAIN entry point of include/ssd_hip.h is called ("the TRAIN head", "the TRAIN FPN", "the TRAIN backbone", "the TRAIN first
-convolution", "the TRAIN ShuffleNet"): the only module that fills ssd_conv_level / ssd_bn_level, orders the arguments, sizes the workspace and passes the
+convolution" from uint8 and from float frames, "the TRAIN ShuffleNet"): the only module that fills ssd_conv_level / ssd_bn_level, orders the arguments, sizes the workspace and passes the
 stream.  One function per entry point family, no autograd, no model.  Arguments are torch tensors, None exactly where the header
 allows NULL; every result is the CALLER's tensor.  Before the library is called every tensor is checked against the shape the
 geometry implies (ValueError naming the argument: shape, dtype, contiguity, level counts) and then for lying on one GPU
@@ -280,6 +280,32 @@ def first_conv_backward(images, dy, dw, workspace=None):
     L = lib()
     _run(dev, workspace, lambda: L.ssd_first_conv_train_workspace_bytes(B, H, W, Cout),
          lambda *tail: L.ssd_first_conv_train_backward(images.data_ptr(), dy.data_ptr(), B, H, W, Cout, dw.data_ptr(), *tail))
+
+
+def first_conv_f32_forward(images, kernel, out):
+    """ssd_first_conv_f32_train_forward: images float32 [B,H,W,3] in [0, 1], kernel [3,3,3,Cout] -> out [B,H/2,W/2,Cout]."""
+    B, H, W, _ = _dense(images, "images", (None, None, None, 3), torch.float32)
+    Cout = _dense(kernel, "kernel", (3, 3, 3, None))[3]
+    _dense(out, "out", (B, H // 2, W // 2, Cout))
+    dev = _one_gpu(None, images=images, kernel=kernel, out=out)
+    with torch.cuda.device(dev):
+        check(lib().ssd_first_conv_f32_train_forward(images.data_ptr(), B, H, W, kernel.data_ptr(), Cout, out.data_ptr(), stream(dev)))
+
+
+def first_conv_f32_workspace_bytes(images, Cout):
+    """ssd_first_conv_f32_train_workspace_bytes: images is the batch or its (B, H, W)."""
+    return lib().ssd_first_conv_f32_train_workspace_bytes(*tuple(getattr(images, "shape", images))[:3], Cout)
+
+
+def first_conv_f32_backward(images, dy, dw, workspace=None):
+    """ssd_first_conv_f32_train_backward from the images float32 [B,H,W,3] and dy [B,H/2,W/2,Cout]: dw [3,3,3,Cout]."""
+    B, H, W, _ = _dense(images, "images", (None, None, None, 3), torch.float32)
+    Cout = _dense(dy, "dy", (B, H // 2, W // 2, None))[3]
+    _dense(dw, "dw", (3, 3, 3, Cout))
+    dev = _one_gpu(workspace, images=images, dy=dy, dw=dw)
+    L = lib()
+    _run(dev, workspace, lambda: L.ssd_first_conv_f32_train_workspace_bytes(B, H, W, Cout),
+         lambda *tail: L.ssd_first_conv_f32_train_backward(images.data_ptr(), dy.data_ptr(), B, H, W, Cout, dw.data_ptr(), *tail))
 
 
 # ----------------------------------------------------------------------------- the batch norm

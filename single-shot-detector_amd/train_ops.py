@@ -1,6 +1,6 @@
 """The differentiable ops under the trainable modules (include/ssd_hip.h, "the TRAIN head", "the TRAIN FPN" and "the TRAIN
-backbone", "the TRAIN first convolution" and "the TRAIN ShuffleNet"), and nothing about any model: conv_same / conv3x3_same,
-depthwise_conv, pointwise_conv, first_conv_train, batch_norm_act (batch_norm_relu is its act="relu" case), concat_shuffle_split,
+backbone", "the TRAIN first convolution" (from uint8 and from float frames) and "the TRAIN ShuffleNet"), and nothing about any model: conv_same / conv3x3_same,
+depthwise_conv, pointwise_conv, first_conv_train, first_conv_train_float, batch_norm_act (batch_norm_relu is its act="relu" case), concat_shuffle_split,
 concat_channels and maxpool3x3s2_train are torch.autograd.Functions over the C entry points (once differentiable), fpn_merge_backward is
 ssd_fpn_merge_backward, and ReferenceVariables is the torch.nn.Module base that holds a block's variables under their reference
 names.  The Functions allocate the results and keep what the backward needs; how an entry point is called (the level structs, the
@@ -207,6 +207,48 @@ def first_conv_train(images, kernel):
     if not (images.is_cuda and kernel.is_cuda):
         raise TypeError("images and kernel must be on a GPU (there is no CPU path)")
     return _FirstConv.apply(images, kernel)
+
+
+class _FirstConvFloat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, images, kernel):
+        images, kernel = images.contiguous(), kernel.contiguous()
+        B, H, W, _ = images.shape
+        out = torch.empty((B, H // 2, W // 2, kernel.shape[3]), dtype=torch.float32, device=images.device)
+        calls.first_conv_f32_forward(images, kernel, out)
+        ctx.save_for_backward(images)
+        ctx.Cout = kernel.shape[3]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        images, = ctx.saved_tensors
+        dw = torch.empty((3, 3, 3, ctx.Cout), dtype=torch.float32, device=images.device)
+        calls.first_conv_f32_backward(images, dy.contiguous(), dw)
+        return None, dw
+
+
+def first_conv_train_float(images, kernel):
+    """first_conv_train on the batches TrainPipeline yields: images float32 [B,H,W,3] in [0, 1] on the GPU at the network's own size
+    (H and W even), kernel [3,3,3,Cout], Cout a multiple of 4 and at most 64.  The pixel value is the reference's 2 * x - 1
+    (mobilenet_v1.py:34), one rounding, no clamp: on frames u * (1 / 255) the forward and the kernel's gradient have the bits of
+    first_conv_train on the bytes u.  The gradient flows to the kernel only (the input is the image; it must not require one)."""
+    if not (isinstance(images, torch.Tensor) and images.dtype == torch.float32):
+        raise TypeError("images must be a float32 tensor on a GPU (there is no CPU path)")
+    if not (isinstance(kernel, torch.Tensor) and kernel.dtype == torch.float32):
+        raise TypeError("kernel must be a float32 tensor on a GPU (there is no CPU path)")
+    if images.dim() != 4 or images.shape[3] != 3 or kernel.dim() != 4 or tuple(kernel.shape[:3]) != (3, 3, 3):
+        raise ValueError("images must be [B,H,W,3] and kernel [3,3,3,Cout]")
+    if (images.shape[1] | images.shape[2]) & 1:
+        raise ValueError("images: even height and width (the network's size)")
+    if kernel.shape[3] % 4 or not 4 <= kernel.shape[3] <= 64:
+        raise ValueError("kernel: Cout must be a multiple of 4 and at most 64")
+    if images.requires_grad:
+        raise ValueError("images must not require a gradient: the first convolution has no data gradient")
+    if not (images.is_cuda and kernel.is_cuda):
+        raise TypeError("images and kernel must be on a GPU (there is no CPU path)")
+    return _FirstConvFloat.apply(images, kernel)
 
 
 # ----------------------------------------------------------------------------- the batch norm
