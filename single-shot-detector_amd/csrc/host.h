@@ -121,8 +121,8 @@ struct ConvW {
     float *wt16w = nullptr;    // wide outputs whose width 256 does not divide (480 class logits): the S16 rows again,
     int CoutPad16 = 0;         //   padded to CoutPad16 = a multiple of 256 rows per tap for the 256x256-tile kernel
     float scale16 = 1.0f;      // 2^-s
-    unsigned short *wscr = nullptr;   // the class logits' screen (logit_screen.hip): [taps][ceil(CoutP / 128) * 256][CinP] f16, per 256-row tile
-                                      //   128 rows max(w, 0) rounded up, 128 rows max(-w, 0) rounded down; scst [CoutP]: the bound's constant term
+    unsigned short *wscr = nullptr;   // the class logits' screen (logit_screen.hip): [taps][ceil(CoutP / 128) * 128][CinP] f16, one signed plane:
+                                      //   max(w, 0) rounded up, or 0x8000 | max(-w, 0) rounded down, never -0; scst [CoutP]: the bound's constant term
     float *scst = nullptr;
     int CinP = 0, CoutP = 0, CoutPad = 0, taps = 1, tile = IGEMM_128x128;
     int Cin_l = 0, Cout_l = 0;

@@ -3,15 +3,19 @@
 // one octet in a thousand.  Four launches on the class tower's stream (DESIGN 4.2 has the derivation of the bound):
 //
 //   convert   the class tower's last output (fp32 rows, x >= 0 behind its ReLU) -> one f16 plane xu >= x, rounded UP and never
-//             subnormal (0 < x < 2^-14 -> 2^-14); x < 0 or NaN -> NaN, which marks.  Also zeroes the row lists' counters.
+//             subnormal (0 < x < 2^-14 -> 2^-14); x < 0 or NaN -> NaN, which marks.
 //   screen    implicit GEMM on v_mfma_f32_32x32x16_f16: P = sum xu * Wp, N = sum xu * Wn with Wp >= max(w, 0) rounded up and
 //             Wn <= max(-w, 0) rounded down (both never subnormal; weights.hip packs them).  Every term of either sum is
 //             non-negative, so ANY summation order and rounding of the matrix pipe is within a relative n * u' of the sum, and
 //                 U = P (1 + 2^-9) - N (1 - 2^-9) + cst + 2^-18 (P + N + |cst|),   cst >= bias + 2^-14 sum Wn + 2^-20 |bias|
 //             is an upper bound of the exact fp32 logit.  The octet's bit is set unless U < scan_lo (written !(U < lo): NaN and
 //             inf mark).  Tile 256 rows x 128 logit columns per block: waves (m, 0) hold P, waves (m, 1) hold N of the same 128
-//             columns -- the B tile's rows 0..127 are Wp, 128..255 Wn.  Staging as igemm16.hip: LDS-DMA, XOR-swizzled 128-B
-//             rows (here 64 channels of f16), zero padding = the buffer range check, two stages of 64 KB.
+//             columns.  For every (k, column) at most one of Wp, Wn is non-zero, so the B tile is ONE signed plane (Wp as it
+//             is, Wn with the sign bit set, never -0) of 128 rows that both waves of a pair read; each takes its operand
+//             with integer operations on the halves (screen_operand).  Staging as igemm16.hip: LDS-DMA, XOR-swizzled 128-B
+//             rows (here 64 channels of f16), zero padding = the buffer range check; a ring of three stages of 48 KB with
+//             counted waits, fragments of the next 16-channel step read under the MFMAs of this one.  Block 0 also zeroes
+//             the row lists' counters.
 //   compact   bitmap -> per column octet the list of marked rows (one LDS counter set per block, one global add per block and
 //             column octet).
 //   fill      per marked octet the 8 logits EXACTLY: acc = fmaf(x_k, w_k, acc) from +0 over k = tap-major, then logical input
@@ -25,7 +29,12 @@ typedef float v16f __attribute__((ext_vector_type(16)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef _Float16 v8h __attribute__((ext_vector_type(8)));
+typedef short v2s __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void *lds_ptr_t;
+
+// the screen's LDS ring: a stage is a 256-row A tile + a 128-row B tile of 128-B rows
+#define SCREEN_STAGE_BYTES ((256 + 128) * 128)
+#define SCREEN_STAGES 3
 
 // x >= 0 -> the smallest normal f16 (or inf) that is >= x, 0 for 0; anything else (x < 0, NaN) -> NaN
 __device__ __forceinline__ unsigned f16_up_bits(float x)
@@ -38,10 +47,8 @@ __device__ __forceinline__ unsigned f16_up_bits(float x)
     return b < 0x0400u ? 0x0400u : b;
 }
 
-__global__ __launch_bounds__(256) void logit_convert_kernel(const float *__restrict__ x, unsigned short *__restrict__ x16, long long n8,
-                                                            int *__restrict__ counts, int ncounts)
+__global__ __launch_bounds__(256) void logit_convert_kernel(const float *__restrict__ x, unsigned short *__restrict__ x16, long long n8)
 {
-    if (blockIdx.x == 0 && (int)threadIdx.x < ncounts) counts[threadIdx.x] = 0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
         const v4f a = *(const v4f *)(x + i * 8), b = *(const v4f *)(x + i * 8 + 4);
         v4u o;
@@ -71,16 +78,32 @@ __device__ __forceinline__ ScreenLevel screen_level_of_row(const ScreenArgs &a, 
     return L;
 }
 
+// the operand of a wave from a fragment of the signed plane, on the 16-bit halves as integers: sgn = 0 keeps the halves with
+// the sign clear (Wp: a NaN stays a NaN), sgn = 0x80008000 flips the signs first and so keeps the magnitudes of the others
+// (Wn); everything else becomes +0.  (A floating-point max would drop the NaNs.)
+__device__ __forceinline__ v8h screen_operand(v4u f, unsigned sgn)
+{
+    v4u o;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const v2s h = __builtin_bit_cast(v2s, f[d] ^ sgn);
+        o[d] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(h, v2s{0, 0}));
+    }
+    return __builtin_bit_cast(v8h, o);
+}
+
 __global__ __launch_bounds__(256, 1) void logit_screen_kernel(const ScreenArgs a)
 {
     constexpr int BM = 256;
     constexpr int A_BYTES = BM * 128;
-    constexpr int STAGE = (BM + 256) * 128;         // 64 KB
+    constexpr int STAGE = SCREEN_STAGE_BYTES;       // 32 KB A + 16 KB B
+    constexpr int NSTAGE = SCREEN_STAGES;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform: the LDS-DMA's base and the wave's role are scalars)
     const int wave_m = wave >> 1, wave_n = wave & 1;
+    const unsigned sgn = wave_n ? 0x80008000u : 0u;                 // waves (m, 0) take Wp, waves (m, 1) Wn of the same fragments
     int swz;
     {   // blocks b, b+8, ... share an XCD: consecutive tiles per XCD (bijective remap, as igemm16.hip)
         const int nblk = gridDim.x, bid = blockIdx.x;
@@ -97,14 +120,13 @@ __global__ __launch_bounds__(256, 1) void logit_screen_kernel(const ScreenArgs a
     const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void *)(a.x16 + L.in_off), 0, (int)((long long)a.B * P * Cin * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)a.w16, 0, (int)((long long)9 * a.NT * 256 * Cin * 2), 0x00020000);
+        (void *)a.w16, 0, (int)((long long)9 * a.NT * 128 * Cin * 2), 0x00020000);
     constexpr unsigned OOB = 0x80000000u;
 
-    // DMA bookkeeping (igemm16.hip): wave w stages rows w*64 .. w*64+63 of the A tile and of the B tile, 8 rows per
-    // instruction: lane -> row (lane >> 3), LDS slot (lane & 7), source chunk slot ^ ((row >> 1) & 7)
+    // DMA bookkeeping (igemm16.hip): wave w stages rows w*64 .. w*64+63 of the A tile and rows w*32 .. w*32+31 of the B tile,
+    // 8 rows per instruction: lane -> row (lane >> 3), LDS slot (lane & 7), source chunk slot ^ ((row >> 1) & 7)
     int abase[8], aiy0[8], aix0[8];
-    unsigned offc[8];
-    int boff[8];
+    int boff[4];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int row = wave * 64 + u * 8 + (lane >> 3);
@@ -117,32 +139,39 @@ __global__ __launch_bounds__(256, 1) void logit_screen_kernel(const ScreenArgs a
         abase[u] = b * P * Cin * 2 + chunk * 16;
         aiy0[u] = rowok ? oy - 1 : -(1 << 20);
         aix0[u] = ox - 1;
-        boff[u] = (tile_n * 256 + row) * Cin * 2 + chunk * 16;
     }
-    auto tap_offsets = [&](int t) {
-        const int tky = t / 3, tkx = t - 3 * tky;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int iy = aiy0[u] + tky, ix = aix0[u] + tkx;
-            const bool ok = ((unsigned)iy < (unsigned)H) & ((unsigned)ix < (unsigned)W);
-            offc[u] = ok ? (unsigned)(abase[u] + (iy * W + ix) * Cin * 2) : OOB;
-        }
-    };
-    const int b_tapstride = a.NT * 256 * Cin * 2;
+    for (int u = 0; u < 4; ++u) {
+        const int row = wave * 32 + u * 8 + (lane >> 3);
+        const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+        boff[u] = (tile_n * 128 + row) * Cin * 2 + chunk * 16;
+    }
+    const int b_tapstride = a.NT * 128 * Cin * 2;
     const int KC = Cin >> 6;
     const int KS = 9 * KC;
     // K order: 64-channel block outer, filter tap inner (the bound does not depend on the order): the nine taps of a block
-    // re-read the same lines nine K-steps apart -> L2 hits
-    auto dma = [&](int stage, int tap, int kc) {
-        unsigned char *abuf = lds + stage * STAGE + wave * 64 * 128;
-        unsigned char *bbuf = lds + stage * STAGE + A_BYTES + wave * 64 * 128;
-        const int so = kc * 128, bso = tap * b_tapstride + kc * 128;
+    // re-read the same lines nine K-steps apart -> L2 hits.  12 DMA instructions per wave and K-step; (dtap, dkc) is the K-step
+    // the next call stages.  Past the last K-step the same 12 instructions are issued with every offset out of range (they
+    // fetch nothing and write zeros into a stage nobody reads again): the loop below stays free of branches and its counted
+    // wait stays right to the end.
+    int dtap = 0, dkc = 0;
+    auto dma = [&](int stage_off) {
+        const bool live = dkc < KC;
+        const int tky = dtap / 3, tkx = dtap - 3 * tky;
+        unsigned char *abuf = lds + stage_off + wave * 64 * 128;
+        unsigned char *bbuf = lds + stage_off + A_BYTES + wave * 32 * 128;
+        const int so = dkc * 128, bso = dtap * b_tapstride + dkc * 128;
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(arsrc, (lds_ptr_t)(abuf + u * 1024), 16, (int)offc[u], so, 0, 0);
+        for (int u = 0; u < 8; ++u) {
+            const int iy = aiy0[u] + tky, ix = aix0[u] + tkx;
+            const bool ok = live & ((unsigned)iy < (unsigned)H) & ((unsigned)ix < (unsigned)W);
+            const unsigned off = ok ? (unsigned)(abase[u] + (iy * W + ix) * Cin * 2) : OOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(arsrc, (lds_ptr_t)(abuf + u * 1024), 16, (int)off, so, 0, 0);
+        }
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(brsrc, (lds_ptr_t)(bbuf + u * 1024), 16, boff[u], bso, 0, 0);
+        for (int u = 0; u < 4; ++u)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(brsrc, (lds_ptr_t)(bbuf + u * 1024), 16, live ? boff[u] : (int)OOB, bso, 0, 0);
+        if (++dtap == 9) { dtap = 0; ++dkc; }
     };
     // fragments of the 16-channel step s: lane group (lane >> 5) takes chunk 2s + group of its row
     int roff[4];
@@ -151,6 +180,14 @@ __global__ __launch_bounds__(256, 1) void logit_screen_kernel(const ScreenArgs a
         const int chunk = 2 * s + (lane >> 5);
         roff[s] = (lane & 31) * 128 + ((chunk ^ (((lane & 31) >> 1) & 7)) << 4);
     }
+    auto rd = [&](int stage_off, int s, v4f (&fa)[4], v4u (&fb)[4]) {
+        const unsigned char *ab = lds + stage_off + wave_m * 4 * 4096;
+        const unsigned char *bb = lds + stage_off + A_BYTES;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fa[i] = *(const v4f *)(ab + i * 4096 + roff[s]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) fb[j] = *(const v4u *)(bb + j * 4096 + roff[s]);
+    };
     v16f acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -158,36 +195,64 @@ __global__ __launch_bounds__(256, 1) void logit_screen_kernel(const ScreenArgs a
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-    tap_offsets(0);
-    dma(0, 0, 0);
-    for (int ks = 0; ks < KS; ++ks) {
-        const int cur = ks & 1;
-        // this wave's share of stage cur has landed and its fragments of the other stage are in registers; behind the
-        // barrier that holds for every wave, so the other stage may be overwritten
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        if (ks + 1 < KS) {
-            const int kc = __builtin_amdgcn_readfirstlane((ks + 1) / 9), tap = ks + 1 - 9 * kc;      // (scalars: the DMA's scalar offset)
-            tap_offsets(tap);
-            dma(cur ^ 1, tap, kc);
-        }
-        const unsigned char *ab = lds + cur * STAGE + wave_m * 4 * 4096;
-        const unsigned char *bb = lds + cur * STAGE + A_BYTES + wave_n * 4 * 4096;
+    auto mf = [&](const v4f (&fa)[4], const v4u (&fb)[4]) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            v4f fa[4], fb[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) fa[i] = *(const v4f *)(ab + i * 4096 + roff[s]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) fb[j] = *(const v4f *)(bb + j * 4096 + roff[s]);
+        for (int j = 0; j < 4; ++j) {
+            const v8h bj = screen_operand(fb[j], sgn);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, fa[i]), __builtin_bit_cast(v8h, fb[j]), acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, fa[i]), bj, acc[i][j], 0, 0, 0);
         }
+    };
+    // 16 MFMAs with the 8 fragment reads of the next 16-channel step (a ds_read_b128 of the four waves together is about one
+    // MFMA long) and the operand selects between them; with_dma: the 12 DMA pieces of a K-step as well
+    auto sched = [&](bool with_dma) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (i < 8) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            if (with_dma && i >= 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            if (with_dma) __builtin_amdgcn_sched_group_barrier(0x006, 8, 0);
+            else __builtin_amdgcn_sched_group_barrier(0x006, 4, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    // A ring of three stages.  The barrier of K-step ks sits before its last 16-channel step: every fragment of stage ks is in
+    // registers by then (lgkmcnt(0)) and every wave's share of stage ks + 1 has landed (vmcnt: only the 12 pieces of K-step
+    // ks + 2 may be outstanding), so behind it the first fragments of K-step ks + 1 are read and stage ks is refilled with
+    // K-step ks + 3 -- a fill has two K-steps to land, up to 96 KB are in flight.
+    v4f fa0[4], fa1[4];
+    v4u fb0[4], fb1[4];
+    int cur = 0, nxt = STAGE, nn = 2 * STAGE;
+    static_assert(NSTAGE == 3, "the ring below rotates three stages");
+    dma(cur);
+    dma(nxt);
+    dma(nn);
+    asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    rd(cur, 0, fa0, fb0);
+#pragma unroll 1
+    for (int ks = 0; ks < KS; ++ks) {
+        rd(cur, 1, fa1, fb1);
+        mf(fa0, fb0);
+        sched(false);
+        rd(cur, 2, fa0, fb0);
+        mf(fa1, fb1);
+        sched(false);
+        rd(cur, 3, fa1, fb1);
+        mf(fa0, fb0);
+        sched(false);
+        asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        rd(nxt, 0, fa0, fb0);       // (behind the last K-step: a stage that is not used)
+        dma(cur);
+        mf(fa1, fb1);
+        sched(true);
+        const int t = cur;
+        cur = nxt; nxt = nn; nn = t;
     }
 
     // ---- epilogue, 32 rows of the wave's sub-tile per pass: every wave puts its sums into LDS ([r][j][lane]: the P wave and
@@ -195,6 +260,8 @@ __global__ __launch_bounds__(256, 1) void logit_screen_kernel(const ScreenArgs a
     // for half of the registers and marks.  acc[i][j][r]: row i*32 + (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column j*32 + (lane & 31).
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
+    // the row lists' counters of the compaction launch behind this one (no DMA is outstanding any more: nothing counts vmcnt here)
+    if (blockIdx.x == 0 && tid < (a.Cout >> 3)) a.counts[tid] = 0;
     float *mine = (float *)lds + wave * 4096;
     const float *Pp = (const float *)lds + (wave_m * 2) * 4096, *Np = Pp + 4096;
     float cst[4];
@@ -370,7 +437,8 @@ static bool screen_args_ok(const ScreenArgs &a)
     if (!a.x || !a.x16 || !a.w16 || !a.wt || !a.bias || !a.cst || !a.logits || !a.bits || !a.counts || !a.lists) return false;
     if (a.Cin % 64 != 0 || a.Cin < 64 || a.Cout % 8 != 0 || a.Cout < 8 || a.Cout > 8 * SCREEN_MAX_OCT || a.Cout > a.CoutPad) return false;
     if (a.NT != (a.Cout + 127) / 128 || a.nlevels < 1 || a.nlevels > SCREEN_MAX_LEVELS) return false;
-    if ((long long)9 * a.NT * 256 * a.Cin * 2 >= (1LL << 31) || (long long)9 * a.Cin * 8 * 4 > 160 * 1024 / 2) return false;
+    // (the signed plane's 32-bit byte offsets; two fill blocks per CU, each with its column octet's weights in LDS)
+    if ((long long)9 * a.NT * 128 * a.Cin * 2 >= (1LL << 31) || (long long)9 * a.Cin * 8 * 4 > 160 * 1024 / 2) return false;
     if (a.out_rstride != a.Cout || a.out_bstride <= 0 || (a.out_bstride & 7) || (long long)a.B * a.out_bstride * 4 >= (1LL << 31)) return false;
     long long rows = 0, tiles = 0, outs = 0;
     for (int i = 0; i < a.nlevels; ++i) {
@@ -389,14 +457,14 @@ hipError_t launch_logit_convert(const ScreenArgs &a, hipStream_t s)
     if (!screen_args_ok(a) || a.x_elems <= 0 || (a.x_elems & 7)) return hipErrorInvalidValue;
     const long long n8 = a.x_elems / 8;
     const long long nblk = (n8 + 255) / 256;
-    hipLaunchKernelGGL(logit_convert_kernel, dim3((unsigned)(nblk < 8192 ? nblk : 8192)), dim3(256), 0, s, a.x, a.x16, n8, a.counts, a.Cout / 8);
+    hipLaunchKernelGGL(logit_convert_kernel, dim3((unsigned)(nblk < 8192 ? nblk : 8192)), dim3(256), 0, s, a.x, a.x16, n8);
     return hipGetLastError();
 }
 
 hipError_t launch_logit_screen(const ScreenArgs &a, hipStream_t s)
 {
     if (!screen_args_ok(a)) return hipErrorInvalidValue;
-    constexpr int lds_bytes = 2 * (256 + 256) * 128;
+    constexpr int lds_bytes = SCREEN_STAGES * SCREEN_STAGE_BYTES;       // 144 KB (the epilogue's 64 KB of sums lie in it)
     static std::atomic<unsigned> attr_done{0};
     hipError_t e = ssd_allow_lds((const void *)logit_screen_kernel, lds_bytes, attr_done);
     if (e != hipSuccess) return e;

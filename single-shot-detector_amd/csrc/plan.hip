@@ -1033,7 +1033,7 @@ static int heads(Builder &b, const Backbone &bb, const Fpn &f)
             o.bytes = (double)py.total * 6.0;
             o.run = [sa](hipStream_t s) { return launch_logit_convert(sa, s); };
             tower_ops[t].push_back(o);
-            o.bytes = (double)py.total * 2.0 + (double)fc.taps * sa.NT * 256 * fc.CinP * 2.0;
+            o.bytes = (double)py.total * 2.0 + (double)fc.taps * sa.NT * 128 * fc.CinP * 2.0;
             o.run = [sa](hipStream_t s) { return launch_logit_screen(sa, s); };
             tower_ops[t].push_back(o);
             o.bytes = (double)B * N * C / 64.0;

@@ -145,7 +145,7 @@ struct ScreenLevel {
 struct ScreenArgs {
     const float *x;                // the class tower's last output, fp32 rows in physical channel order
     unsigned short *x16;           // the same elements as f16 rounded up (written by the convert launch)
-    const unsigned short *w16;     // [9][NT * 256][Cin] f16: per 256-row tile 128 rows Wp, 128 rows Wn (ConvW::wscr)
+    const unsigned short *w16;     // [9][NT * 128][Cin] f16: Wp, or Wn with the sign bit set, in one plane (ConvW::wscr)
     const float *wt;               // [9][CoutPad][Cin] the exact kernel
     const float *bias;             // [Cout]
     const float *cst;              // [Cout] the bound's constant term (ConvW::scst)

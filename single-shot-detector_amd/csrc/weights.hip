@@ -99,17 +99,20 @@ void conv_geometry(const ssd_handle *h, int taps, int CinP, int CoutP, int Cin_l
 // The screen's operands (logit_screen.hip) from the packed kernel t [taps][CoutPad][CinP]: Wp = max(w, 0) rounded UP to
 // f16, Wn = max(-w, 0) rounded DOWN, neither ever subnormal (a positive value below 2^-14 becomes 2^-14 in Wp and 0 in Wn: the
 // bound then holds whether or not the matrix pipe flushes subnormal inputs); a NaN weight goes to Wp, where it marks.
+// For every (k, column) at most one of the two is non-zero, so both live in ONE signed plane [taps][NT * 128][CinP]: the bits of
+// Wp where w > 0 or w is NaN, 0x8000 | Wn where Wn is non-zero, +0 everywhere else (never -0).  The kernel's waves take their
+// operand back out of it with integer operations (screen_operand).
 // cst[n] >= bias + 2^-14 * sum Wn + 2^-20 |bias| (the input plane's round-up to a normal half, the epilogue's one rounding).
 static int pack_screen(DevPool &pool, const std::vector<float> &t, const float *bias, ConvW &cw)
 {
-    const int NT = (cw.CoutP + 127) / 128, rows = NT * 256;
-    std::vector<uint16_t> s((size_t)cw.taps * rows * cw.CinP, 0);
+    const int NT = (cw.CoutP + 127) / 128, rows = NT * 128;
+    std::vector<uint16_t> s((size_t)cw.taps * rows * cw.CinP, 0);       // (+0 wherever neither is non-zero: -0 is never written)
     std::vector<double> wn_sum(cw.CoutP, 0.0);
     auto bits_of = [](_Float16 v) { uint16_t b; memcpy(&b, &v, 2); return b; };
     for (int tap = 0; tap < cw.taps; ++tap)
         for (int n = 0; n < cw.CoutP; ++n) {
             const float *src = &t[((size_t)tap * cw.CoutPad + n) * cw.CinP];
-            uint16_t *dp = &s[((size_t)tap * rows + (n / 128) * 256 + n % 128) * cw.CinP], *dn = dp + (size_t)128 * cw.CinP;
+            uint16_t *dp = &s[((size_t)tap * rows + n) * cw.CinP];
             for (int p = 0; p < cw.CinP; ++p) {
                 const float v = src[p];
                 if (v != v) { dp[p] = 0x7e00; continue; }
@@ -125,7 +128,7 @@ static int pack_screen(DevPool &pool, const std::vector<float> &t, const float *
                     if ((float)hh > m) b -= 1;
                     if (b >= 0x7c00) b = 0x7bff;
                     if (b < 0x0400) b = 0;
-                    dn[p] = b;
+                    dp[p] = b ? (uint16_t)(0x8000 | b) : 0;
                     _Float16 back;
                     memcpy(&back, &b, 2);
                     wn_sum[n] += (double)(float)back;
