@@ -553,6 +553,37 @@ typedef struct ssd_update_scalars {          /* 24 bytes: this step's scalars, a
 int ssd_train_update(const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T,
                      const ssd_update_scalars *scalars, void *stream);
 
+/* ---- the TRAIN step's norms: sum w^2, sum g^2 and the non-finite counts of every tensor of the update's table ----
+ *
+ * What a training loop reports and checks every step (tf.estimator's total_loss holds weight_decay * sum l2_loss(K), model.py:80-81;
+ * NanTensorHook stops a run whose loss is not finite), for a whole model in TWO launches over the table ssd_train_update takes, run
+ * BEFORE the update.  The table, its rows, the first_block rule and every refusal are the TRAIN update's (above); m, v and ema are
+ * validated as there and never dereferenced; w and grad are read and never written.  Outputs, in device memory, rows in table order:
+ *   sums [T][2] double:  sum over the tensor of w^2, of grad^2      bad [T][2] int64:  non-finite elements of w, of grad
+ * Arithmetic: an element's square is formed in double, where it is exact ((double)x * (double)x, 48 significant bits); a non-finite
+ * element (NaN, +inf, -inf) contributes +0.0 to its sum and 1 to its count.  A NULL grad gives sum g^2 = +0.0 and bad g = 0.
+ * Order of the double additions, fixed here so that a numpy float64 restatement is bit-exact:
+ *   The work list is the update's: blocks of SSD_UPDATE_BLOCK_ELEMS VIRTUAL elements counted from the 16-byte boundary at or below
+ *   w; virtual element j of a tensor is its element j - pad, pad = ((uintptr_t)w / 4) % 4 ALWAYS (whatever the alignment of grad:
+ *   grad's element i is taken with w's element i); the tensor is the virtual elements [pad, pad + count).
+ *   Stage 1, one partial per block, j0 the block's first virtual element: lane t of 256 owns the virtual elements
+ *   j0 + (k * 256 + t) * 4 + e, k = 0..3 outer, e = 0..3 inner, and adds the squares of those inside the tensor in that order,
+ *   starting from +0.0.  The 256 lane values a[t] are then added by the binary tree a[t] += a[t + s] for t < s, s = 128, 64, ..., 1;
+ *   a[0] is the block's partial.  (How the tree is carried out -- cross-lane moves, LDS -- is free, as long as it is this tree.)
+ *   Stage 2: a tensor's value is its blocks' partials added in ascending block order, starting from +0.0; a row of no blocks
+ *   gives +0.0 and 0.  Counts are integers.  No atomics anywhere: two calls give the same bits, and the bits do not depend on
+ *   which load width moved an element.
+ * workspace: ssd_train_norms_workspace_bytes(tensors_host, T) = 32 bytes per block of the table (two doubles and two int64 per
+ * block; 0 for a table of empty tensors and for a table the call would refuse), 16-byte aligned, written by stage 1 and read by
+ * stage 2; its contents need no initialisation.  No allocation, no host synchronisation: the call only enqueues two kernels
+ * on `stream` (one when the table has no blocks) and is legal during stream capture.  Beyond the update's refusals (without the
+ * scalars): a NULL sums or bad or one not 8-byte aligned, a NULL workspace or one not 16-byte aligned, a workspace smaller than
+ * the planner's figure: SSD_ERR_INVALID before any HIP call.  Needs no handle. */
+#define SSD_NORMS_BLOCK_BYTES 32
+size_t ssd_train_norms_workspace_bytes(const ssd_update_tensor *tensors_host, int32_t T);
+int ssd_train_norms(const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T, double *sums,
+                    int64_t *bad, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the TRAIN head: forward and backward of RetinaNetBoxPredictor in TRAIN mode (box_predictor.py:34-155) ----
  *
  * The predictor is ten dense 3x3 stride-1 'same' convolutions (two towers of four 256 -> 256 layers shared by the pyramid

@@ -8,7 +8,7 @@ for device memory, streams and torch.distributed.  There is NO CPU fallback: eve
 raises if the HIP library is missing or no GPU is present.
 """
 from .config import load_config, INFERENCE_KEYS, load_loss_config, LOSS_KEYS, load_train_config, TRAIN_KEYS   # noqa: F401
-from .config import load_optimizer_config, OPTIMIZER_KEYS             # noqa: F401
+from .config import load_optimizer_config, OPTIMIZER_KEYS, load_run_config, RUN_KEYS   # noqa: F401
 from .variables import (variable_shapes, synthetic_weights, save_weights,   # noqa: F401
                         load_weights)
 from .pb_import import read_frozen_graph, load_pb_weights             # noqa: F401
@@ -32,3 +32,4 @@ from .head_train import TrainableBoxPredictor, head_variable_shapes   # noqa: F4
 from .fpn_train import TrainableFPN, fpn_variable_shapes, variance_scaling_draw   # noqa: F401
 from .backbone_train import TrainableMobileNet, mobilenet_variable_shapes   # noqa: F401
 from .shufflenet_train import TrainableShuffleNet, shufflenet_variable_shapes   # noqa: F401
+from .trainer import Trainer                                        # noqa: F401  (`python -m ssd_amd.train`: train.py's loop)

@@ -100,3 +100,20 @@ def load_optimizer_config(path_or_dict):
     if not (math.isfinite(out["initial_learning_rate"]) and math.isfinite(out["weight_decay"])):
         raise ValueError("initial_learning_rate and weight_decay must be finite")
     return out
+
+
+RUN_KEYS = ("model_dir", "train_dataset", "val_dataset", "pretrained_checkpoint")
+
+
+def load_run_config(path_or_dict):
+    """The keys of the reference's JSON config that train.py itself reads (train.py:19,36-50): a dict with exactly RUN_KEYS as
+    strings -- where the run lives, its two datasets and the checkpoint whose backbone warm-starts it."""
+    if isinstance(path_or_dict, dict):
+        raw = dict(path_or_dict)
+    else:
+        with open(path_or_dict) as f:
+            raw = json.load(f)
+    missing = [k for k in RUN_KEYS if k not in raw]
+    if missing:
+        raise KeyError("config is missing the key %r" % missing[0])
+    return {k: str(raw[k]) for k in RUN_KEYS}

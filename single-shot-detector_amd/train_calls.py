@@ -1,5 +1,5 @@
 """How a TRAIN entry point of include/ssd_hip.h is called ("the TRAIN head", "the TRAIN FPN", "the TRAIN backbone", "the TRAIN first
-convolution" from uint8 and from float frames, "the TRAIN ShuffleNet"): the only module that fills ssd_conv_level / ssd_bn_level, orders the arguments, sizes the workspace and passes the
+convolution" from uint8 and from float frames, "the TRAIN ShuffleNet", "the TRAIN step's norms"): the only module that fills ssd_conv_level / ssd_bn_level, orders the arguments, sizes the workspace and passes the
 stream.  One function per entry point family, no autograd, no model.  Arguments are torch tensors, None exactly where the header
 allows NULL; every result is the CALLER's tensor.  Before the library is called every tensor is checked against the shape the
 geometry implies (ValueError naming the argument: shape, dtype, contiguity, level counts) and then for lying on one GPU
@@ -407,3 +407,37 @@ def maxpool_backward(x, dy, dx):
     dev = _one_gpu(None, x=x, dy=dy, dx=dx)
     with torch.cuda.device(dev):
         check(lib().ssd_sn_maxpool_train_backward(x.data_ptr(), dy.data_ptr(), B, H, W, C, dx.data_ptr(), stream(dev)))
+
+
+# ----------------------------------------------------------------------------- the TRAIN step's norms
+ROW_BYTES = 56                                                                 # sizeof(ssd_update_tensor)
+
+
+def _rows_host(rows_host, T):
+    """rows_host is the host copy of the update's table: a contiguous CPU uint8 tensor of exactly T * 56 bytes -> T."""
+    if not (isinstance(rows_host, torch.Tensor) and rows_host.dtype == torch.uint8 and not rows_host.is_cuda and rows_host.dim() == 1
+            and rows_host.is_contiguous() and rows_host.numel() % ROW_BYTES == 0 and rows_host.numel() >= ROW_BYTES):
+        raise ValueError("rows_host must be a contiguous 1-D uint8 CPU tensor of T * %d bytes (ssd_update_tensor rows)" % ROW_BYTES)
+    if T is not None and rows_host.numel() != T * ROW_BYTES:
+        raise ValueError("rows_host must hold exactly T = %d rows of %d bytes" % (T, ROW_BYTES))
+    return rows_host.numel() // ROW_BYTES
+
+
+def train_norms_workspace_bytes(rows_host, T=None):
+    """ssd_train_norms_workspace_bytes of the table's host copy (0: a table of empty tensors, or one the call would refuse)."""
+    T = _rows_host(rows_host, T)
+    return lib().ssd_train_norms_workspace_bytes(rows_host.data_ptr(), T)
+
+
+def train_norms(rows_host, rows_dev, sums, bad, workspace=None):
+    """ssd_train_norms over the update's table: rows_host (CPU uint8, T * 56 bytes) is checked, rows_dev (the same bytes on the GPU,
+    the caller's upload, ordered before this call on the current stream) is what the kernels read; sums float64 [T,2] receives
+    sum w^2, sum g^2 and bad int64 [T,2] the non-finite counts, rows in table order."""
+    T = _rows_host(rows_host, None)
+    _dense(rows_dev, "rows_dev", (T * ROW_BYTES,), torch.uint8)
+    _dense(sums, "sums", (T, 2), torch.float64)
+    _dense(bad, "bad", (T, 2), torch.int64)
+    dev = _one_gpu(workspace, rows_dev=rows_dev, sums=sums, bad=bad)
+    L = lib()
+    _run(dev, workspace, lambda: L.ssd_train_norms_workspace_bytes(rows_host.data_ptr(), T),
+         lambda *tail: L.ssd_train_norms(rows_host.data_ptr(), rows_dev.data_ptr(), T, sums.data_ptr(), bad.data_ptr(), *tail))

@@ -264,6 +264,67 @@ class TrainStep:
         self.global_step = t
         return t
 
+    # ------------------------------------------------------------------ the norms
+    def norms(self):
+        """(sums, bad) of the parameters and their current .grad (include/ssd_hip.h, "the TRAIN step's norms"): sums float64 [T,2]
+        holds sum w^2 and sum g^2, bad int64 [T,2] the non-finite elements of w and of the gradient, rows in `names` order; a
+        parameter whose .grad is None gives 0 and 0.  Called BEFORE step(): the values are of the variables the step computed with.
+        One small asynchronous upload (a ring of its own: step()'s is not touched) and two launches on the current stream; never
+        waits for the device; the results are CUDA tensors of this call."""
+        import torch
+        from . import train_calls
+        if torch.cuda.is_current_stream_capturing():
+            # the gradients' addresses are read here, on the host: a captured launch would replay this step's addresses for ever
+            raise RuntimeError("TrainStep.norms() cannot be captured into a graph: the gradient addresses change from step to step "
+                               "on the host; call it outside the capture")
+        T = len(self.names)
+        grads = np.zeros(T, np.uint64)
+        for i, name in enumerate(self.names):
+            p = self.parameters[name]
+            if p.data_ptr() != int(self._w_ptrs[i]):
+                raise RuntimeError("the storage of parameter %r was replaced after TrainStep was built" % name)
+            g = p.grad
+            if g is None:
+                continue
+            if g.dtype != torch.float32 or g.device != self.device or g.shape != p.shape or not g.is_contiguous() or g.data_ptr() % 4:
+                raise ValueError("the gradient of %r must be a contiguous float32 tensor of the parameter's shape and device" % name)
+            grads[i] = g.data_ptr()
+        with torch.cuda.device(self.device):
+            if not hasattr(self, "_norms_ring"):
+                nbytes = T * TENSOR_DTYPE.itemsize
+                self._norms_ring, self._norms_calls = [], 0
+                for _ in range(self.RING):
+                    host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+                    self._norms_ring.append({"host": host, "rows": host.numpy().view(TENSOR_DTYPE),
+                                             "dev": torch.empty(nbytes, dtype=torch.uint8, device=self.device),
+                                             "event": torch.cuda.Event(), "used": False})
+            slot = self._norms_ring[self._norms_calls % self.RING]
+            if slot["used"]:
+                slot["event"].synchronize()      # the upload that last read this pinned slot (RING calls ago) has run
+            rows = slot["rows"]
+            rows[:] = self._table
+            rows["grad"] = grads
+            sums = torch.empty((T, 2), dtype=torch.float64, device=self.device)
+            bad = torch.empty((T, 2), dtype=torch.int64, device=self.device)
+            slot["dev"].copy_(slot["host"], non_blocking=True)
+            slot["event"].record(torch.cuda.current_stream(self.device))
+            slot["used"] = True
+            train_calls.train_norms(slot["host"], slot["dev"], sums, bad)
+        self._norms_calls += 1
+        return sums, bad
+
+    def regularization_loss(self, sums_host):
+        """model.py:80-81 from norms()' sums read back to the host ([T,2] float64): fp32(weight_decay * sum over the decaying rows,
+        in `names` order, of sums[t,0] / 2), formed in float64 and rounded once -- evaluation.regularization_loss's definition on
+        the GPU's per-tensor sums."""
+        sums_host = np.asarray(sums_host, np.float64)
+        if sums_host.shape != (len(self.names), 2):
+            raise ValueError("sums_host must be norms()' sums, shape [%d, 2]" % len(self.names))
+        s = 0.0
+        for t in np.nonzero(self._table["decay"])[0]:
+            s += float(sums_host[t, 0]) / 2.0
+        return np.float32(float(self.config["weight_decay"]) * s)
+
     # ------------------------------------------------------------------ checkpoints
     def _export(self, name, tensor):
         a = tensor.detach().cpu().numpy()

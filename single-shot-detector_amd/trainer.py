@@ -1,0 +1,389 @@
+"""train.py's loop (train.py:36-66, model.py:106-128 in mode TRAIN) without TensorFlow: the Trainer wires the pieces this library
+already has --
+
+    TrainPipeline -> TrainableMobileNet | TrainableShuffleNet (train_first) -> TrainableFPN -> TrainableBoxPredictor
+                  -> differentiable_loss -> backward -> TrainStep.norms() -> TrainStep.step()
+
+-- decides the start state as tf.estimator does (resume from model_dir, else warm-start the backbone from pretrained_checkpoint),
+reports total_loss with the regularisation term from the GPU's per-tensor sums, stops on a non-finite loss, gradient or variable
+(NanTensorHook), writes checkpoints and logs on a schedule and evaluates the moving averages (RestoreMovingAverageHook).
+
+One GPU, no graph capture of a step, no TensorBoard files, no gradient clipping, exact fp32 only.  The host
+logic that needs no GPU -- schedules, seeds, the warm start, pruning, the stop decision -- is the module-level functions below.
+"""
+import json
+import math
+import os
+import re
+import time
+
+import numpy as np
+
+from .ckpt_import import read_checkpoint, read_checkpoint_index, resolve_checkpoint
+from .config import (load_config, load_loss_config, load_optimizer_config, load_run_config, load_train_config)
+
+SAVE_CHECKPOINTS_SECS = 1800            # train.py:39
+EVAL_THROTTLE_SECS = 3 * 3600           # train.py:63
+KEEP_CHECKPOINT_MAX = 5                 # tf.estimator.RunConfig's default
+BACKBONE_SCOPES = {"mobilenet": "MobilenetV1/", "shufflenet": "ShuffleNetV2/"}     # train.py:44-47
+RING = 4                                # read-back slots: step k - 1 is examined after step k was enqueued
+
+
+# ----------------------------------------------------------------------------- host logic
+def due(step, now, last_step, last_time, every_steps, every_secs):
+    """Is a scheduled action (a checkpoint, an evaluation) due after `step` at time `now`, the last one having happened after
+    `last_step` at `last_time`?  every_steps (None: no step schedule) wins over every_secs (None: no time schedule), as in
+    tf.estimator's CheckpointSaverHook, which takes exactly one of the two; never twice for one step."""
+    if step <= last_step:
+        return False
+    if every_steps is not None:
+        return step - last_step >= int(every_steps)
+    if every_secs is not None:
+        return now - last_time >= float(every_secs)
+    return False
+
+
+def pipeline_seed(seed, step):
+    """The TrainPipeline seed of a run (re)started at global_step `step`: the entropy [seed, step], of which TrainPipeline makes
+    SeedSequence([seed, step]), so that a resumed run does not replay the records the interrupted one began with (tf.estimator
+    restarts its input on resume, too)."""
+    if int(seed) < 0 or int(step) < 0:
+        raise ValueError("seed and step must be >= 0")
+    return [int(seed), int(step)]
+
+
+def backbone_names(params):
+    """The variables train.py's WarmStartSettings restores: those of variables.variable_shapes(params) under the backbone's scope."""
+    from .variables import variable_shapes
+    scope = BACKBONE_SCOPES[load_config(params)["backbone"]]
+    return {n: tuple(s) for n, s in variable_shapes(params).items() if n.startswith(scope)}
+
+
+def warm_start_weights(prefix, params):
+    """{name: float32 array} of exactly backbone_names(params) out of the checkpoint `prefix` (a prefix, one of its files or a
+    model_dir).  Whatever else the checkpoint holds -- a classifier's Logits, slots, averages -- is ignored; a missing backbone
+    variable is a KeyError naming it, a wrong shape a ValueError."""
+    found = resolve_checkpoint(prefix)
+    if found is None:
+        raise FileNotFoundError("pretrained_checkpoint %r is not a checkpoint prefix or model_dir" % (prefix,))
+    want = backbone_names(params)
+    _, entries = read_checkpoint_index(found)
+    for name in want:
+        if name not in entries:
+            raise KeyError("pretrained checkpoint %s has no variable %r" % (found, name))
+    got = read_checkpoint(found, list(want))
+    out = {}
+    for name, shape in want.items():
+        a = got[name]
+        if a.dtype != np.float32 or tuple(a.shape) != shape:
+            raise ValueError("pretrained variable %r has shape %s dtype %s, expected %s float32" % (name, tuple(a.shape), a.dtype, shape))
+        out[name] = np.ascontiguousarray(a)
+    return out
+
+
+def head_tower_weights(params, seed):
+    """What box_predictor.py:107-155 initialises besides class_net/logits (which TrainableBoxPredictor draws itself): the towers'
+    kernels by tf.variance_scaling_initializer (fpn_train.variance_scaling_draw), their batch norms (gamma 1, beta 0, moving_mean 0,
+    moving_variance 1) and box_net/encoded_boxes (normal(0, 0.01), bias 0), in variables.variable_shapes order from ONE generator
+    seeded by SeedSequence([seed, 1])."""
+    from .fpn_train import variance_scaling_draw
+    from .head_train import head_variable_shapes
+    rng = np.random.default_rng(np.random.SeedSequence([int(seed), 1]))
+    out = {}
+    for name, shape in head_variable_shapes(params).items():
+        if name.startswith("class_net/logits/"):
+            continue
+        leaf = name.rsplit("/", 1)[1]
+        if name.startswith("box_net/encoded_boxes/"):
+            a = rng.normal(0.0, 0.01, shape) if leaf == "kernel" else np.zeros(shape)
+        elif leaf == "kernel":
+            a = variance_scaling_draw(rng, shape)
+        else:
+            a = np.ones(shape) if leaf in ("gamma", "moving_variance") else np.zeros(shape)
+        out[name] = np.asarray(a, np.float32)
+    return out
+
+
+def checkpoint_steps(model_dir):
+    """The steps N of the complete bundles model.ckpt-N in model_dir, ascending."""
+    if not os.path.isdir(model_dir):
+        return []
+    steps = []
+    for f in os.listdir(model_dir):
+        m = re.match(r"^model\.ckpt-(\d+)\.index$", f)
+        if m:
+            steps.append(int(m.group(1)))
+    return sorted(steps)
+
+
+def prune_checkpoints(model_dir, keep=KEEP_CHECKPOINT_MAX):
+    """Deletes all but the newest `keep` bundles model.ckpt-N of model_dir (tf.train.Saver's max_to_keep); the `checkpoint` state
+    file, which names the newest, is left alone.  Returns the removed prefixes."""
+    if keep < 1:
+        raise ValueError("keep must be >= 1")
+    removed = []
+    for step in checkpoint_steps(model_dir)[:-keep]:
+        base = "model.ckpt-%d" % step
+        for f in os.listdir(model_dir):
+            if f == base + ".index" or re.match("^" + re.escape(base) + r"\.data-\d{5}-of-\d{5}$", f):
+                os.remove(os.path.join(model_dir, f))
+        removed.append(os.path.join(model_dir, base))
+    return removed
+
+
+def first_non_finite(step, names, loc, cls, sums, bad):
+    """NanTensorHook's decision on one step's read-back (host values): None when everything is finite, else the message of the
+    FloatingPointError, which names the step and the first offending variable -- the first row of `names` with a non-finite element
+    in the variable, else in a gradient (bad [T,2]: a non-zero count; sums [T,2]: a non-finite sum, the squares overflowed) -- and, when
+    every row is clean, the loss term that is not finite."""
+    sums, bad = np.asarray(sums, np.float64), np.asarray(bad, np.int64)
+    wrong = (bad != 0) | ~np.isfinite(sums)
+    for col, what in ((0, "variable"), (1, "the gradient of")):                  # a bad variable is the cause, bad gradients follow
+        rows = np.nonzero(wrong[:, col])[0]
+        if len(rows):
+            t = int(rows[0])
+            if bad[t, col]:
+                return "step %d: %s %r has %d non-finite element(s)" % (step, what, names[t], int(bad[t, col]))
+            return "step %d: the sum of squares of %s %r is %r" % (step, what, names[t], float(sums[t, col]))
+    for what, v in (("localization_loss", loc), ("classification_loss", cls)):
+        if not math.isfinite(float(v)):
+            return "step %d: %s is %r" % (step, what, float(v))
+    return None
+
+
+def log_record(step, loc, cls, reg, sums, loss_config, learning_rate, images_per_second, wait_seconds):
+    """One train_log.jsonl record: loss is evaluation.total_loss's rule (tf.losses.get_total_loss) with the regularisation term."""
+    from .evaluation import total_loss
+    return {"step": int(step), "loss": float(total_loss(loc, cls, reg, loss_config)), "localization_loss": float(np.float32(loc)),
+            "classification_loss": float(np.float32(cls)), "regularization_loss": float(np.float32(reg)),
+            "learning_rate": float(learning_rate), "gradient_norm": float(math.sqrt(float(np.sum(np.asarray(sums, np.float64)[:, 1])))),
+            "images_per_second": float(images_per_second), "wait_seconds": float(wait_seconds)}
+
+
+def _append_jsonl(path, record):
+    with open(path, "a") as f:
+        f.write(json.dumps(record, sort_keys=True) + "\n")
+
+
+# ----------------------------------------------------------------------------- the Trainer
+class Trainer:
+    """tf.estimator.Estimator(model_fn, params, config, warm_start_from) + train_and_evaluate of train.py on one GPU.
+
+    config          the reference's JSON (path or dict): every key group of config.py is read from it
+    model_dir       overrides the config's
+    device          the HIP device index
+    seed            the run's seed: the initial FPN and heads, and (with global_step at the start) the input pipeline
+    read_workers, decode    TrainPipeline's (and evaluation.evaluate's)
+
+    Start state: a checkpoint in model_dir resumes the run (variables, statistics, averages, slots, global_step: TrainStep.restore);
+    otherwise the backbone comes from pretrained_checkpoint (warm_start_weights) and fpn/* and the heads are drawn from `seed`.
+    Every variable is trained (train_first, nothing frozen), as the reference does.
+
+    step() never waits for the device on its own account: a step's loss terms, sums and counts go to one of RING pinned slots behind
+    an event, and the host examines step k - 1's slot after it has enqueued step k (at most two slots are in flight)."""
+
+    log_every = 100
+
+    def __init__(self, config, model_dir=None, device=0, seed=0, read_workers=None, decode=None):
+        import torch
+        from .backbone_train import TrainableMobileNet
+        from .fpn_train import TrainableFPN
+        from .head_train import TrainableBoxPredictor
+        from .shufflenet_train import TrainableShuffleNet
+        from .ssd import AnchorGenerator
+        from .train_step import TrainStep
+        if isinstance(config, dict):
+            self.config = dict(config)
+        else:
+            with open(config) as f:
+                self.config = json.load(f)
+        self.params = load_config(self.config)
+        self.loss_config = load_loss_config(self.config)
+        self.train_config = load_train_config(self.config)
+        self.run_config = load_run_config(self.config)
+        load_optimizer_config(self.config)
+        self.model_dir = str(model_dir if model_dir is not None else self.run_config["model_dir"])
+        self.device = torch.device("cuda", int(device))
+        self.seed = int(seed)
+        self.read_workers, self.decode = read_workers, decode
+        os.makedirs(self.model_dir, exist_ok=True)
+        resumed = resolve_checkpoint(self.model_dir)
+        if resumed is not None:
+            from .ckpt_import import load_ckpt_weights
+            W = load_ckpt_weights(resumed, self.params, use_ema=False)
+        else:
+            W = {**warm_start_weights(self.run_config["pretrained_checkpoint"], self.params), **head_tower_weights(self.params, self.seed)}
+        backbone_cls = TrainableMobileNet if self.params["backbone"] == "mobilenet" else TrainableShuffleNet
+        with torch.cuda.device(self.device):
+            self.backbone = backbone_cls(self.params, W, device=self.device, seed=self.seed, train_first=True).train()
+            self.fpn = TrainableFPN(self.params, W, device=self.device, seed=self.seed).train()
+            self.head = TrainableBoxPredictor(self.params, W, device=self.device, seed=self.seed).train()
+            self.variables = {**self.backbone.named_variables(), **self.fpn.named_variables(), **self.head.named_variables()}
+            statistics = {**self.backbone.statistics(), **self.fpn.statistics(), **self.head.statistics()}
+            self.train_step = TrainStep(self.variables, self.config, statistics, layout="tf", params=self.params, frozen={})
+            if resumed is not None:
+                self.train_step.restore(resumed)
+            gen = AnchorGenerator()
+            hw = (self.train_config["image_height"], self.train_config["image_width"])
+            self.anchors = torch.from_numpy(gen(*hw)).to(self.device)
+            self.loc_weight = torch.tensor(np.float32(self.loss_config["localization_loss_weight"]), device=self.device)
+            self.cls_weight = torch.tensor(np.float32(self.loss_config["classification_loss_weight"]), device=self.device)
+            T = len(self.train_step.names)
+            self._ring = [{"losses": torch.empty(2, dtype=torch.float32).pin_memory(), "sums": torch.empty((T, 2), dtype=torch.float64).pin_memory(),
+                           "bad": torch.empty((T, 2), dtype=torch.int64).pin_memory(), "event": torch.cuda.Event(), "step": None}
+                          for _ in range(RING)]
+        self.resumed_from = resumed
+        self.start_step = self.train_step.global_step
+        self._pipe = None
+        self._pending = []                  # ring slots whose read-back the host has not examined, oldest first
+        self._failed = False
+        self._saved_step = self.start_step if resumed is not None else -1
+        self._last_save = (self.start_step, time.monotonic())
+        self._last_log = (self.start_step, time.monotonic())
+        self.last = None                    # the newest examined step's log_record
+
+    @property
+    def global_step(self):
+        return self.train_step.global_step
+
+    # ------------------------------------------------------------------ one step
+    def _pipeline(self):
+        if self._pipe is None:
+            from .augment import TrainPipeline
+            self._pipe = TrainPipeline(self.run_config["train_dataset"], self.train_config, pipeline_seed(self.seed, self.global_step),
+                                       decode=self.decode, read_workers=self.read_workers, device=self.device.index)
+        return self._pipe
+
+    def step(self):
+        """Enqueues one training step and returns its number; examines the read-back of the step before it (FloatingPointError)."""
+        import torch
+        from .ssd import differentiable_loss
+        if self._failed:
+            raise RuntimeError("this run stopped on a non-finite value")
+        with torch.cuda.device(self.device):
+            images, gt = next(self._pipeline())
+            for p in self.variables.values():
+                p.grad = None
+            eb, cp = self.head(self.fpn(self.backbone(images)))
+            out = differentiable_loss(cp, eb, self.anchors, gt, self.loss_config)
+            loc, cls = out["localization_loss"], out["classification_loss"]
+            (self.loc_weight * loc + self.cls_weight * cls).backward()
+            sums, bad = self.train_step.norms()         # before the update: of the variables this step computed with
+            t = self.train_step.step()
+            slot = self._ring[t % RING]
+            slot["losses"][0:1].copy_(loc.detach().reshape(1), non_blocking=True)
+            slot["losses"][1:2].copy_(cls.detach().reshape(1), non_blocking=True)
+            slot["sums"].copy_(sums, non_blocking=True)
+            slot["bad"].copy_(bad, non_blocking=True)
+            slot["event"].record(torch.cuda.current_stream(self.device))
+            slot["step"] = t
+            self._pending.append(slot)
+        while len(self._pending) > 1:                   # step t - 1 (and older), after step t was enqueued
+            self._examine(self._pending[0])
+        return t
+
+    def _examine(self, slot):
+        assert slot is self._pending[0]
+        slot["event"].synchronize()
+        self._pending.pop(0)
+        step = slot["step"]
+        loc, cls = (float(v) for v in slot["losses"].numpy())
+        sums, bad = slot["sums"].numpy(), slot["bad"].numpy()
+        msg = first_non_finite(step, self.train_step.names, loc, cls, sums, bad)
+        if msg is not None:
+            self._failed = True
+            self._pending.clear()
+            raise FloatingPointError(msg)
+        reg = self.train_step.regularization_loss(sums)
+        now = time.monotonic()
+        images = (step - self._last_log[0]) * self.train_config["batch_size"]
+        rate = images / max(now - self._last_log[1], 1e-9)
+        self.last = log_record(step, loc, cls, reg, sums, self.loss_config, self.train_step.learning_rate(step - 1), rate,
+                               self._pipe.wait_seconds if self._pipe is not None else 0.0)
+        if self.log_every and step % self.log_every == 0:
+            _append_jsonl(os.path.join(self.model_dir, "train_log.jsonl"), self.last)
+            self._last_log = (step, now)
+
+    def drain(self):
+        """Examines every outstanding read-back (waits for the device)."""
+        while self._pending:
+            self._examine(self._pending[0])
+
+    # ------------------------------------------------------------------ checkpoints, evaluation
+    def save(self):
+        """A checkpoint of the current step (after draining: none is written once a step was non-finite), the newest
+        KEEP_CHECKPOINT_MAX kept.  Returns the prefix."""
+        if self._failed:
+            raise RuntimeError("this run stopped on a non-finite value")
+        self.drain()
+        prefix = self.train_step.save(self.model_dir)
+        prune_checkpoints(self.model_dir, KEEP_CHECKPOINT_MAX)
+        self._saved_step = self.global_step
+        self._last_save = (self.global_step, time.monotonic())
+        return prefix
+
+    def evaluate(self):
+        """estimator.evaluate with RestoreMovingAverageHook: the moving averages of the current step's checkpoint over val_dataset;
+        the dict (with `step`) is appended to model_dir/eval_log.jsonl and returned."""
+        from .detector import Detector
+        from .evaluation import evaluate
+        if self._saved_step != self.global_step:
+            self.save()
+        self.drain()
+        det = Detector(self.model_dir, visible_device_list=str(self.device.index), config=self.config, use_ema=True)
+        try:
+            res = evaluate(det, self.run_config["val_dataset"], self.config, read_workers=self.read_workers, decode=self.decode)
+        finally:
+            det.close()
+        res = dict(res, step=int(self.global_step))
+        _append_jsonl(os.path.join(self.model_dir, "eval_log.jsonl"), res)
+        return res
+
+    def train(self, max_steps=None, save_checkpoints_steps=None, save_checkpoints_secs=SAVE_CHECKPOINTS_SECS, log_every=100, on_step=None):
+        """Steps until global_step == max_steps (default num_steps), checkpoints on schedule and at the end.  on_step(step) is
+        called after each enqueued step; when it returns True the loop ends early (train_and_evaluate's evaluations)."""
+        max_steps = int(self.config["num_steps"] if max_steps is None else max_steps)
+        self.log_every = int(log_every)
+        try:
+            while self.global_step < max_steps:
+                t = self.step()
+                if due(t, time.monotonic(), self._last_save[0], self._last_save[1], save_checkpoints_steps,
+                       None if save_checkpoints_steps is not None else save_checkpoints_secs):
+                    self.save()
+                if on_step is not None and on_step(t):
+                    break
+            self.drain()
+            if self._saved_step != self.global_step:
+                self.save()
+        finally:
+            self.close_pipeline()
+        return self.global_step
+
+    def train_and_evaluate(self, max_steps=None, eval_every_steps=None, eval_every_secs=EVAL_THROTTLE_SECS, save_checkpoints_steps=None,
+                           save_checkpoints_secs=SAVE_CHECKPOINTS_SECS, log_every=100, on_eval=None):
+        """tf.estimator.train_and_evaluate (train.py:61-66): trains, evaluates on schedule and once more at the end.  Returns the
+        list of evaluation dicts; on_eval(dict) is called with each as it is made."""
+        max_steps = int(self.config["num_steps"] if max_steps is None else max_steps)
+        results = []
+        last = [self.global_step, time.monotonic()]
+
+        def on_step(t):
+            if t < max_steps and due(t, time.monotonic(), last[0], last[1], eval_every_steps,
+                                     None if eval_every_steps is not None else eval_every_secs):
+                results.append(self.evaluate())
+                if on_eval is not None:
+                    on_eval(results[-1])
+                last[0], last[1] = t, time.monotonic()
+            return False
+        self.train(max_steps, save_checkpoints_steps, save_checkpoints_secs, log_every, on_step)
+        results.append(self.evaluate())
+        if on_eval is not None:
+            on_eval(results[-1])
+        return results
+
+    def close_pipeline(self):
+        """Stops the input pipeline's decode threads; the next step() starts a fresh one, seeded by the step it starts at."""
+        if self._pipe is not None:
+            gen, self._pipe = self._pipe._gen, None
+            if gen is not None:
+                gen.close()
