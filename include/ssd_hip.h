@@ -148,6 +148,8 @@ int ssd_get_precision(ssd_handle *h);
  *                     auto: from 32 768 rows on).  Detections are bit-identical; "class_predictions" is made whole by the dense
  *                     launch at its first read behind a screened forward (a caller that reads it every time sets 0) | 2: as 1
  *                     with the tensor pre-filled with 0xff bytes, for tests that read "class_logits_filled"     (-1)
+ *   "hist_scheme"     -1 default | 0 .. 4: how ssd_train_histograms aggregates a wave's equal buckets before the LDS atomic
+ *                     (its block below; process-wide only)                                                    (-1)
  * (Rounds 1-4 carried more switches -- schedule experiments that measured equal or slower: tower_group, head_serial,
  *  side_priority, level_split, fpn_p6_first, lat_one, dwpw_lat, graph, staggered sub-batch plans.  They are out of the library;
  *  scripts/experiments/README.md has what each measured and the commit that holds its source.)
@@ -583,6 +585,57 @@ int ssd_train_update(const ssd_update_tensor *tensors_host, const ssd_update_ten
 size_t ssd_train_norms_workspace_bytes(const ssd_update_tensor *tensors_host, int32_t T);
 int ssd_train_norms(const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T, double *sums,
                     int64_t *bad, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the TRAIN step's histograms: tf.summary.histogram of every variable and of every gradient of total_loss ----
+ *
+ * What train.py's summaries show of a run (model.py:121-123: `<name>_hist`, `<name>_grad_hist`), for a whole model in THREE launches
+ * over the table ssd_train_update takes, run BEFORE the update.  TensorFlow's sources are not available to this project: the rule
+ * below restates histogram::Histogram with its default limits from memory; what is pinned is this rule, NOT parity with TensorFlow.
+ * The table, its rows, the first_block rule and every refusal are the TRAIN update's; m, v and ema are validated and never
+ * dereferenced; w and grad are read and never written.
+ * Limits: start v = 1e-12 (double); while v < 1e20 append v and set v *= 1.1 (one double multiplication each); then append DBL_MAX.
+ *   The table is the negated list reversed, then 0.0, then the list: NB entries, strictly increasing, antisymmetric about its middle.
+ *   ssd_histogram_limits(out, capacity) returns NB and fills out[0 .. NB) when out != NULL and capacity >= NB (else it writes
+ *   nothing): the ONE definition -- the caller uploads exactly this table once and passes it as limits_dev.
+ * Planes: plane 0 of a row is w; plane 1 is the gradient of total_loss, g' = g + weight_decay * w where decay == 1, else g' = g (one
+ *   fp32 multiply and one fp32 add, contraction off: step 1 of ssd_train_update).  A NULL grad gives an all-zero plane 1 with num = 0.
+ * Bucket of a finite element x: widen x to double; the bucket is the index of the first limit strictly greater than it (upper_bound:
+ *   the number of limits <= x; -0.0 goes with +0.0).  A non-finite element (NaN, +inf, -inf) counts in `bad` and enters no bucket and
+ *   no statistic.
+ * Outputs, in device memory, rows in table order; the caller need not clear them:
+ *   counts [T][2][NB] int64     stats [T][2] ssd_histogram_stats: sum of (double)x, sum_squares of (double)x * (double)x, min, max,
+ *   num (the finite elements) and bad.  min and max order -0.0 below +0.0 (so that they do not depend on the order of the elements);
+ *   of a plane without a finite element they are +inf and -inf.
+ * Order of the double additions: exactly the TRAIN step's norms' (above) -- the virtual elements from the 16-byte boundary at or
+ *   below w (pad taken from w, whatever grad's alignment), lane t's 16 elements k outer, e inner from +0.0, the 256-lane tree
+ *   a[t] += a[t + s], the blocks' partials in ascending order from +0.0; an element outside the tensor or not finite adds +0.0.  A
+ *   numpy float64 restatement is bit-exact; stats[t][0].sum_squares has the bits of ssd_train_norms' sums[t][0], and
+ *   stats[t][1].sum_squares those of sums[t][1] where decay == 0.
+ * Atomics: the bucket counts are integers and are added with integer atomics (LDS inside a block, vector global atomics for a
+ *   block's flush); they change no bit: two calls give the same bytes.  No floating-point atomics.  The process-wide option
+ *   "hist_scheme" (ssd_set_option(NULL, ...)) picks how a wave's equal buckets meet the LDS atomic: -1 the library's choice (1) | 0
+ *   one atomic per element | 1 one ballot: a wave whose finite elements all share one bucket adds their number once, any other wave
+ *   takes one atomic per element | 2, 3: one, two rounds in which the lanes that share the first pending lane's bucket are counted
+ *   with a ballot and added by one lane, then one atomic per remaining element | 4 and above: rounds until nothing is pending.
+ *   The results are the same bytes under every value.
+ * workspace: ssd_train_histograms_workspace_bytes(tensors_host, T) = SSD_HISTOGRAM_BLOCK_BYTES per block of the table (0 for a table
+ * of empty tensors and for one the call would refuse), 16-byte aligned, written by stage 1 and read by stage 2, no initialisation.
+ * No allocation, no host synchronisation: the call only enqueues on `stream` (a clear of counts, stage 1 unless the table has no
+ * blocks, stage 2).  Beyond the update's refusals (without its scalars): a NULL limits_dev, counts or stats or one not 8-byte
+ * aligned, a NULL workspace or one not 16-byte aligned, a workspace smaller than the planner's figure, a non-finite weight_decay:
+ * SSD_ERR_INVALID before any HIP call.  Needs no handle. */
+#define SSD_HISTOGRAM_BLOCK_BYTES 64
+#define SSD_HISTOGRAM_STATS_BYTES 40
+typedef struct ssd_histogram_stats {         /* 40 bytes, no padding */
+    double sum, sum_squares;                 /* of the finite elements, in double                              */
+    float min, max;                          /* of the finite elements; +inf, -inf when there is none          */
+    int64_t num, bad;                        /* finite elements; NaN and +-inf                                 */
+} ssd_histogram_stats;
+int32_t ssd_histogram_limits(double *out, int32_t capacity);
+size_t ssd_train_histograms_workspace_bytes(const ssd_update_tensor *tensors_host, int32_t T);
+int ssd_train_histograms(const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T, float weight_decay,
+                         const double *limits_dev, int64_t *counts, ssd_histogram_stats *stats, void *workspace,
+                         size_t workspace_bytes, void *stream);
 
 /* ---- the TRAIN head: forward and backward of RetinaNetBoxPredictor in TRAIN mode (box_predictor.py:34-155) ----
  *

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "logit_screen.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
             "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip", "train_head.hip", "wgrad.hip", "train_backbone.hip", "train_shufflenet.hip",
-            "train_first_f32.hip", "train_norms.hip"]
+            "train_first_f32.hip", "train_norms.hip", "train_hist.hip"]
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
 _lib = None
@@ -212,6 +212,9 @@ SIGNATURES = {
     "ssd_train_update": (ctypes.c_int, [_vp, _vp, _i, ctypes.POINTER(SsdUpdateScalars), _vp]),
     "ssd_train_norms_workspace_bytes": (ctypes.c_size_t, [_vp, _i]),
     "ssd_train_norms": (ctypes.c_int, [_vp, _vp, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_histogram_limits": (ctypes.c_int32, [_vp, _i]),
+    "ssd_train_histograms_workspace_bytes": (ctypes.c_size_t, [_vp, _i]),
+    "ssd_train_histograms": (ctypes.c_int, [_vp, _vp, _i, ctypes.c_float, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "ssd_conv3x3_train_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i]),
     "ssd_conv3x3_train_forward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "ssd_conv3x3_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),

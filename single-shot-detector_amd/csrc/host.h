@@ -61,6 +61,8 @@ enum SsdOpt {
     OPT_DEBUG_SYNC,         // 0 | 1: announce every op, run it alone, wait for it (fault localisation)
     OPT_LOGITS_SCREEN,      // -1 auto | 0: the class logits as one dense launch | 1: screen + fill (logit_screen.hip; exact fp32 mode only)
                             // | 2: as 1, and the logits tensor is filled with 0xff bytes first (tests read what the fill wrote)
+    OPT_HIST_SCHEME,        // -1 default (1) | 0: one LDS atomic per element | 1: one ballot for a wave-uniform bucket | 2, 3: one, two rounds of wave aggregation | 4..: rounds until none is pending
+                            // (train_hist.hip; read process-wide: the call takes no handle)
     OPT_COUNT
 };
 #define SSD_OPT_UNSET INT_MIN

@@ -405,28 +405,31 @@ def _differentiable_loss_function(torch):
 
         class SsdLossFunction(torch.autograd.Function):
             @staticmethod
-            def forward(ctx, logits, codes, anchors, groundtruth, gamma, alpha, anchors_per_level):
+            def forward(ctx, logits, codes, anchors, groundtruth, gamma, alpha, anchors_per_level, with_per_image=False):
                 reg, cls, matches = get_training_targets(anchors, groundtruth["boxes"], groundtruth["labels"],
                                                          groundtruth["num_boxes"])
                 losses, per_image = ssd_loss(logits, codes, anchors, groundtruth, gamma=gamma, alpha=alpha,
                                              anchors_per_level=anchors_per_level)
                 ctx.save_for_backward(logits, codes, reg, cls, matches, per_image)
                 ctx.gamma, ctx.alpha = gamma, alpha
+                if with_per_image:
+                    ctx.mark_non_differentiable(per_image)
+                    return losses[0], losses[1], per_image
                 return losses[0], losses[1]
 
             @staticmethod
             @once_differentiable
-            def backward(ctx, g_loc, g_cls):
+            def backward(ctx, g_loc, g_cls, *_g_per_image):
                 logits, codes, reg, cls, matches, per_image = ctx.saved_tensors
                 g = torch.stack([g_loc.reshape(()), g_cls.reshape(())]).to(torch.float32)
                 d_logits, d_codes = ssd_loss_backward(logits, codes, reg, cls, matches, per_image, ctx.gamma, ctx.alpha, g)
-                return d_logits, d_codes, None, None, None, None, None
+                return d_logits, d_codes, None, None, None, None, None, None
 
         _loss_function = SsdLossFunction
     return _loss_function
 
 
-def differentiable_loss(class_predictions, encoded_boxes, anchors, groundtruth, params, anchors_per_level=()):
+def differentiable_loss(class_predictions, encoded_boxes, anchors, groundtruth, params, anchors_per_level=(), per_image=False):
     """ssd.py:71-133 as a differentiable torch op: {'localization_loss', 'classification_loss'} (0-d CUDA tensors, bit-equal
     to ssd_loss's) whose backward is ssd_loss_backward.  class_predictions [B,N,C] and encoded_boxes [B,N,4] are CUDA
     float32 tensors in the reference's anchor order (non-contiguous ones are copied); anchors [N,4] (unclipped),
@@ -436,11 +439,17 @@ def differentiable_loss(class_predictions, encoded_boxes, anchors, groundtruth, 
     Gradients stop at the head outputs: the tensors an Engine retains (class_predictions / encoded_boxes of a forward)
     are plain tensors, not part of any autograd graph -- this trains a torch model that emits logits and box codes, not
     the HIP network.  The regularisation term of train.py (weight_decay * the sum of squared weights, model.py:132-145)
-    is the caller's to add."""
+    is the caller's to add.  per_image=True adds the key 'per_image': ssd_loss's [B, 3 + levels] tensor of this forward (per image:
+    localization loss, classification loss, matches, matches on each level of anchors_per_level), which carries no gradient; the
+    default return is unchanged."""
     torch = _torch()
     fn = _differentiable_loss_function(torch)
-    loc, cls = fn.apply(class_predictions.contiguous(), encoded_boxes.contiguous(), anchors.contiguous(), groundtruth,
-                        float(params["gamma"]), float(params["alpha"]), tuple(int(n) for n in anchors_per_level))
+    args = (class_predictions.contiguous(), encoded_boxes.contiguous(), anchors.contiguous(), groundtruth,
+            float(params["gamma"]), float(params["alpha"]), tuple(int(n) for n in anchors_per_level))
+    if per_image:
+        loc, cls, rows = fn.apply(*args, True)
+        return {"localization_loss": loc, "classification_loss": cls, "per_image": rows}
+    loc, cls = fn.apply(*args, False)
     return {"localization_loss": loc, "classification_loss": cls}
 
 

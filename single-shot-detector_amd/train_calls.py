@@ -8,6 +8,7 @@ workspace=None: the grow-only buffer per (device, stream), sized by the call's o
 buffer (data_ptr(), numel()), which the family's *_workspace_bytes sizes."""
 import ctypes
 
+import numpy as np
 import torch
 
 from ._lib import SsdBnLevel, SsdConvLevel, check, lib
@@ -441,3 +442,49 @@ def train_norms(rows_host, rows_dev, sums, bad, workspace=None):
     L = lib()
     _run(dev, workspace, lambda: L.ssd_train_norms_workspace_bytes(rows_host.data_ptr(), T),
          lambda *tail: L.ssd_train_norms(rows_host.data_ptr(), rows_dev.data_ptr(), T, sums.data_ptr(), bad.data_ptr(), *tail))
+
+
+# ----------------------------------------------------------------------------- the TRAIN step's histograms
+STATS_BYTES = 40                                                               # sizeof(ssd_histogram_stats)
+# ssd_histogram_stats of include/ssd_hip.h: what a host copy of `stats` (uint8 [T,2,40]) is viewed as
+STATS_DTYPE = np.dtype([("sum", "<f8"), ("sum_squares", "<f8"), ("min", "<f4"), ("max", "<f4"), ("num", "<i8"), ("bad", "<i8")])
+assert STATS_DTYPE.itemsize == STATS_BYTES
+_limits = None
+
+
+def histogram_limits():
+    """ssd_histogram_limits: TF's default histogram limits as a read-only numpy float64 table [NB] (the library's ONE definition)."""
+    global _limits
+    if _limits is None:
+        L = lib()
+        NB = L.ssd_histogram_limits(None, 0)
+        out = np.empty(NB, np.float64)
+        if L.ssd_histogram_limits(out.ctypes.data, NB) != NB:
+            raise RuntimeError("ssd_histogram_limits changed its answer")
+        out.setflags(write=False)
+        _limits = out
+    return _limits
+
+
+def train_histograms_workspace_bytes(rows_host, T=None):
+    """ssd_train_histograms_workspace_bytes of the table's host copy (0: a table of empty tensors, or one the call would refuse)."""
+    T = _rows_host(rows_host, T)
+    return lib().ssd_train_histograms_workspace_bytes(rows_host.data_ptr(), T)
+
+
+def train_histograms(rows_host, rows_dev, weight_decay, limits_dev, counts, stats, workspace=None):
+    """ssd_train_histograms over the update's table (rows_host, rows_dev as for train_norms): limits_dev is histogram_limits() on the
+    GPU (float64 [NB], the caller's one upload), counts int64 [T,2,NB] receives the bucket counts of w and of the gradient of
+    total_loss (g + weight_decay * w on decaying rows), stats uint8 [T,2,40] the ssd_histogram_stats (STATS_DTYPE on the host)."""
+    T = _rows_host(rows_host, None)
+    NB = len(histogram_limits())
+    _dense(rows_dev, "rows_dev", (T * ROW_BYTES,), torch.uint8)
+    _dense(limits_dev, "limits_dev", (NB,), torch.float64)
+    _dense(counts, "counts", (T, 2, NB), torch.int64)
+    _dense(stats, "stats", (T, 2, STATS_BYTES), torch.uint8)
+    dev = _one_gpu(workspace, rows_dev=rows_dev, limits_dev=limits_dev, counts=counts, stats=stats)
+    L = lib()
+    wd = ctypes.c_float(float(weight_decay))
+    _run(dev, workspace, lambda: L.ssd_train_histograms_workspace_bytes(rows_host.data_ptr(), T),
+         lambda *tail: L.ssd_train_histograms(rows_host.data_ptr(), rows_dev.data_ptr(), T, wd, limits_dev.data_ptr(), counts.data_ptr(),
+                                              stats.data_ptr(), *tail))

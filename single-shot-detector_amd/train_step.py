@@ -313,6 +313,58 @@ class TrainStep:
         self._norms_calls += 1
         return sums, bad
 
+    # ------------------------------------------------------------------ the histograms
+    def histograms(self):
+        """(counts, stats) of the parameters and of the gradients of total_loss (include/ssd_hip.h, "the TRAIN step's histograms"):
+        counts int64 [T,2,NB] over train_calls.histogram_limits(), stats uint8 [T,2,40] (train_calls.STATS_DTYPE on the host), plane
+        0 the variable, plane 1 its current .grad plus weight_decay * w where the variable decays; rows in `names` order; a
+        parameter whose .grad is None gives an all-zero plane 1 with num = 0.  Called BEFORE step(), like norms(), whose discipline
+        this is: one small asynchronous upload from a pinned ring of its own (step()'s and norms()' are not touched), a fixed
+        number of launches on the current stream, never waits for the device; the results are CUDA tensors of this call.  The
+        limits are uploaded once per TrainStep."""
+        import torch
+        from . import train_calls
+        if torch.cuda.is_current_stream_capturing():
+            # the gradients' addresses are read here, on the host: a captured launch would replay this step's addresses for ever
+            raise RuntimeError("TrainStep.histograms() cannot be captured into a graph: the gradient addresses change from step to "
+                               "step on the host; call it outside the capture")
+        T = len(self.names)
+        grads = np.zeros(T, np.uint64)
+        for i, name in enumerate(self.names):
+            p = self.parameters[name]
+            if p.data_ptr() != int(self._w_ptrs[i]):
+                raise RuntimeError("the storage of parameter %r was replaced after TrainStep was built" % name)
+            g = p.grad
+            if g is None:
+                continue
+            if g.dtype != torch.float32 or g.device != self.device or g.shape != p.shape or not g.is_contiguous() or g.data_ptr() % 4:
+                raise ValueError("the gradient of %r must be a contiguous float32 tensor of the parameter's shape and device" % name)
+            grads[i] = g.data_ptr()
+        with torch.cuda.device(self.device):
+            if not hasattr(self, "_hist_ring"):
+                nbytes = T * TENSOR_DTYPE.itemsize
+                self._hist_ring, self._hist_calls = [], 0
+                for _ in range(self.RING):
+                    host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+                    self._hist_ring.append({"host": host, "rows": host.numpy().view(TENSOR_DTYPE),
+                                            "dev": torch.empty(nbytes, dtype=torch.uint8, device=self.device),
+                                            "event": torch.cuda.Event(), "used": False})
+                self._hist_limits = torch.from_numpy(train_calls.histogram_limits().copy()).to(self.device)
+            slot = self._hist_ring[self._hist_calls % self.RING]
+            if slot["used"]:
+                slot["event"].synchronize()      # the upload that last read this pinned slot (RING calls ago) has run
+            rows = slot["rows"]
+            rows[:] = self._table
+            rows["grad"] = grads
+            counts = torch.empty((T, 2, self._hist_limits.numel()), dtype=torch.int64, device=self.device)
+            stats = torch.empty((T, 2, train_calls.STATS_BYTES), dtype=torch.uint8, device=self.device)
+            slot["dev"].copy_(slot["host"], non_blocking=True)
+            slot["event"].record(torch.cuda.current_stream(self.device))
+            slot["used"] = True
+            train_calls.train_histograms(slot["host"], slot["dev"], np.float32(self.config["weight_decay"]), self._hist_limits, counts, stats)
+        self._hist_calls += 1
+        return counts, stats
+
     def regularization_loss(self, sums_host):
         """model.py:80-81 from norms()' sums read back to the host ([T,2] float64): fp32(weight_decay * sum over the decaying rows,
         in `names` order, of sums[t,0] / 2), formed in float64 and rounded once -- evaluation.regularization_loss's definition on

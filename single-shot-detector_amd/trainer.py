@@ -8,7 +8,9 @@ already has --
 reports total_loss with the regularisation term from the GPU's per-tensor sums, stops on a non-finite loss, gradient or variable
 (NanTensorHook), writes checkpoints and logs on a schedule and evaluates the moving averages (RestoreMovingAverageHook).
 
-One GPU, no graph capture of a step, no TensorBoard files, no gradient clipping, exact fp32 only.  The host
+TensorBoard's event files (summaries.py: the scalars and a histogram of every variable and gradient, model.py:88-90, 113, 121-123)
+are written every save_summary_steps steps, off by default in the API.  One GPU, no graph capture of a step, no gradient clipping,
+exact fp32 only.  The host
 logic that needs no GPU -- schedules, seeds, the warm start, pruning, the stop decision -- is the module-level functions below.
 """
 import json
@@ -25,6 +27,11 @@ from .config import (load_config, load_loss_config, load_optimizer_config, load_
 SAVE_CHECKPOINTS_SECS = 1800            # train.py:39
 EVAL_THROTTLE_SECS = 3 * 3600           # train.py:63
 KEEP_CHECKPOINT_MAX = 5                 # tf.estimator.RunConfig's default
+SAVE_SUMMARY_STEPS = 600                # train.py:39 (the command's default; the API's is 0: no summaries)
+# the scalar tags of the reference's graph (model.py:88-90, 113 under variable_scope('learning_rate'); `loss` and `global_step/sec`
+# are tf.estimator's own) -> the key of log_record that holds the value
+SUMMARY_SCALARS = (("loss", "loss"), ("regularization_loss", "regularization_loss"), ("localization_loss", "localization_loss"),
+                   ("classification_loss", "classification_loss"), ("learning_rate/learning_rate", "learning_rate"))
 BACKBONE_SCOPES = {"mobilenet": "MobilenetV1/", "shufflenet": "ShuffleNetV2/"}     # train.py:44-47
 RING = 4                                # read-back slots: step k - 1 is examined after step k was enqueued
 
@@ -41,6 +48,36 @@ def due(step, now, last_step, last_time, every_steps, every_secs):
     if every_secs is not None:
         return now - last_time >= float(every_secs)
     return False
+
+
+MATCHES_SCOPE = "losses/loss_summaries/"                                           # ssd.py:86, 125
+
+
+def summary_due(step, last_summary_step, every):
+    """SummarySaverHook's schedule: is a summary due at `step`, the last one of this (re)started run having been written at
+    `last_summary_step` (None: none yet)?  The first step of a run, then every step with step - last >= every; every == 0: never."""
+    every = int(every)
+    if every < 0:
+        raise ValueError("save_summary_steps must be >= 0")
+    if every == 0:
+        return False
+    return last_summary_step is None or int(step) - int(last_summary_step) >= every
+
+
+def summary_scalars(record, steps_per_second=None, per_image=None):
+    """{tag: value} of one summary event from a log_record: SUMMARY_SCALARS, `global_step/sec` when a rate is known, and -- from
+    ssd_loss's per_image rows [B, 3 + levels] -- the matches summaries of ssd.py:125-129, 154-163 under their name scopes: the
+    mean over the batch of the matches per image, on each level (3 ..) and in total, float32 (a sum of small integers, one division)."""
+    out = {tag: record[key] for tag, key in SUMMARY_SCALARS}
+    if steps_per_second is not None:
+        out["global_step/sec"] = float(steps_per_second)
+    if per_image is not None:
+        rows = np.asarray(per_image, np.float32)
+        B = np.float32(rows.shape[0])
+        for level in range(rows.shape[1] - 3):
+            out[MATCHES_SCOPE + "mean_matches_per_image_on_level_%d" % (3 + level)] = float(rows[:, 3 + level].sum(dtype=np.float32) / B)
+        out[MATCHES_SCOPE + "total_mean_matches_per_image"] = float(rows[:, 2].sum(dtype=np.float32) / B)
+    return out
 
 
 def pipeline_seed(seed, step):
@@ -226,6 +263,7 @@ class Trainer:
             gen = AnchorGenerator()
             hw = (self.train_config["image_height"], self.train_config["image_width"])
             self.anchors = torch.from_numpy(gen(*hw)).to(self.device)
+            self.anchors_per_level = tuple(int(n) for n in gen.num_anchors_per_feature_map)
             self.loc_weight = torch.tensor(np.float32(self.loss_config["localization_loss_weight"]), device=self.device)
             self.cls_weight = torch.tensor(np.float32(self.loss_config["classification_loss_weight"]), device=self.device)
             T = len(self.train_step.names)
@@ -240,6 +278,11 @@ class Trainer:
         self._saved_step = self.start_step if resumed is not None else -1
         self._last_save = (self.start_step, time.monotonic())
         self._last_log = (self.start_step, time.monotonic())
+        self.save_summary_steps = 0         # train()'s option: 0 enqueues, allocates and writes nothing
+        self._last_summary = None           # the last step of THIS run with a summary
+        self._last_rate = None              # (step, time) of the last summary event: global_step/sec
+        self._hist_ring = None              # pinned read-back slots of the histograms, made by the first due step
+        self._writers = {}                  # logdir -> summaries.EventFileWriter
         self.last = None                    # the newest examined step's log_record
 
     @property
@@ -265,12 +308,32 @@ class Trainer:
             for p in self.variables.values():
                 p.grad = None
             eb, cp = self.head(self.fpn(self.backbone(images)))
-            out = differentiable_loss(cp, eb, self.anchors, gt, self.loss_config)
+            want_summary = summary_due(self.global_step + 1, self._last_summary, self.save_summary_steps)
+            if want_summary:                            # the loss with its per-image rows: the matches per level (ssd.py:154-163)
+                out = differentiable_loss(cp, eb, self.anchors, gt, self.loss_config, anchors_per_level=self.anchors_per_level,
+                                          per_image=True)
+            else:
+                out = differentiable_loss(cp, eb, self.anchors, gt, self.loss_config)
             loc, cls = out["localization_loss"], out["classification_loss"]
             (self.loc_weight * loc + self.cls_weight * cls).backward()
             sums, bad = self.train_step.norms()         # before the update: of the variables this step computed with
+            hist = None
+            if want_summary:
+                hist = self.train_step.histograms()     # beside the norms, of the same variables and gradients
+                self._last_summary = self.global_step + 1
             t = self.train_step.step()
             slot = self._ring[t % RING]
+            slot["hist"] = None
+            if hist is not None:
+                if self._hist_ring is None:
+                    self._hist_ring = [{"counts": torch.empty(hist[0].shape, dtype=torch.int64).pin_memory(),
+                                        "stats": torch.empty(hist[1].shape, dtype=torch.uint8).pin_memory(),
+                                        "per_image": torch.empty(out["per_image"].shape, dtype=torch.float32).pin_memory()}
+                                       for _ in range(RING)]
+                slot["hist"] = self._hist_ring[t % RING]
+                slot["hist"]["counts"].copy_(hist[0], non_blocking=True)
+                slot["hist"]["stats"].copy_(hist[1], non_blocking=True)
+                slot["hist"]["per_image"].copy_(out["per_image"], non_blocking=True)
             slot["losses"][0:1].copy_(loc.detach().reshape(1), non_blocking=True)
             slot["losses"][1:2].copy_(cls.detach().reshape(1), non_blocking=True)
             slot["sums"].copy_(sums, non_blocking=True)
@@ -303,6 +366,38 @@ class Trainer:
         if self.log_every and step % self.log_every == 0:
             _append_jsonl(os.path.join(self.model_dir, "train_log.jsonl"), self.last)
             self._last_log = (step, now)
+        if slot.get("hist") is not None:
+            try:
+                self._write_summary(step, slot["hist"], now)
+            except FloatingPointError:                  # g + weight_decay * w overflowed where g and w were finite: TF stops here, too
+                self._failed = True
+                self._pending.clear()
+                raise
+
+    def _writer(self, logdir):
+        from .summaries import EventFileWriter
+        if logdir not in self._writers:
+            self._writers[logdir] = EventFileWriter(logdir)
+        return self._writers[logdir]
+
+    def _write_summary(self, step, hist, now):
+        """The summary event of an examined, finite step: the scalars of its log_record and `<name>_hist` / `<name>_grad_hist` of
+        every variable (a parameter without a gradient gets no `_grad_hist`)."""
+        from .summaries import histogram_proto
+        from .train_calls import STATS_DTYPE, histogram_limits
+        limits = histogram_limits()
+        counts = hist["counts"].numpy()
+        stats = hist["stats"].numpy().view(STATS_DTYPE)[:, :, 0]
+        histograms = {}
+        for t, name in enumerate(self.train_step.names):
+            histograms[name + "_hist"] = histogram_proto(limits, counts[t, 0], stats[t, 0])
+            if stats[t, 1]["num"] > 0:
+                histograms[name + "_grad_hist"] = histogram_proto(limits, counts[t, 1], stats[t, 1])
+        rate = None
+        if self._last_rate is not None and now > self._last_rate[1]:
+            rate = (step - self._last_rate[0]) / (now - self._last_rate[1])
+        self._last_rate = (step, now)
+        self._writer(self.model_dir).add_summary(step, summary_scalars(self.last, rate, hist["per_image"].numpy()), histograms)
 
     def drain(self):
         """Examines every outstanding read-back (waits for the device)."""
@@ -337,13 +432,21 @@ class Trainer:
             det.close()
         res = dict(res, step=int(self.global_step))
         _append_jsonl(os.path.join(self.model_dir, "eval_log.jsonl"), res)
+        if self.save_summary_steps:
+            scalars = {k: v for k, v in res.items() if k != "step" and isinstance(v, (int, float)) and not isinstance(v, bool)}
+            self._writer(os.path.join(self.model_dir, "eval")).add_summary(int(self.global_step), scalars)
         return res
 
-    def train(self, max_steps=None, save_checkpoints_steps=None, save_checkpoints_secs=SAVE_CHECKPOINTS_SECS, log_every=100, on_step=None):
+    def train(self, max_steps=None, save_checkpoints_steps=None, save_checkpoints_secs=SAVE_CHECKPOINTS_SECS, log_every=100, on_step=None,
+              save_summary_steps=0):
         """Steps until global_step == max_steps (default num_steps), checkpoints on schedule and at the end.  on_step(step) is
-        called after each enqueued step; when it returns True the loop ends early (train_and_evaluate's evaluations)."""
+        called after each enqueued step; when it returns True the loop ends early (train_and_evaluate's evaluations).
+        save_summary_steps: 0 no summaries | n: model_dir/events.out.tfevents.* gets the scalars and the histograms of every variable
+        and gradient at the run's first step and then every n steps (summary_due)."""
         max_steps = int(self.config["num_steps"] if max_steps is None else max_steps)
         self.log_every = int(log_every)
+        summary_due(0, None, save_summary_steps)        # refuses a negative value
+        self.save_summary_steps = int(save_summary_steps)
         try:
             while self.global_step < max_steps:
                 t = self.step()
@@ -360,10 +463,13 @@ class Trainer:
         return self.global_step
 
     def train_and_evaluate(self, max_steps=None, eval_every_steps=None, eval_every_secs=EVAL_THROTTLE_SECS, save_checkpoints_steps=None,
-                           save_checkpoints_secs=SAVE_CHECKPOINTS_SECS, log_every=100, on_eval=None):
+                           save_checkpoints_secs=SAVE_CHECKPOINTS_SECS, log_every=100, on_eval=None, save_summary_steps=0):
         """tf.estimator.train_and_evaluate (train.py:61-66): trains, evaluates on schedule and once more at the end.  Returns the
-        list of evaluation dicts; on_eval(dict) is called with each as it is made."""
+        list of evaluation dicts; on_eval(dict) is called with each as it is made.  save_summary_steps: train()'s; when set, every
+        evaluation's scalar entries are also written to model_dir/eval/events.out.tfevents.* at its step."""
         max_steps = int(self.config["num_steps"] if max_steps is None else max_steps)
+        summary_due(0, None, save_summary_steps)
+        self.save_summary_steps = int(save_summary_steps)
         results = []
         last = [self.global_step, time.monotonic()]
 
@@ -375,7 +481,7 @@ class Trainer:
                     on_eval(results[-1])
                 last[0], last[1] = t, time.monotonic()
             return False
-        self.train(max_steps, save_checkpoints_steps, save_checkpoints_secs, log_every, on_step)
+        self.train(max_steps, save_checkpoints_steps, save_checkpoints_secs, log_every, on_step, save_summary_steps)
         results.append(self.evaluate())
         if on_eval is not None:
             on_eval(results[-1])
