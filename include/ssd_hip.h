@@ -637,6 +637,60 @@ int ssd_train_histograms(const ssd_update_tensor *tensors_host, const ssd_update
                          const double *limits_dev, int64_t *counts, ssd_histogram_stats *stats, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* ---- the TRAIN step's gradient exchange: every rank's gradients gathered once and summed in rank order ----
+ *
+ * Data-parallel training over G ranks (one process per GPU) without an all-reduce, whose order of additions would depend on the
+ * backend, its ring and the world size: every rank PACKS its gradients, its moving statistics and a 3-word header into one slice
+ * of a receive buffer, the caller runs ONE all-gather of the slices (any backend: the bytes are what matters), and every rank
+ * REDUCES the G slices in ascending rank order back into its own tensors.  Every rank computes the same bits from the same bytes.
+ * The reference has no multi-GPU code; the loss rule below is its loss (ssd.py:121-133) over the global batch.
+ *
+ * The table: T rows (1 .. SSD_UPDATE_MAX_TENSORS), one per tensor; rows_host is read by the call to refuse bad rows, rows_dev holds
+ * the same rows in device memory (8-byte aligned), which the kernel reads -- the caller's upload, ordered before the call on `stream`.
+ *   data     the tensor: read by pack, written by reduce; 4-byte aligned.  NULL: pack ships +0.0 for the row and reduce writes
+ *            nothing (a parameter without a gradient).  The data ranges of a table must not overlap.
+ *   count    elements, 0 .. 2^40
+ *   offset   the row's first float in the payload (below)
+ *   kind     0: a gradient, weighted by c_r | 1: a moving statistic, the plain mean over the ranks
+ * The bucket layout depends on the counts alone, so it is the same on every rank whatever the addresses are:
+ *   offset_0 = 0,  offset_{t+1} = offset_t + roundup(count_t, 4);   payload floats P = roundup(offset_T, SSD_UPDATE_BLOCK_ELEMS)
+ *   a slice = SSD_REDUCE_HEADER_FLOATS header floats, then the payload: ssd_train_bucket_floats(rows_host, T) = 16 + P floats
+ *   (0 for a table the calls would refuse).  Header word 0: this rank's matches n_r (a float), word 1: its localization loss, word 2:
+ *   its classification loss, words 3 .. 15: +0.0.  The gathered buffer is [G][16 + P] floats, 16-byte aligned, rank r's slice at r.
+ * ssd_train_grad_pack writes EVERY float of one slice: the header (header_dev: 3 floats in device memory), each row's elements at its
+ *   offset, and +0.0 for a row's padding to 4, for a NULL row and for the payload behind the last row -- the collective never ships
+ *   an uninitialised byte.  The values are copied, bit for bit.
+ * ssd_train_grad_reduce reads gathered[G][16 + P].  float32, contraction off, every operation rounded once, max(a, 1) = a > 1 ? a : 1:
+ *   S   = n_0 + n_1 + ... + n_{G-1}, added in ascending order
+ *   c_r = max(n_r, 1) / max(S, 1), the division correctly rounded                                       -> weights_out[r]
+ *   kind 0:  acc = x_0 * c_0;  acc = acc + x_r * c_r  for r = 1 .. G-1;  data[i] = acc
+ *   kind 1:  acc = x_0;        acc = acc + x_r        for r = 1 .. G-1;  data[i] = acc * (1.0f / (float)G)
+ *   losses_out[0], [1]: the kind-0 rule on header words 1 and 2 (the losses over the global batch, normalised by max(S, 1), when
+ *   every rank's loss is normalised by its own max(n_r, 1))
+ *   At G = 1, c_0 = 1.0f and x * 1.0f keeps every bit of x (-0.0, denormals, a quiet NaN's payload): the exchange is the identity.
+ *   A NaN an operation creates (inf - inf) is some quiet NaN: its sign and payload are not pinned, and neither is the payload that
+ *   survives where two NaNs meet.  A numpy float32 restatement is otherwise bit-exact.  No atomics: two calls give the same bytes, and the
+ *   bits do not depend on whether an element moved in a 16-byte group (data 16-byte aligned) or alone (any other alignment).
+ * Both calls only enqueue one kernel on `stream` (256 lanes, blocks of SSD_UPDATE_BLOCK_ELEMS bucket floats, a grid of at most 2048
+ * striding over them): no LDS, no allocation, no host synchronisation, no handle.  SSD_ERR_INVALID before any HIP call: NULL tables
+ * or buffers; rows_dev not 8-byte, slice / gathered not 16-byte, header_dev / losses_out / weights_out / data not 4-byte aligned;
+ * T out of range; a negative count or one above 2^40; an offset other than the rule's; a kind other than 0 / 1; G < 1 or
+ * G > SSD_REDUCE_MAX_RANKS; slice_floats other than ssd_train_bucket_floats(rows_host, T); data ranges that overlap. */
+#define SSD_REDUCE_HEADER_FLOATS 16
+#define SSD_REDUCE_MAX_RANKS 16
+typedef struct ssd_reduce_row {              /* 32 bytes, no padding */
+    float *data;                             /* the tensor, or NULL: zeros out, nothing back                   */
+    int64_t count;                           /* elements                                                       */
+    int64_t offset;                          /* first float of the row in the payload (see above)              */
+    int32_t kind;                            /* 0: weighted by c_r | 1: plain mean                             */
+    int32_t reserved;
+} ssd_reduce_row;
+int64_t ssd_train_bucket_floats(const ssd_reduce_row *rows_host, int32_t T);
+int ssd_train_grad_pack(const ssd_reduce_row *rows_host, const ssd_reduce_row *rows_dev, int32_t T, const float *header_dev,
+                        float *slice, int64_t slice_floats, void *stream);
+int ssd_train_grad_reduce(const ssd_reduce_row *rows_host, const ssd_reduce_row *rows_dev, int32_t T, const float *gathered,
+                          int32_t G, int64_t slice_floats, float *losses_out, float *weights_out, void *stream);
+
 /* ---- the TRAIN head: forward and backward of RetinaNetBoxPredictor in TRAIN mode (box_predictor.py:34-155) ----
  *
  * The predictor is ten dense 3x3 stride-1 'same' convolutions (two towers of four 256 -> 256 layers shared by the pyramid

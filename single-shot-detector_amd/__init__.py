@@ -34,4 +34,5 @@ from .head_train import TrainableBoxPredictor, head_variable_shapes   # noqa: F4
 from .fpn_train import TrainableFPN, fpn_variable_shapes, variance_scaling_draw   # noqa: F401
 from .backbone_train import TrainableMobileNet, mobilenet_variable_shapes   # noqa: F401
 from .shufflenet_train import TrainableShuffleNet, shufflenet_variable_shapes   # noqa: F401
+from .grad_exchange import GradientExchange                           # noqa: F401  (data-parallel training's one collective)
 from .trainer import Trainer                                        # noqa: F401  (`python -m ssd_amd.train`: train.py's loop)

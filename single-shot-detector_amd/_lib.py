@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "logit_screen.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
             "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip", "train_head.hip", "wgrad.hip", "train_backbone.hip", "train_shufflenet.hip",
-            "train_first_f32.hip", "train_norms.hip", "train_hist.hip"]
+            "train_first_f32.hip", "train_norms.hip", "train_hist.hip", "train_reduce.hip"]
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
 _lib = None
@@ -140,6 +140,12 @@ class SsdUpdateScalars(ctypes.Structure):
                 ("epsilon", ctypes.c_float), ("weight_decay", ctypes.c_float), ("one_minus_decay", ctypes.c_float)]
 
 
+class SsdReduceRow(ctypes.Structure):
+    """ssd_reduce_row of include/ssd_hip.h (32 bytes)."""
+    _fields_ = [("data", ctypes.c_void_p), ("count", ctypes.c_int64), ("offset", ctypes.c_int64), ("kind", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class SsdConvLevel(ctypes.Structure):
     """ssd_conv_level of include/ssd_hip.h (32 bytes)."""
     _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("x", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("out", ctypes.c_void_p)]
@@ -215,6 +221,9 @@ SIGNATURES = {
     "ssd_histogram_limits": (ctypes.c_int32, [_vp, _i]),
     "ssd_train_histograms_workspace_bytes": (ctypes.c_size_t, [_vp, _i]),
     "ssd_train_histograms": (ctypes.c_int, [_vp, _vp, _i, ctypes.c_float, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "ssd_train_bucket_floats": (ctypes.c_int64, [_vp, _i]),
+    "ssd_train_grad_pack": (ctypes.c_int, [_vp, _vp, _i, _vp, _vp, ctypes.c_int64, _vp]),
+    "ssd_train_grad_reduce": (ctypes.c_int, [_vp, _vp, _i, _vp, _i, ctypes.c_int64, _vp, _vp, _vp]),
     "ssd_conv3x3_train_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i]),
     "ssd_conv3x3_train_forward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "ssd_conv3x3_train_backward": (ctypes.c_int, [ctypes.POINTER(SsdConvLevel), _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),

@@ -343,16 +343,26 @@ class TrainPipeline:
     made by the consumer in stream order from generators seeded by `seed` (one for the record order, one for the
     augmentation): the stream is the same for a seed whatever read_workers is.  While the caller runs step k, batch k + 1
     is uploaded and augmented on a side stream; the caller's current stream waits for it through an event.
-    `wait_seconds` accumulates the time the consumer blocked on a decode."""
+    `wait_seconds` accumulates the time the consumer blocked on a decode.
+    `shard` = (rank, world): this pipeline keeps shards[rank::world] of the sorted shard list (data-parallel training: every
+    rank reads its own files); a rank that would get none is a ValueError.  None: every shard."""
 
     def __init__(self, dataset_path, config, seed, decode=None, read_workers=None, device=0, channels_first=False,
-                 epochs=None, settings=None):
+                 epochs=None, settings=None, shard=None):
         cfg = load_train_config(config)
         self.batch_size = cfg["batch_size"]
         self.out_hw = (cfg["image_height"], cfg["image_width"])
         self.shards = tfrecords.shard_paths(dataset_path)
         if not self.shards:
             raise ValueError("no .tfrecords shards in %r" % (dataset_path,))
+        if shard is not None:
+            rank, world = (int(v) for v in shard)
+            if world < 1 or not 0 <= rank < world:
+                raise ValueError("shard must be (rank, world) with 0 <= rank < world, got %r" % (shard,))
+            mine = sorted(self.shards)[rank::world]
+            if not mine:
+                raise ValueError("rank %d of %d gets no shard: %r holds %d" % (rank, world, dataset_path, len(self.shards)))
+            self.shards = mine
         order_seq, aug_seq = np.random.SeedSequence(seed).spawn(2)
         self.order_rng = np.random.default_rng(order_seq)
         self.aug_rng = np.random.default_rng(aug_seq)

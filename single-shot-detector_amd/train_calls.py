@@ -1,5 +1,5 @@
 """How a TRAIN entry point of include/ssd_hip.h is called ("the TRAIN head", "the TRAIN FPN", "the TRAIN backbone", "the TRAIN first
-convolution" from uint8 and from float frames, "the TRAIN ShuffleNet", "the TRAIN step's norms"): the only module that fills ssd_conv_level / ssd_bn_level, orders the arguments, sizes the workspace and passes the
+convolution" from uint8 and from float frames, "the TRAIN ShuffleNet", "the TRAIN step's norms", "the TRAIN step's gradient exchange"): the only module that fills ssd_conv_level / ssd_bn_level, orders the arguments, sizes the workspace and passes the
 stream.  One function per entry point family, no autograd, no model.  Arguments are torch tensors, None exactly where the header
 allows NULL; every result is the CALLER's tensor.  Before the library is called every tensor is checked against the shape the
 geometry implies (ValueError naming the argument: shape, dtype, contiguity, level counts) and then for lying on one GPU
@@ -488,3 +488,67 @@ def train_histograms(rows_host, rows_dev, weight_decay, limits_dev, counts, stat
     _run(dev, workspace, lambda: L.ssd_train_histograms_workspace_bytes(rows_host.data_ptr(), T),
          lambda *tail: L.ssd_train_histograms(rows_host.data_ptr(), rows_dev.data_ptr(), T, wd, limits_dev.data_ptr(), counts.data_ptr(),
                                               stats.data_ptr(), *tail))
+
+
+# ----------------------------------------------------------------------------- the TRAIN step's gradient exchange
+REDUCE_ROW_BYTES = 32                                                          # sizeof(ssd_reduce_row)
+REDUCE_HEADER_FLOATS = 16                                                      # SSD_REDUCE_HEADER_FLOATS
+REDUCE_MAX_RANKS = 16                                                          # SSD_REDUCE_MAX_RANKS
+REDUCE_BLOCK_ELEMS = 4096                                                      # SSD_UPDATE_BLOCK_ELEMS
+# ssd_reduce_row of include/ssd_hip.h
+REDUCE_ROW_DTYPE = np.dtype([("data", "<u8"), ("count", "<i8"), ("offset", "<i8"), ("kind", "<i4"), ("reserved", "<i4")])
+assert REDUCE_ROW_DTYPE.itemsize == REDUCE_ROW_BYTES
+
+
+def bucket_layout(counts):
+    """The bucket layout of include/ssd_hip.h from the rows' counts alone -> (offsets int64 [T], slice_floats): row t starts at
+    offsets[t] = the counts before it, each rounded up to 4; a slice is the 16 header floats and the payload, rounded up to 4096."""
+    counts = np.asarray(counts, np.int64).reshape(-1)
+    if len(counts) < 1 or (counts < 0).any():
+        raise ValueError("counts: at least one row, none negative")
+    padded = (counts + 3) // 4 * 4
+    ends = np.cumsum(padded)
+    payload = (int(ends[-1]) + REDUCE_BLOCK_ELEMS - 1) // REDUCE_BLOCK_ELEMS * REDUCE_BLOCK_ELEMS
+    return ends - padded, REDUCE_HEADER_FLOATS + payload
+
+
+def _reduce_rows_host(rows_host):
+    """rows_host is the host copy of the exchange's table: a contiguous CPU uint8 tensor of T * 32 bytes -> T."""
+    if not (isinstance(rows_host, torch.Tensor) and rows_host.dtype == torch.uint8 and not rows_host.is_cuda and rows_host.dim() == 1
+            and rows_host.is_contiguous() and rows_host.numel() % REDUCE_ROW_BYTES == 0 and rows_host.numel() >= REDUCE_ROW_BYTES):
+        raise ValueError("rows_host must be a contiguous 1-D uint8 CPU tensor of T * %d bytes (ssd_reduce_row rows)" % REDUCE_ROW_BYTES)
+    return rows_host.numel() // REDUCE_ROW_BYTES
+
+
+def train_bucket_floats(rows_host):
+    """ssd_train_bucket_floats of the table's host copy: the floats of one rank's slice (0: a table the calls would refuse)."""
+    T = _reduce_rows_host(rows_host)
+    return int(lib().ssd_train_bucket_floats(rows_host.data_ptr(), T))
+
+
+def train_grad_pack(rows_host, rows_dev, header, slice_):
+    """ssd_train_grad_pack: rows_host (CPU uint8, T * 32 bytes) is checked, rows_dev (the same bytes on the GPU, the caller's upload,
+    ordered before this call on the current stream) is what the kernel reads; header float32 [3] (matches, localization loss,
+    classification loss) on the GPU; slice_ float32 [16 + P] receives every float of this rank's slice."""
+    T = _reduce_rows_host(rows_host)
+    _dense(rows_dev, "rows_dev", (T * REDUCE_ROW_BYTES,), torch.uint8)
+    _dense(header, "header", (3,))
+    _dense(slice_, "slice_", (None,))
+    dev = _one_gpu(None, rows_dev=rows_dev, header=header, slice_=slice_)
+    with torch.cuda.device(dev):
+        check(lib().ssd_train_grad_pack(rows_host.data_ptr(), rows_dev.data_ptr(), T, header.data_ptr(), slice_.data_ptr(), slice_.numel(),
+                                        stream(dev)))
+
+
+def train_grad_reduce(rows_host, rows_dev, gathered, losses_out, weights_out):
+    """ssd_train_grad_reduce: gathered float32 [G, 16 + P] (every rank's slice, rank order) is summed in ascending rank order into
+    the rows' tensors; losses_out float32 [2] receives the two losses over the global batch, weights_out float32 [G] the c_r."""
+    T = _reduce_rows_host(rows_host)
+    _dense(rows_dev, "rows_dev", (T * REDUCE_ROW_BYTES,), torch.uint8)
+    G = _dense(gathered, "gathered", (None, None))[0]
+    _dense(losses_out, "losses_out", (2,))
+    _dense(weights_out, "weights_out", (G,))
+    dev = _one_gpu(None, rows_dev=rows_dev, gathered=gathered, losses_out=losses_out, weights_out=weights_out)
+    with torch.cuda.device(dev):
+        check(lib().ssd_train_grad_reduce(rows_host.data_ptr(), rows_dev.data_ptr(), T, gathered.data_ptr(), G, gathered.shape[1],
+                                          losses_out.data_ptr(), weights_out.data_ptr(), stream(dev)))

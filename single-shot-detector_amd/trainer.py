@@ -9,8 +9,9 @@ reports total_loss with the regularisation term from the GPU's per-tensor sums, 
 (NanTensorHook), writes checkpoints and logs on a schedule and evaluates the moving averages (RestoreMovingAverageHook).
 
 TensorBoard's event files (summaries.py: the scalars and a histogram of every variable and gradient, model.py:88-90, 113, 121-123)
-are written every save_summary_steps steps, off by default in the API.  One GPU, no graph capture of a step, no gradient clipping,
-exact fp32 only.  The host
+are written every save_summary_steps steps, off by default in the API.  No graph capture of a step, no gradient clipping,
+exact fp32 only.  With `group` the ranks of a process group train in lockstep, one GPU each
+(grad_exchange.py).  The host
 logic that needs no GPU -- schedules, seeds, the warm start, pruning, the stop decision -- is the module-level functions below.
 """
 import json
@@ -33,6 +34,7 @@ SAVE_SUMMARY_STEPS = 600                # train.py:39 (the command's default; th
 SUMMARY_SCALARS = (("loss", "loss"), ("regularization_loss", "regularization_loss"), ("localization_loss", "localization_loss"),
                    ("classification_loss", "classification_loss"), ("learning_rate/learning_rate", "learning_rate"))
 BACKBONE_SCOPES = {"mobilenet": "MobilenetV1/", "shufflenet": "ShuffleNetV2/"}     # train.py:44-47
+GROUP_TIME_CHECK_STEPS = 100            # with a group, a schedule in seconds is examined at these steps only, by rank 0's clock
 RING = 4                                # read-back slots: step k - 1 is examined after step k was enqueued
 
 
@@ -204,13 +206,23 @@ def _append_jsonl(path, record):
 
 # ----------------------------------------------------------------------------- the Trainer
 class Trainer:
-    """tf.estimator.Estimator(model_fn, params, config, warm_start_from) + train_and_evaluate of train.py on one GPU.
+    """tf.estimator.Estimator(model_fn, params, config, warm_start_from) + train_and_evaluate of train.py on one GPU, or with `group`
+    on one GPU per rank.
 
     config          the reference's JSON (path or dict): every key group of config.py is read from it
     model_dir       overrides the config's
     device          the HIP device index
     seed            the run's seed: the initial FPN and heads, and (with global_step at the start) the input pipeline
     read_workers, decode    TrainPipeline's (and evaluation.evaluate's)
+    group           None: one process, one GPU | a torch.distributed process group: data-parallel training over its G ranks, one
+                    process per GPU, every rank built with the same config, model_dir and seed.  The config's batch_size is PER
+                    RANK: a step sees G x batch_size images, and initial_learning_rate is used as given (scaling it with G is the
+                    user's decision).  The pipeline keeps shards[rank::G]; after backward() ONE all-gather exchanges the gradients,
+                    the moving statistics and the loss terms (GradientExchange): the loss is the reference's over the global batch
+                    (normalised by the matches of all ranks), batch statistics stay per replica and the moving statistics are
+                    averaged.  Norms, histograms, the non-finite stop and the update see the reduced values, which are the same
+                    bits on every rank; only rank 0 writes checkpoints, logs and event files (the matches summaries are rank
+                    0's), and a barrier follows every save.  A group of one rank equals group=None bit for bit.
 
     Start state: a checkpoint in model_dir resumes the run (variables, statistics, averages, slots, global_step: TrainStep.restore);
     otherwise the backbone comes from pretrained_checkpoint (warm_start_weights) and fpn/* and the heads are drawn from `seed`.
@@ -221,7 +233,7 @@ class Trainer:
 
     log_every = 100
 
-    def __init__(self, config, model_dir=None, device=0, seed=0, read_workers=None, decode=None):
+    def __init__(self, config, model_dir=None, device=0, seed=0, read_workers=None, decode=None, group=None):
         import torch
         from .backbone_train import TrainableMobileNet
         from .fpn_train import TrainableFPN
@@ -243,6 +255,11 @@ class Trainer:
         self.device = torch.device("cuda", int(device))
         self.seed = int(seed)
         self.read_workers, self.decode = read_workers, decode
+        self.group = group
+        self.rank, self.world = 0, 1
+        if group is not None:
+            import torch.distributed as dist
+            self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
         os.makedirs(self.model_dir, exist_ok=True)
         resumed = resolve_checkpoint(self.model_dir)
         if resumed is not None:
@@ -260,6 +277,10 @@ class Trainer:
             self.train_step = TrainStep(self.variables, self.config, statistics, layout="tf", params=self.params, frozen={})
             if resumed is not None:
                 self.train_step.restore(resumed)
+            self._exchange = None
+            if group is not None:
+                from .grad_exchange import GradientExchange
+                self._exchange = GradientExchange(self.train_step, statistics, group)
             gen = AnchorGenerator()
             hw = (self.train_config["image_height"], self.train_config["image_width"])
             self.anchors = torch.from_numpy(gen(*hw)).to(self.device)
@@ -293,8 +314,9 @@ class Trainer:
     def _pipeline(self):
         if self._pipe is None:
             from .augment import TrainPipeline
+            shard = None if self.group is None else (self.rank, self.world)
             self._pipe = TrainPipeline(self.run_config["train_dataset"], self.train_config, pipeline_seed(self.seed, self.global_step),
-                                       decode=self.decode, read_workers=self.read_workers, device=self.device.index)
+                                       decode=self.decode, read_workers=self.read_workers, device=self.device.index, shard=shard)
         return self._pipe
 
     def step(self):
@@ -309,17 +331,22 @@ class Trainer:
                 p.grad = None
             eb, cp = self.head(self.fpn(self.backbone(images)))
             want_summary = summary_due(self.global_step + 1, self._last_summary, self.save_summary_steps)
-            if want_summary:                            # the loss with its per-image rows: the matches per level (ssd.py:154-163)
+            if want_summary or self._exchange is not None:      # the loss with its per-image rows: the matches per level (ssd.py:154-163)
                 out = differentiable_loss(cp, eb, self.anchors, gt, self.loss_config, anchors_per_level=self.anchors_per_level,
                                           per_image=True)
             else:
                 out = differentiable_loss(cp, eb, self.anchors, gt, self.loss_config)
             loc, cls = out["localization_loss"], out["classification_loss"]
             (self.loc_weight * loc + self.cls_weight * cls).backward()
+            if self._exchange is not None:
+                # this rank's matches and its two losses, on the device; what comes back is over the global batch, on every rank alike
+                header = torch.stack([out["per_image"][:, 2].sum(), loc.detach(), cls.detach()])
+                loc, cls, _weights = self._exchange.exchange(header)
             sums, bad = self.train_step.norms()         # before the update: of the variables this step computed with
             hist = None
             if want_summary:
-                hist = self.train_step.histograms()     # beside the norms, of the same variables and gradients
+                if self.rank == 0:
+                    hist = self.train_step.histograms()     # beside the norms, of the same variables and gradients
                 self._last_summary = self.global_step + 1
             t = self.train_step.step()
             slot = self._ring[t % RING]
@@ -359,12 +386,13 @@ class Trainer:
             raise FloatingPointError(msg)
         reg = self.train_step.regularization_loss(sums)
         now = time.monotonic()
-        images = (step - self._last_log[0]) * self.train_config["batch_size"]
+        images = (step - self._last_log[0]) * self.train_config["batch_size"] * self.world
         rate = images / max(now - self._last_log[1], 1e-9)
         self.last = log_record(step, loc, cls, reg, sums, self.loss_config, self.train_step.learning_rate(step - 1), rate,
                                self._pipe.wait_seconds if self._pipe is not None else 0.0)
         if self.log_every and step % self.log_every == 0:
-            _append_jsonl(os.path.join(self.model_dir, "train_log.jsonl"), self.last)
+            if self.rank == 0:
+                _append_jsonl(os.path.join(self.model_dir, "train_log.jsonl"), self.last)
             self._last_log = (step, now)
         if slot.get("hist") is not None:
             try:
@@ -411,11 +439,23 @@ class Trainer:
         if self._failed:
             raise RuntimeError("this run stopped on a non-finite value")
         self.drain()
-        prefix = self.train_step.save(self.model_dir)
-        prune_checkpoints(self.model_dir, KEEP_CHECKPOINT_MAX)
+        if self.group is not None:
+            prefix = self._save_in_group()
+        else:
+            prefix = self.train_step.save(self.model_dir)
+            prune_checkpoints(self.model_dir, KEEP_CHECKPOINT_MAX)
         self._saved_step = self.global_step
         self._last_save = (self.global_step, time.monotonic())
         return prefix
+
+    def _save_in_group(self):
+        """save()'s write with a group: rank 0 writes and prunes, a barrier follows, every rank returns the prefix."""
+        import torch.distributed as dist
+        if self.rank == 0:
+            self.train_step.save(self.model_dir)
+            prune_checkpoints(self.model_dir, KEEP_CHECKPOINT_MAX)
+        dist.barrier(group=self.group)
+        return os.path.join(self.model_dir, "model.ckpt-%d" % self.global_step)
 
     def evaluate(self):
         """estimator.evaluate with RestoreMovingAverageHook: the moving averages of the current step's checkpoint over val_dataset;
@@ -427,15 +467,33 @@ class Trainer:
         self.drain()
         det = Detector(self.model_dir, visible_device_list=str(self.device.index), config=self.config, use_ema=True)
         try:
-            res = evaluate(det, self.run_config["val_dataset"], self.config, read_workers=self.read_workers, decode=self.decode)
+            res = evaluate(det, self.run_config["val_dataset"], self.config, read_workers=self.read_workers, decode=self.decode,
+                           group=self.group)
         finally:
             det.close()
         res = dict(res, step=int(self.global_step))
+        if self.rank != 0:
+            return res
         _append_jsonl(os.path.join(self.model_dir, "eval_log.jsonl"), res)
         if self.save_summary_steps:
             scalars = {k: v for k, v in res.items() if k != "step" and isinstance(v, (int, float)) and not isinstance(v, bool)}
             self._writer(os.path.join(self.model_dir, "eval")).add_summary(int(self.global_step), scalars)
         return res
+
+    def _due(self, step, last_step, last_time, every_steps, every_secs):
+        """due() now, decided alike on every rank of the group: a schedule in steps needs no exchange; one in seconds is rank 0's
+        decision, taken every GROUP_TIME_CHECK_STEPS steps and sent to the others (a save or an evaluation is a collective:
+        ranks whose clocks disagree would wait for each other for ever)."""
+        mine = due(step, time.monotonic(), last_step, last_time, every_steps, every_secs)
+        if self.group is None or every_steps is not None:
+            return mine
+        if every_secs is None or step % GROUP_TIME_CHECK_STEPS:
+            return False
+        import torch
+        import torch.distributed as dist
+        from .distributed import _all_gather_ints
+        small = self.device if dist.get_backend(self.group) == "nccl" else torch.device("cpu")
+        return bool(_all_gather_ints([int(mine)], self.group, small)[0, 0])
 
     def train(self, max_steps=None, save_checkpoints_steps=None, save_checkpoints_secs=SAVE_CHECKPOINTS_SECS, log_every=100, on_step=None,
               save_summary_steps=0):
@@ -450,8 +508,8 @@ class Trainer:
         try:
             while self.global_step < max_steps:
                 t = self.step()
-                if due(t, time.monotonic(), self._last_save[0], self._last_save[1], save_checkpoints_steps,
-                       None if save_checkpoints_steps is not None else save_checkpoints_secs):
+                if self._due(t, self._last_save[0], self._last_save[1], save_checkpoints_steps,
+                             None if save_checkpoints_steps is not None else save_checkpoints_secs):
                     self.save()
                 if on_step is not None and on_step(t):
                     break
@@ -474,8 +532,8 @@ class Trainer:
         last = [self.global_step, time.monotonic()]
 
         def on_step(t):
-            if t < max_steps and due(t, time.monotonic(), last[0], last[1], eval_every_steps,
-                                     None if eval_every_steps is not None else eval_every_secs):
+            if t < max_steps and self._due(t, last[0], last[1], eval_every_steps,
+                                           None if eval_every_steps is not None else eval_every_secs):
                 results.append(self.evaluate())
                 if on_eval is not None:
                     on_eval(results[-1])
