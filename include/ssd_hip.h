@@ -1052,6 +1052,72 @@ int ssd_sn_split_train(const float *g_dev, int64_t rows, int32_t D, float *dx_de
 int ssd_sn_maxpool_train_backward(const float *x_dev, const float *dy_dev, int32_t B, int32_t H, int32_t W, int32_t C, float *dx_dev,
                                   void *stream);
 
+/* ---- the COCO box matching: CocoBoxEval.evaluate() of coco_metric.py for every cell of a run in one launch ----
+ *
+ * The reference scores val2017 with pycocotools' COCOeval (inference/evaluate_on_COCO.ipynb cell 17); coco_metric.py restates it,
+ * and its evaluate() -- computeIoU + evaluateImg per (category, area range, image) -- is what this call computes, bit for bit.
+ * These semantics are coco_metric.py's, read off its code; this block is their single statement for the kernel, for
+ * tests/helpers/coco_match_ref.py and for the Python that packs and unpacks (coco_match.py).
+ *
+ * A cell is one (category, image) pair with at least one detection or groundtruth box.  The packed arrays hold the cells' rows
+ * back to back; cell c owns detections [det_begin, det_begin + D) and groundtruth boxes [gt_begin, gt_begin + G).
+ *   detections    arrive ordered and truncated: descending score, ties in input order (np.argsort(-scores, kind="mergesort")), the
+ *                 first SSD_COCO_MAX_DET.  Each carries its xywh box (four float64) and its area (float64, float(bbox[2] * bbox[3])
+ *                 as the constructor forms it: passed in, not recomputed).  Scores stay on the host.
+ *   groundtruth   arrives in annotation order: an xywh box (float64), an area (float64) and a crowd byte (non-zero: crowd).
+ * IoU(d, g): float64, one IEEE operation at a time, no contraction:
+ *   w = min(dx + dw, gx + gw) - max(dx, gx),  h = min(dy + dh, gy + gh) - max(dy, gy)
+ *   !(w > 0 && h > 0):  iou = +0.0
+ *   else  inter = w * h,  da = dw * dh,  ga = gw * gh,  union = crowd ? da : (da + ga) - inter,  iou = inter / union
+ *   (bbox_iou of coco_metric.py, bit for bit: the division is correctly rounded).
+ * Area range a with bounds (lo, hi) = area_rng_host[a]:
+ *   ig[g] = crowd[g] || area[g] < lo || area[g] > hi
+ *   the scan order of the groundtruth boxes: all !ig boxes in annotation order, then all ig boxes in annotation order (the stable
+ *   sort by the flag); gt_ignore of the cell is the flags in that order.
+ * Threshold t: thr_host[t], the caller's float64 values (coco_metric.THR_L), never recomputed.
+ * The scan of (a, t), for the detections d in order:
+ *   best = thr, m = none
+ *   for g in scan order:
+ *     skip g if it is taken and not crowd
+ *     stop if m is set, !ig[m] and ig[g]
+ *     skip g if iou(d, g) < best
+ *     best = iou(d, g), m = g                 (an equal IoU moves the match to the later box)
+ *   if m is set: matched[t, d] = 1, ignored[t, d] = ig[m], m becomes taken
+ *   afterwards: ignored[t, d] |= !matched[t, d] && (darea[d] < lo || darea[d] > hi)
+ * A cell without groundtruth gives matched = 0 and ignored = out of range; a cell without detections gives only gt_ignore.
+ * All inputs are finite (the caller checks; the call cannot, they are device memory).
+ *
+ * Outputs: matched_dev / ignored_dev uint16 [A, nd], bit t of element [a, det_begin + d] = matched / ignored [t, d] of the cell at
+ * area range a (bits from T on are 0); gt_ignore_dev uint8 [A, ng], 0 / 1, the cell's flags in SCAN order at [a, gt_begin ..];
+ * iou_dev (nullable; a test aid) float64, cell after cell the [D, G] matrix in ANNOTATION order: cell c's block starts at the sum
+ * of D * G over the cells before it.  Every element that belongs to a cell is written; rows of no cell are left alone.
+ *
+ * The call only enqueues one kernel on `stream` (256 lanes, one wave per cell, SSD_COCO_CELLS_PER_BLOCK cells per block, a grid
+ * of at most SSD_COCO_GRID_CAP blocks striding over the cells): no allocation, no synchronisation, no atomics, no handle; two calls
+ * give the same bits.  cells_host is read by the call to refuse bad cells, cells_dev holds the same rows in device memory (8-byte
+ * aligned), which the kernel reads -- the caller's upload, ordered before the call on `stream`.  n_cells == 0 enqueues nothing.
+ * SSD_ERR_INVALID before any HIP call, the reason naming the argument: a NULL thr_host / area_rng_host; NULL cells with n_cells > 0;
+ * a NULL array whose count (nd or ng) is positive; a pointer not aligned to its element; n_cells, nd or ng outside [0, 2^40]; T outside
+ * [1, SSD_COCO_MAX_THR]; A outside [1, SSD_COCO_MAX_AREA]; T * A > 64; a cell with D outside [0, SSD_COCO_MAX_DET] or G outside
+ * [0, SSD_COCO_MAX_GT]; detection or groundtruth ranges that are not ascending and disjoint, or that run past nd / ng. */
+#define SSD_COCO_MAX_DET 100                 /* MAX_DETS[-1] of coco_metric.py                                  */
+#define SSD_COCO_MAX_GT 256                  /* groundtruth boxes of one cell; larger cells stay on the host   */
+#define SSD_COCO_MAX_THR 16
+#define SSD_COCO_MAX_AREA 4
+#define SSD_COCO_CELLS_PER_BLOCK 4
+#define SSD_COCO_GRID_CAP 1024               /* blocks; the rest of the cell list is grid-strided               */
+typedef struct ssd_coco_cell {               /* 24 bytes, no padding */
+    int64_t det_begin, gt_begin;             /* first row of the cell in the detection / groundtruth arrays    */
+    int32_t D, G;                            /* detections, groundtruth boxes                                  */
+} ssd_coco_cell;
+int ssd_coco_match(const ssd_coco_cell *cells_host, const ssd_coco_cell *cells_dev, int64_t n_cells,
+                   const double *det_box_dev /* [nd,4] */, const double *det_area_dev /* [nd] */, int64_t nd,
+                   const double *gt_box_dev /* [ng,4] */, const double *gt_area_dev, const uint8_t *gt_crowd_dev, int64_t ng,
+                   const double *thr_host /* [T] */, int32_t T, const double *area_rng_host /* [A,2] */, int32_t A,
+                   uint16_t *matched_dev /* [A,nd], bit t */, uint16_t *ignored_dev /* [A,nd] */,
+                   uint8_t *gt_ignore_dev /* [A,ng], scan order */, double *iou_dev /* nullable: cell-major [D,G], annotation order */,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

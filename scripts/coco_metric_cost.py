@@ -1,0 +1,102 @@
+"""What the COCO metric costs on the host and with the matching on the GPU, in ONE process on ONE synthetic
+val2017-sized result set:
+
+    python scripts/coco_metric_cost.py [--images 5000] [--rounds 3]
+
+  the set      `--images` images, 80 categories, 1 to 14 annotations per image (about 7) in 1 to 3 of the categories, 3 % of them
+               crowd; per annotation 0 to 3 detections that are near-duplicates of its box (normal jitter, sigma 6 pixels) and per
+               image 5 to 24 stray detections of any category: about 25 detections per image.
+  the timings  the constructor; CocoBoxEval.evaluate() on the host; evaluate(device=0) end to end and split into pack, upload,
+               launch (HIP events), download and unpack; accumulate().  `--rounds` rounds, host and GPU alternating, the median.
+  the check    the two evaluations' cells() are equal in all seven arrays, key order included; so are the twelve statistics.
+There is no speed gate: the log says what each part costs, whichever way it comes out."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np                                                # noqa: E402
+import torch                                                      # noqa: E402
+import ssd_amd                                                    # noqa: E402
+from ssd_amd import coco_metric                                   # noqa: E402
+
+K = 80
+
+
+def result_set(n_images, seed=0):
+    rng = np.random.default_rng(seed)
+    images = [{"id": i + 1} for i in range(n_images)]
+    cats = [{"id": k + 1} for k in range(K)]
+    anns, dets = [], []
+    for im in images:
+        present = rng.choice(K, size=rng.integers(1, 4), replace=False) + 1
+        for _ in range(rng.integers(1, 15)):
+            w, h = rng.uniform(8, 300, 2)
+            x, y = rng.uniform(0, 340, 2)
+            c = int(rng.choice(present))
+            anns.append({"image_id": im["id"], "category_id": c, "bbox": [float(x), float(y), float(w), float(h)], "area": float(w * h * 0.7),
+                         "iscrowd": int(rng.random() < 0.03)})
+            for _ in range(rng.integers(0, 4)):
+                j = rng.normal(0, 6, 4)
+                dets.append({"image_id": im["id"], "category_id": c, "score": float(np.float32(rng.uniform(0.15, 1))),
+                             "bbox": [int(x + j[0]), int(y + j[1]), max(1, int(w + j[2])), max(1, int(h + j[3]))]})
+        for _ in range(rng.integers(5, 25)):
+            w, h = rng.uniform(8, 300, 2)
+            x, y = rng.uniform(0, 340, 2)
+            dets.append({"image_id": im["id"], "category_id": int(rng.integers(1, K + 1)), "bbox": [int(x), int(y), int(w), int(h)],
+                         "score": float(np.float32(rng.uniform(0.15, 0.6)))})
+    return {"images": images, "annotations": anns, "categories": cats}, dets
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=5000)
+    ap.add_argument("--rounds", type=int, default=3)
+    args = ap.parse_args()
+    print("device: %s" % torch.cuda.get_device_name(0))
+    gt, dets = result_set(args.images)
+    t0 = time.perf_counter()
+    ev = coco_metric.CocoBoxEval(gt, dets)
+    t_init = time.perf_counter() - t0
+    coco_metric.CocoBoxEval(gt, dets[:100]).evaluate(device=0)            # loads the library, creates the context
+    host_s, gpu_s, parts = [], [], []
+    for _ in range(args.rounds):
+        t0 = time.perf_counter()
+        ev.evaluate()
+        host_s.append(time.perf_counter() - t0)
+        host_cells = ev.cells()
+        ev.eval_imgs = {}
+        timings = {}
+        t0 = time.perf_counter()
+        ev._evaluate_on_gpu(ev.img_ids, 0, timings=timings)
+        gpu_s.append(time.perf_counter() - t0)
+        parts.append(timings)
+        gpu_cells = ev.cells()
+        for k in ("keys", "D", "G", "scores", "matched", "ignored", "gt_ignore"):
+            assert gpu_cells[k].dtype == host_cells[k].dtype and np.array_equal(gpu_cells[k], host_cells[k]), k
+    t0 = time.perf_counter()
+    ev.accumulate()
+    t_acc = time.perf_counter() - t0
+    stats_gpu = ev.summarize()
+    stats_host = coco_metric.CocoBoxEval(gt, dets).evaluate().accumulate().summarize()
+    assert all(float(a) == float(b) for a, b in zip(stats_gpu, stats_host))
+    c = host_cells
+    n_cells = len(c["D"]) // len(coco_metric.AREA_RNG)
+    print("images %d, categories %d, annotations %d, detections %d, cells %d, kept detections %d, max D %d, max G %d"
+          % (args.images, K, len(gt["annotations"]), len(dets), n_cells, c["D"].sum() // len(coco_metric.AREA_RNG), c["D"].max(), c["G"].max()))
+    print("the two cells() are equal in all seven arrays and the twelve statistics are equal (%d rounds); AP %.4f" % (args.rounds, stats_gpu[0]))
+    med = lambda xs: float(np.median(xs))
+    print("%-34s %8.3f s" % ("constructor", t_init))
+    print("%-34s %8.3f s   (rounds: %s)" % ("evaluate(), host loop", med(host_s), " ".join("%.3f" % x for x in host_s)))
+    print("%-34s %8.3f s   (rounds: %s)" % ("evaluate(device=0), end to end", med(gpu_s), " ".join("%.3f" % x for x in gpu_s)))
+    for k in ("pack", "upload", "launch", "download", "unpack"):
+        print("    %-30s %8.4f s" % (k + (" (HIP events)" if k == "launch" else ""), med([p[k] for p in parts])))
+    print("%-34s %8.3f s" % ("accumulate()", t_acc))
+    print("evaluate: host / GPU path = %.2fx; after it the metric is constructor %.2f s + evaluate %.2f s + accumulate %.2f s"
+          % (med(host_s) / med(gpu_s), t_init, med(gpu_s), t_acc))
+
+
+if __name__ == "__main__":
+    main()

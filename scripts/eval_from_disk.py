@@ -1,6 +1,7 @@
 """The COCO harness end to end from files on disk (coco_eval.evaluate: JPEGs decoded by a thread pool one chunk ahead, frames
 batched by network shape, records, COCO statistics) on a synthetic val2017-like folder: `n` JPEGs of the 13 COCO-typical sizes.
-usage: python scripts/eval_from_disk.py [n_images]
+usage: python scripts/eval_from_disk.py [n_images] [--gpu-metric]
+--gpu-metric: the per-cell matching of the COCO metric as one launch on the detector's GPU (coco_eval.evaluate(metric_device=)).
 Under `python -m torch.distributed.run --nproc-per-node N scripts/eval_from_disk.py [n_images]` the images shard over the N
 ranks (evaluate(..., group); every rank writes the same folder for itself); rank 0 prints."""
 import os, sys, time, tempfile, json
@@ -8,7 +9,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch, ssd_amd, bench
 from PIL import Image
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 1040
+gpu_metric = "--gpu-metric" in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a != "--gpu-metric"]
+n = int(argv[0]) if argv else 1040
 P = bench.PARAMS
 group, device, rank = None, 0, 0
 if "WORLD_SIZE" in os.environ:
@@ -39,11 +42,12 @@ rank == 0 and print("%d JPEGs, %.1f MB (%.0f KB each) written in %.1f s" % (n, s
 t0 = time.perf_counter(); [np.asarray(Image.open(os.path.join(d, m["file_name"])).convert("RGB")) for m in images[:100]]; dec = (time.perf_counter() - t0) / 100
 rank == 0 and print("decode on one thread: %.2f ms per image" % (dec * 1e3), flush=True)
 ssd_amd.coco_eval.evaluate(det, gt, d, predictions_json=None, group=group)            # builds the plans
+metric_device = device if gpu_metric else None
 for workers in (1, 4, None):
     t0 = time.perf_counter()
-    st = ssd_amd.coco_eval.evaluate(det, gt, d, predictions_json=os.path.join(d, "pred.json"), read_workers=workers, group=group)
+    st = ssd_amd.coco_eval.evaluate(det, gt, d, predictions_json=os.path.join(d, "pred.json"), read_workers=workers, group=group, metric_device=metric_device)
     dt = time.perf_counter() - t0
-    rank == 0 and print("world %d, " % (1 if group is None else dist.get_world_size()) + "evaluate, read_workers=%s: %.2f s = %.0f img/s end to end (files -> COCO statistics); AP %.3f" % (workers, dt, n / dt, st[0]), flush=True)
+    rank == 0 and print("world %d, " % (1 if group is None else dist.get_world_size()) + "evaluate, %s metric, read_workers=%s: %.2f s = %.0f img/s end to end (files -> COCO statistics); AP %.3f" % ("GPU" if gpu_metric else "host", workers, dt, n / dt, st[0]), flush=True)
 rank == 0 and print(det.engine.plan_cache_stats())
 if group is not None:
     dist.destroy_process_group()

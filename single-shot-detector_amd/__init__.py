@@ -19,7 +19,7 @@ from .ssd import (SSD, AnchorGenerator, RetinaNetFeatureExtractor, RetinaNetBoxP
                   batch_multiclass_non_max_suppression, network_input_size, Engine,
                   get_training_targets, ssd_loss, ssd_loss_backward, differentiable_loss)
 from .detector import Detector                                         # noqa: F401
-from . import coco_eval, coco_metric, tfrecords                        # noqa: F401  (evaluation: `python -m ssd_amd.evaluation`, imported on use)
+from . import coco_eval, coco_metric, coco_match, tfrecords            # noqa: F401  (evaluation: `python -m ssd_amd.evaluation`, imported on use)
 from .distributed import shard_range, all_gather_detections, detect_sharded, bind_to_gpu_numa_node  # noqa: F401
 from .distributed import (ChunkAssignment, detect_many_sharded, node_device_and_backend, init_node_process_group,  # noqa: F401
                           launch_local)

@@ -61,7 +61,7 @@ def detection_records_many(detector, images, image_ids, label_to_coco_id, score_
 
 
 def evaluate(detector, annotations_json, images_dir, read_image=None, predictions_json="coco_predictions.json", out=None,
-             score_threshold=0.15, max_batch=32, read_workers=None, group=None, chunk=256):
+             score_threshold=0.15, max_batch=32, read_workers=None, group=None, chunk=256, metric_device=None):
     """Cells 4-17 end to end: every image of the annotation file through the detector (score_threshold 0.15, cell 10), the
     results written as `predictions_json` (cell 11), then the twelve COCO box statistics (cell 17: COCOeval over all image and
     category ids) -- computed by coco_metric.py, this build's restatement of pycocotools' COCOeval (not installed here, not
@@ -76,7 +76,10 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     sorted by id, go to the ranks in round-robin chunks of `chunk` (distributed.ChunkAssignment); each rank reads, decodes and
     detects only its own, builds their result rows and runs the per-(image, category, area) matching for them
     (CocoBoxEval.evaluate(img_ids)); one all-gather of compact arrays (the matching cells, the rows' JSON bytes) follows.  Rank
-    0 writes `predictions_json` (byte for byte the one-process file) and the table; every rank returns the same statistics."""
+    0 writes `predictions_json` (byte for byte the one-process file) and the table; every rank returns the same statistics.
+
+    `metric_device`: None runs that matching as coco_metric's host loop; a CUDA device index or torch.device runs it as one launch
+    on that GPU (CocoBoxEval.evaluate(device=)): the same cells bit for bit, so everything behind it is unchanged."""
     import os
     from . import coco_metric
     from .distributed import ChunkAssignment
@@ -103,7 +106,7 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
         if predictions_json:
             frags.append(json.dumps(rows)[1:-1].encode())      # json.dump of the whole list joins these with ", "
     ev = coco_metric.CocoBoxEval(gt, results)
-    ev.evaluate(img_ids=[m["id"] for m in mine])
+    ev.evaluate(img_ids=[m["id"] for m in mine], device=metric_device)
     if group is not None:
         # one all-gather of every rank's matching cells and its chunks' JSON; the chunks go back in input order (chunk c of the
         # sorted images is rank c % world's: a round-robin split in chunks of one)

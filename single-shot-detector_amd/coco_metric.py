@@ -76,11 +76,13 @@ class CocoBoxEval:
         self.precision = self.recall = self.stats = None
 
     # -- cocoeval.py evaluate(): computeIoU + evaluateImg for every (category, area range, image)
-    def evaluate(self, img_ids=None):
+    def evaluate(self, img_ids=None, device=None):
         """img_ids: evaluate only these images (a subset of self.img_ids, e.g. one rank's share); the cells of the others come
-        from `merge`.  accumulate() / summarize() always run over all self.img_ids."""
-        T = len(IOU_THRS)
-        maxdet = MAX_DETS[-1]
+        from `merge`.  accumulate() / summarize() always run over all self.img_ids.
+        device: None runs the host loop; a CUDA device index or torch.device runs the matching of all cells as one launch of
+        ssd_coco_match (coco_match.py; include/ssd_hip.h "the COCO box matching") on that GPU's current stream -- the same
+        eval_imgs, key for key and bit for bit.  A cell with more groundtruth boxes than the kernel takes is computed by the
+        host loop in its place."""
         self.eval_imgs = {}
         if img_ids is None:
             subset = self.img_ids
@@ -89,59 +91,97 @@ class CocoBoxEval:
             if not want <= set(self.img_ids):
                 raise ValueError("img_ids must be a subset of the evaluated image ids")
             subset = [i for i in self.img_ids if i in want]
+        if device is not None:
+            return self._evaluate_on_gpu(subset, device)
         for cat in self.cat_ids:
             for img in subset:
                 gts = self._gts.get((img, cat), [])
                 dts = self._dts.get((img, cat), [])
                 if not gts and not dts:
                     continue
-                scores = np.array([d[2] for d in dts], np.float64)
-                order = np.argsort(-scores, kind="mergesort")[:maxdet]
-                dbox = [dts[i][0] for i in order]
-                darea = np.array([dts[i][1] for i in order], np.float64)
-                dscore = scores[order]
-                gcrowd = np.array([g[2] for g in gts], np.int64)
-                garea = np.array([g[1] for g in gts], np.float64)
-                ious_all = bbox_iou(dbox, [g[0] for g in gts], gcrowd) if gts and dts else np.zeros((len(dbox), len(gts)))
-                for ai, (lo, hi) in enumerate(AREA_RNG):
-                    if not gts:            # (most cells of a real run: detections of a category the image does not have)
-                        oor = (darea < lo) | (darea > hi)
-                        self.eval_imgs[(cat, ai, img)] = (dscore, np.zeros((T, len(dbox)), bool), np.broadcast_to(oor, (T, len(dbox))), np.zeros(0, bool))
-                        continue
-                    gig = (gcrowd != 0) | (garea < lo) | (garea > hi)
-                    gind = np.argsort(gig.astype(np.int64), kind="mergesort")
-                    gig_s, crowd_s = gig[gind], gcrowd[gind]
-                    ious = ious_all[:, gind]
-                    D, G = len(dbox), len(gts)
-                    dtm = np.zeros((T, D), bool)
-                    dtig = np.zeros((T, D), bool)
-                    if G and D:
-                        # (plain Python lists inside the loops: indexing numpy scalars costs more than the comparisons)
-                        iou_l, ig_l, cr_l = ious.tolist(), gig_s.tolist(), [bool(c) for c in crowd_s.tolist()]
-                        for ti, t in enumerate(THR_L):
-                            gtm = [False] * G
-                            row_m, row_ig = dtm[ti], dtig[ti]
-                            for di in range(D):
-                                best = t
-                                m = -1
-                                row = iou_l[di]
-                                for gi in range(G):
-                                    if gtm[gi] and not cr_l[gi]:
-                                        continue                       # already matched, and not a crowd
-                                    if m > -1 and not ig_l[m] and ig_l[gi]:
-                                        break                          # a regular match is held: ignore boxes (sorted last) cannot take it
-                                    if row[gi] < best:
-                                        continue
-                                    best = row[gi]
-                                    m = gi
-                                if m == -1:
-                                    continue
-                                row_ig[di] = ig_l[m]
-                                row_m[di] = True
-                                gtm[m] = True
-                    out_of_range = (darea < lo) | (darea > hi)
-                    dtig = dtig | (~dtm & out_of_range[None, :])
-                    self.eval_imgs[(cat, ai, img)] = (dscore, dtm, dtig, gig_s)
+                for ai, cell in enumerate(self._evaluate_cell(gts, dts)):
+                    self.eval_imgs[(cat, ai, img)] = cell
+        return self
+
+    @staticmethod
+    def _evaluate_cell(gts, dts):
+        """One (category, image) cell -> its (scores, matched, ignored, gt_ignore) per area range."""
+        T = len(IOU_THRS)
+        maxdet = MAX_DETS[-1]
+        out = []
+        scores = np.array([d[2] for d in dts], np.float64)
+        order = np.argsort(-scores, kind="mergesort")[:maxdet]
+        dbox = [dts[i][0] for i in order]
+        darea = np.array([dts[i][1] for i in order], np.float64)
+        dscore = scores[order]
+        gcrowd = np.array([g[2] for g in gts], np.int64)
+        garea = np.array([g[1] for g in gts], np.float64)
+        ious_all = bbox_iou(dbox, [g[0] for g in gts], gcrowd) if gts and dts else np.zeros((len(dbox), len(gts)))
+        for ai, (lo, hi) in enumerate(AREA_RNG):
+            if not gts:            # (most cells of a real run: detections of a category the image does not have)
+                oor = (darea < lo) | (darea > hi)
+                out.append((dscore, np.zeros((T, len(dbox)), bool), np.broadcast_to(oor, (T, len(dbox))), np.zeros(0, bool)))
+                continue
+            gig = (gcrowd != 0) | (garea < lo) | (garea > hi)
+            gind = np.argsort(gig.astype(np.int64), kind="mergesort")
+            gig_s, crowd_s = gig[gind], gcrowd[gind]
+            ious = ious_all[:, gind]
+            D, G = len(dbox), len(gts)
+            dtm = np.zeros((T, D), bool)
+            dtig = np.zeros((T, D), bool)
+            if G and D:
+                # (plain Python lists inside the loops: indexing numpy scalars costs more than the comparisons)
+                iou_l, ig_l, cr_l = ious.tolist(), gig_s.tolist(), [bool(c) for c in crowd_s.tolist()]
+                for ti, t in enumerate(THR_L):
+                    gtm = [False] * G
+                    row_m, row_ig = dtm[ti], dtig[ti]
+                    for di in range(D):
+                        best = t
+                        m = -1
+                        row = iou_l[di]
+                        for gi in range(G):
+                            if gtm[gi] and not cr_l[gi]:
+                                continue                       # already matched, and not a crowd
+                            if m > -1 and not ig_l[m] and ig_l[gi]:
+                                break                          # a regular match is held: ignore boxes (sorted last) cannot take it
+                            if row[gi] < best:
+                                continue
+                            best = row[gi]
+                            m = gi
+                        if m == -1:
+                            continue
+                        row_ig[di] = ig_l[m]
+                        row_m[di] = True
+                        gtm[m] = True
+            out_of_range = (darea < lo) | (darea > hi)
+            dtig = dtig | (~dtm & out_of_range[None, :])
+            out.append((dscore, dtm, dtig, gig_s))
+        return out
+
+    def _evaluate_on_gpu(self, subset, device, timings=None):
+        """evaluate()'s cells of `subset` through coco_match: pack, one launch, unpack; eval_imgs in the host loop's order."""
+        import time
+        from . import coco_match
+        t0 = time.perf_counter()
+        p = coco_match.pack(self._gts, self._dts, self.cat_ids, subset)
+        t1 = time.perf_counter()
+        matched, ignored, gt_ignore = coco_match.match(p, THR_L, AREA_RNG, device, timings=timings)
+        t2 = time.perf_counter()
+        cells, score = p["cells"], p["det_score"]
+        d0, dn, g0, gn = cells["det_begin"].tolist(), cells["D"].tolist(), cells["gt_begin"].tolist(), cells["G"].tolist()
+        n = 0
+        for (cat, img), packed in zip(p["keys"], p["packed"].tolist()):
+            if not packed:             # more groundtruth boxes than the kernel takes: the host loop, in its place
+                for ai, cell in enumerate(self._evaluate_cell(self._gts.get((img, cat), []), self._dts.get((img, cat), []))):
+                    self.eval_imgs[(cat, ai, img)] = cell
+                continue
+            a, b, c, d = d0[n], d0[n] + dn[n], g0[n], g0[n] + gn[n]
+            n += 1
+            s = score[a:b]
+            for ai in range(len(AREA_RNG)):
+                self.eval_imgs[(cat, ai, img)] = (s, matched[ai, :, a:b], ignored[ai, :, a:b], gt_ignore[ai, c:d])
+        if timings is not None:
+            timings.update(pack=t1 - t0, unpack=time.perf_counter() - t2)
         return self
 
     # -- the cells of evaluate() as a few flat arrays (a subset's evaluation travels between processes this way)
