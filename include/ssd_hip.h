@@ -1118,6 +1118,65 @@ int ssd_coco_match(const ssd_coco_cell *cells_host, const ssd_coco_cell *cells_d
                    uint8_t *gt_ignore_dev /* [A,ng], scan order */, double *iou_dev /* nullable: cell-major [D,G], annotation order */,
                    void *stream);
 
+/* ---- tiled detection: frames larger than the network's input as overlapping tiles of the network's own size, one merge NMS ----
+ *
+ * A frame far larger than min_dimension is served by `ssd_forward` only after shrinking it.  Tiled detection runs the network on
+ * overlapping tiles at the frame's own resolution (every tile takes the identity path of the first kernel: no resize, box_scaler 1),
+ * optionally on the shrunk whole frame too, and merges all records of a frame with the detector's own NMS rule.  This block is the
+ * single statement of the grid and of the merge for the two kernels (csrc/tiles.hip), for tests/helpers/tile_ref.py and for
+ * Detector.detect_tiled.
+ *
+ * The grid of a frame [H, W] under tiles [th, tw] that overlap by oy rows and ox columns (Python: oy = int(overlap * th),
+ * ox = int(overlap * tw)):
+ *   steps     sy = th - oy,  sx = tw - ox                              (both >= 1)
+ *   counts    ny = 1 + ceil((H - th) / sy),  nx = 1 + ceil((W - tw) / sx)
+ *   origins   y0(iy) = min(iy * sy, H - th),  x0(ix) = min(ix * sx, W - tw)     (the last tile is pulled back inside the frame)
+ *   index     t = (f * ny + iy) * nx + ix   for frame f
+ * Origins strictly increase along an axis, the last one is H - th (W - tw), and every pixel lies in a tile.  ssd_tile_grid writes
+ * {ny, nx, sy, sx}; both kernels derive the origins from these four numbers, there is no table.  1200 x 1600 under 640 x 640 tiles
+ * with oy = ox = 160 gives rows 0, 480, 560 and columns 0, 480, 960; 200 x 301 under 128 x 128 with 32 gives rows 0, 72 and columns
+ * 0, 96, 173.
+ * Refused (SSD_ERR_INVALID, the reason naming the argument, before any HIP call -- by all three entry points): th or tw that is not a
+ * positive multiple of 128; H < th or W < tw (such a frame is ssd_forward's); oy or ox negative; a step below 1; F < 1; a frame
+ * block F * H * W * 3 of 2^31 bytes or more (the gather addresses it with 32-bit offsets); more than 2^31 - 1 tiles.
+ *
+ * ssd_tile_gather: frames_dev uint8 [F, H, W, 3] (any alignment) -> tiles_dev uint8 [F * ny * nx, th, tw, 3], dense, 4-byte
+ * aligned; tile t holds rows y0 .. y0 + th - 1, columns x0 .. x0 + tw - 1 of its frame, bit for bit.  One launch on `stream`: no
+ * allocation, no synchronisation.  The source is read through a buffer resource of exactly F * H * W * 3 bytes from frames_dev:
+ * whole dwords at 4-byte aligned addresses wherever all four bytes lie inside the block, single bytes for the at most two dwords
+ * that straddle its ends, so no byte outside the block is ever fetched; a tile row is 3 * tw bytes (a multiple of 384) and is
+ * stored as whole 16-byte groups.  Further refusals: a NULL frames_dev / tiles_dev, tiles_dev not 4-byte aligned.
+ *
+ * ssd_tile_merge: tile_records_dev int32 [F * ny * nx, 6T + 1] (the records of ssd_forward_records on the tiles, T = C * m with
+ * C = num_classes, m = max_boxes_per_class) and full_records_dev int32 [F, 6T + 1] (the records of the whole frames; NULL: none)
+ * -> out_records_dev int32 [F, 6T + 1], the same layout (boxes [T,4] f32 | scores [T] f32 | labels [T] i32 | num_boxes i32), boxes
+ * normalised to the FRAME.
+ *   candidates   of (frame f, class c): the rows below num_boxes (clamped to [0, T]) whose label is c, taken from f's tiles in
+ *                tile order and then from f's full-frame record, in row order within each source.  The position in this sequence
+ *                is the candidate index.  A label outside [0, C) belongs to no class.  Scores are not NaN.
+ *   a tile row   moves to frame coordinates one fp32 operation at a time, no contraction, the division correctly rounded:
+ *                  Y = ((y * fp32(th)) + fp32(y0)) / fp32(H)  for ymin and ymax,   X = ((x * fp32(tw)) + fp32(x0)) / fp32(W)
+ *                its score passes as it is.  A full-frame row passes bit for bit.
+ *   selection    tf.image.non_max_suppression's rule as the detector applies it (postprocess.hip, iou_greater): the candidates in
+ *                descending score, equal scores by ascending candidate index; a candidate is kept iff iou_greater(candidate, kept,
+ *                iou_threshold) is false for every box kept before it; the selection stops at m boxes.  (The comparison is a
+ *                strict >, and a box of area <= 0 neither suppresses nor is suppressed.)
+ *   output       per frame the classes ascending, within a class the selection order; num_boxes; every row from num_boxes on is
+ *                zero.  All 6T + 1 words of every output record are written.
+ * Two launches on `stream` (one wave per (frame, class) selects into the output record's own rows c * m ..; one block per frame
+ * closes the gaps in place), no allocation, no synchronisation, no atomics: two calls give the same bits.  The candidates of one
+ * (frame, class) live in LDS; records from ssd_forward_records hold at most m rows of a class, so there are at most
+ * (ny * nx + 1) * m, and a call whose (ny * nx + 1) * m exceeds SSD_TILE_MAX_CANDIDATES is refused before any HIP call (records of
+ * another origin with more rows of one class: the candidates past the cap are dropped, never addressed).  Further refusals: NULL
+ * tile_records_dev / out_records_dev, a pointer not 4-byte aligned, C < 1, m < 1, C * m above 2^24, a NaN iou_threshold. */
+#define SSD_TILE_MAX_CANDIDATES 2048         /* 20 bytes of LDS each: 40 KiB per (frame, class) wave                    */
+int ssd_tile_grid(int32_t H, int32_t W, int32_t th, int32_t tw, int32_t oy, int32_t ox, int32_t *grid_out /* ny, nx, sy, sx */);
+int ssd_tile_gather(const uint8_t *frames_dev /* [F,H,W,3] */, int32_t F, int32_t H, int32_t W, int32_t th, int32_t tw, int32_t oy,
+                    int32_t ox, uint8_t *tiles_dev /* [F*ny*nx,th,tw,3] */, void *stream);
+int ssd_tile_merge(const int32_t *tile_records_dev /* [F*ny*nx,6T+1] */, const int32_t *full_records_dev /* [F,6T+1] or NULL */,
+                   int32_t F, int32_t H, int32_t W, int32_t th, int32_t tw, int32_t oy, int32_t ox, int32_t C, int32_t m,
+                   float iou_threshold, int32_t *out_records_dev /* [F,6T+1] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,66 @@ class Detector:
                 consume(pending)
         return out
 
+    def detect_tiled(self, image, tile=None, overlap=0.25, full_frame=True, score_threshold=0.1, max_batch=32):
+        """`__call__` for a frame much LARGER than the network's input (a 1200 x 1600 camera frame at min_dimension 640), where
+        shrinking the frame loses the small objects: the network runs on overlapping tiles of its own size at the frame's own
+        resolution, with full_frame also on the shrunk whole frame (the objects larger than a tile), and all records of a frame
+        are merged by the detector's own per-class NMS (include/ssd_hip.h, block "tiled detection").
+            image: uint8 [H, W, 3] or [F, H, W, 3], a host array or a CUDA tensor.
+            tile: a side or (th, tw), multiples of 128 with min(th, tw) == min_dimension (the network sees a tile as it is);
+                default: min_dimension square.  H >= th and W >= tw -- a smaller frame is `__call__`'s (ValueError).
+            overlap: the fraction of a tile side that neighbouring tiles share.
+        Returns (boxes, labels, scores) like `__call__`, boxes normalised to the frame; a list of them for a batch of frames.
+        One upload, the gather of the tiles on the device, the tiles' forwards in batches of `max_batch` and its halvings
+        (ssd.mixed_batches' rule: one layer plan per batch size), the whole frames' forward, the merge, one download.
+        The whole frames run as ONE batch of F whatever `max_batch` says (a layer plan per distinct F): pass a stream of frames
+        in groups of one size."""
+        from . import tiles as tl
+        torch = _torch()
+        md = int(self.params["min_dimension"])
+        th, tw = (md, md) if tile is None else (tile, tile) if np.isscalar(tile) else tile
+        th, tw = int(th), int(tw)
+        if th % 128 or tw % 128 or min(th, tw) != md:
+            raise ValueError("tile: sides that are multiples of 128 with min(th, tw) == min_dimension (%d)" % md)
+        if not isinstance(image, torch.Tensor):
+            image = np.asarray(image)
+        single = image.ndim == 3
+        dtype_ok = image.dtype == (torch.uint8 if isinstance(image, torch.Tensor) else np.uint8)
+        if not dtype_ok or image.ndim not in (3, 4) or image.shape[-1] != 3:
+            raise ValueError("image must be uint8 of shape [height, width, 3] or [frames, height, width, 3]")
+        F, H, W = (1,) + tuple(image.shape[:2]) if single else tuple(image.shape[:3])
+        if H < th or W < tw:
+            raise ValueError("a %d x %d frame is smaller than the %d x %d tile: use __call__" % (H, W, th, tw))
+        ys, xs = tl.tile_grid(H, W, th, tw, overlap)
+        n = F * len(ys) * len(xs)
+        sizes, b = [], max(1, int(max_batch))
+        while b >= 1:
+            sizes.append(b)
+            b //= 2
+        eng = self.engine
+        dev = "cuda:%d" % self.device
+        with eng.lock:
+            frames = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
+            frames = frames.to(dev).contiguous().view(F, H, W, 3)
+            tiles = tl.tile_gather(frames, th, tw, overlap)
+            rec = eng.new_records(n, dev)
+            rec_full = eng.new_records(F, dev) if full_frame else None
+
+            def run():
+                k = 0
+                for b in sizes:
+                    while n - k >= b:
+                        eng.forward(tiles[k:k + b], records=rec[k:k + b])
+                        k += b
+                if full_frame:
+                    eng.forward(frames, records=rec_full)
+                merged = tl.tile_merge(rec, rec_full, (F, H, W), th, tw, overlap, self.params["num_classes"],
+                                       self.params["max_boxes_per_class"], self.params["iou_threshold"])
+                return merged.cpu().numpy()
+            boxes, labels, scores, num = eng.record_views(self._f32_fallback(run))
+        out = [score_filter(boxes[f], labels[f], scores[f], num[f], score_threshold) for f in range(F)]
+        return out[0] if single else out
+
     def detect_stream(self, batches):
         """Steady-state serving: an iterable of host uint8 batches [B,H,W,3] -> a generator of the graph outputs per
         batch, in order, with the host-to-device and device-to-host copies of neighbouring batches hidden under the
