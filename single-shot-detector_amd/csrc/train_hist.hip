@@ -3,16 +3,15 @@
 // bucket rule and the ORDER of the double additions: include/ssd_hip.h, block "the TRAIN step's histograms".
 //
 //   train_hist_clear    zeroes counts [T][2][NB] (the caller need not).
-//   train_hist_blocks   stage 1, train_norms_blocks' shape: 256 lanes, blocks of SSD_UPDATE_BLOCK_ELEMS virtual elements, a grid of at
-//                       most HST_MAX_GRID blocks strides over the work list, the row by the block-uniform search, lane t owns the
-//                       quads j0 + (k * 256 + t) * 4, 16-byte loads where the addresses are congruent and single elements otherwise,
-//                       INTO the same lane.  Per element: the gradient plane's value g' (one fp32 multiply, one fp32 add), the two
+//   train_hist_blocks   stage 1 over the update's work list (train_table.h: the block shape, the row search, walk_block, whose
+//                       tail path lets every lane visit all 16 positions: hist_add's ballots see the whole wave).
+//                       Per element: the gradient plane's value g' (one fp32 multiply, one fp32 add), the two
 //                       buckets, and per plane sum, sum of squares (double), min, max (as ordered integer keys), num and bad.  The
 //                       bucket is the header's upper_bound: a guess from v_log_f32 corrected against the positive limits in LDS
 //                       until the neighbouring limits bracket |x|, so that it equals the search on every float whatever the
 //                       logarithm's error.  The block keeps a private histogram of both planes in LDS (integer atomics), flushes
 //                       the non-zero buckets of the range it touched with vector global atomics and zeroes them again.  The
-//                       doubles go through train_norms' tree; lane 0 writes the block's 64-byte partial.
+//                       doubles go through tree256; lane 0 writes the block's 64-byte partial.
 //                       Contention: trained weights fall into a few dozen buckets and constant tensors (a fresh gamma, a zero
 //                       gradient) into ONE, so the 64 lanes of an LDS atomic mostly hit a handful of addresses.  Equal buckets of a
 //                       wave are aggregated before the atomic in the cheapest form that removes the worst case: the first valid
@@ -22,34 +21,23 @@
 //                       element), 1 this one, 2 / 3 one / two full rounds (the lanes sharing the first pending lane's bucket are
 //                       counted and added by one lane, the rest goes on), 4 rounds until nothing is pending -- counts are integers,
 //                       every scheme gives the same bits; DESIGN.md 4.18 has what each measured.
-//   train_hist_rows     stage 2: one wave per tensor adds its blocks' partials in ascending block order (train_norms_rows' form).
+//   train_hist_rows     stage 2: one wave per tensor adds its blocks' partials in ascending block order (wave_ordered_add).
 // Integer atomics only; reads w and grad, writes the workspace and the outputs only.
-#include "host.h"
+#include "train_table.h"
 
-#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <vector>
 
 #pragma clang fp contract(off)
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const float gcfloat;
-typedef __attribute__((address_space(1))) const v4f gcv4f;
-
 namespace {
 
-constexpr int HST_THREADS = 256;
-constexpr int HST_QUADS = 4;                                        // 16-byte groups per lane and block
-constexpr int HST_MAX_GRID = 2048;                                  // 256 CUs x 8 blocks: the rest is grid-strided
-constexpr int HST_ROW_THREADS = 64;
 constexpr int HST_MAX_HALF = 800;                                   // LDS room for the positive limits (the loop gives 775)
 constexpr int HST_MAX_NB = 2 * HST_MAX_HALF + 1;
 constexpr int HST_UNIFORM = -1;                                     // hist_add's one-ballot form
 constexpr int HST_PEEL_ALL = 64;
 constexpr int HST_SCHEME_DEFAULT = 1;                               // option "hist_scheme" when unset (DESIGN.md 4.18 has the measurement)
-static_assert(HST_THREADS * HST_QUADS * 4 == SSD_UPDATE_BLOCK_ELEMS, "a block is 256 lanes x 4 quads x 4 elements");
-static_assert(sizeof(ssd_update_tensor) == 56, "ssd_update_tensor is the 56-byte row of include/ssd_hip.h");
 static_assert(sizeof(ssd_histogram_stats) == SSD_HISTOGRAM_STATS_BYTES, "ssd_histogram_stats is 40 bytes, no padding");
 
 constexpr unsigned KEY_POS_INF = 0xff800000u;                       // key(+inf): above every finite key
@@ -189,105 +177,43 @@ __device__ __forceinline__ void hist_one(float x, float g, bool in, bool decay, 
     }
 }
 
-// one block of the work list: virtual elements [j0, j0 + 4096) of a tensor -> this lane's statistics, the block's LDS histogram
-template <bool GRAD, int PEEL>
-__device__ __forceinline__ void hist_block(gcfloat *w, gcfloat *grad, int64_t count, int64_t j0, int pad, bool gvec, bool decay,
-                                           float weight_decay, const double *P, int M, int *hist, int NBpad, Plane &pw, Plane &pg, int &blo,
-                                           int &bhi)
+__global__ __launch_bounds__(TBL_THREADS) void train_hist_clear(unsigned long long *__restrict__ counts, int64_t n)
 {
-    const int tid = (int)threadIdx.x;
-    const int64_t end = pad + count;                                 // virtual elements [pad, end) are the tensor
-    if (j0 >= pad && j0 + SSD_UPDATE_BLOCK_ELEMS <= end && (!GRAD || gvec)) {
-        // the main path: every quad of the block is inside the tensor and 16-byte aligned
-        const int64_t i0 = j0 - pad + tid * 4;
-        v4f x[HST_QUADS], g[HST_QUADS];
-#pragma unroll
-        for (int k = 0; k < HST_QUADS; ++k) {
-            const int64_t i = i0 + k * (HST_THREADS * 4);
-            x[k] = *(gcv4f *)(w + i);
-            if (GRAD) g[k] = *(gcv4f *)(grad + i);
-            else g[k] = (v4f){0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int k = 0; k < HST_QUADS; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) hist_one<GRAD, PEEL>(x[k][e], g[k][e], true, decay, weight_decay, P, M, hist, NBpad, pw, pg, blo, bhi);
-    } else {
-        // the block with the tensor's head or tail, or a gradient of another alignment class: whole quads where they fit and are
-        // aligned, single elements otherwise -- always into the quad's own lane.  Every lane walks all 16 positions (an element
-        // outside the tensor is `in == false`), so that the ballots of hist_add see the whole wave
-#pragma unroll 1
-        for (int k = 0; k < HST_QUADS; ++k) {
-            const int64_t j = j0 + (int64_t)(k * HST_THREADS + tid) * 4;
-            const bool whole = j >= pad && j + 4 <= end;
-            v4f x = (v4f){0.f, 0.f, 0.f, 0.f}, g = (v4f){0.f, 0.f, 0.f, 0.f};
-            if (whole) {
-                x = *(gcv4f *)(w + (j - pad));
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (j + e >= pad && j + e < end) x[e] = w[j + e - pad];
-            }
-            if (GRAD) {
-                if (whole && gvec) {
-                    g = *(gcv4f *)(grad + (j - pad));
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (j + e >= pad && j + e < end) g[e] = grad[j + e - pad];
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                hist_one<GRAD, PEEL>(x[e], g[e], j + e >= pad && j + e < end, decay, weight_decay, P, M, hist, NBpad, pw, pg, blo, bhi);
-        }
-    }
-}
-
-__global__ __launch_bounds__(HST_THREADS) void train_hist_clear(unsigned long long *__restrict__ counts, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * HST_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * HST_THREADS) counts[i] = 0;
+    for (int64_t i = (int64_t)blockIdx.x * TBL_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * TBL_THREADS) counts[i] = 0;
 }
 
 template <int PEEL>
-__global__ __launch_bounds__(HST_THREADS) void train_hist_blocks(const ssd_update_tensor *__restrict__ tensors, int T, int total_blocks,
+__global__ __launch_bounds__(TBL_THREADS) void train_hist_blocks(const ssd_update_tensor *__restrict__ tensors, int T, int total_blocks,
                                                                  float weight_decay, const double *__restrict__ limits, int NB,
                                                                  unsigned long long *__restrict__ counts, Partial *__restrict__ partials)
 {
     __shared__ double lds_p[HST_MAX_HALF];                           // the positive limits
     __shared__ int lds_hist[2 * HST_MAX_NB];                         // the block's histogram of both planes
-    __shared__ double lds_d[4][HST_THREADS];
-    __shared__ unsigned lds_u[4][HST_THREADS];
-    __shared__ int lds_i[4][HST_THREADS];
+    __shared__ double lds_d[4][TBL_THREADS];
+    __shared__ unsigned lds_u[4][TBL_THREADS];
+    __shared__ int lds_i[4][TBL_THREADS];
     __shared__ int lds_range[2];
     const int tid = (int)threadIdx.x;
     const int M = (NB - 1) >> 1;
-    for (int i = tid; i < M; i += HST_THREADS) lds_p[i] = limits[M + 1 + i];
-    for (int i = tid; i < 2 * HST_MAX_NB; i += HST_THREADS) lds_hist[i] = 0;
+    for (int i = tid; i < M; i += TBL_THREADS) lds_p[i] = limits[M + 1 + i];
+    for (int i = tid; i < 2 * HST_MAX_NB; i += TBL_THREADS) lds_hist[i] = 0;
     __syncthreads();
     for (int c = (int)blockIdx.x; c < total_blocks; c += (int)gridDim.x) {
-        // the last row whose first_block <= c (a row of no blocks shares its successor's first_block and is never found)
-        int lo = 0, hi = T;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (tensors[mid].first_block <= c) lo = mid; else hi = mid;
-        }
-        const ssd_update_tensor r = tensors[lo];
-        gcfloat *w = (gcfloat *)r.w, *grad = (gcfloat *)r.grad;
+        const int row = row_of_block(tensors, T, &ssd_update_tensor::first_block, c);
+        const ssd_update_tensor r = tensors[row];
+        const gfloat *w = (const gfloat *)r.w, *grad = (const gfloat *)r.grad;
         const int pad = (int)(((uintptr_t)w & 15) >> 2);
         const bool gvec = (((uintptr_t)grad ^ (uintptr_t)w) & 15) == 0;
         const int64_t j0 = (int64_t)(c - r.first_block) * SSD_UPDATE_BLOCK_ELEMS;
         Plane pw = {0.0, 0.0, KEY_POS_INF, KEY_NEG_INF, 0, 0}, pg = pw;
         int blo = NB, bhi = -1;
-        if (grad) hist_block<true, PEEL>(w, grad, r.count, j0, pad, gvec, r.decay != 0, weight_decay, lds_p, M, lds_hist, HST_MAX_NB, pw, pg, blo, bhi);
-        else hist_block<false, PEEL>(w, grad, r.count, j0, pad, false, false, weight_decay, lds_p, M, lds_hist, HST_MAX_NB, pw, pg, blo, bhi);
-        // train_norms' tree a[t] += a[t + s] on the four doubles: s = 128 and 64 through LDS, the rest inside wave 0.  The keys, the
-        // counts and the bucket range are integers (any order): a lane holds at most 16 elements of each kind and a block 4096, so
-        // num and bad of a plane travel in one int
-        lds_d[0][tid] = pw.sum;
-        lds_d[1][tid] = pw.sq;
-        lds_d[2][tid] = pg.sum;
-        lds_d[3][tid] = pg.sq;
+        const bool decay = r.decay != 0;
+        if (grad) walk_block<true>(w, grad, r.count, j0, pad, gvec, [&](float x, float g, bool in) {
+            hist_one<true, PEEL>(x, g, in, decay, weight_decay, lds_p, M, lds_hist, HST_MAX_NB, pw, pg, blo, bhi); });
+        else walk_block<false>(w, grad, r.count, j0, pad, false, [&](float x, float g, bool in) {
+            hist_one<false, PEEL>(x, g, in, false, weight_decay, lds_p, M, lds_hist, HST_MAX_NB, pw, pg, blo, bhi); });
+        // the four doubles go through tree256; the keys, the counts and the bucket range are integers (any order): a lane holds at
+        // most 16 elements of each kind and a block 4096, so num and bad of a plane travel in one int
         lds_u[0][tid] = pw.kmin;
         lds_u[1][tid] = pw.kmax;
         lds_u[2][tid] = pg.kmin;
@@ -296,13 +222,11 @@ __global__ __launch_bounds__(HST_THREADS) void train_hist_blocks(const ssd_updat
         lds_i[1][tid] = pg.num | (pg.bad << 16);
         lds_i[2][tid] = blo;
         lds_i[3][tid] = bhi;
-        __syncthreads();
+        double d[4] = {pw.sum, pw.sq, pg.sum, pg.sq};
+        tree256<4>(d, lds_d);
         if (tid < 64) {
-            double d[4];
             unsigned u[4];
             int n[2], rlo, rhi;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) d[q] = (lds_d[q][tid] + lds_d[q][tid + 128]) + (lds_d[q][tid + 64] + lds_d[q][tid + 192]);
             u[0] = min(min(lds_u[0][tid], lds_u[0][tid + 128]), min(lds_u[0][tid + 64], lds_u[0][tid + 192]));
             u[1] = max(max(lds_u[1][tid], lds_u[1][tid + 128]), max(lds_u[1][tid + 64], lds_u[1][tid + 192]));
             u[2] = min(min(lds_u[2][tid], lds_u[2][tid + 128]), min(lds_u[2][tid + 64], lds_u[2][tid + 192]));
@@ -313,8 +237,6 @@ __global__ __launch_bounds__(HST_THREADS) void train_hist_blocks(const ssd_updat
             rhi = max(max(lds_i[3][tid], lds_i[3][tid + 128]), max(lds_i[3][tid + 64], lds_i[3][tid + 192]));
 #pragma unroll
             for (int s = 32; s >= 1; s >>= 1) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) d[q] = d[q] + __shfl_down(d[q], s, 64);
                 u[0] = min(u[0], (unsigned)__shfl_down((int)u[0], s, 64));
                 u[1] = max(u[1], (unsigned)__shfl_down((int)u[1], s, 64));
                 u[2] = min(u[2], (unsigned)__shfl_down((int)u[2], s, 64));
@@ -346,8 +268,8 @@ __global__ __launch_bounds__(HST_THREADS) void train_hist_blocks(const ssd_updat
         __syncthreads();                                             // the range; every LDS atomic of the block has landed
         // the flush: the non-zero buckets of the touched range of both planes, and the block's histogram is zero again
         const int rlo = lds_range[0], width = lds_range[1] - rlo + 1;
-        unsigned long long *out = counts + (int64_t)lo * 2 * NB;
-        for (int i = tid; i < 2 * width; i += HST_THREADS) {
+        unsigned long long *out = counts + (int64_t)row * 2 * NB;
+        for (int i = tid; i < 2 * width; i += TBL_THREADS) {
             const int plane = i >= width ? 1 : 0;
             const int b = rlo + (i - plane * width);
             const int v = lds_hist[plane * HST_MAX_NB + b];
@@ -360,11 +282,9 @@ __global__ __launch_bounds__(HST_THREADS) void train_hist_blocks(const ssd_updat
     }
 }
 
-// stage 2, one wave per tensor, train_norms_rows' form: the lanes fetch 64 consecutive partials at once, then every lane adds the 64
-// in ascending order, reading lane i's doubles with v_readlane; lanes past the tensor's last block hold +0.0, which leaves a sum that
-// started at +0.0 as it is (a sum of this call is never -0.0: +0.0 + -0.0 = +0.0).  Keys and counts are integers.
-__global__ __launch_bounds__(HST_ROW_THREADS) void train_hist_rows(const ssd_update_tensor *__restrict__ tensors, int T, int total_blocks,
-                                                                   const Partial *__restrict__ partials, ssd_histogram_stats *__restrict__ stats)
+// stage 2, one wave per tensor.  Keys and counts are integers: each lane keeps its own and the wave combines them at the end.
+__global__ __launch_bounds__(TBL_WAVE) void train_hist_rows(const ssd_update_tensor *__restrict__ tensors, int T, int total_blocks,
+                                                            const Partial *__restrict__ partials, ssd_histogram_stats *__restrict__ stats)
 {
     const int t = (int)blockIdx.x, lane = (int)threadIdx.x;
     const int first = tensors[t].first_block;
@@ -372,7 +292,7 @@ __global__ __launch_bounds__(HST_ROW_THREADS) void train_hist_rows(const ssd_upd
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     unsigned kminw = KEY_POS_INF, kmaxw = KEY_NEG_INF, kming = KEY_POS_INF, kmaxg = KEY_NEG_INF;
     long long numw = 0, badw = 0, numg = 0, badg = 0;
-    for (int base = first; base < last; base += HST_ROW_THREADS) {
+    for (int base = first; base < last; base += TBL_WAVE) {
         Partial p = {0.0, 0.0, 0.0, 0.0, KEY_POS_INF, KEY_NEG_INF, KEY_POS_INF, KEY_NEG_INF, 0, 0, 0, 0};
         if (base + lane < last) p = partials[base + lane];
         kminw = min(kminw, p.kminw);
@@ -384,13 +304,7 @@ __global__ __launch_bounds__(HST_ROW_THREADS) void train_hist_rows(const ssd_upd
         numg += p.numg;
         badg += p.badg;
         const double v[4] = {p.sw, p.qw, p.sg, p.qg};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int vlo = __double2loint(v[q]), vhi = __double2hiint(v[q]);
-#pragma unroll
-            for (int i = 0; i < HST_ROW_THREADS; ++i)
-                s[q] = s[q] + __hiloint2double(__builtin_amdgcn_readlane(vhi, i), __builtin_amdgcn_readlane(vlo, i));
-        }
+        wave_ordered_add<4>(s, v);
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
@@ -422,37 +336,11 @@ __global__ __launch_bounds__(HST_ROW_THREADS) void train_hist_rows(const ssd_upd
     }
 }
 
-// the TRAIN update's checks of its table (update.hip, restated as in train_norms.hip: those files stay as they are), in its order
-// and wording -> the blocks
-int check_table(const char *fn, const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T, int64_t *blocks_out)
-{
-    const std::string name(fn);
-    if (!tensors_host || !tensors_dev) return ssd_fail(SSD_ERR_INVALID, name + ": bad arguments");
-    if (T < 1 || T > SSD_UPDATE_MAX_TENSORS)
-        return ssd_fail(SSD_ERR_INVALID, name + ": T must be in [1, " + std::to_string(SSD_UPDATE_MAX_TENSORS) + "]");
-    if ((uintptr_t)tensors_dev & 7) return ssd_fail(SSD_ERR_INVALID, name + ": tensors_dev must be 8-byte aligned");
-    int64_t blocks = 0;
-    for (int32_t t = 0; t < T; ++t) {
-        const ssd_update_tensor &d = tensors_host[t];
-        const std::string row = name + ": tensor " + std::to_string(t) + ": ";
-        if (d.count < 0 || d.count > ((int64_t)1 << 40)) return ssd_fail(SSD_ERR_INVALID, row + "bad count");
-        if (!d.w || !d.m || !d.v || !d.ema) return ssd_fail(SSD_ERR_INVALID, row + "NULL w, m, v or ema");
-        if (((uintptr_t)d.w | (uintptr_t)d.m | (uintptr_t)d.v | (uintptr_t)d.ema | (uintptr_t)d.grad) & 3)
-            return ssd_fail(SSD_ERR_INVALID, row + "w, m, v, ema and grad must be 4-byte aligned");
-        if (d.decay != 0 && d.decay != 1) return ssd_fail(SSD_ERR_INVALID, row + "decay must be 0 or 1");
-        if (d.first_block != blocks) return ssd_fail(SSD_ERR_INVALID, row + "first_block must be " + std::to_string(blocks));
-        blocks += (d.count + (int64_t)(((uintptr_t)d.w >> 2) & 3) + SSD_UPDATE_BLOCK_ELEMS - 1) / SSD_UPDATE_BLOCK_ELEMS;
-        if (blocks > INT_MAX) return ssd_fail(SSD_ERR_INVALID, name + ": more than 2^31 - 1 blocks");
-    }
-    *blocks_out = blocks;
-    return SSD_OK;
-}
-
 template <int PEEL>
 void launch_blocks(unsigned grid, hipStream_t stream, const ssd_update_tensor *tensors_dev, int T, int blocks, float weight_decay,
                    const double *limits_dev, int NB, unsigned long long *counts, Partial *partials)
 {
-    hipLaunchKernelGGL(train_hist_blocks<PEEL>, dim3(grid), dim3(HST_THREADS), 0, stream, tensors_dev, T, blocks, weight_decay, limits_dev, NB,
+    hipLaunchKernelGGL(train_hist_blocks<PEEL>, dim3(grid), dim3(TBL_THREADS), 0, stream, tensors_dev, T, blocks, weight_decay, limits_dev, NB,
                        counts, partials);
 }
 
@@ -469,12 +357,7 @@ extern "C" int32_t ssd_histogram_limits(double *out, int32_t capacity)
 
 extern "C" size_t ssd_train_histograms_workspace_bytes(const ssd_update_tensor *tensors_host, int32_t T)
 {
-    int64_t blocks = 0;
-    // the planner sees no device table: any aligned non-NULL address stands in for it
-    if (check_table("ssd_train_histograms_workspace_bytes", tensors_host, tensors_host ? (const ssd_update_tensor *)(uintptr_t)8 : nullptr, T,
-                    &blocks) != SSD_OK)
-        return 0;
-    return (size_t)blocks * SSD_HISTOGRAM_BLOCK_BYTES;
+    return update_table_bytes("ssd_train_histograms_workspace_bytes", tensors_host, T, SSD_HISTOGRAM_BLOCK_BYTES);
 }
 
 extern "C" int ssd_train_histograms(const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T, float weight_decay,
@@ -482,27 +365,23 @@ extern "C" int ssd_train_histograms(const ssd_update_tensor *tensors_host, const
                                     size_t workspace_bytes, void *stream)
 {
     int64_t blocks = 0;
-    SSDCHK(check_table("ssd_train_histograms", tensors_host, tensors_dev, T, &blocks));
+    SSDCHK(check_update_table("ssd_train_histograms", tensors_host, tensors_dev, T, &blocks));
     if (!std::isfinite(weight_decay)) return ssd_fail(SSD_ERR_INVALID, "ssd_train_histograms: weight_decay is not finite");
     if (!limits_dev || !counts || !stats) return ssd_fail(SSD_ERR_INVALID, "ssd_train_histograms: NULL limits_dev, counts or stats");
     if (((uintptr_t)limits_dev | (uintptr_t)counts | (uintptr_t)stats) & 7)
         return ssd_fail(SSD_ERR_INVALID, "ssd_train_histograms: limits_dev, counts and stats must be 8-byte aligned");
-    if (!workspace) return ssd_fail(SSD_ERR_INVALID, "ssd_train_histograms: NULL workspace");
-    if ((uintptr_t)workspace & 15) return ssd_fail(SSD_ERR_INVALID, "ssd_train_histograms: workspace must be 16-byte aligned");
-    if (workspace_bytes < (size_t)blocks * SSD_HISTOGRAM_BLOCK_BYTES)
-        return ssd_fail(SSD_ERR_INVALID, "ssd_train_histograms: workspace too small: " + std::to_string(workspace_bytes) + " bytes, needs " +
-                                             std::to_string((size_t)blocks * SSD_HISTOGRAM_BLOCK_BYTES));
+    SSDCHK(check_workspace("ssd_train_histograms", workspace, workspace_bytes, (size_t)blocks * SSD_HISTOGRAM_BLOCK_BYTES));
     const int NB = (int)limits_table().size();
     if (NB > HST_MAX_NB) return ssd_fail(SSD_ERR_INVALID, "ssd_train_histograms: the limits table outgrew the kernel's LDS room");
     const int scheme = ssd_opt(nullptr, OPT_HIST_SCHEME, -1);
     const int pick = scheme < 0 ? HST_SCHEME_DEFAULT : scheme;
     hipStream_t s = (hipStream_t)stream;
     const int64_t cells = (int64_t)T * 2 * NB;
-    const unsigned cgrid = (unsigned)std::min<int64_t>((cells + HST_THREADS - 1) / HST_THREADS, HST_MAX_GRID);
-    hipLaunchKernelGGL(train_hist_clear, dim3(cgrid), dim3(HST_THREADS), 0, s, (unsigned long long *)counts, cells);
+    const unsigned cgrid = grid_for((cells + TBL_THREADS - 1) / TBL_THREADS);
+    hipLaunchKernelGGL(train_hist_clear, dim3(cgrid), dim3(TBL_THREADS), 0, s, (unsigned long long *)counts, cells);
     HIPCHK(hipGetLastError());
     if (blocks > 0) {
-        const unsigned grid = (unsigned)(blocks < HST_MAX_GRID ? blocks : HST_MAX_GRID);
+        const unsigned grid = grid_for(blocks);
         unsigned long long *c = (unsigned long long *)counts;
         Partial *p = (Partial *)workspace;
         if (pick == 0) launch_blocks<0>(grid, s, tensors_dev, (int)T, (int)blocks, weight_decay, limits_dev, NB, c, p);
@@ -512,7 +391,7 @@ extern "C" int ssd_train_histograms(const ssd_update_tensor *tensors_host, const
         else launch_blocks<HST_PEEL_ALL>(grid, s, tensors_dev, (int)T, (int)blocks, weight_decay, limits_dev, NB, c, p);
         HIPCHK(hipGetLastError());
     }
-    hipLaunchKernelGGL(train_hist_rows, dim3((unsigned)T), dim3(HST_ROW_THREADS), 0, s, tensors_dev, (int)T, (int)blocks,
+    hipLaunchKernelGGL(train_hist_rows, dim3((unsigned)T), dim3(TBL_WAVE), 0, s, tensors_dev, (int)T, (int)blocks,
                        (const Partial *)workspace, stats);
     HIPCHK(hipGetLastError());
     return SSD_OK;

@@ -1,11 +1,13 @@
 // The TRAIN step's gradient exchange: one slice per rank packed for ONE all-gather, the gathered slices summed in ascending rank
 // order.  Semantics, the bucket layout and every refusal: include/ssd_hip.h, block "the TRAIN step's gradient exchange".
 //
-//   grad_pack      256 lanes per block.  The work list is the payload cut into blocks of SSD_UPDATE_BLOCK_ELEMS (4096) bucket floats;
-//                  a grid of at most RED_MAX_GRID blocks strides over it.  A block finds the row that holds its first float by a
-//                  binary search over the rows' offset (block-uniform: scalar loads, every branch on a row taken by all lanes
-//                  alike) and walks the rows from there until one starts behind the block.  Offsets are multiples of 4 and the
-//                  payload is 16-byte aligned, so a bucket quad lies inside ONE row and is always stored as 16 bytes; it is loaded
+//   walk_rows      under both kernels.  256 lanes per block; the work list is the payload cut into blocks of SSD_UPDATE_BLOCK_ELEMS
+//                  (4096) bucket floats; a grid of at most TBL_MAX_GRID blocks strides over it (train_table.h: the shape, the row
+//                  search).  A block finds the row that holds its first float by the search over the rows' offset (block-uniform:
+//                  scalar loads, every branch on a row taken by all lanes alike) and walks the rows from there until one starts
+//                  behind the block.
+//   grad_pack      Offsets are multiples of 4 and the payload is 16-byte aligned, so a bucket quad lies inside ONE row and is
+//                  always stored as 16 bytes; it is loaded
 //                  as 16 bytes where the row's data is 16-byte aligned and the quad lies inside the tensor, else element by element
 //                  (+0.0 behind the tensor's end and for a NULL row).  A block wholly inside one aligned tensor -- nearly all of a
 //                  model's floats -- moves as 4 loads then 4 stores per lane.  Block 0 also writes the 16 header floats.
@@ -14,26 +16,15 @@
 //                  the row's data as 16 bytes, or element by element where data is not 16-byte aligned or the quad crosses the
 //                  tensor's end.  G is a template parameter (1 .. SSD_REDUCE_MAX_RANKS): the slices' quads and the c_r stay in
 //                  registers.  Block 0's lane 0 writes losses_out and weights_out.  No LDS, no atomics.
-#include "host.h"
+#include "train_table.h"
 
 #include <algorithm>
 
 #pragma clang fp contract(off)
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-// the rows hold plain pointers, whose address space the compiler cannot know: said to be global memory, the kernel's loads and
-// stores are global_load / global_store instead of flat ones
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) v4f gv4f;
-
 namespace {
 
-constexpr int RED_THREADS = 256;
-constexpr int RED_QUADS = 4;                                        // 16-byte groups per lane and block
-constexpr int RED_MAX_GRID = 2048;                                  // 256 CUs x 8 blocks: the rest is grid-strided
 constexpr int64_t RED_BLOCK = SSD_UPDATE_BLOCK_ELEMS;
-constexpr int64_t RED_STEP = RED_THREADS * 4;                       // floats one pass of the 256 lanes covers
-static_assert(RED_THREADS * RED_QUADS * 4 == SSD_UPDATE_BLOCK_ELEMS, "a block is 256 lanes x 4 quads x 4 floats");
 static_assert(sizeof(ssd_reduce_row) == 32, "ssd_reduce_row is the 32-byte row of include/ssd_hip.h");
 static_assert(offsetof(ssd_reduce_row, count) == 8 && offsetof(ssd_reduce_row, offset) == 16 && offsetof(ssd_reduce_row, kind) == 24,
               "ssd_reduce_row has no padding");
@@ -41,21 +32,36 @@ static_assert(SSD_REDUCE_HEADER_FLOATS % 4 == 0, "the payload starts on a 16-byt
 
 __device__ __forceinline__ int64_t roundup4(int64_t n) { return (n + 3) & ~(int64_t)3; }
 
-// the last row whose offset <= b0 (offset_0 == 0; of rows that share an offset -- empty ones -- the last)
-__device__ __forceinline__ int first_row(const ssd_reduce_row *__restrict__ rows, int T, int64_t b0)
-{
-    int lo = 0, hi = T;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (rows[mid].offset <= b0) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ float at_least_one(float a) { return a > 1.0f ? a : 1.0f; }
 
+// One block of the work list, bucket floats [b0, b0 + 4096): every row with floats in it, from the row of b0 on (of rows that share
+// an offset -- empty ones -- the search finds the last), empty rows skipped and, with NEED_DATA, rows whose data is NULL.  A block
+// wholly inside one 16-byte aligned tensor is main(r, data); of any other row, this lane's quads j inside the block are
+// quad(r, data, vec, j), vec: data is there and 16-byte aligned.
+template <bool NEED_DATA, class Main, class Quad>
+__device__ __forceinline__ void walk_rows(const ssd_reduce_row *__restrict__ rows, int T, int64_t b0, Main main, Quad quad)
+{
+    const int64_t b1 = b0 + RED_BLOCK;
+    for (int t = row_of_block(rows, T, &ssd_reduce_row::offset, b0); t < T; ++t) {
+        const ssd_reduce_row r = rows[t];
+        if (r.offset >= b1) break;
+        gfloat *data = (gfloat *)r.data;
+        if (NEED_DATA && !data) continue;
+        const int64_t s0 = r.offset > b0 ? r.offset : b0;
+        const int64_t rend = r.offset + roundup4(r.count), s1 = rend < b1 ? rend : b1;
+        if (s1 <= s0) continue;                                      // an empty row
+        const bool vec = data && ((uintptr_t)data & 15) == 0;
+        if (vec && s0 == b0 && r.offset + r.count >= b1) {
+            main(r, data);                                           // the main path: 4 quads per lane, unrolled
+        } else {
+#pragma unroll 1
+            for (int64_t j = s0 + (int)threadIdx.x * 4; j < s1; j += TBL_STEP) quad(r, data, vec, j);
+        }
+    }
+}
+
 // ----------------------------------------------------------------------------- pack
-__global__ __launch_bounds__(RED_THREADS) void grad_pack(const ssd_reduce_row *__restrict__ rows, int T, int64_t used, int blocks,
+__global__ __launch_bounds__(TBL_THREADS) void grad_pack(const ssd_reduce_row *__restrict__ rows, int T, int64_t used, int blocks,
                                                          const gfloat *__restrict__ header, gfloat *__restrict__ slice)
 {
     const int tid = (int)threadIdx.x;
@@ -63,40 +69,30 @@ __global__ __launch_bounds__(RED_THREADS) void grad_pack(const ssd_reduce_row *_
     gfloat *pay = slice + SSD_REDUCE_HEADER_FLOATS;
     for (int c = (int)blockIdx.x; c < blocks; c += (int)gridDim.x) {
         const int64_t b0 = (int64_t)c * RED_BLOCK, b1 = b0 + RED_BLOCK;
-        for (int t = first_row(rows, T, b0); t < T; ++t) {
-            const ssd_reduce_row r = rows[t];
-            if (r.offset >= b1) break;
-            const gfloat *data = (const gfloat *)r.data;
-            const int64_t s0 = r.offset > b0 ? r.offset : b0;
-            const int64_t rend = r.offset + roundup4(r.count), s1 = rend < b1 ? rend : b1;
-            if (s1 <= s0) continue;                                  // an empty row
-            const bool vec = data && ((uintptr_t)data & 15) == 0;
-            if (vec && s0 == b0 && r.offset + r.count >= b1) {
-                // the main path: the whole block inside one 16-byte aligned tensor
+        walk_rows<false>(
+            rows, T, b0,
+            [&](const ssd_reduce_row &r, const gfloat *data) {
                 const int64_t j0 = b0 + tid * 4;
-                v4f x[RED_QUADS];
+                v4f x[TBL_QUADS];
 #pragma unroll
-                for (int k = 0; k < RED_QUADS; ++k) x[k] = *(const gv4f *)(data + (j0 + k * RED_STEP - r.offset));
+                for (int k = 0; k < TBL_QUADS; ++k) x[k] = *(const gv4f *)(data + (j0 + k * TBL_STEP - r.offset));
 #pragma unroll
-                for (int k = 0; k < RED_QUADS; ++k) *(gv4f *)(pay + j0 + k * RED_STEP) = x[k];
-            } else {
-#pragma unroll 1
-                for (int64_t j = s0 + tid * 4; j < s1; j += RED_STEP) {
-                    const int64_t i = j - r.offset;                  // the quad's first element
-                    v4f x = v4f{0, 0, 0, 0};
-                    if (vec && i + 4 <= r.count) {
-                        x = *(const gv4f *)(data + i);
-                    } else if (data) {
-                        for (int e = 0; e < 4; ++e)
-                            if (i + e < r.count) x[e] = data[i + e];
-                    }
-                    *(gv4f *)(pay + j) = x;
+                for (int k = 0; k < TBL_QUADS; ++k) *(gv4f *)(pay + j0 + k * TBL_STEP) = x[k];
+            },
+            [&](const ssd_reduce_row &r, const gfloat *data, bool vec, int64_t j) {
+                const int64_t i = j - r.offset;                      // the quad's first element
+                v4f x = v4f{0, 0, 0, 0};
+                if (vec && i + 4 <= r.count) {
+                    x = *(const gv4f *)(data + i);
+                } else if (data) {
+                    for (int e = 0; e < 4; ++e)
+                        if (i + e < r.count) x[e] = data[i + e];
                 }
-            }
-        }
+                *(gv4f *)(pay + j) = x;
+            });
         if (used < b1) {                                             // the payload behind the last row
 #pragma unroll 1
-            for (int64_t j = (used > b0 ? used : b0) + tid * 4; j < b1; j += RED_STEP) *(gv4f *)(pay + j) = v4f{0, 0, 0, 0};
+            for (int64_t j = (used > b0 ? used : b0) + tid * 4; j < b1; j += TBL_STEP) *(gv4f *)(pay + j) = v4f{0, 0, 0, 0};
         }
     }
 }
@@ -133,7 +129,7 @@ __device__ __forceinline__ v4f reduce_four(const v4f (&x)[G], const float (&c)[G
 }
 
 template <int G>
-__global__ __launch_bounds__(RED_THREADS) void grad_reduce(const ssd_reduce_row *__restrict__ rows, int T, int blocks,
+__global__ __launch_bounds__(TBL_THREADS) void grad_reduce(const ssd_reduce_row *__restrict__ rows, int T, int blocks,
                                                            const gfloat *__restrict__ gathered, int64_t slice_floats,
                                                            gfloat *__restrict__ losses_out, gfloat *__restrict__ weights_out)
 {
@@ -162,45 +158,33 @@ __global__ __launch_bounds__(RED_THREADS) void grad_reduce(const ssd_reduce_row 
     }
     const gfloat *pay = gathered + SSD_REDUCE_HEADER_FLOATS;
     for (int cb = (int)blockIdx.x; cb < blocks; cb += (int)gridDim.x) {
-        const int64_t b0 = (int64_t)cb * RED_BLOCK, b1 = b0 + RED_BLOCK;
-        for (int t = first_row(rows, T, b0); t < T; ++t) {
-            const ssd_reduce_row r = rows[t];
-            if (r.offset >= b1) break;
-            gfloat *data = (gfloat *)r.data;
-            if (!data) continue;                                     // nothing goes back
-            const bool mean = r.kind != 0;
-            const int64_t s0 = r.offset > b0 ? r.offset : b0;
-            const int64_t rend = r.offset + roundup4(r.count), s1 = rend < b1 ? rend : b1;
-            if (s1 <= s0) continue;                                  // an empty row
-            const bool vec = ((uintptr_t)data & 15) == 0;
-            if (vec && s0 == b0 && r.offset + r.count >= b1) {
-                // the main path: the whole block inside one 16-byte aligned tensor
+        const int64_t b0 = (int64_t)cb * RED_BLOCK;
+        walk_rows<true>(                                             // a row without data: nothing goes back
+            rows, T, b0,
+            [&](const ssd_reduce_row &r, gfloat *data) {
                 const int64_t j0 = b0 + tid * 4;
 #pragma unroll
-                for (int k = 0; k < RED_QUADS; ++k) {
-                    const int64_t j = j0 + k * RED_STEP;
+                for (int k = 0; k < TBL_QUADS; ++k) {
+                    const int64_t j = j0 + k * TBL_STEP;
                     v4f x[G];
 #pragma unroll
                     for (int q = 0; q < G; ++q) x[q] = *(const gv4f *)(pay + q * slice_floats + j);
-                    *(gv4f *)(data + (j - r.offset)) = reduce_four<G>(x, c, mean, inv_g);
+                    *(gv4f *)(data + (j - r.offset)) = reduce_four<G>(x, c, r.kind != 0, inv_g);
                 }
-            } else {
-#pragma unroll 1
-                for (int64_t j = s0 + tid * 4; j < s1; j += RED_STEP) {
-                    const int64_t i = j - r.offset;                  // the quad's first element
-                    v4f x[G];
+            },
+            [&](const ssd_reduce_row &r, gfloat *data, bool vec, int64_t j) {
+                const int64_t i = j - r.offset;                      // the quad's first element
+                v4f x[G];
 #pragma unroll
-                    for (int q = 0; q < G; ++q) x[q] = *(const gv4f *)(pay + q * slice_floats + j);
-                    const v4f y = reduce_four<G>(x, c, mean, inv_g);
-                    if (vec && i + 4 <= r.count) {
-                        *(gv4f *)(data + i) = y;
-                    } else {
-                        for (int e = 0; e < 4; ++e)
-                            if (i + e < r.count) data[i + e] = y[e];
-                    }
+                for (int q = 0; q < G; ++q) x[q] = *(const gv4f *)(pay + q * slice_floats + j);
+                const v4f y = reduce_four<G>(x, c, r.kind != 0, inv_g);
+                if (vec && i + 4 <= r.count) {
+                    *(gv4f *)(data + i) = y;
+                } else {
+                    for (int e = 0; e < 4; ++e)
+                        if (i + e < r.count) data[i + e] = y[e];
                 }
-            }
-        }
+            });
     }
 }
 
@@ -208,7 +192,7 @@ template <int G>
 void launch_reduce(unsigned grid, hipStream_t s, const ssd_reduce_row *rows, int T, int blocks, const float *gathered,
                    int64_t slice_floats, float *losses_out, float *weights_out)
 {
-    hipLaunchKernelGGL(grad_reduce<G>, dim3(grid), dim3(RED_THREADS), 0, s, rows, T, blocks, (const gfloat *)gathered, slice_floats,
+    hipLaunchKernelGGL(grad_reduce<G>, dim3(grid), dim3(TBL_THREADS), 0, s, rows, T, blocks, (const gfloat *)gathered, slice_floats,
                        (gfloat *)losses_out, (gfloat *)weights_out);
 }
 
@@ -261,8 +245,8 @@ extern "C" int ssd_train_grad_pack(const ssd_reduce_row *rows_host, const ssd_re
     if (slice_floats != SSD_REDUCE_HEADER_FLOATS + P)
         return ssd_fail(SSD_ERR_INVALID, who + ": slice_floats must be " + std::to_string(SSD_REDUCE_HEADER_FLOATS + P));
     const int64_t blocks = P / RED_BLOCK;
-    const unsigned grid = (unsigned)(blocks < 1 ? 1 : blocks < RED_MAX_GRID ? blocks : RED_MAX_GRID);     // block 0: the header
-    hipLaunchKernelGGL(grad_pack, dim3(grid), dim3(RED_THREADS), 0, (hipStream_t)stream, rows_dev, (int)T, used, (int)blocks,
+    const unsigned grid = grid_for(blocks < 1 ? 1 : blocks);          // block 0: the header
+    hipLaunchKernelGGL(grad_pack, dim3(grid), dim3(TBL_THREADS), 0, (hipStream_t)stream, rows_dev, (int)T, used, (int)blocks,
                        (const gfloat *)header_dev, (gfloat *)slice);
     HIPCHK(hipGetLastError());
     return SSD_OK;
@@ -284,7 +268,7 @@ extern "C" int ssd_train_grad_reduce(const ssd_reduce_row *rows_host, const ssd_
     if (slice_floats != SSD_REDUCE_HEADER_FLOATS + P)
         return ssd_fail(SSD_ERR_INVALID, who + ": slice_floats must be " + std::to_string(SSD_REDUCE_HEADER_FLOATS + P));
     const int64_t blocks = P / RED_BLOCK;
-    const unsigned grid = (unsigned)(blocks < 1 ? 1 : blocks < RED_MAX_GRID ? blocks : RED_MAX_GRID);     // block 0: losses, weights
+    const unsigned grid = grid_for(blocks < 1 ? 1 : blocks);          // block 0: losses, weights
     const hipStream_t s = (hipStream_t)stream;
     switch (G) {
 #define RED_CASE(g) case g: launch_reduce<g>(grid, s, rows_dev, (int)T, (int)blocks, gathered, slice_floats, losses_out, weights_out); break;

@@ -3,7 +3,7 @@
 // update".
 //
 //   train_update   256 lanes per block.  The work list is the model cut into blocks of SSD_UPDATE_BLOCK_ELEMS (4096) elements, each
-//                  inside ONE tensor; a grid of at most UPD_MAX_GRID blocks strides over it.  A block finds its tensor by a binary
+//                  inside ONE tensor; a grid of at most TBL_MAX_GRID blocks strides over it.  A block finds its tensor by a binary
 //                  search over the rows' first_block (a prefix sum the caller filled and the entry point checked): the block index is
 //                  block-uniform, so the search and the row are scalar loads and every branch on the row (gradient present, decay,
 //                  alignment class, whole block inside the tensor) is taken by all lanes alike.
@@ -12,25 +12,17 @@
 //                  4 x 5 16-byte loads and 4 x 4 16-byte stores per lane, all loads issued before the arithmetic; the blocks that hold
 //                  the tensor's head or tail check each quad and fall to single elements where a quad crosses an end.  Any other
 //                  tensor moves element by element, lane-contiguous.  Each element is read once and written once; no LDS, no atomics.
-#include "host.h"
+// The block shape, the row search and the types are train_table.h's; this walk reads AND writes five arrays, so it stays its own.
+// Below the kernel: the host checks of an ssd_update_tensor table that train_table.h declares, for this file, train_norms.hip and
+// train_hist.hip.
+#include "train_table.h"
 
 #include <cmath>
 
 #pragma clang fp contract(off)
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-// the rows hold plain pointers, whose address space the compiler cannot know: said to be global memory, the kernel's loads and
-// stores are global_load / global_store instead of flat ones
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) v4f gv4f;
-
 namespace {
 
-constexpr int UPD_THREADS = 256;
-constexpr int UPD_QUADS = 4;                                        // 16-byte groups per lane and block
-constexpr int UPD_MAX_GRID = 2048;                                  // 256 CUs x 8 blocks: the rest is grid-strided
-static_assert(UPD_THREADS * UPD_QUADS * 4 == SSD_UPDATE_BLOCK_ELEMS, "a block is 256 lanes x 4 quads x 4 elements");
-static_assert(sizeof(ssd_update_tensor) == 56, "ssd_update_tensor is the 56-byte row of include/ssd_hip.h");
 static_assert(sizeof(ssd_update_scalars) == 24, "ssd_update_scalars is six floats");
 
 struct Row {                                                        // one ssd_update_tensor, its pointers as global ones
@@ -114,10 +106,10 @@ __device__ __forceinline__ void update_block(const Row &d, int64_t j0, int pad, 
     if (vec && j0 >= pad && j0 + SSD_UPDATE_BLOCK_ELEMS <= end) {
         // the main path: every quad of the block is inside the tensor
         const int64_t i0 = j0 - pad + tid * 4;
-        v4f w[UPD_QUADS], ema[UPD_QUADS], g[UPD_QUADS], m[UPD_QUADS], v[UPD_QUADS];
+        v4f w[TBL_QUADS], ema[TBL_QUADS], g[TBL_QUADS], m[TBL_QUADS], v[TBL_QUADS];
 #pragma unroll
-        for (int k = 0; k < UPD_QUADS; ++k) {
-            const int64_t i = i0 + k * (UPD_THREADS * 4);
+        for (int k = 0; k < TBL_QUADS; ++k) {
+            const int64_t i = i0 + k * TBL_STEP;
             w[k] = *(const gv4f *)(d.w + i);
             ema[k] = *(const gv4f *)(d.ema + i);
             if (GRAD) {
@@ -129,8 +121,8 @@ __device__ __forceinline__ void update_block(const Row &d, int64_t j0, int pad, 
             }
         }
 #pragma unroll
-        for (int k = 0; k < UPD_QUADS; ++k) {
-            const int64_t i = i0 + k * (UPD_THREADS * 4);
+        for (int k = 0; k < TBL_QUADS; ++k) {
+            const int64_t i = i0 + k * TBL_STEP;
             update_four<GRAD>(w[k], g[k], m[k], v[k], ema[k], decay, s);
             if (GRAD) {
                 *(gv4f *)(d.w + i) = w[k];
@@ -142,8 +134,8 @@ __device__ __forceinline__ void update_block(const Row &d, int64_t j0, int pad, 
     } else if (vec) {
         // the block with the tensor's head or tail: whole quads where they fit, single elements where a quad crosses an end
 #pragma unroll 1
-        for (int k = 0; k < UPD_QUADS; ++k) {
-            const int64_t j = j0 + (int64_t)(k * UPD_THREADS + tid) * 4;
+        for (int k = 0; k < TBL_QUADS; ++k) {
+            const int64_t j = j0 + (int64_t)(k * TBL_THREADS + tid) * 4;
             if (j >= pad && j + 4 <= end) {
                 update_quad_at<GRAD>(d, j - pad, decay, s);
             } else {
@@ -154,24 +146,18 @@ __device__ __forceinline__ void update_block(const Row &d, int64_t j0, int pad, 
     } else {
         // addresses of different alignment classes (pad == 0 here): element by element, consecutive lanes on consecutive elements
 #pragma unroll 1
-        for (int k = 0; k < UPD_QUADS * 4; ++k) {
-            const int64_t j = j0 + k * UPD_THREADS + tid;
+        for (int k = 0; k < TBL_QUADS * 4; ++k) {
+            const int64_t j = j0 + k * TBL_THREADS + tid;
             if (j < end) update_scalar_at<GRAD>(d, j, decay, s);
         }
     }
 }
 
-__global__ __launch_bounds__(UPD_THREADS) void train_update(const ssd_update_tensor *__restrict__ tensors, int T, int total_blocks,
+__global__ __launch_bounds__(TBL_THREADS) void train_update(const ssd_update_tensor *__restrict__ tensors, int T, int total_blocks,
                                                             ssd_update_scalars s)
 {
     for (int c = (int)blockIdx.x; c < total_blocks; c += (int)gridDim.x) {
-        // the last row whose first_block <= c (a row of no blocks shares its successor's first_block and is never found)
-        int lo = 0, hi = T;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (tensors[mid].first_block <= c) lo = mid; else hi = mid;
-        }
-        const ssd_update_tensor r = tensors[lo];
+        const ssd_update_tensor r = tensors[row_of_block(tensors, T, &ssd_update_tensor::first_block, c)];
         const Row d = {(gfloat *)r.w, (const gfloat *)r.grad, (gfloat *)r.m, (gfloat *)r.v, (gfloat *)r.ema, r.count, r.decay != 0};
         const uintptr_t a = (uintptr_t)d.w & 15;
         const bool vec = ((uintptr_t)d.m & 15) == a && ((uintptr_t)d.v & 15) == a && ((uintptr_t)d.ema & 15) == a &&
@@ -185,21 +171,24 @@ __global__ __launch_bounds__(UPD_THREADS) void train_update(const ssd_update_ten
 
 }  // namespace
 
-extern "C" int ssd_train_update(const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T,
-                                const ssd_update_scalars *scalars, void *stream)
+// ----------------------------------------------------------------------------- the table's host checks (train_table.h)
+int check_update_args(const char *fn, const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T, bool others)
 {
-    if (!tensors_host || !tensors_dev || !scalars) return ssd_fail(SSD_ERR_INVALID, "ssd_train_update: bad arguments");
+    const std::string name(fn);
+    if (!tensors_host || !tensors_dev || !others) return ssd_fail(SSD_ERR_INVALID, name + ": bad arguments");
     if (T < 1 || T > SSD_UPDATE_MAX_TENSORS)
-        return ssd_fail(SSD_ERR_INVALID, "ssd_train_update: T must be in [1, " + std::to_string(SSD_UPDATE_MAX_TENSORS) + "]");
-    if ((uintptr_t)tensors_dev & 7) return ssd_fail(SSD_ERR_INVALID, "ssd_train_update: tensors_dev must be 8-byte aligned");
-    const float sc[6] = {scalars->alpha, scalars->one_minus_beta1, scalars->one_minus_beta2, scalars->epsilon, scalars->weight_decay,
-                         scalars->one_minus_decay};
-    for (float x : sc)
-        if (!std::isfinite(x)) return ssd_fail(SSD_ERR_INVALID, "ssd_train_update: non-finite scalar");
+        return ssd_fail(SSD_ERR_INVALID, name + ": T must be in [1, " + std::to_string(SSD_UPDATE_MAX_TENSORS) + "]");
+    if ((uintptr_t)tensors_dev & 7) return ssd_fail(SSD_ERR_INVALID, name + ": tensors_dev must be 8-byte aligned");
+    return SSD_OK;
+}
+
+int check_update_rows(const char *fn, const ssd_update_tensor *tensors_host, int32_t T, int64_t *blocks_out)
+{
+    const std::string name(fn);
     int64_t blocks = 0;
     for (int32_t t = 0; t < T; ++t) {
         const ssd_update_tensor &d = tensors_host[t];
-        const std::string row = "ssd_train_update: tensor " + std::to_string(t) + ": ";
+        const std::string row = name + ": tensor " + std::to_string(t) + ": ";
         if (d.count < 0 || d.count > ((int64_t)1 << 40)) return ssd_fail(SSD_ERR_INVALID, row + "bad count");
         if (!d.w || !d.m || !d.v || !d.ema) return ssd_fail(SSD_ERR_INVALID, row + "NULL w, m, v or ema");
         if (((uintptr_t)d.w | (uintptr_t)d.m | (uintptr_t)d.v | (uintptr_t)d.ema | (uintptr_t)d.grad) & 3)
@@ -207,11 +196,48 @@ extern "C" int ssd_train_update(const ssd_update_tensor *tensors_host, const ssd
         if (d.decay != 0 && d.decay != 1) return ssd_fail(SSD_ERR_INVALID, row + "decay must be 0 or 1");
         if (d.first_block != blocks) return ssd_fail(SSD_ERR_INVALID, row + "first_block must be " + std::to_string(blocks));
         blocks += (d.count + (int64_t)(((uintptr_t)d.w >> 2) & 3) + SSD_UPDATE_BLOCK_ELEMS - 1) / SSD_UPDATE_BLOCK_ELEMS;
-        if (blocks > INT_MAX) return ssd_fail(SSD_ERR_INVALID, "ssd_train_update: more than 2^31 - 1 blocks");
+        if (blocks > INT_MAX) return ssd_fail(SSD_ERR_INVALID, name + ": more than 2^31 - 1 blocks");
     }
+    *blocks_out = blocks;
+    return SSD_OK;
+}
+
+int check_update_table(const char *fn, const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T, int64_t *blocks_out)
+{
+    SSDCHK(check_update_args(fn, tensors_host, tensors_dev, T));
+    return check_update_rows(fn, tensors_host, T, blocks_out);
+}
+
+size_t update_table_bytes(const char *fn, const ssd_update_tensor *tensors_host, int32_t T, size_t block_bytes)
+{
+    int64_t blocks = 0;
+    // the planner sees no device table: any aligned non-NULL address stands in for it
+    if (check_update_table(fn, tensors_host, (const ssd_update_tensor *)(uintptr_t)8, T, &blocks) != SSD_OK) return 0;
+    return (size_t)blocks * block_bytes;
+}
+
+int check_workspace(const char *fn, const void *workspace, size_t workspace_bytes, size_t needs)
+{
+    const std::string name(fn);
+    if (!workspace) return ssd_fail(SSD_ERR_INVALID, name + ": NULL workspace");
+    if ((uintptr_t)workspace & 15) return ssd_fail(SSD_ERR_INVALID, name + ": workspace must be 16-byte aligned");
+    if (workspace_bytes < needs)
+        return ssd_fail(SSD_ERR_INVALID, name + ": workspace too small: " + std::to_string(workspace_bytes) + " bytes, needs " + std::to_string(needs));
+    return SSD_OK;
+}
+
+extern "C" int ssd_train_update(const ssd_update_tensor *tensors_host, const ssd_update_tensor *tensors_dev, int32_t T,
+                                const ssd_update_scalars *scalars, void *stream)
+{
+    SSDCHK(check_update_args("ssd_train_update", tensors_host, tensors_dev, T, scalars != nullptr));
+    const float sc[6] = {scalars->alpha, scalars->one_minus_beta1, scalars->one_minus_beta2, scalars->epsilon, scalars->weight_decay,
+                         scalars->one_minus_decay};
+    for (float x : sc)
+        if (!std::isfinite(x)) return ssd_fail(SSD_ERR_INVALID, "ssd_train_update: non-finite scalar");
+    int64_t blocks = 0;
+    SSDCHK(check_update_rows("ssd_train_update", tensors_host, T, &blocks));
     if (blocks == 0) return SSD_OK;                                   // every tensor is empty
-    const unsigned grid = (unsigned)(blocks < UPD_MAX_GRID ? blocks : UPD_MAX_GRID);
-    hipLaunchKernelGGL(train_update, dim3(grid), dim3(UPD_THREADS), 0, (hipStream_t)stream, tensors_dev, (int)T, (int)blocks, *scalars);
+    hipLaunchKernelGGL(train_update, dim3(grid_for(blocks)), dim3(TBL_THREADS), 0, (hipStream_t)stream, tensors_dev, (int)T, (int)blocks, *scalars);
     HIPCHK(hipGetLastError());
     return SSD_OK;
 }

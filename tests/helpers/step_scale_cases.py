@@ -15,8 +15,8 @@ from helpers import train_reduce_ref as rref
 
 f32, f64 = np.float32, np.float64
 BLOCK = nref.BLOCK                       # SSD_UPDATE_BLOCK_ELEMS
-GRID = 2048                              # NRM_MAX_GRID, HST_MAX_GRID and RED_MAX_GRID: hardware blocks of one pass
-CHUNK = 64                               # NRM_ROW_THREADS and HST_ROW_THREADS: partials stage 2 loads per trip
+GRID = 2048                              # TBL_MAX_GRID of csrc/train_table.h: hardware blocks of one pass
+CHUNK = 64                               # TBL_WAVE: partials stage 2 loads per trip
 WD = 0.5                                 # the histogram tests' weight_decay: g + 0.5 * w lands in other buckets than g
 GIB = 2 ** 30
 MOBILENET = {"backbone": "mobilenet", "depth_multiplier": 1.0, "num_classes": 80}

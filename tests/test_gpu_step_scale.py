@@ -282,7 +282,7 @@ def test_d1_one_rank_without_a_match(cuda, G):
 
 @pytest.mark.parametrize("k", [0, 2])
 def test_d2_a_table_of_many_small_rows(cuda, k):
-    """1 500 rows of 0 .. 9 elements over three blocks: the blocks walk hundreds of rows each, and first_row lands on a run of empty
+    """1 500 rows of 0 .. 9 elements over three blocks: the blocks walk hundreds of rows each, and the row search lands on a run of empty
     rows at bucket float 4096 and inside a row at 8192."""
     counts, kinds, present, _marks = cases.d2_table()
     rng = np.random.default_rng(3000 + k)

@@ -24,11 +24,15 @@ def _last_block_elements(row):
 def test_the_kernels_still_have_the_grid_and_the_chunk_the_cases_assume():
     import os
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "single-shot-detector_amd", "csrc")
-    for name, words in (("train_norms.hip", ("NRM_MAX_GRID = 2048", "NRM_ROW_THREADS = 64")),
-                        ("train_hist.hip", ("HST_MAX_GRID = 2048", "HST_ROW_THREADS = 64")), ("train_reduce.hip", ("RED_MAX_GRID = 2048",))):
+    # the three files take the grid and the chunk from the one header, by these names, and define no grid of their own
+    for name, words in (("train_table.h", ("TBL_MAX_GRID = 2048", "TBL_WAVE = 64", "blocks < TBL_MAX_GRID ? blocks : TBL_MAX_GRID")),
+                        ("train_norms.hip", ('#include "train_table.h"', "grid_for(blocks)", "dim3(TBL_WAVE)", "base += TBL_WAVE")),
+                        ("train_hist.hip", ('#include "train_table.h"', "grid_for(blocks)", "dim3(TBL_WAVE)", "base += TBL_WAVE")),
+                        ("train_reduce.hip", ('#include "train_table.h"', "grid_for(blocks < 1 ? 1 : blocks)"))):
         with open(os.path.join(csrc, name)) as f:
             text = f.read()
         assert all(w in text for w in words), name
+        assert name == "train_table.h" or "MAX_GRID =" not in text, name
     assert (GRID, CHUNK, BLOCK) == (2048, 64, 4096) and cases.passes(2048) == 1 and cases.passes(2049) == 2 and cases.passes(1) == 1
 
 

@@ -151,6 +151,79 @@ def test_ssd_train_update_refuses_bad_arguments_without_a_gpu(ssd):
     assert train_step.block_starts(q["w"], q["count"])[0].tolist() == [0, 2, 3]
 
 
+def test_the_five_table_entry_points_refuse_alike_and_in_one_order(ssd):
+    """ssd_train_update, ssd_train_norms, ssd_train_histograms and the two planners check one table: the same text behind the
+    function's name for a spoilt row, ssd_train_update's order where two faults meet, and no refusal of a table of empty rows."""
+    from ssd_amd import train_step, _lib
+    L = ssd.lib()
+    rows = np.zeros(3, train_step.TENSOR_DTYPE)
+    for c in ("w", "grad", "m", "v", "ema"):
+        rows[c] = 0x10000                       # never dereferenced: every refusal comes before any HIP call
+    rows["count"] = (5000, 10, 4096)
+    rows["decay"] = (1, 0, 0)
+    rows["first_block"] = (0, 2, 3)
+    good = (0.1, 0.1, 0.001, 1e-8, 5e-5, 0.5)
+    fake, out = ctypes.c_void_p(0x20000), ctypes.c_void_p(0x30000)
+
+    def p(r):
+        return r.ctypes.data_as(ctypes.c_void_p) if r is not None else None
+
+    def update(r, T=3, sc=good, dev=fake):
+        s = _lib.SsdUpdateScalars(*sc) if sc is not None else None
+        return L.ssd_train_update(p(r), dev, T, ctypes.byref(s) if s is not None else None, None)
+    entry = {"ssd_train_update": update,
+             "ssd_train_norms": lambda r, T=3: L.ssd_train_norms(p(r), fake, T, out, out, fake, 1 << 20, None),
+             "ssd_train_norms_workspace_bytes": lambda r, T=3: -1 if L.ssd_train_norms_workspace_bytes(p(r), T) == 0 else 0,
+             "ssd_train_histograms": lambda r, T=3: L.ssd_train_histograms(p(r), fake, T, 1e-4, out, out, out, fake, 1 << 20, None),
+             "ssd_train_histograms_workspace_bytes": lambda r, T=3: -1 if L.ssd_train_histograms_workspace_bytes(p(r), T) == 0 else 0}
+    # one bad row at a time through all five: the text behind the function's name is one
+    for t in range(3):
+        for field, value, text in (("count", -1, "bad count"), ("m", 0, "NULL w, m, v or ema"),
+                                   ("w", 0x10002, "w, m, v, ema and grad must be 4-byte aligned"), ("decay", 2, "decay must be 0 or 1"),
+                                   ("first_block", 7, "first_block must be %d" % rows["first_block"][t])):
+            q = rows.copy()
+            q[t][field] = value
+            for name, fn in entry.items():
+                assert fn(q) == -1, (name, t, field)
+                head, _, tail = L.ssd_last_error().decode().partition(": ")
+                assert head == name and tail == "tensor %d: %s" % (t, text), (name, t, field, head, tail)
+    # two faults at once in ssd_train_update: which one wins
+    nan = (float("nan"),) + good[1:]
+    bad = rows.copy()
+    bad[0]["count"] = -1
+    assert update(bad, sc=nan) == -1 and L.ssd_last_error().decode() == "ssd_train_update: non-finite scalar"
+    assert update(rows, T=0, sc=nan) == -1 and L.ssd_last_error().decode() == "ssd_train_update: T must be in [1, 65536]"
+    for kw in ({"r": bad}, {"r": rows, "T": 0}, {"r": rows, "dev": ctypes.c_void_p(0x20004)}, {"r": None}, {"r": rows, "dev": None}):
+        assert update(sc=None, **kw) == -1 and L.ssd_last_error().decode() == "ssd_train_update: bad arguments", kw
+    assert update(rows, dev=ctypes.c_void_p(0x20004), sc=nan) == -1
+    assert L.ssd_last_error().decode() == "ssd_train_update: tensors_dev must be 8-byte aligned"
+    # a table of empty rows only: nothing to refuse, no block, no workspace byte
+    empty = rows.copy()
+    empty["count"], empty["first_block"] = 0, 0
+    assert update(empty) == 0
+    assert L.ssd_train_norms_workspace_bytes(p(empty), 3) == 0 == L.ssd_train_histograms_workspace_bytes(p(empty), 3)
+    # norms and histograms still launch their stage 2 for such a table (it writes the outputs: zeros).  Where there is a GPU they
+    # get real memory and return SSD_OK; where there is none, the launch's error -- not a refusal -- shows that every check passed
+    import torch
+    if not torch.cuda.is_available():
+        for name in ("ssd_train_norms", "ssd_train_histograms"):
+            assert entry[name](empty) == -2 and L.ssd_last_error().decode().startswith("hipGetLastError()"), name
+        return
+    from ssd_amd import train_calls
+    host = torch.from_numpy(empty.view(np.uint8).copy())
+    dev = host.cuda()
+    sums = torch.full((3, 2), float("nan"), dtype=torch.float64, device="cuda")
+    bad = torch.full((3, 2), -1, dtype=torch.int64, device="cuda")
+    train_calls.train_norms(host, dev, sums, bad)                     # raises on any code but SSD_OK
+    assert not sums.cpu().numpy().view(np.int64).any() and not bad.cpu().numpy().any()
+    limits = train_calls.histogram_limits()
+    counts = torch.full((3, 2, len(limits)), -1, dtype=torch.int64, device="cuda")
+    stats = torch.full((3, 2, train_calls.STATS_BYTES), 255, dtype=torch.uint8, device="cuda")
+    train_calls.train_histograms(host, dev, 1e-4, torch.from_numpy(limits.copy()).cuda(), counts, stats)
+    got = stats.cpu().numpy().view(train_calls.STATS_DTYPE)
+    assert not counts.cpu().numpy().any() and not got["num"].any() and not got["bad"].any() and not got["sum"].any()
+
+
 def _weights(ssd, params):
     W = ssd.synthetic_weights(params, seed=3)
     rng = np.random.default_rng(4)
