@@ -58,9 +58,7 @@ def kernel_lines(reps, rounds):
         train_calls.train_grad_pack(host, dev, header, gathered[r])
     losses = torch.empty(2, dtype=torch.float32, device="cuda")
     weights = torch.empty(max(RANKS), dtype=torch.float32, device="cuda")
-    urows = ts._table.copy()
-    urows["grad"] = [p.grad.data_ptr() for p in P.values()]
-    uhost = torch.from_numpy(urows.view(np.uint8).copy())
+    uhost = torch.from_numpy(ts.gradient_rows().view(np.uint8))
     udev = uhost.cuda()
     scalars = train_step.step_scalars(ts.config, 1)
     L = ssd_amd.lib()

@@ -86,8 +86,7 @@ def kernel_lines(t, reps, rounds):
     P = [ts.parameters[n] for n in names]
     assert all(p.grad is not None for p in P)
     T, N = len(names), sum(p.numel() for p in P)
-    rows = ts._table.copy()
-    rows["grad"] = [p.grad.data_ptr() for p in P]
+    rows = ts.gradient_rows()
     host = torch.from_numpy(rows.view(np.uint8).copy())
     dev = host.cuda()
     limits = torch.from_numpy(train_calls.histogram_limits().copy()).cuda()

@@ -43,8 +43,7 @@ def norms_lines(reps, rounds):
     for p in P.values():
         p.grad = torch.randn(p.shape, device="cuda", generator=g) * 1e-3
     T, N = len(names), sum(p.numel() for p in P.values())
-    rows = ts._table.copy()
-    rows["grad"] = [p.grad.data_ptr() for p in P.values()]
+    rows = ts.gradient_rows()
     host = torch.from_numpy(rows.view(np.uint8).copy())
     dev = host.cuda()
     sums = torch.empty((T, 2), dtype=torch.float64, device="cuda")

@@ -57,14 +57,14 @@ def report(what, ms):
 
 step_ms = report("TrainStep.step() (table upload + launch)", timed(ts.step, a.calls))
 # the bare launch: the table of the last step() stays valid (the gradients are not reallocated here)
-slot = ts._ring[(ts._calls - 1) % ts.RING]
+table_host, table_dev = ts._ring.last()
 sc = train_step.step_scalars(CFG, ts.global_step + 1)
 L = ssd_amd.lib()
 stream = torch.cuda.current_stream().cuda_stream
 
 
 def bare():
-    _lib.check(L.ssd_train_update(slot["host"].data_ptr(), slot["dev"].data_ptr(), len(names), ctypes.byref(sc), stream))
+    _lib.check(L.ssd_train_update(table_host.data_ptr(), table_dev.data_ptr(), len(names), ctypes.byref(sc), stream))
 
 
 bare_ms = report("ssd_train_update alone", timed(bare, a.calls))

@@ -10,6 +10,7 @@ import hashlib
 import numpy as np
 
 from . import train_calls
+from .train_step import TableRing
 
 
 def agree_on_table(table, group, device):
@@ -45,10 +46,8 @@ class GradientExchange:
 
     exchange(header) -> (localization_loss, classification_loss, weights): the two losses over the global batch as device scalars
     and the ranks' weights c_r [G]; afterwards every .grad and every statistic holds the reduced value.  One small asynchronous
-    upload from a pinned ring of its own, two launches and one all-gather on the current stream; over 'nccl' it never waits for the
-    device.  Two receive buffers are used alternately."""
-
-    RING = 4
+    upload from a train_step.TableRing of its own, two launches and one all-gather on the current stream; over 'nccl' it never waits
+    for the device.  Two receive buffers are used alternately."""
 
     def __init__(self, train_step, statistics, group=None):
         import torch
@@ -75,35 +74,20 @@ class GradientExchange:
         table["offset"], self.slice_floats = train_calls.bucket_layout(table["count"])
         table["data"][len(params):] = [s.data_ptr() for s in self.statistics.values()]
         self._table = table
-        nbytes = self.T * train_calls.REDUCE_ROW_BYTES
+        self._ring = TableRing(self.device, train_calls.REDUCE_ROW_DTYPE, self.T)
         with torch.cuda.device(self.device):
-            self._ring = []
-            for _ in range(self.RING):
-                host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-                self._ring.append({"host": host, "rows": host.numpy().view(train_calls.REDUCE_ROW_DTYPE),
-                                   "dev": torch.empty(nbytes, dtype=torch.uint8, device=self.device),
-                                   "event": torch.cuda.Event(), "used": False})
             self._bufs = [torch.zeros((self.world, self.slice_floats), dtype=torch.float32, device=self.device) for _ in range(2)]
             if not self.on_device:
                 self._send = torch.zeros(self.slice_floats, dtype=torch.float32).pin_memory()
                 self._recv = [torch.zeros((self.world, self.slice_floats), dtype=torch.float32).pin_memory() for _ in range(2)]
         self._turn = 0
-        self._calls = 0
         self._agreed = False
 
     def _rows(self):
-        """This call's table: the gradients' addresses as they are now."""
-        import torch
-        ts = self.train_step
+        """This call's table: the gradients' addresses as they are now (TrainStep.gradient_rows, with its checks)."""
         table = self._table.copy()
-        for i, name in enumerate(ts.names):
-            p = ts.parameters[name]
-            g = p.grad
-            if g is None:
-                continue
-            if g.dtype != torch.float32 or g.device != self.device or g.shape != p.shape or not g.is_contiguous() or g.data_ptr() % 4:
-                raise ValueError("the gradient of %r must be a contiguous float32 tensor of the parameter's shape and device" % name)
-            table["data"][i] = g.data_ptr()
+        grads = self.train_step.gradient_rows()["grad"]
+        table["data"][:len(grads)] = grads
         return table
 
     def exchange(self, header):
@@ -123,15 +107,9 @@ class GradientExchange:
             self._agreed = True
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
-            slot = self._ring[self._calls % self.RING]
-            if slot["used"]:
-                slot["event"].synchronize()          # the upload that last read this pinned slot (RING calls ago) has run
-            slot["rows"][:] = table
-            slot["dev"].copy_(slot["host"], non_blocking=True)
-            slot["event"].record(stream)
-            slot["used"] = True
+            rows_host, rows_dev = self._ring.upload(table, stream)
             buf = self._bufs[self._turn]
-            train_calls.train_grad_pack(slot["host"], slot["dev"], header, buf[self.rank])
+            train_calls.train_grad_pack(rows_host, rows_dev, header, buf[self.rank])
             if self.on_device:
                 dist.all_gather_into_tensor(buf.view(-1), buf[self.rank], group=self.group)      # in place (RCCL)
             else:
@@ -142,7 +120,6 @@ class GradientExchange:
                 buf.copy_(recv, non_blocking=True)
             losses = torch.empty(2, dtype=torch.float32, device=self.device)
             weights = torch.empty(self.world, dtype=torch.float32, device=self.device)
-            train_calls.train_grad_reduce(slot["host"], slot["dev"], buf, losses, weights)
+            train_calls.train_grad_reduce(rows_host, rows_dev, buf, losses, weights)
         self._turn ^= 1
-        self._calls += 1
         return losses[0], losses[1], weights

@@ -4,23 +4,21 @@
     TrainPipeline -> TrainableShuffleNet -> TrainableFPN -> TrainableBoxPredictor -> differentiable_loss -> backward (HIP)
                   -> TrainStep over the three modules' variables (frozen = Conv1) -> checkpoint -> Detector / evaluation
 
-It mirrors backbone_train.TrainableMobileNet point for point, with the same MODE of this project that is not parity with the
-reference: BY DEFAULT Conv1 stays FROZEN and runs in the engine's inference form (ssd.first_conv on its
-moving statistics, then ssd.maxpool3x3s2); the three stages and Conv5 -- 55 convolutions, each followed by a batch norm, the
-depthwise ones without an activation -- run on batch statistics and all their variables train.  train_first=True trains Conv1 as
-well, the reference's recipe: first_conv_train on uint8 frames or first_conv_train_float on the float32 batches TrainPipeline
-yields, the batch norm + ReLU on batch statistics, maxpool3x3s2_train.
-The ops (first_conv_train, first_conv_train_float, depthwise_conv, pointwise_conv, batch_norm_act, concat_shuffle_split, concat_channels,
-maxpool3x3s2_train) and the variable loading (ReferenceVariables) are train_ops.py's; this file keeps the unit table and the graph.
+The first convolution -- frozen by default or trained, from uint8 or float32 frames -- is backbone_train.TrainableBackbone's, shared
+with TrainableMobileNet, and with it the MODE of this project that is not parity with the reference: BY DEFAULT
+Conv1 stays FROZEN and runs in the engine's inference form (ssd.first_conv on its moving statistics).  This file adds the max pool
+behind Conv1 (ssd.maxpool3x3s2 with Conv1 frozen, maxpool3x3s2_train with train_first=True, the reference's recipe), the channel
+shuffle, and the three stages and Conv5 -- 55 convolutions, each followed by a batch norm, the depthwise ones without an activation --,
+which run on batch statistics with all their variables training.
+The ops (depthwise_conv, pointwise_conv, concat_shuffle_split, concat_channels, maxpool3x3s2_train) are train_ops.py's; this file keeps
+the unit table and the graph.
 """
-import numpy as np
 import torch
 
-from .train_ops import (BATCH_NORM_EPSILON, ReferenceVariables, batch_norm_act, concat_channels, concat_shuffle_split, depthwise_conv,
-                        first_conv_train, first_conv_train_float, maxpool3x3s2_train, pointwise_conv)
+from .backbone_train import TrainableBackbone
+from .train_ops import concat_channels, concat_shuffle_split, depthwise_conv, maxpool3x3s2_train, pointwise_conv
 from .variables import SHUFFLENET_DEPTHS
 
-FIRST = "ShuffleNetV2/Conv1"
 STAGES = ((2, 4), (3, 8), (4, 4))                   # (stage, units): shufflenet_v2.py:56-66
 
 
@@ -34,7 +32,7 @@ def shufflenet_variable_shapes(params):
     return {k: v for k, v in variable_shapes(params).items() if k.startswith("ShuffleNetV2/")}
 
 
-class TrainableShuffleNet(ReferenceVariables):
+class TrainableShuffleNet(TrainableBackbone):
     """shufflenet_v2(images, is_training, depth_multiplier) (shufflenet_v2.py:7-137) as a torch.nn.Module on the HIP kernels, with
     Conv1 frozen by default.
 
@@ -52,90 +50,36 @@ class TrainableShuffleNet(ReferenceVariables):
     place of first_conv_train; with Conv1 frozen the raw float convolution on the frozen kernel, the inference batch norm + ReLU and
     the inference max pool.  On frames u * (1 / 255) every result has the bits of the uint8 frames u."""
 
+    FIRST, BN_LEAF, ACT = "ShuffleNetV2/Conv1", "batch_norm", "relu"
+    SIZE_MULTIPLE, SIZE_MESSAGE = 32, "images: height and width must be multiples of 32 (the network's stride)"
+
     def __init__(self, params, weights, device=None, seed=0, keep_features=False, train_first=False):
         if params.get("backbone") != "shufflenet":
             raise ValueError("TrainableShuffleNet: the config's backbone is %r" % (params.get("backbone"),))
         if float(params["depth_multiplier"]) not in (0.5, 1.0, 1.5):
             raise ValueError("TrainableShuffleNet: depth_multiplier must be 0.5, 1.0 or 1.5 (2.0: Conv5 has 2048 channels, the batch norm "
                              "takes at most 1024)")
-        shapes = shufflenet_variable_shapes(params)
-        self.train_first = bool(train_first)
-        frozen = {}
-        for name, shape in shapes.items():
-            if name.startswith(FIRST + "/") and not self.train_first:
-                a = weights.get(name)
-                if a is None:
-                    raise KeyError("weights has no variable %r" % name)
-                a = np.ascontiguousarray(a, dtype=np.float32)
-                if tuple(a.shape) != tuple(shape):
-                    raise ValueError("variable %r has shape %s, expected %s" % (name, a.shape, tuple(shape)))
-                frozen[name] = a.copy()
-        trained = {k: v for k, v in shapes.items() if self.train_first or not k.startswith(FIRST + "/")}
-        super().__init__(trained, weights, lambda name, shape, rng: None, device, seed)
-        self._frozen = frozen
-        self._frozen_dev = {}
-        self.params = dict(params)
-        self.keep_features = bool(keep_features)
-        self.features, self._feats = {}, {}
-        if self.train_first:
-            return
-        f = self._frozen
-        one = np.float32(1.0)
-        sf = f[FIRST + "/batch_norm/gamma"] * (one / np.sqrt(f[FIRST + "/batch_norm/moving_variance"] + np.float32(BATCH_NORM_EPSILON)))
-        self._first_bn = (f[FIRST + "/batch_norm/moving_mean"], sf.astype(np.float32), f[FIRST + "/batch_norm/beta"])
-
-    def frozen_variables(self):
-        """{reference name: float32 array} of Conv1: its kernel, gamma, beta and moving statistics, untouched by training ({} with
-        train_first)."""
-        return {k: v.copy() for k, v in self._frozen.items()}
-
-    def _frozen_on(self, device):
-        """Conv1's frozen arrays on `device` for the float route: plain tensors, no variables (no gradient, not in named_variables() /
-        statistics()), copied once per device from the arrays frozen_variables() returns."""
-        dev = self._frozen_dev.get(device)
-        if dev is None:
-            dev = self._frozen_dev[device] = {k: torch.from_numpy(v.copy()).to(device) for k, v in self._frozen.items()}
-        return dev
+        super().__init__(shufflenet_variable_shapes(params), params, weights, device, seed, keep_features, train_first)
+        self._feats = {}
 
     def first_conv(self, images):
-        """Conv1 and MaxPool: frames -> pixel values in [-1, 1] -> 3x3 stride 2 -> batch norm -> ReLU -> 3x3 stride-2 max pool, from uint8
-        frames (2u/255 - 1) or from float32 frames in [0, 1] (2x - 1: TrainPipeline's batches; on u * (1 / 255) the bits of the uint8
-        route).  Frozen: the engine's inference form on the moving statistics -- uint8: ssd.first_conv; float32: the raw float
-        convolution on a device copy of the frozen kernel, then the inference batch norm + ReLU, without a gradient -- and the
-        inference max pool.  train_first: the raw convolution with a weight gradient, the batch norm in the module's mode and the max
-        pool with its gradient."""
+        """Conv1 and MaxPool: TrainableBackbone.first_conv (the convolution, its batch norm and ReLU), then the 3x3 stride-2 max
+        pool -- with its gradient with train_first, the inference max pool with Conv1 frozen."""
         from . import ssd
-        if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype in (torch.uint8, torch.float32) and images.dim() == 4
-                and images.shape[3] == 3):
-            raise TypeError("images must be a uint8 or float32 [B,H,W,3] tensor on a GPU")
-        if images.shape[1] % 32 or images.shape[2] % 32:
-            raise ValueError("images: height and width must be multiples of 32 (the network's stride)")
         self._feats = {}
-        first = first_conv_train_float if images.dtype == torch.float32 else first_conv_train
+        x = super().first_conv(images)
         if self.train_first:
-            x = self._bn(first(images, self.variable(FIRST + "/weights")), FIRST)
             self._keep("Conv1", x)
             x = maxpool3x3s2_train(x)
-        elif images.dtype == torch.float32:
-            f = self._frozen_on(images.device)
-            with torch.no_grad():
-                x = batch_norm_act(first(images, f[FIRST + "/weights"]),
-                                   *[f["%s/batch_norm/%s" % (FIRST, leaf)] for leaf in ("gamma", "beta", "moving_mean", "moving_variance")],
-                                   training=False, act="relu")
-            with torch.cuda.device(images.device):
-                x = ssd.maxpool3x3s2(x)
         else:
             with torch.cuda.device(images.device):
-                x = ssd.maxpool3x3s2(ssd.first_conv(images.contiguous(), self._frozen[FIRST + "/weights"], self._first_bn, "relu"))
+                x = ssd.maxpool3x3s2(x)
         self._keep("MaxPool", x)
         return x
 
     def _keep(self, name, x):
         if self.keep_features:
             self._feats[name] = x.detach()
-
-    def _bn(self, x, scope, act="relu"):
-        return self.batch_norm_relu([x], [scope + "/batch_norm"], act=act)[0]
 
     def _conv(self, x, scope):
         x = self._bn(pointwise_conv(x, self.variable("ShuffleNetV2/" + scope + "/weights")), "ShuffleNetV2/" + scope)

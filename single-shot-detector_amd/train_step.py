@@ -82,6 +82,48 @@ def from_tf_layout(name, a):
     return np.ascontiguousarray(a.transpose(2, 3, 0, 1) if "depthwise_weights" in name else a.transpose(3, 2, 0, 1))
 
 
+class TableRing:
+    """RING pinned slots for a table that changes from call to call: each slot is a pinned host buffer (`bytes`: its NumPy view), a
+    device twin and the event of its last upload.  Call k takes slot k mod RING, so a slot is rewritten only after the upload that
+    read it RING calls ago has run; until then nobody waits for the device.
+
+    device, dtype, T   the device of the twins, the NumPy dtype of one row and the number of rows"""
+
+    RING = 4
+
+    def __init__(self, device, dtype, T, slots=RING):
+        import torch
+        self.device = device
+        self.calls = 0
+        self.slots = []
+        with torch.cuda.device(device):
+            for _ in range(slots):
+                host = torch.empty(T * dtype.itemsize, dtype=torch.uint8).pin_memory()
+                self.slots.append({"host": host, "bytes": host.numpy(), "dev": torch.empty(host.numel(), dtype=torch.uint8, device=device),
+                                   "event": torch.cuda.Event()})
+
+    def upload(self, rows, stream=None):
+        """This call's rows (an array of the ring's dtype) into the next slot and, asynchronously on the current stream of the
+        device (`stream`, where the caller holds it already), into its twin -> the slot's (host, dev) tensors for ssd_train_update
+        or train_calls.*.  Waits only for the upload that last read this slot."""
+        slot = self.slots[self.calls % len(self.slots)]
+        if self.calls >= len(self.slots):
+            slot["event"].synchronize()          # the upload that last read this pinned slot (RING calls ago) has run
+        slot["bytes"][:] = rows.view(np.uint8)   # as bytes (another length raises): NumPy copies a structured array field by field
+        slot["dev"].copy_(slot["host"], non_blocking=True)
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self.device)
+        slot["event"].record(stream)
+        self.calls += 1
+        return slot["host"], slot["dev"]
+
+    def last(self):
+        """(host, dev) of the latest upload: valid until RING - 1 further calls."""
+        slot = self.slots[(self.calls - 1) % len(self.slots)]
+        return slot["host"], slot["dev"]
+
+
 class TrainStep:
     """The optimizer state of one model and its update.
 
@@ -100,7 +142,7 @@ class TrainStep:
     layout); m and v start at 0, ema as a copy of the parameter.  `step()` is one kernel launch behind one small asynchronous
     upload and never waits for the device."""
 
-    RING = 4
+    RING = TableRing.RING
 
     def __init__(self, named_parameters, config, statistics=None, layout="torch", params=None, frozen=None):
         import torch
@@ -188,14 +230,8 @@ class TrainStep:
             table["decay"] = [1 if decays(n) else 0 for n in names]
             table["first_block"], self.blocks = block_starts(self._w_ptrs, counts)
             self._table = table
-            nbytes = T * TENSOR_DTYPE.itemsize
-            self._ring = []
-            for _ in range(self.RING):
-                host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-                self._ring.append({"host": host, "rows": host.numpy().view(TENSOR_DTYPE),
-                                   "dev": torch.empty(nbytes, dtype=torch.uint8, device=device),
-                                   "event": torch.cuda.Event(), "used": False})
-        self._calls = 0
+        self._ring = TableRing(device, TENSOR_DTYPE, T)
+        self._norms_ring = self._hist_ring = self._hist_limits = None       # made by the first norms() / histograms()
         _lib.lib()
 
     def _tf_shape(self, name, shape):
@@ -222,6 +258,26 @@ class TrainStep:
         return ema_decay(step)
 
     # ------------------------------------------------------------------ the update
+    def gradient_rows(self):
+        """A copy of the update table (TENSOR_DTYPE rows in `names` order) with `grad` holding the address of every parameter's
+        current .grad, 0 where it is None.  Read on the host at the time of the call: what step(), norms(), histograms() and the
+        gradient exchange upload."""
+        import torch
+        grads = np.zeros(len(self.names), np.uint64)
+        for i, (name, w) in enumerate(zip(self.names, self._w_ptrs.tolist())):
+            p = self.parameters[name]
+            if p.data_ptr() != w:
+                raise RuntimeError("the storage of parameter %r was replaced after TrainStep was built" % name)
+            g = p.grad
+            if g is None:
+                continue
+            if g.dtype != torch.float32 or g.device != self.device or g.shape != p.shape or not g.is_contiguous() or g.data_ptr() % 4:
+                raise ValueError("the gradient of %r must be a contiguous float32 tensor of the parameter's shape and device" % name)
+            grads[i] = g.data_ptr()
+        rows = self._table.view(np.uint8).copy().view(TENSOR_DTYPE)     # as bytes: NumPy copies a structured array field by field
+        rows["grad"] = grads
+        return rows
+
     def step(self):
         """One update from the parameters' current .grad (None: that parameter keeps its value and slots, its average still moves).
         Enqueues on the current stream and returns; global_step is incremented."""
@@ -231,36 +287,14 @@ class TrainStep:
             # would replay this step's values for ever
             raise RuntimeError("TrainStep.step() cannot be captured into a graph: the learning rate, the EMA decay and the gradient "
                                "addresses change from step to step on the host; call it outside the capture")
-        grads = np.zeros(len(self.names), np.uint64)
-        w_now = np.zeros(len(self.names), np.uint64)
-        for i, name in enumerate(self.names):
-            p = self.parameters[name]
-            w_now[i] = p.data_ptr()
-            g = p.grad
-            if g is None:
-                continue
-            if g.dtype != torch.float32 or g.device != self.device or g.shape != p.shape or not g.is_contiguous() or g.data_ptr() % 4:
-                raise ValueError("the gradient of %r must be a contiguous float32 tensor of the parameter's shape and device" % name)
-            grads[i] = g.data_ptr()
-        if not np.array_equal(w_now, self._w_ptrs):
-            raise RuntimeError("the storage of parameter %r was replaced after TrainStep was built"
-                               % self.names[int(np.nonzero(w_now != self._w_ptrs)[0][0])])
-        slot = self._ring[self._calls % self.RING]
-        if slot["used"]:
-            slot["event"].synchronize()          # the upload that last read this pinned slot (RING steps ago) has run
-        rows = slot["rows"]
-        rows[:] = self._table
-        rows["grad"] = grads
+        rows = self.gradient_rows()
         t = self.global_step + 1
         scalars = step_scalars(self.config, t)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
-            slot["dev"].copy_(slot["host"], non_blocking=True)
-            slot["event"].record(stream)
-            slot["used"] = True
-            _lib.check(_lib.lib().ssd_train_update(slot["host"].data_ptr(), slot["dev"].data_ptr(), len(self.names),
-                                                   ctypes.byref(scalars), stream.cuda_stream))
-        self._calls += 1
+            host, dev = self._ring.upload(rows, stream)
+            _lib.check(_lib.lib().ssd_train_update(host.data_ptr(), dev.data_ptr(), len(self.names), ctypes.byref(scalars),
+                                                   stream.cuda_stream))
         self.global_step = t
         return t
 
@@ -269,8 +303,8 @@ class TrainStep:
         """(sums, bad) of the parameters and their current .grad (include/ssd_hip.h, "the TRAIN step's norms"): sums float64 [T,2]
         holds sum w^2 and sum g^2, bad int64 [T,2] the non-finite elements of w and of the gradient, rows in `names` order; a
         parameter whose .grad is None gives 0 and 0.  Called BEFORE step(): the values are of the variables the step computed with.
-        One small asynchronous upload (a ring of its own: step()'s is not touched) and two launches on the current stream; never
-        waits for the device; the results are CUDA tensors of this call."""
+        One small asynchronous upload (a TableRing of its own, made by the first call: step()'s is not touched) and two launches on
+        the current stream; never waits for the device; the results are CUDA tensors of this call."""
         import torch
         from . import train_calls
         if torch.cuda.is_current_stream_capturing():
@@ -278,39 +312,14 @@ class TrainStep:
             raise RuntimeError("TrainStep.norms() cannot be captured into a graph: the gradient addresses change from step to step "
                                "on the host; call it outside the capture")
         T = len(self.names)
-        grads = np.zeros(T, np.uint64)
-        for i, name in enumerate(self.names):
-            p = self.parameters[name]
-            if p.data_ptr() != int(self._w_ptrs[i]):
-                raise RuntimeError("the storage of parameter %r was replaced after TrainStep was built" % name)
-            g = p.grad
-            if g is None:
-                continue
-            if g.dtype != torch.float32 or g.device != self.device or g.shape != p.shape or not g.is_contiguous() or g.data_ptr() % 4:
-                raise ValueError("the gradient of %r must be a contiguous float32 tensor of the parameter's shape and device" % name)
-            grads[i] = g.data_ptr()
+        rows = self.gradient_rows()
         with torch.cuda.device(self.device):
-            if not hasattr(self, "_norms_ring"):
-                nbytes = T * TENSOR_DTYPE.itemsize
-                self._norms_ring, self._norms_calls = [], 0
-                for _ in range(self.RING):
-                    host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-                    self._norms_ring.append({"host": host, "rows": host.numpy().view(TENSOR_DTYPE),
-                                             "dev": torch.empty(nbytes, dtype=torch.uint8, device=self.device),
-                                             "event": torch.cuda.Event(), "used": False})
-            slot = self._norms_ring[self._norms_calls % self.RING]
-            if slot["used"]:
-                slot["event"].synchronize()      # the upload that last read this pinned slot (RING calls ago) has run
-            rows = slot["rows"]
-            rows[:] = self._table
-            rows["grad"] = grads
+            if self._norms_ring is None:
+                self._norms_ring = TableRing(self.device, TENSOR_DTYPE, T)
             sums = torch.empty((T, 2), dtype=torch.float64, device=self.device)
             bad = torch.empty((T, 2), dtype=torch.int64, device=self.device)
-            slot["dev"].copy_(slot["host"], non_blocking=True)
-            slot["event"].record(torch.cuda.current_stream(self.device))
-            slot["used"] = True
-            train_calls.train_norms(slot["host"], slot["dev"], sums, bad)
-        self._norms_calls += 1
+            host, dev = self._norms_ring.upload(rows)
+            train_calls.train_norms(host, dev, sums, bad)
         return sums, bad
 
     # ------------------------------------------------------------------ the histograms
@@ -319,9 +328,9 @@ class TrainStep:
         counts int64 [T,2,NB] over train_calls.histogram_limits(), stats uint8 [T,2,40] (train_calls.STATS_DTYPE on the host), plane
         0 the variable, plane 1 its current .grad plus weight_decay * w where the variable decays; rows in `names` order; a
         parameter whose .grad is None gives an all-zero plane 1 with num = 0.  Called BEFORE step(), like norms(), whose discipline
-        this is: one small asynchronous upload from a pinned ring of its own (step()'s and norms()' are not touched), a fixed
-        number of launches on the current stream, never waits for the device; the results are CUDA tensors of this call.  The
-        limits are uploaded once per TrainStep."""
+        this is: one small asynchronous upload from a TableRing of its own, made by the first call (step()'s and norms()' are not
+        touched), a fixed number of launches on the current stream, never waits for the device; the results are CUDA tensors of
+        this call.  The limits are uploaded once per TrainStep, by the first call."""
         import torch
         from . import train_calls
         if torch.cuda.is_current_stream_capturing():
@@ -329,40 +338,15 @@ class TrainStep:
             raise RuntimeError("TrainStep.histograms() cannot be captured into a graph: the gradient addresses change from step to "
                                "step on the host; call it outside the capture")
         T = len(self.names)
-        grads = np.zeros(T, np.uint64)
-        for i, name in enumerate(self.names):
-            p = self.parameters[name]
-            if p.data_ptr() != int(self._w_ptrs[i]):
-                raise RuntimeError("the storage of parameter %r was replaced after TrainStep was built" % name)
-            g = p.grad
-            if g is None:
-                continue
-            if g.dtype != torch.float32 or g.device != self.device or g.shape != p.shape or not g.is_contiguous() or g.data_ptr() % 4:
-                raise ValueError("the gradient of %r must be a contiguous float32 tensor of the parameter's shape and device" % name)
-            grads[i] = g.data_ptr()
+        rows = self.gradient_rows()
         with torch.cuda.device(self.device):
-            if not hasattr(self, "_hist_ring"):
-                nbytes = T * TENSOR_DTYPE.itemsize
-                self._hist_ring, self._hist_calls = [], 0
-                for _ in range(self.RING):
-                    host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-                    self._hist_ring.append({"host": host, "rows": host.numpy().view(TENSOR_DTYPE),
-                                            "dev": torch.empty(nbytes, dtype=torch.uint8, device=self.device),
-                                            "event": torch.cuda.Event(), "used": False})
+            if self._hist_ring is None:
+                self._hist_ring = TableRing(self.device, TENSOR_DTYPE, T)
                 self._hist_limits = torch.from_numpy(train_calls.histogram_limits().copy()).to(self.device)
-            slot = self._hist_ring[self._hist_calls % self.RING]
-            if slot["used"]:
-                slot["event"].synchronize()      # the upload that last read this pinned slot (RING calls ago) has run
-            rows = slot["rows"]
-            rows[:] = self._table
-            rows["grad"] = grads
             counts = torch.empty((T, 2, self._hist_limits.numel()), dtype=torch.int64, device=self.device)
             stats = torch.empty((T, 2, train_calls.STATS_BYTES), dtype=torch.uint8, device=self.device)
-            slot["dev"].copy_(slot["host"], non_blocking=True)
-            slot["event"].record(torch.cuda.current_stream(self.device))
-            slot["used"] = True
-            train_calls.train_histograms(slot["host"], slot["dev"], np.float32(self.config["weight_decay"]), self._hist_limits, counts, stats)
-        self._hist_calls += 1
+            host, dev = self._hist_ring.upload(rows)
+            train_calls.train_histograms(host, dev, np.float32(self.config["weight_decay"]), self._hist_limits, counts, stats)
         return counts, stats
 
     def regularization_loss(self, sums_host):

@@ -8,7 +8,8 @@ import pytest
 
 from helpers import backbone_train_ref as ref
 from helpers import head_train_ref as href
-from helpers.backbone_train_gpu import dw_backward_raw as _dw_backward_raw
+from helpers.backbone_train_gpu import (dw_backward_raw as _dw_backward_raw, dw_data as _dw_data, dw_exact as _dw_exact,
+                                        loop_closes_through_a_checkpoint)
 from helpers.head_train_gpu import bn_raw, conv_backward, dev as _dev, same_bits
 from conftest import TINY_PARAMS
 
@@ -17,18 +18,8 @@ pytestmark = pytest.mark.gpu
 f32 = np.float32
 f64 = np.float64
 B = 2
-LP = {"gamma": 2.0, "alpha": 0.25}
 SIZES = [(6, 8), (5, 7), (13, 17), (1, 1), (2, 2)]                    # 13 x 17 leaves remainders in every thread's 2 x 4 patch
 WIDTHS = [4, 36, 1024]
-
-
-def _dw_data(rng, h, w, C, stride, integers=False, batch=B):
-    oh, ow = ref.dw_out_hw(h, w, stride)
-    if integers:
-        return (rng.integers(-3, 4, (batch, h, w, C)).astype(f32), rng.integers(-2, 3, (3, 3, C, 1)).astype(f32),
-                rng.integers(-3, 4, (batch, oh, ow, C)).astype(f32))
-    return (rng.normal(0, 1, (batch, h, w, C)).astype(f32), rng.normal(0, 0.5, (3, 3, C, 1)).astype(f32),
-            rng.normal(0, 1, (batch, oh, ow, C)).astype(f32))
 
 
 # ----------------------------------------------------------------------------- 1. the depthwise forward
@@ -63,16 +54,6 @@ def test_depthwise_data_gradient_is_the_oracles_convolution_of_E_bit_for_bit(ssd
 
 
 # ----------------------------------------------------------------------------- 3. the depthwise weight gradient
-def _dw_exact(ssd, cuda, h, w, C, stride, batch, seed):
-    x, k, dy = _dw_data(np.random.default_rng(seed), h, w, C, stride, integers=True, batch=batch)
-    terms = ref.dw_terms(x, dy, stride)
-    assert np.abs(terms).sum(0).max() < 2 ** 24                        # the premise: every partial sum is an exact integer
-    want = terms.sum(0).reshape(3, 3, C, 1)
-    _, dw = _dw_backward_raw(ssd, cuda, x, k, dy, stride, with_dx=False)
-    assert dw.shape == k.shape and np.array_equal(dw.astype(f64), want), (h, w, C, stride)
-    return want
-
-
 @pytest.mark.parametrize("stride", [1, 2])
 @pytest.mark.parametrize("C", WIDTHS)
 def test_depthwise_weight_gradient_is_exact_on_small_integers(ssd, cuda, C, stride):
@@ -442,39 +423,5 @@ def test_fpn_on_features_without_a_gradient_runs_the_frozen_backbone_sequence(ss
 def test_the_loop_closes_through_a_checkpoint(ssd, cuda, tmp_path):
     """images -> TrainableMobileNet -> TrainableFPN -> TrainableBoxPredictor -> differentiable_loss -> backward -> one TrainStep over
     the three modules' variables with Conv2d_0 frozen -> save -> a fresh Detector on that checkpoint."""
-    W = ssd.synthetic_weights(TINY_PARAMS, seed=51, logits_bias=-4.0)
-    img = cuda.from_numpy(np.random.default_rng(52).integers(0, 256, (B, 128, 128, 3), dtype=np.uint8)).cuda()
-    anchors, boxes, labels, num = href.groundtruth(ssd, B, 53)
-    gt = {"boxes": boxes, "labels": labels, "num_boxes": num}
-    backbone = ssd.TrainableMobileNet(TINY_PARAMS, W, device="cuda").train()
-    fpn = ssd.TrainableFPN(TINY_PARAMS, W, device="cuda").train()
-    head = ssd.TrainableBoxPredictor(TINY_PARAMS, W, device="cuda").train()
-    frozen = backbone.frozen_variables()
-    assert len(frozen) == 5 and all(k.startswith("MobilenetV1/Conv2d_0/") for k in frozen)
-    cfg = {"initial_learning_rate": 1e-3, "num_steps": 100, "weight_decay": 1e-4}
-    variables = {**backbone.named_variables(), **fpn.named_variables(), **head.named_variables()}
-    statistics = {**backbone.statistics(), **fpn.statistics(), **head.statistics()}
-    assert len(variables) + len(statistics) + len(frozen) == len(W)
-    ts = ssd.TrainStep(variables, cfg, statistics, layout="tf", params=TINY_PARAMS, frozen=frozen)
-    eb, cp = head(fpn(backbone(img)))
-    out = ssd.differentiable_loss(cp, eb, _dev(cuda, anchors), gt, LP)
-    (out["localization_loss"] + out["classification_loss"]).backward()
-    for name, p in variables.items():
-        assert p.grad is not None and bool(cuda.isfinite(p.grad).all()) and float(p.grad.abs().max()) > 0, name
-    ts.step()
-    ts.save(str(tmp_path))
-    for name, p in backbone.named_variables().items():
-        if name.endswith("weights"):                                    # every backbone kernel has moved
-            assert not np.array_equal(p.detach().cpu().numpy(), W[name]), name
-    saved = ssd.read_checkpoint(ssd.resolve_checkpoint(str(tmp_path)), list(frozen))
-    for k, v in frozen.items():
-        assert same_bits(saved[k], W[k]) and same_bits(v, W[k]), k
-    with cuda.no_grad():
-        cs = backbone.eval()(img)
-        want_c5 = cs[2].cpu().numpy()
-        want_p3 = fpn.eval()(cs)[0].cpu().numpy()
-    det = ssd.Detector(str(tmp_path), config=dict(TINY_PARAMS))
-    det.engine.forward(img)
-    assert np.array_equal(det.engine.get_tensor("c5"), want_c5) and np.abs(want_c5).max() > 0
-    assert np.array_equal(det.engine.get_tensor("p3"), want_p3)
-    det.close()
+    loop_closes_through_a_checkpoint(ssd, cuda, tmp_path, ssd.TrainableMobileNet, TINY_PARAMS, "MobilenetV1/Conv2d_0/", lambda variables: set(),
+                                     "c5")

@@ -9,7 +9,8 @@ import pytest
 from helpers import backbone_train_ref as bref
 from helpers import head_train_ref as href
 from helpers import shufflenet_train_ref as ref
-from helpers.head_train_gpu import dev as _dev, exact_workspace, same_bits
+from helpers.backbone_train_gpu import dw_backward_raw, dw_data as _dw_data, dw_exact, loop_closes_through_a_checkpoint
+from helpers.head_train_gpu import dev as _dev, same_bits
 from helpers.shufflenet_train_gpu import bn_raw as _bn_raw, dw_forward as _dw_forward, pw as _pw
 from conftest import TINY_PARAMS
 
@@ -18,28 +19,8 @@ pytestmark = pytest.mark.gpu
 f32 = np.float32
 f64 = np.float64
 B = 2
-LP = {"gamma": 2.0, "alpha": 0.25}
 SN_PARAMS = dict(TINY_PARAMS, backbone="shufflenet")
 DW_CASES = [(5, 7, 1), (6, 8, 2), (7, 9, 2)]                          # stride 1; stride 2 with pad_beg 0 and with pad_beg 1
-
-
-# ----------------------------------------------------------------------------- the raw calls
-def _dw_backward(ssd, cuda, x, k, dy, stride, entry, with_dx=True):
-    X, K, DY = _dev(cuda, x), _dev(cuda, k), _dev(cuda, dy)
-    DX = cuda.full_like(X, float("nan")) if with_dx else None
-    DW = cuda.full_like(K, float("nan"))
-    ws = exact_workspace(cuda, ssd.train_calls.depthwise_workspace_bytes(X, stride, entry=entry))
-    ssd.train_calls.depthwise_backward(X, K, DY, DW, stride, DX, workspace=ws, entry=entry)
-    return DX.cpu().numpy() if with_dx else None, DW.cpu().numpy()
-
-
-def _dw_data(rng, h, w, C, stride, integers=False, batch=B):
-    oh, ow = bref.dw_out_hw(h, w, stride)
-    if integers:
-        return (rng.integers(-3, 4, (batch, h, w, C)).astype(f32), rng.integers(-2, 3, (3, 3, C, 1)).astype(f32),
-                rng.integers(-3, 4, (batch, oh, ow, C)).astype(f32))
-    return (rng.normal(0, 1, (batch, h, w, C)).astype(f32), rng.normal(0, 0.5, (3, 3, C, 1)).astype(f32),
-            rng.normal(0, 1, (batch, oh, ow, C)).astype(f32))
 
 
 # ----------------------------------------------------------------------------- 1. depthwise
@@ -53,7 +34,7 @@ def test_depthwise_forward_and_data_gradient_bit_for_bit(ssd, cuda, oracle_ops, 
         y = _dw_forward(ssd, cuda, x, k, stride, "sn_depthwise")
         assert same_bits(y, oracle_ops.depthwise3x3(x, k, stride)), (h, w, stride)
         assert same_bits(y, ssd.ssd.depthwise3x3(_dev(cuda, x), k, stride).cpu().numpy()) and np.abs(y).max() > 0
-        dx, _ = _dw_backward(ssd, cuda, x, k, dy, stride, "sn_depthwise")
+        dx, _ = dw_backward_raw(ssd, cuda, x, k, dy, stride, entry="sn_depthwise")
         want = oracle_ops.depthwise3x3(bref.dilate_E(dy, h, w, stride), bref.flip(k), 1)
         assert dx.shape == want.shape and np.array_equal(dx, want) and np.abs(dx).max() > 0, (h, w, stride)
         tx, tk = _dev(cuda, x).requires_grad_(), _dev(cuda, k).requires_grad_()
@@ -62,21 +43,11 @@ def test_depthwise_forward_and_data_gradient_bit_for_bit(ssd, cuda, oracle_ops, 
         assert same_bits(ty.detach().cpu().numpy(), y) and same_bits(tx.grad.cpu().numpy(), dx), (h, w, stride)
 
 
-def _dw_exact(ssd, cuda, h, w, C, stride, batch, seed):
-    x, k, dy = _dw_data(np.random.default_rng(seed), h, w, C, stride, integers=True, batch=batch)
-    terms = bref.dw_terms(x, dy, stride)
-    assert np.abs(terms).sum(0).max() < 2 ** 24                        # the premise: every partial sum is an exact integer
-    want = terms.sum(0).reshape(3, 3, C, 1)
-    _, dw = _dw_backward(ssd, cuda, x, k, dy, stride, "sn_depthwise", with_dx=False)
-    assert dw.shape == k.shape and np.array_equal(dw.astype(f64), want), (h, w, C, stride)
-    return want
-
-
 @pytest.mark.parametrize("C", [6, 58, 8])
 def test_depthwise_weight_gradient_is_exact_on_small_integers(ssd, cuda, C):
     any_nonzero = False
     for h, w, stride in DW_CASES:
-        any_nonzero |= bool(np.abs(_dw_exact(ssd, cuda, h, w, C, stride, B, C + h * w + stride)).max() > 0)
+        any_nonzero |= bool(np.abs(dw_exact(ssd, cuda, h, w, C, stride, B, C + h * w + stride, entry="sn_depthwise")).max() > 0)
     assert any_nonzero
 
 
@@ -84,7 +55,7 @@ def test_depthwise_weight_gradient_is_exact_over_several_slabs_at_58_channels(ss
     """C = 58: G = 15 quads, rpp = 17 row lanes, slabs of 136 rows; 2 x 16 x 16 = 512 rows are four slabs, the last partial."""
     rpp, slab_rows, slabs = bref.slab_plan(2 * 16 * 16, 58)
     assert (rpp, slab_rows, slabs) == (17, 136, 4) and 512 % slab_rows
-    assert np.abs(_dw_exact(ssd, cuda, 16, 16, 58, 1, 2, 99)).max() > 0
+    assert np.abs(dw_exact(ssd, cuda, 16, 16, 58, 1, 2, 99, entry="sn_depthwise")).max() > 0
 
 
 def test_depthwise_at_8_channels_is_the_old_entry_point_bit_for_bit(ssd, cuda):
@@ -92,7 +63,7 @@ def test_depthwise_at_8_channels_is_the_old_entry_point_bit_for_bit(ssd, cuda):
     for h, w, stride in DW_CASES:
         x, k, dy = _dw_data(rng, h, w, 8, stride)
         assert same_bits(_dw_forward(ssd, cuda, x, k, stride, "sn_depthwise"), _dw_forward(ssd, cuda, x, k, stride, "depthwise"))
-        new, old = _dw_backward(ssd, cuda, x, k, dy, stride, "sn_depthwise"), _dw_backward(ssd, cuda, x, k, dy, stride, "depthwise")
+        new, old = dw_backward_raw(ssd, cuda, x, k, dy, stride, entry="sn_depthwise"), dw_backward_raw(ssd, cuda, x, k, dy, stride, entry="depthwise")
         assert same_bits(new[0], old[0]) and same_bits(new[1], old[1]) and np.abs(old[1]).max() > 0
 
 
@@ -480,42 +451,8 @@ def test_gradients_flow_from_the_fpn_into_the_backbone(ssd, cuda):
 def test_the_loop_closes_through_a_checkpoint(ssd, cuda, tmp_path):
     """images -> TrainableShuffleNet -> TrainableFPN -> TrainableBoxPredictor -> differentiable_loss -> backward -> one TrainStep over
     the three modules' variables with Conv1 frozen -> save -> a fresh Detector on that checkpoint."""
-    W = ssd.synthetic_weights(SN_PARAMS, seed=51, logits_bias=-4.0)
-    img = cuda.from_numpy(np.random.default_rng(52).integers(0, 256, (B, 128, 128, 3), dtype=np.uint8)).cuda()
-    anchors, boxes, labels, num = href.groundtruth(ssd, B, 53)
-    gt = {"boxes": boxes, "labels": labels, "num_boxes": num}
-    backbone = ssd.TrainableShuffleNet(SN_PARAMS, W, device="cuda").train()
-    fpn = ssd.TrainableFPN(SN_PARAMS, W, device="cuda").train()
-    head = ssd.TrainableBoxPredictor(SN_PARAMS, W, device="cuda").train()
-    frozen = backbone.frozen_variables()
-    assert len(frozen) == 5 and all(k.startswith("ShuffleNetV2/Conv1/") for k in frozen)
-    cfg = {"initial_learning_rate": 1e-3, "num_steps": 100, "weight_decay": 1e-4}
-    variables = {**backbone.named_variables(), **fpn.named_variables(), **head.named_variables()}
-    statistics = {**backbone.statistics(), **fpn.statistics(), **head.statistics()}
-    assert len(variables) + len(statistics) + len(frozen) == len(W)
-    ts = ssd.TrainStep(variables, cfg, statistics, layout="tf", params=SN_PARAMS, frozen=frozen)
-    eb, cp = head(fpn(backbone(img)))
-    out = ssd.differentiable_loss(cp, eb, _dev(cuda, anchors), gt, LP)
-    (out["localization_loss"] + out["classification_loss"]).backward()
-    dead = ref.dead_betas(variables)                                    # the depthwise batch norms' betas: their gradient is zero
-    assert len(dead) == 19
-    for name, p in variables.items():
-        assert p.grad is not None and bool(cuda.isfinite(p.grad).all()), name
-        assert name in dead or float(p.grad.abs().max()) > 0, name
-    ts.step()
-    ts.save(str(tmp_path))
-    for name, p in backbone.named_variables().items():
-        if name.endswith("weights"):                                    # every backbone kernel has moved
-            assert not np.array_equal(p.detach().cpu().numpy(), W[name]), name
-    saved = ssd.read_checkpoint(ssd.resolve_checkpoint(str(tmp_path)), list(frozen))
-    for k, v in frozen.items():
-        assert same_bits(saved[k], W[k]) and same_bits(v, W[k]), k
-    with cuda.no_grad():
-        cs = backbone.eval()(img)
-        want_c3 = cs[0].cpu().numpy()
-        want_p3 = fpn.eval()(cs)[0].cpu().numpy()
-    det = ssd.Detector(str(tmp_path), config=dict(SN_PARAMS))
-    det.engine.forward(img)
-    assert np.array_equal(det.engine.get_tensor("c3"), want_c3) and np.abs(want_c3).max() > 0
-    assert np.array_equal(det.engine.get_tensor("p3"), want_p3)
-    det.close()
+    def dead_betas(variables):                                          # the depthwise batch norms' betas: their gradient is zero
+        dead = ref.dead_betas(variables)
+        assert len(dead) == 19
+        return dead
+    loop_closes_through_a_checkpoint(ssd, cuda, tmp_path, ssd.TrainableShuffleNet, SN_PARAMS, "ShuffleNetV2/Conv1/", dead_betas, "c3")

@@ -207,7 +207,7 @@ def test_one_shufflenet_iteration_from_the_pipeline(ssd, cuda, tmp_path, monkeyp
     assert len(dead) == 19
     anchors = cuda.from_numpy(ssd.AnchorGenerator()(128, 128)).cuda()
     captured = []
-    _hook_first_conv(monkeypatch, ssd.shufflenet_train, captured)
+    _hook_first_conv(monkeypatch, ssd.backbone_train, captured)      # TrainableBackbone.first_conv looks the op up there
     images, gt = next(pipe)
     off, x = _off_the_byte_grid(images)
     assert off > 0 and int(gt["num_boxes"].min()) >= 1

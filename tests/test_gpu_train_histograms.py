@@ -321,14 +321,15 @@ def test_trainstep_histograms_after_a_real_backward_of_the_head(ssd, cuda):
                                   {"gamma": 2.0, "alpha": 0.25})
     (out["localization_loss"] + out["classification_loss"]).backward()
     ts.parameters[ts.names[3]].grad = None                           # a NULL gradient row
-    rings = [id(s["host"]) for s in ts._ring] + ([id(s["host"]) for s in ts._norms_ring] if hasattr(ts, "_norms_ring") else [])
+    assert ts._hist_ring is None and ts._hist_limits is None         # made by the first call
+    rings = [id(s["host"]) for s in ts._ring.slots] + [id(s["host"]) for s in (ts._norms_ring.slots if ts._norms_ring else [])]
     counts, stats = ts.histograms()
     T, NB = len(ts.names), ref.NB
     assert tuple(counts.shape) == (T, 2, NB) and counts.dtype == cuda.int64 and tuple(stats.shape) == (T, 2, 40) and stats.dtype == cuda.uint8
     limits = ts._hist_limits
     again = ts.histograms()
     assert ts._hist_limits is limits                                 # uploaded once
-    assert not set(id(s["host"]) for s in ts._hist_ring) & set(rings)
+    assert not set(id(s["host"]) for s in ts._hist_ring.slots) & set(rings)
     c, s = counts.cpu().numpy(), _host_stats(stats)
     assert np.array_equal(again[0].cpu().numpy(), c) and _host_stats(again[1]).tobytes() == s.tobytes()
     want = []
@@ -341,6 +342,8 @@ def test_trainstep_histograms_after_a_real_backward_of_the_head(ssd, cuda):
     assert s["num"][3, 1] == 0 and c[3, 1].sum() == 0 and not s["bad"].any()
     sums, _bad = ts.norms()
     assert np.array_equal(np.ascontiguousarray(s["sum_squares"][:, 0]).view(np.int64), sums.cpu().numpy()[:, 0].copy().view(np.int64))
+    pinned = [slot["host"].data_ptr() for ring in (ts._ring, ts._norms_ring, ts._hist_ring) for slot in ring.slots]
+    assert len(set(pinned)) == 3 * ts.RING                           # the three rings are pairwise distinct pinned buffers
     # refused under stream capture, for norms()' reason; the capture around it stays usable
     x = cuda.zeros(8, device="cuda")
     cuda.cuda.synchronize()

@@ -1,8 +1,8 @@
 """ssd_train_norms on the GPU against its numpy restatement (helpers/train_norms_ref.py), bit for bit: tensor sizes around the block
 size at every offset of w inside its 16-byte group, gradients of w's alignment class, of another one and NULL, a table with an empty
 tensor in the middle, values whose sum depends on the order of the additions, NaN and infinities on the ends of a tensor and across a
-block boundary; outputs and workspace pre-filled with NaN bytes behind guard words; and TrainStep.norms() after a real backward of
-the head."""
+block boundary; outputs and workspace pre-filled with NaN bytes behind guard words; TrainStep.norms() after a real backward of the head; and
+norms() and histograms() past one turn of their pinned rings while the stream is still busy."""
 import numpy as np
 import pytest
 
@@ -212,3 +212,40 @@ def test_trainstep_norms_after_a_real_backward_of_the_head(ssd, cuda):
     graph.replay()
     cuda.cuda.synchronize()
     assert x.cpu().numpy().tolist() == [1.0] * 8
+
+
+def test_norms_and_histograms_reuse_every_pinned_slot_while_the_stream_is_busy(ssd, cuda):
+    """RING + 2 calls of norms() and of histograms() back to back, each on a gradient set of its own (all allocated before, all alive:
+    every address is distinct), enqueued behind work that keeps the stream busy, so that the uploads of the first calls have not run
+    when their pinned slots come round again.  One synchronise at the end; call k must report call k's gradients bit for bit (the
+    restatements of helpers/train_norms_ref.py and helpers/histogram_ref.py).  A slot rewritten before its upload ran shows as call k
+    reporting the gradients of call k + RING."""
+    from helpers import histogram_ref
+    from test_gpu_train_histograms import _compare, _host_stats
+    rng = np.random.default_rng(11)
+    sizes = {"a/weights": 5, "b/beta": 64, "c/kernel": 1031}
+    cfg = {"initial_learning_rate": 1e-3, "num_steps": 100, "weight_decay": 0.5}
+    P = {n: cuda.from_numpy(_values(rng, c)).cuda().requires_grad_() for n, c in sizes.items()}
+    ts = ssd.TrainStep(P, cfg, layout="tf")
+    calls = ts.RING + 2
+    host = [[_values(rng, c) for c in sizes.values()] for _ in range(calls)]
+    grads = [[cuda.from_numpy(g).cuda() for g in gs] for gs in host]
+    assert len({g.data_ptr() for gs in grads for g in gs}) == calls * len(sizes)
+    busy = cuda.zeros(1 << 27, device="cuda")
+    cuda.cuda.synchronize()
+    for _ in range(40):
+        busy.add_(1.0)                                               # 1 GiB of traffic each: the stream stays behind the host
+    got = []
+    for gs in grads:
+        for p, g in zip(P.values(), gs):
+            p.grad = g
+        got.append((ts.norms(), ts.histograms()))
+    cuda.cuda.synchronize()
+    w = [(p.detach().cpu().numpy(), (p.data_ptr() // 4) % 4, 1 if ssd.train_step.decays(n) else 0) for n, p in P.items()]
+    assert [d for _w, _o, d in w] == [1, 0, 1]
+    for k, ((sums, bad), (counts, stats)) in enumerate(got):
+        want_s, want_b = ref.table_norms([(x, g, wo) for (x, wo, _d), g in zip(w, host[k])])
+        assert np.array_equal(sums.cpu().numpy().view(np.int64), want_s.view(np.int64)) and np.array_equal(bad.cpu().numpy(), want_b), k
+        want_c, want_st = histogram_ref.table_histograms([(x, g, wo, d) for (x, wo, d), g in zip(w, host[k])], f32(cfg["weight_decay"]))
+        _compare("call %d" % k, counts.cpu().numpy(), _host_stats(stats), want_c, want_st)
+    assert len({sums.cpu().numpy().tobytes() for (sums, _b), _h in got}) == calls      # the calls differ: none stood in for another

@@ -96,7 +96,7 @@ def test_summaries_change_no_bit_and_decode_to_the_restatement(ssd, cuda, data, 
     differ = [k for k in want if not same_bits(got[k], want[k])]
     assert not differ, differ[:5]
     assert _events(ssd, tmp_path / "off") == ([], []) and not os.path.exists(tmp_path / "off" / "eval")
-    assert off._hist_ring is None and not hasattr(off.train_step, "_hist_ring")      # nothing enqueued or allocated
+    assert off._hist_ring is None and off.train_step._hist_ring is None and off.train_step._hist_limits is None   # nothing enqueued or allocated
 
     events, files = _events(ssd, tmp_path / "on")
     assert len(files) == 1 and [step for _w, step, _v in events] == [1, 2, 3]
