@@ -1118,6 +1118,90 @@ int ssd_coco_match(const ssd_coco_cell *cells_host, const ssd_coco_cell *cells_d
                    uint8_t *gt_ignore_dev /* [A,ng], scan order */, double *iou_dev /* nullable: cell-major [D,G], annotation order */,
                    void *stream);
 
+/* ---- the VOC-style metric: coco_eval.Evaluator.evaluate() (train.py's evaluation metric) in two launches ----
+ *
+ * coco_eval.average_precision walks the detections of one label in descending confidence and decides, one after the other, which
+ * are true positives.  Whether a detection is one depends only on the detections and groundtruth boxes of its own (label, image)
+ * and on their relative order; the order over all images is needed only for the cumulative counts.  So: ssd_voc_match decides
+ * every (label, image) cell on its own, ssd_voc_curve walks each label's rows once.  These semantics are coco_eval.py's, read off
+ * its code; this block is their single statement for the two kernels (csrc/voc_match.hip), for tests/helpers/voc_match_ref.py and
+ * for the Python that packs (voc_match.py).
+ *
+ * Rows.  A row is a detection: a label, an image, an insertion index (the order the detections were added in), a float64
+ *   confidence and a float64 box (ymin, xmin, ymax, xmax).  The global order is ascending label, then descending confidence, then
+ *   ascending insertion index (list.sort / the stable argsort(-conf) of every label).  A row's place in it is its `pos`; the rows
+ *   of a label are consecutive.  n_rows < 2^31.
+ * Cells.  A cell is the rows of one (label, image), in global order, with the groundtruth boxes of that label and image in
+ *   insertion order.  The packed arrays hold the cells' rows back to back: cell c owns detections [det_begin, det_begin + D) of
+ *   det_box / det_pos and groundtruth boxes [gt_begin, gt_begin + G) of gt_box; det_pos[i] is the pos of packed detection i.
+ * IoU(d, g): float64, one IEEE operation at a time, no contraction, the division correctly rounded (_iou_matrix of coco_eval.py):
+ *   w = min(d.xmax, g.xmax) - max(d.xmin, g.xmin),  h = min(d.ymax, g.ymax) - max(d.ymin, g.ymin)
+ *   inter = w * h if w > 0 and h > 0, else +0.0
+ *   a_d = (d.xmax - d.xmin) * (d.ymax - d.ymin), a_g alike;  iou = inter / ((a_d + a_g) - inter) if inter > 0, else +0.0
+ *   All inputs are finite and no product overflows (the caller checks finiteness; the calls cannot, they are device memory).
+ * The scan of a cell, for its detections in order:
+ *   best = the FIRST groundtruth box with the maximal IoU (a strict > in insertion order)
+ *   the detection is a true positive iff iou[best] > 0, iou[best] >= thr and best is not taken; it then takes best and records
+ *   iou[best].  A cell with G = 0 has no true positive.
+ *   On the GPU lane l looks at the boxes l + 64 * j in ascending j and keeps its first maximum; the wave takes the exact maximum of
+ *   the 64 lane maxima and, among the lanes that hold it, the smallest box index -- the first maximum of the cell.  Lane l keeps
+ *   `taken` of its boxes as bit j of one 64-bit mask: SSD_VOC_MAX_GT = 64 * 64 boxes per cell; larger cells stay on the host.
+ * The curve of a label over its rows k = 0 .. n - 1 in global order, with num_gt = max(groundtruth boxes of the label, 1):
+ *   ctp_k = true positives among rows 0 .. k (integers);  P_k = double(ctp_k) / double(k + 1),  R_k = double(ctp_k) / double(num_gt)
+ *   best_index = the first k that maximises (P_k * R_k) * (1.0 - |P_k - R_k|); precision, recall = P, R there; best_threshold = the
+ *     confidence of that row
+ *   ap = the sum, from +0.0 in ascending k, of P_k * (R_k - double(ctp_k - 1) / double(num_gt)) for a true positive, +0.0 otherwise
+ *   iou_sum = the sum, in the same order, of the recorded IoUs (+0.0 for the others);  mean_iou = iou_sum / double(max(tp, 1))
+ *   n = 0: every field is 0.
+ *   (R_k - R_(k-1) is exactly that difference for a true positive and 0 otherwise; every term is >= +0.0, so the +0.0 terms and the
+ *   +0.0 a lane past the end contributes change no bit.  The host forms ap with np.sum's pairwise order instead: the two agree
+ *   within rounding, every other field bit for bit.)
+ *
+ * ssd_voc_match: one wave per cell, SSD_VOC_CELLS_PER_BLOCK cells per block of 256 lanes, a grid of at most SSD_VOC_GRID_CAP blocks
+ * striding over the cells.  Writes tp_dev[det_pos[i]] (0 / 1) and tp_iou_dev[det_pos[i]] (the recorded IoU, +0.0 unless a true
+ * positive) for every packed detection i, cells with G = 0 included; an element whose index is not in det_pos is left alone (the
+ * caller's host fallback of an oversize cell lives there), and a det_pos outside [0, n_rows) is never stored through.  With
+ * nd == n_rows and det_pos a permutation every element of both outputs is written.
+ * ssd_voc_curve: one wave per label, the same block and grid shape, over segments {begin, count, num_gt}: the label's rows are
+ * [begin, begin + count) of tp_dev / tp_iou_dev / conf_dev (the confidences in global order).  64 rows at a time: ctp from one
+ * ballot and a running carry, a running first maximum per lane (the final reduction takes the larger value and, of equal values,
+ * the smaller index), the two ordered sums as chains of dependent additions in ascending lane order.  Writes one ssd_voc_result
+ * per label, all 64 bytes.
+ *
+ * Both calls only enqueue one kernel on `stream`: no allocation, no synchronisation, no atomics, no handle; two calls give the same
+ * bits.  cells_host / segments_host are read by the call to refuse bad rows; cells_dev / segments_dev hold the same rows in device
+ * memory (8-byte aligned) -- the caller's upload, ordered before the call on `stream`.  n_cells == 0 / n_labels == 0 enqueues nothing.
+ * SSD_ERR_INVALID before any HIP call, the reason "<fn>: ..." naming the argument:
+ *   ssd_voc_match   n_cells, nd or ng outside [0, 2^40]; n_rows outside [0, 2^31 - 1]; nd > n_rows; a thr that is not finite; NULL cells
+ *                   with n_cells > 0; a NULL array whose count is positive; a pointer not aligned to its element; a cell with D < 0
+ *                   or G outside [0, SSD_VOC_MAX_GT]; detection ranges that do not tile [0, nd) in order (det_begin of the first
+ *                   cell 0, of every other cell the end of the cell before, the last end nd); groundtruth ranges that are not
+ *                   ascending and disjoint or run past ng.
+ *   ssd_voc_curve   n_labels outside [0, 2^24]; n_rows outside [0, 2^31 - 1]; NULL segments or results with n_labels > 0; a NULL array
+ *                   with n_rows > 0; a pointer not aligned to its element; a segment with count < 0, begin < 0, begin + count past
+ *                   n_rows, or num_gt outside [1, 2^40]. */
+#define SSD_VOC_MAX_GT 4096                  /* groundtruth boxes of one cell: 64 lanes x one 64-bit mask      */
+#define SSD_VOC_CELLS_PER_BLOCK 4
+#define SSD_VOC_GRID_CAP 1024                /* blocks; the rest of the cell / label list is grid-strided      */
+typedef struct ssd_voc_cell {                /* 24 bytes, no padding */
+    int64_t det_begin, gt_begin;             /* first row of the cell in the packed detection / groundtruth arrays */
+    int32_t D, G;                            /* detections, groundtruth boxes                                  */
+} ssd_voc_cell;
+typedef struct ssd_voc_segment {             /* 24 bytes: the rows of one label in global order                */
+    int64_t begin, count, num_gt;
+} ssd_voc_segment;
+typedef struct ssd_voc_result {              /* 64 bytes */
+    double ap, precision, recall, best_threshold, mean_iou;
+    int64_t tp, best_index, reserved;        /* reserved: written as 0                                         */
+} ssd_voc_result;
+int ssd_voc_match(const ssd_voc_cell *cells_host, const ssd_voc_cell *cells_dev, int64_t n_cells,
+                  const double *det_box_dev /* [nd,4], cell order */, const int32_t *det_pos_dev /* [nd] */, int64_t nd,
+                  const double *gt_box_dev /* [ng,4] */, int64_t ng, double thr,
+                  uint8_t *tp_dev /* [n_rows], global order */, double *tp_iou_dev /* [n_rows] */, int64_t n_rows, void *stream);
+int ssd_voc_curve(const ssd_voc_segment *segments_host, const ssd_voc_segment *segments_dev, int32_t n_labels,
+                  const uint8_t *tp_dev /* [n_rows] */, const double *tp_iou_dev /* [n_rows] */, const double *conf_dev /* [n_rows] */,
+                  int64_t n_rows, ssd_voc_result *results_dev /* [n_labels] */, void *stream);
+
 /* ---- tiled detection: frames larger than the network's input as overlapping tiles of the network's own size, one merge NMS ----
  *
  * A frame far larger than min_dimension is served by `ssd_forward` only after shrinking it.  Tiled detection runs the network on

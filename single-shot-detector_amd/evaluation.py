@@ -1,7 +1,7 @@
 """train.py's evaluation (train.py:61-65: EvalSpec over the validation shards, model.py:79-104 in mode EVAL) without
 TensorFlow: the validation loss of a checkpoint and the VOC-style AP of metrics.py.
 
-    python -m ssd_amd.evaluation MODEL_PATH --config config.json [--val_dataset DIR] [--use_ema]
+    python -m ssd_amd.evaluation MODEL_PATH --config config.json [--val_dataset DIR] [--use_ema] [--gpu-metric]
 
 EVAL runs at batch 1 (pipeline.py:22-27), so every image is normalised by its OWN matches; `loss` is the mean over
 images of total_loss = localization_loss_weight * localization + classification_loss_weight * classification +
@@ -108,7 +108,7 @@ def image_losses(per_image_row, regularization, loss_config):
     return loc, cls, total_loss(loc, cls, regularization, loss_config)
 
 
-def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, decode=None, group=None, chunk=256):
+def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, decode=None, group=None, chunk=256, metric_device=None):
     """estimator.evaluate of train.py:61-65 for `detector` (a Detector) over `val_dataset` (a directory of .tfrecords
     shards, a shard path, or an iterable of (JPEG bytes | uint8 array, boxes [n,4], labels [n])).  config: the
     reference's JSON (path or dict).  Returns {'loss', 'localization_loss', 'classification_loss',
@@ -119,7 +119,12 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
     iterates the whole record stream (bytes only) and decodes and runs only its own round-robin chunks of `chunk` images
     (distributed.ChunkAssignment); per round one all-gather of one fixed-size row per image (the ssd_loss row, the frame size
     and the predictions) follows, and the means and the Evaluator are fed in dataset order on every rank: every rank
-    returns the one-process dict, float for float."""
+    returns the one-process dict, float for float.
+
+    `metric_device`: None computes the metric with coco_eval.Evaluator's host loop; a CUDA device index or torch.device computes it
+    on that GPU (voc_match.VocEvaluator: two launches over all images; under `group` every rank on the device it names, as every
+    rank runs the host loop): every 'metrics/*' value the same float, except the AP and mAP, whose sums the kernel forms in row
+    order -- equal or the adjacent float32."""
     from concurrent.futures import ThreadPoolExecutor
     from . import tfrecords
     from .distributed import ChunkAssignment
@@ -129,7 +134,11 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
     if decode is None:
         decode = tfrecords.decode_image
     data = tfrecords.read_dataset(val_dataset) if isinstance(val_dataset, (str, os.PathLike)) else val_dataset
-    evaluator = Evaluator(int(eng.params["num_classes"]))
+    if metric_device is None:
+        evaluator = Evaluator(int(eng.params["num_classes"]))
+    else:
+        from .voc_match import VocEvaluator
+        evaluator = VocEvaluator(int(eng.params["num_classes"]))
     run = _Run(eng)
     sums = np.zeros(4, np.float64)
     count = 0
@@ -183,7 +192,7 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
     means = sums / count
     out = {"loss": float(np.float32(means[0])), "localization_loss": float(np.float32(means[1])),
            "classification_loss": float(np.float32(means[2])), "regularization_loss": float(np.float32(means[3]))}
-    m = evaluator.evaluate()
+    m = evaluator.evaluate() if metric_device is None else evaluator.evaluate(device=metric_device)
     if evaluator.num_classes == 1:
         for k in _METRIC_NAMES:
             out["metrics/" + k] = float(np.float32(m[0][k]))
@@ -239,6 +248,8 @@ def main(argv=None):
                     help="processes to shard the images over: N > 1 starts torch.distributed.run with N ranks as a child process "
                          "(rank r on device LOCAL_RANK %% device_count; RCCL only when every rank has a device of its own, else "
                          "gloo); inside such a launch the collective path runs, also at N = 1")
+    ap.add_argument("--gpu-metric", "--gpu_metric", dest="gpu_metric", action="store_true",
+                    help="the AP on the GPU (voc_match.VocEvaluator) instead of coco_eval.Evaluator's host loop")
     a = ap.parse_args(argv)
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -249,7 +260,8 @@ def main(argv=None):
     val = a.val_dataset or json.load(open(a.config))["val_dataset"]
     if "WORLD_SIZE" not in os.environ:
         with Detector(a.model_path, config=a.config, use_ema=a.use_ema) as det:
-            print(json.dumps(evaluate(det, val, a.config, max_batch=a.max_batch), sort_keys=True))
+            print(json.dumps(evaluate(det, val, a.config, max_batch=a.max_batch, metric_device=det.engine.device if a.gpu_metric else None),
+                             sort_keys=True))
         return
     import torch.distributed as dist
     from .distributed import init_node_process_group
@@ -258,7 +270,8 @@ def main(argv=None):
     device, _backend = init_node_process_group()
     try:
         with Detector(a.model_path, config=a.config, use_ema=a.use_ema, visible_device_list=str(device)) as det:
-            res = evaluate(det, val, a.config, max_batch=a.max_batch, group=dist.group.WORLD)
+            res = evaluate(det, val, a.config, max_batch=a.max_batch, group=dist.group.WORLD,
+                           metric_device=det.engine.device if a.gpu_metric else None)
         if dist.get_rank() == 0:
             print(json.dumps(res, sort_keys=True), flush=True)
     finally:

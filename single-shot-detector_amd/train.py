@@ -2,7 +2,7 @@
 
     python -m ssd_amd.train --config config.json [--model_dir DIR] [--max_steps N] [--save_checkpoints_steps N]
                             [--eval_every_steps N] [--log_every N] [--seed S] [--no_eval]
-                            [--save-summary-steps N] [--gpus N]
+                            [--save-summary-steps N] [--gpus N] [--gpu-metric]
 
 One JSON file of the reference drives everything (model_dir, train_dataset, val_dataset, pretrained_checkpoint and the model, loss,
 input and optimizer keys).  A model_dir that holds a checkpoint resumes; otherwise the backbone is warm-started from
@@ -35,6 +35,8 @@ def main(argv=None):
                     help="data-parallel training over N processes: N > 1 starts torch.distributed.run with N ranks as a child process "
                          "(rank r on device LOCAL_RANK %% device_count; RCCL only when every rank has a device of its own, else "
                          "gloo); inside such a launch the exchange runs, also at N = 1")
+    ap.add_argument("--gpu-metric", "--gpu_metric", dest="gpu_metric", action="store_true",
+                    help="every evaluation's AP on the training GPU (voc_match.VocEvaluator) instead of the host loop")
     a = ap.parse_args(argv)
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -51,7 +53,7 @@ def main(argv=None):
                                    log_every=a.log_every, save_summary_steps=a.save_summary_steps,
                                    on_eval=(lambda res: print(json.dumps(res, sort_keys=True), flush=True)) if show else None)
     if "WORLD_SIZE" not in os.environ:
-        run(Trainer(a.config, model_dir=a.model_dir, seed=a.seed), True)
+        run(Trainer(a.config, model_dir=a.model_dir, seed=a.seed, metric_device=0 if a.gpu_metric else None), True)
         return
     import torch.distributed as dist
     from .distributed import init_node_process_group
@@ -59,7 +61,8 @@ def main(argv=None):
         raise SystemExit("--gpus (%d) != WORLD_SIZE (%s)" % (a.gpus, os.environ["WORLD_SIZE"]))
     device, _backend = init_node_process_group()
     try:
-        run(Trainer(a.config, model_dir=a.model_dir, device=device, seed=a.seed, group=dist.group.WORLD), dist.get_rank() == 0)
+        run(Trainer(a.config, model_dir=a.model_dir, device=device, seed=a.seed, group=dist.group.WORLD,
+                    metric_device=device if a.gpu_metric else None), dist.get_rank() == 0)
     finally:
         dist.destroy_process_group()
 

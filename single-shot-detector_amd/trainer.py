@@ -223,6 +223,7 @@ class Trainer:
                     averaged.  Norms, histograms, the non-finite stop and the update see the reduced values, which are the same
                     bits on every rank; only rank 0 writes checkpoints, logs and event files (the matches summaries are rank
                     0's), and a barrier follows every save.  A group of one rank equals group=None bit for bit.
+    metric_device   evaluation.evaluate's: None computes the AP of evaluate() on the host, a device computes it on that GPU
 
     Start state: a checkpoint in model_dir resumes the run (variables, statistics, averages, slots, global_step: TrainStep.restore);
     otherwise the backbone comes from pretrained_checkpoint (warm_start_weights) and fpn/* and the heads are drawn from `seed`.
@@ -233,7 +234,7 @@ class Trainer:
 
     log_every = 100
 
-    def __init__(self, config, model_dir=None, device=0, seed=0, read_workers=None, decode=None, group=None):
+    def __init__(self, config, model_dir=None, device=0, seed=0, read_workers=None, decode=None, group=None, metric_device=None):
         import torch
         from .backbone_train import TrainableMobileNet
         from .fpn_train import TrainableFPN
@@ -256,6 +257,7 @@ class Trainer:
         self.seed = int(seed)
         self.read_workers, self.decode = read_workers, decode
         self.group = group
+        self.metric_device = metric_device
         self.rank, self.world = 0, 1
         if group is not None:
             import torch.distributed as dist
@@ -468,7 +470,7 @@ class Trainer:
         det = Detector(self.model_dir, visible_device_list=str(self.device.index), config=self.config, use_ema=True)
         try:
             res = evaluate(det, self.run_config["val_dataset"], self.config, read_workers=self.read_workers, decode=self.decode,
-                           group=self.group)
+                           group=self.group, metric_device=self.metric_device)
         finally:
             det.close()
         res = dict(res, step=int(self.global_step))
