@@ -1118,6 +1118,67 @@ int ssd_coco_match(const ssd_coco_cell *cells_host, const ssd_coco_cell *cells_d
                    uint8_t *gt_ignore_dev /* [A,ng], scan order */, double *iou_dev /* nullable: cell-major [D,G], annotation order */,
                    void *stream);
 
+/* ---- the COCO accumulation: CocoBoxEval.accumulate() of coco_metric.py for every (category, area range, maxDets) in one launch ----
+ *
+ * accumulate() merges the cells of a category by descending score and reads the precision / recall curves off the cumulative
+ * counts.  These semantics are coco_metric.py's, read off its code; this block is their single statement for the kernel
+ * (csrc/coco_accumulate.hip), for tests/helpers/coco_accumulate_ref.py and for the Python that packs (coco_accumulate.py).
+ *
+ * Rows.  The rows are the packed detections of ssd_coco_match: cells category-major with the image ascending, inside a cell at most
+ *   SSD_COCO_MAX_DET detections in descending score (what coco_match.pack produces).  nd < 2^31.
+ * Segments.  One ssd_coco_segment per category k, in cat_ids order: the category's consecutive rows [det_begin, det_begin +
+ *   det_count) of the detection arrays and [gt_begin, gt_begin + gt_count) of gt_ignore.  A category with no cell has both counts 0.
+ * Row inputs.
+ *   order_dev  int32 [nd]: order[p] is the packed row at global position p.  Global order: ascending category, then descending
+ *              score, then ascending packed row -- the host's stable argsort(-sc, kind="mergesort") over the concatenation in image
+ *              order.  Scores stay on the host, which computes the order (one np.lexsort); positions [det_begin, det_begin +
+ *              det_count) of segment k hold exactly that category's rows.  An element outside [0, nd) is never read through.
+ *   rank_dev   uint8 [nd]: a row's position inside its cell, 0 .. SSD_COCO_MAX_DET - 1.
+ * Matching inputs.  matched_dev / ignored_dev uint16 [A, nd], bit t; gt_ignore_dev uint8 [A, ng]: exactly ssd_coco_match's outputs.
+ * Settings.  max_dets_host int32 [M], positive and ascending; rec_thr_host float64 [R], ascending and finite, the caller's values
+ *   (coco_metric.REC_THRS), never recomputed; rec_thr_dev the same values in device memory.  T <= SSD_COCO_MAX_THR,
+ *   A <= SSD_COCO_MAX_AREA, M <= SSD_COCO_MAX_MAXDETS, R <= SSD_COCO_MAX_REC.
+ * Per (k, a):  npig = the number of zero bytes among the category's gt_ignore[a, ..].  npig == 0: precision[:, :, k, a, :] and
+ *   recall[:, k, a, :] are -1.0.
+ * Per (k, a, m, t) with npig > 0:  the participating rows are the category's rows in global order with rank < max_dets[m], j = 0 .. n - 1.
+ *   tp_j = rows <= j with matched && !ignored,  fp_j = rows <= j with !matched && !ignored  (integers; an ignored row participates
+ *   and changes no count)
+ *   float64, one IEEE operation at a time, every division correctly rounded, eps = 2^-52:
+ *     rc_j = double(tp_j) / double(npig),   pr_j = double(tp_j) / ((double(fp_j) + double(tp_j)) + eps)
+ *   E_j = max(pr_j, .., pr_(n-1))
+ *   recall[t, k, a, m] = rc_(n-1), +0.0 for n == 0
+ *   precision[t, r, k, a, m] = E_pos with pos the first j with rc_j >= rec_thr[r]; +0.0 if there is none, or if n == 0
+ *   rc_j depends on tp_j alone and is monotone in it, so with c_r the smallest integer c >= 0 with
+ *   double(c) / double(npig) >= rec_thr[r], pos is the first j with tp_j >= c_r -- the row where tp steps to c_r -- and row 0 when
+ *   c_r == 0; there is none when c_r > tp_(n-1).  This is the form the kernel uses.  (After a real matching tp_(n-1) <= npig, every
+ *   true positive holding a box of its own, so a c_r above npig never has a row; the kernel does not rely on it.)
+ * Outputs.  precision_dev float64 [T, R, K, A, M], recall_dev float64 [T, K, A, M], the host arrays' C order; every element is written.
+ *
+ * The call only enqueues one kernel on `stream` (256 lanes, one wave per (k, a, m), SSD_COCO_CELLS_PER_BLOCK of them per block, a
+ * grid of at most SSD_COCO_GRID_CAP blocks striding over the list): no allocation, no synchronisation, no atomics, no handle, no
+ * scratch; two calls give the same bits.  segments_host is read by the call to refuse bad rows, segments_dev holds the same rows in
+ * device memory (8-byte aligned) -- the caller's upload, ordered before the call on `stream`.  K == 0 enqueues nothing.
+ * SSD_ERR_INVALID before any HIP call, the reason "ssd_coco_accumulate: ..." naming the argument: a NULL max_dets_host /
+ * rec_thr_host; NULL segments, rec_thr_dev, precision_dev or recall_dev with K > 0; a NULL array whose count (nd or ng) is positive;
+ * a pointer not aligned to its element; T outside [1, SSD_COCO_MAX_THR]; A outside [1, SSD_COCO_MAX_AREA]; M outside
+ * [1, SSD_COCO_MAX_MAXDETS]; R outside [1, SSD_COCO_MAX_REC]; K outside [0, 2^20]; nd outside [0, 2^31 - 1]; ng outside [0, 2^40];
+ * max_dets not positive and ascending; rec_thr not finite and ascending; a segment with a negative count; detection ranges that do
+ * not tile [0, nd) in order (det_begin of the first segment 0, of every other the end of the one before, the last end nd);
+ * groundtruth ranges that are not ascending and disjoint, or that run past ng. */
+#define SSD_COCO_MAX_MAXDETS 4
+#define SSD_COCO_MAX_REC 128
+typedef struct ssd_coco_segment {            /* 32 bytes, no padding: the rows of one category                 */
+    int64_t det_begin, det_count;            /* its positions of order_dev = its rows of the detection arrays  */
+    int64_t gt_begin, gt_count;              /* its elements of every row of gt_ignore_dev                     */
+} ssd_coco_segment;
+int ssd_coco_accumulate(const ssd_coco_segment *segments_host, const ssd_coco_segment *segments_dev, int32_t K,
+                        const int32_t *order_dev /* [nd] */, const uint8_t *rank_dev /* [nd] */,
+                        const uint16_t *matched_dev /* [A,nd], bit t */, const uint16_t *ignored_dev /* [A,nd] */, int64_t nd,
+                        const uint8_t *gt_ignore_dev /* [A,ng] */, int64_t ng, int32_t T, int32_t A,
+                        const int32_t *max_dets_host /* [M] */, int32_t M,
+                        const double *rec_thr_host /* [R] */, const double *rec_thr_dev /* [R] */, int32_t R,
+                        double *precision_dev /* [T,R,K,A,M] */, double *recall_dev /* [T,K,A,M] */, void *stream);
+
 /* ---- the VOC-style metric: coco_eval.Evaluator.evaluate() (train.py's evaluation metric) in two launches ----
  *
  * coco_eval.average_precision walks the detections of one label in descending confidence and decides, one after the other, which

@@ -78,8 +78,10 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     (CocoBoxEval.evaluate(img_ids)); one all-gather of compact arrays (the matching cells, the rows' JSON bytes) follows.  Rank
     0 writes `predictions_json` (byte for byte the one-process file) and the table; every rank returns the same statistics.
 
-    `metric_device`: None runs that matching as coco_metric's host loop; a CUDA device index or torch.device runs it as one launch
-    on that GPU (CocoBoxEval.evaluate(device=)): the same cells bit for bit, so everything behind it is unchanged."""
+    `metric_device`: None runs that matching and the accumulation behind it as coco_metric's host loops; a CUDA device index or
+    torch.device runs each as one launch on that GPU (CocoBoxEval.evaluate(device=, unpack=False), accumulate(device=)): the same
+    cells, precision and recall arrays bit for bit, so the statistics are unchanged.  One process never builds eval_imgs then; with
+    `group` the cells still travel as `cells()`, and every rank accumulates the merged cells on its own `metric_device`."""
     import os
     from . import coco_metric
     from .distributed import ChunkAssignment
@@ -106,7 +108,7 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
         if predictions_json:
             frags.append(json.dumps(rows)[1:-1].encode())      # json.dump of the whole list joins these with ", "
     ev = coco_metric.CocoBoxEval(gt, results)
-    ev.evaluate(img_ids=[m["id"] for m in mine], device=metric_device)
+    ev.evaluate(img_ids=[m["id"] for m in mine], device=metric_device, unpack=False)
     if group is not None:
         # one all-gather of every rank's matching cells and its chunks' JSON; the chunks go back in input order (chunk c of the
         # sorted images is rank c % world's: a round-robin split in chunks of one)
@@ -126,7 +128,7 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     if predictions_json and rank == 0:
         with open(predictions_json, "wb") as f:
             f.write(b"[" + b", ".join(x for x in frags if x) + b"]")
-    return ev.accumulate().summarize(out if rank == 0 else None)
+    return ev.accumulate(device=metric_device).summarize(out if rank == 0 else None)
 
 
 def _read_chunks(metas, images_dir, read_image, workers, chunk):

@@ -1,7 +1,8 @@
 """The GPU path of CocoBoxEval.evaluate (include/ssd_hip.h, "the COCO box matching"): the cells of a run packed
 into flat arrays, one ssd_coco_match launch, the packed bits unpacked into the tuples the host loop makes.
 
-pack() needs numpy alone (the host tests call it); match() uploads, launches on the current stream and downloads."""
+pack() needs numpy alone (the host tests call it); match() uploads, launches on the current stream and downloads; match_device()
+leaves the outputs on the GPU, where ssd_coco_accumulate reads them (coco_accumulate.py)."""
 import ctypes
 
 import numpy as np
@@ -111,13 +112,14 @@ def launch(cells_host, cells_dev, det_box, det_area, nd, gt_box, gt_area, gt_cro
                                    ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
 
 
-def match(p, thr, area_rng, device, want_iou=False, timings=None):
-    """pack()'s arrays through the kernel -> matched, ignored bool [A, T, nd], gt_ignore bool [A, ng] (and the IoU dump float64
-    [sum D * G] with want_iou).  timings: a dict that receives 'upload', 'launch' (HIP events) and 'download' in seconds."""
+def match_device(p, thr, area_rng, device, want_iou=False, timings=None):
+    """pack()'s arrays through the kernel, the outputs left on the GPU -> matched, ignored torch uint8 [A, nd, 2] (the uint16 words'
+    bytes), gt_ignore torch uint8 [A, ng], the IoU dump float64 [sum D * G] or None.  The launch is enqueued on the current stream;
+    nothing waits for it unless timings is given: a dict that receives 'upload' and 'launch' (HIP events) in seconds."""
     import time
     import torch
     dev = _device(device)
-    T, A = len(thr), len(area_rng)
+    A = len(area_rng)
     nd, ng = len(p["det_area"]), len(p["gt_area"])
     t0 = time.perf_counter()
     with torch.cuda.device(dev):
@@ -138,14 +140,29 @@ def match(p, thr, area_rng, device, want_iou=False, timings=None):
         if timings is not None:
             e1.record()
             e1.synchronize()
-            t2 = time.perf_counter()
-        m = matched.cpu().numpy().view(np.uint16).reshape(A, nd)
-        i = ignored.cpu().numpy().view(np.uint16).reshape(A, nd)
-        g = gt_ignore.cpu().numpy()
-        dump = iou.cpu().numpy() if want_iou else None
-        if timings is not None:
-            timings.update(upload=t1 - t0, launch=e0.elapsed_time(e1) * 1e-3, download=time.perf_counter() - t2)
-    out = unpack_bits(m, T), unpack_bits(i, T), g.astype(bool)
+            timings.update(upload=t1 - t0, launch=e0.elapsed_time(e1) * 1e-3)
+    return matched, ignored, gt_ignore, iou
+
+
+def download_words(matched, ignored, gt_ignore):
+    """match_device()'s tensors on the host -> matched, ignored uint16 [A, nd] (bit t), gt_ignore uint8 [A, ng]"""
+    A, nd = matched.shape[0], matched.shape[1]
+    m = matched.cpu().numpy().view(np.uint16).reshape(A, nd)
+    i = ignored.cpu().numpy().view(np.uint16).reshape(A, nd)
+    return m, i, gt_ignore.cpu().numpy()
+
+
+def match(p, thr, area_rng, device, want_iou=False, timings=None):
+    """pack()'s arrays through the kernel -> matched, ignored bool [A, T, nd], gt_ignore bool [A, ng] (and the IoU dump float64
+    [sum D * G] with want_iou).  timings: a dict that receives 'upload', 'launch' (HIP events) and 'download' in seconds."""
+    import time
+    matched, ignored, gt_ignore, iou = match_device(p, thr, area_rng, device, want_iou, timings)
+    t2 = time.perf_counter()
+    m, i, g = download_words(matched, ignored, gt_ignore)
+    dump = iou.cpu().numpy() if want_iou else None
+    if timings is not None:
+        timings.update(download=time.perf_counter() - t2)
+    out = unpack_bits(m, len(thr)), unpack_bits(i, len(thr)), g.astype(bool)
     return out + (dump,) if want_iou else out
 
 

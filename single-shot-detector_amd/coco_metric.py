@@ -72,17 +72,31 @@ class CocoBoxEval:
             if d["image_id"] in imgs and d["category_id"] in cats:
                 bb = list(d["bbox"])
                 self._dts.setdefault((d["image_id"], d["category_id"]), []).append((bb, float(bb[2] * bb[3]), float(d["score"])))
+        self._retained = None
         self.eval_imgs = None
         self.precision = self.recall = self.stats = None
 
+    def __getattr__(self, name):
+        """eval_imgs is a plain attribute: {(category, area index, image): (scores, matched, ignored, gt_ignore)}.  Only after
+        evaluate(device, unpack=False) is it absent -- the cells then exist as the packed arrays on the host and the matching's
+        outputs on the GPU -- and its first read, which lands here, builds it."""
+        if name == "eval_imgs" and self.__dict__.get("_retained") is not None:
+            self._unpack_retained()
+            return self.__dict__["eval_imgs"]
+        raise AttributeError(name)
+
     # -- cocoeval.py evaluate(): computeIoU + evaluateImg for every (category, area range, image)
-    def evaluate(self, img_ids=None, device=None):
+    def evaluate(self, img_ids=None, device=None, unpack=True):
         """img_ids: evaluate only these images (a subset of self.img_ids, e.g. one rank's share); the cells of the others come
         from `merge`.  accumulate() / summarize() always run over all self.img_ids.
         device: None runs the host loop; a CUDA device index or torch.device runs the matching of all cells as one launch of
         ssd_coco_match (coco_match.py; include/ssd_hip.h "the COCO box matching") on that GPU's current stream -- the same
         eval_imgs, key for key and bit for bit.  A cell with more groundtruth boxes than the kernel takes is computed by the
-        host loop in its place."""
+        host loop in its place.
+        unpack (with a device): False keeps the packed arrays on the host and the matching's outputs on the GPU, where
+        accumulate(device=) reads them, and builds no eval_imgs; cells(), merge(), accumulate() or a read of eval_imgs builds
+        it on demand, equal to what unpack=True gives."""
+        self._retained = None
         self.eval_imgs = {}
         if img_ids is None:
             subset = self.img_ids
@@ -92,7 +106,7 @@ class CocoBoxEval:
                 raise ValueError("img_ids must be a subset of the evaluated image ids")
             subset = [i for i in self.img_ids if i in want]
         if device is not None:
-            return self._evaluate_on_gpu(subset, device)
+            return self._evaluate_on_gpu(subset, device, unpack=unpack)
         for cat in self.cat_ids:
             for img in subset:
                 gts = self._gts.get((img, cat), [])
@@ -158,31 +172,54 @@ class CocoBoxEval:
             out.append((dscore, dtm, dtig, gig_s))
         return out
 
-    def _evaluate_on_gpu(self, subset, device, timings=None):
-        """evaluate()'s cells of `subset` through coco_match: pack, one launch, unpack; eval_imgs in the host loop's order."""
+    def _evaluate_on_gpu(self, subset, device, timings=None, unpack=True):
+        """evaluate()'s cells of `subset` through coco_match: pack, one launch, unpack; eval_imgs in the host loop's order.
+        unpack=False: pack and one launch; the outputs stay on the GPU (self._retained)."""
         import time
         from . import coco_match
+        self._retained = None
         t0 = time.perf_counter()
         p = coco_match.pack(self._gts, self._dts, self.cat_ids, subset)
         t1 = time.perf_counter()
+        if not unpack:
+            matched, ignored, gt_ignore, _ = coco_match.match_device(p, THR_L, AREA_RNG, device, timings=timings)
+            self._retained = {"p": p, "matched": matched, "ignored": ignored, "gt_ignore": gt_ignore,
+                              "whole": bool(p["packed"].all()) and list(subset) == list(self.img_ids)}
+            del self.eval_imgs             # (__getattr__ builds it on the first read)
+            if timings is not None:
+                timings.update(pack=t1 - t0)
+            return self
         matched, ignored, gt_ignore = coco_match.match(p, THR_L, AREA_RNG, device, timings=timings)
         t2 = time.perf_counter()
+        self._unpack(p, matched, ignored, gt_ignore)
+        if timings is not None:
+            timings.update(pack=t1 - t0, unpack=time.perf_counter() - t2)
+        return self
+
+    def _unpack_retained(self):
+        """eval_imgs from what evaluate(device, unpack=False) kept: the download and the unpacking it skipped"""
+        from . import coco_match
+        r = self._retained
+        m, i, g = coco_match.download_words(r["matched"], r["ignored"], r["gt_ignore"])
+        self.eval_imgs = r["built"] = {}       # (accumulate(device) trusts the GPU's arrays only while eval_imgs is this very dict)
+        self._unpack(r["p"], coco_match.unpack_bits(m, len(THR_L)), coco_match.unpack_bits(i, len(THR_L)), g.astype(bool))
+
+    def _unpack(self, p, matched, ignored, gt_ignore):
+        """pack()'s dict and the matching's outputs (bool [A, T, nd], [A, T, nd], [A, ng]) -> eval_imgs, the host loop's tuples in its order"""
         cells, score = p["cells"], p["det_score"]
         d0, dn, g0, gn = cells["det_begin"].tolist(), cells["D"].tolist(), cells["gt_begin"].tolist(), cells["G"].tolist()
+        out = self.eval_imgs
         n = 0
         for (cat, img), packed in zip(p["keys"], p["packed"].tolist()):
             if not packed:             # more groundtruth boxes than the kernel takes: the host loop, in its place
                 for ai, cell in enumerate(self._evaluate_cell(self._gts.get((img, cat), []), self._dts.get((img, cat), []))):
-                    self.eval_imgs[(cat, ai, img)] = cell
+                    out[(cat, ai, img)] = cell
                 continue
             a, b, c, d = d0[n], d0[n] + dn[n], g0[n], g0[n] + gn[n]
             n += 1
             s = score[a:b]
             for ai in range(len(AREA_RNG)):
-                self.eval_imgs[(cat, ai, img)] = (s, matched[ai, :, a:b], ignored[ai, :, a:b], gt_ignore[ai, c:d])
-        if timings is not None:
-            timings.update(pack=t1 - t0, unpack=time.perf_counter() - t2)
-        return self
+                out[(cat, ai, img)] = (s, matched[ai, :, a:b], ignored[ai, :, a:b], gt_ignore[ai, c:d])
 
     # -- the cells of evaluate() as a few flat arrays (a subset's evaluation travels between processes this way)
     def cells(self):
@@ -204,6 +241,7 @@ class CocoBoxEval:
         """Adds the cells another subset's evaluate() produced (the dict of `cells()`); the subsets must be disjoint."""
         if self.eval_imgs is None:
             self.eval_imgs = {}
+        self._retained = None              # what a GPU holds no longer is all of eval_imgs
         d0 = np.concatenate([[0], np.cumsum(cells["D"])])
         g0 = np.concatenate([[0], np.cumsum(cells["G"])])
         for n, key in enumerate(cells["keys"].tolist()):
@@ -217,7 +255,15 @@ class CocoBoxEval:
         return self
 
     # -- cocoeval.py accumulate()
-    def accumulate(self):
+    def accumulate(self, device=None):
+        """device: None runs the host loops below; a CUDA device index or torch.device computes the same precision and recall
+        arrays, bit for bit, as one launch of ssd_coco_accumulate (coco_accumulate.py; include/ssd_hip.h "the COCO accumulation")
+        on that GPU's current stream.  It reads the matching's outputs where evaluate(device, unpack=False) left them if that call
+        covered every image on this GPU without a host-fallback cell (the two calls are ordered by that GPU's current stream: make
+        them under the same one); any other eval_imgs -- the host loop's, merged subsets, a fallback cell -- is flattened on the
+        host and uploaded."""
+        if device is not None:
+            return self._accumulate_on_gpu(device)
         if self.eval_imgs is None:
             self.evaluate()
         T, R, K, A, M = len(IOU_THRS), len(REC_THRS), len(self.cat_ids), len(AREA_RNG), len(MAX_DETS)
@@ -253,6 +299,30 @@ class CocoBoxEval:
                         q[ok] = pr[pos[ok]]
                         precision[t, :, k, a, m] = q
         self.precision, self.recall = precision, recall
+        return self
+
+    def _accumulate_on_gpu(self, device, timings=None):
+        """accumulate() through coco_accumulate: the global order by one lexsort, one launch, the two arrays read back.
+        timings: a dict that receives 'route' ('retained' | 'upload'), 'pack_order' and accumulate()'s parts in seconds."""
+        import time
+        from . import coco_accumulate as ca
+        T, A = len(IOU_THRS), len(AREA_RNG)
+        t0 = time.perf_counter()
+        r = self._retained
+        if r is not None and self.__dict__.get("eval_imgs", r.get("built")) is not r.get("built"):
+            r = self._retained = None          # the caller replaced eval_imgs: what the GPU holds is not it
+        if r is not None and r["whole"] and r["matched"].device == ca._device(device):
+            q = ca.pack_order(r["p"], self.cat_ids)
+            matched, ignored, gt_ignore = r["matched"], r["ignored"], r["gt_ignore"]
+        else:
+            if self.eval_imgs is None:
+                self.evaluate()
+            q = ca.pack_cells(self.cells(), self.cat_ids, self.img_ids, A)
+            matched, ignored, gt_ignore = q["matched"], q["ignored"], q["gt_ignore"]
+        t1 = time.perf_counter()
+        self.precision, self.recall = ca.accumulate(q, matched, ignored, gt_ignore, T, A, MAX_DETS, REC_THRS, device, timings=timings)
+        if timings is not None:
+            timings.update(route="retained" if matched is not q.get("matched") else "upload", pack_order=t1 - t0)
         return self
 
     # -- cocoeval.py summarize()
