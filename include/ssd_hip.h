@@ -1179,6 +1179,60 @@ int ssd_coco_accumulate(const ssd_coco_segment *segments_host, const ssd_coco_se
                         const double *rec_thr_host /* [R] */, const double *rec_thr_dev /* [R] */, int32_t R,
                         double *precision_dev /* [T,R,K,A,M] */, double *recall_dev /* [T,K,A,M] */, void *stream);
 
+/* ---- the COCO rows: the detections of ssd_coco_match built from the engine's record blocks, for every image in two launches ----
+ *
+ * The dict route turns a record into ssd_coco_match's rows in four host steps: ssd.score_filter, coco_eval.detection_records,
+ * CocoBoxEval.__init__ and coco_match.pack.  These two calls are those four steps for all images at once; the semantics are that
+ * Python's, read off its code; this block is their single statement for the kernel (csrc/coco_rows.hip) and for
+ * coco_rows.rows_host, the same function in numpy.
+ *
+ * Records.  records_dev holds n_images records of ssd_record_words() = 6T + 1 32-bit words each, back to back:
+ *   boxes [T,4] f32 (ymin, xmin, ymax, xmax, normalised) | scores [T] f32 | labels [T] i32 | num_boxes i32.
+ *   Image i is record i, row i of image_hw_dev and column i of the [K, n_images] tables; the caller orders the images by ascending
+ *   id, so a flattened [K, n_images] table is in coco_match.pack's cell order (category ascending, then image ascending).
+ *   image_hw_dev int32 [n_images, 2]: height, width of the ORIGINAL image (positive; float(height) is what the boxes are scaled by).
+ *   label_to_cat_dev int32 [num_labels]: the index of the label's category in cat_ids, or -1 for a category that is not evaluated
+ *   (a value outside [-1, K) counts as -1).
+ * Row semantics.  Only rows j < num_boxes exist; the words behind them are never read into a result.  In float32, every operation
+ *   rounded on its own (no fused multiply-add):
+ *     kept     score > (float)score_threshold                       (strict; what numpy does for scores[:n] > 0.15)
+ *     py0 = ymin * H, px0 = xmin * W, py1 = ymax * H, px1 = xmax * W      (H = (float)height, W = (float)width)
+ *     x = trunc(px0), y = trunc(py0), w = trunc(px1 - px0), h = trunc(py1 - py0)     (toward zero)
+ *   and then x, y, w, h as float64, area = (double)((int64)w * (int64)h), score = (double)score.
+ *   k = label_to_cat[label]; a kept row with k == -1 is dropped.
+ *   A row is BAD if its score is not finite, or if it is kept and its label lies outside [0, num_labels) or one of its four products
+ *   is not below 2^30 in magnitude (a NaN, an infinity, or a box no image holds).  A bad row is dropped.
+ *   bad[i] = the lowest bad row of image i, or -1; T if num_boxes lies outside [0, T] (the image then has no rows).  The caller
+ *   raises on bad[i] != -1 -- the role coco_match._finite plays on the dict route -- so rows of such an image may hold anything.
+ * Order within a cell.  The rows of one (category, image) cell are ordered by descending score, ties by ascending record row; the
+ *   first SSD_COCO_MAX_DET are kept.  rank(j) = #{j' kept, same category : s' > s or (s' == s and j' < j)}.
+ * ssd_coco_rows_count writes counts[k, i] = min(rows of the cell, SSD_COCO_MAX_DET) for every k, zeros included, and bad[i].
+ * ssd_coco_rows_fill recomputes the ranks and writes the row of rank r < SSD_COCO_MAX_DET at det_begin[k, i] + r of det_box_dev
+ *   (xywh), det_area_dev and det_score_dev; det_begin is the exclusive scan of the flattened counts, nd its total.  A position
+ *   outside [0, nd) is not written; rows of no cell are left alone.
+ *
+ * Each call only enqueues one kernel on `stream` (256 lanes, one wave per image, SSD_COCO_CELLS_PER_BLOCK images per block, a grid
+ * of at most SSD_COCO_GRID_CAP blocks striding over the images, 32 * T bytes of LDS per block): no allocation, no synchronisation,
+ * no atomics, no handle; two calls give the same bits.  The 32-byte box row is stored as two 16-byte stores when det_box_dev is
+ * 16-byte aligned, else as four 8-byte stores.  n_images == 0 enqueues nothing, and neither does a fill with nd == 0.
+ * SSD_ERR_INVALID before any HIP call, the reason "ssd_coco_rows_count: ..." / "ssd_coco_rows_fill: ..." naming the argument:
+ * n_images outside [0, 2^31 - 1]; T outside [1, SSD_COCO_ROWS_MAX_T]; K outside [1, 2^20]; K * n_images > 2^31 - 1; num_labels
+ * outside [1, 2^20]; a score_threshold that is not finite; nd outside [0, 2^31 - 1]; with n_images > 0 a NULL records_dev,
+ * image_hw_dev, label_to_cat_dev, counts_dev, bad_dev or det_begin_dev, and with nd > 0 too a NULL det_box_dev, det_area_dev or
+ * det_score_dev; a pointer not aligned to its element (4 bytes, 8 for det_begin_dev and the three row arrays). */
+#define SSD_COCO_ROWS_MAX_T 2048             /* rows of one record: two words of LDS per row and wave, 64 KB per block; the    */
+                                             /* reference's configs have T = 80 classes * 25 boxes = 2000                     */
+int ssd_coco_rows_count(const int32_t *records_dev, int64_t n_images, int32_t T,
+                        const int32_t *image_hw_dev /* [n_images,2] */, const int32_t *label_to_cat_dev /* [num_labels] */,
+                        int32_t num_labels, int32_t K, float score_threshold,
+                        int32_t *counts_dev /* [K,n_images] */, int32_t *bad_dev /* [n_images] */, void *stream);
+int ssd_coco_rows_fill(const int32_t *records_dev, int64_t n_images, int32_t T,
+                       const int32_t *image_hw_dev /* [n_images,2] */, const int32_t *label_to_cat_dev /* [num_labels] */,
+                       int32_t num_labels, int32_t K, float score_threshold,
+                       const int64_t *det_begin_dev /* [K,n_images] */, int64_t nd,
+                       double *det_box_dev /* [nd,4] xywh */, double *det_area_dev /* [nd] */, double *det_score_dev /* [nd] */,
+                       void *stream);
+
 /* ---- the VOC-style metric: coco_eval.Evaluator.evaluate() (train.py's evaluation metric) in two launches ----
  *
  * coco_eval.average_precision walks the detections of one label in descending confidence and decides, one after the other, which

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "logit_screen.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
             "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip", "train_head.hip", "wgrad.hip", "train_backbone.hip", "train_shufflenet.hip",
-            "train_first_f32.hip", "train_norms.hip", "train_hist.hip", "train_reduce.hip", "coco_match.hip", "coco_accumulate.hip", "voc_match.hip", "tiles.hip"]
+            "train_first_f32.hip", "train_norms.hip", "train_hist.hip", "train_reduce.hip", "coco_match.hip", "coco_accumulate.hip", "coco_rows.hip", "voc_match.hip", "tiles.hip"]
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
 _lib = None
@@ -267,6 +267,8 @@ SIGNATURES = {
                                       ctypes.POINTER(ctypes.c_double), _i, ctypes.POINTER(ctypes.c_double), _i, _vp, _vp, _vp, _vp, _vp]),
     "ssd_coco_accumulate": (ctypes.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i, _i, _i32p, _i,
                                            ctypes.POINTER(ctypes.c_double), _vp, _i, _vp, _vp, _vp]),
+    "ssd_coco_rows_count": (ctypes.c_int, [_vp, ctypes.c_int64, _i, _vp, _vp, _i, _i, ctypes.c_float, _vp, _vp, _vp]),
+    "ssd_coco_rows_fill": (ctypes.c_int, [_vp, ctypes.c_int64, _i, _vp, _vp, _i, _i, ctypes.c_float, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     "ssd_voc_match": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_double, _vp, _vp,
                                      ctypes.c_int64, _vp]),
     "ssd_voc_curve": (ctypes.c_int, [_vp, _vp, _i, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp]),

@@ -61,7 +61,7 @@ def detection_records_many(detector, images, image_ids, label_to_coco_id, score_
 
 
 def evaluate(detector, annotations_json, images_dir, read_image=None, predictions_json="coco_predictions.json", out=None,
-             score_threshold=0.15, max_batch=32, read_workers=None, group=None, chunk=256, metric_device=None):
+             score_threshold=0.15, max_batch=32, read_workers=None, group=None, chunk=256, metric_device=None, rows_device=None):
     """Cells 4-17 end to end: every image of the annotation file through the detector (score_threshold 0.15, cell 10), the
     results written as `predictions_json` (cell 11), then the twelve COCO box statistics (cell 17: COCOeval over all image and
     category ids) -- computed by coco_metric.py, this build's restatement of pycocotools' COCOeval (not installed here, not
@@ -81,7 +81,14 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     `metric_device`: None runs that matching and the accumulation behind it as coco_metric's host loops; a CUDA device index or
     torch.device runs each as one launch on that GPU (CocoBoxEval.evaluate(device=, unpack=False), accumulate(device=)): the same
     cells, precision and recall arrays bit for bit, so the statistics are unchanged.  One process never builds eval_imgs then; with
-    `group` the cells still travel as `cells()`, and every rank accumulates the merged cells on its own `metric_device`."""
+    `group` the cells still travel as `cells()`, and every rank accumulates the merged cells on its own `metric_device`.
+
+    `rows_device`: None builds the result dicts as above; a CUDA device index or torch.device -- the detector's GPU; `metric_device`
+    must be None or the same device (ValueError) and is taken to be it -- never builds them: the detector leaves every image's
+    record on that GPU (Detector.detect_many_records), the metric's rows are built there from the records
+    (CocoBoxEval.from_records; include/ssd_hip.h "the COCO rows") and matched and accumulated there, and the predictions file is
+    formatted from the downloaded records per chunk (coco_rows.write_predictions).  The same statistics and the same file, byte for
+    byte.  With `group` every rank builds the rows of its own images; the cells travel as before."""
     import os
     from . import coco_metric
     from .distributed import ChunkAssignment
@@ -100,6 +107,14 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
         import torch.distributed as dist
         world, rank = dist.get_world_size(group), dist.get_rank(group)
     mine = [m for _i, m in ChunkAssignment(world, rank, chunk).select(metas)]
+    if rows_device is not None:
+        from .coco_match import _device
+        dev = _device(rows_device)
+        if metric_device is not None and _device(metric_device) != dev:
+            raise ValueError("metric_device must be None or rows_device (%s): the rows are matched where they are built" % dev)
+        ev, frags = _evaluate_records(detector, gt, mine, images_dir, read_image, workers, chunk, mapping, score_threshold, max_batch,
+                                      dev, bool(predictions_json))
+        return _finish(ev, frags, metas, chunk, group, world, rank, predictions_json, out, dev)
     results, frags = [], []
     for part, images in _read_chunks(mine, images_dir, read_image, workers, chunk):
         # images read, then detected as batches grouped by network shape (the notebook's loop, one image per sess.run, at batch throughput)
@@ -109,7 +124,35 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
             frags.append(json.dumps(rows)[1:-1].encode())      # json.dump of the whole list joins these with ", "
     ev = coco_metric.CocoBoxEval(gt, results)
     ev.evaluate(img_ids=[m["id"] for m in mine], device=metric_device, unpack=False)
+    return _finish(ev, frags, metas, chunk, group, world, rank, predictions_json, out, metric_device)
+
+
+def _evaluate_records(detector, gt, mine, images_dir, read_image, workers, chunk, mapping, score_threshold, max_batch, dev, want_json):
+    """evaluate()'s detection and matching of the images `mine` without a result dict: -> the evaluated CocoBoxEval (outputs on
+    `dev`) and the predictions file's fragments per chunk."""
+    import torch
+    from . import coco_metric, coco_rows
+    records = detector.engine.new_records(len(mine), dev)
+    frags, shapes, k = [], [], 0
+    with torch.cuda.device(dev):
+        for part, images in _read_chunks(mine, images_dir, read_image, workers, chunk):
+            block = records[k:k + len(part)]
+            detector.detect_many_records(images, block, max_batch=max_batch)
+            shapes += [im.shape[:2] for im in images]
+            if want_json:
+                frags.append(coco_rows.write_predictions(block.cpu().numpy(), [m["id"] for m in part], shapes[k:], mapping, score_threshold))
+            k += len(part)
+        ids = [m["id"] for m in mine]
+        ev = coco_metric.CocoBoxEval.from_records(gt, records, ids, mapping, score_threshold, device=dev, image_hw=shapes)
+        ev.evaluate(img_ids=ids, device=dev, unpack=False)
+    return ev, frags
+
+
+def _finish(ev, frags, metas, chunk, group, world, rank, predictions_json, out, metric_device):
+    """evaluate() behind the matching: the ranks' exchange, the predictions file, the accumulation and the table."""
+    from .distributed import ChunkAssignment
     if group is not None:
+        import torch.distributed as dist
         # one all-gather of every rank's matching cells and its chunks' JSON; the chunks go back in input order (chunk c of the
         # sorted images is rank c % world's: a round-robin split in chunks of one)
         payload = {"cells": ev.cells(), "json": np.frombuffer(b"".join(frags), np.uint8),

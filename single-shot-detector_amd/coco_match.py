@@ -113,7 +113,7 @@ def launch(cells_host, cells_dev, det_box, det_area, nd, gt_box, gt_area, gt_cro
 
 
 def match_device(p, thr, area_rng, device, want_iou=False, timings=None):
-    """pack()'s arrays through the kernel, the outputs left on the GPU -> matched, ignored torch uint8 [A, nd, 2] (the uint16 words'
+    """pack()'s arrays (det_box / det_area numpy, or torch tensors already on `device`) through the kernel, the outputs left on the GPU -> matched, ignored torch uint8 [A, nd, 2] (the uint16 words'
     bytes), gt_ignore torch uint8 [A, ng], the IoU dump float64 [sum D * G] or None.  The launch is enqueued on the current stream;
     nothing waits for it unless timings is given: a dict that receives 'upload' and 'launch' (HIP events) in seconds."""
     import time
@@ -123,7 +123,12 @@ def match_device(p, thr, area_rng, device, want_iou=False, timings=None):
     nd, ng = len(p["det_area"]), len(p["gt_area"])
     t0 = time.perf_counter()
     with torch.cuda.device(dev):
-        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        def up(x):
+            if isinstance(x, torch.Tensor):            # rows that coco_rows.rows_device left on this GPU
+                if x.device != dev:
+                    raise ValueError("the detections' rows live on %s, not on %s" % (x.device, dev))
+                return x.contiguous()
+            return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
         cells_dev = up(p["cells"].view(np.uint8).reshape(-1))
         det_box, det_area = up(p["det_box"]), up(p["det_area"])
         gt_box, gt_area, gt_crowd = up(p["gt_box"]), up(p["gt_area"]), up(p["gt_crowd"])

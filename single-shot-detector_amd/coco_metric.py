@@ -72,9 +72,135 @@ class CocoBoxEval:
             if d["image_id"] in imgs and d["category_id"] in cats:
                 bb = list(d["bbox"])
                 self._dts.setdefault((d["image_id"], d["category_id"]), []).append((bb, float(bb[2] * bb[3]), float(d["score"])))
+        self._rows = None                  # from_records: the detections as flat rows instead of _dts
         self._retained = None
         self.eval_imgs = None
         self.precision = self.recall = self.stats = None
+
+    @classmethod
+    def from_records(cls, groundtruth, records, image_ids, label_to_coco_id, score_threshold, device=None, img_ids=None, cat_ids=None,
+                     image_hw=None):
+        """The evaluator of a run whose detections are the engine's record blocks (ssd.split_records; Detector.detect_many_records),
+        unfiltered: no result dict and no tuple per detection is built.  records: int32 [n, 6T + 1], a torch tensor on the GPU or a
+        numpy block; image_ids: the id of every record's image (each once, all of them in the annotation file); image_hw: (height,
+        width) of every record's ORIGINAL image, which the boxes are scaled to -- default: 'height' and 'width' of the annotation
+        file's 'images'; label_to_coco_id: {detector label:
+        category id}, a label it lacks is not evaluated; score_threshold: rows with score > threshold count (float32, strict).
+        device: None builds the rows with coco_rows.rows_host and keeps them on the host; a CUDA device index or torch.device builds
+        them with ssd_coco_rows_count / ssd_coco_rows_fill (coco_rows.rows_device; include/ssd_hip.h "the COCO rows") and leaves the
+        boxes and areas on that GPU, where evaluate(device=, unpack=False) matches them.  The rows are those of the dict route --
+        coco_eval.detection_records into the ordinary constructor -- bit for bit, so evaluate(), cells(), merge(), accumulate() and
+        summarize() give what they give there.  A record the header calls bad raises ValueError naming the image and the row.
+        If the annotation file has a (category, image) cell with more than coco_match.MAX_GT groundtruth boxes, which the matching
+        kernel leaves to the host loop, the WHOLE call takes the dict route instead: the records are downloaded, detection_records
+        builds the result dicts and the ordinary constructor takes them."""
+        from . import coco_match, coco_rows
+        gt = json.load(open(groundtruth)) if isinstance(groundtruth, str) else groundtruth
+        self = cls(gt, [], img_ids, cat_ids)
+        ids = [int(i) for i in image_ids]
+        if len(ids) != len(records):
+            raise ValueError("%d image ids for %d records" % (len(ids), len(records)))
+        sizes = {im["id"]: im for im in gt["images"]}
+        for k, i in enumerate(ids):
+            if i not in sizes:
+                raise ValueError("records[%d] names image_id %r, which the annotation file does not have" % (k, i))
+            if image_hw is None and ("height" not in sizes[i] or "width" not in sizes[i]):
+                raise ValueError("image %r of the annotation file has no 'height' / 'width': pass image_hw" % i)
+        if len(set(ids)) != len(ids):
+            raise ValueError("image_ids names an image twice")
+        hw = np.array([[sizes[i]["height"], sizes[i]["width"]] for i in ids] if image_hw is None else image_hw, np.int32).reshape(-1, 2)
+        if len(hw) != len(ids):
+            raise ValueError("%d image sizes for %d records" % (len(hw), len(ids)))
+        is_tensor = not isinstance(records, np.ndarray)
+        if any(len(g) > coco_match.MAX_GT for g in self._gts.values()):
+            from .coco_eval import detection_records
+            from .ssd import score_filter, split_records
+            host = records.cpu().numpy() if is_tensor else records
+            results = []
+            for i, (h, w), b, l, s, n in zip(ids, hw.tolist(), *split_records(np.ascontiguousarray(host))):
+                results += detection_records(None, np.empty((h, w, 0), np.uint8), i, label_to_coco_id, score_threshold,
+                                             detections=score_filter(b, l, s, n, np.float32(score_threshold)))
+            return cls(gt, results, img_ids, cat_ids)
+        # the records of the evaluated images, ascending by id: column c of the [K, m] tables is image img_ids[img_pos[c]]
+        pos = {img: k for k, img in enumerate(self.img_ids)}
+        take = [k for k in np.argsort(np.array(ids, np.int64), kind="stable").tolist() if ids[k] in pos]
+        if take != list(range(len(ids))):
+            if is_tensor:
+                import torch
+                records = records[torch.tensor(take, dtype=torch.int64, device=records.device)]
+            else:
+                records = records[take]
+        ids, hw = [ids[k] for k in take], hw[take]
+        cat_at = {c: k for k, c in enumerate(self.cat_ids)}
+        label_to_cat = np.full(max([int(l) for l in label_to_coco_id] + [0]) + 1, -1, np.int32)
+        for label, cat in label_to_coco_id.items():
+            label_to_cat[int(label)] = cat_at.get(cat, -1)
+        K = max(len(self.cat_ids), 1)
+        if device is None:
+            rows = coco_rows.rows_host(records.cpu().numpy() if is_tensor else records, hw, label_to_cat, K, score_threshold, image_ids=ids)
+        else:
+            rows = coco_rows.rows_device(records, hw, label_to_cat, K, score_threshold, device, image_ids=ids)
+        rows["img_pos"] = np.array([pos[i] for i in ids], np.int64)
+        self._rows, self._dts = rows, None
+        return self
+
+    def _need_dts(self):
+        """from_records keeps flat rows; the host loops read _dts: built here, on their first use, from the rows (already in every
+        cell's order and truncated, which the loops' own stable sort and truncation leave as they are)."""
+        if self._dts is not None:
+            return
+        r = self._rows
+        to_host = lambda x: x if isinstance(x, np.ndarray) else x.cpu().numpy()
+        box, area, score = to_host(r["det_box"]).tolist(), to_host(r["det_area"]).tolist(), r["det_score"].tolist()
+        flat = r["counts"].reshape(-1).astype(np.int64)
+        first = np.cumsum(flat) - flat
+        m = max(r["counts"].shape[1], 1)
+        self._dts = {}
+        for c in np.nonzero(flat)[0].tolist():
+            a, b = int(first[c]), int(first[c] + flat[c])
+            self._dts[(self.img_ids[int(r["img_pos"][c % m])], self.cat_ids[c // m])] = list(zip(box[a:b], area[a:b], score[a:b]))
+
+    def _rows_pack(self, subset):
+        """coco_match.pack()'s dict for the images `subset` from the flat rows of from_records: the groundtruth side by pack() itself
+        (the detections' dict empty), the cells that hold detections from the counts, merged in the cell order; det_box / det_area
+        stay torch tensors when the rows were built on a GPU."""
+        from . import coco_match
+        from .coco_accumulate import _ranges
+        r = self._rows
+        if r.get("gt_of") != tuple(subset):
+            r["gt_of"], r["gt"] = tuple(subset), coco_match.pack(self._gts, {}, self.cat_ids, subset)
+        g = r["gt"]
+        N = max(len(self.img_ids), 1)
+        img_arr, cat_arr = np.array(self.img_ids, np.int64), np.array(self.cat_ids, np.int64)
+        gkeys = np.array(g["keys"], np.int64).reshape(-1, 2)
+        gt_cell = np.searchsorted(cat_arr, gkeys[:, 0]) * N + np.searchsorted(img_arr, gkeys[:, 1])
+        counts = r["counts"].astype(np.int64)
+        flat = counts.reshape(-1)
+        first = np.cumsum(flat) - flat
+        col_in = np.isin(r["img_pos"], np.searchsorted(img_arr, np.array(list(subset), np.int64)))
+        mask = ((counts > 0) & col_in[None, :]).reshape(-1)
+        at = np.nonzero(mask)[0]
+        m = max(counts.shape[1], 1)
+        det_cell = (at // m) * N + r["img_pos"][at % m]
+        det_box, det_area, det_score = r["det_box"], r["det_area"], r["det_score"]
+        if not col_in.all():                # rows of images outside the subset lie between the others: gather
+            rows = _ranges(first[at], flat[at])
+            det_score = det_score[rows]
+            if isinstance(det_box, np.ndarray):
+                det_box, det_area = det_box[rows], det_area[rows]
+            else:
+                import torch
+                idx = torch.from_numpy(rows).to(det_box.device)
+                det_box, det_area = det_box[idx], det_area[idx]
+        union = np.union1d(gt_cell, det_cell)
+        cells = np.zeros(len(union), coco_match.CELL_DTYPE)
+        cells["D"][np.searchsorted(union, det_cell)] = flat[at]
+        cells["G"][np.searchsorted(union, gt_cell)] = g["cells"]["G"]
+        D, G = cells["D"].astype(np.int64), cells["G"].astype(np.int64)
+        cells["det_begin"], cells["gt_begin"] = np.cumsum(D) - D, np.cumsum(G) - G
+        keys = list(zip(cat_arr[union // N].tolist(), img_arr[union % N].tolist()))
+        return {"keys": keys, "packed": np.ones(len(keys), bool), "cells": cells, "det_box": det_box, "det_area": det_area,
+                "det_score": det_score, "gt_box": g["gt_box"], "gt_area": g["gt_area"], "gt_crowd": g["gt_crowd"]}
 
     def __getattr__(self, name):
         """eval_imgs is a plain attribute: {(category, area index, image): (scores, matched, ignored, gt_ignore)}.  Only after
@@ -107,6 +233,8 @@ class CocoBoxEval:
             subset = [i for i in self.img_ids if i in want]
         if device is not None:
             return self._evaluate_on_gpu(subset, device, unpack=unpack)
+        if self._rows is not None:
+            self._need_dts()
         for cat in self.cat_ids:
             for img in subset:
                 gts = self._gts.get((img, cat), [])
@@ -179,7 +307,7 @@ class CocoBoxEval:
         from . import coco_match
         self._retained = None
         t0 = time.perf_counter()
-        p = coco_match.pack(self._gts, self._dts, self.cat_ids, subset)
+        p = self._rows_pack(subset) if self._rows is not None else coco_match.pack(self._gts, self._dts, self.cat_ids, subset)
         t1 = time.perf_counter()
         if not unpack:
             matched, ignored, gt_ignore, _ = coco_match.match_device(p, THR_L, AREA_RNG, device, timings=timings)

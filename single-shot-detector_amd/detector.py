@@ -141,6 +141,30 @@ class Detector:
                 consume(pending)
         return out
 
+    def detect_many_records(self, images, records, max_batch=32):
+        """`detect_many` for a caller that keeps the detections on the GPU: the same grouping and the same batches, but the record of
+        image i (ssd.split_records) is left UNFILTERED in row i of `records`, a contiguous device int32 tensor [len(images), 6T + 1]
+        on this detector's GPU -- bit for bit ssd.pack_records of what detect_many's batches produce.  Nothing is downloaded and
+        nothing waits: the forwards and the row copies are enqueued on the current stream.  Returns `records`.  Mode f32 only
+        (mode f16x3 needs the per-batch status check of detect_batch): ValueError otherwise."""
+        torch = _torch()
+        if self.engine.precision != "f32":
+            raise ValueError("detect_many_records runs in precision mode f32 only")
+        imgs = [host_frame(im, "every image") for im in images]
+        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.device.index == self.device):
+            raise ValueError("records must be a tensor on cuda:%d" % self.device)
+        self.engine._check_records(records, len(imgs))
+        parts = mixed_batches(self.engine, [im.shape[:2] for im in imgs], max_batch)
+        with self.engine.lock:
+            for part in parts:
+                if part == list(range(part[0], part[0] + len(part))):
+                    self.engine.forward_mixed_host([imgs[i] for i in part], records[part[0]:part[0] + len(part)])
+                else:
+                    block = self.engine.new_records(len(part), records.device)
+                    self.engine.forward_mixed_host([imgs[i] for i in part], block)
+                    records.index_copy_(0, torch.tensor(part, dtype=torch.int64).to(records.device, non_blocking=True), block)
+        return records
+
     def detect_tiled(self, image, tile=None, overlap=0.25, full_frame=True, score_threshold=0.1, max_batch=32):
         """`__call__` for a frame much LARGER than the network's input (a 1200 x 1600 camera frame at min_dimension 640), where
         shrinking the frame loses the small objects: the network runs on overlapping tiles of its own size at the frame's own
