@@ -57,6 +57,7 @@ extern "C" {
 #define SSD_ERR_HIP (-2)       /* a HIP runtime call failed                  */
 #define SSD_ERR_STATE (-3)     /* call out of order (e.g. forward before finalize) */
 #define SSD_ERR_WEIGHT (-4)    /* missing / mis-shaped / unknown variable    */
+#define SSD_ERR_UNSUPPORTED (-5)   /* a well-formed JPEG of a kind the decoder does not take (block "the JPEG decoder") */
 
 #define SSD_ACT_NONE 0
 #define SSD_ACT_RELU 1         /* tf.nn.relu  */
@@ -1375,6 +1376,122 @@ int ssd_tile_gather(const uint8_t *frames_dev /* [F,H,W,3] */, int32_t F, int32_
 int ssd_tile_merge(const int32_t *tile_records_dev /* [F*ny*nx,6T+1] */, const int32_t *full_records_dev /* [F,6T+1] or NULL */,
                    int32_t F, int32_t H, int32_t W, int32_t th, int32_t tw, int32_t oy, int32_t ox, int32_t C, int32_t m,
                    float iou_threshold, int32_t *out_records_dev /* [F,6T+1] */, void *stream);
+
+/* ---- the JPEG decoder: baseline JPEG bytes -> uint8 RGB frames in device memory, laid out as ssd_forward_mixed reads them ----
+ *
+ * Every workload starts from JPEG bytes (inference/evaluate_on_COCO.ipynb reads files, create_tfrecords.py stores them).  The decode
+ * splits: parsing and Huffman decoding are serial and run on the HOST (csrc/jpeg_host.cpp, plain C++: ssd_jpeg_info_read,
+ * ssd_jpeg_entropy, ssd_jpeg_plan), everything behind the quantised coefficients is integer arithmetic with a fixed definition and
+ * runs on the GPU (csrc/jpeg.hip: ssd_jpeg_decode, two launches per batch).  The definition below is the one libjpeg(-turbo)'s
+ * default decompressor implements (jidctint.c "slow integer", jdsample.c "fancy" upsampling, jdcolor.c), which is what
+ * PIL.Image.open(...).convert("RGB") returns: the frames are that decoder's, bit for bit.  This block is the single statement of
+ * the rules for the host stage, for the kernels, for tests/helpers/jpeg_ref.py and for jpeg.py.
+ *
+ * Accepted streams -- all of:
+ *   SOF0 (baseline), sample precision 8, 8-bit quantisation tables (Pq = 0);
+ *   ONE scan that interleaves all components (Ns = Nf, the frame's order, Ss = 0, Se = 63, Ah = Al = 0), then EOI;
+ *   1 component with sampling 1x1, or 3 components whose chroma factors are 1x1 and whose luma factors (h x v) are 1x1, 2x1 or 2x2;
+ *   3 components are YCbCr: a JFIF APP0 was seen; else an Adobe APP14 was seen and its transform is 1; else neither was seen and
+ *   the component ids are not 'R', 'G', 'B'.
+ *   Restart intervals (DRI + RSTn, numbered modulo 8), optimised Huffman tables, fill bytes FF FF in front of a marker and
+ *   APPn / COM segments are handled.
+ * SSD_ERR_UNSUPPORTED (the caller decodes the file as before): every other SOFn, DAC, another precision, 16-bit tables, 2 or 4 and
+ * more components, other sampling factors (4:4:0, 4:1:1, ..), a scan of fewer components or a second scan, DNL or height 0, RGB or
+ * another Adobe transform, and -- from ssd_jpeg_entropy -- a coefficient outside int16 or with |coefficient * q| > 32767 (there
+ * the library's own SIMD and C paths stop agreeing, so nothing can be pinned).
+ * SSD_ERR_INVALID: anything malformed or truncated -- no SOI, a segment that runs past the end, an undefined or over-subscribed
+ * table, a code that no table holds, a run past coefficient 63, a DC category above 11, entropy data that ends before its last
+ * block, a wrong or missing restart marker, no EOI.  The stricter reading is deliberate: such a file goes to the caller's reader.
+ *
+ * Coefficients: int16 [64] per block in NATURAL (row-major, de-zigzagged) order, NOT dequantised; a component's blocks in raster
+ * order over its PADDED block grid, (mcus_y * v) rows by (mcus_x * h) blocks, mcus_x = ceil(width / (8 h_max)), mcus_y =
+ * ceil(height / (8 v_max)); the components one after the other.  The DC predictor is kept per component and reset at every restart
+ * marker.  Quantisation tables: uint16 [64] in natural order, one per component (components * 64 values).
+ *
+ * IDCT of a block ("slow integer", CONST_BITS 13, PASS1_BITS 2), on the dequantised values x = coefficient * q:
+ *   pass 1 over the COLUMNS of x, every output descaled (t + 2^10) >> 11;
+ *   pass 2 over the ROWS of pass 1's result, every output descaled (t + 2^17) >> 18; then + 128, clamped to 0 .. 255.
+ *   The order -- columns first, with the intermediate rounding -- is part of the definition.
+ *   The one-dimensional kernel on x0 .. x7 (pass 1 takes them as they are, pass 2 likewise; the shifts by 13 are part of it):
+ *     even   z1 = (x2 + x6) * 4433,  t2 = z1 - x6 * 15137,  t3 = z1 + x2 * 6270
+ *            t0 = (x0 + x4) << 13,  t1 = (x0 - x4) << 13
+ *            t10 = t0 + t3,  t13 = t0 - t3,  t11 = t1 + t2,  t12 = t1 - t2
+ *     odd    a = x7, b = x5, c = x3, d = x1
+ *            z1 = a + d,  z2 = b + c,  z3 = a + c,  z4 = b + d,  z5 = (z3 + z4) * 9633
+ *            a *= 2446,  b *= 16819,  c *= 25172,  d *= 12299
+ *            z1 *= -7373,  z2 *= -20995,  z3 = z3 * -16069 + z5,  z4 = z4 * -3196 + z5
+ *            a += z1 + z3,  b += z2 + z4,  c += z2 + z3,  d += z1 + z4
+ *     out    0 .. 7 = t10 + d, t11 + c, t12 + b, t13 + a, t13 - a, t12 - b, t11 - c, t10 - d
+ *   (0.298631336 = 2446, 0.390180644 = 3196, 0.541196100 = 4433, 0.765366865 = 6270, 0.899976223 = 7373, 1.175875602 = 9633,
+ *    1.501321110 = 12299, 1.847759065 = 15137, 1.961570560 = 16069, 2.053119869 = 16819, 2.562915447 = 20995, 3.072711026 = 25172.)
+ *   All arithmetic is 32-bit two's complement (the code forms the sums in uint32), all right shifts are arithmetic.
+ *
+ * Upsampling of a chroma plane s with REAL extents n = ceil(width / 2) columns and, for 2x2, m = ceil(height / 2) rows (samples
+ * outside the real extent are never read: block padding is no neighbour, edges replicate the last real sample):
+ *   2x1   per row:  out[2i] = (3 s[i] + s[i-1] + 1) >> 2,  out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2;  out[0] = s[0], out[2n-1] = s[n-1]
+ *   2x2   output row 2j + v: the neighbour row nb = j - 1 for v = 0, j + 1 for v = 1 (row -1 is row 0, row m is row m - 1);
+ *         c[i] = 3 s[j][i] + s[nb][i];  out[2i] = (3 c[i] + c[i-1] + 8) >> 4,  out[2i+1] = (3 c[i] + c[i+1] + 7) >> 4;
+ *         out[0] = (4 c[0] + 8) >> 4,  out[2n-1] = (4 c[n-1] + 7) >> 4
+ *   n <= 2 (width <= 4): both modes REPLICATE each sample (2x1 or 2x2) instead -- the library's rule.
+ *   The result is cropped to height x width.
+ * Colour, with cb, cr centred by -128:
+ *   R = Y + ((91881 cr + 32768) >> 16),  B = Y + ((116130 cb + 32768) >> 16),  G = Y + ((-22554 cb - 46802 cr + 32768) >> 16)
+ *   (one arithmetic shift of the signed sum), each clamped to 0 .. 255.  One component: R = G = B = Y.
+ *
+ * Host stage (no HIP, no global state, re-entrant; never reads outside [bytes, bytes + n), never writes outside what `info` reports):
+ *   ssd_jpeg_info_read  parses the whole marker structure (headers, the scan's extent up to EOI) and fills *out.
+ *   ssd_jpeg_entropy    decodes the scan into coef_host [info->coef_count] and quant_host [info->components * 64]; `info` must be
+ *                       what ssd_jpeg_info_read gave for these bytes (SSD_ERR_INVALID otherwise).  After a refusal the two
+ *                       arrays hold unspecified values inside their bounds.
+ *   ssd_jpeg_plan       the batch layout: images_out[b] for infos[b], b < B, in order -- coefficients back to back (64 * blocks
+ *                       each), tables back to back, each image's sample planes on the next 16-byte boundary of the workspace,
+ *                       each frame on the next 16-byte boundary (ssd_forward_mixed's default layout), block_begin / tile_begin the
+ *                       running sums -- and totals_out = {coefficients (int16), table values (uint16), workspace bytes, frame
+ *                       bytes}.  SSD_ERR_INVALID for an info no accepted stream gives, or frames of 2^31 bytes and more.
+ * Device stage: ssd_jpeg_decode enqueues two launches on `stream` whatever B and the sizes are; no allocation, no synchronisation,
+ * no atomics, no handle; every byte of every frame is written exactly once, no byte between frames, two calls give the same bytes.
+ *   images_host / images_dev  the same B rows in host memory (read by the call, which refuses a bad table before any HIP call) and in
+ *                       device memory (8-byte aligned; the kernels read it; the caller's upload, ordered before the call on `stream`)
+ *   coef_dev, quant_dev 16-byte aligned; an image's coefficients at coef_offset (a multiple of 8), its tables at quant_offset (a
+ *                       multiple of 8)
+ *   workspace_dev       16-byte aligned, ssd_jpeg_workspace_bytes(images_host, B) bytes: the sample planes of component k of an
+ *                       image, pitch 8 * blocks per row, at plane_offset (a multiple of 8) + 64 * the blocks of the components before
+ *   frames_dev          16-byte aligned; frame b = uint8 [height, width, 3] at frame_offset (a multiple of 16), within 2 GiB
+ *   launch 1            dequantise + IDCT: 8 lanes per block, a wave reads 8 blocks as 1 KiB of 16-byte row loads; 32 blocks per
+ *                       256-lane group, at most SSD_COCO_GRID_CAP groups striding over all blocks of the batch
+ *   launch 2            upsample + convert + crop: a 256-lane group takes a tile of SSD_JPEG_TILE consecutive pixels (row-major) of
+ *                       ONE frame, so the sampling mode is uniform in the group; a lane owns a run of SSD_JPEG_RUN of them (48
+ *                       bytes: three 16-byte stores; a frame's last, shorter run stores its bytes singly); at most
+ *                       SSD_COCO_GRID_CAP groups striding over all tiles of the batch
+ *   Refused with SSD_ERR_INVALID, the reason "ssd_jpeg_decode: ..." naming the argument: B outside [0, 2^20]; NULL or misaligned
+ *   pointers with B > 0; a row whose geometry no accepted stream gives; offsets that are negative, misaligned, or not ascending and
+ *   disjoint (planes, frames); block_begin / tile_begin that are not the running sums; a frame that ends past 2^31 - 1.  B == 0
+ *   enqueues nothing. */
+#define SSD_JPEG_RUN 16                      /* pixels a lane of launch 2 owns                                          */
+#define SSD_JPEG_TILE 4096                   /* pixels a 256-lane group of launch 2 takes: 256 runs                     */
+typedef struct ssd_jpeg_info {               /* 56 bytes, no padding */
+    int32_t height, width, components;       /* 1 or 3 components                                               */
+    int32_t h, v;                            /* luma sampling factors: 1x1, 2x1 (4:2:2) or 2x2 (4:2:0)         */
+    int32_t mcus_x, mcus_y, restart_interval;    /* restart_interval in MCUs, 0: none                          */
+    int32_t blocks[3];                       /* blocks of each component (0 for an absent one)                 */
+    int32_t reserved;                        /* 0                                                              */
+    int64_t coef_count;                      /* 64 * (blocks[0] + blocks[1] + blocks[2])                       */
+} ssd_jpeg_info;
+typedef struct ssd_jpeg_image {              /* 80 bytes, no padding: one image of a batch                     */
+    int32_t height, width, components, h, v, mcus_x, mcus_y, reserved;
+    int64_t coef_offset;                     /* int16 elements from coef_dev                                   */
+    int64_t quant_offset;                    /* uint16 elements from quant_dev                                 */
+    int64_t plane_offset;                    /* bytes from workspace_dev                                       */
+    int64_t frame_offset;                    /* bytes from frames_dev                                          */
+    int64_t block_begin;                     /* blocks of the images before this one                           */
+    int64_t tile_begin;                      /* tiles (ceil(height * width / SSD_JPEG_TILE)) of the images before */
+} ssd_jpeg_image;
+int ssd_jpeg_info_read(const uint8_t *bytes, int64_t n, ssd_jpeg_info *out);
+int ssd_jpeg_entropy(const uint8_t *bytes, int64_t n, const ssd_jpeg_info *info, int16_t *coef_host, uint16_t *quant_host);
+int ssd_jpeg_plan(const ssd_jpeg_info *infos, int32_t B, ssd_jpeg_image *images_out, int64_t *totals_out /* [4] */);
+size_t ssd_jpeg_workspace_bytes(const ssd_jpeg_image *images_host, int32_t B);     /* 0 for a table ssd_jpeg_decode refuses */
+int ssd_jpeg_decode(const ssd_jpeg_image *images_host, const ssd_jpeg_image *images_dev, int32_t B, const int16_t *coef_dev,
+                    const uint16_t *quant_dev, void *workspace_dev, uint8_t *frames_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "logit_screen.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
             "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip", "train_head.hip", "wgrad.hip", "train_backbone.hip", "train_shufflenet.hip",
-            "train_first_f32.hip", "train_norms.hip", "train_hist.hip", "train_reduce.hip", "coco_match.hip", "coco_accumulate.hip", "coco_rows.hip", "voc_match.hip", "tiles.hip"]
+            "train_first_f32.hip", "train_norms.hip", "train_hist.hip", "train_reduce.hip", "coco_match.hip", "coco_accumulate.hip", "coco_rows.hip", "voc_match.hip", "tiles.hip", "jpeg.hip",
+            "jpeg_host.cpp"]        # (the one plain C++ source: the JPEG decoder's host stage, compiled without an offload target)
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
 _lib = None
@@ -35,7 +36,7 @@ def build(force=False, verbose=False, diag=False):
     include/ssd_hip_diag.h) for scripts/ -- never loaded by the product."""
     srcs = [os.path.join(_CSRC, s) for s in _SOURCES]
     deps = srcs + [os.path.join(_CSRC, "ssd_internal.h"), os.path.join(_CSRC, "host.h"), os.path.join(_CSRC, "igemm_mfma16.h"),
-                   os.path.join(_CSRC, "train_head.h"), os.path.join(_CSRC, "train_table.h"), os.path.join(_CSRC, "first_pixels.h"), os.path.join(_CSRC, "first_pixels_f32.h"), os.path.join(_CSRC, "iou_greater.h"),
+                   os.path.join(_CSRC, "train_head.h"), os.path.join(_CSRC, "train_table.h"), os.path.join(_CSRC, "first_pixels.h"), os.path.join(_CSRC, "first_pixels_f32.h"), os.path.join(_CSRC, "iou_greater.h"), os.path.join(_CSRC, "jpeg_geom.h"),
                    os.path.join(_HERE, "..", "include", "ssd_hip.h"),
                    os.path.join(_HERE, "..", "include", "ssd_hip_diag.h"), os.path.join(_CSRC, "exports.map")]
     target = _DIAG_PATH if diag else _LIB_PATH
@@ -80,7 +81,9 @@ def build(force=False, verbose=False, diag=False):
                         oh.update(f.read())
                 ostamp, odig = obj + ".sha", oh.hexdigest()
                 if force or not os.path.exists(obj) or not os.path.exists(ostamp) or open(ostamp).read().strip() != odig:
-                    jobs.append(([hipcc] + cflags + ["-c", src, "-o", obj], ostamp, odig))
+                    host_only = src.endswith(".cpp")
+                    jobs.append(([hipcc] + (["-x", "c++"] + [f for f in cflags if not f.startswith("--offload-arch")] if host_only else cflags)
+                                 + ["-c", src, "-o", obj], ostamp, odig))
             if verbose:
                 for j in jobs:
                     print(" ".join(j[0]))
@@ -156,6 +159,21 @@ class SsdBnLevel(ctypes.Structure):
     _fields_ = [("rows", ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
         "x", "dy", "out", "gamma", "beta", "moving_mean", "moving_variance", "mean", "var", "invstd", "dgamma", "dbeta")]
 
+
+class SsdJpegInfo(ctypes.Structure):
+    """ssd_jpeg_info of include/ssd_hip.h (56 bytes)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("height", "width", "components", "h", "v", "mcus_x", "mcus_y", "restart_interval")] + \
+               [("blocks", ctypes.c_int32 * 3), ("reserved", ctypes.c_int32), ("coef_count", ctypes.c_int64)]
+
+
+class SsdJpegImage(ctypes.Structure):
+    """ssd_jpeg_image of include/ssd_hip.h (80 bytes)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("height", "width", "components", "h", "v", "mcus_x", "mcus_y", "reserved")] + \
+               [(n, ctypes.c_int64) for n in ("coef_offset", "quant_offset", "plane_offset", "frame_offset", "block_begin", "tile_begin")]
+
+
+SSD_ERR_INVALID, SSD_ERR_UNSUPPORTED = -1, -5       # the two refusals of the JPEG decoder's host stage
+SSD_JPEG_RUN, SSD_JPEG_TILE = 16, 4096
 
 # every symbol include/ssd_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -275,6 +293,11 @@ SIGNATURES = {
     "ssd_tile_grid": (ctypes.c_int, [_i, _i, _i, _i, _i, _i, _i32p]),
     "ssd_tile_gather": (ctypes.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ssd_tile_merge": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _vp]),
+    "ssd_jpeg_info_read": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(SsdJpegInfo)]),
+    "ssd_jpeg_entropy": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(SsdJpegInfo), _vp, _vp]),
+    "ssd_jpeg_plan": (ctypes.c_int, [ctypes.POINTER(SsdJpegInfo), _i, ctypes.POINTER(SsdJpegImage), ctypes.POINTER(ctypes.c_int64)]),
+    "ssd_jpeg_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SsdJpegImage), _i]),
+    "ssd_jpeg_decode": (ctypes.c_int, [ctypes.POINTER(SsdJpegImage), _vp, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

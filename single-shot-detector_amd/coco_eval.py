@@ -61,7 +61,8 @@ def detection_records_many(detector, images, image_ids, label_to_coco_id, score_
 
 
 def evaluate(detector, annotations_json, images_dir, read_image=None, predictions_json="coco_predictions.json", out=None,
-             score_threshold=0.15, max_batch=32, read_workers=None, group=None, chunk=256, metric_device=None, rows_device=None):
+             score_threshold=0.15, max_batch=32, read_workers=None, group=None, chunk=256, metric_device=None, rows_device=None,
+             jpeg_device=None):
     """Cells 4-17 end to end: every image of the annotation file through the detector (score_threshold 0.15, cell 10), the
     results written as `predictions_json` (cell 11), then the twelve COCO box statistics (cell 17: COCOeval over all image and
     category ids) -- computed by coco_metric.py, this build's restatement of pycocotools' COCOeval (not installed here, not
@@ -88,7 +89,15 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     record on that GPU (Detector.detect_many_records), the metric's rows are built there from the records
     (CocoBoxEval.from_records; include/ssd_hip.h "the COCO rows") and matched and accumulated there, and the predictions file is
     formatted from the downloaded records per chunk (coco_rows.write_predictions).  The same statistics and the same file, byte for
-    byte.  With `group` every rank builds the rows of its own images; the cells travel as before."""
+    byte.  With `group` every rank builds the rows of its own images; the cells travel as before.
+
+    `jpeg_device`: None reads and decodes every file with `read_image` as above; a CUDA device index or torch.device -- the
+    detector's GPU (ValueError otherwise) -- reads the files' BYTES instead, runs the entropy stage of the JPEG decoder on the
+    reader threads and turns the coefficients into frames on the GPU, where the detector reads them (Detector.detect_many_records_jpeg's
+    core; include/ssd_hip.h "the JPEG decoder"): chunk k + 1 is read and entropy-decoded while chunk k is detected.  A file the
+    decoder refuses (progressive, CMYK, not a JPEG, ..) is read with `read_image` and takes the host route.  The frames are PIL's
+    bit for bit, so with the default reader the statistics and the predictions file are the same, byte for byte; combinable with
+    `rows_device` and `metric_device`.  A chunk's frames must stay below 2 GiB (256 files of 1600 x 1600)."""
     import os
     from . import coco_metric
     from .distributed import ChunkAssignment
@@ -107,18 +116,26 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
         import torch.distributed as dist
         world, rank = dist.get_world_size(group), dist.get_rank(group)
     mine = [m for _i, m in ChunkAssignment(world, rank, chunk).select(metas)]
+    if jpeg_device is not None:
+        from .coco_match import _device
+        if not hasattr(detector, "_jpeg_records") or _device(jpeg_device).index != detector.device:
+            raise ValueError("jpeg_device must be the GPU of a Detector: the frames are detected where they are decoded")
+    jpeg = jpeg_device is not None
     if rows_device is not None:
         from .coco_match import _device
         dev = _device(rows_device)
         if metric_device is not None and _device(metric_device) != dev:
             raise ValueError("metric_device must be None or rows_device (%s): the rows are matched where they are built" % dev)
         ev, frags = _evaluate_records(detector, gt, mine, images_dir, read_image, workers, chunk, mapping, score_threshold, max_batch,
-                                      dev, bool(predictions_json))
+                                      dev, bool(predictions_json), jpeg)
         return _finish(ev, frags, metas, chunk, group, world, rank, predictions_json, out, dev)
     results, frags = [], []
-    for part, images in _read_chunks(mine, images_dir, read_image, workers, chunk):
+    for part, images in (_read_jpeg_chunks if jpeg else _read_chunks)(mine, images_dir, read_image, workers, chunk, detector):
         # images read, then detected as batches grouped by network shape (the notebook's loop, one image per sess.run, at batch throughput)
-        rows = detection_records_many(detector, images, [m["id"] for m in part], mapping, score_threshold, max_batch)
+        if jpeg:
+            rows = _jpeg_detection_records(detector, part, images, mapping, score_threshold, max_batch)
+        else:
+            rows = detection_records_many(detector, images, [m["id"] for m in part], mapping, score_threshold, max_batch)
         results += rows
         if predictions_json:
             frags.append(json.dumps(rows)[1:-1].encode())      # json.dump of the whole list joins these with ", "
@@ -127,7 +144,21 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     return _finish(ev, frags, metas, chunk, group, world, rank, predictions_json, out, metric_device)
 
 
-def _evaluate_records(detector, gt, mine, images_dir, read_image, workers, chunk, mapping, score_threshold, max_batch, dev, want_json):
+def _jpeg_detection_records(detector, part, batch, mapping, score_threshold, max_batch):
+    """detection_records_many for one chunk that arrives as a decoder batch (_read_jpeg_chunks): the same rows."""
+    from .ssd import score_filter, split_records
+    records = detector.engine.new_records(len(part), "cuda:%d" % detector.device)
+    shapes = detector._jpeg_records(batch, records, max_batch, batch.fallback_at)
+    boxes, labels, scores, num = split_records(records.cpu().numpy())
+    out = []
+    for i, (m, (h, w)) in enumerate(zip(part, shapes)):
+        d = score_filter(boxes[i], labels[i], scores[i], num[i], score_threshold)
+        out += detection_records(detector, np.empty((h, w, 0), np.uint8), m["id"], mapping, score_threshold, detections=d)
+    return out
+
+
+def _evaluate_records(detector, gt, mine, images_dir, read_image, workers, chunk, mapping, score_threshold, max_batch, dev, want_json,
+                      jpeg=False):
     """evaluate()'s detection and matching of the images `mine` without a result dict: -> the evaluated CocoBoxEval (outputs on
     `dev`) and the predictions file's fragments per chunk."""
     import torch
@@ -135,10 +166,13 @@ def _evaluate_records(detector, gt, mine, images_dir, read_image, workers, chunk
     records = detector.engine.new_records(len(mine), dev)
     frags, shapes, k = [], [], 0
     with torch.cuda.device(dev):
-        for part, images in _read_chunks(mine, images_dir, read_image, workers, chunk):
+        for part, images in (_read_jpeg_chunks if jpeg else _read_chunks)(mine, images_dir, read_image, workers, chunk, detector):
             block = records[k:k + len(part)]
-            detector.detect_many_records(images, block, max_batch=max_batch)
-            shapes += [im.shape[:2] for im in images]
+            if jpeg:
+                shapes += detector._jpeg_records(images, block, max_batch, images.fallback_at)
+            else:
+                detector.detect_many_records(images, block, max_batch=max_batch)
+                shapes += [im.shape[:2] for im in images]
             if want_json:
                 frags.append(coco_rows.write_predictions(block.cpu().numpy(), [m["id"] for m in part], shapes[k:], mapping, score_threshold))
             k += len(part)
@@ -174,7 +208,7 @@ def _finish(ev, frags, metas, chunk, group, world, rank, predictions_json, out, 
     return ev.accumulate(device=metric_device).summarize(out if rank == 0 else None)
 
 
-def _read_chunks(metas, images_dir, read_image, workers, chunk):
+def _read_chunks(metas, images_dir, read_image, workers, chunk, detector=None):
     """(metas of a chunk, its decoded images) for consecutive chunks of `metas`; the next chunk is read while the caller
     works on this one (PIL and cv2 release the interpreter lock while they decode)."""
     import os
@@ -187,6 +221,38 @@ def _read_chunks(metas, images_dir, read_image, workers, chunk):
             images = [f.result() for f in ahead]
             ahead = start(k + chunk)
             yield metas[k:k + chunk], images
+
+
+def _read_file(path):
+    with open(path, "rb") as f:
+        return f.read()
+
+
+def _read_jpeg_chunks(metas, images_dir, read_image, workers, chunk, detector):
+    """(metas of a chunk, its decoder batch) for consecutive chunks of `metas`: the threads read the files' bytes and run the JPEG
+    decoder's entropy stage (plain C behind ctypes: the interpreter lock is released); chunk k + 1 is being entropy-decoded while
+    the caller detects chunk k, and the files of chunk k + 2 are being read.  batch.fallback_at(i) reads file i of the chunk with
+    `read_image` (a file the decoder refuses)."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    dec = detector.jpeg_decoder()
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        def read(k):
+            return [pool.submit(_read_file, os.path.join(images_dir, m["file_name"])) for m in metas[k:k + chunk]]
+
+        def begin(k, files):
+            part = metas[k:k + chunk]
+            batch = dec.begin([f.result() for f in files], pool)
+            batch.fallback_at = lambda i: read_image(os.path.join(images_dir, part[i]["file_name"]))
+            return batch
+        files = read(0)
+        ahead = begin(0, files) if metas else None
+        files = read(chunk)
+        for k in range(0, len(metas), chunk):
+            batch = ahead
+            ahead = begin(k + chunk, files) if k + chunk < len(metas) else None
+            files = read(k + 2 * chunk)
+            yield metas[k:k + chunk], batch
 
 
 # ----------------------------------------------------------------------------- VOC-style AP self-check

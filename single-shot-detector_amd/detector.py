@@ -22,6 +22,14 @@ from .ckpt_import import load_ckpt_weights, resolve_checkpoint
 from .variables import load_weights
 
 
+def _pil_rgb(blob):
+    """The reference notebooks' reader on bytes (inference/just_try_detector.ipynb: PIL, RGB)."""
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(blob)) as im:
+        return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
 class Detector:
     def __init__(self, model_path, gpu_memory_fraction=0.25, visible_device_list='0',
                  config=None, precision=None, use_ema=False):
@@ -164,6 +172,102 @@ class Detector:
                     self.engine.forward_mixed_host([imgs[i] for i in part], block)
                     records.index_copy_(0, torch.tensor(part, dtype=torch.int64).to(records.device, non_blocking=True), block)
         return records
+
+    # ------------------------------------------------------------------------- from JPEG bytes, decoded on the GPU
+    JPEG_GROUP = 256                 # files decoded as one batch of the decoder ..
+    JPEG_GROUP_BYTES = 1 << 30       # .. and the frame bytes of one (ssd_forward_mixed addresses 2 GiB from the base)
+
+    def jpeg_decoder(self):
+        """This detector's jpeg.JpegDecoder (created on first use)."""
+        if getattr(self, "_jpeg", None) is None:
+            from .jpeg import JpegDecoder
+            self._jpeg = JpegDecoder(self.device)
+        return self._jpeg
+
+    def _jpeg_groups(self, blobs):
+        """Consecutive index ranges of `blobs`, each within JPEG_GROUP files and JPEG_GROUP_BYTES of frames."""
+        dec, groups, start, size = self.jpeg_decoder(), [], 0, 0
+        for i, blob in enumerate(blobs):
+            rc, info = dec.read_info(blob)
+            nbytes = 3 * info.height * info.width + 16 if rc == 0 else 0
+            if i > start and (i - start >= self.JPEG_GROUP or size + nbytes > self.JPEG_GROUP_BYTES):
+                groups.append((start, i))
+                start, size = i, 0
+            size += nbytes
+        if len(blobs) > start:
+            groups.append((start, len(blobs)))
+        return groups
+
+    def _jpeg_records(self, batch, records, max_batch, fallback_at):
+        """The records of one decoder batch (JpegDecoder.begin's) into `records` [len(batch.blobs), 6T + 1] on this GPU, row for
+        row: the accepted files as mixed-size batches straight from the decoded frames, the refused ones -- fallback_at(index) ->
+        ndarray -- through detect_many_records.  Returns every file's (height, width).  The caller holds no lock."""
+        torch = _torch()
+        (flat, hw, offsets), refused = self.jpeg_decoder().finish(batch)
+        n = len(batch.blobs)
+        taken = [i for i in range(n) if i not in refused]
+        shapes = [None] * n
+        for i, s in zip(taken, hw):
+            shapes[i] = s
+
+        def rows(idx):
+            return torch.tensor(idx, dtype=torch.int64).to(records.device, non_blocking=True)
+        with self.engine.lock:
+            for part in mixed_batches(self.engine, hw, max_batch):
+                frames = (flat, [hw[j] for j in part], [offsets[j] for j in part])
+                dst = [taken[j] for j in part]
+                if dst == list(range(dst[0], dst[0] + len(dst))):
+                    self.engine.forward_mixed(frames, records[dst[0]:dst[0] + len(dst)])
+                else:
+                    block = self.engine.new_records(len(part), records.device)
+                    self.engine.forward_mixed(frames, block)
+                    records.index_copy_(0, rows(dst), block)
+        if refused:
+            idx = sorted(refused)
+            imgs = [host_frame(fallback_at(i), "every image") for i in idx]
+            for i, im in zip(idx, imgs):
+                shapes[i] = tuple(int(v) for v in im.shape[:2])
+            block = self.engine.new_records(len(idx), records.device)
+            self.detect_many_records(imgs, block, max_batch=max_batch)
+            records.index_copy_(0, rows(idx), block)
+        return shapes
+
+    def detect_many_records_jpeg(self, blobs, records, max_batch=32, fallback=None, pool=None):
+        """`detect_many_records` for JPEG BYTES: the files are entropy-decoded on the host (on `pool`, a concurrent.futures
+        executor, when given) and turned into frames on this GPU (jpeg.JpegDecoder; include/ssd_hip.h "the JPEG decoder"), which
+        ssd_forward_mixed reads where they lie -- no decoded frame exists on the host.  Row i of `records` is bit for bit what
+        detect_many_records leaves for the PIL-decoded array of blobs[i].  A file the decoder refuses (progressive, CMYK, damaged,
+        ..) goes through `fallback(bytes) -> uint8 RGB ndarray` (default: PIL) and the host route.  Group k + 1 of the files is
+        entropy-decoded while group k computes.  Returns (records, [(height, width) of every file]).  Mode f32 only."""
+        torch = _torch()
+        if self.engine.precision != "f32":
+            raise ValueError("detect_many_records_jpeg runs in precision mode f32 only")
+        blobs = [b if isinstance(b, bytes) else bytes(b) for b in blobs]
+        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.device.index == self.device):
+            raise ValueError("records must be a tensor on cuda:%d" % self.device)
+        self.engine._check_records(records, len(blobs))
+        fallback = fallback or _pil_rgb
+        dec, shapes = self.jpeg_decoder(), []
+        with self.engine.lock, torch.cuda.device(self.device):      # (the decoder's two buffers are this detector's: one caller at a time)
+            groups = self._jpeg_groups(blobs)
+            ahead = dec.begin(blobs[groups[0][0]:groups[0][1]], pool) if groups else None
+            for g, (a, b) in enumerate(groups):
+                batch = ahead
+                ahead = dec.begin(blobs[groups[g + 1][0]:groups[g + 1][1]], pool) if g + 1 < len(groups) else None
+                shapes += self._jpeg_records(batch, records[a:b], max_batch, lambda i, a=a: fallback(blobs[a + i]))
+        return records, shapes
+
+    def detect_many_jpeg(self, blobs, score_threshold=0.1, max_batch=32, fallback=None, pool=None):
+        """`detect_many` for a list of JPEG byte strings, decoded on the GPU (detect_many_records_jpeg): (boxes, labels, scores) per
+        file, in order, each bit for bit what `detect_many` returns for the PIL-decoded arrays.  Refused files go through
+        `fallback(bytes) -> ndarray` (default: PIL) and the existing host route."""
+        fallback = fallback or _pil_rgb
+        if self.engine.precision != "f32":
+            return self.detect_many([fallback(b) for b in blobs], score_threshold, max_batch)
+        records = self.engine.new_records(len(blobs), "cuda:%d" % self.device)
+        self.detect_many_records_jpeg(blobs, records, max_batch, fallback, pool)
+        boxes, labels, scores, num = self.engine.record_views(records.cpu().numpy())
+        return [score_filter(boxes[i], labels[i], scores[i], num[i], score_threshold) for i in range(len(blobs))]
 
     def detect_tiled(self, image, tile=None, overlap=0.25, full_frame=True, score_threshold=0.1, max_batch=32):
         """`__call__` for a frame much LARGER than the network's input (a 1200 x 1600 camera frame at min_dimension 640), where

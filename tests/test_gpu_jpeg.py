@@ -1,0 +1,240 @@
+"""-m gpu: the JPEG decoder (include/ssd_hip.h, block "the JPEG decoder"; csrc/jpeg.hip, jpeg.py) against the decoder the product
+used before, PIL.Image.open(...).convert("RGB"), bit for bit -- the shared case list as one batch and reversed, images past one
+grid pass of either launch, the call between guard words at 16-byte-not-32-byte addresses, a side stream, the edge batch sizes,
+refused files, and the routes built on it: Detector.detect_many_jpeg, detect_many_records_jpeg, coco_eval.evaluate(jpeg_device=)."""
+import ctypes
+import io
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from tests.helpers import guarded, jpeg_cases
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+INVALID, UNSUPPORTED = -1, -5
+GRID_CAP = 1024                     # SSD_COCO_GRID_CAP: groups of a launch; 32 blocks / 4096 pixels per group and pass
+
+
+@pytest.fixture(scope="module")
+def dec(cuda, ssd):
+    return ssd.JpegDecoder(0)
+
+
+def frames_of(result):
+    """decode_many's ((flat, hw, offsets), refused) -> ([uint8 [H, W, 3]...], refused)."""
+    (flat, hw, offsets), refused = result
+    host = flat.cpu().numpy()
+    return [host[o:o + 3 * h * w].reshape(h, w, 3) for (h, w), o in zip(hw, offsets)], refused
+
+
+def progressive(arr):
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(arr).save(buf, "JPEG", progressive=True, quality=90)
+    return buf.getvalue()
+
+
+def loud(arr):
+    """A baseline file whose table values are all 255: ssd_jpeg_info_read accepts it, ssd_jpeg_entropy refuses it."""
+    blob, p = bytearray(jpeg_cases.encode(arr, "444", 90)), 2
+    while blob[p + 1] != 0xDA:
+        n = (blob[p + 2] << 8) | blob[p + 3]
+        if blob[p + 1] == 0xDB:
+            for q in range(p + 4, p + 2 + n, 65):
+                blob[q + 1:q + 65] = b"\xff" * 64
+        p += 2 + n
+    return bytes(blob)
+
+
+def test_whole_case_list_as_one_batch_and_reversed(dec):
+    blobs = [b for _n, b in jpeg_cases.cases()]
+    want = jpeg_cases.expected()
+    got, refused = frames_of(dec.decode_many(blobs))
+    assert refused == {} and len(got) == len(want) == 432
+    bad = [jpeg_cases.cases()[i][0] for i in range(432) if not np.array_equal(got[i], want[i])]
+    assert not bad, "%d frames differ from PIL, the first: %s" % (len(bad), bad[:5])
+    back, refused = frames_of(dec.decode_many(blobs[::-1]))
+    assert refused == {}
+    bad = [jpeg_cases.cases()[431 - i][0] for i in range(432) if not np.array_equal(back[i], want[431 - i])]
+    assert not bad, "reversed: %d frames differ, the first: %s" % (len(bad), bad[:5])
+
+
+def test_past_one_grid_pass_of_both_launches(dec):
+    """One 480x640 4:2:0 (7200 blocks) and one 427x640 4:2:2 (8640) cannot pass the first launch's 1024 x 32 blocks, nor the
+    second's 1024 x 4096 pixels, so the batch holds them three and two times (38 880 blocks: the stride loop of launch 1 runs
+    twice) and, for launch 2, the smallest 4:2:0 image that alone exceeds a pass: 2064 x 2040 (4 210 560 pixels, 49 665 blocks)."""
+    a = jpeg_cases.encode(jpeg_cases.pixels(480, 640, "ramp", 1), "420", 90)
+    b = jpeg_cases.encode(jpeg_cases.pixels(427, 640, "noise", 2), "422", 30)
+    big = jpeg_cases.encode(jpeg_cases.pixels(2064, 2040, "ramp", 3), "420", 90)
+    blobs = [a, b, a, b, a]
+    infos = [dec.read_info(x)[1] for x in blobs]
+    assert sum(sum(i.blocks) for i in infos) > GRID_CAP * 32
+    got, refused = frames_of(dec.decode_many(blobs))
+    assert refused == {}
+    for g, blob in zip(got, blobs):
+        assert np.array_equal(g, jpeg_cases.pil_rgb(blob))
+    info = dec.read_info(big)[1]
+    assert info.height * info.width > GRID_CAP * 4096 and sum(info.blocks) > GRID_CAP * 32
+    got, refused = frames_of(dec.decode_many([big, a]))
+    assert refused == {} and np.array_equal(got[0], jpeg_cases.pil_rgb(big)) and np.array_equal(got[1], jpeg_cases.pil_rgb(a))
+
+
+def host_batch(ssd, blobs):
+    """The host stage by hand: (table, coef int16, quant uint16, totals) of a batch of accepted files."""
+    from importlib import import_module
+    L, lib = import_module("ssd_amd._lib"), ssd.lib()
+    infos = (L.SsdJpegInfo * len(blobs))()
+    for k, blob in enumerate(blobs):
+        assert lib.ssd_jpeg_info_read(blob, len(blob), ctypes.byref(infos[k])) == 0
+    table, totals = (L.SsdJpegImage * len(blobs))(), (ctypes.c_int64 * 4)()
+    assert lib.ssd_jpeg_plan(infos, len(blobs), table, totals) == 0
+    coef, quant = np.zeros(totals[0], np.int16), np.zeros(totals[1], np.uint16)
+    for k, blob in enumerate(blobs):
+        assert lib.ssd_jpeg_entropy(blob, len(blob), ctypes.byref(infos[k]), coef.ctypes.data + 2 * table[k].coef_offset,
+                                    quant.ctypes.data + 2 * table[k].quant_offset) == 0
+    return table, coef, quant, list(totals)
+
+
+@pytest.mark.parametrize("layout", ["skewed", "aligned"])
+def test_between_guard_words_every_frame_byte_written_once(cuda, ssd, layout):
+    """Table, coefficients, tables, workspace and frames in ONE arena between guard words (skewed: every base 16 and not 32 bytes
+    aligned): every frame byte is written whatever it held before, the bytes between frames keep what they held, no guard changes."""
+    picks = list(range(0, 432, 5))                                   # every size, sampling, quality and variant
+    blobs = [jpeg_cases.cases()[i][1] for i in picks] + [jpeg_cases.encode(jpeg_cases.pixels(150, 211, "ramp", 9), "420", 90)]
+    want = [jpeg_cases.expected()[i] for i in picks] + [jpeg_cases.pil_rgb(blobs[-1])]
+    table, coef, quant, totals = host_batch(ssd, blobs)
+    ws_bytes = int(ssd.lib().ssd_jpeg_workspace_bytes(table, len(blobs)))
+    assert ws_bytes == totals[2] and ssd.lib().ssd_jpeg_workspace_bytes(table, len(blobs) + (1 << 21)) == 0
+    inside = np.zeros(totals[3], bool)
+    for t in table:
+        inside[t.frame_offset:t.frame_offset + 3 * t.height * t.width] = True
+    assert (~inside).sum() > 0, "the batch must leave gaps between frames"
+    results = []
+    for fill in (0x3C, 0xC3):
+        arena = guarded.Arena(cuda, "cuda:0", layout)
+        arena.add("table", np.frombuffer(bytes(table), np.uint8).copy(), np.uint8, 16, "input")
+        arena.add("coef", coef.view(np.uint8), np.uint8, 16, "input")
+        arena.add("quant", quant.view(np.uint8), np.uint8, 16, "input")
+        arena.add("ws", (ws_bytes,), np.uint8, 16, "workspace")
+        arena.add("frames", (totals[3],), np.uint8, 16, "output", fill=fill)
+        if layout == "skewed":
+            assert all(arena.ptr(n) % 32 == 16 for n in ("table", "coef", "quant", "ws", "frames"))
+        ssd._lib.check(ssd.lib().ssd_jpeg_decode(table, arena.ptr("table"), len(blobs), arena.ptr("coef"), arena.ptr("quant"),
+                                                 arena.ptr("ws"), arena.ptr("frames"), None))
+        cuda.cuda.synchronize()
+        arena.check()
+        out = arena.read("frames")
+        assert np.all(out[~inside] == fill), "a byte between two frames was written"
+        for t, w in zip(table, want):
+            assert np.array_equal(out[t.frame_offset:t.frame_offset + w.size].reshape(w.shape), w)
+        results.append(out[inside])
+    assert np.array_equal(results[0], results[1])
+
+
+def test_side_stream_second_launch_and_edge_batches(cuda, dec):
+    blobs = [b for _n, b in jpeg_cases.cases()[::9]]
+    first, _ = frames_of(dec.decode_many(blobs))
+    side = cuda.cuda.Stream()
+    with cuda.cuda.stream(side):
+        second = dec.decode_many(blobs)
+        third = dec.decode_many(blobs)
+        side.synchronize()
+        second, third = frames_of(second)[0], frames_of(third)[0]
+    for a, b, c, w in zip(first, second, third, jpeg_cases.expected()[::9]):
+        assert np.array_equal(a, w) and np.array_equal(b, w) and np.array_equal(c, w)
+    got, refused = frames_of(dec.decode_many(blobs[3:4]))
+    assert refused == {} and len(got) == 1 and np.array_equal(got[0], jpeg_cases.expected()[27])
+    (flat, hw, offsets), refused = dec.decode_many([])
+    assert flat.numel() == 0 and hw == [] and offsets == [] and refused == {}
+
+
+def test_refused_files_are_reported_and_the_others_unaffected(dec):
+    arr = jpeg_cases.pixels(40, 56, "ramp", 4)
+    ok = [jpeg_cases.encode(jpeg_cases.pixels(h, w, "noise", h), s, 90) for h, w, s in ((40, 56, "420"), (33, 20, "422"), (8, 8, "gray"), (64, 64, "444"))]
+    blobs = [ok[0], progressive(arr), ok[1], ok[0][:len(ok[0]) // 2], loud(np.full((16, 16, 3), 250, np.uint8)), ok[2], b"not a jpeg", ok[3]]
+    got, refused = frames_of(dec.decode_many(blobs))
+    assert refused == {1: UNSUPPORTED, 3: INVALID, 4: UNSUPPORTED, 6: INVALID}
+    assert len(got) == 4
+    for g, blob in zip(got, ok):
+        assert np.array_equal(g, jpeg_cases.pil_rgb(blob))
+    got, refused = frames_of(dec.decode_many([blobs[1], blobs[4]]))
+    assert got == [] and refused == {0: UNSUPPORTED, 1: UNSUPPORTED}
+
+
+# ----------------------------------------------------------------------------- end to end
+@pytest.fixture(scope="module")
+def detector(cuda, ssd):
+    """The model of tests/golden/tiny_mobilenet_128.npz (its seeded weights)."""
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    import make_golden as mg
+    Wt, _img = mg.inputs()
+    det = ssd.Detector(Wt, config=mg.TINY)
+    yield det
+    det.close()
+
+
+def twelve_files():
+    """12 JPEGs of three source sizes (two network shapes), samplings mixed, one progressive among them."""
+    blobs = []
+    for k in range(12):
+        h, w = ((128, 128), (100, 151), (97, 203))[k % 3]
+        arr = jpeg_cases.pixels(h, w, "noise" if k % 2 else "ramp", 50 + k)
+        blobs.append(progressive(arr) if k == 7 else jpeg_cases.encode(arr, ("420", "444", "422", "gray")[k % 4], 90))
+    return blobs
+
+
+def test_detect_many_jpeg_equals_detect_many_on_pil_arrays(cuda, detector):
+    blobs = twelve_files()
+    arrays = [jpeg_cases.pil_rgb(b) for b in blobs]
+    want = detector.detect_many(arrays, score_threshold=0.15, max_batch=4)
+    got = detector.detect_many_jpeg(blobs, score_threshold=0.15, max_batch=4)
+    assert sum(len(w[2]) for w in want) > 20
+    for w, g in zip(want, got):
+        for a, b in zip(w, g):
+            assert a.dtype == b.dtype and np.array_equal(a, b)
+    dev = "cuda:%d" % detector.device
+    rec_want = detector.detect_many_records(arrays, detector.engine.new_records(12, dev).zero_(), max_batch=4)
+    rec_got, shapes = detector.detect_many_records_jpeg(blobs, detector.engine.new_records(12, dev).zero_(), max_batch=4)
+    assert cuda.equal(rec_want, rec_got) and shapes == [a.shape[:2] for a in arrays]
+
+
+def test_coco_evaluate_from_jpeg_bytes_equals_the_default_route(cuda, ssd, detector, tmp_path):
+    """coco_eval.evaluate(jpeg_device=0) on a folder of JPEGs (one progressive, one PNG under a .jpg name: both refused and read
+    by the default reader): every statistic and the predictions file's bytes equal the default route's, alone and with rows_device."""
+    cats = [{"id": i + 1 + (i > 10), "name": n} for i, n in enumerate(ssd.coco_eval.COCO_NAMES)]
+    mapping = ssd.coco_eval.integer_to_coco_id(cats)
+    from PIL import Image
+    images, anns = [], []
+    for k, blob in enumerate(twelve_files()):
+        name = "%012d.jpg" % (k + 1)
+        if k == 4:
+            Image.fromarray(jpeg_cases.pil_rgb(blob)).save(str(tmp_path / name), "PNG")
+        else:
+            with open(tmp_path / name, "wb") as f:
+                f.write(blob)
+        im = np.asarray(Image.open(str(tmp_path / name)).convert("RGB"))
+        images.append({"id": 1000 + k, "file_name": name, "height": im.shape[0], "width": im.shape[1]})
+        for r in ssd.coco_eval.detection_records(detector, im, 1000 + k, mapping, score_threshold=0.3):
+            x, y, w, h = r["bbox"]
+            if w > 0 and h > 0:
+                anns.append({"id": len(anns) + 1, "image_id": r["image_id"], "category_id": r["category_id"], "bbox": r["bbox"],
+                             "area": float(w * h), "iscrowd": 0})
+    gt = {"images": images, "annotations": anns, "categories": cats}
+    assert len(anns) > 10
+
+    def run(name, **kw):
+        path = str(tmp_path / name)
+        stats = ssd.coco_eval.evaluate(detector, gt, str(tmp_path), predictions_json=path, max_batch=4, chunk=5, read_workers=4, **kw)
+        return stats, open(path, "rb").read()
+    base_stats, base_file = run("base.json")
+    assert len(json.loads(base_file)) > 20
+    for kw in ({"jpeg_device": 0}, {"jpeg_device": 0, "rows_device": 0}, {"jpeg_device": 0, "metric_device": 0}):
+        stats, blob = run("jpeg.json", **kw)
+        assert np.array_equal(np.asarray(stats), np.asarray(base_stats)), kw
+        assert blob == base_file, kw
+    with pytest.raises(ValueError):
+        ssd.coco_eval.evaluate(detector, gt, str(tmp_path), predictions_json=None, jpeg_device=1)
