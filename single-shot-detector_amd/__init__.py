@@ -31,6 +31,7 @@ from .augment import augment_batch, sample_augmentation, TrainPipeline   # noqa:
 from .train_step import TrainStep                                     # noqa: F401
 from . import train_calls                                             # noqa: F401  (how the TRAIN entry points are called)
 from .train_calls import histogram_limits                             # noqa: F401
+from . import metric_calls                                            # noqa: F401  (what the metrics' GPU paths share round their entry points)
 from . import summaries                                               # noqa: F401  (TensorBoard event files, by hand)
 from .train_ops import (conv_same, conv3x3_same, batch_norm_relu, batch_norm_act, depthwise_conv, pointwise_conv,   # noqa: F401
                         fpn_merge_backward, first_conv_train, first_conv_train_float, concat_shuffle_split, concat_channels, maxpool3x3s2_train)

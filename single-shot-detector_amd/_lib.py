@@ -36,7 +36,7 @@ def build(force=False, verbose=False, diag=False):
     include/ssd_hip_diag.h) for scripts/ -- never loaded by the product."""
     srcs = [os.path.join(_CSRC, s) for s in _SOURCES]
     deps = srcs + [os.path.join(_CSRC, "ssd_internal.h"), os.path.join(_CSRC, "host.h"), os.path.join(_CSRC, "igemm_mfma16.h"),
-                   os.path.join(_CSRC, "train_head.h"), os.path.join(_CSRC, "train_table.h"), os.path.join(_CSRC, "first_pixels.h"), os.path.join(_CSRC, "first_pixels_f32.h"), os.path.join(_CSRC, "iou_greater.h"), os.path.join(_CSRC, "jpeg_geom.h"),
+                   os.path.join(_CSRC, "train_head.h"), os.path.join(_CSRC, "train_table.h"), os.path.join(_CSRC, "first_pixels.h"), os.path.join(_CSRC, "first_pixels_f32.h"), os.path.join(_CSRC, "iou_greater.h"), os.path.join(_CSRC, "jpeg_geom.h"), os.path.join(_CSRC, "metric_host.h"),
                    os.path.join(_HERE, "..", "include", "ssd_hip.h"),
                    os.path.join(_HERE, "..", "include", "ssd_hip_diag.h"), os.path.join(_CSRC, "exports.map")]
     target = _DIAG_PATH if diag else _LIB_PATH

@@ -7,7 +7,7 @@ import ctypes
 
 import numpy as np
 
-from .coco_match import CELLS_PER_BLOCK, GRID_CAP, MAX_AREA, MAX_DET, MAX_THR, _device      # noqa: F401  (one launch shape for both kernels)
+from .coco_match import CELLS_PER_BLOCK, GRID_CAP, MAX_AREA, MAX_DET, MAX_THR      # noqa: F401  (one launch shape for both kernels)
 
 # include/ssd_hip.h (tests/test_coco_accumulate_host.py compares them with the header)
 MAX_MAXDETS = 4
@@ -104,6 +104,7 @@ def launch(segments_host, segments_dev, order, rank, matched, ignored, nd, gt_ig
     float64 [T, R, K, A, M], recall float64 [T, K, A, M]."""
     import torch
     from ._lib import check, lib
+    from .metric_calls import stream
     segments_host = np.ascontiguousarray(segments_host, SEGMENT_DTYPE)
     max_dets = np.ascontiguousarray(max_dets, np.int32).reshape(-1)
     rec_thr = np.ascontiguousarray(rec_thr, np.float64).reshape(-1)
@@ -113,7 +114,7 @@ def launch(segments_host, segments_dev, order, rank, matched, ignored, nd, gt_ig
                                         matched.data_ptr(), ignored.data_ptr(), int(nd), gt_ignore.data_ptr(), int(ng), int(T), int(A),
                                         max_dets.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(max_dets),
                                         rec_thr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), rec_thr_dev.data_ptr(), len(rec_thr),
-                                        precision.data_ptr(), recall.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                        precision.data_ptr(), recall.data_ptr(), stream(dev)))
 
 
 def accumulate(q, matched, ignored, gt_ignore, T, A, max_dets, rec_thr, device, timings=None):
@@ -122,33 +123,23 @@ def accumulate(q, matched, ignored, gt_ignore, T, A, max_dets, rec_thr, device, 
     timings: a dict that receives 'upload', 'launch' (HIP events) and 'download' in seconds."""
     import time
     import torch
-    dev = _device(device)
+    from . import metric_calls
+    dev = metric_calls.device_of(device)
+    up, tm = metric_calls.uploader(dev, "the matching's outputs", as_bytes=True), metric_calls.Timer(dev, timings is not None)
     K, M, R = len(q["segments"]), len(max_dets), len(rec_thr)
     rec_thr = np.ascontiguousarray(rec_thr, np.float64).reshape(-1)
     t0 = time.perf_counter()
     with torch.cuda.device(dev):
-        def up(x):
-            if isinstance(x, torch.Tensor):
-                if x.device != dev:
-                    raise ValueError("the matching's outputs live on %s, not on %s" % (x.device, dev))
-                return x
-            return torch.from_numpy(np.ascontiguousarray(x).reshape(-1).view(np.uint8)).to(dev)
         segments_dev, order, rank, thr_dev = up(q["segments"]), up(q["order"]), up(q["rank"]), up(rec_thr)
         matched, ignored, gt_ignore = up(matched), up(ignored), up(gt_ignore)
         precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
         recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
-        if timings is not None:
-            torch.cuda.current_stream(dev).synchronize()
-            t1 = time.perf_counter()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        t1, e0 = tm.uploaded(), tm.mark()
         launch(q["segments"], segments_dev, order, rank, matched, ignored, q["nd"], gt_ignore, q["ng"], T, A, max_dets, rec_thr, thr_dev,
                precision, recall)
-        if timings is not None:
-            e1.record()
-            e1.synchronize()
-            t2 = time.perf_counter()
+        launch_s = tm.seconds(e0, tm.mark())
+        t2 = time.perf_counter()
         out = precision.cpu().numpy(), recall.cpu().numpy()
         if timings is not None:
-            timings.update(upload=t1 - t0, launch=e0.elapsed_time(e1) * 1e-3, download=time.perf_counter() - t2)
+            timings.update(upload=t1 - t0, launch=launch_s, download=time.perf_counter() - t2)
     return out

@@ -117,14 +117,14 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
         world, rank = dist.get_world_size(group), dist.get_rank(group)
     mine = [m for _i, m in ChunkAssignment(world, rank, chunk).select(metas)]
     if jpeg_device is not None:
-        from .coco_match import _device
-        if not hasattr(detector, "_jpeg_records") or _device(jpeg_device).index != detector.device:
+        from .metric_calls import device_of
+        if not hasattr(detector, "_jpeg_records") or device_of(jpeg_device).index != detector.device:
             raise ValueError("jpeg_device must be the GPU of a Detector: the frames are detected where they are decoded")
     jpeg = jpeg_device is not None
     if rows_device is not None:
-        from .coco_match import _device
-        dev = _device(rows_device)
-        if metric_device is not None and _device(metric_device) != dev:
+        from .metric_calls import device_of
+        dev = device_of(rows_device)
+        if metric_device is not None and device_of(metric_device) != dev:
             raise ValueError("metric_device must be None or rows_device (%s): the rows are matched where they are built" % dev)
         ev, frags = _evaluate_records(detector, gt, mine, images_dir, read_image, workers, chunk, mapping, score_threshold, max_batch,
                                       dev, bool(predictions_json), jpeg)

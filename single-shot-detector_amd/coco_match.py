@@ -84,14 +84,6 @@ def pack(gts, dts, cat_ids, subset):
             "det_score": np.ascontiguousarray(score[order]), "gt_box": gt_box, "gt_area": gt_area, "gt_crowd": gt_crowd}
 
 
-def _device(device):
-    import torch
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("device must be a GPU (a CUDA device index or torch.device): the host loop is evaluate(device=None)")
-    return torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
-
-
 def launch(cells_host, cells_dev, det_box, det_area, nd, gt_box, gt_area, gt_crowd, ng, thr, area_rng, matched, ignored, gt_ignore, iou=None):
     """ssd_coco_match on the current stream of the tensors' device.  cells_host: CELL_DTYPE array; every other array a torch tensor
     on one GPU, of any dtype that holds the bytes: cells_dev [n * 24 bytes], float64 boxes [nd, 4] / [ng, 4] and areas [nd] / [ng],
@@ -99,6 +91,7 @@ def launch(cells_host, cells_dev, det_box, det_area, nd, gt_box, gt_area, gt_cro
     thr [T], area_rng [A, 2]: float64 values on the host."""
     import torch
     from ._lib import check, lib
+    from .metric_calls import stream
     thr = np.ascontiguousarray(thr, np.float64).reshape(-1)
     rng = np.ascontiguousarray(area_rng, np.float64).reshape(-1, 2)
     cells_host = np.ascontiguousarray(cells_host, CELL_DTYPE)
@@ -109,7 +102,7 @@ def launch(cells_host, cells_dev, det_box, det_area, nd, gt_box, gt_area, gt_cro
                                    int(nd), gt_box.data_ptr(), gt_area.data_ptr(), gt_crowd.data_ptr(), int(ng),
                                    thr.ctypes.data_as(dp), len(thr), rng.ctypes.data_as(dp), len(rng), matched.data_ptr(),
                                    ignored.data_ptr(), gt_ignore.data_ptr(), None if iou is None else iou.data_ptr(),
-                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                   stream(dev)))
 
 
 def match_device(p, thr, area_rng, device, want_iou=False, timings=None):
@@ -118,34 +111,25 @@ def match_device(p, thr, area_rng, device, want_iou=False, timings=None):
     nothing waits for it unless timings is given: a dict that receives 'upload' and 'launch' (HIP events) in seconds."""
     import time
     import torch
-    dev = _device(device)
+    from . import metric_calls
+    dev = metric_calls.device_of(device)
+    up = metric_calls.uploader(dev, "the detections' rows", contiguous=True)    # (tensors: the rows coco_rows.rows_device left on this GPU)
+    tm = metric_calls.Timer(dev, timings is not None)
     A = len(area_rng)
     nd, ng = len(p["det_area"]), len(p["gt_area"])
     t0 = time.perf_counter()
     with torch.cuda.device(dev):
-        def up(x):
-            if isinstance(x, torch.Tensor):            # rows that coco_rows.rows_device left on this GPU
-                if x.device != dev:
-                    raise ValueError("the detections' rows live on %s, not on %s" % (x.device, dev))
-                return x.contiguous()
-            return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-        cells_dev = up(p["cells"].view(np.uint8).reshape(-1))
+        cells_dev = up(p["cells"], as_bytes=True)
         det_box, det_area = up(p["det_box"]), up(p["det_area"])
         gt_box, gt_area, gt_crowd = up(p["gt_box"]), up(p["gt_area"]), up(p["gt_crowd"])
         matched = torch.empty((A, nd, 2), dtype=torch.uint8, device=dev)
         ignored = torch.empty((A, nd, 2), dtype=torch.uint8, device=dev)
         gt_ignore = torch.empty((A, ng), dtype=torch.uint8, device=dev)
         iou = torch.empty(int((p["cells"]["D"].astype(np.int64) * p["cells"]["G"]).sum()), dtype=torch.float64, device=dev) if want_iou else None
-        if timings is not None:
-            torch.cuda.current_stream(dev).synchronize()
-            t1 = time.perf_counter()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        t1, e0 = tm.uploaded(), tm.mark()
         launch(p["cells"], cells_dev, det_box, det_area, nd, gt_box, gt_area, gt_crowd, ng, thr, area_rng, matched, ignored, gt_ignore, iou)
         if timings is not None:
-            e1.record()
-            e1.synchronize()
-            timings.update(upload=t1 - t0, launch=e0.elapsed_time(e1) * 1e-3)
+            timings.update(upload=t1 - t0, launch=tm.seconds(e0, tm.mark()))
     return matched, ignored, gt_ignore, iou
 
 

@@ -434,12 +434,13 @@ class CocoBoxEval:
         timings: a dict that receives 'route' ('retained' | 'upload'), 'pack_order' and accumulate()'s parts in seconds."""
         import time
         from . import coco_accumulate as ca
+        from .metric_calls import device_of
         T, A = len(IOU_THRS), len(AREA_RNG)
         t0 = time.perf_counter()
         r = self._retained
         if r is not None and self.__dict__.get("eval_imgs", r.get("built")) is not r.get("built"):
             r = self._retained = None          # the caller replaced eval_imgs: what the GPU holds is not it
-        if r is not None and r["whole"] and r["matched"].device == ca._device(device):
+        if r is not None and r["whole"] and r["matched"].device == device_of(device):
             q = ca.pack_order(r["p"], self.cat_ids)
             matched, ignored, gt_ignore = r["matched"], r["ignored"], r["gt_ignore"]
         else:

@@ -7,7 +7,7 @@ an exclusive scan of the counts and ssd_coco_rows_fill on the current stream, th
 formats the predictions file's rows from the same flat arrays.  Both row builders raise ValueError for a record the kernels flag."""
 import numpy as np
 
-from .coco_match import CELLS_PER_BLOCK, GRID_CAP, MAX_DET, _device      # noqa: F401  (one launch shape for the family)
+from .coco_match import CELLS_PER_BLOCK, GRID_CAP, MAX_DET      # noqa: F401  (one launch shape for the family)
 from .ssd import split_records
 
 # include/ssd_hip.h (tests/test_coco_rows_host.py compares them with the header)
@@ -100,28 +100,27 @@ def rows_host(records, image_hw, label_to_cat, K, score_threshold, image_ids=Non
 def launch_count(records, image_hw, label_to_cat, K, score_threshold, counts, bad):
     """ssd_coco_rows_count on the current stream of the tensors' device: records int32 [n, 6T + 1], image_hw int32 [n, 2],
     label_to_cat int32 [num_labels], counts int32 [K, n], bad int32 [n] -- torch tensors on one GPU."""
-    import ctypes
     import torch
     from ._lib import check, lib
+    from .metric_calls import stream
     n, words = records.shape
     with torch.cuda.device(records.device):
         check(lib().ssd_coco_rows_count(records.data_ptr(), n, (words - 1) // 6, image_hw.data_ptr(), label_to_cat.data_ptr(),
                                         label_to_cat.numel(), int(K), float(score_threshold), counts.data_ptr(), bad.data_ptr(),
-                                        ctypes.c_void_p(torch.cuda.current_stream(records.device).cuda_stream)))
+                                        stream(records.device)))
 
 
 def launch_fill(records, image_hw, label_to_cat, K, score_threshold, det_begin, nd, det_box, det_area, det_score):
     """ssd_coco_rows_fill on the current stream of the tensors' device: det_begin int64 [K, n], the three row arrays float64 [nd, 4] /
     [nd] / [nd] (any dtype that holds the bytes)."""
-    import ctypes
     import torch
     from ._lib import check, lib
+    from .metric_calls import stream
     n, words = records.shape
     with torch.cuda.device(records.device):
         check(lib().ssd_coco_rows_fill(records.data_ptr(), n, (words - 1) // 6, image_hw.data_ptr(), label_to_cat.data_ptr(),
                                        label_to_cat.numel(), int(K), float(score_threshold), det_begin.data_ptr(), int(nd),
-                                       det_box.data_ptr(), det_area.data_ptr(), det_score.data_ptr(),
-                                       ctypes.c_void_p(torch.cuda.current_stream(records.device).cuda_stream)))
+                                       det_box.data_ptr(), det_area.data_ptr(), det_score.data_ptr(), stream(records.device)))
 
 
 def rows_device(records, image_hw, label_to_cat, K, score_threshold, device, image_ids=None, timings=None):
@@ -132,49 +131,42 @@ def rows_device(records, image_hw, label_to_cat, K, score_threshold, device, ima
     'download' in seconds."""
     import time
     import torch
-    dev = _device(device)
+    from . import metric_calls
+    dev = metric_calls.device_of(device)
+    up, tm = metric_calls.uploader(dev, "the records", contiguous=True), metric_calls.Timer(dev, timings is not None)
     K = int(K)
     with torch.cuda.device(dev):
-        if isinstance(records, torch.Tensor):
-            if records.device != dev:
-                raise ValueError("the records live on %s, not on %s" % (records.device, dev))
-            rec = records.contiguous()
-            if rec.dtype != torch.int32 or rec.dim() != 2 or rec.shape[1] % 6 != 1 or rec.shape[1] < 7:
-                raise ValueError("records must be an int32 block [n_images, 6T + 1]")
-        else:
-            rec = torch.from_numpy(_as_records(records)).to(dev)
+        rec = up(records if isinstance(records, torch.Tensor) else _as_records(records))
+        if rec.dtype != torch.int32 or rec.dim() != 2 or rec.shape[1] % 6 != 1 or rec.shape[1] < 7:
+            raise ValueError("records must be an int32 block [n_images, 6T + 1]")
         n = rec.shape[0]
-        hw = torch.from_numpy(_as_hw(image_hw, n)).to(dev)
-        l2c = torch.from_numpy(np.ascontiguousarray(label_to_cat, np.int32).reshape(-1)).to(dev)
+        hw = up(_as_hw(image_hw, n))
+        l2c = up(np.ascontiguousarray(label_to_cat, np.int32).reshape(-1))
         counts = torch.empty((K, n), dtype=torch.int32, device=dev)
         bad = torch.empty((n,), dtype=torch.int32, device=dev)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)] if timings is not None else None
-        mark = (lambda i: ev[i].record()) if ev else (lambda i: None)
-        mark(0)
+        e0 = tm.mark()
         launch_count(rec, hw, l2c, K, score_threshold, counts, bad)
-        mark(1)
+        e1 = tm.mark()
         t0 = time.perf_counter()
         counts_host, bad_host = counts.cpu().numpy(), bad.cpu().numpy()
         t1 = time.perf_counter()
         _raise_bad(bad_host, image_ids)
         nd = int(counts_host.sum(dtype=np.int64))
-        mark(2)
+        e2 = tm.mark()
         flat = counts.view(-1)
         det_begin = torch.cumsum(flat, 0, dtype=torch.int64) - flat
-        mark(3)
+        e3 = tm.mark()
         det_box = torch.empty((nd, 4), dtype=torch.float64, device=dev)
         det_area = torch.empty((nd,), dtype=torch.float64, device=dev)
         det_score = torch.empty((nd,), dtype=torch.float64, device=dev)
-        mark(4)
+        e4 = tm.mark()
         launch_fill(rec, hw, l2c, K, score_threshold, det_begin, nd, det_box, det_area, det_score)
-        mark(5)
+        e5 = tm.mark()
         t2 = time.perf_counter()
         score_host = det_score.cpu().numpy()
         if timings is not None:
             t3 = time.perf_counter()
-            ev[5].synchronize()
-            timings.update(count=ev[0].elapsed_time(ev[1]) * 1e-3, scan=ev[2].elapsed_time(ev[3]) * 1e-3,
-                           fill=ev[4].elapsed_time(ev[5]) * 1e-3, download=(t1 - t0) + (t3 - t2))
+            timings.update(count=tm.seconds(e0, e1), scan=tm.seconds(e2, e3), fill=tm.seconds(e4, e5), download=(t1 - t0) + (t3 - t2))
     return {"counts": counts_host, "det_box": det_box, "det_area": det_area, "det_score": score_host}
 
 

@@ -19,7 +19,7 @@
 //                                  chunk's counts read their slot and store precision[t, r].
 //                     What no row stores is stored once at the end: +0.0 for c_r > tp total (and for n == 0), E_0 -- the final running
 //                     maximum -- for c_r == 0, and recall = tp total / npig.  Every element is written exactly once; no atomics.
-#include "host.h"
+#include "metric_host.h"
 
 #include <cmath>
 
@@ -43,14 +43,6 @@ __device__ __forceinline__ int lane_value(int v, int l) { return __builtin_amdgc
 __device__ __forceinline__ double lane_value(double v, int l)
 {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-
-// the wave's own LDS row is written by some lanes and read by others: order the two sides inside the wave
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // c_r of the header: the smallest integer c >= 0 with double(c) / double(npig) >= thr; 2^31, which no count reaches, when that is
@@ -212,42 +204,25 @@ extern "C" int ssd_coco_accumulate(const ssd_coco_segment *segments_host, const 
     if (!max_dets_host) return ssd_fail(SSD_ERR_INVALID, who + ": max_dets_host is NULL");
     if (!rec_thr_host) return ssd_fail(SSD_ERR_INVALID, who + ": rec_thr_host is NULL");
     if (K > 0 && !segments_host) return ssd_fail(SSD_ERR_INVALID, who + ": segments_host is NULL");
-    const struct { const void *p; bool need; unsigned align; const char *name; } ptrs[] = {
-        {segments_dev, K > 0, 8, "segments_dev"},   {order_dev, nd > 0, 4, "order_dev"},         {rank_dev, nd > 0, 1, "rank_dev"},
-        {matched_dev, nd > 0, 2, "matched_dev"},    {ignored_dev, nd > 0, 2, "ignored_dev"},     {gt_ignore_dev, ng > 0, 1, "gt_ignore_dev"},
-        {rec_thr_dev, K > 0, 8, "rec_thr_dev"},     {precision_dev, K > 0, 8, "precision_dev"},  {recall_dev, K > 0, 8, "recall_dev"}};
-    for (const auto &q : ptrs) {
-        if (q.need && !q.p) return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " is NULL");
-        if ((uintptr_t)q.p & (q.align - 1))
-            return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " must be " + std::to_string(q.align) + "-byte aligned");
-    }
+    SSDCHK(check_ptrs(who, {{segments_dev, K > 0, 8, "segments_dev"}, {order_dev, nd > 0, 4, "order_dev"}, {rank_dev, nd > 0, 1, "rank_dev"},
+                            {matched_dev, nd > 0, 2, "matched_dev"}, {ignored_dev, nd > 0, 2, "ignored_dev"},
+                            {gt_ignore_dev, ng > 0, 1, "gt_ignore_dev"}, {rec_thr_dev, K > 0, 8, "rec_thr_dev"},
+                            {precision_dev, K > 0, 8, "precision_dev"}, {recall_dev, K > 0, 8, "recall_dev"}}));
     for (int m = 0; m < M; ++m)
         if (max_dets_host[m] < 1 || (m > 0 && max_dets_host[m] <= max_dets_host[m - 1]))
             return ssd_fail(SSD_ERR_INVALID, who + ": max_dets_host[" + std::to_string(m) + "] must be positive and above the one before");
     for (int r = 0; r < R; ++r)
         if (!std::isfinite(rec_thr_host[r]) || (r > 0 && !(rec_thr_host[r] >= rec_thr_host[r - 1])))
             return ssd_fail(SSD_ERR_INVALID, who + ": rec_thr_host[" + std::to_string(r) + "] must be finite and not below the one before");
-    int64_t det_end = 0, gt_end = 0;
-    for (int32_t k = 0; k < K; ++k) {
-        const ssd_coco_segment &seg = segments_host[k];
-        const auto bad = [&](const char *what) { return ssd_fail(SSD_ERR_INVALID, who + ": segment " + std::to_string(k) + ": " + what); };
-        if (seg.det_count < 0) return bad("det_count must not be negative");
-        if (seg.gt_count < 0) return bad("gt_count must not be negative");
-        if (seg.det_begin != det_end) return bad("det_begin must be the end of the segment before (the detection ranges tile [0, nd))");
-        if (seg.det_begin > nd - seg.det_count) return bad("det_begin + det_count runs past nd");
-        if (seg.gt_begin < gt_end) return bad("gt_begin overlaps the segment before (ranges ascend and are disjoint)");
-        if (seg.gt_begin > ng - seg.gt_count) return bad("gt_begin + gt_count runs past ng");
-        det_end = seg.det_begin + seg.det_count;
-        gt_end = seg.gt_begin + seg.gt_count;
-    }
+    const auto row = [&](int64_t k) { const ssd_coco_segment &x = segments_host[k]; return std::array<int64_t, 4>{x.det_begin, x.det_count, x.gt_begin, x.gt_count}; };
+    int64_t det_end;
+    SSDCHK(check_ranges(who, {"segment", "det_count", "gt_count", -1, -1, true}, K, nd, ng, row, &det_end));
     if (K > 0 && det_end != nd)
         return ssd_fail(SSD_ERR_INVALID, who + ": the segments' detection ranges end at " + std::to_string(det_end) + ", not at nd");
     if (K == 0) return SSD_OK;
     AccParams p;
     for (int m = 0; m < SSD_COCO_MAX_MAXDETS; ++m) p.max_dets[m] = max_dets_host[m < M ? m : 0];
-    const int64_t items = (int64_t)K * A * M, blocks = (items + CA_WAVES - 1) / CA_WAVES;
-    const unsigned grid = (unsigned)(blocks < SSD_COCO_GRID_CAP ? blocks : SSD_COCO_GRID_CAP);
-    hipLaunchKernelGGL(coco_accumulate, dim3(grid), dim3(CA_THREADS), 0, (hipStream_t)stream, segments_dev, (int)K, order_dev, rank_dev,
+    hipLaunchKernelGGL(coco_accumulate, dim3(wave_grid((int64_t)K * A * M)), dim3(CA_THREADS), 0, (hipStream_t)stream, segments_dev, (int)K, order_dev, rank_dev,
                        matched_dev, ignored_dev, nd, gt_ignore_dev, ng, (int)T, (int)A, (int)M, p, rec_thr_dev, (int)R, precision_dev,
                        recall_dev);
     HIPCHK(hipGetLastError());

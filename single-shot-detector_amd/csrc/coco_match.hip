@@ -15,7 +15,7 @@
 //                of its area range and stores one uint16.  gt_ignore in scan order is `j >= number of boxes not ignored`, written by
 //                the whole wave; so is the optional IoU dump, whose offset (the sum of D * G over the cells before) every wave
 //                carries forward from its previous cell.  No atomics; 62 976 bytes of LDS per block.
-#include "host.h"
+#include "metric_host.h"
 
 #pragma clang fp contract(off)
 
@@ -189,34 +189,14 @@ extern "C" int ssd_coco_match(const ssd_coco_cell *cells_host, const ssd_coco_ce
     if (T > SSD_COCO_MAX_THR) return ssd_fail(SSD_ERR_INVALID, t_range);
     if (A > SSD_COCO_MAX_AREA) return ssd_fail(SSD_ERR_INVALID, a_range);
     if (n_cells > 0 && !cells_host) return ssd_fail(SSD_ERR_INVALID, who + ": cells_host is NULL");
-    if (n_cells > 0 && !cells_dev) return ssd_fail(SSD_ERR_INVALID, who + ": cells_dev is NULL");
-    if ((uintptr_t)cells_dev & 7) return ssd_fail(SSD_ERR_INVALID, who + ": cells_dev must be 8-byte aligned");
-    const struct { const void *p; bool need; unsigned align; const char *name; } ptrs[] = {
-        {det_box_dev, nd > 0, 8, "det_box_dev"},   {det_area_dev, nd > 0, 8, "det_area_dev"}, {gt_box_dev, ng > 0, 8, "gt_box_dev"},
-        {gt_area_dev, ng > 0, 8, "gt_area_dev"},   {gt_crowd_dev, ng > 0, 1, "gt_crowd_dev"}, {matched_dev, nd > 0, 2, "matched_dev"},
-        {ignored_dev, nd > 0, 2, "ignored_dev"},   {gt_ignore_dev, ng > 0, 1, "gt_ignore_dev"}, {iou_dev, false, 8, "iou_dev"}};
-    for (const auto &q : ptrs) {
-        if (q.need && !q.p) return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " is NULL");
-        if ((uintptr_t)q.p & (q.align - 1))
-            return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " must be " + std::to_string(q.align) + "-byte aligned");
-    }
-    int64_t det_end = 0, gt_end = 0;
-    for (int64_t c = 0; c < n_cells; ++c) {
-        const ssd_coco_cell &cell = cells_host[c];
-        const std::string row = who + ": cell " + std::to_string(c) + ": ";
-        if (cell.D < 0 || cell.D > SSD_COCO_MAX_DET)
-            return ssd_fail(SSD_ERR_INVALID, row + "D must be in [0, " + std::to_string(SSD_COCO_MAX_DET) + "]");
-        if (cell.G < 0 || cell.G > SSD_COCO_MAX_GT)
-            return ssd_fail(SSD_ERR_INVALID, row + "G must be in [0, " + std::to_string(SSD_COCO_MAX_GT) + "]");
-        if (cell.det_begin < det_end)
-            return ssd_fail(SSD_ERR_INVALID, row + "det_begin overlaps the cell before (ranges ascend and are disjoint)");
-        if (cell.det_begin > nd - cell.D) return ssd_fail(SSD_ERR_INVALID, row + "det_begin + D runs past nd");
-        if (cell.gt_begin < gt_end)
-            return ssd_fail(SSD_ERR_INVALID, row + "gt_begin overlaps the cell before (ranges ascend and are disjoint)");
-        if (cell.gt_begin > ng - cell.G) return ssd_fail(SSD_ERR_INVALID, row + "gt_begin + G runs past ng");
-        det_end = cell.det_begin + cell.D;
-        gt_end = cell.gt_begin + cell.G;
-    }
+    SSDCHK(check_ptrs(who, {{cells_dev, n_cells > 0, 8, "cells_dev"}, {det_box_dev, nd > 0, 8, "det_box_dev"},
+                            {det_area_dev, nd > 0, 8, "det_area_dev"}, {gt_box_dev, ng > 0, 8, "gt_box_dev"},
+                            {gt_area_dev, ng > 0, 8, "gt_area_dev"}, {gt_crowd_dev, ng > 0, 1, "gt_crowd_dev"},
+                            {matched_dev, nd > 0, 2, "matched_dev"}, {ignored_dev, nd > 0, 2, "ignored_dev"},
+                            {gt_ignore_dev, ng > 0, 1, "gt_ignore_dev"}, {iou_dev, false, 8, "iou_dev"}}));
+    const auto row = [&](int64_t c) { const ssd_coco_cell &x = cells_host[c]; return std::array<int64_t, 4>{x.det_begin, x.D, x.gt_begin, x.G}; };
+    int64_t det_end;
+    SSDCHK(check_ranges(who, {"cell", "D", "G", SSD_COCO_MAX_DET, SSD_COCO_MAX_GT, false}, n_cells, nd, ng, row, &det_end));
     if (n_cells == 0) return SSD_OK;
     CocoParams p;
     for (int k = 0; k < SSD_COCO_MAX_THR; ++k) p.thr[k] = thr_host[k < T ? k : 0];
@@ -224,9 +204,7 @@ extern "C" int ssd_coco_match(const ssd_coco_cell *cells_host, const ssd_coco_ce
         p.rng[k][0] = area_rng_host[2 * (k < A ? k : 0)];
         p.rng[k][1] = area_rng_host[2 * (k < A ? k : 0) + 1];
     }
-    const int64_t blocks = (n_cells + CM_WAVES - 1) / CM_WAVES;
-    const unsigned grid = (unsigned)(blocks < SSD_COCO_GRID_CAP ? blocks : SSD_COCO_GRID_CAP);
-    hipLaunchKernelGGL(coco_match, dim3(grid), dim3(CM_THREADS), 0, (hipStream_t)stream, cells_dev, n_cells, det_box_dev, det_area_dev, nd,
+    hipLaunchKernelGGL(coco_match, dim3(wave_grid(n_cells)), dim3(CM_THREADS), 0, (hipStream_t)stream, cells_dev, n_cells, det_box_dev, det_area_dev, nd,
                        gt_box_dev, gt_area_dev, gt_crowd_dev, ng, p, (int)T, (int)A, matched_dev, ignored_dev, gt_ignore_dev, iou_dev);
     HIPCHK(hipGetLastError());
     return SSD_OK;

@@ -15,7 +15,7 @@
 //                               rank if that lies in [0, nd).  No sort, no atomics.
 //                     The four products and the two differences of a box are single float32 operations (__fmul_rn / __fsub_rn, and
 //                     contraction is off for the file): fusing a product into the subtraction changes w or h of a few boxes per million.
-#include "host.h"
+#include "metric_host.h"
 
 #include <cmath>
 
@@ -42,14 +42,6 @@ struct Row {
     int cat;                        // the category index of a kept row, -1 for every other row
     bool bad;
 };
-
-// the wave's own LDS rows are written by some lanes and read by others: order the two sides inside the wave
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // row j of the record at `rec` (include/ssd_hip.h: "Row semantics"); j >= num is no row at all
 __device__ __forceinline__ Row load_row(const RowArgs &a, const int32_t *__restrict__ rec, int j, int num, float H, float W)
@@ -180,19 +172,8 @@ int check_rows(const std::string &who, const int32_t *records_dev, int64_t n_ima
     if ((int64_t)K * n_images > INT32_MAX) return ssd_fail(SSD_ERR_INVALID, who + ": K * n_images must not pass 2^31 - 1");
     if (num_labels < 1 || num_labels > (1 << 20)) return ssd_fail(SSD_ERR_INVALID, who + ": num_labels must be in [1, 2^20]");
     if (!std::isfinite(score_threshold)) return ssd_fail(SSD_ERR_INVALID, who + ": score_threshold must be finite");
-    const struct { const void *p; const char *name; } ptrs[] = {
-        {records_dev, "records_dev"}, {image_hw_dev, "image_hw_dev"}, {label_to_cat_dev, "label_to_cat_dev"}};
-    for (const auto &q : ptrs) {
-        if (n_images > 0 && !q.p) return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " is NULL");
-        if ((uintptr_t)q.p & 3) return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " must be 4-byte aligned");
-    }
-    return SSD_OK;
-}
-
-unsigned rows_grid(int64_t n_images)
-{
-    const int64_t blocks = (n_images + CR_WAVES - 1) / CR_WAVES;
-    return (unsigned)(blocks < SSD_COCO_GRID_CAP ? blocks : SSD_COCO_GRID_CAP);
+    return check_ptrs(who, {{records_dev, n_images > 0, 4, "records_dev"}, {image_hw_dev, n_images > 0, 4, "image_hw_dev"},
+                            {label_to_cat_dev, n_images > 0, 4, "label_to_cat_dev"}});
 }
 
 }  // namespace
@@ -203,14 +184,10 @@ extern "C" int ssd_coco_rows_count(const int32_t *records_dev, int64_t n_images,
 {
     const std::string who = "ssd_coco_rows_count";
     SSDCHK(check_rows(who, records_dev, n_images, T, image_hw_dev, label_to_cat_dev, num_labels, K, score_threshold));
-    const struct { const void *p; const char *name; } outs[] = {{counts_dev, "counts_dev"}, {bad_dev, "bad_dev"}};
-    for (const auto &q : outs) {
-        if (n_images > 0 && !q.p) return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " is NULL");
-        if ((uintptr_t)q.p & 3) return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " must be 4-byte aligned");
-    }
+    SSDCHK(check_ptrs(who, {{counts_dev, n_images > 0, 4, "counts_dev"}, {bad_dev, n_images > 0, 4, "bad_dev"}}));
     if (n_images == 0) return SSD_OK;
     const RowArgs a = {records_dev, n_images, (int)T, image_hw_dev, label_to_cat_dev, (int)num_labels, (int)K, score_threshold};
-    hipLaunchKernelGGL(coco_rows<false>, dim3(rows_grid(n_images)), dim3(CR_THREADS), (size_t)CR_WAVES * 2 * T * 4, (hipStream_t)stream, a,
+    hipLaunchKernelGGL(coco_rows<false>, dim3(wave_grid(n_images)), dim3(CR_THREADS), (size_t)CR_WAVES * 2 * T * 4, (hipStream_t)stream, a,
                        counts_dev, bad_dev, (const int64_t *)nullptr, (int64_t)0, (double *)nullptr, (double *)nullptr, (double *)nullptr, 0);
     HIPCHK(hipGetLastError());
     return SSD_OK;
@@ -224,17 +201,12 @@ extern "C" int ssd_coco_rows_fill(const int32_t *records_dev, int64_t n_images, 
     const std::string who = "ssd_coco_rows_fill";
     SSDCHK(check_rows(who, records_dev, n_images, T, image_hw_dev, label_to_cat_dev, num_labels, K, score_threshold));
     if (nd < 0 || nd > INT32_MAX) return ssd_fail(SSD_ERR_INVALID, who + ": nd must be in [0, 2^31 - 1]");
-    const struct { const void *p; bool need; const char *name; } ptrs[] = {{det_begin_dev, n_images > 0, "det_begin_dev"},
-                                                                          {det_box_dev, n_images > 0 && nd > 0, "det_box_dev"},
-                                                                          {det_area_dev, n_images > 0 && nd > 0, "det_area_dev"},
-                                                                          {det_score_dev, n_images > 0 && nd > 0, "det_score_dev"}};
-    for (const auto &q : ptrs) {
-        if (q.need && !q.p) return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " is NULL");
-        if ((uintptr_t)q.p & 7) return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " must be 8-byte aligned");
-    }
+    const bool rows = n_images > 0 && nd > 0;
+    SSDCHK(check_ptrs(who, {{det_begin_dev, n_images > 0, 8, "det_begin_dev"}, {det_box_dev, rows, 8, "det_box_dev"},
+                            {det_area_dev, rows, 8, "det_area_dev"}, {det_score_dev, rows, 8, "det_score_dev"}}));
     if (n_images == 0 || nd == 0) return SSD_OK;            // no row of any image has a place
     const RowArgs a = {records_dev, n_images, (int)T, image_hw_dev, label_to_cat_dev, (int)num_labels, (int)K, score_threshold};
-    hipLaunchKernelGGL(coco_rows<true>, dim3(rows_grid(n_images)), dim3(CR_THREADS), (size_t)CR_WAVES * 2 * T * 4, (hipStream_t)stream, a,
+    hipLaunchKernelGGL(coco_rows<true>, dim3(wave_grid(n_images)), dim3(CR_THREADS), (size_t)CR_WAVES * 2 * T * 4, (hipStream_t)stream, a,
                        (int32_t *)nullptr, (int32_t *)nullptr, det_begin_dev, nd, det_box_dev, det_area_dev, det_score_dev,
                        ((uintptr_t)det_box_dev & 15) == 0 ? 1 : 0);
     HIPCHK(hipGetLastError());

@@ -4,7 +4,8 @@
 //                path shares: permute_rows / permute_bn (channel order), conv_geometry, pack_conv, upload_bn, upload_dw, pack_dw
 //   plan.hip     the layer plan of one (B,H,W): ops, streams, dependencies; enqueue
 //   stages.hip   the stage entry points the parity tests call (StagePool: their scratch), anchors, resize arithmetic, diagnostics (-DSSD_DIAG)
-// Kernels and their launch wrappers: ssd_internal.h.
+// Kernels and their launch wrappers: ssd_internal.h.  On top of this header: train_table.h (the TRAIN step's table kernels) and
+// metric_host.h (the evaluation entry points: coco_match.hip, coco_accumulate.hip, coco_rows.hip, voc_match.hip, jpeg.hip).
 #pragma once
 #include "../../include/ssd_hip.h"
 #include "ssd_internal.h"

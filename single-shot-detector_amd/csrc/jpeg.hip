@@ -1,7 +1,7 @@
 // The JPEG decoder's device stage: quantised coefficients -> uint8 RGB frames, two launches per batch whatever its size.
 // The arithmetic (IDCT, upsampling, colour), the table and every refusal: include/ssd_hip.h, block "the JPEG decoder".
 //
-//   jpeg_idct     256 lanes = 32 blocks of 8 lanes; a grid of at most SSD_COCO_GRID_CAP groups strides over ALL blocks of all
+//   jpeg_idct     256 lanes = 32 blocks of 8 lanes; a grid of at most WAVE_GRID_CAP groups (metric_host.h) strides over ALL blocks of all
 //                 components of all images (the table's block_begin: one binary search per lane, then a forward walk).
 //                 Lane r of a block loads row r of the coefficients and of the component's table (16 bytes each: a wave reads 8
 //                 blocks as 1 KiB in a row), multiplies, and writes the row into the block's LDS tile of pitch 9 words -- the
@@ -16,7 +16,7 @@
 //                 of a frame stores its bytes singly, so no byte outside a frame is written.  Chroma neighbours are clamped to
 //                 the real extent, which IS the edge rule of the header (3 c + c = 4 c).
 // No atomics, every output byte written once: two calls give the same bytes.
-#include "host.h"
+#include "metric_host.h"
 #include "jpeg_geom.h"
 
 namespace {
@@ -25,14 +25,6 @@ constexpr int JT = 256;
 constexpr int J_BLOCKS = JT / 8;                // blocks of a group per pass
 constexpr int J_PITCH = 9;                      // words between the rows of a block's LDS tile
 static_assert(SSD_JPEG_TILE == JT * SSD_JPEG_RUN, "a lane per run");
-
-// the wave's own LDS tiles are written by some lanes and read by others: order the two sides inside the wave
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // the one-dimensional kernel of the header, in uint32 (the sums wrap, nothing relies on signed overflow)
 __device__ __forceinline__ void idct_1d(const int *x, uint32_t *o)
@@ -306,20 +298,13 @@ extern "C" int ssd_jpeg_decode(const ssd_jpeg_image *images_host, const ssd_jpeg
     const std::string who = "ssd_jpeg_decode";
     int64_t blocks, tiles, ws;
     SSDCHK(check_table(who, images_host, B, &blocks, &tiles, &ws));
-    const struct { const void *p; int align; const char *name; } ptrs[] = {
-        {images_dev, 8, "images_dev"}, {coef_dev, 16, "coef_dev"}, {quant_dev, 16, "quant_dev"},
-        {workspace_dev, 16, "workspace_dev"}, {frames_dev, 16, "frames_dev"}};
-    for (const auto &q : ptrs) {
-        if (B > 0 && !q.p) return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " is NULL");
-        if ((uintptr_t)q.p & (uintptr_t)(q.align - 1))
-            return ssd_fail(SSD_ERR_INVALID, who + ": " + q.name + " must be " + std::to_string(q.align) + "-byte aligned");
-    }
+    SSDCHK(check_ptrs(who, {{images_dev, B > 0, 8, "images_dev"}, {coef_dev, B > 0, 16, "coef_dev"}, {quant_dev, B > 0, 16, "quant_dev"},
+                            {workspace_dev, B > 0, 16, "workspace_dev"}, {frames_dev, B > 0, 16, "frames_dev"}}));
     if (B == 0) return SSD_OK;
-    const int64_t g1 = (blocks + J_BLOCKS - 1) / J_BLOCKS;
-    hipLaunchKernelGGL(jpeg_idct, dim3((unsigned)(g1 < SSD_COCO_GRID_CAP ? g1 : SSD_COCO_GRID_CAP)), dim3(JT), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(jpeg_idct, dim3(capped_grid((blocks + J_BLOCKS - 1) / J_BLOCKS)), dim3(JT), 0, (hipStream_t)stream,
                        images_dev, (int)B, blocks, coef_dev, quant_dev, (uint8_t *)workspace_dev);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(jpeg_pixels, dim3((unsigned)(tiles < SSD_COCO_GRID_CAP ? tiles : SSD_COCO_GRID_CAP)), dim3(JT), 0,
+    hipLaunchKernelGGL(jpeg_pixels, dim3(capped_grid(tiles)), dim3(JT), 0,
                        (hipStream_t)stream, images_dev, (int)B, tiles, (const uint8_t *)workspace_dev, frames_dev);
     HIPCHK(hipGetLastError());
     return SSD_OK;

@@ -33,6 +33,15 @@ static inline hipError_t ssd_allow_lds(const void *fn, int bytes, std::atomic<un
     return e;
 }
 
+// A wave's own LDS rows are written by some of its lanes and read by others: order the two sides inside the wave (no other
+// wave touches the rows, so no __syncthreads).
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // floor(n / d) for 0 <= n < 2^31 without a division (Granlund-Montgomery: l = ceil(log2 d), mag = ceil(2^(31+l) / d) < 2^32,
 // q = mulhi(n, mag) >> (l - 1); d == 1: sh < 0, q = n).  The compiler's run-time division is ~22 vector instructions, this
 // is 2-3; the kernels' prologues and epilogues are paid in issue slots.  Host side fills, device side divides.

@@ -15,13 +15,11 @@
 //               (its rows ascend), and the final reduction takes the larger score and of equal scores the smaller row.  The terms
 //               of ap and iou_sum go through wave_ordered_add<2> (train_table.h): dependent additions in ascending lane order,
 //               which is ascending row order; a lane past the end adds +0.0 to sums that are never -0.0.
+#include "metric_host.h"
 #include "train_table.h"
 
 #include <climits>
 #include <cmath>
-#include <initializer_list>
-#include <string>
-#include <tuple>
 
 #pragma clang fp contract(off)
 
@@ -157,22 +155,6 @@ __global__ __launch_bounds__(VM_THREADS) void voc_curve(const ssd_voc_segment *_
     }
 }
 
-int check_ptrs(const std::string &who, const std::initializer_list<std::tuple<const void *, bool, unsigned, const char *>> &ptrs)
-{
-    for (const auto &[p, need, align, name] : ptrs) {
-        if (need && !p) return ssd_fail(SSD_ERR_INVALID, who + ": " + name + " is NULL");
-        if ((uintptr_t)p & (align - 1))
-            return ssd_fail(SSD_ERR_INVALID, who + ": " + name + " must be " + std::to_string(align) + "-byte aligned");
-    }
-    return SSD_OK;
-}
-
-unsigned grid_of(int64_t rows)
-{
-    const int64_t blocks = (rows + VM_WAVES - 1) / VM_WAVES;
-    return (unsigned)(blocks < SSD_VOC_GRID_CAP ? blocks : SSD_VOC_GRID_CAP);
-}
-
 }  // namespace
 
 extern "C" int ssd_voc_match(const ssd_voc_cell *cells_host, const ssd_voc_cell *cells_dev, int64_t n_cells, const double *det_box_dev,
@@ -190,23 +172,12 @@ extern "C" int ssd_voc_match(const ssd_voc_cell *cells_host, const ssd_voc_cell 
     SSDCHK(check_ptrs(who, {{cells_dev, n_cells > 0, 8, "cells_dev"}, {det_box_dev, nd > 0, 8, "det_box_dev"},
                             {det_pos_dev, nd > 0, 4, "det_pos_dev"}, {gt_box_dev, ng > 0, 8, "gt_box_dev"},
                             {tp_dev, nd > 0, 1, "tp_dev"}, {tp_iou_dev, nd > 0, 8, "tp_iou_dev"}}));
-    int64_t det_end = 0, gt_end = 0;
-    for (int64_t c = 0; c < n_cells; ++c) {
-        const ssd_voc_cell &cell = cells_host[c];
-        // the text is built only for a refusal: a run has tens of thousands of cells
-        const auto bad = [&](const std::string &what) { return ssd_fail(SSD_ERR_INVALID, who + ": cell " + std::to_string(c) + ": " + what); };
-        if (cell.D < 0) return bad("D must not be negative");
-        if (cell.G < 0 || cell.G > SSD_VOC_MAX_GT) return bad("G must be in [0, " + std::to_string(SSD_VOC_MAX_GT) + "]");
-        if (cell.det_begin != det_end) return bad("det_begin must be the end of the cell before (the detection ranges tile [0, nd))");
-        if (cell.det_begin > nd - cell.D) return bad("det_begin + D runs past nd");
-        if (cell.gt_begin < gt_end) return bad("gt_begin overlaps the cell before (ranges ascend and are disjoint)");
-        if (cell.gt_begin > ng - cell.G) return bad("gt_begin + G runs past ng");
-        det_end = cell.det_begin + cell.D;
-        gt_end = cell.gt_begin + cell.G;
-    }
+    const auto row = [&](int64_t c) { const ssd_voc_cell &x = cells_host[c]; return std::array<int64_t, 4>{x.det_begin, x.D, x.gt_begin, x.G}; };
+    int64_t det_end;
+    SSDCHK(check_ranges(who, {"cell", "D", "G", -1, SSD_VOC_MAX_GT, true}, n_cells, nd, ng, row, &det_end));
     if (det_end != nd) return ssd_fail(SSD_ERR_INVALID, who + ": the cells' detection ranges end at " + std::to_string(det_end) + ", not at nd");
     if (n_cells == 0) return SSD_OK;
-    hipLaunchKernelGGL(voc_match, dim3(grid_of(n_cells)), dim3(VM_THREADS), 0, (hipStream_t)stream, cells_dev, n_cells, det_box_dev,
+    hipLaunchKernelGGL(voc_match, dim3(wave_grid(n_cells)), dim3(VM_THREADS), 0, (hipStream_t)stream, cells_dev, n_cells, det_box_dev,
                        det_pos_dev, gt_box_dev, thr, tp_dev, tp_iou_dev, n_rows);
     HIPCHK(hipGetLastError());
     return SSD_OK;
@@ -232,7 +203,7 @@ extern "C" int ssd_voc_curve(const ssd_voc_segment *segments_host, const ssd_voc
         if (seg.num_gt < 1 || seg.num_gt > ((int64_t)1 << 40)) return bad("num_gt must be in [1, 2^40]");
     }
     if (n_labels == 0) return SSD_OK;
-    hipLaunchKernelGGL(voc_curve, dim3(grid_of(n_labels)), dim3(VM_THREADS), 0, (hipStream_t)stream, segments_dev, (int)n_labels, tp_dev,
+    hipLaunchKernelGGL(voc_curve, dim3(wave_grid(n_labels)), dim3(VM_THREADS), 0, (hipStream_t)stream, segments_dev, (int)n_labels, tp_dev,
                        tp_iou_dev, conf_dev, results_dev);
     HIPCHK(hipGetLastError());
     return SSD_OK;

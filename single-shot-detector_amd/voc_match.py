@@ -4,8 +4,6 @@ launch, n_labels x 64 bytes downloaded and turned into the dict Evaluator.evalua
 
 pack() and scan_cell() need numpy alone (the host tests call them); evaluate_packed() uploads, launches on the current stream and
 downloads."""
-import ctypes
-
 import numpy as np
 
 # include/ssd_hip.h (tests/test_voc_match_host.py compares them with the header)
@@ -92,14 +90,6 @@ def pack(num_classes, n_images, gt_box, gt_label, gt_image, det_box, det_label, 
             "fallback": fallback}
 
 
-def _device(device):
-    import torch
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("device must be a GPU (a CUDA device index or torch.device): the host loop is evaluate(device=None)")
-    return torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
-
-
 def launch(cells_host, cells_dev, det_box, det_pos, nd, gt_box, ng, thr, tp, tp_iou, n_rows, segments_host=None, segments_dev=None,
            conf=None, results=None):
     """ssd_voc_match and, with segments, ssd_voc_curve behind it on the current stream of the tensors' device.  cells_host /
@@ -108,10 +98,11 @@ def launch(cells_host, cells_dev, det_box, det_pos, nd, gt_box, ng, thr, tp, tp_
     segments_dev [L * 24 bytes], results [L * 64 bytes].  cells_host None: the curve alone."""
     import torch
     from ._lib import check, lib
+    from . import metric_calls
     dev = tp.device
     ptr = lambda t: None if t is None else t.data_ptr()
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = metric_calls.stream(dev)                                   # both calls on one stream
         if cells_host is not None:
             cells_host = np.ascontiguousarray(cells_host, CELL_DTYPE)
             check(lib().ssd_voc_match(cells_host.ctypes.data, ptr(cells_dev), len(cells_host), ptr(det_box), ptr(det_pos), int(nd), ptr(gt_box),
@@ -128,14 +119,15 @@ def evaluate_packed(p, thr, device, want_rows=False, timings=None):
     rows the match kernel never writes.  timings: a dict that receives 'upload', 'match', 'curve' (HIP events), 'download' in seconds."""
     import time
     import torch
+    from . import metric_calls
     if not np.isfinite(thr):
         raise ValueError("iou_threshold %r is not finite" % (thr,))
-    dev = _device(device)
+    dev = metric_calls.device_of(device)
+    up, tm = metric_calls.uploader(dev), metric_calls.Timer(dev, timings is not None)
     n_rows, nd, ng, L = p["n_rows"], len(p["det_pos"]), len(p["gt_box"]), len(p["segments"])
     t0 = time.perf_counter()
     with torch.cuda.device(dev):
-        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-        cells_dev, segments_dev = up(p["cells"].view(np.uint8).reshape(-1)), up(p["segments"].view(np.uint8).reshape(-1))
+        cells_dev, segments_dev = up(p["cells"], as_bytes=True), up(p["segments"], as_bytes=True)
         det_box, det_pos, gt_box, conf = up(p["det_box"]), up(p["det_pos"]), up(p["gt_box"]), up(p["conf"])
         if p["fallback"]:
             tp_host, iou_host = np.zeros(n_rows, np.uint8), np.zeros(n_rows, np.float64)
@@ -146,24 +138,16 @@ def evaluate_packed(p, thr, device, want_rows=False, timings=None):
             tp = torch.empty(n_rows, dtype=torch.uint8, device=dev)
             tp_iou = torch.empty(n_rows, dtype=torch.float64, device=dev)
         results = torch.empty(L * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        if timings is not None:
-            torch.cuda.current_stream(dev).synchronize()
-            t1 = time.perf_counter()
-            e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-            e[0].record()
-            launch(p["cells"], cells_dev, det_box, det_pos, nd, gt_box, ng, thr, tp, tp_iou, n_rows)
-            e[1].record()
-            launch(None, None, None, None, 0, None, 0, thr, tp, tp_iou, n_rows, p["segments"], segments_dev, conf, results)
-            e[2].record()
-            e[2].synchronize()
-            t2 = time.perf_counter()
-        else:
-            launch(p["cells"], cells_dev, det_box, det_pos, nd, gt_box, ng, thr, tp, tp_iou, n_rows, p["segments"], segments_dev, conf, results)
+        t1, e0 = tm.uploaded(), tm.mark()
+        launch(p["cells"], cells_dev, det_box, det_pos, nd, gt_box, ng, thr, tp, tp_iou, n_rows)
+        e1 = tm.mark()
+        launch(None, None, None, None, 0, None, 0, thr, tp, tp_iou, n_rows, p["segments"], segments_dev, conf, results)
+        curve, match = tm.seconds(e1, tm.mark()), tm.seconds(e0, e1)
+        t2 = time.perf_counter()
         out = results.cpu().numpy().view(RESULT_DTYPE)
         rows = (tp.cpu().numpy(), tp_iou.cpu().numpy()) if want_rows else None
         if timings is not None:
-            timings.update(upload=t1 - t0, match=e[0].elapsed_time(e[1]) * 1e-3, curve=e[1].elapsed_time(e[2]) * 1e-3,
-                           download=time.perf_counter() - t2)
+            timings.update(upload=t1 - t0, match=match, curve=curve, download=time.perf_counter() - t2)
     return (out,) + rows if want_rows else out
 
 

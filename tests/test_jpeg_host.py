@@ -213,6 +213,38 @@ def test_plan_lays_a_batch_out(ssd, host):
     assert ssd.lib().ssd_jpeg_plan(arr, 3, table, totals) == INVALID
 
 
+def test_the_entry_point_refuses_before_any_hip_call(ssd, host):
+    """No GPU here: every refusal below returns before the first HIP call, so the 'device' pointers are host addresses the call
+    never reads."""
+    L, lib = import_lib(ssd), ssd.lib()
+    info_read, _ = host
+    rc, info = info_read(_base("gray", 1, 1))
+    assert rc == OK
+    table, totals = (L.SsdJpegImage * 1)(), (ctypes.c_int64 * 4)()
+    assert lib.ssd_jpeg_plan((L.SsdJpegInfo * 1)(info), 1, table, totals) == OK
+    buf = np.zeros(4096, np.uint8)
+    fake = buf.ctypes.data + (-buf.ctypes.data) % 16
+    names = ("images_dev", "coef_dev", "quant_dev", "workspace_dev", "frames_dev")
+
+    def call(B=1, **kw):
+        a = dict({n: fake for n in names}, **kw)
+        rc = lib.ssd_jpeg_decode(table, a["images_dev"], B, a["coef_dev"], a["quant_dev"], a["workspace_dev"], a["frames_dev"], None)
+        return rc, lib.ssd_last_error().decode()
+
+    def refused(word, **kw):
+        rc, msg = call(**kw)
+        assert rc == INVALID and msg == "ssd_jpeg_decode: " + word, (rc, msg)
+
+    for name, align in zip(names, (8, 16, 16, 16, 16)):
+        refused(name + " is NULL", **{name: None})
+        refused("%s must be %d-byte aligned" % (name, align), **{name: fake + align // 2})
+        refused("%s must be %d-byte aligned" % (name, align), **{name: fake + 1})
+    refused("images_dev is NULL", **{n: None for n in names})                   # the first of the table is the one reported
+    refused("coef_dev must be 16-byte aligned", coef_dev=fake + 8, frames_dev=None)
+    assert call(B=0, **{n: None for n in names})[0] == OK
+    assert lib.ssd_jpeg_decode(None, None, 0, None, None, None, None, None) == OK
+
+
 # ----------------------------------------------------------------------------- the parser under the sanitizers
 def test_parser_under_sanitizers_on_damaged_files(tmp_path):
     """tests/jpeg_host_check.cpp + csrc/jpeg_host.cpp alone, built with -fsanitize=address,undefined: every prefix and every
