@@ -459,6 +459,41 @@ int ssd_loss_backward(const float *logits_dev, const float *codes_dev, int32_t B
                       const float *per_image_dev, int32_t per_image_stride, const ssd_loss_config *cfg,
                       const float *grad_losses_dev, float *d_logits_dev, float *d_codes_dev, void *stream);
 
+/* ---- the per-level top losses: the input of the `*_losses_on_level_*` histograms (ssd.py:135-152) ----
+ *
+ * Of every image and every pyramid level the top 20 % of the per-anchor losses, and their mean over the batch, slot by slot.  The
+ * reference takes tf.nn.top_k(sorted=False), whose slot order TensorFlow leaves open; the SET it returns is defined, and at batch 1
+ * the histogram of the mean is the histogram of that set.  For larger batches this library states its own order, single-sourced
+ * here and unpinned against TF like the NMS and argmax tie rules: DESCENDING, so that slot j is the mean over the batch of each
+ * image's j-th largest loss.
+ * Inputs: plane 0 = cls_losses_dev, plane 1 = loc_losses_dev, ssd_loss's per-anchor outputs, float32 [B, N] with row stride N,
+ *   4-byte aligned.  Levels: anchors_per_level[0 .. n_levels), 1 <= n_levels <= SSD_LOSS_MAX_LEVELS, every n_l >= 1, their sum == N;
+ *   level l of image b is the slice [off_l, off_l + n_l) of row b, off_l the sum of the levels before it.
+ * Count: k_l = ceil(n_l / 5).  The reference's ceil(fp32(n_l) * fp32(0.20)) (ssd.py:145) equals it for every n_l < 2^24 (the fp32
+ *   product of a multiple of 5 never rounds past its integer); N >= 2^24 is refused.  ssd_loss_top_counts fills k_out[n_levels] and
+ *   returns K = the sum of the k_l, or -1 for levels a call would refuse: the ONE definition of the count rule.
+ * Order: the total order on bit patterns, key = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000) compared as uint32: -0.0 lies below
+ *   +0.0, a NaN with the sign bit clear above +inf, a NaN with the sign bit set below -inf.  V[p][b][l][j], j = 0 .. k_l - 1, is the
+ *   value whose key is the j-th largest of the segment.  Equal keys are equal values: ties need no rule.
+ * Mean: M[p][l][j] = fp32( fp32( sum over b of (double)V[p][b][l][j] ) / fp32(B) ): the double sum runs from +0.0 in ascending b and
+ *   is rounded once (the reduce_sum convention of the EVAL loss), then one correctly rounded fp32 division.  Non-finite values
+ *   propagate (V holds their bits as they are; WHICH quiet NaN a mean over a NaN holds is not pinned).
+ * Output: means_dev float32 [2][K], plane-major, level l at offset sum of k_l' over l' < l; every element is written.
+ * Workspace: V, 2 * B * K floats, 16-byte aligned: ssd_loss_top_workspace_bytes (0 for a call that would be refused); its contents
+ *   need no initialisation.
+ * SSD_LOSS_TOP_MAX_K: the largest k_l a call takes (the sort buffer of one workgroup: 128 KiB of the 160 KiB of LDS), so n_l up to
+ *   163840 -- level 3 of a 1280 x 1280 frame.
+ * The call only enqueues two kernels on `stream`: no allocation, no host synchronisation, no floating-point atomics (integer LDS
+ * atomics count keys; they change no bit): two calls give the same bytes.  Needs no handle.  SSD_ERR_INVALID before any HIP call: a
+ * NULL plane or means_dev or one not 4-byte aligned; B < 1; n_levels outside [1, SSD_LOSS_MAX_LEVELS]; a NULL anchors_per_level; an
+ * n_l < 1; N (or the levels' sum) >= 2^24; a k_l above SSD_LOSS_TOP_MAX_K; levels that do not sum to N; a NULL workspace, one not
+ * 16-byte aligned or one smaller than the planner's figure. */
+#define SSD_LOSS_TOP_MAX_K 32768
+int64_t ssd_loss_top_counts(const int64_t *anchors_per_level, int32_t n_levels, int64_t *k_out);
+size_t ssd_loss_top_workspace_bytes(int32_t B, const int64_t *anchors_per_level, int32_t n_levels);
+int ssd_loss_top_means(const float *cls_losses_dev, const float *loc_losses_dev, int32_t B, int32_t N, const int64_t *anchors_per_level,
+                       int32_t n_levels, float *means_dev, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the TRAIN input pipeline: Pipeline.augmentation after the decode (pipeline.py:117-135) ----
  *
  * The host decodes each JPEG and draws the image's random scalars (the crop window included: its rejection sampling reads the

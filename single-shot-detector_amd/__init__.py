@@ -17,7 +17,7 @@ from .ckpt_import import (read_checkpoint, read_checkpoint_index, resolve_checkp
 from ._lib import build, lib, lib_path, SsdError, set_option, get_option                       # noqa: F401
 from .ssd import (SSD, AnchorGenerator, RetinaNetFeatureExtractor, RetinaNetBoxPredictor, BackboneFeatures,     # noqa: F401
                   batch_multiclass_non_max_suppression, network_input_size, Engine,
-                  get_training_targets, ssd_loss, ssd_loss_backward, differentiable_loss)
+                  get_training_targets, ssd_loss, ssd_loss_backward, differentiable_loss, level_top_means)
 from .detector import Detector                                         # noqa: F401
 from . import tiles                                                    # noqa: F401  (Detector.detect_tiled's grid, gather and merge)
 from .tiles import tile_grid                                           # noqa: F401

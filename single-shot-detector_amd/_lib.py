@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "logit_screen.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
             "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip", "train_head.hip", "wgrad.hip", "train_backbone.hip", "train_shufflenet.hip",
-            "train_first_f32.hip", "train_norms.hip", "train_hist.hip", "train_reduce.hip", "coco_match.hip", "coco_accumulate.hip", "coco_rows.hip", "voc_match.hip", "tiles.hip", "jpeg.hip",
+            "train_first_f32.hip", "train_norms.hip", "train_hist.hip", "loss_top.hip", "train_reduce.hip", "coco_match.hip", "coco_accumulate.hip", "coco_rows.hip", "voc_match.hip", "tiles.hip", "jpeg.hip",
             "jpeg_host.cpp"]        # (the one plain C++ source: the JPEG decoder's host stage, compiled without an offload target)
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
@@ -232,6 +232,9 @@ SIGNATURES = {
                                 _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "ssd_loss_backward": (ctypes.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(SsdLossConfig),
                                          _vp, _vp, _vp, _vp]),
+    "ssd_loss_top_counts": (ctypes.c_int64, [_vp, _i, _vp]),
+    "ssd_loss_top_workspace_bytes": (ctypes.c_size_t, [_i, _vp, _i]),
+    "ssd_loss_top_means": (ctypes.c_int, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, ctypes.c_size_t, _vp]),
     "ssd_augment": (ctypes.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ssd_train_update": (ctypes.c_int, [_vp, _vp, _i, ctypes.POINTER(SsdUpdateScalars), _vp]),
     "ssd_train_norms_workspace_bytes": (ctypes.c_size_t, [_vp, _i]),

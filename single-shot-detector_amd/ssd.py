@@ -405,17 +405,18 @@ def _differentiable_loss_function(torch):
 
         class SsdLossFunction(torch.autograd.Function):
             @staticmethod
-            def forward(ctx, logits, codes, anchors, groundtruth, gamma, alpha, anchors_per_level, with_per_image=False):
+            def forward(ctx, logits, codes, anchors, groundtruth, gamma, alpha, anchors_per_level, with_per_image=False,
+                        with_per_anchor=False):
                 reg, cls, matches = get_training_targets(anchors, groundtruth["boxes"], groundtruth["labels"],
                                                          groundtruth["num_boxes"])
-                losses, per_image = ssd_loss(logits, codes, anchors, groundtruth, gamma=gamma, alpha=alpha,
-                                             anchors_per_level=anchors_per_level)
+                losses, per_image, *planes = ssd_loss(logits, codes, anchors, groundtruth, gamma=gamma, alpha=alpha,
+                                                      anchors_per_level=anchors_per_level, per_anchor=with_per_anchor)
                 ctx.save_for_backward(logits, codes, reg, cls, matches, per_image)
                 ctx.gamma, ctx.alpha = gamma, alpha
-                if with_per_image:
-                    ctx.mark_non_differentiable(per_image)
-                    return losses[0], losses[1], per_image
-                return losses[0], losses[1]
+                extra = ((per_image,) if with_per_image else ()) + tuple(planes)     # planes: cls_losses, loc_losses of the SAME pass
+                if extra:
+                    ctx.mark_non_differentiable(*extra)
+                return (losses[0], losses[1]) + extra
 
             @staticmethod
             @once_differentiable
@@ -423,13 +424,13 @@ def _differentiable_loss_function(torch):
                 logits, codes, reg, cls, matches, per_image = ctx.saved_tensors
                 g = torch.stack([g_loc.reshape(()), g_cls.reshape(())]).to(torch.float32)
                 d_logits, d_codes = ssd_loss_backward(logits, codes, reg, cls, matches, per_image, ctx.gamma, ctx.alpha, g)
-                return d_logits, d_codes, None, None, None, None, None, None
+                return d_logits, d_codes, None, None, None, None, None, None, None
 
         _loss_function = SsdLossFunction
     return _loss_function
 
 
-def differentiable_loss(class_predictions, encoded_boxes, anchors, groundtruth, params, anchors_per_level=(), per_image=False):
+def differentiable_loss(class_predictions, encoded_boxes, anchors, groundtruth, params, anchors_per_level=(), per_image=False, per_anchor=False):
     """ssd.py:71-133 as a differentiable torch op: {'localization_loss', 'classification_loss'} (0-d CUDA tensors, bit-equal
     to ssd_loss's) whose backward is ssd_loss_backward.  class_predictions [B,N,C] and encoded_boxes [B,N,4] are CUDA
     float32 tensors in the reference's anchor order (non-contiguous ones are copied); anchors [N,4] (unclipped),
@@ -441,16 +442,36 @@ def differentiable_loss(class_predictions, encoded_boxes, anchors, groundtruth, 
     the HIP network.  The regularisation term of train.py (weight_decay * the sum of squared weights, model.py:132-145)
     is the caller's to add.  per_image=True adds the key 'per_image': ssd_loss's [B, 3 + levels] tensor of this forward (per image:
     localization loss, classification loss, matches, matches on each level of anchors_per_level), which carries no gradient; the
-    default return is unchanged."""
+    default return is unchanged.  per_anchor=True adds 'cls_losses' and 'loc_losses' [B,N]: ssd_loss's per-anchor planes, written by this
+    same forward (no second loss pass) and carrying no gradient -- the input of level_top_means."""
     torch = _torch()
     fn = _differentiable_loss_function(torch)
     args = (class_predictions.contiguous(), encoded_boxes.contiguous(), anchors.contiguous(), groundtruth,
             float(params["gamma"]), float(params["alpha"]), tuple(int(n) for n in anchors_per_level))
+    loc, cls, *extra = fn.apply(*args, bool(per_image), bool(per_anchor))
+    out = {"localization_loss": loc, "classification_loss": cls}
     if per_image:
-        loc, cls, rows = fn.apply(*args, True)
-        return {"localization_loss": loc, "classification_loss": cls, "per_image": rows}
-    loc, cls = fn.apply(*args, False)
-    return {"localization_loss": loc, "classification_loss": cls}
+        out["per_image"] = extra.pop(0)
+    if per_anchor:
+        out["cls_losses"], out["loc_losses"] = extra
+    return out
+
+
+def level_top_means(cls_losses, loc_losses, anchors_per_level):
+    """The input of the reference's `classification_losses_on_level_*` / `localization_losses_on_level_*` histograms
+    (ssd.py:135-152) on the GPU (ssd_loss_top_means; semantics in include/ssd_hip.h, "the per-level top losses"): cls_losses and
+    loc_losses are ssd_loss's per-anchor planes [B,N] (CUDA float32), anchors_per_level sums to N.  Returns (means [2,K], counts):
+    of every level the ceil(n / 5) largest losses of each image in descending order, averaged over the batch slot by slot; plane
+    0 classification, plane 1 localisation; level l occupies means[:, sum(counts[:l]) : sum(counts[:l + 1])].  A CUDA tensor,
+    asynchronous on the current stream."""
+    torch = _torch()
+    from . import train_calls
+    for t, n in ((cls_losses, "cls_losses"), (loc_losses, "loc_losses")):
+        _check_dev(torch, t, torch.float32, n)
+    counts = train_calls.loss_top_counts(anchors_per_level)
+    means = torch.empty((2, sum(counts)), dtype=torch.float32, device=cls_losses.device)
+    train_calls.loss_top_means(cls_losses.contiguous(), loc_losses.contiguous(), anchors_per_level, means)
+    return means, counts
 
 
 # ----------------------------------------------------------------------------- records, frames, batches

@@ -490,6 +490,53 @@ def train_histograms(rows_host, rows_dev, weight_decay, limits_dev, counts, stat
                                               stats.data_ptr(), *tail))
 
 
+# ----------------------------------------------------------------------------- the per-level top losses
+LOSS_MAX_LEVELS = 8                                                            # SSD_LOSS_MAX_LEVELS
+LOSS_TOP_MAX_K = 32768                                                         # SSD_LOSS_TOP_MAX_K
+
+
+def _level_array(anchors_per_level):
+    """anchors_per_level as the int64 array the entry points read (any length: the library refuses what it does not take)."""
+    try:
+        levels = [int(n) for n in anchors_per_level]
+    except TypeError:
+        raise ValueError("anchors_per_level must be a sequence of integers") from None
+    return (ctypes.c_int64 * max(len(levels), 1))(*levels), len(levels)
+
+
+def loss_top_counts(anchors_per_level):
+    """ssd_loss_top_counts: the per-level counts k_l = ceil(n_l / 5) as a tuple (their sum is K); SsdError for levels the family
+    refuses."""
+    arr, L = _level_array(anchors_per_level)
+    out = (ctypes.c_int64 * max(L, 1))()
+    K = lib().ssd_loss_top_counts(arr, L, out)
+    if K < 0:
+        check(-1)
+    counts = tuple(int(out[l]) for l in range(L))
+    assert sum(counts) == K
+    return counts
+
+
+def loss_top_workspace_bytes(B, anchors_per_level):
+    """ssd_loss_top_workspace_bytes: 2 * B * K floats (0: a call that would be refused)."""
+    arr, L = _level_array(anchors_per_level)
+    return lib().ssd_loss_top_workspace_bytes(int(B), arr, L)
+
+
+def loss_top_means(cls_losses, loc_losses, anchors_per_level, means, workspace=None):
+    """ssd_loss_top_means: cls_losses and loc_losses float32 [B,N] (ssd_loss's per-anchor planes), anchors_per_level summing to N;
+    means float32 [2,K] (K = sum(loss_top_counts(anchors_per_level))) receives the mean over the batch of every image's j-th
+    largest loss of each level, plane 0 the classification, plane 1 the localisation losses."""
+    B, N = _dense(cls_losses, "cls_losses", (None, None))
+    _dense(loc_losses, "loc_losses", (B, N))
+    arr, L = _level_array(anchors_per_level)
+    _dense(means, "means", (2, sum(loss_top_counts(anchors_per_level))))
+    dev = _one_gpu(workspace, cls_losses=cls_losses, loc_losses=loc_losses, means=means)
+    fn = lib().ssd_loss_top_means
+    _run(dev, workspace, lambda: lib().ssd_loss_top_workspace_bytes(B, arr, L),
+         lambda *tail: fn(cls_losses.data_ptr(), loc_losses.data_ptr(), B, N, arr, L, means.data_ptr(), *tail))
+
+
 # ----------------------------------------------------------------------------- the TRAIN step's gradient exchange
 REDUCE_ROW_BYTES = 32                                                          # sizeof(ssd_reduce_row)
 REDUCE_HEADER_FLOATS = 16                                                      # SSD_REDUCE_HEADER_FLOATS

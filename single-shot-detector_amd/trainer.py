@@ -305,6 +305,8 @@ class Trainer:
         self._last_summary = None           # the last step of THIS run with a summary
         self._last_rate = None              # (step, time) of the last summary event: global_step/sec
         self._hist_ring = None              # pinned read-back slots of the histograms, made by the first due step
+        self.loss_histograms = False        # train()'s option: off enqueues, allocates and writes nothing
+        self._loss_top = None               # the per-level top losses' buffers and table, made by the first due step that wants them
         self._writers = {}                  # logdir -> summaries.EventFileWriter
         self.last = None                    # the newest examined step's log_record
 
@@ -333,7 +335,11 @@ class Trainer:
                 p.grad = None
             eb, cp = self.head(self.fpn(self.backbone(images)))
             want_summary = summary_due(self.global_step + 1, self._last_summary, self.save_summary_steps)
-            if want_summary or self._exchange is not None:      # the loss with its per-image rows: the matches per level (ssd.py:154-163)
+            want_top = want_summary and self.loss_histograms and self.rank == 0
+            if want_top:                                        # ... and its per-anchor planes, of the same pass (ssd.py:135-152)
+                out = differentiable_loss(cp, eb, self.anchors, gt, self.loss_config, anchors_per_level=self.anchors_per_level,
+                                          per_image=True, per_anchor=True)
+            elif want_summary or self._exchange is not None:    # the loss with its per-image rows: the matches per level (ssd.py:154-163)
                 out = differentiable_loss(cp, eb, self.anchors, gt, self.loss_config, anchors_per_level=self.anchors_per_level,
                                           per_image=True)
             else:
@@ -345,10 +351,11 @@ class Trainer:
                 header = torch.stack([out["per_image"][:, 2].sum(), loc.detach(), cls.detach()])
                 loc, cls, _weights = self._exchange.exchange(header)
             sums, bad = self.train_step.norms()         # before the update: of the variables this step computed with
-            hist = None
+            hist = top = None
             if want_summary:
                 if self.rank == 0:
                     hist = self.train_step.histograms()     # beside the norms, of the same variables and gradients
+                    top = self._loss_top_histograms(out["cls_losses"], out["loc_losses"]) if want_top else None
                 self._last_summary = self.global_step + 1
             t = self.train_step.step()
             slot = self._ring[t % RING]
@@ -363,6 +370,13 @@ class Trainer:
                 slot["hist"]["counts"].copy_(hist[0], non_blocking=True)
                 slot["hist"]["stats"].copy_(hist[1], non_blocking=True)
                 slot["hist"]["per_image"].copy_(out["per_image"], non_blocking=True)
+                slot["hist"]["has_top"] = top is not None
+                if top is not None:
+                    if "top_counts" not in slot["hist"]:
+                        slot["hist"].update(top_counts=torch.empty(top[0].shape, dtype=torch.int64).pin_memory(),
+                                            top_stats=torch.empty(top[1].shape, dtype=torch.uint8).pin_memory())
+                    slot["hist"]["top_counts"].copy_(top[0], non_blocking=True)
+                    slot["hist"]["top_stats"].copy_(top[1], non_blocking=True)
             slot["losses"][0:1].copy_(loc.detach().reshape(1), non_blocking=True)
             slot["losses"][1:2].copy_(cls.detach().reshape(1), non_blocking=True)
             slot["sums"].copy_(sums, non_blocking=True)
@@ -373,6 +387,36 @@ class Trainer:
         while len(self._pending) > 1:                   # step t - 1 (and older), after step t was enqueued
             self._examine(self._pending[0])
         return t
+
+    def _loss_top_histograms(self, cls_losses, loc_losses):
+        """(counts, stats) of the ten `*_losses_on_level_*` histograms of this step (include/ssd_hip.h, "the per-level top losses"):
+        ssd_loss_top_means into a persistent [2,K] buffer, then ssd_train_histograms over a table of 2 * L rows, row p * L + l the
+        K-slice of plane p and level l (no gradient: only plane 0 of a row counts; m, v and ema point at the row itself, where the
+        table's checks accept them, and are never dereferenced).  The buffers, the limits and the table are made and uploaded by the
+        first call; every later call enqueues the five launches and nothing else."""
+        import torch
+        from . import train_calls
+        from .train_step import TENSOR_DTYPE, block_starts
+        if self._loss_top is None:
+            counts = train_calls.loss_top_counts(self.anchors_per_level)
+            L, K = len(counts), sum(counts)
+            means = torch.empty((2, K), dtype=torch.float32, device=self.device)
+            starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+            rows = np.zeros(2 * L, TENSOR_DTYPE)
+            ptrs = np.array([means.data_ptr() + 4 * (p * K + int(starts[l])) for p in range(2) for l in range(L)], np.uint64)
+            for field in ("w", "m", "v", "ema"):
+                rows[field] = ptrs
+            rows["count"] = np.tile(np.asarray(counts, np.int64), 2)
+            rows["first_block"], _blocks = block_starts(ptrs, rows["count"])
+            host = torch.from_numpy(rows.view(np.uint8).copy())
+            limits = torch.from_numpy(train_calls.histogram_limits().copy()).to(self.device)
+            self._loss_top = {"means": means, "host": host, "dev": host.to(self.device), "limits": limits,
+                              "counts": torch.empty((2 * L, 2, limits.numel()), dtype=torch.int64, device=self.device),
+                              "stats": torch.empty((2 * L, 2, train_calls.STATS_BYTES), dtype=torch.uint8, device=self.device)}
+        top = self._loss_top
+        train_calls.loss_top_means(cls_losses, loc_losses, self.anchors_per_level, top["means"])
+        train_calls.train_histograms(top["host"], top["dev"], np.float32(0.0), top["limits"], top["counts"], top["stats"])
+        return top["counts"], top["stats"]
 
     def _examine(self, slot):
         assert slot is self._pending[0]
@@ -423,6 +467,14 @@ class Trainer:
             histograms[name + "_hist"] = histogram_proto(limits, counts[t, 0], stats[t, 0])
             if stats[t, 1]["num"] > 0:
                 histograms[name + "_grad_hist"] = histogram_proto(limits, counts[t, 1], stats[t, 1])
+        if hist.get("has_top"):                         # ssd.py:135-152: row p * L + l of the table, plane 0
+            top_counts = hist["top_counts"].numpy()
+            top_stats = hist["top_stats"].numpy().view(STATS_DTYPE)[:, :, 0]
+            L = top_counts.shape[0] // 2
+            for p, kind in enumerate(("classification", "localization")):
+                for l in range(L):
+                    histograms[MATCHES_SCOPE + "%s_losses_on_level_%d" % (kind, 3 + l)] = \
+                        histogram_proto(limits, top_counts[p * L + l, 0], top_stats[p * L + l, 0])
         rate = None
         if self._last_rate is not None and now > self._last_rate[1]:
             rate = (step - self._last_rate[0]) / (now - self._last_rate[1])
@@ -498,15 +550,20 @@ class Trainer:
         return bool(_all_gather_ints([int(mine)], self.group, small)[0, 0])
 
     def train(self, max_steps=None, save_checkpoints_steps=None, save_checkpoints_secs=SAVE_CHECKPOINTS_SECS, log_every=100, on_step=None,
-              save_summary_steps=0):
+              save_summary_steps=0, loss_histograms=False):
         """Steps until global_step == max_steps (default num_steps), checkpoints on schedule and at the end.  on_step(step) is
         called after each enqueued step; when it returns True the loop ends early (train_and_evaluate's evaluations).
         save_summary_steps: 0 no summaries | n: model_dir/events.out.tfevents.* gets the scalars and the histograms of every variable
-        and gradient at the run's first step and then every n steps (summary_due)."""
+        and gradient at the run's first step and then every n steps (summary_due).
+        loss_histograms: with summaries on, every summary event also gets the reference's ten `classification_losses_on_level_3..7`
+        / `localization_losses_on_level_3..7` histograms (ssd.py:135-152; rank 0's batch under `group`): of each image the top 20 %
+        of a level's per-anchor losses in descending order, averaged over the batch slot by slot (include/ssd_hip.h, "the per-level
+        top losses": the set is the reference's, the slot order is this library's).  Off: nothing is enqueued, allocated or written."""
         max_steps = int(self.config["num_steps"] if max_steps is None else max_steps)
         self.log_every = int(log_every)
         summary_due(0, None, save_summary_steps)        # refuses a negative value
         self.save_summary_steps = int(save_summary_steps)
+        self.loss_histograms = bool(loss_histograms)
         try:
             while self.global_step < max_steps:
                 t = self.step()
@@ -523,9 +580,10 @@ class Trainer:
         return self.global_step
 
     def train_and_evaluate(self, max_steps=None, eval_every_steps=None, eval_every_secs=EVAL_THROTTLE_SECS, save_checkpoints_steps=None,
-                           save_checkpoints_secs=SAVE_CHECKPOINTS_SECS, log_every=100, on_eval=None, save_summary_steps=0):
+                           save_checkpoints_secs=SAVE_CHECKPOINTS_SECS, log_every=100, on_eval=None, save_summary_steps=0,
+                           loss_histograms=False):
         """tf.estimator.train_and_evaluate (train.py:61-66): trains, evaluates on schedule and once more at the end.  Returns the
-        list of evaluation dicts; on_eval(dict) is called with each as it is made.  save_summary_steps: train()'s; when set, every
+        list of evaluation dicts; on_eval(dict) is called with each as it is made.  save_summary_steps, loss_histograms: train()'s; when set, every
         evaluation's scalar entries are also written to model_dir/eval/events.out.tfevents.* at its step."""
         max_steps = int(self.config["num_steps"] if max_steps is None else max_steps)
         summary_due(0, None, save_summary_steps)
@@ -541,7 +599,7 @@ class Trainer:
                     on_eval(results[-1])
                 last[0], last[1] = t, time.monotonic()
             return False
-        self.train(max_steps, save_checkpoints_steps, save_checkpoints_secs, log_every, on_step, save_summary_steps)
+        self.train(max_steps, save_checkpoints_steps, save_checkpoints_secs, log_every, on_step, save_summary_steps, loss_histograms)
         results.append(self.evaluate())
         if on_eval is not None:
             on_eval(results[-1])
