@@ -2,6 +2,7 @@
 scripts/eval_from_disk.py (JPEGs of the 13 COCO-typical sizes, 480 x 640 class, 4:2:0, quality 90):
 
     python scripts/jpeg_cost.py [--images 1040] [--rounds 3] [--parent DIR] [--log profiles/jpeg_decode_cost.log]
+    python scripts/jpeg_cost.py --tree DIR --folder DIR [--only rows_device] [--gc] [--label NAME] [--rounds 5]
 
   per image    PIL decode on one core; ssd_jpeg_info_read + ssd_jpeg_entropy on one core (into pinned memory); the upload of a
                32-image batch's coefficients, tables and table rows (HIP events); ssd_jpeg_decode's two launches on that batch
@@ -12,9 +13,12 @@ scripts/eval_from_disk.py (JPEGs of the 13 COCO-typical sizes, 480 x 640 class, 
   --parent DIR another checkout of this repository (the commit before the decoder) with its library built: a child process of this
                script imports THAT tree and times its default and rows_device routes on the same folder, once in front of and once
                behind this tree's rounds.
+  --tree DIR   the end-to-end routes of the checkout at DIR alone, in this one process, on --folder: a change and its parent commit
+               timed alternately, process after process (profiles/records_route_refactor_ab.log).
 There is no speed gate: no ratio was promised in advance, the log says what was measured, whichever way it comes out."""
 import argparse
 import ctypes
+import gc
 import json
 import os
 import subprocess
@@ -28,7 +32,10 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--parent", default=None)
 ap.add_argument("--log", default=None)
 ap.add_argument("--tree", default=None, help="(the child's mode) time the default routes of the checkout at this path on --folder")
-ap.add_argument("--folder", default=None)
+ap.add_argument("--folder", default=None, help="(the child's mode) the folder; written first when it holds no instances.json")
+ap.add_argument("--only", default=None, help="(the child's mode) all four routes whose name contains this, not the two default ones")
+ap.add_argument("--gc", action="store_true", help="(the child's mode) an untimed gc.collect() in front of every timed route")
+ap.add_argument("--label", default="parent", help="(the child's mode) what the printed lines begin with")
 args = ap.parse_args()
 ROOT = os.path.abspath(args.tree) if args.tree else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -73,6 +80,8 @@ def harness(det, gt, d, routes, rounds, say, label):
         want = None
         for name, kw in (routes if r % 2 == 0 else routes[::-1]):
             path = os.path.join(d, "pred_%s.json" % name.replace(" ", "_"))
+            if args.gc:                                         # (a full collection then never falls into a timed route)
+                gc.collect()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             st = ssd_amd.coco_eval.evaluate(det, gt, d, predictions_json=path, **kw)
@@ -87,12 +96,20 @@ def harness(det, gt, d, routes, rounds, say, label):
     return times
 
 
+ROUTES = [("default", {}), ("jpeg_device=0", {"jpeg_device": 0}), ("rows_device=0", {"rows_device": 0}),
+          ("jpeg_device=0, rows_device=0", {"jpeg_device": 0, "rows_device": 0})]
+
+
 def child():
-    """The other checkout's default routes on the folder; prints the lines the parent process relays."""
+    """The checkout at --tree on the folder, one fresh process: its default and rows_device routes (the lines the parent process
+    relays), or with --only every route of that name -- two trees timed alternately, run after run, on one folder."""
+    if not os.path.exists(os.path.join(args.folder, "instances.json")):
+        os.makedirs(args.folder, exist_ok=True)
+        write_folder(args.folder, args.images)
     gt = json.load(open(os.path.join(args.folder, "instances.json")))
     det = ssd_amd.Detector(ssd_amd.synthetic_weights(P, seed=0, logits_bias=-7.5), config=P)
-    harness(det, gt, args.folder, [("default", {}), ("rows_device=0", {"rows_device": 0})], args.rounds, lambda s: print(s, flush=True),
-            "parent")
+    routes = [r for r in ROUTES if args.only in r[0]] if args.only else [ROUTES[0], ROUTES[2]]
+    harness(det, gt, args.folder, routes, args.rounds, lambda s: print(s, flush=True), args.label + (" gc" if args.gc else ""))
 
 
 def main():
@@ -187,9 +204,7 @@ def main():
         % (len(blobs), os.cpu_count()))
     relay()
     det = ssd_amd.Detector(ssd_amd.synthetic_weights(P, seed=0, logits_bias=-7.5), config=P)
-    routes = [("default", {}), ("jpeg_device=0", {"jpeg_device": 0}), ("rows_device=0", {"rows_device": 0}),
-              ("jpeg_device=0, rows_device=0", {"jpeg_device": 0, "rows_device": 0})]
-    harness(det, gt, d, routes, args.rounds, say, "this tree")
+    harness(det, gt, d, ROUTES, args.rounds, say, "this tree")
     relay()
     say("every route's statistics and predictions file equal the default route's in every round")
     say("no ratio was promised in advance, this is what was measured")

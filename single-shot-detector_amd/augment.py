@@ -12,7 +12,6 @@ cb, cr), grayscale, pixel scale (probability, key), four jitter numbers per kept
 """
 import collections
 import ctypes
-import os
 import time
 
 import numpy as np
@@ -20,6 +19,7 @@ import numpy as np
 from . import tfrecords
 from ._lib import check, lib
 from .config import load_train_config
+from .distributed import read_worker_count
 
 AUG_COLOR, AUG_GRAY, AUG_SCALE, AUG_FLIP = 1, 2, 4, 8          # SSD_AUG_* of include/ssd_hip.h
 # ssd_augment_params of include/ssd_hip.h (64 bytes, no padding)
@@ -367,7 +367,7 @@ class TrainPipeline:
         self.order_rng = np.random.default_rng(order_seq)
         self.aug_rng = np.random.default_rng(aug_seq)
         self.decode = decode or tfrecords.decode_image
-        self.read_workers = max(1, int(read_workers if read_workers is not None else min(16, os.cpu_count() or 1)))
+        self.read_workers = read_worker_count(read_workers)
         self.device = int(device)
         self.channels_first = bool(channels_first)
         self.epochs = epochs

@@ -10,6 +10,7 @@ which is the standard 80-name COCO order (COCO_NAMES below); the official catego
 from the annotation file (name -> id), exactly as cell 7 builds `integer_to_coco_id`.
 """
 import json
+import os
 
 import numpy as np
 
@@ -31,12 +32,11 @@ def integer_to_coco_id(categories):
     return {labels[c["name"]]: c["id"] for c in categories}
 
 
-def detection_records(detector, image, image_id, label_to_coco_id, score_threshold=0.15, detections=None):
-    """One image -> COCO result dicts, exactly as cell 10: boxes scaled to pixels of the
-    ORIGINAL image, x, y = int(xmin), int(ymin); w, h = int(xmax - xmin), int(ymax - ymin).
-    `detections` = (boxes, labels, scores) already computed for this image (a batched run), else the detector is called."""
-    height, width, _ = image.shape
-    boxes, labels, scores = detections if detections is not None else detector(image, score_threshold=score_threshold)
+def result_rows(hw, image_id, label_to_coco_id, detections):
+    """One image's (boxes, labels, scores) -> COCO result dicts, exactly as cell 10: boxes scaled to pixels of the ORIGINAL image
+    of (height, width) `hw`, x, y = int(xmin), int(ymin); w, h = int(xmax - xmin), int(ymax - ymin)."""
+    height, width = hw
+    boxes, labels, scores = detections
     scaler = np.array([height, width, height, width], dtype="float32")
     boxes = np.asarray(boxes, np.float32).reshape(-1, 4) * scaler
     # cell 10 per detection: x, y = int(xmin), int(ymin); w, h = int(xmax - xmin), int(ymax - ymin) on float32 values -- the same
@@ -49,15 +49,65 @@ def detection_records(detector, image, image_id, label_to_coco_id, score_thresho
     return [{"image_id": image_id, "category_id": c, "bbox": [xi, yi, wi, hi], "score": s} for c, xi, yi, wi, hi, s in zip(cats, x, y, w, h, sc)]
 
 
+def detection_records(detector, image, image_id, label_to_coco_id, score_threshold=0.15, detections=None):
+    """One image -> COCO result dicts (result_rows).  `detections` = (boxes, labels, scores) already computed for this image (a
+    batched run), else the detector is called."""
+    height, width, _ = image.shape
+    if detections is None:
+        detections = detector(image, score_threshold=score_threshold)
+    return result_rows((height, width), image_id, label_to_coco_id, detections)
+
+
+def _rows_of(image_ids, shapes, detections, label_to_coco_id):
+    return [row for image_id, hw, d in zip(image_ids, shapes, detections) for row in result_rows(hw, image_id, label_to_coco_id, d)]
+
+
 def detection_records_many(detector, images, image_ids, label_to_coco_id, score_threshold=0.15, max_batch=32):
     """The same for a list of images of any sizes, with the detector's batched form when it has one (Detector.detect_many: images
     grouped by the size the network sees, frames of different source sizes in one batch; each result bit for bit the single call's)."""
-    many = getattr(detector, "detect_many", None)
-    dets = many(images, score_threshold=score_threshold, max_batch=max_batch) if many else [None] * len(images)
-    out = []
-    for image, image_id, d in zip(images, image_ids, dets):
-        out += detection_records(detector, image, image_id, label_to_coco_id, score_threshold, detections=d)
-    return out
+    dets, shapes = _HostChunk(None, images).detections(detector, score_threshold, max_batch)
+    return _rows_of(image_ids, shapes, dets, label_to_coco_id)
+
+
+class _HostChunk:
+    """A chunk of evaluate(): the metas of consecutive images and the images themselves, decoded on the host."""
+
+    def __init__(self, metas, images):
+        self.metas, self.images = metas, images
+
+    def records_into(self, detector, block, max_batch):
+        """Every image's unfiltered record into its row of `block`, a record block on the detector's GPU (nothing waits) -> the
+        images' (height, width)."""
+        detector.detect_many_records(self.images, block, max_batch=max_batch)
+        return [im.shape[:2] for im in self.images]
+
+    def detections(self, detector, score_threshold, max_batch):
+        """-> ((boxes, labels, scores) per image, the images' (height, width)): Detector.detect_many, or one call per image of
+        a detector that has no batched form."""
+        many = getattr(detector, "detect_many", None)
+        dets = (many(self.images, score_threshold=score_threshold, max_batch=max_batch) if many
+                else [detector(im, score_threshold=score_threshold) for im in self.images])
+        return dets, [im.shape[:2] for im in self.images]
+
+
+class _JpegChunk:
+    """The same chunk as a batch of the detector's JPEG decoder (JpegDecoder.begin's): the frames come into being on the GPU and
+    are detected where they lie; a file the decoder refuses is read from `images_dir` with `read_image` and takes the host route."""
+
+    def __init__(self, metas, batch, images_dir, read_image):
+        self.metas, self.batch, self.images_dir, self.read_image = metas, batch, images_dir, read_image
+
+    def _fallback_at(self, i):
+        return self.read_image(os.path.join(self.images_dir, self.metas[i]["file_name"]))
+
+    def records_into(self, detector, block, max_batch):
+        return detector._jpeg_records(self.batch, block, max_batch, self._fallback_at)
+
+    def detections(self, detector, score_threshold, max_batch):
+        from .detector import filtered_records
+        block = detector.engine.new_records(len(self.metas), "cuda:%d" % detector.device)
+        shapes = self.records_into(detector, block, max_batch)
+        return filtered_records(block, score_threshold), shapes
 
 
 def evaluate(detector, annotations_json, images_dir, read_image=None, predictions_json="coco_predictions.json", out=None,
@@ -97,10 +147,12 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     core; include/ssd_hip.h "the JPEG decoder"): chunk k + 1 is read and entropy-decoded while chunk k is detected.  A file the
     decoder refuses (progressive, CMYK, not a JPEG, ..) is read with `read_image` and takes the host route.  The frames are PIL's
     bit for bit, so with the default reader the statistics and the predictions file are the same, byte for byte; combinable with
-    `rows_device` and `metric_device`.  A chunk's frames must stay below 2 GiB (256 files of 1600 x 1600)."""
-    import os
+    `rows_device` and `metric_device`.  A chunk's frames must stay below 2 GiB (256 files of 1600 x 1600).
+
+    Either way the images arrive as chunk objects (_HostChunk, _JpegChunk: `metas`, `records_into`, `detections`) from
+    _read_chunks, and the loops below do not know which."""
     from . import coco_metric
-    from .distributed import ChunkAssignment
+    from .distributed import ChunkAssignment, read_worker_count
     if read_image is None:
         from PIL import Image
 
@@ -109,77 +161,69 @@ def evaluate(detector, annotations_json, images_dir, read_image=None, prediction
     gt = json.load(open(annotations_json)) if isinstance(annotations_json, str) else annotations_json
     mapping = integer_to_coco_id(gt["categories"])
     metas = sorted(gt["images"], key=lambda m: m["id"])
-    workers = max(1, int(read_workers if read_workers is not None else min(16, os.cpu_count() or 1)))
     if group is None:
         world, rank = 1, 0
     else:
         import torch.distributed as dist
         world, rank = dist.get_world_size(group), dist.get_rank(group)
     mine = [m for _i, m in ChunkAssignment(world, rank, chunk).select(metas)]
+    ids = [m["id"] for m in mine]
     if jpeg_device is not None:
+        from .detector import Detector
         from .metric_calls import device_of
-        if not hasattr(detector, "_jpeg_records") or device_of(jpeg_device).index != detector.device:
+        if not isinstance(detector, Detector) or device_of(jpeg_device).index != detector.device:
             raise ValueError("jpeg_device must be the GPU of a Detector: the frames are detected where they are decoded")
-    jpeg = jpeg_device is not None
     if rows_device is not None:
         from .metric_calls import device_of
         dev = device_of(rows_device)
         if metric_device is not None and device_of(metric_device) != dev:
             raise ValueError("metric_device must be None or rows_device (%s): the rows are matched where they are built" % dev)
-        ev, frags = _evaluate_records(detector, gt, mine, images_dir, read_image, workers, chunk, mapping, score_threshold, max_batch,
-                                      dev, bool(predictions_json), jpeg)
-        return _finish(ev, frags, metas, chunk, group, world, rank, predictions_json, out, dev)
-    results, frags = [], []
-    for part, images in (_read_jpeg_chunks if jpeg else _read_chunks)(mine, images_dir, read_image, workers, chunk, detector):
-        # images read, then detected as batches grouped by network shape (the notebook's loop, one image per sess.run, at batch throughput)
-        if jpeg:
-            rows = _jpeg_detection_records(detector, part, images, mapping, score_threshold, max_batch)
-        else:
-            rows = detection_records_many(detector, images, [m["id"] for m in part], mapping, score_threshold, max_batch)
-        results += rows
-        if predictions_json:
-            frags.append(json.dumps(rows)[1:-1].encode())      # json.dump of the whole list joins these with ", "
-    ev = coco_metric.CocoBoxEval(gt, results)
-    ev.evaluate(img_ids=[m["id"] for m in mine], device=metric_device, unpack=False)
+        metric_device = dev
+    workers = read_worker_count(read_workers)
+    if jpeg_device is None:
+        # chunk k + 1 is being read and decoded while chunk k is consumed (PIL and cv2 release the interpreter lock while they decode)
+        chunks = _read_chunks(mine, images_dir, workers, chunk, read_image, 0,
+                              lambda part, files, pool: _HostChunk(part, [f.result() for f in files]))
+    else:
+        # the threads read the files' bytes and run the decoder's entropy stage (plain C behind ctypes: the interpreter lock is
+        # released): chunk k + 1 is being entropy-decoded while chunk k is consumed, and the files of chunk k + 2 are being read
+        dec = detector.jpeg_decoder()
+        chunks = _read_chunks(mine, images_dir, workers, chunk, _read_file, 1, lambda part, files, pool: _JpegChunk(
+            part, dec.begin([f.result() for f in files], pool), images_dir, read_image))
+    frags = []
+    if rows_device is not None:
+        import torch
+        with torch.cuda.device(dev):
+            ev = _evaluate_records(detector, gt, chunks, ids, mapping, score_threshold, max_batch, dev, frags if predictions_json else None)
+    else:
+        results = []
+        for c in chunks:
+            # images read, then detected as batches grouped by network shape (the notebook's loop, one image per sess.run, at batch throughput)
+            dets, shapes = c.detections(detector, score_threshold, max_batch)
+            rows = _rows_of([m["id"] for m in c.metas], shapes, dets, mapping)
+            results += rows
+            if predictions_json:
+                frags.append(json.dumps(rows)[1:-1].encode())      # json.dump of the whole list joins these with ", "
+        ev = coco_metric.CocoBoxEval(gt, results)
+        ev.evaluate(img_ids=ids, device=metric_device, unpack=False)
     return _finish(ev, frags, metas, chunk, group, world, rank, predictions_json, out, metric_device)
 
 
-def _jpeg_detection_records(detector, part, batch, mapping, score_threshold, max_batch):
-    """detection_records_many for one chunk that arrives as a decoder batch (_read_jpeg_chunks): the same rows."""
-    from .ssd import score_filter, split_records
-    records = detector.engine.new_records(len(part), "cuda:%d" % detector.device)
-    shapes = detector._jpeg_records(batch, records, max_batch, batch.fallback_at)
-    boxes, labels, scores, num = split_records(records.cpu().numpy())
-    out = []
-    for i, (m, (h, w)) in enumerate(zip(part, shapes)):
-        d = score_filter(boxes[i], labels[i], scores[i], num[i], score_threshold)
-        out += detection_records(detector, np.empty((h, w, 0), np.uint8), m["id"], mapping, score_threshold, detections=d)
-    return out
-
-
-def _evaluate_records(detector, gt, mine, images_dir, read_image, workers, chunk, mapping, score_threshold, max_batch, dev, want_json,
-                      jpeg=False):
-    """evaluate()'s detection and matching of the images `mine` without a result dict: -> the evaluated CocoBoxEval (outputs on
-    `dev`) and the predictions file's fragments per chunk."""
-    import torch
+def _evaluate_records(detector, gt, chunks, ids, mapping, score_threshold, max_batch, dev, frags):
+    """evaluate()'s detection and matching of the images `ids`, chunk by chunk, without a result dict: -> the evaluated CocoBoxEval
+    (outputs on `dev`); the predictions file's fragment of every chunk is appended to `frags` unless that is None."""
     from . import coco_metric, coco_rows
-    records = detector.engine.new_records(len(mine), dev)
-    frags, shapes, k = [], [], 0
-    with torch.cuda.device(dev):
-        for part, images in (_read_jpeg_chunks if jpeg else _read_chunks)(mine, images_dir, read_image, workers, chunk, detector):
-            block = records[k:k + len(part)]
-            if jpeg:
-                shapes += detector._jpeg_records(images, block, max_batch, images.fallback_at)
-            else:
-                detector.detect_many_records(images, block, max_batch=max_batch)
-                shapes += [im.shape[:2] for im in images]
-            if want_json:
-                frags.append(coco_rows.write_predictions(block.cpu().numpy(), [m["id"] for m in part], shapes[k:], mapping, score_threshold))
-            k += len(part)
-        ids = [m["id"] for m in mine]
-        ev = coco_metric.CocoBoxEval.from_records(gt, records, ids, mapping, score_threshold, device=dev, image_hw=shapes)
-        ev.evaluate(img_ids=ids, device=dev, unpack=False)
-    return ev, frags
+    records = detector.engine.new_records(len(ids), dev)
+    shapes, k = [], 0
+    for c in chunks:
+        block = records[k:k + len(c.metas)]
+        shapes += c.records_into(detector, block, max_batch)
+        if frags is not None:
+            frags.append(coco_rows.write_predictions(block.cpu().numpy(), ids[k:k + len(c.metas)], shapes[k:], mapping, score_threshold))
+        k += len(c.metas)
+    ev = coco_metric.CocoBoxEval.from_records(gt, records, ids, mapping, score_threshold, device=dev, image_hw=shapes)
+    ev.evaluate(img_ids=ids, device=dev, unpack=False)
+    return ev
 
 
 def _finish(ev, frags, metas, chunk, group, world, rank, predictions_json, out, metric_device):
@@ -208,51 +252,27 @@ def _finish(ev, frags, metas, chunk, group, world, rank, predictions_json, out, 
     return ev.accumulate(device=metric_device).summarize(out if rank == 0 else None)
 
 
-def _read_chunks(metas, images_dir, read_image, workers, chunk, detector=None):
-    """(metas of a chunk, its decoded images) for consecutive chunks of `metas`; the next chunk is read while the caller
-    works on this one (PIL and cv2 release the interpreter lock while they decode)."""
-    import os
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=workers) as pool:
-        def start(k):
-            return [pool.submit(read_image, os.path.join(images_dir, m["file_name"])) for m in metas[k:k + chunk]]
-        ahead = start(0)
-        for k in range(0, len(metas), chunk):
-            images = [f.result() for f in ahead]
-            ahead = start(k + chunk)
-            yield metas[k:k + chunk], images
-
-
 def _read_file(path):
     with open(path, "rb") as f:
         return f.read()
 
 
-def _read_jpeg_chunks(metas, images_dir, read_image, workers, chunk, detector):
-    """(metas of a chunk, its decoder batch) for consecutive chunks of `metas`: the threads read the files' bytes and run the JPEG
-    decoder's entropy stage (plain C behind ctypes: the interpreter lock is released); chunk k + 1 is being entropy-decoded while
-    the caller detects chunk k, and the files of chunk k + 2 are being read.  batch.fallback_at(i) reads file i of the chunk with
-    `read_image` (a file the decoder refuses)."""
-    import os
+def _read_chunks(metas, images_dir, workers, chunk, read, ahead, build):
+    """The chunk objects of consecutive chunks of `metas`, on one thread pool: read(path) runs on the pool for every file of a
+    chunk, build(the chunk's metas, those futures, the pool) makes its object.  Chunk k + ahead is built and the reads of chunk
+    k + ahead + 1 are submitted just before chunk k is handed out, so they proceed while the caller works on chunk k."""
     from concurrent.futures import ThreadPoolExecutor
-    dec = detector.jpeg_decoder()
+    parts = [metas[k:k + chunk] for k in range(0, len(metas), chunk)]
     with ThreadPoolExecutor(max_workers=workers) as pool:
-        def read(k):
-            return [pool.submit(_read_file, os.path.join(images_dir, m["file_name"])) for m in metas[k:k + chunk]]
-
-        def begin(k, files):
-            part = metas[k:k + chunk]
-            batch = dec.begin([f.result() for f in files], pool)
-            batch.fallback_at = lambda i: read_image(os.path.join(images_dir, part[i]["file_name"]))
-            return batch
-        files = read(0)
-        ahead = begin(0, files) if metas else None
-        files = read(chunk)
-        for k in range(0, len(metas), chunk):
-            batch = ahead
-            ahead = begin(k + chunk, files) if k + chunk < len(metas) else None
-            files = read(k + 2 * chunk)
-            yield metas[k:k + chunk], batch
+        def submit(j):
+            return [pool.submit(read, os.path.join(images_dir, m["file_name"])) for m in parts[j]] if j < len(parts) else []
+        files, built = submit(0), []
+        for i in range(len(parts) + ahead):         # round i: chunk i is built, chunk i + 1 is read, chunk i - ahead goes out
+            if i < len(parts):
+                built.append(build(parts[i], files, pool))
+            files = submit(i + 1)
+            if i >= ahead:
+                yield built.pop(0)
 
 
 # ----------------------------------------------------------------------------- VOC-style AP self-check

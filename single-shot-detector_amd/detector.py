@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from .config import load_config
-from .ssd import Engine, _torch, host_frame, mixed_batches, score_filter
+from .ssd import Engine, _torch, host_frame, mixed_batches, record_batches, score_filter, split_records
 from .pb_import import load_pb_weights
 from .ckpt_import import load_ckpt_weights, resolve_checkpoint
 from .variables import load_weights
@@ -28,6 +28,12 @@ def _pil_rgb(blob):
     from PIL import Image
     with Image.open(io.BytesIO(blob)) as im:
         return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
+def filtered_records(records, score_threshold):
+    """A record block [B, 6T + 1] (a tensor; downloaded here) -> (boxes, labels, scores) of every image at `score_threshold`."""
+    boxes, labels, scores, num = split_records(records.cpu().numpy())
+    return [score_filter(boxes[i], labels[i], scores[i], num[i], score_threshold) for i in range(len(num))]
 
 
 class Detector:
@@ -149,28 +155,28 @@ class Detector:
                 consume(pending)
         return out
 
+    def _records_argument(self, name, records, items, convert):
+        """The refusals the records routes share, in their order: mode f32; every item taken by `convert` (which refuses its own);
+        `records` a tensor on this detector's GPU with len(items) rows of the engine's.  Returns the converted items."""
+        torch = _torch()
+        if self.engine.precision != "f32":
+            raise ValueError("%s runs in precision mode f32 only" % name)
+        items = [convert(x) for x in items]
+        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.device.index == self.device):
+            raise ValueError("records must be a tensor on cuda:%d" % self.device)
+        self.engine._check_records(records, len(items))
+        return items
+
     def detect_many_records(self, images, records, max_batch=32):
         """`detect_many` for a caller that keeps the detections on the GPU: the same grouping and the same batches, but the record of
         image i (ssd.split_records) is left UNFILTERED in row i of `records`, a contiguous device int32 tensor [len(images), 6T + 1]
         on this detector's GPU -- bit for bit ssd.pack_records of what detect_many's batches produce.  Nothing is downloaded and
-        nothing waits: the forwards and the row copies are enqueued on the current stream.  Returns `records`.  Mode f32 only
-        (mode f16x3 needs the per-batch status check of detect_batch): ValueError otherwise."""
-        torch = _torch()
-        if self.engine.precision != "f32":
-            raise ValueError("detect_many_records runs in precision mode f32 only")
-        imgs = [host_frame(im, "every image") for im in images]
-        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.device.index == self.device):
-            raise ValueError("records must be a tensor on cuda:%d" % self.device)
-        self.engine._check_records(records, len(imgs))
-        parts = mixed_batches(self.engine, [im.shape[:2] for im in imgs], max_batch)
+        nothing waits: the forwards and the row copies (ssd.record_batches) are enqueued on the current stream.  Returns `records`.
+        Mode f32 only (mode f16x3 needs the per-batch status check of detect_batch): ValueError otherwise."""
+        imgs = self._records_argument("detect_many_records", records, images, lambda im: host_frame(im, "every image"))
         with self.engine.lock:
-            for part in parts:
-                if part == list(range(part[0], part[0] + len(part))):
-                    self.engine.forward_mixed_host([imgs[i] for i in part], records[part[0]:part[0] + len(part)])
-                else:
-                    block = self.engine.new_records(len(part), records.device)
-                    self.engine.forward_mixed_host([imgs[i] for i in part], block)
-                    records.index_copy_(0, torch.tensor(part, dtype=torch.int64).to(records.device, non_blocking=True), block)
+            record_batches(self.engine, [im.shape[:2] for im in imgs], max_batch, records,
+                           lambda part, block: self.engine.forward_mixed_host([imgs[i] for i in part], block))
         return records
 
     # ------------------------------------------------------------------------- from JPEG bytes, decoded on the GPU
@@ -200,37 +206,22 @@ class Detector:
 
     def _jpeg_records(self, batch, records, max_batch, fallback_at):
         """The records of one decoder batch (JpegDecoder.begin's) into `records` [len(batch.blobs), 6T + 1] on this GPU, row for
-        row: the accepted files as mixed-size batches straight from the decoded frames, the refused ones -- fallback_at(index) ->
-        ndarray -- through detect_many_records.  Returns every file's (height, width).  The caller holds no lock."""
-        torch = _torch()
+        row: the accepted files as mixed-size batches straight from the decoded frames, then the refused ones -- fallback_at(index)
+        -> ndarray -- as mixed-size batches of host frames, both through ssd.record_batches.  Returns every file's (height, width).
+        The caller holds no lock."""
         (flat, hw, offsets), refused = self.jpeg_decoder().finish(batch)
-        n = len(batch.blobs)
-        taken = [i for i in range(n) if i not in refused]
-        shapes = [None] * n
-        for i, s in zip(taken, hw):
-            shapes[i] = s
-
-        def rows(idx):
-            return torch.tensor(idx, dtype=torch.int64).to(records.device, non_blocking=True)
+        taken = [i for i in range(len(batch.blobs)) if i not in refused]
+        shapes = dict(zip(taken, hw))
         with self.engine.lock:
-            for part in mixed_batches(self.engine, hw, max_batch):
-                frames = (flat, [hw[j] for j in part], [offsets[j] for j in part])
-                dst = [taken[j] for j in part]
-                if dst == list(range(dst[0], dst[0] + len(dst))):
-                    self.engine.forward_mixed(frames, records[dst[0]:dst[0] + len(dst)])
-                else:
-                    block = self.engine.new_records(len(part), records.device)
-                    self.engine.forward_mixed(frames, block)
-                    records.index_copy_(0, rows(dst), block)
-        if refused:
-            idx = sorted(refused)
-            imgs = [host_frame(fallback_at(i), "every image") for i in idx]
-            for i, im in zip(idx, imgs):
-                shapes[i] = tuple(int(v) for v in im.shape[:2])
-            block = self.engine.new_records(len(idx), records.device)
-            self.detect_many_records(imgs, block, max_batch=max_batch)
-            records.index_copy_(0, rows(idx), block)
-        return shapes
+            record_batches(self.engine, hw, max_batch, records, lambda part, block: self.engine.forward_mixed(
+                (flat, [hw[j] for j in part], [offsets[j] for j in part]), block), taken)
+        idx = sorted(refused)
+        imgs = [host_frame(fallback_at(i), "every image") for i in idx]
+        shapes.update((i, tuple(int(v) for v in im.shape[:2])) for i, im in zip(idx, imgs))
+        with self.engine.lock:
+            record_batches(self.engine, [shapes[i] for i in idx], max_batch, records,
+                           lambda part, block: self.engine.forward_mixed_host([imgs[j] for j in part], block), idx)
+        return [shapes[i] for i in range(len(batch.blobs))]
 
     def detect_many_records_jpeg(self, blobs, records, max_batch=32, fallback=None, pool=None):
         """`detect_many_records` for JPEG BYTES: the files are entropy-decoded on the host (on `pool`, a concurrent.futures
@@ -240,12 +231,7 @@ class Detector:
         ..) goes through `fallback(bytes) -> uint8 RGB ndarray` (default: PIL) and the host route.  Group k + 1 of the files is
         entropy-decoded while group k computes.  Returns (records, [(height, width) of every file]).  Mode f32 only."""
         torch = _torch()
-        if self.engine.precision != "f32":
-            raise ValueError("detect_many_records_jpeg runs in precision mode f32 only")
-        blobs = [b if isinstance(b, bytes) else bytes(b) for b in blobs]
-        if not (isinstance(records, torch.Tensor) and records.is_cuda and records.device.index == self.device):
-            raise ValueError("records must be a tensor on cuda:%d" % self.device)
-        self.engine._check_records(records, len(blobs))
+        blobs = self._records_argument("detect_many_records_jpeg", records, blobs, lambda b: b if isinstance(b, bytes) else bytes(b))
         fallback = fallback or _pil_rgb
         dec, shapes = self.jpeg_decoder(), []
         with self.engine.lock, torch.cuda.device(self.device):      # (the decoder's two buffers are this detector's: one caller at a time)
@@ -266,8 +252,7 @@ class Detector:
             return self.detect_many([fallback(b) for b in blobs], score_threshold, max_batch)
         records = self.engine.new_records(len(blobs), "cuda:%d" % self.device)
         self.detect_many_records_jpeg(blobs, records, max_batch, fallback, pool)
-        boxes, labels, scores, num = self.engine.record_views(records.cpu().numpy())
-        return [score_filter(boxes[i], labels[i], scores[i], num[i], score_threshold) for i in range(len(blobs))]
+        return filtered_records(records, score_threshold)
 
     def detect_tiled(self, image, tile=None, overlap=0.25, full_frame=True, score_threshold=0.1, max_batch=32):
         """`__call__` for a frame much LARGER than the network's input (a 1200 x 1600 camera frame at min_dimension 640), where

@@ -6,6 +6,8 @@ collective exists on the path.
 
 Record per image: ssd.split_records (6T+1 32-bit words, 48 004 B at T = 2000).
 """
+import os
+
 import torch
 import torch.distributed as dist
 
@@ -217,6 +219,11 @@ def launch_local(nproc, module, argv, env=None):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(int(nproc)),
            "--master-addr", "127.0.0.1", "--master-port", str(port), "--module", module] + list(argv)
     return subprocess.call(cmd, env=env)
+
+
+def read_worker_count(read_workers=None):
+    """The threads that read and decode a chunk's files: `read_workers`, by default min(16, CPUs); at least one."""
+    return max(1, int(read_workers if read_workers is not None else min(16, os.cpu_count() or 1)))
 
 
 class ChunkAssignment:

@@ -127,7 +127,7 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
     order -- equal or the adjacent float32."""
     from concurrent.futures import ThreadPoolExecutor
     from . import tfrecords
-    from .distributed import ChunkAssignment
+    from .distributed import ChunkAssignment, read_worker_count
     lc = load_loss_config(config)
     eng = detector.engine
     reg = detector.regularization_loss(lc["weight_decay"])
@@ -142,7 +142,7 @@ def evaluate(detector, val_dataset, config, max_batch=32, read_workers=None, dec
     run = _Run(eng)
     sums = np.zeros(4, np.float64)
     count = 0
-    workers = max(1, int(read_workers if read_workers is not None else min(16, os.cpu_count() or 1)))
+    workers = read_worker_count(read_workers)
     if group is None:
         world, rank = 1, 0
     else:

@@ -21,7 +21,7 @@ def _up16(n):
 
 class _Batch:
     """A batch between begin() and finish(): its pinned slot, the first plan and the entropy jobs."""
-    __slots__ = ("blobs", "slot", "taken", "infos", "plan", "jobs", "refused", "done", "fallback_at")
+    __slots__ = ("blobs", "slot", "taken", "infos", "plan", "jobs", "refused", "done")
 
 
 class JpegDecoder:

@@ -542,6 +542,23 @@ def mixed_batches(engine, shapes, max_batch):
     return parts
 
 
+def record_batches(engine, shapes, max_batch, records, enqueue, rows=None):
+    """The records of mixed_batches' parts into rows of `records`, a record block of the caller's: frame i belongs in row rows[i]
+    (default: row i).  For every part, in mixed_batches' order, enqueue(part, block) must write len(part) records into `block`:
+    the slice of `records` itself when the part's rows are consecutive and ascending, else a block of
+    engine.new_records(len(part), records.device) that one indexed copy then moves to the rows.  Holds no lock and checks no
+    device -- the caller's business; every other row of `records` keeps what it held."""
+    import torch
+    for part in mixed_batches(engine, shapes, max_batch):
+        dst = part if rows is None else [rows[i] for i in part]
+        if dst == list(range(dst[0], dst[0] + len(dst))):
+            enqueue(part, records[dst[0]:dst[0] + len(dst)])
+        else:
+            block = engine.new_records(len(part), records.device)
+            enqueue(part, block)
+            records.index_copy_(0, torch.tensor(dst, dtype=torch.int64).to(records.device, non_blocking=True), block)
+
+
 # ----------------------------------------------------------------------------- whole graph
 class Engine:
     """Owns one ssd_handle: weights + workspace on one GPU.  `forward` is the frozen

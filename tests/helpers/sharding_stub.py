@@ -1,5 +1,5 @@
 """A stand-in Detector for the sharding tests without a GPU: its engine has the record interface detect_many_sharded uses
-(record_words, network_shape, MIXED_MAX, forward_mixed_host(images, records=...)) and writes, per image, a record that is a
+(record_words, network_shape, MIXED_MAX, new_records, forward_mixed_host(images, records=...)) and writes, per image, a record that is a
 pure function of the image -- a varying number of detections, zero included, scores on both sides of the threshold and
 garbage beyond num_boxes."""
 import threading
@@ -37,6 +37,10 @@ class StubEngine:
 
     def network_shape(self, height, width):
         return (-(-height // 64) * 64, -(-width // 64) * 64)
+
+    def new_records(self, B, dev):
+        import torch
+        return torch.empty((B, self.record_words), dtype=torch.int32, device=dev)
 
     def forward_mixed_host(self, images, records):
         import torch

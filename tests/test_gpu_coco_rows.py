@@ -305,6 +305,7 @@ def test_coco_eval_end_to_end_from_records(cuda, ssd, tiny, tmp_path, monkeypatc
     st_dict = ssd.coco_eval.evaluate(det, gt, str(tmp_path), predictions_json=a, max_batch=4, chunk=4, metric_device=0)
     calls = []
     monkeypatch.setattr(ssd.coco_eval, "detection_records", lambda *args, **kw: calls.append(1))
+    monkeypatch.setattr(ssd.coco_eval, "result_rows", lambda *args, **kw: calls.append(1))     # (what builds the dicts, for either caller)
     st_rec = ssd.coco_eval.evaluate(det, gt, str(tmp_path), predictions_json=b, max_batch=4, chunk=4, rows_device=0)
     assert not calls
     assert len(st_rec) == 12 and all(float(x) == float(y) for x, y in zip(st_rec, st_dict)), (st_rec, st_dict)

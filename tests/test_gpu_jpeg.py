@@ -178,7 +178,7 @@ def detector(cuda, ssd):
 
 
 def twelve_files():
-    """12 JPEGs of three source sizes (two network shapes), samplings mixed, one progressive among them."""
+    """12 JPEGs of three source sizes (three network shapes), samplings mixed, one progressive among them."""
     blobs = []
     for k in range(12):
         h, w = ((128, 128), (100, 151), (97, 203))[k % 3]
@@ -200,6 +200,42 @@ def test_detect_many_jpeg_equals_detect_many_on_pil_arrays(cuda, detector):
     rec_want = detector.detect_many_records(arrays, detector.engine.new_records(12, dev).zero_(), max_batch=4)
     rec_got, shapes = detector.detect_many_records_jpeg(blobs, detector.engine.new_records(12, dev).zero_(), max_batch=4)
     assert cuda.equal(rec_want, rec_got) and shapes == [a.shape[:2] for a in arrays]
+
+
+def test_refused_files_at_the_ends_and_across_group_boundaries(cuda, ssd, detector):
+    """The twelve files with 0, 1, 4, 5 and 11 progressive as well (7 is): a refused file in the first row, in the last row and on both
+    sides of the boundary between the decoder groups [0, 5) and [5, 10) (JPEG_GROUP = 5 on this instance: three groups), the
+    accepted 128 x 128 files of the second group in non-consecutive rows, and the refused 100 x 151 files of the first group as
+    ONE host batch into rows 1 and 4 (a fresh block and the indexed copy on the refused route too).  The rows equal pack_records of what detect_many's own
+    batches produce for the PIL arrays -- mixed_batches' parts through Engine.detect_host_mixed, the call detect_many makes and
+    nothing this route runs -- and detect_many_jpeg equals detect_many."""
+    blobs = twelve_files()
+    for k in (0, 1, 4, 5, 11):
+        blobs[k] = progressive(jpeg_cases.pil_rgb(blobs[k]))
+    arrays = [jpeg_cases.pil_rgb(b) for b in blobs]
+    shapes = [a.shape[:2] for a in arrays]
+    assert set(shapes) == {(128, 128), (100, 151), (97, 203)}
+    parts = ssd.ssd.mixed_batches(detector.engine, shapes, 4)
+    assert len({detector.engine.network_shape(*s) for s in shapes}) == 3          # (128 x 128, 128 x 256, 128 x 384: every part strides)
+    assert all(p != list(range(p[0], p[0] + len(p))) for p in parts if len(p) > 1) and max(map(len, parts)) == 4
+    want = np.zeros((12, detector.engine.record_words), np.int32)
+    for part in parts:
+        want[part] = ssd.ssd.pack_records(*detector.engine.detect_host_mixed([arrays[i] for i in part]))
+    detector.JPEG_GROUP = 5
+    try:
+        assert detector._jpeg_groups(blobs) == [(0, 5), (5, 10), (10, 12)]
+        rec = detector.engine.new_records(12, "cuda:%d" % detector.device).fill_(-1)
+        got, got_shapes = detector.detect_many_records_jpeg(blobs, rec, max_batch=4)
+        assert got is rec and cuda.equal(rec.cpu(), cuda.from_numpy(want)) and got_shapes == shapes
+        many = detector.detect_many(arrays, score_threshold=0.15, max_batch=4)
+        from_jpeg = detector.detect_many_jpeg(blobs, score_threshold=0.15, max_batch=4)
+    finally:
+        del detector.JPEG_GROUP
+    assert sum(len(m[2]) for m in many) > 20
+    for i, (m, j) in enumerate(zip(many, from_jpeg)):
+        b, l, s, n = ssd.ssd.split_records(want[i:i + 1])
+        for x, y, z in zip(m, j, ssd.ssd.score_filter(b[0], l[0], s[0], n[0], 0.15)):
+            assert x.dtype == y.dtype == z.dtype and np.array_equal(x, y) and np.array_equal(x, z)
 
 
 def test_coco_evaluate_from_jpeg_bytes_equals_the_default_route(cuda, ssd, detector, tmp_path):
@@ -238,3 +274,35 @@ def test_coco_evaluate_from_jpeg_bytes_equals_the_default_route(cuda, ssd, detec
         assert blob == base_file, kw
     with pytest.raises(ValueError):
         ssd.coco_eval.evaluate(detector, gt, str(tmp_path), predictions_json=None, jpeg_device=1)
+
+
+def test_the_records_routes_refuse_alike(cuda, ssd, detector):
+    """The refusals detect_many_records and detect_many_records_jpeg share, by type and text."""
+    blobs = twelve_files()[:3]
+    arrays = [jpeg_cases.pil_rgb(b) for b in blobs]
+    dev = "cuda:%d" % detector.device
+    routes = (("detect_many_records", lambda r: detector.detect_many_records(arrays, r)),
+              ("detect_many_records_jpeg", lambda r: detector.detect_many_records_jpeg(blobs, r)))
+    words = detector.engine.record_words
+    for name, call in routes:
+        detector.engine.set_precision("f16x3")
+        try:
+            with pytest.raises(ValueError) as e:
+                call(detector.engine.new_records(3, dev))
+        finally:
+            detector.engine.set_precision("f32")
+        assert str(e.value) == "%s runs in precision mode f32 only" % name
+        for records in (cuda.zeros((3, words), dtype=cuda.int32), np.zeros((3, words), np.int32), None):
+            with pytest.raises(ValueError) as e:
+                call(records)
+            assert str(e.value) == "records must be a tensor on cuda:%d" % detector.device
+        for records in (detector.engine.new_records(4, dev), detector.engine.new_records(3, dev).float(),
+                        detector.engine.new_records(6, dev)[::2]):
+            with pytest.raises(ValueError) as e:
+                call(records)
+            assert str(e.value) == "records must be a contiguous int32 tensor [B, %d]" % words
+    gt = {"images": [], "annotations": [], "categories": [{"id": i + 1, "name": n} for i, n in enumerate(ssd.coco_eval.COCO_NAMES)]}
+    for bad in ({"detector": detector, "jpeg_device": detector.device + 1}, {"detector": lambda im, score_threshold: None, "jpeg_device": 0}):
+        with pytest.raises(ValueError) as e:
+            ssd.coco_eval.evaluate(bad["detector"], gt, "", predictions_json=None, jpeg_device=bad["jpeg_device"])
+        assert str(e.value) == "jpeg_device must be the GPU of a Detector: the frames are detected where they are decoded"
