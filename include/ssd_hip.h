@@ -1528,6 +1528,118 @@ size_t ssd_jpeg_workspace_bytes(const ssd_jpeg_image *images_host, int32_t B);  
 int ssd_jpeg_decode(const ssd_jpeg_image *images_host, const ssd_jpeg_image *images_dev, int32_t B, const int16_t *coef_dev,
                     const uint16_t *quant_dev, void *workspace_dev, uint8_t *frames_dev, void *stream);
 
+/* ---- the JPEG encoder: uint8 RGB frames in device memory -> baseline JPEG bytes, the write-side twin of the block above ----
+ *
+ * data/create_tfrecords.py re-encodes every grayscale file as an RGB JPEG with PIL's default save (to_jpeg_bytes); python -m
+ * ssd_amd.create_tfrecords --jpeg_device does the same without a pixel on the host.  The encode splits where the decode does:
+ * everything in front of the quantised coefficients is integer arithmetic with a fixed definition and runs on the GPU
+ * (csrc/jpeg_enc.hip: ssd_jpeg_encode, two launches per batch), the Huffman coding and the marker structure are serial and run
+ * on the HOST (csrc/jpeg_emit.cpp, plain C++: ssd_jpeg_emit).  The definition below is the one libjpeg(-turbo)'s default
+ * compressor implements (jccolor.c, jcsample.c, jfdctint.c "slow integer", jcdctmgr.c, jchuff.c, jcmarker.c -- public algorithms,
+ * restated), which is what PIL's Image.save(format="jpeg") writes: the files are that encoder's, byte for byte.  This block is the
+ * single statement of the rules for the kernels, the host stage, tests/helpers/jpeg_enc_ref.py and jpeg.py.
+ *
+ * Input: uint8 RGB frames [height, width, 3], height and width from 1 to 65 535; any byte address.
+ * quality 1 .. 100 (PIL's default: 75) by jpeg_quality_scaling: scale = 5000 / quality (integer division) below 50, else
+ *   200 - 2 quality; entry = clamp((base * scale + 50) / 100, 1, 255) on the Annex K base tables (luma for component 0, chroma for
+ *   components 1 and 2).  ssd_jpeg_quant_tables writes the two tables, uint16 [2][64] in natural order.
+ * sampling: SSD_JPEG_SAMPLING_420 (luma 2x2, PIL's default) or SSD_JPEG_SAMPLING_444 (1x1); chroma factors are 1x1.  Any other
+ *   value, 422 included, is SSD_ERR_UNSUPPORTED.  Anything else out of range is SSD_ERR_INVALID.
+ *
+ * Colour (16 fractional bits; every sum is positive and below 2^32, the code forms it in uint32):
+ *   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *   Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ * Geometry as the decoder's: mcus_x = ceil(width / (8 h)), mcus_y = ceil(height / (8 v)); a component's PADDED grid is
+ *   (mcus_y * v_c) rows by (mcus_x * h_c) blocks.  Its OWN whole blocks are ceil(width h_c / (8 h)) by ceil(height v_c / (8 v)).
+ * Edge replication: a full-size plane (luma; chroma of 4:4:4) continues its last column and its last row.
+ * Downsampling (4:2:0 chroma, "h2v2" box): the converted plane continues its last column first, and its last row to an even row
+ *   count; out[j][i] = (s[2j][2i] + s[2j][2i+1] + s[2j+1][2i] + s[2j+1][2i+1] + bias) >> 2 with bias 1 for even i, 2 for odd i
+ *   (every output column counts, replicated ones too); the ceil(height / 2) rows so formed then continue their last ROW.
+ * Forward DCT of a block ("slow integer", CONST_BITS 13, PASS1_BITS 2) on d = sample - 128:
+ *   pass 1 over the ROWS, pass 2 over the COLUMNS of pass 1's result; D(x, n) = (x + 2^(n-1)) >> n, arithmetic shift.
+ *   The one-dimensional kernel on d0 .. d7, n = 11 in pass 1 and 15 in pass 2:
+ *     t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4
+ *     t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2
+ *     out0, out4 = (t10 + t11) << 2, (t10 - t11) << 2 in pass 1;  D(t10 + t11, 2), D(t10 - t11, 2) in pass 2
+ *     z1 = (t12 + t13) * 4433;  out2 = D(z1 + t13 * 6270, n),  out6 = D(z1 - t12 * 15137, n)
+ *     z1 = t4 + t7, z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7, z5 = (z3 + z4) * 9633
+ *     t4 *= 2446, t5 *= 16819, t6 *= 25172, t7 *= 12299
+ *     z1 *= -7373, z2 *= -20995, z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5
+ *     out7 = D(t4 + z1 + z3, n), out5 = D(t5 + z2 + z4, n), out3 = D(t6 + z2 + z3, n), out1 = D(t7 + z1 + z4, n)
+ *   32-bit two's complement (the code forms the sums in uint32: nothing rests on signed overflow; no sum leaves int32 here).
+ * Quantisation: the result carries a factor 8; coefficient = sign(x) * ((|x| + 4 q) / (8 q)), integer division: x / (8 q)
+ *   rounded to nearest, halves away from zero.
+ * Dummy blocks: a component's plane is replicated only up to its OWN whole blocks; the remaining blocks of its padded grid (4:2:0
+ *   luma with an odd count of 8-blocks in either direction) are dummy blocks: all AC coefficients zero, the DC of the block coded
+ *   before it.  In the stream a dummy block is therefore "DC difference 0, end of block", and the predictor is unchanged.
+ * Coefficients: THE DECODER'S LAYOUT -- int16 [64] per block in natural order, quantised, a component's blocks in raster order
+ *   over its padded grid, the components one after the other.  ssd_jpeg_encode writes dummy blocks as 64 zeros; ssd_jpeg_emit
+ *   never reads them.
+ * The file, in this order: SOI; APP0 JFIF 1.01, units 0, density 1 x 1, no thumbnail; DQT table 0; DQT table 1 (8-bit entries in
+ *   zigzag order); SOF0 (precision 8; components 1, 2, 3 with tables 0, 1, 1); DHT DC 0, AC 0, DC 1, AC 1: the Annex K tables, not
+ *   optimised; SOS (tables 0/0, 1/1, 1/1; 0, 63, 0); the scan; EOI.  No restart interval.  The scan: MCUs in raster order, in an
+ *   MCU the luma blocks (row by row) then Cb then Cr; per block the DC difference to the component's predictor as category +
+ *   bits, the AC coefficients in zigzag order as (run, category) + bits with ZRL (F0) for 16 zeros and EOB (00) behind the last
+ *   non-zero one; a negative value v is coded as the low bits of v - 1; FF in the data is followed by 00; the last byte is
+ *   filled with 1-bits.
+ *
+ * Host stage (csrc/jpeg_emit.cpp: no HIP, no global state beyond constant tables, re-entrant, no thread pool: the callers' threads
+ * run images in parallel):
+ *   ssd_jpeg_quant_tables  the two tables of `quality`.
+ *   ssd_jpeg_emit_bound    a size no file of this geometry exceeds (1024 + 416 per block of the padded grids), or the refusal (< 0).
+ *   ssd_jpeg_emit          writes the whole file of ONE image from its coefficients (coef: the image's first coefficient, the
+ *                          layout above) into out[0, capacity) and its size into *size_out.  A capacity below the file's size is
+ *                          SSD_ERR_INVALID; nothing is ever written at or past out + capacity.  After a refusal out holds
+ *                          unspecified bytes inside its capacity.  NULL coef / out (with capacity > 0) / size_out: SSD_ERR_INVALID.
+ *   ssd_jpeg_encode_plan   the batch layout, as ssd_jpeg_plan: images_out[b] for frames[b] = {height, width, sampling, quality},
+ *                          in order (a batch may mix samplings and qualities) -- frames on 16-byte boundaries one after the
+ *                          other (ssd_jpeg_plan's layout of them), each image's
+ *                          sample planes on the next 16-byte boundary of the workspace, coefficients back to back (128 bytes per
+ *                          block: 16-byte boundaries), block_begin / tile_begin the running sums -- and totals_out = {coefficients
+ *                          (int16), workspace bytes, frame bytes, blocks}.
+ * Device stage: ssd_jpeg_encode enqueues two launches on `stream` whatever B and the sizes are; no allocation, no synchronisation,
+ * no atomics, no handle; two calls give the same bytes.
+ *   images_host / images_dev  the same B rows in host memory (checked by the call before any HIP call) and in device memory (8-byte
+ *                       aligned; the kernels read it); a row carries its own sampling (h, v) and quality
+ *   frames_dev          frame b = uint8 [height, width, 3] at frame_offset (any byte offset >= 0)
+ *   workspace_dev       16-byte aligned, ssd_jpeg_encode_workspace_bytes(images_host, B) bytes: component k's padded sample plane,
+ *                       pitch 8 * blocks per row, at plane_offset (a multiple of 16) + 64 * the blocks of the components before
+ *   coef_dev            16-byte aligned; an image's coefficients at coef_offset (a multiple of 8), 64 * blocks of them
+ *   launch 1            convert + replicate + downsample: a 256-lane group takes a tile of SSD_JPEG_ENC_TILE units of ONE image, so
+ *                       the sampling is uniform in the group; a unit is 8 chroma samples of one row of the padded chroma plane
+ *                       with the 8 h by v luma samples they cover (one lane: 8-byte chroma stores, 8 h-byte luma stores).  Every
+ *                       sample of the padded planes is written (those of dummy blocks hold replicated values nobody reads).
+ *   launch 2            level shift + both DCT passes + quantise: 8 lanes per block, 32 blocks per 256-lane group, the block's tile
+ *                       in LDS; lane r scales row r of the base table by the image's quality and stores row r of the block as
+ *                       ONE 16-byte store.  Every coefficient of every padded grid is
+ *                       written exactly once, dummy blocks as zeros; no byte between two images' coefficients is written.
+ *   Both launches: at most SSD_COCO_GRID_CAP groups striding over the batch's tiles / blocks.
+ *   Refused before any HIP call: SSD_ERR_UNSUPPORTED for a row whose (h, v) is neither 1x1 nor 2x2; SSD_ERR_INVALID, the reason
+ *   "ssd_jpeg_encode: ..." naming the argument, for B outside [0, 2^20], a row's quality outside 1 .. 100, NULL or misaligned pointers
+ *   with B > 0, a row whose height, width or MCU counts are not the geometry above, offsets that are negative or misaligned,
+ *   planes or coefficients that do not ascend disjointly, block_begin / tile_begin that are not the running sums.  B == 0
+ *   enqueues nothing. */
+#define SSD_JPEG_SAMPLING_444 444
+#define SSD_JPEG_SAMPLING_420 420
+#define SSD_JPEG_ENC_TILE 256                /* units a 256-lane group of launch 1 takes: one per lane                  */
+typedef struct ssd_jpeg_encode_image {       /* 72 bytes, no padding: one image of a batch                     */
+    int32_t height, width, h, v, mcus_x, mcus_y, quality, reserved;
+    int64_t frame_offset;                    /* bytes from frames_dev                                          */
+    int64_t plane_offset;                    /* bytes from workspace_dev                                       */
+    int64_t coef_offset;                     /* int16 elements from coef_dev                                   */
+    int64_t block_begin;                     /* blocks of the images before this one                           */
+    int64_t tile_begin;                      /* tiles (ceil(8 * mcus_y * mcus_x / SSD_JPEG_ENC_TILE)) of the images before */
+} ssd_jpeg_encode_image;
+int ssd_jpeg_quant_tables(int32_t quality, uint16_t *tables_out /* [2][64] */);
+int64_t ssd_jpeg_emit_bound(int32_t height, int32_t width, int32_t sampling);
+int ssd_jpeg_emit(const int16_t *coef, int32_t height, int32_t width, int32_t sampling, int32_t quality, uint8_t *out,
+                  int64_t capacity, int64_t *size_out);
+int ssd_jpeg_encode_plan(const int32_t *frames /* [B][4] */, int32_t B, ssd_jpeg_encode_image *images_out, int64_t *totals_out /* [4] */);
+size_t ssd_jpeg_encode_workspace_bytes(const ssd_jpeg_encode_image *images_host, int32_t B);   /* 0 for a table ssd_jpeg_encode refuses */
+int ssd_jpeg_encode(const ssd_jpeg_encode_image *images_host, const ssd_jpeg_encode_image *images_dev, int32_t B,
+                    const uint8_t *frames_dev, void *workspace_dev, int16_t *coef_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

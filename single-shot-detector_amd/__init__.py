@@ -22,7 +22,7 @@ from .detector import Detector                                         # noqa: F
 from . import tiles                                                    # noqa: F401  (Detector.detect_tiled's grid, gather and merge)
 from .tiles import tile_grid                                           # noqa: F401
 from . import jpeg                                                     # noqa: F401  (JPEG bytes -> frames on the GPU)
-from .jpeg import JpegDecoder                                          # noqa: F401
+from .jpeg import JpegDecoder, JpegEncoder                             # noqa: F401
 from . import coco_eval, coco_metric, coco_match, coco_accumulate, coco_rows, voc_match, tfrecords            # noqa: F401  (evaluation: `python -m ssd_amd.evaluation`, imported on use)
 from .distributed import shard_range, all_gather_detections, detect_sharded, bind_to_gpu_numa_node  # noqa: F401
 from .distributed import (ChunkAssignment, detect_many_sharded, node_device_and_backend, init_node_process_group,  # noqa: F401

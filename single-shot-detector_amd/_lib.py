@@ -12,7 +12,8 @@ _CSRC = os.path.join(_HERE, "csrc")
 _SOURCES = ["abi.hip", "weights.hip", "plan.hip", "stages.hip", "igemm.hip", "igemm_lat.hip", "igemm16.hip", "logit_screen.hip", "dwpw_stream.hip", "sn_pw.hip", "front.hip",
             "elementwise.hip", "postprocess.hip", "loss.hip", "augment.hip", "update.hip", "train_head.hip", "wgrad.hip", "train_backbone.hip", "train_shufflenet.hip",
             "train_first_f32.hip", "train_norms.hip", "train_hist.hip", "loss_top.hip", "train_reduce.hip", "coco_match.hip", "coco_accumulate.hip", "coco_rows.hip", "voc_match.hip", "tiles.hip", "jpeg.hip",
-            "jpeg_host.cpp"]        # (the one plain C++ source: the JPEG decoder's host stage, compiled without an offload target)
+            "jpeg_enc.hip",
+            "jpeg_host.cpp", "jpeg_emit.cpp"]   # (the plain C++ sources: the JPEG decoder's and encoder's host stages, compiled without an offload target)
 _LIB_PATH = os.path.join(_CSRC, "libssd_hip.so")
 _DIAG_PATH = os.path.join(_CSRC, "libssd_hip_diag.so")       # -DSSD_DIAG build, scripts/ only
 _lib = None
@@ -36,7 +37,7 @@ def build(force=False, verbose=False, diag=False):
     include/ssd_hip_diag.h) for scripts/ -- never loaded by the product."""
     srcs = [os.path.join(_CSRC, s) for s in _SOURCES]
     deps = srcs + [os.path.join(_CSRC, "ssd_internal.h"), os.path.join(_CSRC, "host.h"), os.path.join(_CSRC, "igemm_mfma16.h"),
-                   os.path.join(_CSRC, "train_head.h"), os.path.join(_CSRC, "train_table.h"), os.path.join(_CSRC, "first_pixels.h"), os.path.join(_CSRC, "first_pixels_f32.h"), os.path.join(_CSRC, "iou_greater.h"), os.path.join(_CSRC, "jpeg_geom.h"), os.path.join(_CSRC, "metric_host.h"),
+                   os.path.join(_CSRC, "train_head.h"), os.path.join(_CSRC, "train_table.h"), os.path.join(_CSRC, "first_pixels.h"), os.path.join(_CSRC, "first_pixels_f32.h"), os.path.join(_CSRC, "iou_greater.h"), os.path.join(_CSRC, "jpeg_geom.h"), os.path.join(_CSRC, "jpeg_quant.h"), os.path.join(_CSRC, "jpeg_table.h"), os.path.join(_CSRC, "metric_host.h"),
                    os.path.join(_HERE, "..", "include", "ssd_hip.h"),
                    os.path.join(_HERE, "..", "include", "ssd_hip_diag.h"), os.path.join(_CSRC, "exports.map")]
     target = _DIAG_PATH if diag else _LIB_PATH
@@ -172,8 +173,15 @@ class SsdJpegImage(ctypes.Structure):
                [(n, ctypes.c_int64) for n in ("coef_offset", "quant_offset", "plane_offset", "frame_offset", "block_begin", "tile_begin")]
 
 
-SSD_ERR_INVALID, SSD_ERR_UNSUPPORTED = -1, -5       # the two refusals of the JPEG decoder's host stage
+class SsdJpegEncodeImage(ctypes.Structure):
+    """ssd_jpeg_encode_image of include/ssd_hip.h (72 bytes)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("height", "width", "h", "v", "mcus_x", "mcus_y", "quality", "reserved")] + \
+               [(n, ctypes.c_int64) for n in ("frame_offset", "plane_offset", "coef_offset", "block_begin", "tile_begin")]
+
+
+SSD_ERR_INVALID, SSD_ERR_UNSUPPORTED = -1, -5       # the two refusals of the JPEG decoder's and encoder's host stages
 SSD_JPEG_RUN, SSD_JPEG_TILE = 16, 4096
+SSD_JPEG_SAMPLING_444, SSD_JPEG_SAMPLING_420, SSD_JPEG_ENC_TILE = 444, 420, 256
 
 # every symbol include/ssd_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -301,6 +309,12 @@ SIGNATURES = {
     "ssd_jpeg_plan": (ctypes.c_int, [ctypes.POINTER(SsdJpegInfo), _i, ctypes.POINTER(SsdJpegImage), ctypes.POINTER(ctypes.c_int64)]),
     "ssd_jpeg_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SsdJpegImage), _i]),
     "ssd_jpeg_decode": (ctypes.c_int, [ctypes.POINTER(SsdJpegImage), _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ssd_jpeg_quant_tables": (ctypes.c_int, [_i, _vp]),
+    "ssd_jpeg_emit_bound": (ctypes.c_int64, [_i, _i, _i]),
+    "ssd_jpeg_emit": (ctypes.c_int, [_vp, _i, _i, _i, _i, _vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "ssd_jpeg_encode_plan": (ctypes.c_int, [_vp, _i, ctypes.POINTER(SsdJpegEncodeImage), ctypes.POINTER(ctypes.c_int64)]),
+    "ssd_jpeg_encode_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SsdJpegEncodeImage), _i]),
+    "ssd_jpeg_encode": (ctypes.c_int, [ctypes.POINTER(SsdJpegEncodeImage), _vp, _i, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -18,6 +18,7 @@
 // No atomics, every output byte written once: two calls give the same bytes.
 #include "metric_host.h"
 #include "jpeg_geom.h"
+#include "jpeg_table.h"
 
 namespace {
 
@@ -44,19 +45,6 @@ __device__ __forceinline__ void idct_1d(const int *x, uint32_t *o)
     a += z1 + z3, b += z2 + z4, c += z2 + z3, d += z1 + z4;
     o[0] = t10 + d, o[1] = t11 + c, o[2] = t12 + b, o[3] = t13 + a;
     o[4] = t13 - a, o[5] = t12 - b, o[6] = t11 - c, o[7] = t10 - d;
-}
-
-// the last row i of a table with begin(i) <= g, begin ascending from 0, g below the batch's total
-template <class Begin>
-__device__ __forceinline__ int find_row(int B, int64_t g, Begin begin)
-{
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (begin(mid) <= g) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
 }
 
 typedef int int4_t __attribute__((ext_vector_type(4)));

@@ -190,6 +190,13 @@ class Detector:
             self._jpeg = JpegDecoder(self.device)
         return self._jpeg
 
+    def jpeg_encoder(self):
+        """This detector's jpeg.JpegEncoder (created on first use)."""
+        if getattr(self, "_jpeg_enc", None) is None:
+            from .jpeg import JpegEncoder
+            self._jpeg_enc = JpegEncoder(self.device)
+        return self._jpeg_enc
+
     def _jpeg_groups(self, blobs):
         """Consecutive index ranges of `blobs`, each within JPEG_GROUP files and JPEG_GROUP_BYTES of frames."""
         dec, groups, start, size = self.jpeg_decoder(), [], 0, 0

@@ -53,6 +53,25 @@ def write_records(path, records):
             f.write(head + struct.pack("<I", masked_crc32c(head)) + r + struct.pack("<I", masked_crc32c(r)))
 
 
+def serialize_example(image, xmin, xmax, ymin, ymax, labels):
+    """The tf.train.Example of one image as create_tfrecords.py:116-123 fills it: 'image' one bytes value, the four box columns
+    float lists, 'labels' an int64 list -- the map entries in THAT order (a map's order on the wire is the writer's choice and no
+    reader may depend on it), repeated scalars packed, an empty list as an empty FloatList / Int64List."""
+    from .ckpt_export import _field_bytes, _varint
+
+    def floats(values):
+        payload = np.asarray(values, "<f4").tobytes()
+        return _field_bytes(2, _field_bytes(1, payload) if payload else b"")
+
+    def ints(values):
+        payload = b"".join(bytes(_varint(int(v) & 0xFFFFFFFFFFFFFFFF)) for v in values)
+        return _field_bytes(3, _field_bytes(1, payload) if payload else b"")
+    entries = [("image", _field_bytes(1, _field_bytes(1, bytes(image)))), ("xmin", floats(xmin)), ("xmax", floats(xmax)),
+               ("ymin", floats(ymin)), ("ymax", floats(ymax)), ("labels", ints(labels))]
+    features = b"".join(bytes(_field_bytes(1, _field_bytes(1, key.encode()) + _field_bytes(2, bytes(feature)))) for key, feature in entries)
+    return bytes(_field_bytes(1, features))
+
+
 def _repeated(buf, kind):
     """The `value` field (1) of a BytesList / FloatList / Int64List, packed or unpacked."""
     out = []
