@@ -1432,8 +1432,7 @@ int ssd_tile_merge(const int32_t *tile_records_dev /* [F*ny*nx,6T+1] */, const i
  *   APPn / COM segments are handled.
  * SSD_ERR_UNSUPPORTED (the caller decodes the file as before): every other SOFn, DAC, another precision, 16-bit tables, 2 or 4 and
  * more components, other sampling factors (4:4:0, 4:1:1, ..), a scan of fewer components or a second scan, DNL or height 0, RGB or
- * another Adobe transform, and -- from ssd_jpeg_entropy -- a coefficient outside int16 or with |coefficient * q| > 32767 (there
- * the library's own SIMD and C paths stop agreeing, so nothing can be pinned).
+ * another Adobe transform, and -- from ssd_jpeg_entropy -- a coefficient outside int16 or a stream that is not PINNED (below).
  * SSD_ERR_INVALID: anything malformed or truncated -- no SOI, a segment that runs past the end, an undefined or over-subscribed
  * table, a code that no table holds, a run past coefficient 63, a DC category above 11, entropy data that ends before its last
  * block, a wrong or missing restart marker, no EOI.  The stricter reading is deliberate: such a file goes to the caller's reader.
@@ -1460,6 +1459,23 @@ int ssd_tile_merge(const int32_t *tile_records_dev /* [F*ny*nx,6T+1] */, const i
  *   (0.298631336 = 2446, 0.390180644 = 3196, 0.541196100 = 4433, 0.765366865 = 6270, 0.899976223 = 7373, 1.175875602 = 9633,
  *    1.501321110 = 12299, 1.847759065 = 15137, 1.961570560 = 16069, 2.053119869 = 16819, 2.562915447 = 20995, 3.072711026 = 25172.)
  *   All arithmetic is 32-bit two's complement (the code forms the sums in uint32), all right shifts are arithmetic.
+ *   This wrap-and-clamp definition is what the kernels compute on ANY coefficients and tables (tests/test_gpu_jpeg.py holds them to
+ *   it over all of int16 x uint16); it is the library's result only for pinned streams.
+ *
+ * Pinned streams.  With x, w (pass 1's descaled outputs) and v (pass 2's descaled outputs, before + 128) taken as EXACT integers,
+ * nothing wrapped, a stream is pinned if and only if in every block of every component
+ *     every |x| <= 16383,   every |w| <= 16383,   every v in [-512, 511].
+ *   Why these: with inputs of at most 16383 no sum of the one-dimensional kernel leaves int32 in either pass (the largest, t10 + d,
+ *   stays below 61214 * 16383 ~ 1.0e9), so the 32-bit wrap above, the library's C path and its SIMD paths form the same numbers;
+ *   the SIMD paths' 16-bit pair sums (x0 +- x4, x1 + x5, ..) fit int16 and a saturating 16-bit workspace never saturates; and for
+ *   v in [-512, 511] every path's clamp -- a range table indexed by (v + 128) & 1023, or a saturating pack -- is the plain clamp
+ *   to 0 .. 255.  Outside, the library's own paths stop agreeing with each other (a table that wraps at 1024 against a pack that
+ *   saturates, 16-bit sums that wrap or saturate), so "what PIL returns" depends on the build and the CPU, and nothing can be
+ *   pinned: with the earlier rule |coefficient * q| <= 32767, files under loud constant tables gave frames up to 255 counts from
+ *   PIL's from |coefficient * q| = 2920 on.  The v limb binds first: |w| > 16383 or |x| > 16383 in a block imply
+ *   some |v| of about 512 and 2048 there.  Files encoded from pixels stay a factor 2 to 4 inside every limb.
+ *   ssd_jpeg_entropy tests the rule block by block: S = sum |x| <= 2047 implies all three limbs (the derivation stands in
+ *   csrc/jpeg_host.cpp), and a louder block goes through both passes in 64-bit integers on the host.
  *
  * Upsampling of a chroma plane s with REAL extents n = ceil(width / 2) columns and, for 2x2, m = ceil(height / 2) rows (samples
  * outside the real extent are never read: block padding is no neighbour, edges replicate the last real sample):
@@ -1476,7 +1492,8 @@ int ssd_tile_merge(const int32_t *tile_records_dev /* [F*ny*nx,6T+1] */, const i
  * Host stage (no HIP, no global state, re-entrant; never reads outside [bytes, bytes + n), never writes outside what `info` reports):
  *   ssd_jpeg_info_read  parses the whole marker structure (headers, the scan's extent up to EOI) and fills *out.
  *   ssd_jpeg_entropy    decodes the scan into coef_host [info->coef_count] and quant_host [info->components * 64]; `info` must be
- *                       what ssd_jpeg_info_read gave for these bytes (SSD_ERR_INVALID otherwise).  After a refusal the two
+ *                       what ssd_jpeg_info_read gave for these bytes (SSD_ERR_INVALID otherwise); SSD_ERR_UNSUPPORTED for a
+ *                       stream that is not pinned, from the first block outside the rule.  After a refusal the two
  *                       arrays hold unspecified values inside their bounds.
  *   ssd_jpeg_plan       the batch layout: images_out[b] for infos[b], b < B, in order -- coefficients back to back (64 * blocks
  *                       each), tables back to back, each image's sample planes on the next 16-byte boundary of the workspace,

@@ -3,6 +3,7 @@ scripts/eval_from_disk.py (JPEGs of the 13 COCO-typical sizes, 480 x 640 class, 
 
     python scripts/jpeg_cost.py [--images 1040] [--rounds 3] [--parent DIR] [--log profiles/jpeg_decode_cost.log]
     python scripts/jpeg_cost.py --tree DIR --folder DIR [--only rows_device] [--gc] [--label NAME] [--rounds 5]
+    python scripts/jpeg_cost.py --entropy-against DIR [--images 208] [--rounds 5] [--log profiles/jpeg_loud_cost.log]
 
   per image    PIL decode on one core; ssd_jpeg_info_read + ssd_jpeg_entropy on one core (into pinned memory); the upload of a
                32-image batch's coefficients, tables and table rows (HIP events); ssd_jpeg_decode's two launches on that batch
@@ -15,6 +16,9 @@ scripts/eval_from_disk.py (JPEGs of the 13 COCO-typical sizes, 480 x 640 class, 
                behind this tree's rounds.
   --tree DIR   the end-to-end routes of the checkout at DIR alone, in this one process, on --folder: a change and its parent commit
                timed alternately, process after process (profiles/records_route_refactor_ab.log).
+  --entropy-against DIR   the host stage alone (ssd_jpeg_info_read + ssd_jpeg_entropy, one core) of this tree's library and of the
+               library built in the checkout at DIR, both loaded into this ONE process and timed file by file in alternating order;
+               per library the median per image of every round.  Needs no GPU.
 There is no speed gate: no ratio was promised in advance, the log says what was measured, whichever way it comes out."""
 import argparse
 import ctypes
@@ -36,6 +40,7 @@ ap.add_argument("--folder", default=None, help="(the child's mode) the folder; w
 ap.add_argument("--only", default=None, help="(the child's mode) all four routes whose name contains this, not the two default ones")
 ap.add_argument("--gc", action="store_true", help="(the child's mode) an untimed gc.collect() in front of every timed route")
 ap.add_argument("--label", default="parent", help="(the child's mode) what the printed lines begin with")
+ap.add_argument("--entropy-against", default=None, help="time the host stage of this tree and of the checkout at this path alternately")
 args = ap.parse_args()
 ROOT = os.path.abspath(args.tree) if args.tree else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -112,12 +117,57 @@ def child():
     harness(det, gt, args.folder, routes, args.rounds, lambda s: print(s, flush=True), args.label + (" gc" if args.gc else ""))
 
 
+def entropy_ab(say):
+    """The host stage of two builds on the same files, alternating file by file in one process."""
+    from ssd_amd._lib import SsdJpegInfo, lib_path
+    other = os.path.join(os.path.abspath(args.entropy_against), os.path.relpath(lib_path(), ROOT))
+    libs = []
+    for label, path in (("this tree", lib_path()), ("other tree", other)):
+        L = ctypes.CDLL(path)
+        L.ssd_jpeg_info_read.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_void_p]
+        L.ssd_jpeg_entropy.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        libs.append((label, L))
+    d = tempfile.mkdtemp(prefix="val_like_")
+    gt = write_folder(d, args.images)
+    blobs = [open(os.path.join(d, m["file_name"]), "rb").read() for m in gt["images"]]
+    say("%d JPEGs, %.0f KB each; ssd_jpeg_info_read + ssd_jpeg_entropy, one core, ms per image (median over the files of a round)"
+        % (len(blobs), sum(map(len, blobs)) / 1024 / len(blobs)))
+    out = np.empty(32 << 20, np.int16)
+    rounds = {label: [] for label, _L in libs}
+    for r in range(args.rounds + 1):                            # (round 0 warms both up and is not reported)
+        times = {label: [] for label, _L in libs}
+        for i, b in enumerate(blobs):
+            for label, L in (libs if (r + i) % 2 == 0 else libs[::-1]):
+                info = SsdJpegInfo()
+                t0 = time.perf_counter()
+                rc = L.ssd_jpeg_info_read(b, len(b), ctypes.byref(info))
+                if rc == 0:
+                    rc = L.ssd_jpeg_entropy(b, len(b), ctypes.byref(info), out.ctypes.data, out.ctypes.data + 2 * info.coef_count)
+                times[label].append(time.perf_counter() - t0)
+                assert rc == 0, "%s refused file %d" % (label, i)
+        if r:
+            for label in times:
+                rounds[label].append(med(times[label]) * 1e3)
+    for label, _L in libs:
+        say("  %-10s %.4f ms   (rounds: %s; spread %.4f)" % (label, med(rounds[label]), " ".join("%.4f" % t for t in rounds[label]),
+                                                            max(rounds[label]) - min(rounds[label])))
+    a, b = med(rounds["this tree"]), med(rounds["other tree"])
+    say("  this tree / other tree = %.4f" % (a / b))
+
+
 def main():
     lines = []
 
     def say(text):
         print(text, flush=True)
         lines.append(text)
+    if args.entropy_against:
+        entropy_ab(say)
+        log = args.log or os.path.join(ROOT, "profiles", "jpeg_loud_cost.log")
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     from ssd_amd._lib import SsdJpegImage, SsdJpegInfo, lib
     d = tempfile.mkdtemp(prefix="val_like_")
     t0 = time.perf_counter()

@@ -292,6 +292,71 @@ inline bool receive_extend(Bits &br, int s, int &out)
     return true;
 }
 
+// ----------------------------------------------------------------------------- the pinned rule
+// include/ssd_hip.h, "Pinned streams": in every block |x| <= 16383, |w| <= 16383 and -512 <= v <= 511, x the dequantised values,
+// w pass 1's descaled outputs, v pass 2's before + 128, all in exact integers.
+constexpr int X_LIMIT = 16383, W_LIMIT = 16383, V_MIN = -512, V_MAX = 511;
+
+// The screen: a block with S = sum |x| <= SCREEN_SUM holds all three limbs, so only louder blocks pay for the exact passes.
+//   The one-dimensional kernel is linear and exact (its roundings are the two descales); written out, output k = sum_j c[k][j] x[j]
+//   with max |c[k][j]| = 11363 (x1 into output 0: 12299 - 7373 - 3196 + 9633), so |output| <= 11363 * sum_j |x[j]|.
+//   pass 1, column c with S_c = its sum |x|:  |w| <= (11363 S_c + 1024) / 2048 < 5.5484 S_c + 1
+//   pass 2, a row holds one w of every column:  sum |w| < 5.5484 S + 8,  |v| <= (11363 (5.5484 S + 8) + 2^17) / 2^18 + 1
+//                                                                            < 0.24050 S + 1.85
+//   S <= 2047:  |x| <= 2047,  |w| < 11359,  |v| < 494.2 -- inside 16383, 16383 and [-512, 511].
+constexpr int SCREEN_SUM = 2047;
+
+// the header's one-dimensional kernel in 64-bit integers (nothing wraps for |x| <= X_LIMIT, nor for |w| <= W_LIMIT); the inputs
+// and the outputs stride by `step`
+inline void idct_1d_exact(const int64_t *x, int step, int64_t *out)
+{
+    const int64_t x0 = x[0], x1 = x[step], x2 = x[2 * step], x3 = x[3 * step], x4 = x[4 * step], x5 = x[5 * step], x6 = x[6 * step],
+                  x7 = x[7 * step];
+    int64_t z1 = (x2 + x6) * 4433;
+    const int64_t t2 = z1 - x6 * 15137, t3 = z1 + x2 * 6270;
+    const int64_t t0 = (x0 + x4) * 8192, t1 = (x0 - x4) * 8192;
+    const int64_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    int64_t a = x7, b = x5, c = x3, d = x1;
+    z1 = a + d;
+    int64_t z2 = b + c, z3 = a + c, z4 = b + d;
+    const int64_t z5 = (z3 + z4) * 9633;
+    a *= 2446, b *= 16819, c *= 25172, d *= 12299;
+    z1 *= -7373, z2 *= -20995, z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+    a += z1 + z3, b += z2 + z4, c += z2 + z3, d += z1 + z4;
+    out[0] = t10 + d, out[step] = t11 + c, out[2 * step] = t12 + b, out[3 * step] = t13 + a;
+    out[4 * step] = t13 - a, out[5 * step] = t12 - b, out[6 * step] = t11 - c, out[7 * step] = t10 - d;
+}
+
+// floor(t / 2^s) of a signed value without shifting a negative one
+inline int64_t descale(int64_t t, int s)
+{
+    const int64_t r = t + ((int64_t)1 << (s - 1)), d = (int64_t)1 << s;
+    return r >= 0 ? r / d : -((-r + d - 1) / d);
+}
+
+// the limbs on w and v of one block by both passes in exact integers; every |coefficient * q| <= X_LIMIT already
+bool block_pinned(const int16_t *coef, const uint16_t *q)
+{
+    int64_t x[64], w[64], v[8];
+    for (int i = 0; i < 64; ++i) x[i] = (int64_t)coef[i] * (int64_t)q[i];
+    for (int c = 0; c < 8; ++c) {
+        idct_1d_exact(x + c, 8, w + c);
+        for (int r = 0; r < 8; ++r) {
+            const int64_t d = descale(w[8 * r + c], 11);
+            if (d > W_LIMIT || d < -W_LIMIT) return false;
+            w[8 * r + c] = d;
+        }
+    }
+    for (int r = 0; r < 8; ++r) {
+        idct_1d_exact(w + 8 * r, 1, v);
+        for (int c = 0; c < 8; ++c) {
+            const int64_t d = descale(v[c], 18);
+            if (d > V_MAX || d < V_MIN) return false;
+        }
+    }
+    return true;
+}
+
 // one block into `dst` (64 zeros on entry): SSD_OK or the refusal
 inline int decode_block(Bits &br, const Huff &dc, const Huff &ac, const uint16_t *q, int &pred, int16_t *dst)
 {
@@ -303,9 +368,11 @@ inline int decode_block(Bits &br, const Huff &dc, const Huff &ac, const uint16_t
         pred += diff;                                                // |pred| stays below 2^11 * blocks < 2^31
     }
     if (pred < -32768 || pred > 32767) return SSD_ERR_UNSUPPORTED;
+    int sum;                                                         // S = sum |x| of the block: at most 64 * X_LIMIT
     {
         const int prod = pred * (int)q[0];
-        if (prod > 32767 || prod < -32767) return SSD_ERR_UNSUPPORTED;
+        if (prod > X_LIMIT || prod < -X_LIMIT) return SSD_ERR_UNSUPPORTED;
+        sum = prod < 0 ? -prod : prod;
     }
     dst[0] = (int16_t)pred;
     for (int k = 1; k < 64;) {
@@ -323,10 +390,12 @@ inline int decode_block(Bits &br, const Huff &dc, const Huff &ac, const uint16_t
         if (!receive_extend(br, sz, val)) return SSD_ERR_INVALID;
         const int nat = ZIGZAG[k];
         const int prod = val * (int)q[nat];
-        if (prod > 32767 || prod < -32767) return SSD_ERR_UNSUPPORTED;
+        if (prod > X_LIMIT || prod < -X_LIMIT) return SSD_ERR_UNSUPPORTED;
+        sum += prod < 0 ? -prod : prod;
         dst[nat] = (int16_t)val;                                     // |val| < 2^15
         ++k;
     }
+    if (sum > SCREEN_SUM && !block_pinned(dst, q)) return SSD_ERR_UNSUPPORTED;
     return SSD_OK;
 }
 

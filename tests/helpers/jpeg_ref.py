@@ -4,7 +4,9 @@ dequantisation, the inverse DCT, the chroma upsampling and the colour conversion
 
     parse(blob)  -> dict(height, width, components, h, v, mcus_x, mcus_y, restart, coef [int16 per component: blocks x 64],
                          quant [uint16 components x 64])
-    pixels(p)    -> uint8 [height, width, 3]"""
+    pixels(p)    -> uint8 [height, width, 3]
+    ranges(p)    -> (max |x|, max |pass-1 output|, min v, max v) of both passes in exact integers, nothing wrapped
+    pinned(p)    -> the header's rule for "PIL's frame is pinned": what ssd_jpeg_entropy accepts"""
 import numpy as np
 
 ZIGZAG = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35,
@@ -143,8 +145,13 @@ def _i32(x):
     return ((np.asarray(x, np.int64) + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)
 
 
-def _idct_1d(x):
-    """The one-dimensional kernel over the LAST axis (8 values) -> the eight outputs before descaling."""
+def _exact(x):
+    return np.asarray(x, np.int64)
+
+
+def _idct_1d(x, _i32=_i32):
+    """The one-dimensional kernel over the LAST axis (8 values) -> the eight outputs before descaling; `_i32` is the wrap of
+    every sum (ranges() passes none: int64 holds every exact value of 8-bit tables on int16 coefficients)."""
     x0, x1, x2, x3, x4, x5, x6, x7 = [x[..., i] for i in range(8)]
     z1 = _i32((x2 + x6) * 4433)
     t2, t3 = _i32(z1 - x6 * 15137), _i32(z1 + x2 * 6270)
@@ -168,6 +175,38 @@ def idct_blocks(coef, q):
     ws = cols.transpose(0, 2, 1)                                            # [n, row, column]
     rows = _i32(_idct_1d(ws) + (1 << 17)) >> 18
     return np.clip(rows + 128, 0, 255).astype(np.uint8)
+
+
+X_LIMIT, W_LIMIT, V_MIN, V_MAX = 16383, 16383, -512, 511           # the header's three limbs
+
+
+def block_ranges(coef, q):
+    """Per block of coef int [n, 64] under the table q [64]: (max |x|, max |w|, min v, max v), int64 [n] each -- x the dequantised
+    values, w pass 1's descaled outputs, v pass 2's descaled outputs before + 128: the header's two passes in exact integers,
+    nothing wrapped."""
+    x = (np.asarray(coef, np.int64).reshape(-1, 64) * np.asarray(q, np.int64).reshape(64)).reshape(-1, 8, 8)
+    assert int(np.abs(x).max(initial=0)) < 1 << 24, "exact in int64 for 8-bit tables on int16 coefficients"
+    ws = ((_idct_1d(x.transpose(0, 2, 1), _exact) + (1 << 10)) >> 11).transpose(0, 2, 1)
+    v = ((_idct_1d(ws, _exact) + (1 << 17)) >> 18).reshape(-1, 64)
+    return np.abs(x).reshape(-1, 64).max(1), np.abs(ws).reshape(-1, 64).max(1), v.min(1), v.max(1)
+
+
+def blocks_pinned(coef, q):
+    """bool [n]: the header's three limbs, block by block."""
+    ax, aw, lo, hi = block_ranges(coef, q)
+    return (ax <= X_LIMIT) & (aw <= W_LIMIT) & (lo >= V_MIN) & (hi <= V_MAX)
+
+
+def ranges(p):
+    """(max |x|, max |w|, min v, max v) over every block of every component of a parsed file."""
+    parts = [block_ranges(coef, q) for coef, q in zip(p["coef"], p["quant"])]
+    return (max(int(a.max()) for a, _w, _l, _h in parts), max(int(w.max()) for _a, w, _l, _h in parts),
+            min(int(lo.min()) for _a, _w, lo, _h in parts), max(int(hi.max()) for _a, _w, _l, hi in parts))
+
+
+def pinned(p):
+    """The header's rule "pinned streams": what ssd_jpeg_entropy accepts of the streams its parser takes."""
+    return all(bool(blocks_pinned(coef, q).all()) for coef, q in zip(p["coef"], p["quant"]))
 
 
 def plane(coef, q, blocks_y, blocks_x):

@@ -1,11 +1,13 @@
 // Stand-alone check of the JPEG decoder's host stage, linked with csrc/jpeg_host.cpp alone and built by tests/test_jpeg_host.py
 // with -fsanitize=address,undefined: the parser eats untrusted bytes, so this is where its memory safety is checked.
 //
-//   jpeg_host_check FILE...
+//   jpeg_host_check FILE... [--refused FILE...]
 // For every file: the file itself, every proper prefix, and every single-byte change (three values) at each of the first 700
 // bytes go through ssd_jpeg_info_read and, when that accepts, ssd_jpeg_entropy.  Every input is an exact-size heap copy and the
 // two output buffers are sized exactly as `info` says, so a read or a write one byte outside is the sanitizer's to report.
 // Prints "FILE: runs N accepted M" per file; the exit status is 0 unless a prefix was accepted or the untouched file was not.
+// A file behind --refused is one the parser takes and ssd_jpeg_entropy refuses as not pinned (the exact passes of a loud block run
+// on it): untouched it must give SSD_ERR_UNSUPPORTED, and its line ends "accepted M refused".
 #include "../include/ssd_hip.h"
 
 #include <cstdio>
@@ -33,7 +35,12 @@ static int run(const uint8_t *data, size_t n)
 int main(int argc, char **argv)
 {
     int bad = 0;
+    bool refused = false;       // behind --refused: the untouched file is one ssd_jpeg_entropy refuses
     for (int a = 1; a < argc; ++a) {
+        if (strcmp(argv[a], "--refused") == 0) {
+            refused = true;
+            continue;
+        }
         FILE *f = fopen(argv[a], "rb");
         if (!f) {
             fprintf(stderr, "%s: cannot open\n", argv[a]);
@@ -44,11 +51,12 @@ int main(int argc, char **argv)
         for (size_t got; (got = fread(buf, 1, sizeof(buf), f)) > 0;) d.insert(d.end(), buf, buf + got);
         fclose(f);
         long runs = 0, accepted = 0;
-        if (run(d.data(), d.size()) != SSD_OK) {
-            fprintf(stderr, "%s: the untouched file was refused\n", argv[a]);
+        const int whole = run(d.data(), d.size());
+        if (whole != (refused ? SSD_ERR_UNSUPPORTED : SSD_OK)) {
+            fprintf(stderr, "%s: the untouched file gave status %d\n", argv[a], whole);
             ++bad;
         }
-        ++runs, ++accepted;
+        ++runs, accepted += whole == SSD_OK;
         for (size_t n = 0; n < d.size(); ++n, ++runs) {
             const int rc = run(d.data(), n);
             if (rc != SSD_ERR_INVALID && rc != SSD_ERR_UNSUPPORTED) {
@@ -71,7 +79,7 @@ int main(int argc, char **argv)
             }
             m[p] = d[p];
         }
-        printf("%s: runs %ld accepted %ld\n", argv[a], runs, accepted);
+        printf("%s: runs %ld accepted %ld%s\n", argv[a], runs, accepted, refused ? " refused" : "");
     }
     return bad ? 1 : 0;
 }

@@ -1,7 +1,10 @@
 """-m gpu: the JPEG decoder (include/ssd_hip.h, block "the JPEG decoder"; csrc/jpeg.hip, jpeg.py) against the decoder the product
 used before, PIL.Image.open(...).convert("RGB"), bit for bit -- the shared case list as one batch and reversed, images past one
 grid pass of either launch, the call between guard words at 16-byte-not-32-byte addresses, a side stream, the edge batch sizes,
-refused files, and the routes built on it: Detector.detect_many_jpeg, detect_many_records_jpeg, coco_eval.evaluate(jpeg_device=)."""
+refused files, and the routes built on it: Detector.detect_many_jpeg, detect_many_records_jpeg, coco_eval.evaluate(jpeg_device=).
+Independently of PIL and of any file: ssd_jpeg_decode on synthetic tables and coefficients over its whole input domain (int16
+extremes, 16-bit table values: sums that wrap in both passes) against the header's restatement.  And the files of
+tests/helpers/jpeg_loud.py at and past the edge of the header's "pinned streams" rule, through the decoder and the detector routes."""
 import ctypes
 import io
 import json
@@ -11,7 +14,7 @@ import sys
 import numpy as np
 import pytest
 
-from tests.helpers import guarded, jpeg_cases
+from tests.helpers import guarded, jpeg_cases, jpeg_loud, jpeg_ref
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -165,6 +168,102 @@ def test_refused_files_are_reported_and_the_others_unaffected(dec):
     assert got == [] and refused == {0: UNSUPPORTED, 1: UNSUPPORTED}
 
 
+# ----------------------------------------------------------------------------- the kernels over their whole input domain
+DOMAIN_IMAGES = ((8, 8, 1, 1, 1), (8, 24, 3, 1, 1), (24, 17, 3, 2, 1), (16, 16, 3, 2, 2), (33, 65, 3, 2, 2))     # H, W, components, h, v
+
+
+def domain_batch(table_value, seed):
+    """Five parses in jpeg_ref's form whose coefficients no stream needs to give: per component the first blocks hold int16's
+    extremes (all 32767, all -32768, their checkerboards by position, row and column, one extreme among zeros), the rest seeded
+    values over all of int16, a third of them sparse; the tables hold `table_value` everywhere, or (None) a seeded choice among
+    1, 255 and 65535 per entry."""
+    rng, out = np.random.default_rng(seed), []
+    k = np.arange(64)
+    head = [np.full(64, 32767), np.full(64, -32768), np.where(k % 2, 32767, -32768), np.where((k // 8) % 2, -32768, 32767),
+            np.where((k // 8 + k % 8) % 2, 32767, -32768)]
+    for H, W, n, h, v in DOMAIN_IMAGES:
+        mx, my = -(-W // (8 * h)), -(-H // (8 * v))
+        coef = []
+        for c in range(n):
+            blocks = my * mx * (h * v if c == 0 else 1)
+            a = rng.integers(-32768, 32768, (blocks, 64))
+            a[rng.random((blocks, 64)) < 0.8 * (rng.random((blocks, 1)) < 1 / 3)] = 0
+            if blocks > 2:
+                for i, pattern in enumerate(head[c::n][:blocks - 2]):
+                    a[i] = pattern
+                a[-1] = 0
+                a[-1, int(rng.integers(64))] = (32767, -32768)[c % 2]
+            coef.append(a.astype(np.int16))
+        quant = (np.full((n, 64), table_value) if table_value else rng.choice([1, 255, 65535], (n, 64))).astype(np.uint16)
+        out.append({"height": H, "width": W, "components": n, "h": h, "v": v, "mcus_x": mx, "mcus_y": my, "restart": 0,
+                    "coef": coef, "quant": quant})
+    return out
+
+
+@pytest.mark.parametrize("table_value", [1, 255, 65535, None])
+def test_kernels_equal_the_header_over_the_whole_input_domain(cuda, ssd, table_value):
+    """ssd_jpeg_decode by hand, as host_batch does, on tables and coefficients that come from no file: the frames equal
+    jpeg_ref.pixels bit for bit where x = coefficient * q passes 2^31 and the sums of both passes wrap -- the uint32 arithmetic, the
+    arithmetic shifts and the clamp of csrc/jpeg.hip against the header's definition, with PIL nowhere in it."""
+    from importlib import import_module
+    L, lib = import_module("ssd_amd._lib"), ssd.lib()
+    batch = domain_batch(table_value, 11 if table_value is None else table_value)
+    infos = (L.SsdJpegInfo * len(batch))()
+    for info, p in zip(infos, batch):
+        info.height, info.width, info.components, info.h, info.v = p["height"], p["width"], p["components"], p["h"], p["v"]
+        info.mcus_x, info.mcus_y, info.restart_interval, info.reserved = p["mcus_x"], p["mcus_y"], 0, 0
+        for c, a in enumerate(p["coef"]):
+            info.blocks[c] = len(a)
+        info.coef_count = 64 * sum(len(a) for a in p["coef"])
+    table, totals = (L.SsdJpegImage * len(batch))(), (ctypes.c_int64 * 4)()
+    assert lib.ssd_jpeg_plan(infos, len(batch), table, totals) == 0
+    coef, quant = np.zeros(totals[0], np.int16), np.zeros(totals[1], np.uint16)
+    for t, p in zip(table, batch):
+        flat = np.concatenate([a.reshape(-1) for a in p["coef"]])
+        coef[t.coef_offset:t.coef_offset + flat.size] = flat
+        quant[t.quant_offset:t.quant_offset + p["quant"].size] = p["quant"].reshape(-1)
+    want = [jpeg_ref.pixels(p) for p in batch]
+    if table_value != 1:                                            # the batch does wrap: exact integers leave int32 in both passes
+        x = np.abs(batch[4]["coef"][0].astype(np.int64) * batch[4]["quant"][0].astype(np.int64))
+        assert x.max() >= 1 << 31 or x.reshape(-1, 8, 8).sum(1).max() * 8192 >= 1 << 31
+    assert all(0 < np.count_nonzero((w > 0) & (w < 255)) < w.size for w in want[1:]), "clamped and unclamped samples (one block may clamp throughout)"
+    arena = guarded.Arena(cuda, "cuda:0", "aligned")
+    arena.add("table", np.frombuffer(bytes(table), np.uint8).copy(), np.uint8, 16, "input")
+    arena.add("coef", coef.view(np.uint8), np.uint8, 16, "input")
+    arena.add("quant", quant.view(np.uint8), np.uint8, 16, "input")
+    arena.add("ws", (int(lib.ssd_jpeg_workspace_bytes(table, len(batch))),), np.uint8, 16, "workspace")
+    arena.add("frames", (totals[3],), np.uint8, 16, "output", fill=0x3C)
+    ssd._lib.check(lib.ssd_jpeg_decode(table, arena.ptr("table"), len(batch), arena.ptr("coef"), arena.ptr("quant"), arena.ptr("ws"),
+                                       arena.ptr("frames"), None))
+    cuda.cuda.synchronize()
+    arena.check()
+    out = arena.read("frames")
+    for k, (t, w) in enumerate(zip(table, want)):
+        got = out[t.frame_offset:t.frame_offset + w.size].reshape(w.shape)
+        assert np.array_equal(got, w), "image %d: %d of %d bytes differ from the header's restatement" % (k, (got != w).sum(), w.size)
+
+
+# ----------------------------------------------------------------------------- at and past the edge of the pinned rule
+def edge_files():
+    """[(name, blob, p)]: the loud, single-coefficient, colour-corner and upsampling files of tests/test_jpeg_loud_host.py."""
+    return jpeg_loud.loud() + jpeg_loud.single() + jpeg_loud.corners() + jpeg_loud.upsampling()
+
+
+def test_files_at_the_edge_of_the_rule_equal_pil_or_are_refused(dec):
+    """One batch: every file the rule pins equals PIL bit for bit -- the IDCT's clamp up to v = -512 .. 511, the colour clamp at its
+    corners, the upsampling's biases where they decide --, every other one is refused with SSD_ERR_UNSUPPORTED, in between them, and
+    leaves its neighbours' frames alone."""
+    files = edge_files()
+    pinned = [jpeg_ref.pinned(p) for _n, _b, p in files]
+    assert len(files) == 96 + 256 + 1 + 144 and sum(pinned) == 72 + 128 + 1 + 144
+    got, refused = frames_of(dec.decode_many([blob for _n, blob, _p in files]))
+    assert refused == {i: UNSUPPORTED for i, ok in enumerate(pinned) if not ok}
+    kept = [f for f, ok in zip(files, pinned) if ok]
+    assert len(got) == len(kept)
+    bad = [name for (name, blob, _p), g in zip(kept, got) if not np.array_equal(g, jpeg_cases.pil_rgb(blob))]
+    assert not bad, "%d frames differ from PIL, the first: %s" % (len(bad), bad[:5])
+
+
 # ----------------------------------------------------------------------------- end to end
 @pytest.fixture(scope="module")
 def detector(cuda, ssd):
@@ -306,3 +405,26 @@ def test_the_records_routes_refuse_alike(cuda, ssd, detector):
         with pytest.raises(ValueError) as e:
             ssd.coco_eval.evaluate(bad["detector"], gt, "", predictions_json=None, jpeg_device=bad["jpeg_device"])
         assert str(e.value) == "jpeg_device must be the GPU of a Detector: the frames are detected where they are decoded"
+
+
+def test_routes_with_refused_loud_files_equal_the_pil_array_routes(cuda, dec, detector):
+    """detect_many_jpeg and detect_many_records_jpeg on the twelve files with two of them (a 128 x 128 and a 100 x 151 one) under
+    constant tables past the rule: the parser takes them, ssd_jpeg_entropy refuses them, the caller's reader decodes them, and the
+    results equal the routes on PIL's arrays."""
+    blobs = twelve_files()
+    for k, value in ((3, 255), (4, 200)):
+        tables = 1 if k % 4 == 3 else 2                              # (twelve_files' sampling order: every fourth is grayscale)
+        blobs[k] = jpeg_loud.constant_tables(blobs[k], [value] * tables)
+    assert all(dec.read_info(blobs[k])[0] == 0 for k in (3, 4))
+    assert frames_of(dec.decode_many([blobs[3], blobs[4]])) == ([], {0: UNSUPPORTED, 1: UNSUPPORTED})
+    arrays = [jpeg_cases.pil_rgb(b) for b in blobs]
+    want = detector.detect_many(arrays, score_threshold=0.15, max_batch=4)
+    got = detector.detect_many_jpeg(blobs, score_threshold=0.15, max_batch=4)
+    assert sum(len(w[2]) for w in want) > 20
+    for w, g in zip(want, got):
+        for a, b in zip(w, g):
+            assert a.dtype == b.dtype and np.array_equal(a, b)
+    dev = "cuda:%d" % detector.device
+    rec_want = detector.detect_many_records(arrays, detector.engine.new_records(12, dev).zero_(), max_batch=4)
+    rec_got, shapes = detector.detect_many_records_jpeg(blobs, detector.engine.new_records(12, dev).zero_(), max_batch=4)
+    assert cuda.equal(rec_want, rec_got) and shapes == [a.shape[:2] for a in arrays]

@@ -61,6 +61,14 @@ def test_restatement_equals_pil_on_the_whole_case_list(parsed):
     assert not bad, "%d of %d differ from PIL, the first: %s" % (len(bad), len(parsed), bad[:5])
 
 
+def test_every_case_is_pinned_with_room(parsed):
+    """None of the 432 files comes near a limb of the header's "pinned streams" rule: a factor 2 below each of them."""
+    worst = np.array([jpeg_ref.ranges(p) for p in parsed])
+    assert all(jpeg_ref.pinned(p) for p in parsed)
+    assert worst[:, 0].max() * 2 <= jpeg_ref.X_LIMIT and worst[:, 1].max() * 2 <= jpeg_ref.W_LIMIT
+    assert worst[:, 2].min() * 2 >= jpeg_ref.V_MIN and worst[:, 3].max() * 2 <= jpeg_ref.V_MAX
+
+
 def test_entropy_stage_equals_the_restatement(host, parsed):
     info_read, entropy = host
     for (name, blob), p in zip(jpeg_cases.cases(), parsed):
@@ -248,7 +256,9 @@ def test_the_entry_point_refuses_before_any_hip_call(ssd, host):
 # ----------------------------------------------------------------------------- the parser under the sanitizers
 def test_parser_under_sanitizers_on_damaged_files(tmp_path):
     """tests/jpeg_host_check.cpp + csrc/jpeg_host.cpp alone, built with -fsanitize=address,undefined: every prefix and every
-    single-byte change at each of the first 700 bytes of three files, the output buffers sized exactly as `info` says."""
+    single-byte change at each of the first 700 bytes of three files, the output buffers sized exactly as `info` says; and of two
+    loud files (tests/helpers/jpeg_loud.py), whose blocks pass the block-sum screen and run the exact passes: one the rule pins,
+    one it refuses."""
     cxx = shutil.which("g++") or shutil.which("clang++")
     if cxx is None:
         pytest.skip("no host C++ compiler")
@@ -259,14 +269,21 @@ def test_parser_under_sanitizers_on_damaged_files(tmp_path):
     if built.returncode != 0 and re.search(r"asan|ubsan|sanitize", built.stderr):
         pytest.skip("the sanitizer runtime is absent: %s" % built.stderr.strip().splitlines()[-1])
     assert built.returncode == 0, built.stderr
+    from tests.helpers import jpeg_loud
+    loud = {name: (blob, p) for name, blob, p in jpeg_loud.loud()}
+    pinned, past = loud["loud-16x16-420-noise-v500"], loud["loud-16x16-420-noise-past-v"]
+    assert jpeg_ref.pinned(pinned[1]) and not jpeg_ref.pinned(past[1])
     files = []
-    for k, blob in enumerate((_base("420", 21, 19), _base("422", 8, 24, restart_marker_blocks=1, optimize=True), _base("gray", 16, 16, 30))):
+    for k, blob in enumerate((_base("420", 21, 19), _base("422", 8, 24, restart_marker_blocks=1, optimize=True), _base("gray", 16, 16, 30),
+                              pinned[0], past[0])):
         path = str(tmp_path / ("f%d.jpg" % k))
         with open(path, "wb") as f:
             f.write(blob)
         files.append(path)
-    run = subprocess.run([exe] + files, capture_output=True, text=True, timeout=300)
+    run = subprocess.run([exe] + files[:4] + ["--refused"] + files[4:], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     counts = [int(v) for v in re.findall(r"runs (\d+)", run.stdout)]
-    assert len(counts) == 3 and all(c > 700 for c in counts), run.stdout
-    assert all(int(v) > 0 for v in re.findall(r"accepted (\d+)", run.stdout)), "the untouched file must decode"
+    assert len(counts) == 5 and all(c > 700 for c in counts), run.stdout
+    accepted = [int(v) for v in re.findall(r"accepted (\d+)", run.stdout)]
+    assert len(accepted) == 5 and all(v > 0 for v in accepted[:4]), "the untouched file must decode"
+    assert run.stdout.count(" refused\n") == 1 and run.stdout.splitlines()[4].endswith(" refused")
